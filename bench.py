@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — room-phase steps/sec of the batch stepper on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 N > 1 without WORLD_SIZE in the environment: this process starts N fresh rank processes
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...`) BEFORE anything touches the GPU
@@ -36,6 +36,9 @@ Prints ONE JSON line on rank 0 (contract in the task brief):
                   GPUs = 2 097 152 per rank) and C5 (50/50 mix), with the timed summary all-gather, each with its own
                   roofline block, and C4 with the single-turn launches of every rank's share (hbm_streaming);
   cpu_baseline    the oracle's C restatement on the host cores of rank 0 (the ONLY place bench.py touches oracle/).
+
+--dump-outputs DIR: after the line, the rooms and summary the last timed step left in the timed batch go to DIR/*.npy
+(dump_outputs below); the same arguments give the same inputs on every run, so two builds can be compared file by file.
 """
 import argparse
 import json
@@ -86,6 +89,52 @@ OTHER_SHAPES = (
     ("1048576 Two-Truths x4 (C3)", "c3", WORKLOADS["c3"]),
     ("524288 Werewolf x8 + 524288 Two-Truths x4 (one GPU's share of C5)", "c5", WORKLOADS["c5"]),
 )
+
+
+DUMP_BYTES = 64_000_000       # --dump-outputs: at most this much .npy data in all (64 MB)
+DUMP_CHUNK = 1 << 20           # rooms per read when only a sample of the rooms is dumped
+
+
+def dump_outputs(out_dir, read_rooms, n_rooms, first_room, summary_words, budget=DUMP_BYTES, prefix=""):
+    """--dump-outputs: what a caller of the timed path receives after its last step, as float .npy files in `out_dir`.
+    read_rooms(first, count) -> ROOM_VIEW_DTYPE views (RoomBatch.read_rooms); summary_words: the uint64 ge_summary words.
+      <prefix>summary_words.npy   [words, 2] float64: every summary word as its (high, low) 32-bit halves (the checksum is 64-bit)
+      <prefix>room_index.npy      float64: global index of every dumped room
+      <prefix>rooms_<field>.npy   one per view field (padding left out): float64 for the int32 fields, float32 for the bytes
+    Every value is exact in its float type.  If all rooms would exceed `budget`, a fixed sample of them (seeded, sorted) is
+    dumped instead, read in chunks.  Returns the paths written."""
+    import numpy as np
+    from game_engine_amd.stepper import ROOM_VIEW_DTYPE
+    os.makedirs(out_dir, exist_ok=True)
+    fields = [f for f in ROOM_VIEW_DTYPE.names if f != "pad"]
+
+    def as_float(a):
+        return a.astype(np.float64 if a.dtype.itemsize > 1 else np.float32)
+
+    words = np.asarray(summary_words, dtype=np.uint64)
+    arrays = {"summary_words": np.stack([words >> np.uint64(32), words & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64)}
+    per_room = 8 + sum(as_float(np.zeros(1, ROOM_VIEW_DTYPE)[f]).nbytes for f in fields)
+    fit = max(0, (budget - arrays["summary_words"].nbytes - 4096 * (len(fields) + 2)) // per_room)
+    if n_rooms <= fit:
+        idx = np.arange(n_rooms, dtype=np.int64)
+        views = read_rooms(0, n_rooms)
+    else:
+        idx = np.sort(np.random.default_rng(SEED).choice(n_rooms, size=fit, replace=False))
+        views = np.empty(len(idx), dtype=ROOM_VIEW_DTYPE)
+        for lo in range(0, n_rooms, DUMP_CHUNK):
+            cnt = min(DUMP_CHUNK, n_rooms - lo)
+            sel = (idx >= lo) & (idx < lo + cnt)
+            if sel.any():
+                views[sel] = read_rooms(lo, cnt)[idx[sel] - lo]
+    arrays["room_index"] = (idx + first_room).astype(np.float64)
+    for f in fields:
+        arrays["rooms_" + f] = as_float(views[f])
+    paths = []
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, prefix + name + ".npy")
+        np.save(path, np.ascontiguousarray(a))
+        paths.append(path)
+    return paths
 
 
 def load_dsl(game=GAME):
@@ -256,6 +305,8 @@ def main():
     ap.add_argument("--no-unfused", action="store_true", help="skip the one-launch-per-turn points")
     ap.add_argument("--no-other-shapes", action="store_true", help="skip the other BASELINE shapes (N = 1) / workloads (N > 1)")
     ap.add_argument("--no-from-init", action="store_true", help="skip the S=64-from-initial-state variant")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the timed batch's rooms and summary as DIR/<name>.npy (float, <= 64 MB)")
     args = ap.parse_args()
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0 or args.fuse < 1:
         raise SystemExit("bench.py: --gpus/--steps/--fuse must be >= 1, --warmup >= 0")
@@ -613,6 +664,12 @@ def main():
             if world > 1 and other_workloads:
                 other_workloads["c4"]["cpu_baseline"] = cpu_baseline(WORKLOADS["c4"], budget_s=4.0, sample_rooms=1 << 18, single_thread=False)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
+    if args.dump_outputs:
+        # the timed batch has not been stepped since its last timed step: its rooms and summary are what that step left;
+        # with N > 1 every rank writes its own shard (rank<r>_*), the 64 MB shared evenly
+        paths = dump_outputs(args.dump_outputs, batch.read_rooms, batch.n_rooms, shard_first_room(rooms, rank), batch.summary_words(),
+                             budget=DUMP_BYTES // world, prefix=f"rank{rank}_" if world > 1 else "")
+        print(f"bench.py: wrote {len(paths)} arrays to {args.dump_outputs}", file=sys.stderr)
     barrier()
     batch.close()
     if use_dist:

@@ -67,3 +67,25 @@ def views_as_oracle_rooms(orc, views: np.ndarray) -> np.ndarray:
     r["p"] = views["players"]
     r["det"] = views["det"]
     return r
+
+
+def rendered_turn_calls(orc, table, case, restart=False):
+    """For every turn of one golden case, stepped by the oracle: (turn, the tool calls game_engine_amd.toolcalls renders for
+    it, whether the turn recycled the room).  A recycled room's calls are rendered from a fresh room, as a new thread's."""
+    from game_engine_amd.toolcalls import turn_tool_calls
+    rooms = orc.init_rooms(1)
+    for t in range(len(case["turns"])):
+        before = oracle_rooms_as_views(orc, rooms)[0].copy()
+        orc.run(rooms, case["seed"], case["room"], t, 1, restart=restart)
+        after = oracle_rooms_as_views(orc, rooms)[0]
+        ev = oracle_events(orc, rooms, t)[0]
+        if ev["restarted"]:
+            before = oracle_rooms_as_views(orc, orc.init_rooms(1))[0]
+        yield t, turn_tool_calls(table, before, after, ev), bool(ev["restarted"])
+
+
+def calls_digest(calls) -> str:
+    """A short, order-sensitive digest of one turn's tool calls (names and arguments)."""
+    import hashlib
+    import json
+    return hashlib.sha256(json.dumps(calls, ensure_ascii=False, separators=(",", ":")).encode("utf-8")).hexdigest()[:16]

@@ -143,3 +143,77 @@ def test_n1_line_carries_the_physical_figures_in_the_roofline_block():
     assert 0.02 < rows[0]["frac"] < 1.0 and rows[0]["hbm_floor_frac"] == 0.0
     assert rf["fused"][0]["steps_per_s"] == d["value"] and d["cpu_baseline"]["kind"] == "port"
     assert "note" not in rf and len(lines[0]) < 8192             # without the other shapes the whole line fits a tail
+
+
+def test_dump_outputs_writes_exact_floats_within_budget(tmp_path):
+    """--dump-outputs' writer (CPU, a fake batch): every view field and summary word comes back exactly from float .npy files;
+    over the byte budget, a fixed sorted sample of rooms read in chunks, the same on every call."""
+    import numpy as np
+    from game_engine_amd.stepper import ROOM_VIEW_DTYPE
+    bench = _bench_module()
+    rng = np.random.default_rng(3)
+    n = 5000
+    views = np.frombuffer(rng.integers(0, 256, n * ROOM_VIEW_DTYPE.itemsize, dtype=np.uint8).tobytes(), dtype=ROOM_VIEW_DTYPE)
+    reads = []
+
+    def read_rooms(first, count):
+        reads.append((first, count))
+        return views[first:first + count].copy()
+
+    words = np.array([0, 1, (1 << 64) - 1, 0x0123456789ABCDEF], dtype=np.uint64)
+
+    def check(out, budget, first_room=7):
+        paths = bench.dump_outputs(str(out), read_rooms, n, first_room, words, budget=budget)
+        assert sum(os.path.getsize(p) for p in paths) <= budget
+        arr = {os.path.basename(p)[:-4]: np.load(p) for p in paths}
+        assert all(a.dtype in (np.float32, np.float64) for a in arr.values())
+        s = arr["summary_words"].astype(np.uint64)
+        assert ((s[:, 0] << np.uint64(32)) | s[:, 1]).tolist() == words.tolist()
+        idx = arr["room_index"].astype(np.int64) - first_room
+        assert (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < n
+        for f in ROOM_VIEW_DTYPE.names:
+            if f != "pad":
+                assert (arr["rooms_" + f] == views[f][idx]).all(), f
+        assert "rooms_pad" not in arr
+        return idx
+
+    assert len(check(tmp_path / "all", 64 << 20)) == n and reads == [(0, n)]
+    bench.DUMP_CHUNK = 1000
+    reads.clear()
+    part = check(tmp_path / "s1", 2 << 20)
+    assert 0 < len(part) < n and reads == [(lo, 1000) for lo in range(0, n, 1000)]
+    assert check(tmp_path / "s2", 2 << 20).tolist() == part.tolist()
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_what_the_timed_steps_computed(tmp_path):
+    """`--dump-outputs DIR`: the dumped rooms and summary equal a batch of the same workload stepped on its own through the
+    fixed pre-roll, W warm-up and K timed launches - so the run is reproducible and --steps sets the number of timed turns."""
+    import numpy as np
+    from conftest import load_dsl
+    from game_engine_amd import GameTable, RoomBatch, ROOM_VIEW_DTYPE
+    bench = _bench_module()
+    fuse, warmup = 64, 1
+    tb = GameTable(load_dsl("werewolf-(mafia)"))
+    for steps in (3, 5):
+        out = tmp_path / f"k{steps}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--fuse", str(fuse),
+                            "--no-cpu-baseline", "--no-unfused", "--no-other-shapes", "--no-from-init", "--dump-outputs", str(out)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        d = json.loads(p.stdout.decode().strip().splitlines()[-1])
+        assert d["steps"] == steps
+        launches = -(-bench.PREROLL_TURNS // fuse) + warmup + steps
+        with RoomBatch([(tb, 8, 65536)], seed=bench.SEED, first_room=0, max_fuse=fuse, restart=True) as b:
+            for _ in range(launches):
+                b.step(fuse)
+            want, words = b.read_rooms(), b.summary_words()
+        s = np.load(out / "summary_words.npy").astype(np.uint64)
+        got_words = (s[:, 0] << np.uint64(32)) | s[:, 1]
+        assert got_words.tolist() == words.tolist()
+        assert int(got_words[39]) == launches * fuse                     # the summary's turn counter
+        assert (np.load(out / "room_index.npy") == np.arange(65536)).all()
+        for f in ROOM_VIEW_DTYPE.names:
+            if f != "pad":
+                assert (np.load(out / f"rooms_{f}.npy") == want[f]).all(), (steps, f)
+        assert sum(f.stat().st_size for f in out.iterdir()) <= 64_000_000

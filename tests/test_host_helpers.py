@@ -1,14 +1,10 @@
 """Host helpers that keep the reference's names and contracts (CPU)."""
-import asyncio
 import os
-import sys
 
 import pytest
 
-from conftest import GOLD, load_dsl
+from conftest import GOLD, load_dsl, load_golden
 from game_engine_amd import initialize_player_states_from_dsl, load_dsl_by_gamename
-
-REF = "/root/reference/agent/tools/utils.py"
 
 
 def test_load_dsl_by_gamename_contract(tmp_path):
@@ -31,19 +27,14 @@ def test_initialize_player_states(dsl_ww, dsl_tt):
     assert initialize_player_states_from_dsl(no_tmpl, [{"name": "Z"}]) == {"1": {"score": 0, "ok": True, "tag": "x", "name": "Z"}}
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="needs the reference checkout (build container)")
 @pytest.mark.parametrize("game", ["werewolf-(mafia)", "two-truths-and-a-lie"])
 def test_initialize_player_states_equals_reference(game):
-    from oracle.refharness import walker
-    for p in (walker._STANDINS, os.path.join(walker.REFERENCE_ROOT, "agent")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    sys.dont_write_bytecode = True
-    import tools.utils as ut
-    import yaml
-    with open(os.path.join(walker.REFERENCE_ROOT, "games", f"{game}.yaml"), encoding="utf-8") as f:
-        dsl_yaml = yaml.safe_load(f)
-    players = [{"name": f"P{i}"} for i in range(5)] + [{}]
-    want = asyncio.run(ut.initialize_player_states_from_dsl(dsl_yaml, players))
+    """Against what utils.py's own initialize_player_states_from_dsl returned for the game's YAML DSL
+    (tests/golden/ref_initialize_player_states.json, oracle/refharness/make_ref_pins.py)."""
+    from oracle.refharness.make_ref_pins import yaml_form
+    pins = load_golden("ref_initialize_player_states.json")
+    players, want = pins["players"], pins["player_states"][game]
+    assert players == [{"name": f"P{i}"} for i in range(5)] + [{}]
+    dsl_yaml = yaml_form(load_dsl(game))                                             # what yaml.safe_load gives (pinned in test_table.py)
     assert initialize_player_states_from_dsl(dsl_yaml, players) == want            # YAML (int keys) form
     assert initialize_player_states_from_dsl(load_dsl(game), players) == want      # JSON (str keys) form

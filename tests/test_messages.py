@@ -51,18 +51,17 @@ def test_classification(text, kind):
     assert M.classify(text) == kind
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/agent"), reason="the reference is only in the build container")
 def test_classification_against_the_reference_functions():
-    """classify / logged_text against the reference's own router test and process_human_action_if_needed."""
-    from oracle.refharness.walker import load_reference
-    load_reference("v2")
-    from langchain_core.messages import HumanMessage
-    from tools.utils import process_human_action_if_needed
+    """classify / logged_text against the reference's own router test and what its process_human_action_if_needed logged
+    for each sample (tests/golden/ref_human_action_logging.json, oracle/refharness/make_ref_pins.py)."""
     dsl = load_dsl("werewolf-(mafia)")
+    pins = load_golden("ref_human_action_logging.json")
+    assert pins["room_session"] == {"players": [{"gamePlayerId": 1, "name": "Alice"}]}
     samples = ["Continue", " continue", "Start game.", "start game", "Player A in game chat: x", "Player A to Bot 2: y", "to bot", "TO BOT 2",
                "Input: " + "z" * 300, 'Player 4 voted "Bot 2" in voting vote-p7-t11', "", "In Game Chat: q", "hello", "CONTINUE"]
-    for text in samples:
-        logged = process_human_action_if_needed([HumanMessage(content=text)], {}, {}, 0, {"players": [{"gamePlayerId": 1, "name": "Alice"}]}, dsl)
+    assert [c["message"] for c in pins["cases"]] == samples
+    for text, case in zip(samples, pins["cases"]):
+        logged = case["logged"]
         routed_to_chat = "in game chat:" in text or "to Bot" in text                  # v2:307, quoted
         kind = M.classify(text)
         assert (kind == M.CHAT) == routed_to_chat, text

@@ -137,13 +137,14 @@ def test_reference_draft_dsl_binds_its_own_field_names():
 
 
 def test_draft_fixture_is_the_reference_file():
-    """The fixture is yaml.safe_load of the reference's file (checked where the reference checkout exists)."""
-    import os
-    path = "/root/reference/game_draft/werewolf-(mafia).yaml"
-    if not os.path.exists(path):
-        pytest.skip("needs the reference checkout (build container)")
-    import json
-    import yaml
-    from conftest import load_dsl
-    with open(path, encoding="utf-8") as f:
-        assert json.loads(json.dumps(yaml.safe_load(f))) == load_dsl("draft-werewolf-(mafia)")
+    """The fixture is yaml.safe_load of the reference's file: its digest, and that of its YAML form, are the ones recorded from
+    the reference's file (tests/golden/ref_dsl_sources.json, oracle/refharness/make_ref_pins.py) - and so are the other games'."""
+    from conftest import load_dsl, load_golden
+    from oracle.refharness.make_ref_pins import canonical_digest, yaml_form
+    pins = load_golden("ref_dsl_sources.json")["games"]
+    assert set(pins) == {"draft-werewolf-(mafia)", "werewolf-(mafia)", "two-truths-and-a-lie"}
+    assert pins["draft-werewolf-(mafia)"]["file"] == "game_draft/werewolf-(mafia).yaml"
+    for game, pin in pins.items():
+        dsl = load_dsl(game)
+        assert json.loads(json.dumps(yaml_form(dsl))) == dsl, game
+        assert canonical_digest(yaml_form(dsl)) == pin["safe_load_sha256"], game

@@ -2,7 +2,7 @@
 frontend tool calls of a phase, derived from oracle-stepped rooms (CPU)."""
 import pytest
 
-from conftest import load_dsl
+from conftest import load_dsl, load_golden
 from game_engine_amd import GameTable
 from game_engine_amd.stepper import view_to_agent_state
 from game_engine_amd.ui_script import audience_groups, compile_criteria, frontend_tools, ui_tool_calls, validate_call
@@ -47,22 +47,16 @@ def _ui_sequence(dsl, n, turns, seed=2, states=None):
 
 
 def test_frontend_tool_table_is_the_reference_surface():
-    """frontend_tools.json = the parameter lists of page.tsx's useCopilotAction handlers; where the reference
-    checkout is present (build container) the committed table must equal a fresh extraction."""
-    import os
+    """frontend_tools.json = the parameter lists of page.tsx's useCopilotAction handlers: the committed table must equal
+    the extraction from the reference's page recorded in tests/golden/ref_frontend_tools.json
+    (oracle/refharness/make_ref_pins.py)."""
     tools = frontend_tools()
     req = lambda t: [p[0] for p in tools[t] if p[2]]
     assert req("createVotingPanel") == ["name", "votingId", "options", "position"]            # page.tsx:1146-1157
     assert req("markPlayerDead") == ["playerId", "playerName"]                                # page.tsx:1256-1262
     assert [p[0] for p in tools["clearCanvas"]] == ["exemptList"] and req("clearCanvas") == []  # page.tsx:2418-2426
     assert FRONTEND_TOOLS <= set(tools)
-    if os.path.exists("/root/reference/src/app/page.tsx"):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("extract_frontend_tools", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "extract_frontend_tools.py"))
-        ex = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(ex)
-        page = open("/root/reference/src/app/page.tsx", encoding="utf-8").read()
-        assert ex.extract(page) == tools
+    assert load_golden("ref_frontend_tools.json")["tools"] == tools
 
 
 @pytest.mark.parametrize("game,n,turns", [("werewolf-(mafia)", 8, 80), ("werewolf-(mafia)", 12, 110), ("two-truths-and-a-lie", 4, 50),
