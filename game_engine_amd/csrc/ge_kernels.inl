@@ -622,9 +622,11 @@ __global__ void __launch_bounds__(256) ge_summary_kernel(const StepArgs a, const
         default: { uint32_t w[12]; load_words<12>(sg.base, sg.rooms_padded, room, w); q = stats_tt<12>(w, rows, sg.n_players, h_score); h = fold_words<12>(h0, w); break; }
         }
         ck += (uint64_t)h | ((uint64_t)mix32(h ^ 0x5BD1E995u) << 32);
-        if (q.finished) atomicAdd(&h_end[(q.end_turn >> 3) < 15 ? (q.end_turn >> 3) : 15], 1u);
+        // a terminal room whose end_turn is unset (a state written by ge_batch_write_rooms) is finished but has no end turn
+        const bool ended = q.finished && q.end_turn != END_NONE;
+        if (ended) atomicAdd(&h_end[(q.end_turn >> 3) < 15 ? (q.end_turn >> 3) : 15], 1u);
         r.finished += q.finished; r.village += q.village; r.wolves += q.wolves; r.alive += q.alive;
-        r.end_turn += q.finished ? q.end_turn : 0u; r.games += q.games;
+        r.end_turn += ended ? q.end_turn : 0u; r.games += q.games;
     }
     const uint64_t v0 = wave_sum(r.finished), v1 = wave_sum(r.village), v2 = wave_sum(r.wolves);
     const uint64_t v3 = wave_sum(r.alive), v4 = wave_sum(r.end_turn), v5 = wave_sum(ck);

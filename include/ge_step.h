@@ -233,8 +233,9 @@ typedef struct ge_summary {
     uint64_t rooms;
     uint64_t finished;                    /* rooms in a terminal phase */
     uint64_t village_wins, wolf_wins;     /* werewolf rooms finished with no / some wolves alive */
-    uint64_t alive_players;
-    uint64_t sum_end_turn;                /* over finished rooms */
+    uint64_t alive_players;               /* werewolf: alive seats; two-truths: every seat (n_players per room) */
+    uint64_t sum_end_turn;                /* over finished rooms whose end_turn is set: a room written in a terminal
+                                             phase with end_turn -1 counts as finished but adds nothing here or below */
     uint64_t end_turn_hist[16];           /* finished rooms by end_turn / 8 (last bucket open) */
     uint64_t score_hist[16];              /* two-truths: players by total_score (last bucket open) */
     uint64_t checksum;                    /* sum over rooms of hash(global room index, packed state) */

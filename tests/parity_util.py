@@ -89,3 +89,61 @@ def calls_digest(calls) -> str:
     import hashlib
     import json
     return hashlib.sha256(json.dumps(calls, ensure_ascii=False, separators=(",", ":")).encode("utf-8")).hexdigest()[:16]
+
+
+def assert_summary_equal(got, want, what=""):
+    """Summaries as words (RoomBatch.summary_words / oracle.summary.reference_summary_words) or dicts, field by field."""
+    from game_engine_amd.stepper import summary_to_dict
+    g, w = (x if isinstance(x, dict) else summary_to_dict(np.asarray(x, dtype=np.uint64)) for x in (got, want))
+    bad = {k: (g[k], w[k]) for k in g if g[k] != w[k]}
+    assert not bad, f"{what}: summary fields differ (got, reference): {bad}"
+
+
+def raw_records(batch, segment, n_rooms, words):
+    """The packed records of a segment as they lie in HBM (ge_batch_state + a D2H copy), [n_rooms, words] uint32:
+    plane j holds words 4j..4j+3 of every room (ge_layout.h)."""
+    import ctypes as C
+    batch.sync()
+    ptr, nbytes, bpr = batch.state(segment)
+    assert bpr == 4 * words
+    raw = np.empty(nbytes, dtype=np.uint8)
+    assert C.CDLL("libamdhip64.so").hipMemcpy(C.c_void_p(raw.ctypes.data), C.c_void_p(ptr), C.c_size_t(nbytes), 2) == 0
+    planes = (words + 3) // 4
+    padded = nbytes // (16 * planes)
+    out = np.empty((n_rooms, words), dtype=np.uint32)
+    for j in range(planes):
+        pw = min(4, words - 4 * j)
+        plane = raw[j * 16 * padded:(j + 1) * 16 * padded].view(np.uint32)[: padded * pw].reshape(padded, pw)
+        out[:, 4 * j:4 * j + pw] = plane[:n_rooms]
+    return out
+
+
+def assert_records_canonical(batch, segment, orc, rooms, what=""):
+    """Every raw record of the segment == the summary reference's canonical packing of the oracle's rooms (Werewolf x 8:
+    the prepared-deal cache, word 7's upper half, aside) - no bit outside the view depends on which kernel wrote it."""
+    from oracle.summary import WORDS, kind_of, pack_records, K_WW8
+    kind = kind_of(orc.table.pack, orc.n)
+    got = raw_records(batch, segment, len(rooms), WORDS[kind])
+    if kind == K_WW8:
+        got[:, 7] &= 0xFFFF
+    want = pack_records(kind, rooms, orc.table)
+    bad = np.nonzero((got != want).any(axis=1))[0]
+    if len(bad):
+        i = int(bad[0])
+        raise AssertionError(f"{what}: {len(bad)} raw records differ from the canonical packing; first room {i}: "
+                             f"HBM {[hex(x) for x in got[i]]} canonical {[hex(x) for x in want[i]]}")
+
+
+def oracle_summary_words(orc, n_rooms, seed, first, turns, restart=False, chunk=1 << 20, each=None):
+    """The reference summary of n_rooms rooms of one game stepped by the oracle from the initial state, run chunk by chunk
+    (rooms are independent and keyed by their global index).  each(lo, rooms) sees every chunk's oracle rooms."""
+    from oracle.summary import SUMMARY_WORDS, W_TURN, add_rooms
+    words = np.zeros(SUMMARY_WORDS, dtype=np.uint64)
+    for lo in range(0, n_rooms, chunk):
+        rooms = orc.init_rooms(min(chunk, n_rooms - lo))
+        orc.run(rooms, seed, first + lo, 0, turns, threads=0, restart=restart)
+        add_rooms(words, orc.table, orc.n, rooms, first + lo)
+        if each is not None:
+            each(lo, rooms)
+    words[W_TURN] = turns
+    return words

@@ -21,20 +21,14 @@ def _free_port():
 
 
 def _oracle_summary_words(game, n, seed, lo, hi, turns):
-    """ge_summary words for rooms [lo, hi) computed from oracle rooms (checksum left 0)."""
+    """ge_summary words for rooms [lo, hi), checksum included, from oracle rooms (oracle/summary.py)."""
     from oracle.oracle import Oracle
+    from oracle.summary import reference_summary_words
     orc = Oracle(load_dsl(game), n)
     rooms = orc.init_rooms(hi - lo)
     orc.run(rooms, seed, lo, 0, turns, threads=1)
-    w = np.zeros(SUMMARY_WORDS, dtype=np.uint64)
-    fin = rooms["end_turn"] >= 0
-    alive = rooms["p"][:, :n, 2]
-    wolves = ((rooms["p"][:, :n, 1] == 2) & (alive == 1)).sum(axis=1)
-    w[0], w[1] = hi - lo, fin.sum()
-    w[2], w[3] = (fin & (wolves == 0)).sum(), (fin & (wolves > 0)).sum()
-    w[4], w[5] = alive.sum(), rooms["end_turn"][fin].sum()
-    w[6:22] = np.bincount(np.minimum(rooms["end_turn"][fin] // 8, 15), minlength=16)
-    w[39] = turns
+    w = reference_summary_words([(orc.table, n, rooms)], lo, turns)
+    assert w.shape == (SUMMARY_WORDS,)
     return w
 
 
@@ -67,6 +61,7 @@ def test_sharded_summary_equals_whole_job(world):
     ranges = sorted((lo, hi) for _, lo, hi, _ in results)
     assert ranges[0][0] == 0 and ranges[-1][1] == total
     assert all(a[1] == b[0] for a, b in zip(ranges, ranges[1:]))
+    assert whole[38] != 0 and whole[1] > 0    # the whole-job summary carries a real checksum, and finished games
     for _, _, _, summed in results:           # every rank ends up with the whole-job summary
         assert summed == whole
 

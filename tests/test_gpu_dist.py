@@ -53,3 +53,7 @@ def test_two_ranks_summary_equals_single_batch():
         assert p.exitcode == 0
     for _, s in results:
         assert s == whole
+    from oracle.oracle import Oracle
+    from parity_util import assert_summary_equal, oracle_summary_words
+    ref = oracle_summary_words(Oracle(load_dsl("werewolf-(mafia)"), 8), TOTAL, SEED, FIRST, TURNS)
+    assert_summary_equal(whole, ref, "two ranks' whole-job summary vs reference")

@@ -186,3 +186,179 @@ def test_hand_built_edge_cases(dsl_ww):
     assert first["end_turn"][3] == 3
     dd = [int(x["phase_id"][2]) for x in traj]
     assert 11 in dd and dd[dd.index(11) + 1] == 12 if dd.index(11) + 1 < len(dd) else True   # empty target set: one turn only
+
+
+# ---- random states where the matrix above does not reach: the mixed kernel, Werewolf with absent seats of the x 12 layout
+# ---- (9 - 11 players) and 5 - 7 players on the large-batch build, Two-Truths on the large-batch build and in single-turn
+# ---- launches, the draft DSL's bound fields, host-driven seats with batched injection, the event trace.  Every room
+# ---- against the oracle after every block of turns, and the summary (checksum included) against the host reference.
+
+def _summary_ref(parts, first, turn):
+    from oracle.summary import reference_summary_words
+    return reference_summary_words([(orc.table, orc.n, rooms) for orc, rooms in parts], first, turn)
+
+
+def _random_views(orc, n, R, rng):
+    if orc.table.pack == 1:
+        return _random_ww_views(orc, n, R, rng, consistent=bool(R % 2))
+    return _random_tt_views(orc, n, R, rng, rounds=1)
+
+
+def _play_blocks(b, parts, seed, first, chunks, restart, what):
+    """Steps `b` by each chunk and the oracle with it; every room and the summary compared after each block."""
+    from parity_util import assert_summary_equal
+    for chunk in chunks:
+        b.step(chunk)
+        base = 0
+        for orc, rooms in parts:
+            orc.run(rooms, seed, first + base, b.turn - chunk, chunk, threads=0, restart=restart)
+            assert_views_equal(b.read_rooms(base, len(rooms)), oracle_rooms_as_views(orc, rooms),
+                               f"{what}: x{orc.n} segment at {base}, turn {b.turn}")
+            base += len(rooms)
+        assert_summary_equal(b.summary_words(), _summary_ref(parts, first, b.turn), f"{what}: turn {b.turn}")
+
+
+@pytest.mark.parametrize("fuse", [1, 16])
+@pytest.mark.parametrize("sizes", [(3001, 2999, 3037, 2903), (20011, 17003, 16411, 15013)])   # total below / above 65 536
+def test_mixed_batch_from_random_states(dsl_ww, dsl_tt, sizes, fuse):
+    """The mixed kernel (one launch for Werewolf x 6, Two-Truths x 4, Werewolf x 10, Two-Truths x 7), steady state."""
+    seed, first = 31337, (1 << 34) + 5
+    games = [(dsl_ww, 6), (dsl_tt, 4), (dsl_ww, 10), (dsl_tt, 7)]
+    rng = np.random.default_rng(sum(sizes) + fuse)
+    parts, segs = [], []
+    for (dsl, n), R in zip(games, sizes):
+        orc = _oracle(dsl, n)
+        views = _random_views(orc, n, R, rng)
+        parts.append((orc, views_as_oracle_rooms(orc, views)))
+        segs.append(((GameTable(dsl), n, R), views))
+    with RoomBatch([s for s, _ in segs], seed=seed, first_room=first, max_fuse=fuse, restart=True) as b:
+        b.step(4)
+        base = 0
+        for (_, _, R), views in segs:
+            b.write_rooms(base, views)
+            base += R
+        _play_blocks(b, parts, seed, first, (1, 1, 16, 2, 33), True, f"mixed {sizes} fuse {fuse}")
+        assert b.summary()["games_recycled"] > 0
+
+
+@pytest.mark.parametrize("n,R,fuse", [(5, 3000, 1), (7, 3000, 16), (7, 90000, 1), (9, 3000, 1), (10, 3000, 16),
+                                      (10, 90000, 8), (11, 3000, 1)])
+def test_werewolf_player_counts_from_random_states(dsl_ww, n, R, fuse):
+    """Werewolf with absent seats: x 5 / x 7 in the x 8 layout, x 9 - x 11 in the x 12 layout; both builds for 7 and 10."""
+    seed, first = 4243, 1 << 37
+    rng = np.random.default_rng(n * 13 + R + fuse)
+    orc = _oracle(dsl_ww, n)
+    views = _random_ww_views(orc, n, R, rng, consistent=False)
+    parts = [(orc, views_as_oracle_rooms(orc, views))]
+    with RoomBatch([(GameTable(dsl_ww), n, R)], seed=seed, first_room=first, max_fuse=fuse, restart=True) as b:
+        b.step(3)
+        b.write_rooms(0, views)
+        _play_blocks(b, parts, seed, first, (1, 17, 1, 40), True, f"werewolf x{n} {R} rooms fuse {fuse}")
+
+
+@pytest.mark.parametrize("n,fuse", [(4, 1), (4, 8), (7, 8)])
+def test_two_truths_large_batch_from_random_states(dsl_tt, n, fuse):
+    """The shipped Two-Truths table on the large-batch build, single-turn launches and fused ones."""
+    R, seed, first = 150000, 6, 1 << 41
+    rng = np.random.default_rng(n * 3 + fuse)
+    orc = _oracle(dsl_tt, n)
+    views = _random_tt_views(orc, n, R, rng, 1)
+    parts = [(orc, views_as_oracle_rooms(orc, views))]
+    with RoomBatch([(GameTable(dsl_tt), n, R)], seed=seed, first_room=first, max_fuse=fuse, restart=True) as b:
+        b.step(2)
+        b.write_rooms(0, views)
+        _play_blocks(b, parts, seed, first, (1, 8, 1, 16), True, f"two-truths x{n} fuse {fuse}")
+
+
+def _random_draft_views(orc, n, R, rng):
+    """Random states of the reference's draft Werewolf DSL: the slots it declares (through its own field names) take random
+    values; the slots it does not declare (has_secret_role, night_action_submitted, selected_target_id) keep what the
+    template gives every room, as they would in a real game of this DSL."""
+    from parity_util import oracle_rooms_as_views as as_views
+    v = _random_ww_views(orc, n, R, rng, consistent=False)
+    init = as_views(orc, orc.init_rooms(1))[0]
+    slots = ("role", "team", "is_alive", "role_revealed", "can_vote", "has_secret_role", "night_action_eligible",
+             "night_action_submitted", "selected_target_id")
+    for col, slot in enumerate(slots):
+        if not orc.table.declared(slot):
+            v["players"][:, :n, col] = init["players"][:n, col]
+    if not orc.table.declared("investigated_alignments"):
+        v["det"][:] = 0
+    return v
+
+
+@pytest.mark.parametrize("n,fuse", [(8, 1), (11, 16)])
+def test_draft_werewolf_from_random_states(n, fuse):
+    from conftest import load_dsl
+    dsl = load_dsl("draft-werewolf-(mafia)")
+    R, seed, first = 6000, 12, 999
+    orc = _oracle(dsl, n)
+    assert not orc.table.declared("selected_target_id")             # the binding the builder respects
+    views = _random_draft_views(orc, n, R, np.random.default_rng(n + fuse))
+    parts = [(orc, views_as_oracle_rooms(orc, views))]
+    with RoomBatch([(GameTable(dsl), n, R)], seed=seed, first_room=first, max_fuse=fuse, restart=True) as b:
+        b.step(1)
+        b.write_rooms(0, views)
+        _play_blocks(b, parts, seed, first, (1, 16, 1, 16), True, f"draft werewolf x{n} fuse {fuse}")
+
+
+@pytest.mark.parametrize("game,n,mask", [("werewolf-(mafia)", 8, 0b10000001), ("werewolf-(mafia)", 11, 0b10000000101),
+                                         ("two-truths-and-a-lie", 5, 0b11)])
+def test_host_driven_seats_from_random_states(game, n, mask):
+    """Random states with host-driven seats: batched injection (ge_batch_inject_actions) of random actions between
+    single-turn launches, accepted / refused exactly as Oracle.inject decides, then every room and the summary."""
+    from conftest import load_dsl
+    dsl = load_dsl(game)
+    R, seed, first = 2000, 8, 1 << 30
+    rng = np.random.default_rng(n + mask)
+    orc = _oracle(dsl, n)
+    views = _random_views(orc, n, R, rng)
+    rooms = views_as_oracle_rooms(orc, views)
+    human = [i + 1 for i in range(n) if (mask >> i) & 1]
+    accepted = refused = 0
+    with RoomBatch([(GameTable(dsl), n, R, mask)], seed=seed, first_room=first, max_fuse=1) as b:
+        b.step(2)
+        b.write_rooms(0, views)
+        for t in range(12):
+            rs = np.sort(rng.choice(R, size=600, replace=False)).astype(np.uint64)
+            pl = rng.choice(human, size=len(rs)).astype(np.uint32)
+            ch = rng.integers(0, n + 2, len(rs)).astype(np.uint32)
+            status = b.inject_actions(rs, pl, ch)
+            for k in range(len(rs)):
+                ok = orc.inject(rooms, int(rs[k]), int(pl[k]), int(ch[k]))
+                assert ok == (status[k] == 0), (t, int(rs[k]), int(pl[k]), int(ch[k]), int(status[k]))
+                accepted += ok
+                refused += not ok
+            b.step(1)
+            orc.run(rooms, seed, first, b.turn - 1, 1, threads=0, human_mask=mask)
+            assert_views_equal(b.read_rooms(), oracle_rooms_as_views(orc, rooms), f"{game} x{n} turn {b.turn}")
+        from parity_util import assert_summary_equal
+        assert_summary_equal(b.summary_words(), _summary_ref([(orc, rooms)], first, b.turn), f"{game} x{n} host-driven")
+    assert accepted > 100 and refused > 100
+
+
+@pytest.mark.parametrize("game,n,R", [("werewolf-(mafia)", 8, 3000), ("werewolf-(mafia)", 10, 70001),
+                                      ("two-truths-and-a-lie", 4, 3000), ("two-truths-and-a-lie", 9, 70001)])
+def test_event_trace_from_random_states(game, n, R):
+    """trace=True from random states: every turn's events (read_events) == the oracle's record of that turn."""
+    from conftest import load_dsl
+    from parity_util import oracle_events
+    dsl = load_dsl(game)
+    seed, first = 515, 1 << 20
+    orc = _oracle(dsl, n)
+    views = _random_views(orc, n, R, np.random.default_rng(n * R))
+    rooms = views_as_oracle_rooms(orc, views)
+    with RoomBatch([(GameTable(dsl), n, R)], seed=seed, first_room=first, max_fuse=16, restart=True, trace=True) as b:
+        b.step(1)
+        b.write_rooms(0, views)
+        for chunk in (1, 16, 5):
+            b.step(chunk)
+            ev = b.read_events()
+            assert ev.shape == (R, chunk)
+            for k in range(chunk):
+                t = b.turn - chunk + k
+                orc.run(rooms, seed, first, t, 1, threads=0, restart=True)
+                want, got = oracle_events(orc, rooms, t), np.ascontiguousarray(ev[:, k])
+                for f in ("turn", "from_phase_id", "to_phase_id", "acted_now", "restarted", "choice"):
+                    assert (got[f] == want[f]).all(), (game, n, f, t)
+            assert_views_equal(b.read_rooms(), oracle_rooms_as_views(orc, rooms), f"{game} x{n} traced, turn {b.turn}")

@@ -9,7 +9,8 @@ import numpy as np
 from game_engine_amd import GameTable, GeError, RoomBatch, RoomGroup
 from game_engine_amd.stepper import RoomShards, sum_summaries
 from game_engine_amd.dist import reduce_summaries
-from parity_util import assert_views_equal
+from oracle.oracle import Oracle
+from parity_util import assert_summary_equal, assert_views_equal, oracle_summary_words
 
 pytestmark = pytest.mark.gpu
 
@@ -33,6 +34,15 @@ def test_one_device_group_equals_single_batch():
     assert got == want
     assert len(parts) == 1 and parts[0] == want
     assert_views_equal(rooms, want_rooms, "group of one device vs one batch")
+    # and the whole-job summary == the host reference over the oracle's rooms
+    ref = np.zeros(41, dtype=np.uint64)
+    base = first
+    for tb, n, R in _segs():
+        with np.errstate(over="ignore"):
+            ref += oracle_summary_words(Oracle(tb.dsl, n), R, seed, base, 70, restart=True)
+        base += R
+    ref[39] = 70
+    assert_summary_equal(got, ref, "device group vs reference")
 
 
 def test_duplicate_devices_and_bad_ordinals_are_refused_cleanly():

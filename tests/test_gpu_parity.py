@@ -8,8 +8,8 @@ import pytest
 
 from conftest import golden_dsl, golden_files, human_files, load_dsl, load_golden, restart_files
 from game_engine_amd import GameTable, GeError, RoomBatch
-from game_engine_amd.stepper import project_view
-from parity_util import assert_views_equal, oracle_batch, oracle_rooms_as_views
+from game_engine_amd.stepper import project_view, summary_to_dict
+from parity_util import assert_summary_equal, assert_views_equal, oracle_batch, oracle_rooms_as_views, oracle_summary_words
 
 pytestmark = pytest.mark.gpu
 SEEDS = [0, 1, 0xC0FFEE]
@@ -119,19 +119,20 @@ def test_high_occupancy_path_equals_oracle(game, n, n_rooms):
 def test_full_baseline_sizes_equal_oracle(game, n, n_rooms, first):
     """The BASELINE shapes at their full per-GPU size (256-room blocks, 16+ wavefronts per SIMD), every
     room against the oracle: the oracle runs chunk by chunk on the host cores (rooms are independent
-    and keyed by their global index), the GPU batch in one piece."""
+    and keyed by their global index), the GPU batch in one piece.  The summary (every word, checksum included) == the
+    reference over every room."""
     dsl = load_dsl(game)
     orc = _oracle(dsl, n)
     seed, turns, chunk = 0xC0FFEE, 80, 1 << 18
     with RoomBatch([(GameTable(dsl), n, n_rooms)], seed=seed, first_room=first, restart=True) as b:
         b.step(turns)
-        s = b.summary()
-        recycled = 0
-        for lo in range(0, n_rooms, chunk):
-            want = oracle_batch(orc, chunk, seed, first + lo, turns, restart=True)
-            assert_views_equal(b.read_rooms(lo, chunk), want, f"{game} n={n} rooms {lo}..{lo + chunk}")
-            recycled += int(want["games"].sum())
-    assert s["games_recycled"] == recycled and s["rooms"] == n_rooms
+        s = b.summary_words()
+
+        def each(lo, rooms):
+            assert_views_equal(b.read_rooms(lo, chunk), oracle_rooms_as_views(orc, rooms), f"{game} n={n} rooms {lo}..{lo + chunk}")
+        want = oracle_summary_words(orc, n_rooms, seed, first, turns, restart=True, chunk=chunk, each=each)
+    assert_summary_equal(s, want, f"{game} n={n}, {n_rooms} rooms")
+    assert want[40] > 0 and want[0] == n_rooms
 
 
 @pytest.mark.parametrize("name", human_files())
@@ -467,14 +468,17 @@ def test_single_turn_launches_beyond_the_infinity_cache_equal_fused_and_oracle(g
     seed, first, turns, win = 0xC0FFEE, 1 << 36, 70, 4096
     with RoomBatch([(tb, n, n_rooms)], seed=seed, first_room=first, max_fuse=1, restart=True) as k1:
         k1.step(turns)
-        s1 = k1.summary()
+        w1 = k1.summary_words()
         for lo in (0, n_rooms // 2 - 77, n_rooms - win):
             assert_views_equal(k1.read_rooms(lo, win), oracle_batch(orc, win, seed, first + lo, turns, restart=True),
                                f"{game} x{n}: rooms {lo}.. of {n_rooms}, single-turn launches")
     with RoomBatch([(tb, n, n_rooms)], seed=seed, first_room=first, max_fuse=64, restart=True) as fz:
         fz.step(turns)
         sf = fz.summary()
+    s1 = summary_to_dict(w1)
     assert s1 == sf and s1["rooms"] == n_rooms and s1["turn"] == turns and s1["games_recycled"] > 0
+    # every room against the oracle, through the summary: parity for all of them, not only for the windows
+    assert_summary_equal(w1, oracle_summary_words(orc, n_rooms, seed, first, turns, restart=True), f"{game} x{n}, {n_rooms} rooms")
 
 
 def test_mixed_batch_single_turn_launches_full_c5_share(dsl_ww, dsl_tt):
@@ -485,7 +489,8 @@ def test_mixed_batch_single_turn_launches_full_c5_share(dsl_ww, dsl_tt):
     segs = [(GameTable(dsl_ww), 8, half), (GameTable(dsl_tt), 4, half)]
     with RoomBatch(segs, seed=seed, first_room=first, max_fuse=1, restart=True) as k1:
         k1.step(turns)
-        s1 = k1.summary()
+        k1_words = k1.summary_words()
+        s1 = summary_to_dict(k1_words)
         for dsl, n, base in ((dsl_ww, 8, 0), (dsl_tt, 4, half)):
             orc = _oracle(dsl, n)
             for lo in (base, base + half // 2 - 33, base + half - win):
@@ -495,6 +500,11 @@ def test_mixed_batch_single_turn_launches_full_c5_share(dsl_ww, dsl_tt):
         fz.step(turns)
         sf = fz.summary()
     assert s1 == sf and s1["rooms"] == 2 * half and s1["games_recycled"] > 0
+    want = oracle_summary_words(_oracle(dsl_ww, 8), half, seed, first, turns, restart=True)
+    with np.errstate(over="ignore"):
+        want += oracle_summary_words(_oracle(dsl_tt, 4), half, seed, first + half, turns, restart=True)
+    want[39] = turns
+    assert_summary_equal(k1_words, want, "C5 share, every room")
 
 
 @pytest.mark.parametrize("n_rooms", [700, 140001])               # lone-wavefront and large-batch builds
