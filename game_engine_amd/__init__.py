@@ -8,6 +8,7 @@ from .stepper import (GameTable, RoomBatch, RoomGroup, GeError, load_dsl_by_game
                       ROOM_VIEW_DTYPE, EVENT_DTYPE, WW_FIELDS, TT_FIELDS)
 
 from .room_service import RoomService, room_index_of
+from .room_pool import RoomPoolService
 
-__all__ = ["RoomService", "room_index_of", "GameTable", "RoomBatch", "RoomGroup", "GeError", "load_dsl_by_gamename", "initialize_player_states_from_dsl", "library_path",
+__all__ = ["RoomService", "RoomPoolService", "room_index_of", "GameTable", "RoomBatch", "RoomGroup", "GeError", "load_dsl_by_gamename", "initialize_player_states_from_dsl", "library_path",
            "ROOM_VIEW_DTYPE", "EVENT_DTYPE", "WW_FIELDS", "TT_FIELDS"]

@@ -1,0 +1,325 @@
+// ge_pool.inl — the indexed single-turn step (ge_batch_step_rooms) and the indexed read (ge_batch_read_rooms_at): many game
+// threads hosted in one resident batch, each slot stepped under its own RNG key and turn number (included at the end of
+// ge_step.hip, behind every other kernel: the existing kernels keep their code-object offsets; it needs ge_batch's internals).
+//
+// The reference runs one LangGraph thread per room and a thread plays a turn only when its own message arrives
+// (src/app/api/copilotkit/route.ts:24-37).  ge_batch_step moves every room under one batch-wide turn counter; here a list of
+// entries k moves room rooms[k] by one turn keyed as global room keys[k] at turn turns[k] - what a lone batch with first_room =
+// keys[k] and turn counter turns[k] does to that room in one ge_batch_step(b, 1).
+//
+// One lane per entry.  What a step launch keeps uniform per wavefront - the turn, the deal period, the room key - is per lane
+// here; the turn itself is ge_device.h's single-turn form (ww_turn / tt_turn, SINGLE), in the lone-wavefront build: these
+// launches are a few wavefronts at tick sizes, a chain of latencies, and that build reads its tables where they lie in global
+// memory (GE_SINGLE_GLOBAL's reasoning) instead of filling LDS behind a barrier.
+//
+// Prepared role deals.  A prepared deal is a pure function of (seed, global room, game index) tagged only by the game index
+// (Werewolf x 8: the record's upper half-word 7; Werewolf x 12: the side plane of ge_kernels.inl run_ww), so a deal prepared
+// for a slot under the batch's own key would mislead a turn under another key.  So an indexed step never reads or writes the
+// side plane, ignores a record's prepared deal, deals on the spot (ww_apply_effect), and stores every record without one - as
+// ge_batch_write_rooms does.  Ordinary ge_batch_step calls before or after on the same batch stay exact: the side plane still
+// holds only deals of the slots' own keys, and a record without a deal gets its next one prepared or dealt on the spot.
+//
+// Mixed batches: entries are grouped by segment on the host (a stable counting sort) and each segment present gets one launch of
+// its layout's kernel - a wavefront never mixes layouts (the action queue is a wave-wide collective).
+
+namespace {
+
+struct PoolArgs {
+    const uint64_t *rooms;     // segment-local room of each entry of this launch
+    const uint64_t *keys;      // global room index its RNG stream is keyed by
+    const uint32_t *turns;     // its turn number
+    uint32_t *events;          // [n] x 4 words: turn | from, to, restarted, acted (as the GE_FLAG_TRACE record) | choice nibbles
+    uint32_t n, seg, seed_key, restart;
+};
+
+__device__ __forceinline__ void pool_event(uint32_t *events, uint32_t k, uint32_t turn, uint32_t p, uint32_t q, uint32_t restarted,
+                                           uint32_t newly, uint64_t choice) {
+    u32x4 v;
+    v.x = turn; v.y = p | (q << 8) | (restarted << 16) | (newly << 20);
+    v.z = (uint32_t)choice; v.w = (uint32_t)(choice >> 32);
+    reinterpret_cast<u32x4 *>(events)[k] = v;
+}
+
+__device__ __forceinline__ CondShape pool_cond_shape(const DevTable &tb) {
+    return CondShape{(uint32_t)__builtin_amdgcn_readfirstlane(tb.cond_shape), (uint32_t)__builtin_amdgcn_readfirstlane(tb.cond_g[0]), (uint32_t)__builtin_amdgcn_readfirstlane(tb.cond_g[1]),
+                     (uint32_t)__builtin_amdgcn_readfirstlane(tb.cond_fields[0]), (uint32_t)__builtin_amdgcn_readfirstlane(tb.cond_fields[1])};
+}
+
+template <int NB, int GENERIC>
+__device__ __forceinline__ void pool_ww(const SegDev &sg, const DevTable *__restrict__ tables, const PoolArgs &a, void *lw, uint32_t k_in) {
+    using L = WWLayout<NB>;
+    // lanes past the list stay in the wavefront (the action queue is a wave-wide collective): they shadow entry 0 and store nothing
+    const bool valid = k_in < a.n;
+    const uint32_t k = valid ? k_in : 0u;
+    const uint64_t room = a.rooms[k];
+    uint32_t w[L::WORDS];
+    load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+    const uint32_t rk = room_key_from(a.seed_key, a.keys[k]);
+    const uint32_t turn = a.turns[k];
+    const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
+    const DevRow *rows = reinterpret_cast<const DevRow *>(img);
+    const CondShape cs = GENERIC ? pool_cond_shape(tables[sg.table_idx]) : CondShape{0u, 0u, 0u, 0u, 0u};
+    const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
+    const WwCtx ctx = {rows, CondCtx{reinterpret_cast<const unsigned char *>(tables[sg.table_idx].cond_img), cs}, lw, img + IMG_NTH8,
+                       reinterpret_cast<const uint32_t *>(img + IMG_ORD8), valid, sg.n_players, sg.nw, sg.phase0_idx, rk, sg.human_mask, term_mask};
+    WWR<NB> s;
+    uint32_t cache;                                           // the record's prepared deal: not of this key, never used
+    ww_load_regs<NB>(w, s, cache);
+    uint32_t restarted = 0;
+    if (a.restart && ((term_mask >> s.phase) & 1u)) {         // recycle a finished room (run_ww's single-turn form)
+        uint32_t ir[20];
+        load_init_regs<WWR<NB>::NREGS>(sg, ir);
+        const uint32_t g = s.games;
+        WWR<NB> s0;
+        s0.from_regs(ir);
+        s = s0;
+        s.games = g < 0xFFFFu ? g + 1u : g;
+        restarted = 1;
+    }
+    DevRow row = lds_row<false>(rows, s.phase);
+    const uint32_t p = s.phase;
+    Deal deal = {0u, 0u, 0u, 0u, 0u};                         // no prepared deal (gv = 0): an assignment deals on the spot
+    uint32_t tk = turn_key(rk, turn);
+    uint32_t ev_newly = 0;
+    uint64_t ev_choice = 0;
+    ww_turn<NB, true, GENERIC, true>(s, row, ctx, turn, tk, true, deal, false, ev_newly, ev_choice, nullptr);
+    if (!valid) return;
+    pool_event(a.events, k, turn, p, s.phase, restarted, ev_newly, ev_choice);
+    ww_store_regs<NB>(s, 0u, w);                              // stored without a prepared deal
+    store_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+}
+
+template <int NB, int GENERIC>
+__device__ __forceinline__ void pool_tt(const SegDev &sg, const DevTable *__restrict__ tables, const PoolArgs &a, void *lw, uint32_t k_in) {
+    using L = TTLayout<NB>;
+    const bool valid = k_in < a.n;
+    const uint32_t k = valid ? k_in : 0u;
+    const uint64_t room = a.rooms[k];
+    uint32_t w[L::WORDS];
+    load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+    const uint32_t rk = room_key_from(a.seed_key, a.keys[k]);
+    const uint32_t turn = a.turns[k];
+    const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
+    const DevRow *rows = reinterpret_cast<const DevRow *>(img);
+    const CondShape cs = GENERIC ? pool_cond_shape(tables[sg.table_idx]) : CondShape{0u, 0u, 0u, 0u, 0u};
+    const CondCtx cc = {reinterpret_cast<const unsigned char *>(tables[sg.table_idx].cond_img), cs};
+    const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
+    TT<NB> s;
+    L::unpack(w, s);
+    uint32_t done = tt_done_mask<NB>(s.rounds, sg.rounds);
+    uint32_t restarted = 0;
+    if (a.restart && ((term_mask >> s.phase) & 1u)) {
+        uint32_t ir[20];
+        load_init_regs<TT<NB>::NREGS>(sg, ir);
+        const uint32_t g = s.games;
+        TT<NB> s0;
+        s0.from_regs(ir);
+        s = s0;
+        s.games = g < 0xFFFFu ? g + 1u : g;
+        done = __builtin_amdgcn_readfirstlane(sg.done0);
+        restarted = 1;
+    }
+    DevRow row = lds_row<false>(rows, s.phase);
+    const uint32_t p = s.phase;
+    uint32_t ev_newly = 0;
+    uint64_t ev_choice = 0;
+    tt_turn<NB, tt_uses_queue(NB, true), false, GENERIC, true>(s, done, row, rows, cc, lw, img + IMG_NTH8, valid, sg.n_players, sg.rounds, sg.phase0_idx,
+                                                             rk, turn, true, sg.human_mask, term_mask, ev_newly, ev_choice);
+    if (!valid) return;
+    pool_event(a.events, k, turn, p, s.phase, restarted, ev_newly, ev_choice);
+    L::pack(s, w);
+    store_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+}
+
+// one wavefront per block; its action queue (WaveLdsLow) is the block's dynamic LDS (none for Two-Truths x 4: no queue)
+template <int KIND, int GENERIC>
+__global__ void __launch_bounds__(64) ge_pool_kernel(const SegDev *__restrict__ segs, const DevTable *__restrict__ tables, const PoolArgs a) {
+    const SegDev &sg = segs[a.seg];
+    const uint32_t k = blockIdx.x * 64u + threadIdx.x;
+    void *lw = ge_lds;
+    if (KIND == K_WW8) pool_ww<8, GENERIC>(sg, tables, a, lw, k);
+    else if (KIND == K_WW12) pool_ww<12, GENERIC>(sg, tables, a, lw, k);
+    else if (KIND == K_TT4) pool_tt<4, GENERIC>(sg, tables, a, lw, k);
+    else if (KIND == K_TT8) pool_tt<8, GENERIC>(sg, tables, a, lw, k);
+    else pool_tt<12, GENERIC>(sg, tables, a, lw, k);
+}
+
+// ge_batch_read_rooms_at: the packed record of batch room rooms[k] -> out[k * 12 ..] (its segment's words; the rest untouched)
+__global__ void __launch_bounds__(64) ge_pool_gather(const SegDev *__restrict__ segs, uint32_t n_seg, const uint64_t *__restrict__ rooms, uint64_t n,
+                                                      uint32_t *__restrict__ out) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const uint64_t room = rooms[k];
+    uint32_t si = 0;
+    for (uint32_t j = 1; j < n_seg; j++)
+        if (room >= segs[j].local_first) si = j;
+    const SegDev &sg = segs[si];
+    const uint64_t r = room - sg.local_first;
+    if (r >= sg.rooms) return;                                // (the host checked every room)
+    const int W = (int)sg.words;
+    for (int j = 0; j < planes_of(W); j++) {
+        const int pw = plane_words(W, j);
+        const uint32_t *plane = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(sg.base) + plane_offset(sg.rooms_padded, j));
+        for (int x = 0; x < pw; x++) out[k * 12u + 4u * (uint32_t)j + (uint32_t)x] = plane[r * (uint64_t)pw + (uint64_t)x];
+    }
+}
+
+// the device scratch of the indexed calls (shared with ge_batch_inject_actions: every user synchronises before it returns)
+int pool_scratch(ge_batch *b, size_t bytes, char **out) {
+    if (b->inj_cap < bytes) {
+        if (b->inj_buf) (void)hipFree(b->inj_buf);
+        b->inj_buf = nullptr; b->inj_cap = 0;
+        const size_t cap = bytes < 4096 ? 4096 : bytes * 2;
+        if (hipMalloc(&b->inj_buf, cap) != hipSuccess) return GE_ERR_NOMEM;
+        b->inj_cap = cap;
+    }
+    *out = static_cast<char *>(b->inj_buf);
+    return GE_OK;
+}
+
+// index of the segment holding batch room `room` (< n_rooms)
+uint32_t pool_segment_of(const ge_batch *b, uint64_t room) {
+    uint32_t si = 0;
+    for (uint32_t j = 1; j < (uint32_t)b->segs.size(); j++)
+        if (room >= b->segs[j].local_first) si = j;
+    return si;
+}
+
+template <int GEN> hipError_t pool_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const PoolArgs &a) {
+    const uint32_t lds = (kind == K_TT4) ? 0u : (uint32_t)sizeof(WaveLdsLow);
+    switch (kind) {
+    case K_WW8: hipLaunchKernelGGL((ge_pool_kernel<K_WW8, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
+    case K_WW12: hipLaunchKernelGGL((ge_pool_kernel<K_WW12, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
+    case K_TT4: hipLaunchKernelGGL((ge_pool_kernel<K_TT4, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
+    case K_TT8: hipLaunchKernelGGL((ge_pool_kernel<K_TT8, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
+    default: hipLaunchKernelGGL((ge_pool_kernel<K_TT12, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace
+
+static int step_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, ge_turn_event *events) {
+    if (n == 0) return GE_OK;
+    if (!rooms || !keys || !turns || n > 0x7FFFFFFFull) return GE_ERR_ARG;
+    for (uint64_t k = 0; k < n; k++)                              // all-or-nothing: every entry is checked before anything runs
+        if (rooms[k] >= b->n_rooms || turns[k] == 0xFFFFFFFFu) return GE_ERR_RANGE;
+    {
+        std::vector<uint64_t> sorted(rooms, rooms + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return GE_ERR_ARG;
+    }
+    GE_ON_DEVICE(b);
+    int st = sync_impl(b);
+    if (st != GE_OK) return st;
+    // stable counting sort by segment: entry order[i] goes to position i; segment s holds [begin[s], begin[s + 1])
+    const uint32_t n_seg = (uint32_t)b->segs.size();
+    std::vector<uint32_t> seg_of((size_t)n), begin(n_seg + 1u, 0u), order((size_t)n);
+    for (uint64_t k = 0; k < n; k++) { seg_of[k] = pool_segment_of(b, rooms[k]); begin[seg_of[k] + 1u]++; }
+    for (uint32_t s = 0; s < n_seg; s++) begin[s + 1u] += begin[s];
+    {
+        std::vector<uint32_t> at(begin.begin(), begin.end() - 1);
+        for (uint64_t k = 0; k < n; k++) order[at[seg_of[k]]++] = (uint32_t)k;
+    }
+    // one upload: [rooms u64 x n][keys u64 x n][turns u32 x n (padded to 16 B)], then events 16 B x n
+    const size_t off_keys = 8 * (size_t)n, off_turns = 16 * (size_t)n, off_ev = (off_turns + 4 * (size_t)n + 15u) & ~(size_t)15u;
+    const size_t total = off_ev + 16 * (size_t)n;
+    uint32_t *host32 = nullptr;
+    if ((st = io_stage(b, total, &host32)) != GE_OK) return st;
+    unsigned char *host = reinterpret_cast<unsigned char *>(host32);
+    uint64_t *h_rooms = reinterpret_cast<uint64_t *>(host), *h_keys = reinterpret_cast<uint64_t *>(host + off_keys);
+    uint32_t *h_turns = reinterpret_cast<uint32_t *>(host + off_turns);
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t k = order[i];
+        h_rooms[i] = rooms[k] - b->segs[seg_of[k]].local_first;
+        h_keys[i] = keys[k];
+        h_turns[i] = turns[k];
+    }
+    char *dev = nullptr;
+    if ((st = pool_scratch(b, total, &dev)) != GE_OK) return st;
+    hipStream_t s = b->last_stream;
+    if ((st = order_after_previous(b, s)) != GE_OK) return st;
+    HIP_TRY(hipMemcpyAsync(dev, host, off_ev, hipMemcpyHostToDevice, s));
+    const uint32_t seed_k = seed_key((uint32_t)b->seed, (uint32_t)(b->seed >> 32));
+    for (uint32_t g = 0; g < n_seg; g++) {
+        const uint32_t lo = begin[g], cnt = begin[g + 1u] - lo;
+        if (!cnt) continue;
+        PoolArgs a;
+        a.rooms = reinterpret_cast<const uint64_t *>(dev) + lo;
+        a.keys = reinterpret_cast<const uint64_t *>(dev + off_keys) + lo;
+        a.turns = reinterpret_cast<const uint32_t *>(dev + off_turns) + lo;
+        a.events = reinterpret_cast<uint32_t *>(dev + off_ev) + 4u * (size_t)lo;
+        a.n = cnt; a.seg = g; a.seed_key = seed_k;
+        a.restart = (b->flags & GE_FLAG_RESTART) ? 1u : 0u;
+        const dim3 grid((cnt + 63u) / 64u);
+        HIP_TRY(b->generic ? pool_launch<1>(b->segs[g].dev.kind, grid, s, b, a) : pool_launch<0>(b->segs[g].dev.kind, grid, s, b, a));
+    }
+    uint32_t *h_ev = reinterpret_cast<uint32_t *>(host + off_ev);
+    HIP_TRY(hipMemcpyAsync(h_ev, dev + off_ev, 16 * (size_t)n, hipMemcpyDeviceToHost, s));
+    if ((st = sync_impl(b)) != GE_OK) return st;
+    if (events) {
+        for (size_t i = 0; i < n; i++) {                          // as read_events_impl decodes the trace record
+            const uint32_t *w = h_ev + 4 * i;
+            const ge_game_table &tb = b->segs[seg_of[order[i]]].table;
+            ge_turn_event &e = events[order[i]];
+            memset(&e, 0, sizeof e);
+            e.turn = w[0];
+            e.from_phase_id = tb.rows[w[1] & 255u].phase_id;
+            e.to_phase_id = tb.rows[(w[1] >> 8) & 255u].phase_id;
+            e.restarted = (w[1] >> 16) & 1u;
+            e.acted_now = (uint16_t)(w[1] >> 20);
+            const uint64_t ch = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
+            for (int c = 0; c < 16; c++) e.choice[c] = (uint8_t)((ch >> (4 * c)) & 15u);
+        }
+    }
+    return GE_OK;
+}
+
+static int read_rooms_at_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, ge_room_view *dst) {
+    for (uint64_t k = 0; k < n; k++)
+        if (rooms[k] >= b->n_rooms) return GE_ERR_RANGE;
+    if (n == 0) return GE_OK;
+    GE_ON_DEVICE(b);
+    int st = sync_impl(b);
+    if (st != GE_OK) return st;
+    // [rooms u64 x n][records 12 words x n]
+    const size_t off_rec = 8 * (size_t)n, total = off_rec + 48 * (size_t)n;
+    uint32_t *host32 = nullptr;
+    if ((st = io_stage(b, total, &host32)) != GE_OK) return st;
+    unsigned char *host = reinterpret_cast<unsigned char *>(host32);
+    memcpy(host, rooms, 8 * (size_t)n);
+    char *dev = nullptr;
+    if ((st = pool_scratch(b, total, &dev)) != GE_OK) return st;
+    hipStream_t s = b->last_stream;
+    if ((st = order_after_previous(b, s)) != GE_OK) return st;
+    HIP_TRY(hipMemcpyAsync(dev, host, off_rec, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(ge_pool_gather, dim3((uint32_t)((n + 63u) / 64u)), dim3(64), 0, s, b->segs_dev, (uint32_t)b->segs.size(),
+                       reinterpret_cast<const uint64_t *>(dev), n, reinterpret_cast<uint32_t *>(dev + off_rec));
+    HIP_TRY(hipGetLastError());
+    const uint32_t *h_rec = reinterpret_cast<const uint32_t *>(host + off_rec);
+    HIP_TRY(hipMemcpyAsync(host + off_rec, dev + off_rec, 48 * (size_t)n, hipMemcpyDeviceToHost, s));
+    if ((st = sync_impl(b)) != GE_OK) return st;
+    for (uint64_t k = 0; k < n; k++) {
+        const Segment &sg = b->segs[pool_segment_of(b, rooms[k])];
+        uint32_t w[12] = {0};
+        for (uint32_t x = 0; x < sg.dev.words; x++) w[x] = h_rec[12 * k + x];
+        words_to_view(sg.dev.kind, w, sg.table, (int)sg.dev.n_players, dst[k]);
+    }
+    return GE_OK;
+}
+
+extern "C" {
+
+int ge_batch_step_rooms(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
+                        ge_turn_event *events) {
+    if (!b) return GE_ERR_ARG;
+    return guarded([&] { return step_rooms_impl(b, n, rooms, keys, turns, events); });
+}
+
+int ge_batch_read_rooms_at(ge_batch *b, uint64_t n, const uint64_t *rooms, ge_room_view *dst, size_t cap_bytes) {
+    if (!b || (n && (!rooms || !dst))) return GE_ERR_ARG;
+    if (cap_bytes / sizeof(ge_room_view) < n) return GE_ERR_ARG;
+    return guarded([&] { return read_rooms_at_impl(b, n, rooms, dst); });
+}
+
+}  // extern "C"

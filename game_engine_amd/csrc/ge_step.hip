@@ -1009,3 +1009,4 @@ void ge_batch_destroy(ge_batch *b) {
 }  // extern "C"
 
 #include "ge_group.inl"
+#include "ge_pool.inl"          // behind every existing kernel: indexed single-turn step and read (ge_batch_step_rooms)

@@ -440,6 +440,59 @@ napi_value ReadEvents(napi_env env, napi_callback_info info) {
     return out;
 }
 
+// stepRooms(batch, rooms: BigUint64Array, keys: BigUint64Array, turns: Uint32Array): { nTurns: 1, buffer: ArrayBuffer of
+// rooms.length ge_turn_event } (readEvents' shape) - one turn of each listed room under its own key and turn
+napi_value StepRooms(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
+    if (!b || argc < 4) return throw_status(env, GE_ERR_ARG, "stepRooms");
+    napi_typedarray_type tt[3];
+    size_t len[3];
+    void *data[3];
+    for (int k = 0; k < 3; k++) {
+        napi_value ab;
+        size_t off;
+        if (napi_get_typedarray_info(env, argv[1 + k], &tt[k], &len[k], &data[k], &ab, &off) != napi_ok)
+            return throw_status(env, GE_ERR_ARG, "stepRooms", "typed arrays expected");
+    }
+    if (tt[0] != napi_biguint64_array || tt[1] != napi_biguint64_array || tt[2] != napi_uint32_array || len[0] != len[1] || len[1] != len[2])
+        return throw_status(env, GE_ERR_ARG, "stepRooms", "BigUint64Array, BigUint64Array, Uint32Array of equal length");
+    void *ev = nullptr;
+    napi_value buf, out, v;
+    NAPI_OK(napi_create_arraybuffer(env, len[0] * sizeof(ge_turn_event), &ev, &buf));
+    const int st = ge_batch_step_rooms(b, len[0], static_cast<const uint64_t *>(data[0]), static_cast<const uint64_t *>(data[1]),
+                                       static_cast<const uint32_t *>(data[2]), static_cast<ge_turn_event *>(ev));
+    if (st != GE_OK) return throw_status(env, st, "stepRooms");
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_create_uint32(env, 1, &v));
+    NAPI_OK(napi_set_named_property(env, out, "nTurns", v));
+    NAPI_OK(napi_set_named_property(env, out, "buffer", buf));
+    return out;
+}
+
+// readRoomsAt(batch, rooms: BigUint64Array): ArrayBuffer of rooms.length ge_room_view, view k = room rooms[k]
+napi_value ReadRoomsAt(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
+    if (!b || argc < 2) return throw_status(env, GE_ERR_ARG, "readRoomsAt");
+    napi_typedarray_type tt;
+    size_t len, off;
+    void *rooms = nullptr;
+    napi_value ab;
+    if (napi_get_typedarray_info(env, argv[1], &tt, &len, &rooms, &ab, &off) != napi_ok || tt != napi_biguint64_array)
+        return throw_status(env, GE_ERR_ARG, "readRoomsAt", "BigUint64Array expected");
+    void *data = nullptr;
+    napi_value buf;
+    NAPI_OK(napi_create_arraybuffer(env, len * sizeof(ge_room_view), &data, &buf));
+    int st = ge_batch_read_rooms_at(b, len, static_cast<const uint64_t *>(rooms), static_cast<ge_room_view *>(data), len * sizeof(ge_room_view));
+    if (st != GE_OK) return throw_status(env, st, "readRoomsAt");
+    return buf;
+}
+
 // summary(batch): BigUint64Array-compatible ArrayBuffer of ge_summary words
 napi_value Summary(napi_env env, napi_callback_info info) {
     size_t argc = 1;
@@ -661,6 +714,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"writeRooms", nullptr, WriteRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"destroyBatch", nullptr, DestroyBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"readEvents", nullptr, ReadEvents, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"stepRooms", nullptr, StepRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"readRoomsAt", nullptr, ReadRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"summary", nullptr, Summary, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"reset", nullptr, Reset, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"deviceCount", nullptr, DeviceCount, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -66,6 +66,11 @@ export class RoomBatch {
   readRoom(room: number): RoomState;
   readRooms(first: number, count: number): RoomState[];
   readEvents(first: number, count: number): TurnEvent[][];
+  /** One turn of each listed room (local, pairwise distinct), room k keyed as global room keys[k] at turn turns[k]; event k of room k. */
+  stepRooms(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>): TurnEvent[];
+  /** out[k] = room rooms[k] (any order, repeats allowed). */
+  readRoomsAt(rooms: ArrayLike<number | bigint>): RoomState[];
+  readRoomsAtRaw(rooms: ArrayLike<number | bigint>): ArrayBuffer;
   summary(): Summary;
 }
 /** One Node process, several GPUs: device d owns the global rooms [firstRoom + d*R, firstRoom + (d+1)*R). */

@@ -296,6 +296,12 @@ class RoomLog {
   }
 }
 
+function decodeEvent(buffer, off) {
+  const dv = new DataView(buffer, off, EVENT_SIZE);
+  return { turn: dv.getUint32(0, true), from_phase_id: dv.getInt32(4, true), to_phase_id: dv.getInt32(8, true),
+           acted_now: dv.getUint16(12, true), restarted: dv.getUint8(14), choice: Array.from(new Uint8Array(buffer, off + 16, 16)) };
+}
+
 class RoomBatch {
   /** segments: [{table: GameTable, nPlayers, nRooms}] */
   constructor({ segments, seed = 0n, firstRoom = 0n, device = 0, maxFuse = 0, restart = false, trace = false }) {
@@ -355,16 +361,27 @@ class RoomBatch {
     const out = [];
     for (let r = 0; r < count; r++) {
       const row = [];
-      for (let t = 0; t < nTurns; t++) {
-        const off = (r * nTurns + t) * EVENT_SIZE;
-        const dv = new DataView(buffer, off, EVENT_SIZE);
-        row.push({ turn: dv.getUint32(0, true), from_phase_id: dv.getInt32(4, true), to_phase_id: dv.getInt32(8, true),
-                   acted_now: dv.getUint16(12, true), restarted: dv.getUint8(14), choice: Array.from(new Uint8Array(buffer, off + 16, 16)) });
-      }
+      for (let t = 0; t < nTurns; t++) row.push(decodeEvent(buffer, (r * nTurns + t) * EVENT_SIZE));
       out.push(row);
     }
     return out;
   }
+  /** One turn of each listed room (local indices, pairwise distinct), room k keyed as global room keys[k] at turn turns[k]
+   * (what a lone batch with firstRoom = keys[k] and turn counter turns[k] does to it in one step); the batch's turn counter,
+   * its trace and every unlisted room are untouched.  Returns event k of room k (readEvents' event shape).  Synchronous. */
+  stepRooms(rooms, keys, turns) {
+    const { buffer } = addon.stepRooms(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r)), BigUint64Array.from(keys, (k) => BigInt(k)),
+                                       Uint32Array.from(turns));
+    const out = [];
+    for (let k = 0; k < rooms.length; k++) out.push(decodeEvent(buffer, k * EVENT_SIZE));
+    return out;
+  }
+  /** The listed rooms' states, out[k] = room rooms[k] (any order, repeats allowed). */
+  readRoomsAt(rooms) {
+    const buf = this.readRoomsAtRaw(rooms);
+    return Array.from(rooms, (r, k) => decodeRoom(this.tableOf(Number(r)), buf, k * VIEW.size));
+  }
+  readRoomsAtRaw(rooms) { return addon.readRoomsAt(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r))); }
   summary() { return decodeSummary(addon.summary(this.handle)); }
 }
 
@@ -491,5 +508,5 @@ class DeviceGroup {
 
 const { compileCriteria, audienceGroups, uiToolCalls } = require('./ui_script.js');
 
-module.exports = { GameTable, RoomBatch, ShardedBatch, DeviceGroup, locateInShards, RoomLog, formatNote, loadDslByGamename, findGameFile, initializePlayers, turnToolCalls, compileCriteria, audienceGroups, uiToolCalls,
+module.exports = { GameTable, RoomBatch, decodeRoom, ShardedBatch, DeviceGroup, locateInShards, RoomLog, formatNote, loadDslByGamename, findGameFile, initializePlayers, turnToolCalls, compileCriteria, audienceGroups, uiToolCalls,
                    deviceCount: addon.deviceCount, addon };

@@ -1,0 +1,18 @@
+// Types for room_pool.js — many game threads hosted in a few resident batches.
+import { AgentStateView, RoomPlayer, TurnResult } from './room_service';
+
+export type MessageResult = TurnResult & { played: boolean; kind: 'chat' | 'control' | 'action' };
+export class RoomPoolService {
+  /** chunkRooms: slots per batch chunk of a pool (one pool per game, player count and human seats) */
+  constructor(opts?: { gamesDir?: string; seed?: bigint | number; device?: number; chunkRooms?: number });
+  /** As RoomService.createRoom: the thread's RNG is keyed by roomIndex (default: hash of the thread id), its turn counter starts at 0. */
+  createRoom(opts: { threadId: string; gameName: string; players: RoomPlayer[]; dsl?: object; roomIndex?: number | bigint }): AgentStateView;
+  humanAction(threadId: string, playerId: number, choice: number): Promise<AgentStateView>;
+  continueRoom(threadId: string, items?: { id: string; type: string }[]): Promise<TurnResult>;
+  handleMessage(threadId: string, text: string, items?: { id: string; type: string }[]): Promise<MessageResult>;
+  /** One tick for many threads (each at most once): per chunk touched one stepRooms and one readRoomsAt; outputs in input order. */
+  handleMessages(msgs: [string, string, { id: string; type: string }[]?][]): Promise<MessageResult[]>;
+  /** Forget a thread (its slot is reused); without an id, every thread and every chunk's device memory. */
+  close(threadId?: string): Promise<boolean>;
+}
+export function roomIndexOf(threadId: string): bigint;

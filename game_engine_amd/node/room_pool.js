@@ -1,0 +1,187 @@
+'use strict';
+/**
+ * RoomPoolService — many game threads hosted in a few resident batches (twin of game_engine_amd/room_pool.py).
+ *
+ * RoomService gives every thread its own N = 1 batch and pays about three synchronising calls per message.  Here threads of
+ * the same (game, player count, human seats) share a pool of fixed-capacity batch chunks, a thread owning one slot.  Its RNG
+ * stream is keyed by roomIndexOf(threadId) (or the roomIndex it was created with) and its turn counter is its own, so a thread
+ * plays exactly the game it plays on a RoomService: RoomBatch.stepRooms moves a slot by one turn keyed as that global room at
+ * that turn.  handleMessages is one tick for many threads: per chunk touched, one injection round per candidate seat, one
+ * stepRooms and one readRoomsAt.  The chunks are shared, so every call of the service runs strictly one after the other.
+ */
+const { GameTable, RoomBatch, RoomLog, decodeRoom, turnToolCalls, uiToolCalls } = require('./index.js');
+const { roomIndexOf } = require('./room_service.js');
+const M = require('./messages.js');
+
+const GE_ERR_ARG = -1;
+
+class RoomPoolService {
+  constructor({ gamesDir = 'games', seed = 0n, device = 0, chunkRooms = 1024 } = {}) {
+    if (!(chunkRooms >= 1)) throw new RangeError('chunkRooms must be >= 1');
+    this.gamesDir = gamesDir; this.seed = BigInt(seed); this.device = device; this.chunkRooms = chunkRooms;
+    this.tables = new Map();       // gameName -> GameTable
+    this.pools = new Map();        // `${gameName}/${nPlayers}/${humanMask}` -> { table, nPlayers, humanMask, chunks, free, used, templateRaw }
+    this.rooms = new Map();        // threadId -> { pool, chunk, ci, slot, key, turn, table, gameName, names, humanSeats, panel, state, log }
+    this.queue = Promise.resolve();
+  }
+  table(gameName, dsl) {
+    if (!this.tables.has(gameName)) this.tables.set(gameName, dsl ? new GameTable(dsl) : GameTable.fromGamename(gameName, this.gamesDir));
+    return this.tables.get(gameName);
+  }
+  _serial(fn) {
+    const p = this.queue.then(fn);
+    this.queue = p.catch(() => {});
+    return p;
+  }
+  _acquire(pool) {
+    if (pool.free.length === 0) {
+      const ci = pool.chunks.length;
+      const chunk = new RoomBatch({ segments: [{ table: pool.table, nPlayers: pool.nPlayers, nRooms: this.chunkRooms, humanMask: pool.humanMask }],
+                                    seed: this.seed, firstRoom: 0n, device: this.device, maxFuse: 1 });
+      pool.chunks.push(chunk);
+      if (!pool.templateRaw) pool.templateRaw = chunk.readRoomsAtRaw([0]);
+      for (let s = this.chunkRooms - 1; s >= 0; s--) pool.free.push([ci, s]);
+    }
+    const [ci, slot] = pool.free.pop();
+    const chunk = pool.chunks[ci];
+    const id = `${ci}/${slot}`;
+    if (pool.used.has(id)) chunk.writeRoomsRaw(slot, pool.templateRaw);   // a reused slot starts from the template (no prepared deal)
+    pool.used.add(id);
+    return { chunk, ci, slot };
+  }
+  /** As RoomService.createRoom: players[i].isBot === false marks a human seat; roomIndex = the global room index the RNG is keyed by. */
+  createRoom({ threadId, gameName, players, dsl, roomIndex }) {
+    const table = this.table(gameName, dsl);
+    const humanMask = players.reduce((m, p, i) => (p.isBot === false ? m | (1 << i) : m), 0);
+    if (this.rooms.has(threadId)) this._release(threadId);
+    const pk = `${gameName}/${players.length}/${humanMask}`;
+    if (!this.pools.has(pk)) this.pools.set(pk, { table, nPlayers: players.length, humanMask, chunks: [], free: [], used: new Set(), templateRaw: null });
+    const pool = this.pools.get(pk);
+    const { chunk, ci, slot } = this._acquire(pool);
+    const names = players.map((p, i) => p.name || `Player ${i + 1}`);
+    const humanSeats = players.map((p, i) => (p.isBot === false ? i + 1 : 0)).filter((x) => x);
+    const room = { pool, chunk, ci, slot, key: roomIndex === undefined ? roomIndexOf(threadId) : BigInt(roomIndex), turn: 0,
+                   table, gameName, names, humanSeats, panel: null, state: decodeRoom(table, pool.templateRaw, 0), log: new RoomLog(table, names, gameName) };
+    this.rooms.set(threadId, room);
+    return this.agentState(room);
+  }
+  agentState(room) { return room.log.agentState(room.state); }
+  _room(threadId) {
+    const room = this.rooms.get(threadId);
+    if (!room) throw new Error(`unknown thread ${threadId}`);
+    return room;
+  }
+  humanAction(threadId, playerId, choice) {
+    return this._serial(() => {
+      const room = this._room(threadId);
+      const st = room.chunk.injectActions([room.slot], [playerId], [choice]);
+      if (st[0] !== 0) { const e = new Error(`injectAction: status ${st[0]}`); e.code = `GE${st[0]}`; throw e; }
+      room.state = room.chunk.readRoomsAt([room.slot])[0];
+      return this.agentState(room);
+    });
+  }
+  continueRoom(threadId, items) {
+    return this._serial(() => this._turns([this._room(threadId)], [items])[0]);
+  }
+  handleMessage(threadId, text, items) {
+    return this.handleMessages([[threadId, text, items]]).then((o) => o[0]);
+  }
+  /** One tick: [[threadId, text, items?], ...] -> [output, ...] in the same order, each what handleMessage resolves for it.
+   * A thread may appear once per tick (rejected before anything runs otherwise). */
+  handleMessages(msgs) {
+    return this._serial(() => {
+      const seen = new Set();
+      const entries = msgs.map(([tid, text, items]) => {
+        if (seen.has(tid)) throw new Error(`thread ${tid} is named twice in one tick`);
+        seen.add(tid);
+        return { room: this._room(tid), text, items };
+      });
+      const out = new Array(entries.length).fill(null);
+      const play = [];
+      let pending = [];
+      entries.forEach((e, i) => {
+        const kind = M.classify(e.text);
+        if (kind === M.CHAT) { out[i] = { state: this.agentState(e.room), toolCalls: [], uiCalls: [], played: false, kind }; return; }
+        play.push([i, kind]);
+        if (kind === M.ACTION) {
+          const room = e.room;
+          room.log.personMessage(e.text);
+          const st = room.state, info = room.table.info;
+          const phase = info.phases.find((x) => x.id === st.current_phase_id);
+          const alive = st.slots.map((v) => (st.pack === 1 ? !!v[2] : true));
+          const cands = M.resolve(e.text, room.panel, phase ? phase.act : 0, st.pack, room.names, alive, room.humanSeats);
+          if (cands.length) pending.push([i, cands]);
+        }
+      });
+      // injection rounds: a thread's next candidate seat only where the previous one was refused with GE_ERR_ARG (RoomService's loop)
+      for (let r = 0; pending.length; r++) {
+        const byChunk = new Map();
+        for (const p of pending) {
+          const c = entries[p[0]].room.chunk;
+          if (!byChunk.has(c)) byChunk.set(c, []);
+          byChunk.get(c).push(p);
+        }
+        const next = [];
+        for (const [chunk, group] of byChunk) {
+          const st = chunk.injectActions(group.map(([i]) => entries[i].room.slot), group.map(([, c]) => c[r][0]), group.map(([, c]) => c[r][1]));
+          group.forEach((p, k) => {
+            if (st[k] === 0) return;
+            if (st[k] !== GE_ERR_ARG) { const e = new Error(`injectActions: status ${st[k]}`); e.code = `GE${st[k]}`; throw e; }
+            if (r + 1 < p[1].length) next.push(p);
+          });
+        }
+        pending = next;
+      }
+      const res = this._turns(play.map(([i]) => entries[i].room), play.map(([i]) => entries[i].items));
+      play.forEach(([i, kind], k) => { out[i] = Object.assign(res[k], { played: true, kind }); });
+      return out;
+    });
+  }
+  /** One turn of each room (distinct threads): one stepRooms and one readRoomsAt per chunk touched. */
+  _turns(rooms, items) {
+    const byChunk = new Map();
+    rooms.forEach((room, j) => {
+      if (!byChunk.has(room.chunk)) byChunk.set(room.chunk, []);
+      byChunk.get(room.chunk).push(j);
+    });
+    const events = new Array(rooms.length), afters = new Array(rooms.length);
+    for (const [chunk, js] of byChunk) {
+      const slots = js.map((j) => rooms[j].slot);
+      const ev = chunk.stepRooms(slots, js.map((j) => rooms[j].key), js.map((j) => rooms[j].turn));
+      const views = chunk.readRoomsAt(slots);
+      js.forEach((j, k) => { events[j] = ev[k]; afters[j] = views[k]; rooms[j].turn += 1; });
+    }
+    return rooms.map((room, j) => this._finish(room, afters[j], events[j], items[j]));
+  }
+  _finish(room, after, event, items) {
+    // as RoomService._continue: `before` is the state before any action injected with this message
+    const before = room.state;
+    const toolCalls = turnToolCalls(room.table, before, after, event);
+    room.log.fold(toolCalls, after);
+    room.state = after;
+    const state = this.agentState(room);
+    const deaths = toolCalls.filter((c) => c.name === 'update_player_state' && c.args.state_name === 'is_alive' && c.args.state_value === false).map((c) => c.args.player_id);
+    const uiCalls = uiToolCalls(room.table.dsl, state, { table: room.table, turn: event.turn, deaths, items });
+    room.panel = M.newestPanel(uiCalls);
+    return { state, toolCalls, uiCalls };
+  }
+  _release(threadId) {
+    const room = this.rooms.get(threadId);
+    if (!room) return false;
+    this.rooms.delete(threadId);
+    room.pool.free.push([room.ci, room.slot]);
+    return true;
+  }
+  /** Forget a thread (its slot goes back to the pool); without an id, every thread and every chunk's device memory. */
+  close(threadId) {
+    return this._serial(() => {
+      if (threadId !== undefined) return this._release(threadId);
+      this.rooms.clear();
+      for (const pool of this.pools.values()) for (const c of pool.chunks) c.close();
+      this.pools.clear();
+      return true;
+    });
+  }
+}
+
+module.exports = { RoomPoolService, roomIndexOf };

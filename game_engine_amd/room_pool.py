@@ -1,0 +1,208 @@
+"""RoomPoolService — many game threads hosted in a few resident batches (twin of node/room_pool.js).
+
+RoomService gives every thread its own N = 1 batch: its own device allocations, table upload and staging buffers, and
+per message one launch, one read of the room, one read of the events and a synchronisation for each.  Here threads of the
+same (game, player count, human seats) share a pool of fixed-capacity batch chunks; a thread owns one slot of one chunk.
+Its RNG stream is keyed by `room_index_of(thread_id)` (or the `room_index` it was created with) and its turn counter is its
+own, so a thread plays exactly the game it plays on a RoomService: `RoomBatch.step_rooms` moves a slot by one turn keyed
+as that global room at that turn.  `handle_messages` is one tick for many threads: per chunk touched, one injection round
+per candidate seat, one `step_rooms` and one `read_rooms_at` - against about three synchronising calls per message.
+
+Same per-thread API and outputs as RoomService (create_room / human_action / continue_room / handle_message / close).
+"""
+from __future__ import annotations
+
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import messages as M
+from .room_service import room_index_of
+from .stepper import GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, load_dsl_by_gamename, slot_values
+from .toolcalls import WW_IS_ALIVE, RoomLog, turn_tool_calls
+from .ui_script import ui_tool_calls
+
+
+class _Pool:
+    """The chunks of one (game, n_players, human_mask) and their free slots."""
+
+    def __init__(self, table: GameTable, n_players: int, human_mask: int):
+        self.table, self.n_players, self.human_mask = table, n_players, human_mask
+        self.chunks: List[Any] = []
+        self.free: List[Tuple[int, int]] = []      # (chunk, slot), popped from the end
+        self.used: set = set()                     # slots a thread has held: written back to the template when reused
+        self.template = None                       # the initial room view (player_states_template, phase 0)
+
+
+class RoomPoolService:
+    def __init__(self, games_dir: str = "games", seed: int = 0, device: int = 0, chunk_rooms: int = 1024):
+        if chunk_rooms < 1:
+            raise ValueError("chunk_rooms must be >= 1")
+        self.games_dir, self.seed, self.device, self.chunk_rooms = games_dir, seed, device, chunk_rooms
+        self._tables: Dict[str, GameTable] = {}
+        self._pools: Dict[Tuple[str, int, int], _Pool] = {}
+        self._rooms: Dict[str, Dict[str, Any]] = {}
+
+    def table(self, game_name: str, dsl: Optional[dict] = None) -> GameTable:
+        if game_name not in self._tables:
+            self._tables[game_name] = GameTable(dsl if dsl else load_dsl_by_gamename(game_name, self.games_dir))
+        return self._tables[game_name]
+
+    def _new_chunk(self, tb: GameTable, n_players: int, human_mask: int, n_rooms: int):
+        """One chunk of a pool: an untraced batch whose slots are stepped only through step_rooms (the device is required)."""
+        return RoomBatch([(tb, n_players, n_rooms, human_mask)], seed=self.seed, first_room=0, device=self.device, max_fuse=1)
+
+    # ---- slots
+    def _acquire(self, pool: _Pool) -> Tuple[Any, int, int]:
+        if not pool.free:
+            ci = len(pool.chunks)
+            chunk = self._new_chunk(pool.table, pool.n_players, pool.human_mask, self.chunk_rooms)
+            pool.chunks.append(chunk)
+            if pool.template is None:
+                pool.template = chunk.read_rooms_at([0])[0].copy()
+            pool.free.extend((ci, s) for s in reversed(range(self.chunk_rooms)))
+        ci, slot = pool.free.pop()
+        chunk = pool.chunks[ci]
+        if (ci, slot) in pool.used:               # a reused slot starts from the template (which also drops any prepared deal)
+            chunk.write_rooms(slot, np.array([pool.template], dtype=pool.template.dtype))
+        pool.used.add((ci, slot))
+        return chunk, ci, slot
+
+    def create_room(self, thread_id: str, game_name: str, players: List[Dict[str, Any]], dsl: Optional[dict] = None,
+                    room_index: Optional[int] = None) -> Dict[str, Any]:
+        """As RoomService.create_room: `isBot: False` marks a human seat; room_index = the global room index the thread's RNG
+        is keyed by (default: derived from the thread id)."""
+        tb = self.table(game_name, dsl)
+        human_mask = sum(1 << i for i, p in enumerate(players) if p.get("isBot") is False)
+        if thread_id in self._rooms:
+            self.close(thread_id)
+        key = (game_name, len(players), human_mask)
+        pool = self._pools.get(key)
+        if pool is None:
+            pool = self._pools[key] = _Pool(tb, len(players), human_mask)
+        chunk, ci, slot = self._acquire(pool)
+        names = [p.get("name") or f"Player {i + 1}" for i, p in enumerate(players)]
+        room = {"pool": pool, "chunk": chunk, "ci": ci, "slot": slot, "turn": 0,
+                "key": room_index_of(thread_id) if room_index is None else int(room_index),
+                "table": tb, "gameName": game_name, "names": names, "panel": None,
+                "human_seats": [i + 1 for i in range(len(players)) if (human_mask >> i) & 1],
+                "view": pool.template.copy(), "log": RoomLog(tb, names, game_name)}
+        self._rooms[thread_id] = room
+        return self._agent_state(room)
+
+    def _agent_state(self, room: Dict[str, Any]) -> Dict[str, Any]:
+        return room["log"].agent_state(room["view"])
+
+    def human_action(self, thread_id: str, player_id: int, choice: int) -> Dict[str, Any]:
+        room = self._rooms[thread_id]
+        st = room["chunk"].inject_actions([room["slot"]], [player_id], [choice])
+        if int(st[0]) != 0:
+            raise GeError(int(st[0]), "ge_batch_inject_actions")
+        room["view"] = room["chunk"].read_rooms_at([room["slot"]])[0]
+        return self._agent_state(room)
+
+    def continue_room(self, thread_id: str, items: Optional[List[Dict[str, Any]]] = None) -> Dict[str, Any]:
+        """One turn of one thread: {"state", "toolCalls", "uiCalls"}, as RoomService.continue_room."""
+        room = self._rooms[thread_id]
+        return self._turns([room], [items])[0]
+
+    def handle_message(self, thread_id: str, text: str, items: Optional[List[Dict[str, Any]]] = None) -> Dict[str, Any]:
+        """As RoomService.handle_message (one message of one thread)."""
+        return self.handle_messages([(thread_id, text, items)])[0]
+
+    def handle_messages(self, msgs: Sequence[Tuple]) -> List[Dict[str, Any]]:
+        """One tick: [(thread_id, text[, items]), ...] -> [output, ...] in the same order, each what handle_message returns
+        for it.  A thread may appear once per tick (ValueError otherwise, before anything runs)."""
+        entries = []
+        seen = set()
+        for m in msgs:
+            tid, text, items = m[0], m[1], (m[2] if len(m) > 2 else None)
+            if tid in seen:
+                raise ValueError(f"thread {tid!r} is named twice in one tick")
+            seen.add(tid)
+            entries.append((self._rooms[tid], text, items))       # KeyError for an unknown thread, before anything runs
+        out: List[Optional[Dict[str, Any]]] = [None] * len(entries)
+        play, pending = [], []                                  # indices into entries; (index, candidates) of action messages
+        for i, (room, text, _) in enumerate(entries):
+            kind = M.classify(text)
+            if kind == M.CHAT:
+                out[i] = {"state": self._agent_state(room), "toolCalls": [], "uiCalls": [], "played": False, "kind": kind}
+                continue
+            play.append((i, kind))
+            if kind == M.ACTION:
+                room["log"].person_message(text)
+                view, tb = room["view"], room["table"]
+                n = int(view["n_players"])
+                pid = int(view["phase_id"])
+                act = next((r["act"] for r in tb.rows() if r["phase_id"] == pid), 0)
+                alive = [bool(slot_values(tb, view, j)[WW_IS_ALIVE]) for j in range(n)] if tb.pack == PACK_WEREWOLF else [True] * n
+                cands = list(M.resolve(text, room["panel"], act, tb.pack, room["names"], alive, room["human_seats"]))
+                if cands:
+                    pending.append((i, cands))
+        # injection rounds: a thread's next candidate seat is tried only where the previous one was refused with GE_ERR_ARG
+        # (not a living pending target of this phase: logged, no game effect), as RoomService.handle_message's loop
+        r = 0
+        while pending:
+            by_chunk: Dict[int, List[Tuple[int, List]]] = {}
+            for i, cands in pending:
+                by_chunk.setdefault(id(entries[i][0]["chunk"]), []).append((i, cands))
+            nxt = []
+            for group in by_chunk.values():
+                chunk = entries[group[0][0]][0]["chunk"]
+                st = chunk.inject_actions([entries[i][0]["slot"] for i, _ in group], [c[r][0] for _, c in group],
+                                          [c[r][1] for _, c in group])
+                for (i, cands), s in zip(group, st):
+                    if int(s) == 0:
+                        continue
+                    if int(s) != GE_ERR_ARG:
+                        raise GeError(int(s), "ge_batch_inject_actions")
+                    if r + 1 < len(cands):
+                        nxt.append((i, cands))
+            pending, r = nxt, r + 1
+        res = self._turns([entries[i][0] for i, _ in play], [entries[i][2] for i, _ in play])
+        for (i, kind), o in zip(play, res):
+            o.update(played=True, kind=kind)
+            out[i] = o
+        return out
+
+    def _turns(self, rooms: List[Dict[str, Any]], items: List[Optional[List[Dict[str, Any]]]]) -> List[Dict[str, Any]]:
+        """One turn of each room (distinct threads): one step_rooms and one read_rooms_at per chunk touched."""
+        by_chunk: Dict[int, List[int]] = {}
+        for j, room in enumerate(rooms):
+            by_chunk.setdefault(id(room["chunk"]), []).append(j)
+        events, afters = [None] * len(rooms), [None] * len(rooms)
+        for js in by_chunk.values():
+            chunk = rooms[js[0]]["chunk"]
+            slots = np.array([rooms[j]["slot"] for j in js], dtype=np.uint64)
+            ev = chunk.step_rooms(slots, np.array([rooms[j]["key"] for j in js], dtype=np.uint64),
+                                  np.array([rooms[j]["turn"] for j in js], dtype=np.uint32))
+            views = chunk.read_rooms_at(slots)
+            for k, j in enumerate(js):
+                events[j], afters[j] = ev[k], views[k]
+                rooms[j]["turn"] += 1
+        return [self._finish(room, afters[j], events[j], items[j]) for j, room in enumerate(rooms)]
+
+    def _finish(self, room: Dict[str, Any], after, event, items) -> Dict[str, Any]:
+        # as RoomService._turn: `before` is the view before any action injected with this message
+        before = room["view"]
+        calls = turn_tool_calls(room["table"], before, after, event)
+        room["log"].fold(calls, after)
+        room["view"] = after
+        state = self._agent_state(room)
+        deaths = [c["args"]["player_id"] for c in calls if c["name"] == "update_player_state"
+                  and c["args"]["state_name"] == "is_alive" and c["args"]["state_value"] is False]
+        ui = ui_tool_calls(room["table"].dsl, state, room["table"], turn=int(event["turn"]), deaths=deaths, items=items)
+        room["panel"] = M.newest_panel(ui)
+        return {"state": state, "toolCalls": calls, "uiCalls": ui}
+
+    def close(self, thread_id: Optional[str] = None):
+        """Close one thread (its slot goes back to the pool's free list) or, without an id, every thread and every chunk."""
+        if thread_id is not None:
+            room = self._rooms.pop(thread_id)
+            room["pool"].free.append((room["ci"], room["slot"]))
+            return
+        self._rooms.clear()
+        for pool in self._pools.values():
+            for chunk in pool.chunks:
+                chunk.close()
+        self._pools.clear()

@@ -272,6 +272,29 @@ class RoomBatch:
                "ge_batch_read_events")
         return out[:, : n.value]
 
+    def step_rooms(self, rooms, keys, turns) -> np.ndarray:
+        """One turn of each listed room (local indices, pairwise distinct), room k keyed as global room keys[k] at turn
+        turns[k]: what a lone batch with first_room = keys[k] and turn counter turns[k] does to it in one step(1).  The
+        batch's turn counter, its trace and every unlisted room are untouched.  Returns event k of room k (EVENT_DTYPE).
+        All-or-nothing: a room outside the batch, turn 0xFFFFFFFF or a repeated room raises and steps nothing."""
+        rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        turns = np.ascontiguousarray(turns, dtype=np.uint32)
+        if not (len(rooms) == len(keys) == len(turns)):
+            raise GeError(-1, "step_rooms: arrays differ in length")
+        out = np.zeros(len(rooms), dtype=EVENT_DTYPE)
+        _check(self._lib.ge_batch_step_rooms(self._h, len(rooms), rooms.ctypes.data, keys.ctypes.data, turns.ctypes.data,
+                                             out.ctypes.data), "ge_batch_step_rooms")
+        return out
+
+    def read_rooms_at(self, rooms) -> np.ndarray:
+        """Canonical views of the listed rooms, out[k] = room rooms[k] (any order, repeats allowed)."""
+        rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
+        out = np.empty(len(rooms), dtype=ROOM_VIEW_DTYPE)        # the library writes every byte of every view
+        _check(self._lib.ge_batch_read_rooms_at(self._h, len(rooms), rooms.ctypes.data, out.ctypes.data, out.nbytes),
+               "ge_batch_read_rooms_at")
+        return out
+
     def summary(self) -> Dict[str, Any]:
         s = _lib.Summary()
         _check(self._lib.ge_batch_summary(self._h, C.byref(s)), "ge_batch_summary")

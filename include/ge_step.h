@@ -37,7 +37,9 @@ extern "C" {
  *      `pack` / player count is not the segment's or whose phase ids name no row of its table (until then unknown ids were
  *      silently stored as row 0) - a caller that zero-initialises views must set `pack`
  *   5  ge_group_partition + ge_batch_create_shard (the group's sharding arithmetic for hosts that place shards themselves); ge_last_rejected_room;
- *      mixed and generic batches get single-turn kernel builds; the Werewolf x 12 deal side plane is allocated on first use */
+ *      mixed and generic batches get single-turn kernel builds; the Werewolf x 12 deal side plane is allocated on first use;
+ *      later additions, new symbols only (the version stays 5): ge_batch_step_rooms + ge_batch_read_rooms_at (many game threads
+ *      in one resident batch, each room stepped under its own key and turn) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -294,6 +296,20 @@ int ge_batch_inject_action(ge_batch *b, uint64_t room, uint32_t player_id, uint3
  * status of the first refused one.  Synchronises. */
 int ge_batch_inject_actions(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint32_t *player_ids,
                             const uint32_t *choices, int32_t *status);
+
+/* One turn of each listed room, room k keyed as global room keys[k] at turn turns[k] (what a lone batch with
+ * first_room = keys[k] and turn counter turns[k] would do to that room in one ge_batch_step(b, 1)).  rooms[] are local
+ * indices, pairwise distinct.  Unlisted rooms, the batch's turn counter and its GE_FLAG_TRACE buffer are untouched.
+ * events (may be NULL) receives event k of room k.  All-or-nothing: GE_ERR_RANGE for a room outside the batch or
+ * turns[k] == 0xFFFFFFFF, GE_ERR_ARG for a repeated room; nothing is stepped then.  n == 0: GE_OK.  Synchronises.
+ * The batch's segment flags apply (human mask, GE_FLAG_RESTART, generic conditions).  A stepped record is stored without a
+ * prepared role deal (as ge_batch_write_rooms stores one), so ordinary ge_batch_step calls before and after stay exact. */
+int ge_batch_step_rooms(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
+                        ge_turn_event *events);
+/* Canonical views of the listed rooms, dst[k] = room rooms[k] (any order, repeats allowed): a device gather of the packed
+ * records into the staging buffer, one copy, host-side unpacking as in ge_batch_read_rooms.  GE_ERR_RANGE for a room
+ * outside the batch.  cap_bytes >= n * sizeof(ge_room_view).  Synchronises. */
+int ge_batch_read_rooms_at(ge_batch *b, uint64_t n, const uint64_t *rooms, ge_room_view *dst, size_t cap_bytes);
 
 /* GE_FLAG_TRACE: events of the most recent ge_batch_step call, dst[(room - first) * *n_turns + t].
  * cap_bytes >= count * n_turns * sizeof(ge_turn_event).  Synchronises. */

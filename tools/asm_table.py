@@ -33,6 +33,9 @@ def describe(mangled: str) -> dict:
     if m:
         return {"kernel": "ge_step_kernel", "layout": KINDS[int(m.group(1))], "lowocc": m.group(2) == "1", "generic": int(m.group(3)),
                 "single": m.group(4) == "1", "ld": int(m.group(5))}
+    m = re.search(r"ge_pool_kernelILi(\d)ELi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_pool_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True}
     m = re.search(r"N_1\d+(ge_[a-z_0-9]+?)E", mangled)
     return {"kernel": m.group(1) if m else mangled, "layout": "-", "lowocc": False, "generic": False, "single": False}
 
@@ -59,6 +62,8 @@ def collect(rebuild=True):
 
 
 def label(r):
+    if r["kernel"] == "ge_pool_kernel":                          # ge_batch_step_rooms: one launch per segment present
+        return f"{r['layout']}, indexed single-turn (ge_batch_step_rooms)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] not in ("ge_step_kernel", "ge_step_kernel_mixed"):
         return r["kernel"]
     form = "single-turn" if r["single"] else "fused"
