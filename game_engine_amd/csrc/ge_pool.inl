@@ -1,6 +1,7 @@
-// ge_pool.inl — the indexed single-turn step (ge_batch_step_rooms) and the indexed read (ge_batch_read_rooms_at): many game
-// threads hosted in one resident batch, each slot stepped under its own RNG key and turn number (included at the end of
-// ge_step.hip, behind every other kernel: the existing kernels keep their code-object offsets; it needs ge_batch's internals).
+// ge_pool.inl — the indexed single-turn step (ge_batch_step_rooms), the indexed read (ge_batch_read_rooms_at) and the indexed
+// write (ge_batch_write_rooms_at): many game threads hosted in one resident batch, each slot stepped under its own RNG key and
+// turn number (included at the end of ge_step.hip, behind every other kernel: the existing kernels keep their code-object
+// offsets; it needs ge_batch's internals).
 //
 // The reference runs one LangGraph thread per room and a thread plays a turn only when its own message arrives
 // (src/app/api/copilotkit/route.ts:24-37).  ge_batch_step moves every room under one batch-wide turn counter; here a list of
@@ -21,6 +22,12 @@
 //
 // Mixed batches: entries are grouped by segment on the host (a stable counting sort) and each segment present gets one launch of
 // its layout's kernel - a wavefront never mixes layouts (the action queue is a wave-wide collective).
+//
+// The indexed write (ge_batch_write_rooms_at) is the scatter twin of the indexed read: a thread adopted mid-game into a slot of a
+// resident batch.  The host packs each view with view_to_words - the record ge_batch_write_rooms stores for it, without a prepared
+// deal (Werewolf x 8: word 7's upper half is 0) - and ge_pool_scatter stores it plane by plane.  The Werewolf x 12 side plane is not
+// touched, as ge_batch_write_rooms does not touch it: a deal there is a function of the slot's own key and the game index alone, so
+// it stays right for whatever record is written over the slot.
 
 namespace {
 
@@ -161,6 +168,36 @@ __global__ void __launch_bounds__(64) ge_pool_gather(const SegDev *__restrict__ 
         const int pw = plane_words(W, j);
         const uint32_t *plane = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(sg.base) + plane_offset(sg.rooms_padded, j));
         for (int x = 0; x < pw; x++) out[k * 12u + 4u * (uint32_t)j + (uint32_t)x] = plane[r * (uint64_t)pw + (uint64_t)x];
+    }
+}
+
+// ge_batch_write_rooms_at: the packed record src[k * 12 ..] (12 words, 16-byte aligned; its segment's words used) -> batch room
+// rooms[k], plane by plane: a 4-word plane is one 16-byte store, the 2-word last plane of a 6- or 10-word layout one 8-byte store
+__global__ void __launch_bounds__(64) ge_pool_scatter(const SegDev *__restrict__ segs, uint32_t n_seg, const uint64_t *__restrict__ rooms, uint64_t n,
+                                                       const uint32_t *__restrict__ src) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const uint64_t room = rooms[k];
+    uint32_t si = 0;
+    for (uint32_t j = 1; j < n_seg; j++)
+        if (room >= segs[j].local_first) si = j;
+    const SegDev &sg = segs[si];
+    const uint64_t r = room - sg.local_first;
+    if (r >= sg.rooms) return;                                // (the host checked every room)
+    const u32x4 *in = reinterpret_cast<const u32x4 *>(src) + 3u * k;
+    const int W = (int)sg.words;
+    for (int j = 0; j < planes_of(W); j++) {
+        const int pw = plane_words(W, j);
+        char *plane = reinterpret_cast<char *>(sg.base) + plane_offset(sg.rooms_padded, j);
+        const u32x4 v = in[j];
+        if (pw == 4) {
+            reinterpret_cast<u32x4 *>(plane)[r] = v;
+        } else if (pw == 2) {
+            u32x2 h; h.x = v.x; h.y = v.y;
+            reinterpret_cast<u32x2 *>(plane)[r] = h;
+        } else {
+            for (int x = 0; x < pw; x++) reinterpret_cast<uint32_t *>(plane)[r * (uint64_t)pw + (uint64_t)x] = v[x];
+        }
     }
 }
 
@@ -308,6 +345,50 @@ static int read_rooms_at_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, ge
     return GE_OK;
 }
 
+static int write_rooms_at_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const ge_room_view *src) {
+    if (n == 0) return GE_OK;
+    for (uint64_t k = 0; k < n; k++)                              // all-or-nothing: every entry is checked before anything is written
+        if (rooms[k] >= b->n_rooms) return GE_ERR_RANGE;
+    {
+        std::vector<uint64_t> sorted(rooms, rooms + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return GE_ERR_ARG;
+    }
+    std::vector<uint32_t> seg_of((size_t)n);
+    for (uint64_t k = 0; k < n; k++) {
+        seg_of[k] = pool_segment_of(b, rooms[k]);
+        const Segment &sg = b->segs[seg_of[k]];
+        if (!view_fits(src[k], sg.table, sg.dev.n_players)) { g_last_rejected_room = rooms[k]; return GE_ERR_ARG; }
+    }
+    GE_ON_DEVICE(b);
+    int st = sync_impl(b);
+    if (st != GE_OK) return st;
+    // one upload: [rooms u64 x n (padded to 16 B)][records 12 words x n]
+    const size_t off_rec = (8 * (size_t)n + 15u) & ~(size_t)15u, total = off_rec + 48 * (size_t)n;
+    uint32_t *host32 = nullptr;
+    if ((st = io_stage(b, total, &host32)) != GE_OK) return st;
+    unsigned char *host = reinterpret_cast<unsigned char *>(host32);
+    memcpy(host, rooms, 8 * (size_t)n);
+    uint32_t *h_rec = reinterpret_cast<uint32_t *>(host + off_rec);
+    for_room_ranges(n, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t k = lo; k < hi; k++) {
+            const Segment &sg = b->segs[seg_of[k]];
+            uint32_t *w = h_rec + 12 * k;
+            memset(w, 0, 48);
+            view_to_words(sg.dev.kind, src[k], sg.table, w);
+        }
+    });
+    char *dev = nullptr;
+    if ((st = pool_scratch(b, total, &dev)) != GE_OK) return st;
+    hipStream_t s = b->last_stream;
+    if ((st = order_after_previous(b, s)) != GE_OK) return st;
+    HIP_TRY(hipMemcpyAsync(dev, host, total, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(ge_pool_scatter, dim3((uint32_t)((n + 63u) / 64u)), dim3(64), 0, s, b->segs_dev, (uint32_t)b->segs.size(),
+                       reinterpret_cast<const uint64_t *>(dev), n, reinterpret_cast<const uint32_t *>(dev + off_rec));
+    HIP_TRY(hipGetLastError());
+    return sync_impl(b);
+}
+
 extern "C" {
 
 int ge_batch_step_rooms(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
@@ -320,6 +401,11 @@ int ge_batch_read_rooms_at(ge_batch *b, uint64_t n, const uint64_t *rooms, ge_ro
     if (!b || (n && (!rooms || !dst))) return GE_ERR_ARG;
     if (cap_bytes / sizeof(ge_room_view) < n) return GE_ERR_ARG;
     return guarded([&] { return read_rooms_at_impl(b, n, rooms, dst); });
+}
+
+int ge_batch_write_rooms_at(ge_batch *b, uint64_t n, const uint64_t *rooms, const ge_room_view *src) {
+    if (!b || (n && (!rooms || !src))) return GE_ERR_ARG;
+    return guarded([&] { return write_rooms_at_impl(b, n, rooms, src); });
 }
 
 }  // extern "C"

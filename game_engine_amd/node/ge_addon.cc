@@ -101,7 +101,7 @@ napi_value CompileTable(napi_env env, napi_callback_info info) {
     return ext;
 }
 
-// tableInfo(table): { pack, rounds, minPlayers, roleNames[], fieldNames[], phases:[{id,name,completion,act,effect}] }
+// tableInfo(table): { pack, rounds, minPlayers, roleNames[], fieldNames[], phases:[{id,name,completion,act,effect,nBranches}], initFields[] }
 napi_value TableInfo(napi_env env, napi_callback_info info) {
     size_t argc = 1;
     napi_value argv[1];
@@ -136,9 +136,17 @@ napi_value TableInfo(napi_env env, napi_callback_info info) {
         NAPI_OK(napi_create_int32(env, t->rows[i].completion, &v)); NAPI_OK(napi_set_named_property(env, ph, "completion", v));
         NAPI_OK(napi_create_int32(env, t->rows[i].act, &v)); NAPI_OK(napi_set_named_property(env, ph, "act", v));
         NAPI_OK(napi_create_int32(env, t->rows[i].effect, &v)); NAPI_OK(napi_set_named_property(env, ph, "effect", v));
+        NAPI_OK(napi_create_int32(env, t->rows[i].n_branches, &v)); NAPI_OK(napi_set_named_property(env, ph, "nBranches", v));
         NAPI_OK(napi_set_element(env, phases, i, ph));
     }
     NAPI_OK(napi_set_named_property(env, out, "phases", phases));
+    napi_value init;                       // player_states_template in canonical field order (what a fresh room's players hold)
+    NAPI_OK(napi_create_array_with_length(env, 12, &init));
+    for (uint32_t i = 0; i < 12; i++) {
+        NAPI_OK(napi_create_uint32(env, t->init_fields[i], &v));
+        NAPI_OK(napi_set_element(env, init, i, v));
+    }
+    NAPI_OK(napi_set_named_property(env, out, "initFields", init));
     return out;
 }
 
@@ -493,6 +501,33 @@ napi_value ReadRoomsAt(napi_env env, napi_callback_info info) {
     return buf;
 }
 
+// writeRoomsAt(batch, rooms: BigUint64Array, views: ArrayBuffer of rooms.length ge_room_view): view k -> room rooms[k], all or nothing
+napi_value WriteRoomsAt(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
+    if (!b || argc < 3) return throw_status(env, GE_ERR_ARG, "writeRoomsAt");
+    napi_typedarray_type tt;
+    size_t len, off, bytes = 0;
+    void *rooms = nullptr, *data = nullptr;
+    napi_value ab;
+    if (napi_get_typedarray_info(env, argv[1], &tt, &len, &rooms, &ab, &off) != napi_ok || tt != napi_biguint64_array ||
+        napi_get_arraybuffer_info(env, argv[2], &data, &bytes) != napi_ok || bytes != len * sizeof(ge_room_view))
+        return throw_status(env, GE_ERR_ARG, "writeRoomsAt", "BigUint64Array and an ArrayBuffer of as many room views");
+    const int st = ge_batch_write_rooms_at(b, len, static_cast<const uint64_t *>(rooms), static_cast<const ge_room_view *>(data));
+    if (st == GE_ERR_ARG && len) {                // all-or-nothing: say which room's view did not fit its segment, if one did not
+        const uint64_t bad = ge_last_rejected_room();
+        for (size_t k = 0; k < len; k++)
+            if (static_cast<const uint64_t *>(rooms)[k] == bad) {
+                const std::string d = "room " + std::to_string(bad) + " does not fit its segment (nothing was written)";
+                return throw_status(env, st, "writeRoomsAt", d.c_str());
+            }
+    }
+    if (st != GE_OK) return throw_status(env, st, "writeRoomsAt");
+    return nullptr;
+}
+
 // summary(batch): BigUint64Array-compatible ArrayBuffer of ge_summary words
 napi_value Summary(napi_env env, napi_callback_info info) {
     size_t argc = 1;
@@ -716,6 +751,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"readEvents", nullptr, ReadEvents, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"stepRooms", nullptr, StepRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"readRoomsAt", nullptr, ReadRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"writeRoomsAt", nullptr, WriteRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"summary", nullptr, Summary, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"reset", nullptr, Reset, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"deviceCount", nullptr, DeviceCount, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -33,7 +33,7 @@ export interface TurnEvent {
   turn: number; from_phase_id: number; to_phase_id: number; acted_now: number; restarted: number; choice: number[];
 }
 export interface ToolCall { name: 'update_player_actions' | 'set_next_phase' | 'update_player_state' | 'add_game_note'; args: Record<string, unknown>; }
-export interface PhaseInfo { id: number; name: string; completion: number; act: number; effect: number; }
+export interface PhaseInfo { id: number; name: string; completion: number; act: number; effect: number; nBranches: number; }
 
 export class GameTable {
   constructor(dsl: object, rounds?: number);
@@ -71,6 +71,11 @@ export class RoomBatch {
   /** out[k] = room rooms[k] (any order, repeats allowed). */
   readRoomsAt(rooms: ArrayLike<number | bigint>): RoomState[];
   readRoomsAtRaw(rooms: ArrayLike<number | bigint>): ArrayBuffer;
+  /** views[k] -> room rooms[k] (pairwise distinct): one copy and one device scatter; all or nothing. */
+  writeRoomsAt(rooms: ArrayLike<number | bigint>, views: ArrayBuffer | ArrayBuffer[]): void;
+  /** Adopt a reference AgentState into one room (agentStateToView); returns its host-side fields. */
+  writeAgentState(room: number, state: AgentStateInput, visitActions?: Record<string, number>): HostSide;
+  writeAgentStates(rooms: ArrayLike<number>, states: AgentStateInput[], visitActions?: (Record<string, number> | undefined)[]): HostSide[];
   summary(): Summary;
 }
 /** One Node process, several GPUs: device d owns the global rooms [firstRoom + d*R, firstRoom + (d+1)*R). */
@@ -127,3 +132,24 @@ export function uiToolCalls(dsl: object, room: RoomState, opts?: { table?: GameT
 export function validateCall(call: FrontendToolCall): string[];
 /** [part, index inside the part's batch, segment] of a room of the whole job after the group's sharding (ge_group_partition). */
 export function locateInShards(segmentRooms: number[], nParts: number, room: number): [number, number, number];
+
+/** A reference AgentState as a LangGraph thread holds it (agent/game_agent_v2.py:97-117). */
+export interface AgentStateInput {
+  current_phase_id: number;
+  player_states: Record<string, Record<string, unknown>>;
+  playerActions?: Record<string, { name?: string; actions: Record<string, { action: string; phase: string; id?: string }> }>;
+  phase_history?: { phase_id: number; phase_name?: string }[];
+  game_notes?: string[];
+  previous_phase_id?: number;
+  end_turn?: number;
+  games?: number;
+}
+/** What the record does not carry: names, Two-Truths statements, and keys the record does not model, per player id. */
+export interface HostSide {
+  names: Record<string, string>;
+  statements: Record<string, Record<string, string>>;
+  extra: Record<string, Record<string, unknown>>;
+}
+/** The room view of an AgentState (one ge_room_view); TypeError for a wrong type, RangeError for a value that does not fit. */
+export function agentStateToView(table: GameTable, state: AgentStateInput,
+                                 opts?: { nPlayers?: number; visitActions?: Record<string, number> }): { view: ArrayBuffer; hostSide: HostSide };

@@ -147,6 +147,196 @@ function decodeRoom(table, buf, off) {
   };
 }
 
+// ---- AgentState -> room view: the inverse of decodeRoom / RoomLog.agentState (twin of stepper.agent_state_to_view)
+const ACTION_TAG = /^\[t=(\d+)\|c=(\d+)\]/;
+const WW_INTS = { 8: null };                       // integer slots and the largest value the record holds (null: the player count)
+const TT_INTS = { 2: 3, 5: 3, 7: 255, 8: 15 };
+const ACT_NIGHT = [1, 2, 3];                       // GE_ACT_WOLF_TARGET, GE_ACT_DOCTOR_PROTECT, GE_ACT_DETECTIVE
+const EFF_NIGHT_BEGIN = 2;
+const GE_MAX_PLAYERS = 12;
+const isInt = (x) => typeof x === 'number' && Number.isInteger(x);
+const isDict = (x) => x !== null && typeof x === 'object' && !Array.isArray(x);
+const sameValue = (a, b) => JSON.stringify(a) === JSON.stringify(b);
+
+function taggedActions(pa, n, keep) {               // [pid, turn, choice, phase] of every "[t=..|c=..]" entry keep() accepts
+  const out = [];
+  for (const [key, rec] of Object.entries(pa)) {
+    const pid = Number(key);
+    if (!Number.isInteger(pid) || pid < 1 || pid > n || !isDict(rec)) continue;
+    const acts = rec.actions || {};
+    for (const a of (Array.isArray(acts) ? acts : Object.values(acts))) {
+      if (!isDict(a)) continue;
+      const m = ACTION_TAG.exec(String(a.action === undefined ? '' : a.action));
+      if (m && keep(a.phase)) out.push([pid, Number(m[1]), Number(m[2])]);
+    }
+  }
+  return out;
+}
+
+/**
+ * The room view of a reference AgentState (current_phase_id, player_states, playerActions, phase_history) under the DSL's own
+ * field names: the exact inverse of decodeRoom / RoomLog.agentState, with the rules of the Python host's
+ * stepper.agent_state_to_view (INTEGRATION.md "Handing a running thread to the stepper").  Returns { view: ArrayBuffer of one
+ * ge_room_view, hostSide: { names, statements, extra } }.  A value of the wrong type throws TypeError; one that does not fit the
+ * record or the table (unknown role, team typo, out of range, missing player, a derived slot that disagrees) throws RangeError.
+ */
+function agentStateToView(table, state, { nPlayers, visitActions } = {}) {
+  if (!isDict(state)) throw new TypeError('state must be an object');
+  const info = table.info, names = info.fieldNames, ww = info.pack === 1;
+  const ps = state.player_states;
+  if (!isDict(ps) || !Object.keys(ps).length) throw new TypeError("state.player_states must be a non-empty object");
+  const n = nPlayers === undefined || nPlayers === null ? Object.keys(ps).length : Number(nPlayers);
+  if (!(n >= 1 && n <= GE_MAX_PLAYERS)) throw new RangeError(`${n} players: a room holds 1..${GE_MAX_PLAYERS}`);
+  const byId = new Map();
+  for (const [key, rec] of Object.entries(ps)) {
+    const pid = Number(key);
+    if (!Number.isInteger(pid)) throw new RangeError(`player_states key ${JSON.stringify(key)} is not a player id`);
+    if (!isDict(rec)) throw new TypeError(`player ${key}: not an object`);
+    byId.set(pid, rec);
+  }
+  const ids = [...byId.keys()].sort((a, b) => a - b);
+  if (ids.length !== n || ids.some((x, i) => x !== i + 1)) throw new RangeError(`player_states must name players 1..${n} exactly, got ${JSON.stringify(ids)}`);
+  const phases = info.phases, phaseIds = phases.map((p) => p.id);
+  const cur = state.current_phase_id;
+  if (!isInt(cur)) throw new TypeError(`current_phase_id ${JSON.stringify(cur)} is not an integer`);
+  if (!phaseIds.includes(cur)) throw new RangeError(`current_phase_id ${cur} is not a phase of the table`);
+  const hist = state.phase_history === undefined || state.phase_history === null ? [] : state.phase_history;
+  if (!Array.isArray(hist)) throw new TypeError('phase_history must be an array');
+  const histIds = hist.map((e) => {
+    if (!isDict(e) || !isInt(e.phase_id)) throw new TypeError(`phase_history entries need an integer phase_id, got ${JSON.stringify(e)}`);
+    return e.phase_id;
+  });
+  let s = histIds.length;                                   // the trailing run of the current phase: hist[s..]
+  while (s > 0 && histIds[s - 1] === cur) s--;
+
+  const buf = new ArrayBuffer(VIEW.size);
+  const dv = new DataView(buf), u8 = new Uint8Array(buf);
+  u8[17] = n; u8[18] = info.pack;
+  dv.setInt32(0, cur, true);
+  let prev = state.previous_phase_id;
+  if (prev === undefined || prev === null) prev = s > 0 ? histIds[s - 1] : 0;   // a fresh room holds phase 0 as its previous phase
+  if (!isInt(prev)) throw new TypeError(`previous_phase_id ${JSON.stringify(prev)} is not an integer`);
+  if (!phaseIds.includes(prev)) throw new RangeError(`previous_phase_id ${prev} is not a phase of the table`);
+  dv.setInt32(4, prev, true);
+  u8[16] = histIds.includes(0) ? 1 : 0;
+  let end = state.end_turn;
+  if (end === undefined || end === null) end = phases[phaseIds.indexOf(cur)].nBranches === 0 ? Math.min(s, 0xFFFE) : -1;
+  if (!isInt(end)) throw new TypeError(`end_turn ${JSON.stringify(end)} is not an integer`);
+  if (end < -1 || end > 0xFFFE) throw new RangeError(`end_turn ${end} is out of range (-1 .. 65534)`);
+  dv.setInt32(8, end, true);
+  const games = state.games === undefined || state.games === null ? 0 : state.games;
+  if (!isInt(games)) throw new TypeError(`games ${JSON.stringify(games)} is not an integer`);
+  if (games < 0 || games > 0xFFFF) throw new RangeError(`games ${games} is out of range (0 .. 65535)`);
+  dv.setInt32(12, games, true);
+
+  const roles = info.roleNames, ints = ww ? WW_INTS : TT_INTS;
+  const modelled = new Set(['name', ...names.filter((x) => x)]);
+  const host = { names: {}, statements: {}, extra: {} };
+  const row = (i) => VIEW.players + 12 * i;
+  for (let pid = 1; pid <= n; pid++) {
+    const rec = byId.get(pid), where = `player ${pid}`;
+    const f = info.initFields.slice(0, 12);
+    f[9] = f[10] = f[11] = 0;
+    for (let k = 0; k < 9; k++) {
+      const name = names[k];
+      if (!name || !(name in rec)) continue;
+      const val = rec[name];
+      if (ww && k === 0) {
+        if (typeof val !== 'string') throw new TypeError(`${where}: field '${name}': ${JSON.stringify(val)} is not a string`);
+        if (!roles.includes(val)) throw new RangeError(`${where}: field '${name}': unknown role ${JSON.stringify(val)} (the DSL declares ${JSON.stringify(roles.slice(1))})`);
+        f[k] = roles.indexOf(val);
+      } else if (ww && k === 1) {
+        if (typeof val !== 'string') throw new TypeError(`${where}: field '${name}': ${JSON.stringify(val)} is not a string`);
+        if (!TEAMS.includes(val)) throw new RangeError(`${where}: field '${name}': team ${JSON.stringify(val)} is not one of ${JSON.stringify(TEAMS)}`);
+        f[k] = TEAMS.indexOf(val);
+      } else if (k in ints) {
+        const hi = ints[k] === null ? n : ints[k];
+        if (!isInt(val)) throw new TypeError(`${where}: field '${name}': ${JSON.stringify(val)} is not an integer`);
+        if (val < 0 || val > hi) throw new RangeError(`${where}: field '${name}': ${val} is not an integer in 0..${hi}`);
+        f[k] = val;
+      } else {
+        if (typeof val !== 'boolean') throw new TypeError(`${where}: field '${name}': ${JSON.stringify(val)} is not a boolean`);
+        f[k] = val ? 1 : 0;
+      }
+    }
+    u8.set(f, row(pid - 1));
+    if (ww && names[9] && names[9] in rec) {
+      const field = names[9], mem = rec[field];
+      if (!isDict(mem)) throw new TypeError(`${where}: field '${field}' must be an object`);
+      if (Object.keys(mem).length && f[0] !== 4) throw new RangeError(`${where}: field '${field}': only the ${roles[4]} holds investigation results`);
+      for (const [q, team] of Object.entries(mem)) {
+        const qi = Number(q);
+        if (!(Number.isInteger(qi) && qi >= 1 && qi <= n) || (team !== 'villagers' && team !== 'werewolves'))
+          throw new RangeError(`${where}: field '${field}': entry ${JSON.stringify(q)}: ${JSON.stringify(team)} must name a player 1..${n} and a team`);
+        u8[VIEW.det + qi - 1] = TEAMS.indexOf(team);
+      }
+    }
+    host.names[String(pid)] = rec.name === undefined ? `Player ${pid}` : rec.name;
+    if (!ww && names[9]) {
+      const st = rec[names[9]] === undefined ? {} : rec[names[9]];
+      if (!isDict(st)) throw new TypeError(`${where}: field '${names[9]}' must be an object`);
+      host.statements[String(pid)] = Object.assign({}, st);
+    }
+    const extra = {};
+    for (const [k, v] of Object.entries(rec)) if (!modelled.has(k)) extra[k] = v;
+    if (Object.keys(extra).length) host.extra[String(pid)] = extra;
+  }
+
+  // acted / choice: this visit's latest tagged action per player (turns past the one that entered the phase)
+  const pa = state.playerActions === undefined || state.playerActions === null ? {} : state.playerActions;
+  if (!isDict(pa)) throw new TypeError('playerActions must be an object');
+  const curName = table.phaseName(cur);
+  const first = s === 0 && cur === 0 ? 0 : s + 1;
+  const latest = new Map();
+  for (const [pid, t, c] of taggedActions(pa, n, (ph) => ph === curName))
+    if (first <= t && t < histIds.length && t >= (latest.has(pid) ? latest.get(pid)[0] : -1)) latest.set(pid, [t, c]);
+  const acted = new Map([...latest].map(([pid, [, c]]) => [pid, c]));
+  const visit = new Map(Object.entries(visitActions || {}).map(([k, c]) => [Number(k), c]));
+  for (const [pid, c] of visit) acted.set(pid, c);
+  const top = ww ? n : 3;
+  for (const [pid, c] of acted) {
+    if (!isInt(c)) throw new TypeError(`player ${pid}: visit action ${JSON.stringify(c)} is not an integer`);
+    if (!(pid >= 1 && pid <= n) || c < 1 || c > top) throw new RangeError(`player ${pid}: visit action ${c} is not a choice in 1..${top}`);
+    u8[row(pid - 1) + 9] = 1; u8[row(pid - 1) + 10] = c;
+  }
+  if (ww && !(names[5] && names[7] && names[8])) {
+    // slots the DSL leaves undeclared still drive the rules: derived from the role and this night's logged actions
+    let since = -1;
+    histIds.forEach((pid, t) => {
+      const p = phases.find((x) => x.id === pid);
+      if (p && p.effect === EFF_NIGHT_BEGIN && (t === 0 || histIds[t - 1] !== pid)) since = t;
+    });
+    const actOf = new Map(phases.map((p) => [p.name, p.act]));
+    const night = new Map();
+    for (const [pid, t, c] of taggedActions(pa, n, (ph) => ACT_NIGHT.includes(actOf.get(ph))))
+      if (since < t && t < histIds.length && t >= (night.has(pid) ? night.get(pid)[0] : -1)) night.set(pid, [t, c]);
+    if (ACT_NIGHT.includes(phases[phaseIds.indexOf(cur)].act)) for (const [pid, c] of visit) night.set(pid, [histIds.length, c]);
+    for (let i = 0; i < n; i++) {
+      const o = row(i);
+      if (!names[5] && u8[o] >= 2) u8[o + 5] = 1;
+      if (night.has(i + 1)) {
+        if (!names[7]) u8[o + 7] = 1;
+        if (!names[8]) u8[o + 8] = night.get(i + 1)[1];
+      }
+    }
+  }
+
+  // self-check: every modelled field reads back as given
+  const back = decodeRoom(table, buf, 0).player_states;
+  for (let pid = 1; pid <= n; pid++) {
+    const rec = byId.get(pid), got = back[String(pid)];
+    names.forEach((name, k) => {
+      if (!name || !(name in rec) || !(name in got)) return;
+      let want = rec[name];
+      if (ww && k === 9) { const w = {}; for (const [q, t] of Object.entries(want)) w[String(q)] = t; want = w; }
+      const g = got[name];
+      const eq = isDict(want) ? (isDict(g) && sameValue(Object.entries(g).sort(), Object.entries(want).sort())) : g === want;
+      if (!eq) throw new RangeError(`player ${pid}: field '${name}' = ${JSON.stringify(want)} does not fit the record (it reads back as ${JSON.stringify(g)})`);
+    });
+  }
+  return { view: buf, hostSide: host };
+}
+
 const EVENT_SIZE = 32;
 
 function actionText(act, player, c) {
@@ -251,6 +441,18 @@ class RoomLog {
   constructor(table, names, gameName = '') {
     this.table = table; this.names = names.slice(); this.gameName = gameName;
     this.playerActions = {}; this.gameNotes = []; this.phaseHistory = []; this.statements = {};
+    this.extra = {};               // per player: fields the record does not model (an adopted thread's)
+  }
+  /** Seed the log of a thread handed over mid-game: its playerActions, game_notes and phase_history, and the host-side fields
+   * agentStateToView returned (names, statements, fields the record does not model). */
+  adopt(state, hostSide) {
+    const copy = (x) => JSON.parse(JSON.stringify(x === undefined || x === null ? null : x));
+    this.playerActions = copy(state.playerActions) || {};
+    this.gameNotes = copy(state.game_notes) || [];
+    this.phaseHistory = copy(state.phase_history) || [];
+    this.names = this.names.map((nm, i) => (hostSide.names[String(i + 1)] !== undefined ? hostSide.names[String(i + 1)] : nm));
+    this.statements = copy(hostSide.statements) || {};
+    this.extra = copy(hostSide.extra) || {};
   }
   /** Apply one turn's calls; `after`: the RoomState after the turn. */
   fold(calls, after, now = Date.now()) {
@@ -289,6 +491,7 @@ class RoomLog {
         const fn = this.table.info.fieldNames;
         if (this.table.info.pack === 2 && k === fn[0] && fn[9]) out[fn[9]] = Object.assign({}, this.statements[pid] || {});
       }
+      Object.assign(out, this.extra[pid] || {});
       ps[pid] = out;
     });
     return { gameName: this.gameName, current_phase_id: room.current_phase_id, current_phase_name: room.current_phase_name,
@@ -382,6 +585,34 @@ class RoomBatch {
     return Array.from(rooms, (r, k) => decodeRoom(this.tableOf(Number(r)), buf, k * VIEW.size));
   }
   readRoomsAtRaw(rooms) { return addon.readRoomsAt(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r))); }
+  /** Store views[k] (ArrayBuffers of one room view each, or one ArrayBuffer of rooms.length views) into room rooms[k] (pairwise
+   * distinct): one copy and one device scatter, each record exactly as writeRoomsRaw stores it.  All or nothing. */
+  writeRoomsAt(rooms, views) {
+    let buf = views;
+    if (Array.isArray(views)) {
+      const u8 = new Uint8Array(VIEW.size * views.length);
+      views.forEach((v, k) => u8.set(new Uint8Array(v), k * VIEW.size));
+      buf = u8.buffer;
+    }
+    addon.writeRoomsAt(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r)), buf);
+  }
+  segmentOf(room) {
+    let base = 0;
+    for (const s of this.segments) { if (room < base + s.nRooms) return s; base += s.nRooms; }
+    throw new RangeError(`room ${room}`);
+  }
+  /** Adopt a reference AgentState into one room (agentStateToView); returns its host-side fields. */
+  writeAgentState(room, state, visitActions) { return this.writeAgentStates([room], [state], visitActions ? [visitActions] : undefined)[0]; }
+  /** Many at once: every state is converted (and refused) before one writeRoomsAt. */
+  writeAgentStates(rooms, states, visitActions) {
+    if (rooms.length !== states.length || (visitActions && visitActions.length !== states.length)) throw new RangeError('rooms, states and visitActions differ in length');
+    const conv = states.map((st, k) => {
+      const seg = this.segmentOf(Number(rooms[k]));
+      return agentStateToView(seg.table, st, { nPlayers: seg.nPlayers, visitActions: visitActions ? visitActions[k] : undefined });
+    });
+    this.writeRoomsAt(rooms, conv.map((c) => c.view));
+    return conv.map((c) => c.hostSide);
+  }
   summary() { return decodeSummary(addon.summary(this.handle)); }
 }
 
@@ -508,5 +739,5 @@ class DeviceGroup {
 
 const { compileCriteria, audienceGroups, uiToolCalls } = require('./ui_script.js');
 
-module.exports = { GameTable, RoomBatch, decodeRoom, ShardedBatch, DeviceGroup, locateInShards, RoomLog, formatNote, loadDslByGamename, findGameFile, initializePlayers, turnToolCalls, compileCriteria, audienceGroups, uiToolCalls,
+module.exports = { GameTable, RoomBatch, decodeRoom, agentStateToView, ShardedBatch, DeviceGroup, locateInShards, RoomLog, formatNote, loadDslByGamename, findGameFile, initializePlayers, turnToolCalls, compileCriteria, audienceGroups, uiToolCalls,
                    deviceCount: addon.deviceCount, addon };

@@ -1,5 +1,5 @@
 // Types for room_pool.js — many game threads hosted in a few resident batches.
-import { AgentStateView, RoomPlayer, TurnResult } from './room_service';
+import { AdoptOptions, AgentStateView, RoomPlayer, TurnResult } from './room_service';
 
 export type MessageResult = TurnResult & { played: boolean; kind: 'chat' | 'control' | 'action' };
 export class RoomPoolService {
@@ -7,6 +7,8 @@ export class RoomPoolService {
   constructor(opts?: { gamesDir?: string; seed?: bigint | number; device?: number; chunkRooms?: number });
   /** As RoomService.createRoom: the thread's RNG is keyed by roomIndex (default: hash of the thread id), its turn counter starts at 0. */
   createRoom(opts: { threadId: string; gameName: string; players: RoomPlayer[]; dsl?: object; roomIndex?: number | bigint }): AgentStateView;
+  /** As RoomService.adoptRoom for many threads: every state is converted before a slot is taken, then one writeRoomsAt per chunk. */
+  adoptRooms(entries: AdoptOptions[]): Promise<TurnResult[]>;
   humanAction(threadId: string, playerId: number, choice: number): Promise<AgentStateView>;
   continueRoom(threadId: string, items?: { id: string; type: string }[]): Promise<TurnResult>;
   handleMessage(threadId: string, text: string, items?: { id: string; type: string }[]): Promise<MessageResult>;

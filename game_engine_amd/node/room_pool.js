@@ -10,7 +10,7 @@
  * stepRooms and one readRoomsAt.  The chunks are shared, so every call of the service runs strictly one after the other.
  */
 const { GameTable, RoomBatch, RoomLog, decodeRoom, turnToolCalls, uiToolCalls } = require('./index.js');
-const { roomIndexOf } = require('./room_service.js');
+const { roomIndexOf, prepareAdoption, adoptedOutput } = require('./room_service.js');
 const M = require('./messages.js');
 
 const GE_ERR_ARG = -1;
@@ -33,7 +33,7 @@ class RoomPoolService {
     this.queue = p.catch(() => {});
     return p;
   }
-  _acquire(pool) {
+  _acquire(pool, template = true) {
     if (pool.free.length === 0) {
       const ci = pool.chunks.length;
       const chunk = new RoomBatch({ segments: [{ table: pool.table, nPlayers: pool.nPlayers, nRooms: this.chunkRooms, humanMask: pool.humanMask }],
@@ -45,7 +45,7 @@ class RoomPoolService {
     const [ci, slot] = pool.free.pop();
     const chunk = pool.chunks[ci];
     const id = `${ci}/${slot}`;
-    if (pool.used.has(id)) chunk.writeRoomsRaw(slot, pool.templateRaw);   // a reused slot starts from the template (no prepared deal)
+    if (template && pool.used.has(id)) chunk.writeRoomsRaw(slot, pool.templateRaw);   // a reused slot starts from the template (no prepared deal)
     pool.used.add(id);
     return { chunk, ci, slot };
   }
@@ -64,6 +64,53 @@ class RoomPoolService {
                    table, gameName, names, humanSeats, panel: null, state: decodeRoom(table, pool.templateRaw, 0), log: new RoomLog(table, names, gameName) };
     this.rooms.set(threadId, room);
     return this.agentState(room);
+  }
+  /**
+   * Take over many threads that are already mid-game (twin of the Python RoomPoolService.adopt_rooms): entries
+   * [{ threadId, gameName, state, players?, humanSeats?, dsl?, roomIndex?, turn?, visitActions? }].  Every state is converted
+   * first and the slots taken next; a refusal leaves the service as it was.  Then one writeRoomsAt per chunk touched (a reused
+   * slot is written over directly).  Resolves, in order, what RoomService.adoptRoom returns for each.
+   */
+  adoptRooms(entries) {
+    return this._serial(() => {
+      const seen = new Set();
+      const prep = entries.map((e) => {
+        if (seen.has(e.threadId)) throw new Error(`thread ${e.threadId} is named twice`);
+        seen.add(e.threadId);
+        const table = this.table(e.gameName, e.dsl);
+        return Object.assign({ e, table }, prepareAdoption(table, e));
+      });
+      const taken = [];
+      try {
+        for (const p of prep) {
+          const pk = `${p.e.gameName}/${p.n}/${p.humanMask}`;
+          if (!this.pools.has(pk)) this.pools.set(pk, { table: p.table, nPlayers: p.n, humanMask: p.humanMask, chunks: [], free: [], used: new Set(), templateRaw: null });
+          const pool = this.pools.get(pk);
+          taken.push(Object.assign({ pool }, this._acquire(pool, false)));
+        }
+        const byChunk = new Map();
+        taken.forEach((t, k) => {
+          if (!byChunk.has(t.chunk)) byChunk.set(t.chunk, []);
+          byChunk.get(t.chunk).push(k);
+        });
+        for (const [chunk, ks] of byChunk) chunk.writeRoomsAt(ks.map((k) => taken[k].slot), ks.map((k) => prep[k].view));
+        const states = new Array(prep.length);
+        for (const [chunk, ks] of byChunk) chunk.readRoomsAt(ks.map((k) => taken[k].slot)).forEach((st, j) => { states[ks[j]] = st; });
+        return prep.map((p, k) => {
+          const { pool, chunk, ci, slot } = taken[k];
+          if (this.rooms.has(p.e.threadId)) this._release(p.e.threadId);
+          const room = { pool, chunk, ci, slot, key: p.e.roomIndex === undefined ? roomIndexOf(p.e.threadId) : BigInt(p.e.roomIndex), turn: p.turn,
+                         table: p.table, gameName: p.e.gameName, names: p.names, humanSeats: p.humanSeats, panel: null, state: states[k],
+                         log: new RoomLog(p.table, p.names, p.e.gameName) };
+          room.log.adopt(p.e.state, Object.assign({}, p.hostSide, { names: Object.fromEntries(p.names.map((nm, i) => [String(i + 1), nm])) }));
+          this.rooms.set(p.e.threadId, room);
+          return adoptedOutput(room, p.turn);
+        });
+      } catch (err) {
+        for (const t of taken) if (![...this.rooms.values()].some((r) => r.chunk === t.chunk && r.slot === t.slot)) t.pool.free.push([t.ci, t.slot]);
+        throw err;
+      }
+    });
   }
   agentState(room) { return room.log.agentState(room.state); }
   _room(threadId) {

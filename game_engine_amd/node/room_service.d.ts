@@ -1,5 +1,5 @@
 // Types for room_service.js — the single-room (one LangGraph thread) drop-in.
-import { RoomState, ToolCall, FrontendToolCall } from './index';
+import { RoomState, ToolCall, FrontendToolCall, AgentStateInput } from './index';
 
 export interface RoomPlayer { name?: string; gamePlayerId?: number; /** false marks a human seat (host-driven) */ isBot?: boolean; }
 /** AgentState as the frontend syncs it (src/lib/canvas/types.ts:338-360), log-shaped parts included. */
@@ -10,10 +10,18 @@ export interface AgentStateView {
   phase_history: { phase_id: number; phase_name: string }[];
   game_notes: string[];
 }
+export interface AdoptOptions {
+  threadId: string; gameName: string; state: AgentStateInput; players?: RoomPlayer[]; /** player ids of human seats */ humanSeats?: number[];
+  dsl?: object; roomIndex?: number | bigint; /** the thread's next turn (default phase_history.length) */ turn?: number;
+  /** a human seat's action already logged in this visit: {playerId: choice} */ visitActions?: Record<string, number>;
+}
 export interface TurnResult { state: AgentStateView; toolCalls: ToolCall[]; uiCalls: FrontendToolCall[]; }
 export class RoomService {
   constructor(opts?: { gamesDir?: string; seed?: bigint | number; device?: number });
   createRoom(opts: { threadId: string; gameName: string; players: RoomPlayer[]; dsl?: object; /** global room index the RNG is keyed by (default: hash of the thread id) */ roomIndex?: number | bigint }): AgentStateView;
+  /** Take over a thread that is already mid-game (INTEGRATION.md "Handing a running thread to the stepper"): toolCalls is empty,
+   *  uiCalls the UI of the phase now showing.  Throws TypeError / RangeError for a state that does not fit, before anything changes. */
+  adoptRoom(opts: AdoptOptions): TurnResult;
   /** Requests of one thread are served strictly one after the other. */
   humanAction(threadId: string, playerId: number, choice: number): Promise<AgentStateView>;
   /** One message of the browser, as the reference's graph reads it (page.tsx:272-275, 302-305, 341-349, 2774, 2843, 2962;

@@ -13,7 +13,7 @@
  * LangGraphAgent (route.ts:30-39); `serve()` exposes the same over plain HTTP for a quick try.
  */
 const http = require('http');
-const { GameTable, RoomBatch, RoomLog, loadDslByGamename, turnToolCalls, uiToolCalls } = require('./index.js');
+const { GameTable, RoomBatch, RoomLog, agentStateToView, loadDslByGamename, turnToolCalls, uiToolCalls } = require('./index.js');
 const M = require('./messages.js');
 
 /** stable 48-bit room index from a thread id (the RNG is keyed by it) */
@@ -21,6 +21,49 @@ function roomIndexOf(threadId) {
   let h = 0xcbf29ce484222325n;
   for (const ch of Buffer.from(String(threadId), 'utf8')) { h ^= BigInt(ch); h = (h * 0x100000001b3n) & 0xffffffffffffffffn; }
   return h & 0xffffffffffffn;
+}
+
+/** humanSeats / players' isBot === false -> the segment's human mask */
+function humanMaskOf(players, humanSeats, n) {
+  let mask = (players || []).reduce((m, p, i) => (p.isBot === false ? m | (1 << i) : m), 0);
+  for (const seat of humanSeats || []) {
+    if (!(Number.isInteger(seat) && seat >= 1 && seat <= n)) throw new RangeError(`human seat ${seat} is not a player 1..${n}`);
+    mask |= 1 << (seat - 1);
+  }
+  return mask;
+}
+
+/** The players eliminated by the turn that the last "[t=<turn>]" phase note reports (its CRITICAL notes): what that turn's UI marked. */
+function lastTurnDeaths(notes, turn) {
+  let at = -1;
+  notes.forEach((x, i) => { if (x.includes(`PHASE_STATUS: [t=${turn}] `)) at = i; });
+  if (at < 0) return [];
+  const out = [];
+  for (let i = at + 1; i < notes.length && !notes[i].includes('PHASE_STATUS: '); i++) {
+    const m = /CRITICAL: Player (\d+) \(.*\) eliminated/.exec(notes[i]);
+    if (m) out.push(m[1]);
+  }
+  return out;
+}
+
+/** What adopting a thread returns: its state and the UI of the phase now showing, as its last turn (turn - 1) rendered it. */
+function adoptedOutput(room, turn) {
+  const state = room.log.agentState(room.state);
+  const last = Math.max(turn - 1, 0);
+  const uiCalls = uiToolCalls(room.table.dsl, state, { table: room.table, turn: last, deaths: lastTurnDeaths(room.log.gameNotes, last) });
+  room.panel = M.newestPanel(uiCalls);
+  return { state, toolCalls: [], uiCalls };
+}
+
+/** agentStateToView of an adoption request and what follows from it (both services) */
+function prepareAdoption(table, { state, players, humanSeats, turn, visitActions }) {
+  const { view, hostSide } = agentStateToView(table, state, { nPlayers: players ? players.length : undefined, visitActions });
+  const n = new Uint8Array(view)[17];
+  const humanMask = humanMaskOf(players, humanSeats, n);
+  const t = turn === undefined || turn === null ? (state.phase_history || []).length : Number(turn);
+  const names = Array.from({ length: n }, (_, i) => (players && players[i] && players[i].name) || hostSide.names[String(i + 1)]);
+  const seats = Array.from({ length: n }, (_, i) => i + 1).filter((i) => (humanMask >> (i - 1)) & 1);
+  return { view, hostSide, n, humanMask, turn: t, names, humanSeats: seats };
 }
 
 class RoomService {
@@ -47,6 +90,31 @@ class RoomService {
     const room = { batch, table, gameName, names, humanSeats, panel: null, state: batch.readRoom(0), log: new RoomLog(table, names, gameName), queue: Promise.resolve() };
     this.rooms.set(threadId, room);
     return this.agentState(room);
+  }
+  /**
+   * Take over a thread that is already mid-game (twin of the Python RoomService.adopt_room): `state` is its AgentState
+   * (current_phase_id, player_states, playerActions, phase_history, game_notes).  players (optional): isBot === false marks a
+   * human seat, as does humanSeats (player ids); names default to the state's.  turn: the thread's next turn (default
+   * phase_history.length); visitActions {playerId: choice}: a human seat's action already logged in this visit.  Returns
+   * { state, toolCalls: [], uiCalls } - the UI of the phase now showing, as the last turn rendered it.  A state that does not
+   * fit throws (TypeError / RangeError) before anything is created or closed.
+   */
+  adoptRoom({ threadId, gameName, state, players, humanSeats, dsl, roomIndex, turn, visitActions }) {
+    const table = this.table(gameName, dsl);
+    const a = prepareAdoption(table, { state, players, humanSeats, turn, visitActions });
+    const batch = new RoomBatch({ segments: [{ table, nPlayers: a.n, nRooms: 1, humanMask: a.humanMask }], seed: this.seed,
+                                  firstRoom: roomIndex === undefined ? roomIndexOf(threadId) : BigInt(roomIndex),
+                                  device: this.device, maxFuse: 1, trace: true });
+    try {
+      batch.writeRoomsAt([0], [a.view]);
+      batch.setTurn(a.turn);
+    } catch (e) { batch.close(); throw e; }
+    if (this.rooms.has(threadId)) this.close(threadId);
+    const room = { batch, table, gameName, names: a.names, humanSeats: a.humanSeats, panel: null, state: batch.readRoom(0),
+                   log: new RoomLog(table, a.names, gameName), queue: Promise.resolve() };
+    room.log.adopt(state, Object.assign({}, a.hostSide, { names: Object.fromEntries(a.names.map((nm, i) => [String(i + 1), nm])) }));
+    this.rooms.set(threadId, room);
+    return adoptedOutput(room, a.turn);
   }
   agentState(room) { return room.log.agentState(room.state); }
   /** Requests of one thread run strictly one after the other (the reference's LangGraph server queues
@@ -153,4 +221,4 @@ class RoomService {
   }
 }
 
-module.exports = { RoomService, roomIndexOf };
+module.exports = { RoomService, roomIndexOf, prepareAdoption, adoptedOutput };

@@ -17,7 +17,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import messages as M
-from .room_service import room_index_of
+from .room_service import adopted_output, prepare_adoption, room_index_of
 from .stepper import GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, load_dsl_by_gamename, slot_values
 from .toolcalls import WW_IS_ALIVE, RoomLog, turn_tool_calls
 from .ui_script import ui_tool_calls
@@ -53,7 +53,7 @@ class RoomPoolService:
         return RoomBatch([(tb, n_players, n_rooms, human_mask)], seed=self.seed, first_room=0, device=self.device, max_fuse=1)
 
     # ---- slots
-    def _acquire(self, pool: _Pool) -> Tuple[Any, int, int]:
+    def _acquire(self, pool: _Pool, template: bool = True) -> Tuple[Any, int, int]:
         if not pool.free:
             ci = len(pool.chunks)
             chunk = self._new_chunk(pool.table, pool.n_players, pool.human_mask, self.chunk_rooms)
@@ -63,7 +63,7 @@ class RoomPoolService:
             pool.free.extend((ci, s) for s in reversed(range(self.chunk_rooms)))
         ci, slot = pool.free.pop()
         chunk = pool.chunks[ci]
-        if (ci, slot) in pool.used:               # a reused slot starts from the template (which also drops any prepared deal)
+        if template and (ci, slot) in pool.used:  # a reused slot starts from the template (which also drops any prepared deal)
             chunk.write_rooms(slot, np.array([pool.template], dtype=pool.template.dtype))
         pool.used.add((ci, slot))
         return chunk, ci, slot
@@ -89,6 +89,60 @@ class RoomPoolService:
                 "view": pool.template.copy(), "log": RoomLog(tb, names, game_name)}
         self._rooms[thread_id] = room
         return self._agent_state(room)
+
+    def adopt_room(self, thread_id: str, game_name: str, state: Dict[str, Any], **kw) -> Dict[str, Any]:
+        """As RoomService.adopt_room, into a pool slot."""
+        return self.adopt_rooms([(thread_id, game_name, state, kw)])[0]
+
+    def adopt_rooms(self, entries: Sequence[Tuple]) -> List[Dict[str, Any]]:
+        """Take over many threads that are already mid-game: [(thread_id, game_name, state[, options]), ...] with the options of
+        RoomService.adopt_room as a dict (players, human_seats, dsl, room_index, turn, visit_actions).  Every state is converted
+        first (ValueError, before any slot is taken); then one write_rooms_at per chunk touched.  A reused slot is written over
+        directly (no template write first).  Returns, in order, what RoomService.adopt_room returns for each."""
+        prepared, seen = [], set()
+        for e in entries:
+            tid, game, state = e[0], e[1], e[2]
+            kw = dict(e[3]) if len(e) > 3 and e[3] else {}
+            if tid in seen:
+                raise ValueError(f"thread {tid!r} is named twice")
+            seen.add(tid)
+            tb = self.table(game, kw.get("dsl"))
+            a = prepare_adoption(tb, state, kw.get("players"), kw.get("human_seats", ()), kw.get("turn"), kw.get("visit_actions"))
+            prepared.append((tid, game, tb, state, kw, a))
+        # slots next (new chunks may be created); a failure gives them back, and no thread has been touched yet
+        taken: List[Tuple[_Pool, Any, int, int]] = []
+        try:
+            for tid, game, tb, state, kw, a in prepared:
+                key = (game, a["n"], a["human_mask"])
+                pool = self._pools.get(key)
+                if pool is None:
+                    pool = self._pools[key] = _Pool(tb, a["n"], a["human_mask"])
+                taken.append((pool,) + self._acquire(pool, template=False))
+            by_chunk: Dict[int, Tuple[Any, List[int]]] = {}
+            for k, (_, chunk, _, _) in enumerate(taken):
+                by_chunk.setdefault(id(chunk), (chunk, []))[1].append(k)
+            views = [None] * len(taken)
+            for chunk, ks in by_chunk.values():
+                slots = [taken[k][3] for k in ks]
+                chunk.write_rooms_at(slots, [prepared[k][5]["view"] for k in ks])
+                for k, v in zip(ks, chunk.read_rooms_at(slots)):     # the canonical views, as RoomService reads its room back
+                    views[k] = v
+        except BaseException:
+            for pool, _, ci, slot in taken:
+                pool.free.append((ci, slot))
+            raise
+        rooms = []
+        for (tid, game, tb, state, kw, a), (pool, chunk, ci, slot), view in zip(prepared, taken, views):
+            if tid in self._rooms:
+                self.close(tid)
+            room = {"pool": pool, "chunk": chunk, "ci": ci, "slot": slot, "turn": a["turn"],
+                    "key": room_index_of(tid) if kw.get("room_index") is None else int(kw["room_index"]),
+                    "table": tb, "gameName": game, "names": a["names"], "panel": None,
+                    "human_seats": a["human_seats"], "view": view, "log": RoomLog(tb, a["names"], game)}
+            room["log"].adopt(state, a["host"])
+            self._rooms[tid] = room
+            rooms.append(room)
+        return [adopted_output(room, room["turn"]) for room in rooms]
 
     def _agent_state(self, room: Dict[str, Any]) -> Dict[str, Any]:
         return room["log"].agent_state(room["view"])

@@ -11,10 +11,12 @@ are folded from those calls exactly as the reference's `_execute_*` functions wo
 """
 from __future__ import annotations
 
+import re
 from typing import Any, Dict, List, Optional
 
 from . import messages as M
-from .stepper import GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, load_dsl_by_gamename, slot_values, view_to_agent_state
+from .stepper import (GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, agent_state_to_view, load_dsl_by_gamename, slot_values,
+                      view_to_agent_state)
 from .toolcalls import WW_IS_ALIVE, RoomLog, turn_tool_calls
 from .ui_script import ui_tool_calls
 
@@ -27,6 +29,55 @@ def room_index_of(thread_id: str) -> int:
         h ^= ch
         h = (h * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
     return h & 0xFFFFFFFFFFFF
+
+
+def _human_mask(players: Optional[List[Dict[str, Any]]], human_seats, n: int) -> int:
+    mask = sum(1 << i for i, p in enumerate(players or []) if p.get("isBot") is False)
+    for seat in human_seats or ():
+        if not 1 <= int(seat) <= n:
+            raise ValueError(f"human seat {seat} is not a player 1..{n}")
+        mask |= 1 << (int(seat) - 1)
+    return mask
+
+
+def prepare_adoption(tb: GameTable, state: Dict[str, Any], players, human_seats, turn, visit_actions) -> Dict[str, Any]:
+    """agent_state_to_view of an adoption request and what follows from it (both services; nothing is created here)."""
+    view, host = agent_state_to_view(tb, state, len(players) if players else None, visit_actions)
+    n = int(view["n_players"])
+    mask = _human_mask(players, human_seats, n)
+    names = [(players[i].get("name") if players else None) or host["names"][str(i + 1)] for i in range(n)]
+    return {"view": view, "n": n, "human_mask": mask, "names": names,
+            "turn": len(state.get("phase_history") or []) if turn is None else int(turn),
+            "human_seats": [i + 1 for i in range(n) if (mask >> i) & 1],
+            "host": dict(host, names={str(i + 1): nm for i, nm in enumerate(names)})}
+
+
+_DEATH_NOTE = re.compile(r"CRITICAL: Player (\d+) \(.*\) eliminated")
+
+
+def last_turn_deaths(notes: List[str], turn: int) -> List[str]:
+    """The players eliminated by `turn`, as its notes report them (the CRITICAL notes after its "[t=<turn>]" phase note):
+    what that turn's UI marked dead."""
+    at = max((i for i, x in enumerate(notes) if f"PHASE_STATUS: [t={turn}] " in x), default=-1)
+    if at < 0:
+        return []
+    out = []
+    for x in notes[at + 1:]:
+        if "PHASE_STATUS: " in x:
+            break
+        m = _DEATH_NOTE.search(x)
+        if m:
+            out.append(m.group(1))
+    return out
+
+
+def adopted_output(room: Dict[str, Any], turn: int) -> Dict[str, Any]:
+    """What adopting a thread returns: its state and the UI of the phase now showing, as the last turn (turn - 1) rendered it."""
+    state = room["log"].agent_state(room["view"])
+    last = max(turn - 1, 0)
+    ui = ui_tool_calls(room["table"].dsl, state, room["table"], turn=last, deaths=last_turn_deaths(room["log"].game_notes, last))
+    room["panel"] = M.newest_panel(ui)
+    return {"state": state, "toolCalls": [], "uiCalls": ui}
 
 
 class RoomService:
@@ -56,6 +107,35 @@ class RoomService:
                 "view": batch.read_rooms(0, 1)[0], "log": RoomLog(tb, names, game_name)}
         self._rooms[thread_id] = room
         return self._agent_state(room)
+
+    def adopt_room(self, thread_id: str, game_name: str, state: Dict[str, Any], players: Optional[List[Dict[str, Any]]] = None,
+                   human_seats=(), dsl: Optional[dict] = None, room_index: Optional[int] = None, turn: Optional[int] = None,
+                   visit_actions: Optional[Dict[Any, int]] = None) -> Dict[str, Any]:
+        """Take over a thread that is already mid-game: `state` is its AgentState (current_phase_id, player_states, playerActions,
+        phase_history, game_notes - what update_complete_player_states replaces wholesale in the reference).  The room continues
+        from it exactly as the thread would have gone on.  players (optional, roomSession.players): `isBot: False` marks a human
+        seat, as does human_seats (player ids); the names default to the state's.  turn: the thread's next turn (default
+        len(phase_history), one entry per run); visit_actions={player_id: choice}: a human seat's action already logged in this
+        visit (see stepper.agent_state_to_view).  Returns {"state", "toolCalls": [], "uiCalls"}: the UI of the phase now showing,
+        rendered for the last turn, so that a person's next vote resolves against the panel the thread showed.
+        A state that does not fit raises ValueError before anything is created."""
+        tb = self.table(game_name, dsl)
+        a = prepare_adoption(tb, state, players, human_seats, turn, visit_actions)
+        batch = self._new_batch(tb, a["n"], a["human_mask"], room_index_of(thread_id) if room_index is None else room_index)
+        try:
+            batch.write_rooms_at([0], [a["view"]])
+            batch.set_turn(a["turn"])
+            view = batch.read_rooms(0, 1)[0]
+        except BaseException:
+            batch.close()
+            raise
+        if thread_id in self._rooms:                      # only now: a refused state leaves an existing thread of this id alone
+            self.close(thread_id)
+        room = {"batch": batch, "table": tb, "gameName": game_name, "names": a["names"], "panel": None,
+                "human_seats": a["human_seats"], "view": view, "log": RoomLog(tb, a["names"], game_name)}
+        room["log"].adopt(state, a["host"])
+        self._rooms[thread_id] = room
+        return adopted_output(room, a["turn"])
 
     def _new_batch(self, tb: GameTable, n_players: int, human_mask: int, first_room: int) -> RoomBatch:
         """The room's N=1 traced batch on the device (there is no other stepper: without the HIP library this raises)."""

@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes as C
 import json
 import os
+import re
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -36,6 +37,7 @@ SLOT_DET_MEMORY, SLOT_WOLF_CHAT, SLOT_STATEMENTS = 9, 10, 9
 
 
 GE_ERR_ARG = -1                           # include/ge_step.h ge_status
+GE_MAX_PLAYERS = 12                       # include/ge_step.h
 
 
 class GeError(RuntimeError):
@@ -294,6 +296,40 @@ class RoomBatch:
         _check(self._lib.ge_batch_read_rooms_at(self._h, len(rooms), rooms.ctypes.data, out.ctypes.data, out.nbytes),
                "ge_batch_read_rooms_at")
         return out
+
+    def write_rooms_at(self, rooms, views):
+        """Store views[k] into room rooms[k] (local indices, pairwise distinct): the indexed twin of write_rooms, one copy and
+        one device scatter.  A record is stored exactly as write_rooms stores it.  All-or-nothing: a room outside the batch, a
+        repeated room or a view that does not fit its room's segment raises and writes nothing."""
+        rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
+        views = np.ascontiguousarray(np.asarray(views, dtype=ROOM_VIEW_DTYPE).reshape(-1))
+        if len(rooms) != len(views):
+            raise GeError(-1, "write_rooms_at: rooms and views differ in length")
+        st = self._lib.ge_batch_write_rooms_at(self._h, len(rooms), rooms.ctypes.data, views.ctypes.data)
+        if st == -1 and len(rooms) and len(np.unique(rooms)) == len(rooms):
+            bad = int(self._lib.ge_last_rejected_room())
+            if bad in set(int(r) for r in rooms):
+                raise GeError(st, f"ge_batch_write_rooms_at: room {bad} does not fit its segment (nothing was written)")
+        _check(st, "ge_batch_write_rooms_at")
+
+    def write_agent_state(self, room: int, state: Dict[str, Any], visit_actions: Optional[Dict[Any, int]] = None) -> Dict[str, Any]:
+        """Adopt a reference AgentState into one room (agent_state_to_view); returns its host-side fields."""
+        return self.write_agent_states([room], [state], None if visit_actions is None else [visit_actions])[0]
+
+    def write_agent_states(self, rooms, states: Sequence[Dict[str, Any]],
+                           visit_actions: Optional[Sequence[Optional[Dict[Any, int]]]] = None) -> List[Dict[str, Any]]:
+        """Adopt many AgentStates at once: every state is converted (and refused, ValueError) before one write_rooms_at."""
+        rooms = [int(r) for r in rooms]
+        if len(rooms) != len(states) or (visit_actions is not None and len(visit_actions) != len(states)):
+            raise ValueError("write_agent_states: rooms, states and visit_actions differ in length")
+        views, hosts = [], []
+        for k, (room, st) in enumerate(zip(rooms, states)):
+            tb, n = self._segment_of(room)
+            v, host = agent_state_to_view(tb, st, n, None if visit_actions is None else visit_actions[k])
+            views.append(v)
+            hosts.append(host)
+        self.write_rooms_at(rooms, views)
+        return hosts
 
     def summary(self) -> Dict[str, Any]:
         s = _lib.Summary()
@@ -575,3 +611,245 @@ def view_to_agent_state(tb: GameTable, view) -> Dict[str, Any]:
     pid = int(view["phase_id"])
     return {"current_phase_id": pid, "current_phase_name": tb.phase_name(pid), "player_states": ps,
             "previous_phase_id": int(view["prev_phase_id"]), "end_turn": int(view["end_turn"])}
+
+
+# ---- AgentState -> room view: the inverse of view_to_agent_state / RoomLog.agent_state, for threads handed over mid-game
+_ACTION_TAG = re.compile(r"^\[t=(\d+)\|c=(\d+)\]")
+# integer slots and the largest value the record holds for them (None: the player count); the rest are booleans
+_WW_INTS = {8: None}
+_TT_INTS = {2: 3, 5: 3, 7: 255, 8: 15}
+
+
+def _phase_of(entry, where: str) -> int:
+    pid = entry.get("phase_id") if isinstance(entry, dict) else None
+    if not isinstance(pid, int) or isinstance(pid, bool):
+        raise ValueError(f"{where}: phase_history entries need an integer phase_id, got {entry!r}")
+    return pid
+
+
+_ACT_NIGHT = (1, 2, 3)                      # include/ge_step.h GE_ACT_WOLF_TARGET, GE_ACT_DOCTOR_PROTECT, GE_ACT_DETECTIVE
+_EFF_NIGHT_BEGIN = 2                       # GE_EFF_NIGHT_BEGIN
+
+
+def _derive_undeclared_ww(table: GameTable, v, n: int, pa: Dict[str, Any], hist_ids: List[int], visit: Dict[int, int], cur: int):
+    """Werewolf slots a DSL may leave undeclared (the reference's draft declares no has_secret_role, night_action_submitted or
+    selected_target_id) still drive the rules.  Their state then lives where the reference keeps it: in the role and the action
+    log.  has_secret_role = any role but Villager once roles are dealt; night_action_submitted / selected_target_id = the latest
+    night action (wolf target, protection, investigation) since the room last entered a night-begin phase, as the record effects
+    write and the night-begin effect clears them (POLICY.md 3)."""
+    names = table.field_names
+    if names[5] and names[7] and names[8]:
+        return
+    rows = {r["phase_id"]: r for r in table.rows()}
+    name_act = {r["name"]: r["act"] for r in rows.values()}
+    since = -1                                 # the last turn that entered a night-begin phase
+    for t, pid in enumerate(hist_ids):
+        if rows.get(pid, {}).get("effect") == _EFF_NIGHT_BEGIN and (t == 0 or hist_ids[t - 1] != pid):
+            since = t
+    night: Dict[int, Tuple[int, int]] = {}
+    for key, rec in pa.items():
+        try:
+            pid = int(key)
+        except (TypeError, ValueError):
+            continue
+        acts = (rec or {}).get("actions") or {} if isinstance(rec, dict) else {}
+        for a in (acts.values() if isinstance(acts, dict) else acts):
+            if not isinstance(a, dict) or name_act.get(a.get("phase")) not in _ACT_NIGHT:
+                continue
+            m = _ACTION_TAG.match(str(a.get("action", "")))
+            if m and since < int(m.group(1)) < len(hist_ids) and 1 <= pid <= n and int(m.group(1)) >= night.get(pid, (-1, 0))[0]:
+                night[pid] = (int(m.group(1)), int(m.group(2)))
+    if rows[cur]["act"] in _ACT_NIGHT:
+        for pid, c in visit.items():
+            night[pid] = (len(hist_ids), c)
+    for i in range(n):
+        f = v["players"][i]
+        if not names[5] and f[0] >= 2:
+            f[5] = 1
+        if i + 1 in night:
+            if not names[7]:
+                f[7] = 1
+            if not names[8]:
+                f[8] = night[i + 1][1]
+
+
+def agent_state_to_view(table: GameTable, state: Dict[str, Any], n_players: Optional[int] = None,
+                        visit_actions: Optional[Dict[Any, int]] = None) -> Tuple[np.ndarray, Dict[str, Any]]:
+    """The room view of a reference AgentState (agent/game_agent_v2.py:97-117: current_phase_id, player_states, playerActions,
+    phase_history) under the DSL's own field names: the exact inverse of view_to_agent_state and RoomLog.agent_state.
+
+    Returns (view, host_side).  host_side holds what the record does not carry and a host renders back: per player the `name`,
+    the Two-Truths `statements` text, and every key the record does not model ({"names", "statements", "extra"}, keyed "1".."n").
+    A modelled field the state leaves out takes the template's value (player_states_template).  Phase fields:
+      prev_phase_id  state["previous_phase_id"], else the phase of the phase_history entry before the trailing run of the current
+                     phase (the phase the room last left: phase_history[-2] when the last turn moved), else a fresh room's;
+      phase0_done    some phase_history entry is phase 0 (the guard of v2:1025-1052);
+      end_turn       state["end_turn"], else for a terminal phase the history index where its trailing run began, else -1;
+      games          state.get("games", 0).
+    acted / choice (this visit's log) come from the playerActions entries tagged "[t=<turn>|c=<choice>]" (as
+    toolcalls.turn_tool_calls writes them) filed under the current phase's name at a turn of the current visit; untagged entries
+    (a person's messages) are ignored.  visit_actions={player_id: choice} overrides that: how a host passes a human seat's
+    pending action.  The thread's next turn is len(phase_history) (one entry per run, v2:1207-1215).
+    Anything that does not fit, or that would not read back unchanged through view_to_agent_state, raises ValueError naming the
+    player and field; no library call is made."""
+    if not isinstance(state, dict):
+        raise ValueError("state must be a dict")
+    ww = table.pack == PACK_WEREWOLF
+    names = table.field_names
+    ps = state.get("player_states")
+    if not isinstance(ps, dict) or not ps:
+        raise ValueError("state['player_states'] must be a non-empty dict")
+    n = len(ps) if n_players is None else int(n_players)
+    if not 1 <= n <= GE_MAX_PLAYERS:
+        raise ValueError(f"{n} players: a room holds 1..{GE_MAX_PLAYERS}")
+    by_id: Dict[int, Dict[str, Any]] = {}
+    for key, rec in ps.items():
+        try:
+            pid = int(key)
+        except (TypeError, ValueError):
+            raise ValueError(f"player_states key {key!r} is not a player id") from None
+        if pid in by_id or not isinstance(rec, dict):
+            raise ValueError(f"player {key!r}: repeated or not a dict")
+        by_id[pid] = rec
+    if sorted(by_id) != list(range(1, n + 1)):
+        raise ValueError(f"player_states must name players 1..{n} exactly, got {sorted(by_id)}")
+    rows = table.rows()
+    ids = [r["phase_id"] for r in rows]
+    cur = state.get("current_phase_id")
+    if not isinstance(cur, int) or isinstance(cur, bool) or cur not in ids:
+        raise ValueError(f"current_phase_id {cur!r} is not a phase of the table")
+    hist = state.get("phase_history") or []
+    if not isinstance(hist, list):
+        raise ValueError("phase_history must be a list")
+    hist_ids = [_phase_of(e, "phase_history") for e in hist]
+    s = len(hist_ids)                                          # the trailing run of the current phase: hist[s:]
+    while s > 0 and hist_ids[s - 1] == cur:
+        s -= 1
+
+    v = np.zeros(1, dtype=ROOM_VIEW_DTYPE)[0]
+    v["n_players"], v["pack"] = n, table.pack
+    v["phase_id"] = cur
+    prev = state.get("previous_phase_id")
+    if prev is None:
+        prev = hist_ids[s - 1] if s > 0 else 0                 # a fresh room holds phase 0 as its previous phase
+    if not isinstance(prev, int) or isinstance(prev, bool) or prev not in ids:
+        raise ValueError(f"previous_phase_id {prev!r} is not a phase of the table")
+    v["prev_phase_id"] = prev
+    v["phase0_done"] = 1 if 0 in hist_ids else 0
+    end = state.get("end_turn")
+    if end is None:
+        end = min(s, 0xFFFE) if not rows[ids.index(cur)]["branches"] else -1
+    if not isinstance(end, int) or isinstance(end, bool) or not -1 <= end <= 0xFFFE:
+        raise ValueError(f"end_turn {end!r} is out of range (-1 .. 65534)")
+    v["end_turn"] = end
+    games = state.get("games", 0)
+    if not isinstance(games, int) or isinstance(games, bool) or not 0 <= games <= 0xFFFF:
+        raise ValueError(f"games {games!r} is out of range (0 .. 65535)")
+    v["games"] = games
+
+    roles = [table.role_name(c) for c in range(5)] if ww else []
+    teams = {t: k for k, t in enumerate(_TEAMS)}
+    ints = _WW_INTS if ww else _TT_INTS
+    n_slots = 9
+    modelled = {names[k] for k in range(_lib.GE_MAX_SLOTS) if names[k]} | {"name"}
+    host: Dict[str, Any] = {"names": {}, "statements": {}, "extra": {}}
+    for pid in range(1, n + 1):
+        rec, where = by_id[pid], f"player {pid}"
+        f = [int(x) for x in table.c.init_fields[:12]]
+        f[9] = f[10] = f[11] = 0
+        for k in range(n_slots):
+            name = names[k]
+            if not name or name not in rec:
+                continue
+            val = rec[name]
+            if ww and k == 0:
+                if val not in roles:
+                    raise ValueError(f"{where}: field {name!r}: unknown role {val!r} (the DSL declares {roles[1:]})")
+                f[k] = roles.index(val)
+            elif ww and k == 1:
+                if val not in teams:
+                    raise ValueError(f"{where}: field {name!r}: team {val!r} is not one of {_TEAMS}")
+                f[k] = teams[val]
+            elif k in ints:
+                hi = n if ints[k] is None else ints[k]
+                if not isinstance(val, int) or isinstance(val, bool) or not 0 <= val <= hi:
+                    raise ValueError(f"{where}: field {name!r}: {val!r} is not an integer in 0..{hi}")
+                f[k] = val
+            else:
+                if not isinstance(val, bool):
+                    raise ValueError(f"{where}: field {name!r}: {val!r} is not a boolean")
+                f[k] = int(val)
+        v["players"][pid - 1] = f
+        if ww and names[SLOT_DET_MEMORY] in rec:
+            mem = rec[names[SLOT_DET_MEMORY]]
+            field = names[SLOT_DET_MEMORY]
+            if not isinstance(mem, dict):
+                raise ValueError(f"{where}: field {field!r} must be a dict")
+            if mem and f[0] != 4:
+                raise ValueError(f"{where}: field {field!r}: only the {roles[4]} holds investigation results")
+            for q, team in mem.items():
+                try:
+                    qi = int(q)
+                except (TypeError, ValueError):
+                    qi = 0
+                if not 1 <= qi <= n or team not in ("villagers", "werewolves"):
+                    raise ValueError(f"{where}: field {field!r}: entry {q!r}: {team!r} must name a player 1..{n} and a team")
+                v["det"][qi - 1] = teams[team]
+        host["names"][str(pid)] = rec.get("name", f"Player {pid}")
+        if not ww and names[SLOT_STATEMENTS]:
+            st = rec.get(names[SLOT_STATEMENTS], {})
+            if not isinstance(st, dict):
+                raise ValueError(f"{where}: field {names[SLOT_STATEMENTS]!r} must be a dict")
+            host["statements"][str(pid)] = dict(st)
+        extra = {k: val for k, val in rec.items() if k not in modelled}
+        if extra:
+            host["extra"][str(pid)] = extra
+
+    # acted / choice: this visit's latest tagged action per player (turns past the one that entered the phase; a room that
+    # never left phase 0 has been in it since turn 0)
+    cur_name = table.phase_name(cur)
+    first = 0 if (s == 0 and cur == 0) else s + 1
+    latest: Dict[int, Tuple[int, int]] = {}
+    pa = state.get("playerActions") or {}
+    if not isinstance(pa, dict):
+        raise ValueError("playerActions must be a dict")
+    for key, rec in pa.items():
+        try:
+            pid = int(key)
+        except (TypeError, ValueError):
+            continue
+        acts = (rec or {}).get("actions") or {} if isinstance(rec, dict) else {}
+        for a in (acts.values() if isinstance(acts, dict) else acts):
+            if not isinstance(a, dict) or a.get("phase") != cur_name:
+                continue
+            m = _ACTION_TAG.match(str(a.get("action", "")))
+            if not m:
+                continue
+            t, c = int(m.group(1)), int(m.group(2))
+            if first <= t < len(hist_ids) and 1 <= pid <= n and t >= latest.get(pid, (-1, 0))[0]:
+                latest[pid] = (t, c)
+    acted = {pid: c for pid, (_, c) in latest.items()}
+    for key, c in (visit_actions or {}).items():
+        acted[int(key)] = c
+    top = n if ww else 3
+    for pid, c in acted.items():
+        if not 1 <= pid <= n or not isinstance(c, int) or isinstance(c, bool) or not 1 <= c <= top:
+            raise ValueError(f"player {pid}: visit action {c!r} is not a choice in 1..{top}")
+        v["players"][pid - 1][9], v["players"][pid - 1][10] = 1, c
+    if ww:
+        _derive_undeclared_ww(table, v, n, pa, hist_ids, {int(k): c for k, c in (visit_actions or {}).items()}, cur)
+
+    # self-check: every modelled field reads back as given
+    back = view_to_agent_state(table, v)["player_states"]
+    for pid in range(1, n + 1):
+        rec, got = by_id[pid], back[str(pid)]
+        for k in range(_lib.GE_MAX_SLOTS):
+            name = names[k]
+            if not name or name not in rec or name not in got:
+                continue
+            want = rec[name]
+            if ww and k == SLOT_DET_MEMORY:
+                want = {str(q): t for q, t in want.items()}
+            if got[name] != want or type(got[name]) is not type(want):
+                raise ValueError(f"player {pid}: field {name!r} = {want!r} does not fit the record (it reads back as {got[name]!r})")
+    return v, host

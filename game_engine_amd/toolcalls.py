@@ -168,6 +168,18 @@ class RoomLog:
         self.game_notes: List[str] = []
         self.phase_history: List[Dict[str, Any]] = []
         self.statements: Dict[str, Dict[str, str]] = {}
+        self.extra: Dict[str, Dict[str, Any]] = {}            # per player: fields the record does not model (an adopted thread's)
+
+    def adopt(self, state: Dict[str, Any], host_side: Dict[str, Any]) -> None:
+        """Seed the log of a thread handed over mid-game: its playerActions, game_notes and phase_history, and the host-side
+        fields agent_state_to_view returned (names, statements, fields the record does not model)."""
+        import copy
+        self.player_actions = copy.deepcopy(state.get("playerActions") or {})
+        self.game_notes = list(state.get("game_notes") or [])
+        self.phase_history = copy.deepcopy(list(state.get("phase_history") or []))
+        self.names = [host_side["names"].get(str(i + 1), name) for i, name in enumerate(self.names)]
+        self.statements = copy.deepcopy(host_side.get("statements") or {})
+        self.extra = copy.deepcopy(host_side.get("extra") or {})
 
     def fold(self, calls: List[Dict[str, Any]], after, now_ms: Optional[int] = None) -> None:
         """Apply one turn's calls; `after`: the room view after the turn."""
@@ -219,6 +231,7 @@ class RoomLog:
                 out[k] = v
                 if tt and k == self.table.field_names[TT_IS_SPEAKER] and self.table.field_names[SLOT_STATEMENTS]:
                     out[self.table.field_names[SLOT_STATEMENTS]] = dict(self.statements.get(pid, {}))
+            out.update(self.extra.get(pid, {}))
             s["player_states"][pid] = out
         s.update(gameName=self.game_name, playerActions=self.player_actions, phase_history=self.phase_history,
                  game_notes=self.game_notes)

@@ -39,7 +39,7 @@ extern "C" {
  *   5  ge_group_partition + ge_batch_create_shard (the group's sharding arithmetic for hosts that place shards themselves); ge_last_rejected_room;
  *      mixed and generic batches get single-turn kernel builds; the Werewolf x 12 deal side plane is allocated on first use;
  *      later additions, new symbols only (the version stays 5): ge_batch_step_rooms + ge_batch_read_rooms_at (many game threads
- *      in one resident batch, each room stepped under its own key and turn) */
+ *      in one resident batch, each room stepped under its own key and turn); ge_batch_write_rooms_at (the indexed write) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -310,6 +310,12 @@ int ge_batch_step_rooms(ge_batch *b, uint64_t n, const uint64_t *rooms, const ui
  * records into the staging buffer, one copy, host-side unpacking as in ge_batch_read_rooms.  GE_ERR_RANGE for a room
  * outside the batch.  cap_bytes >= n * sizeof(ge_room_view).  Synchronises. */
 int ge_batch_read_rooms_at(ge_batch *b, uint64_t n, const uint64_t *rooms, ge_room_view *dst, size_t cap_bytes);
+/* The scatter twin: src[k] is stored into batch room rooms[k] (a thread adopted mid-game into a slot of a resident batch).
+ * The record stored is exactly what ge_batch_write_rooms stores for the same view (no prepared role deal).  All-or-nothing:
+ * GE_ERR_RANGE for a room outside the batch, GE_ERR_ARG for a repeated room or for a view that does not fit the segment its
+ * room lies in (as ge_batch_write_rooms checks it; ge_last_rejected_room() then names that entry's batch room); nothing is
+ * written then.  n == 0: GE_OK.  One copy through the staging buffer, one device scatter.  Synchronises. */
+int ge_batch_write_rooms_at(ge_batch *b, uint64_t n, const uint64_t *rooms, const ge_room_view *src);
 
 /* GE_FLAG_TRACE: events of the most recent ge_batch_step call, dst[(room - first) * *n_turns + t].
  * cap_bytes >= count * n_turns * sizeof(ge_turn_event).  Synchronises. */
@@ -364,7 +370,7 @@ int ge_last_comm_error(void);             /* ncclResult_t of the last GE_ERR_COM
 
 const char *ge_strerror(int status);
 int ge_last_hip_error(void);              /* hipError_t of the last GE_ERR_HIP on this thread */
-uint64_t ge_last_rejected_room(void);     /* ge_batch_write_rooms returned GE_ERR_ARG for a view that does not fit its segment: the index (in the batch) of
+uint64_t ge_last_rejected_room(void);     /* ge_batch_write_rooms(_at) returned GE_ERR_ARG for a view that does not fit its segment: the index (in the batch) of
                                              the first such room, on this thread; ~0 if none yet (ABI 5) */
 int ge_abi_version(void);
 int ge_device_count(void);                /* number of HIP devices, 0 if none; never fails */
