@@ -1,0 +1,332 @@
+// ge_rollout.inl — on-device playouts (ge_batch_rollout_rooms): from where a room stands, R replicas of it are played to the end
+// (or for M turns) and only their outcome is reduced (included at the end of ge_step.hip, behind ge_pool.inl: the existing kernels
+// keep their code-object offsets; it needs ge_batch's internals and ge_pool.inl's helpers).
+//
+// Replica r of entry k is what a lone batch B' (seed, first_room = keys[k], flags 0, one segment of R rooms with human mask 0)
+// does to a copy of batch room rooms[k] under set_turn(turns[k]) + step(M): global room keys[k] + r at turns turns[k] ..
+// turns[k] + M - 1, every seat played by the policy, a terminal phase absorbing (no GE_FLAG_RESTART).  The result of entry k is
+// ge_batch_summary(B') word for word plus per-seat counts (ge_rollout_stats).
+//
+// One wavefront per (entry, 64 replicas); the lane is the replica.  Nothing of a replica lives in HBM: the source record is loaded
+// once (the same address in every lane), unpacked into registers and stepped there with the single-turn ww_turn / tt_turn of the
+// lone-wavefront build (tables read where they lie in global memory, as ge_pool_kernel does).  Lanes past R stay in the wavefront
+// (the action queue is a wave-wide collective): they play replica 0's game again, acting as it does, so that they settle when it
+// does, and add nothing.  Prepared role deals are never used (Deal
+// {0}: an assignment deals on the spot), so neither the record's deal cache nor the Werewolf x 12 side plane is read.
+//
+// Early exit.  A turn taken from a terminal phase with restart off moves nowhere (no branch) and applies no effect, but it is not
+// always a no-op: bots still act where the terminal row's completion is "action" (orc_room_step / ww_turn / tt_turn log them), and
+// the phase-0 guard sets its flag.  A replica is settled when its phase is terminal, that row's completion is not "action" (the
+// host's settle mask) and the guard is behind it (not phase 0, or its flag set): then no bot is due, nothing is drawn, and every
+// further turn leaves the record bit-identical.  A wavefront leaves the turn loop once __ballot shows every lane settled.
+//
+// Reduction.  Per wavefront: ballot + popc for the booleans, wave_sum (ge_kernels.inl) for the sums, LDS atomics for the two
+// histograms (as ge_summary_kernel); then one lane per field adds the wavefront's non-zero fields to the entry's 75 accumulator
+// words with u64 global atomics.  Chosen over per-wave partials + a reduce kernel because partials would need a buffer of
+// n * R / 64 records (up to 600 B x 2^20 wavefronts at the caps) and a second launch, while the atomics are at most 75 per
+// wavefront after tens to hundreds of turns of work each.  Every field is an integer sum, so the result does not depend on the
+// order the wavefronts arrive in.
+
+namespace {
+
+// accumulator words of one entry: [0] finished [1] village [2] wolves [3] alive [4] sum_end [5..20] end hist [21..36] score hist
+// [37] checksum [38] games [39..50] seat_alive [51..62] seat_wins [63..74] seat_score (stride ROLL_STRIDE)
+constexpr uint32_t ROLL_FIELDS = 75, ROLL_STRIDE = 80;
+
+struct RolloutArgs {
+    const uint64_t *rooms;      // segment-local source room of each entry of this launch
+    const uint64_t *keys;       // replica r of entry e is global room keys[e] + r
+    const uint32_t *turns;      // its first turn
+    unsigned long long *acc;    // [n] x ROLL_STRIDE accumulator words, zeroed by the host
+    uint32_t n, seg, seed_key, n_rollouts, max_turns, waves;   // waves: wavefronts per entry (ceil(R / 64))
+    uint32_t settle_mask;       // bit p = row p is terminal and its completion is not "action"
+};
+
+struct RollLane {
+    RoomStats q;                // (zero on lanes past R)
+    uint64_t ck;
+    uint32_t alive_mask, win_mask;
+};
+
+// a wave-uniform 64-bit value in scalar registers (readfirstlane returns int: each half is taken back as uint32_t before widening)
+__device__ __forceinline__ uint64_t uniform_u64(uint64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+
+__device__ __forceinline__ uint32_t roll_popc(bool b) { return (uint32_t)__popcll(__ballot(b)); }
+
+// the wavefront's contribution -> the entry's accumulator words (lane 0 holds every wave_sum; the block is one wavefront)
+template <int NB>
+__device__ __forceinline__ void roll_reduce(const RollLane &l, bool valid, const uint32_t *score, unsigned long long *part, uint32_t *h_end,
+                                            const uint32_t *h_score, unsigned long long *acc) {
+    const uint32_t lane = threadIdx.x;
+    const bool ended = valid && l.q.finished && l.q.end_turn != END_NONE;
+    if (ended) atomicAdd(&h_end[(l.q.end_turn >> 3) < 15 ? (l.q.end_turn >> 3) : 15], 1u);
+    const uint64_t v3 = wave_sum(l.q.alive), v4 = wave_sum(ended ? l.q.end_turn : 0u), v5 = wave_sum(l.ck), v6 = wave_sum(l.q.games);
+    uint64_t sc[NB];
+#pragma unroll
+    for (int i = 0; i < NB; i++) sc[i] = wave_sum(score[i]);
+    uint32_t alive_n[NB], win_n[NB];
+#pragma unroll
+    for (int i = 0; i < NB; i++) {
+        alive_n[i] = roll_popc(valid && ((l.alive_mask >> i) & 1u));
+        win_n[i] = roll_popc(valid && ((l.win_mask >> i) & 1u));
+    }
+    const uint32_t fin = roll_popc(valid && l.q.finished), vil = roll_popc(valid && l.q.village), wol = roll_popc(valid && l.q.wolves);
+    if (lane == 0) {
+        part[0] = fin; part[1] = vil; part[2] = wol; part[3] = v3; part[4] = v4; part[37] = v5; part[38] = v6;
+#pragma unroll
+        for (int i = 0; i < 12; i++) {
+            part[39 + i] = i < NB ? alive_n[i < NB ? i : 0] : 0u;
+            part[51 + i] = i < NB ? win_n[i < NB ? i : 0] : 0u;
+            part[63 + i] = i < NB ? sc[i < NB ? i : 0] : 0u;
+        }
+    }
+    __syncthreads();
+    if (lane < 16) { part[5 + lane] = h_end[lane]; part[21 + lane] = h_score[lane]; }
+    __syncthreads();
+    for (uint32_t f = lane; f < ROLL_FIELDS; f += 64u) {
+        const unsigned long long v = part[f];
+        if (v) atomicAdd(&acc[f], v);
+    }
+}
+
+__device__ __forceinline__ uint64_t roll_ck(uint32_t h_words) {
+    return (uint64_t)h_words | ((uint64_t)mix32(h_words ^ 0x5BD1E995u) << 32);
+}
+__device__ __forceinline__ uint32_t roll_h0(uint64_t g) { return mix32((uint32_t)g ^ mix32((uint32_t)(g >> 32) ^ 0xA5A5A5A5u)); }
+
+template <int NB, int GENERIC>
+__device__ __forceinline__ void roll_ww(const SegDev &sg, const DevTable *__restrict__ tables, const RolloutArgs &a, void *lw, uint32_t e,
+                                        uint32_t r_in, unsigned long long *part, uint32_t *h_end, uint32_t *h_score) {
+    using L = WWLayout<NB>;
+    const bool valid = r_in < a.n_rollouts;
+    const uint32_t r = valid ? r_in : 0u;
+    const uint64_t room = uniform_u64(a.rooms[e]), key = uniform_u64(a.keys[e]);
+    const uint32_t turn0 = (uint32_t)__builtin_amdgcn_readfirstlane(a.turns[e]);
+    uint32_t w[L::WORDS];
+    load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+    const uint64_t g = key + r;
+    const uint32_t rk = room_key_from(a.seed_key, g);
+    const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
+    const DevRow *rows = reinterpret_cast<const DevRow *>(img);
+    const CondShape cs = GENERIC ? pool_cond_shape(tables[sg.table_idx]) : CondShape{0u, 0u, 0u, 0u, 0u};
+    const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
+    const uint32_t phase0 = __builtin_amdgcn_readfirstlane(sg.phase0_idx);
+    const WwCtx ctx = {rows, CondCtx{reinterpret_cast<const unsigned char *>(tables[sg.table_idx].cond_img), cs}, lw, img + IMG_NTH8,
+                       reinterpret_cast<const uint32_t *>(img + IMG_ORD8), true, sg.n_players, sg.nw, sg.phase0_idx, rk, 0u, term_mask};
+    WWR<NB> s;
+    uint32_t cache;                                           // the record's prepared deal: not of these keys, never used
+    ww_load_regs<NB>(w, s, cache);
+    for (uint32_t t = 0; t < a.max_turns; t++) {
+        DevRow row = lds_row<false>(rows, s.phase);
+        Deal deal = {0u, 0u, 0u, 0u, 0u};
+        uint32_t tk = turn_key(rk, turn0 + t);
+        uint32_t ev_newly = 0;
+        uint64_t ev_choice = 0;
+        ww_turn<NB, true, GENERIC, true>(s, row, ctx, turn0 + t, tk, false, deal, false, ev_newly, ev_choice, nullptr);
+        const bool settled = ((a.settle_mask >> s.phase) & 1u) && (s.phase != phase0 || (s.flags & FLAG_PHASE0_DONE));
+        if (__ballot(!settled) == 0ull) break;
+    }
+    ww_store_regs<NB>(s, 0u, w);                              // the canonical record: no prepared deal
+    RollLane l;
+    l.q = stats_ww<NB>(w, rows, h_score);
+    if (NB == 8) w[7] &= WWLayout<8>::CHECKSUM_MASK7;
+    l.ck = roll_ck(fold_words<L::WORDS>(roll_h0(g), w));
+    const uint32_t alive = s.template get<F_ALIVE>();
+    l.alive_mask = alive;
+    l.win_mask = !l.q.finished ? 0u : (l.q.village ? s.template get<F_TEAM_V>() : s.template get<F_TEAM_W>());
+    if (!valid) { l.q = RoomStats{0, 0, 0, 0, 0, 0}; l.ck = 0; }
+    uint32_t score[NB];
+#pragma unroll
+    for (int i = 0; i < NB; i++) score[i] = 0u;
+    roll_reduce<NB>(l, valid, score, part, h_end, h_score, a.acc + (size_t)e * ROLL_STRIDE);
+}
+
+template <int NB, int GENERIC>
+__device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__restrict__ tables, const RolloutArgs &a, void *lw, uint32_t e,
+                                        uint32_t r_in, unsigned long long *part, uint32_t *h_end, uint32_t *h_score) {
+    using L = TTLayout<NB>;
+    const bool valid = r_in < a.n_rollouts;
+    const uint32_t r = valid ? r_in : 0u;
+    const uint64_t room = uniform_u64(a.rooms[e]), key = uniform_u64(a.keys[e]);
+    const uint32_t turn0 = (uint32_t)__builtin_amdgcn_readfirstlane(a.turns[e]);
+    uint32_t w[L::WORDS];
+    load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+    const uint64_t g = key + r;
+    const uint32_t rk = room_key_from(a.seed_key, g);
+    const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
+    const DevRow *rows = reinterpret_cast<const DevRow *>(img);
+    const CondShape cs = GENERIC ? pool_cond_shape(tables[sg.table_idx]) : CondShape{0u, 0u, 0u, 0u, 0u};
+    const CondCtx cc = {reinterpret_cast<const unsigned char *>(tables[sg.table_idx].cond_img), cs};
+    const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
+    const uint32_t phase0 = __builtin_amdgcn_readfirstlane(sg.phase0_idx);
+    TT<NB> s;
+    L::unpack(w, s);
+    uint32_t done = tt_done_mask<NB>(s.rounds, sg.rounds);
+    for (uint32_t t = 0; t < a.max_turns; t++) {
+        DevRow row = lds_row<false>(rows, s.phase);
+        uint32_t ev_newly = 0;
+        uint64_t ev_choice = 0;
+        tt_turn<NB, tt_uses_queue(NB, true), false, GENERIC, true>(s, done, row, rows, cc, lw, img + IMG_NTH8, true, sg.n_players, sg.rounds,
+                                                                 sg.phase0_idx, rk, turn0 + t, false, 0u, term_mask, ev_newly, ev_choice);
+        const bool settled = ((a.settle_mask >> s.phase) & 1u) && (s.phase != phase0 || (s.flags & FLAG_PHASE0_DONE));
+        if (__ballot(!settled) == 0ull) break;
+    }
+    L::pack(s, w);
+    RollLane l;
+    l.q = stats_tt<NB>(w, rows, valid ? sg.n_players : 0u, h_score);   // (0 players: a lane past R adds nothing to the histogram)
+    l.ck = roll_ck(fold_words<L::WORDS>(roll_h0(g), w));
+    uint32_t score[NB], top = 0;
+#pragma unroll
+    for (int i = 0; i < NB; i++) {                            // static indices: no scratch
+        score[i] = (uint32_t)i < sg.n_players ? (s.score[i / 4] >> (8 * (i % 4))) & 255u : 0u;
+        top = score[i] > top ? score[i] : top;
+    }
+    uint32_t win = 0;
+#pragma unroll
+    for (int i = 0; i < NB; i++) win |= ((uint32_t)i < sg.n_players && score[i] == top ? 1u : 0u) << i;
+    l.alive_mask = 0;
+    l.win_mask = l.q.finished ? win : 0u;
+    if (!valid) {
+        l.q = RoomStats{0, 0, 0, 0, 0, 0}; l.ck = 0;
+#pragma unroll
+        for (int i = 0; i < NB; i++) score[i] = 0u;
+    }
+    roll_reduce<NB>(l, valid, score, part, h_end, h_score, a.acc + (size_t)e * ROLL_STRIDE);
+}
+
+// one wavefront per block = one entry's 64 replicas; its action queue (WaveLdsLow) is the block's dynamic LDS (none for
+// Two-Truths x 4: no queue)
+template <int KIND, int GENERIC>
+__global__ void __launch_bounds__(64) ge_rollout_kernel(const SegDev *__restrict__ segs, const DevTable *__restrict__ tables, const RolloutArgs a) {
+    __shared__ unsigned long long part[ROLL_FIELDS];
+    __shared__ uint32_t h_end[16], h_score[16];
+    const SegDev &sg = segs[a.seg];
+    const uint32_t e = blockIdx.x / a.waves, r = (blockIdx.x - e * a.waves) * 64u + threadIdx.x;
+    if (threadIdx.x < ROLL_FIELDS) part[threadIdx.x] = 0;
+    if (threadIdx.x < 16) { h_end[threadIdx.x] = 0; h_score[threadIdx.x] = 0; }
+    __syncthreads();
+    void *lw = ge_lds;
+    if (KIND == K_WW8) roll_ww<8, GENERIC>(sg, tables, a, lw, e, r, part, h_end, h_score);
+    else if (KIND == K_WW12) roll_ww<12, GENERIC>(sg, tables, a, lw, e, r, part, h_end, h_score);
+    else if (KIND == K_TT4) roll_tt<4, GENERIC>(sg, tables, a, lw, e, r, part, h_end, h_score);
+    else if (KIND == K_TT8) roll_tt<8, GENERIC>(sg, tables, a, lw, e, r, part, h_end, h_score);
+    else roll_tt<12, GENERIC>(sg, tables, a, lw, e, r, part, h_end, h_score);
+}
+
+template <int GEN> hipError_t rollout_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const RolloutArgs &a) {
+    const uint32_t lds = (kind == K_TT4) ? 0u : (uint32_t)sizeof(WaveLdsLow);
+    switch (kind) {
+    case K_WW8: hipLaunchKernelGGL((ge_rollout_kernel<K_WW8, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
+    case K_WW12: hipLaunchKernelGGL((ge_rollout_kernel<K_WW12, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
+    case K_TT4: hipLaunchKernelGGL((ge_rollout_kernel<K_TT4, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
+    case K_TT8: hipLaunchKernelGGL((ge_rollout_kernel<K_TT8, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
+    default: hipLaunchKernelGGL((ge_rollout_kernel<K_TT12, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
+    }
+    return hipGetLastError();
+}
+
+// bit p = row p of the segment's table is terminal and no bot acts in it (see "Early exit" above)
+uint32_t rollout_settle_mask(const Segment &sg) {
+    uint32_t m = 0;
+    for (int p = 0; p < sg.table.n_phases && p < 32; p++)
+        if (((sg.dev.term_mask >> p) & 1u) && sg.table.rows[p].completion != GE_COMP_ACTION) m |= 1u << p;
+    return m;
+}
+
+}  // namespace
+
+static int rollout_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, uint32_t n_rollouts,
+                              uint32_t max_turns, uint64_t seed, ge_rollout_stats *out) {
+    GE_ON_DEVICE(b);
+    int st = sync_impl(b);
+    if (st != GE_OK) return st;
+    const uint32_t n_seg = (uint32_t)b->segs.size();
+    const uint32_t waves = (n_rollouts + 63u) / 64u;
+    const uint32_t seed_k = seed_key((uint32_t)seed, (uint32_t)(seed >> 32));
+    std::vector<uint32_t> settle(n_seg);
+    for (uint32_t g = 0; g < n_seg; g++) settle[g] = rollout_settle_mask(b->segs[g]);
+    // entries in chunks (bounded staging and accumulator memory); within a chunk a stable counting sort by segment, one launch
+    // per segment present (a wavefront never mixes layouts)
+    const uint64_t CHUNK = 65536;
+    for (uint64_t c0 = 0; c0 < n; c0 += CHUNK) {
+        const uint32_t cn = (uint32_t)std::min<uint64_t>(CHUNK, n - c0);
+        std::vector<uint32_t> seg_of(cn), begin(n_seg + 1u, 0u), order(cn);
+        for (uint32_t k = 0; k < cn; k++) { seg_of[k] = pool_segment_of(b, rooms[c0 + k]); begin[seg_of[k] + 1u]++; }
+        for (uint32_t s = 0; s < n_seg; s++) begin[s + 1u] += begin[s];
+        {
+            std::vector<uint32_t> at(begin.begin(), begin.end() - 1);
+            for (uint32_t k = 0; k < cn; k++) order[at[seg_of[k]]++] = k;
+        }
+        // one upload: [rooms u64 x cn][keys u64 x cn][turns u32 x cn (padded to 16 B)], then the accumulators 8 B x ROLL_STRIDE x cn
+        const size_t off_keys = 8 * (size_t)cn, off_turns = 16 * (size_t)cn, off_acc = (off_turns + 4 * (size_t)cn + 15u) & ~(size_t)15u;
+        const size_t acc_bytes = 8 * (size_t)ROLL_STRIDE * cn, total = off_acc + acc_bytes;
+        uint32_t *host32 = nullptr;
+        if ((st = io_stage(b, total, &host32)) != GE_OK) return st;
+        unsigned char *host = reinterpret_cast<unsigned char *>(host32);
+        uint64_t *h_rooms = reinterpret_cast<uint64_t *>(host), *h_keys = reinterpret_cast<uint64_t *>(host + off_keys);
+        uint32_t *h_turns = reinterpret_cast<uint32_t *>(host + off_turns);
+        for (uint32_t i = 0; i < cn; i++) {
+            const uint64_t k = c0 + order[i];
+            h_rooms[i] = rooms[k] - b->segs[seg_of[order[i]]].local_first;
+            h_keys[i] = keys[k];
+            h_turns[i] = turns[k];
+        }
+        char *dev = nullptr;
+        if ((st = pool_scratch(b, total, &dev)) != GE_OK) return st;
+        hipStream_t s = b->last_stream;
+        if ((st = order_after_previous(b, s)) != GE_OK) return st;
+        HIP_TRY(hipMemcpyAsync(dev, host, off_acc, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(dev + off_acc, 0, acc_bytes, s));
+        for (uint32_t g = 0; g < n_seg; g++) {
+            const uint32_t lo = begin[g], cnt = begin[g + 1u] - lo;
+            if (!cnt) continue;
+            RolloutArgs a;
+            a.rooms = reinterpret_cast<const uint64_t *>(dev) + lo;
+            a.keys = reinterpret_cast<const uint64_t *>(dev + off_keys) + lo;
+            a.turns = reinterpret_cast<const uint32_t *>(dev + off_turns) + lo;
+            a.acc = reinterpret_cast<unsigned long long *>(dev + off_acc) + (size_t)ROLL_STRIDE * lo;
+            a.n = cnt; a.seg = g; a.seed_key = seed_k; a.n_rollouts = n_rollouts; a.max_turns = max_turns; a.waves = waves;
+            a.settle_mask = settle[g];
+            const dim3 grid(cnt * waves);                         // <= 2^26 blocks (n * R <= 2^26)
+            HIP_TRY(b->generic ? rollout_launch<1>(b->segs[g].dev.kind, grid, s, b, a) : rollout_launch<0>(b->segs[g].dev.kind, grid, s, b, a));
+        }
+        const unsigned long long *h_acc = reinterpret_cast<const unsigned long long *>(host + off_acc);
+        HIP_TRY(hipMemcpyAsync(host + off_acc, dev + off_acc, acc_bytes, hipMemcpyDeviceToHost, s));
+        if ((st = sync_impl(b)) != GE_OK) return st;
+        for (uint32_t i = 0; i < cn; i++) {                      // scattered back into input order
+            const uint64_t k = c0 + order[i];
+            const unsigned long long *h = h_acc + (size_t)ROLL_STRIDE * i;
+            ge_rollout_stats &o = out[k];
+            memset(&o, 0, sizeof o);
+            o.summary.rooms = n_rollouts;
+            o.summary.finished = h[0]; o.summary.village_wins = h[1]; o.summary.wolf_wins = h[2]; o.summary.alive_players = h[3];
+            o.summary.sum_end_turn = h[4];
+            for (int j = 0; j < 16; j++) { o.summary.end_turn_hist[j] = h[5 + j]; o.summary.score_hist[j] = h[21 + j]; }
+            o.summary.checksum = h[37];
+            o.summary.turn = (uint64_t)turns[k] + max_turns;
+            o.summary.games_recycled = h[38];
+            for (int j = 0; j < 12; j++) { o.seat_alive[j] = h[39 + j]; o.seat_wins[j] = h[51 + j]; o.seat_score[j] = h[63 + j]; }
+        }
+    }
+    return GE_OK;
+}
+
+extern "C" {
+
+int ge_batch_rollout_rooms(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, uint32_t n_rollouts,
+                           uint32_t max_turns, uint64_t seed, ge_rollout_stats *out) {
+    if (!b) return GE_ERR_ARG;
+    if (n == 0) return GE_OK;
+    // every entry is checked before anything runs; on an error *out is untouched
+    if (!rooms || !keys || !turns || !out) return GE_ERR_ARG;
+    if (n_rollouts == 0 || n_rollouts > (1u << 20) || n > (1ull << 26) || n * (uint64_t)n_rollouts > (1ull << 26) || max_turns > 4096u)
+        return GE_ERR_ARG;
+    for (uint64_t k = 0; k < n; k++)
+        if (rooms[k] >= b->n_rooms || (uint64_t)turns[k] + max_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;
+    return guarded([&] { return rollout_rooms_impl(b, n, rooms, keys, turns, n_rollouts, max_turns, seed, out); });
+}
+
+}  // extern "C"

@@ -480,6 +480,42 @@ napi_value StepRooms(napi_env env, napi_callback_info info) {
     return out;
 }
 
+// rolloutRooms(batch, rooms: BigUint64Array, keys: BigUint64Array, turns: Uint32Array, nRollouts, maxTurns, seed: bigint):
+// BigUint64Array of rooms.length x 77 words (ge_rollout_stats k at [77 k, 77 k + 77)) - playouts of each listed room
+napi_value RolloutRooms(napi_env env, napi_callback_info info) {
+    size_t argc = 7;
+    napi_value argv[7];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
+    if (!b || argc < 7) return throw_status(env, GE_ERR_ARG, "rolloutRooms");
+    napi_typedarray_type tt[3];
+    size_t len[3];
+    void *data[3];
+    for (int k = 0; k < 3; k++) {
+        napi_value ab;
+        size_t off;
+        if (napi_get_typedarray_info(env, argv[1 + k], &tt[k], &len[k], &data[k], &ab, &off) != napi_ok)
+            return throw_status(env, GE_ERR_ARG, "rolloutRooms", "typed arrays expected");
+    }
+    if (tt[0] != napi_biguint64_array || tt[1] != napi_biguint64_array || tt[2] != napi_uint32_array || len[0] != len[1] || len[1] != len[2])
+        return throw_status(env, GE_ERR_ARG, "rolloutRooms", "BigUint64Array, BigUint64Array, Uint32Array of equal length");
+    uint32_t n_rollouts = 0, max_turns = 0;
+    uint64_t seed = 0;
+    if (napi_get_value_uint32(env, argv[4], &n_rollouts) != napi_ok || napi_get_value_uint32(env, argv[5], &max_turns) != napi_ok ||
+        !get_u64(env, argv[6], &seed))
+        return throw_status(env, GE_ERR_ARG, "rolloutRooms", "nRollouts, maxTurns: numbers; seed: bigint");
+    const size_t words = sizeof(ge_rollout_stats) / 8;
+    void *out = nullptr;
+    napi_value buf, arr;
+    NAPI_OK(napi_create_arraybuffer(env, len[0] * sizeof(ge_rollout_stats), &out, &buf));
+    const int st = ge_batch_rollout_rooms(b, len[0], static_cast<const uint64_t *>(data[0]), static_cast<const uint64_t *>(data[1]),
+                                          static_cast<const uint32_t *>(data[2]), n_rollouts, max_turns, seed,
+                                          static_cast<ge_rollout_stats *>(out));
+    if (st != GE_OK) return throw_status(env, st, "rolloutRooms");
+    NAPI_OK(napi_create_typedarray(env, napi_biguint64_array, len[0] * words, buf, 0, &arr));
+    return arr;
+}
+
 // readRoomsAt(batch, rooms: BigUint64Array): ArrayBuffer of rooms.length ge_room_view, view k = room rooms[k]
 napi_value ReadRoomsAt(napi_env env, napi_callback_info info) {
     size_t argc = 2;
@@ -751,6 +787,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"readEvents", nullptr, ReadEvents, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"stepRooms", nullptr, StepRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"readRoomsAt", nullptr, ReadRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"rolloutRooms", nullptr, RolloutRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"writeRoomsAt", nullptr, WriteRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"summary", nullptr, Summary, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"reset", nullptr, Reset, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -68,6 +68,10 @@ export class RoomBatch {
   readEvents(first: number, count: number): TurnEvent[][];
   /** One turn of each listed room (local, pairwise distinct), room k keyed as global room keys[k] at turn turns[k]; event k of room k. */
   stepRooms(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>): TurnEvent[];
+  /** Playouts of each listed room (replica r of entry k = global room keys[k] + r under seed, default the batch's): rooms.length x 77
+   *  words of ge_rollout_stats (41 summary words, then seat_alive, seat_wins, seat_score x 12).  The batch is only read. */
+  rolloutRooms(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, nRollouts: number,
+               maxTurns?: number, seed?: bigint | number): BigUint64Array;
   /** out[k] = room rooms[k] (any order, repeats allowed). */
   readRoomsAt(rooms: ArrayLike<number | bigint>): RoomState[];
   readRoomsAtRaw(rooms: ArrayLike<number | bigint>): ArrayBuffer;

@@ -509,6 +509,7 @@ class RoomBatch {
   /** segments: [{table: GameTable, nPlayers, nRooms}] */
   constructor({ segments, seed = 0n, firstRoom = 0n, device = 0, maxFuse = 0, restart = false, trace = false }) {
     this.segments = segments;
+    this.seed = BigInt(seed);
     this.handle = addon.createBatch({
       seed, firstRoom, device, maxFuse, restart, trace,
       segments: segments.map((s) => ({ table: s.table.handle, nPlayers: s.nPlayers, nRooms: s.nRooms, humanMask: s.humanMask || 0 })),
@@ -578,6 +579,14 @@ class RoomBatch {
     const out = [];
     for (let k = 0; k < rooms.length; k++) out.push(decodeEvent(buffer, k * EVENT_SIZE));
     return out;
+  }
+  /** Playouts (twin of the Python RoomBatch.rollout_rooms): entry k is played nRollouts times from room rooms[k] as it stands,
+   * replica r as global room keys[k] + r (mod 2^64) under `seed` (default: the batch's) at turns turns[k] .. turns[k] + maxTurns - 1,
+   * every seat played by the policy and a finished game left finished.  Returns a BigUint64Array of rooms.length x 77 words
+   * (ge_rollout_stats: the 41 summary words, then seat_alive, seat_wins, seat_score x 12).  The batch is only read.  Synchronous. */
+  rolloutRooms(rooms, keys, turns, nRollouts, maxTurns = 1024, seed) {
+    return addon.rolloutRooms(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r)), BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))),
+                              Uint32Array.from(turns), nRollouts, maxTurns, seed === undefined ? this.seed : BigInt(seed));
   }
   /** The listed rooms' states, out[k] = room rooms[k] (any order, repeats allowed). */
   readRoomsAt(rooms) {

@@ -1,5 +1,5 @@
 // Types for room_pool.js — many game threads hosted in a few resident batches.
-import { AdoptOptions, AgentStateView, RoomPlayer, TurnResult } from './room_service';
+import { AdoptOptions, AgentStateView, Forecast, RoomPlayer, TurnResult } from './room_service';
 
 export type MessageResult = TurnResult & { played: boolean; kind: 'chat' | 'control' | 'action' };
 export class RoomPoolService {
@@ -14,6 +14,10 @@ export class RoomPoolService {
   handleMessage(threadId: string, text: string, items?: { id: string; type: string }[]): Promise<MessageResult>;
   /** One tick for many threads (each at most once): per chunk touched one stepRooms and one readRoomsAt; outputs in input order. */
   handleMessages(msgs: [string, string, { id: string; type: string }[]?][]): Promise<MessageResult[]>;
+  /** As RoomService.forecast (same keys, seed and output), from the thread's slot. */
+  forecast(threadId: string, nRollouts?: number, maxTurns?: number): Promise<Forecast>;
+  /** Forecasts of many threads in order: one rolloutRooms per chunk touched. */
+  forecasts(threadIds: string[], nRollouts?: number, maxTurns?: number): Promise<Forecast[]>;
   /** Forget a thread (its slot is reused); without an id, every thread and every chunk's device memory. */
   close(threadId?: string): Promise<boolean>;
 }

@@ -10,7 +10,7 @@
  * stepRooms and one readRoomsAt.  The chunks are shared, so every call of the service runs strictly one after the other.
  */
 const { GameTable, RoomBatch, RoomLog, decodeRoom, turnToolCalls, uiToolCalls } = require('./index.js');
-const { roomIndexOf, prepareAdoption, adoptedOutput } = require('./room_service.js');
+const { roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput } = require('./room_service.js');
 const M = require('./messages.js');
 
 const GE_ERR_ARG = -1;
@@ -181,6 +181,34 @@ class RoomPoolService {
       }
       const res = this._turns(play.map(([i]) => entries[i].room), play.map(([i]) => entries[i].items));
       play.forEach(([i, kind], k) => { out[i] = Object.assign(res[k], { played: true, kind }); });
+      return out;
+    });
+  }
+  /** As RoomService.forecast (same keys, seed and output), from the thread's pool slot. */
+  forecast(threadId, nRollouts = 4096, maxTurns = 1024) {
+    return this.forecasts([threadId], nRollouts, maxTurns).then((o) => o[0]);
+  }
+  /** Forecasts of many threads, in order: one rolloutRooms per chunk touched.  No thread changes. */
+  forecasts(threadIds, nRollouts = 4096, maxTurns = 1024) {
+    checkForecastArgs(nRollouts, maxTurns);
+    return this._serial(() => {
+      const rooms = threadIds.map((t) => this._room(t));
+      const byChunk = new Map();
+      rooms.forEach((room, j) => {
+        if (!byChunk.has(room.chunk)) byChunk.set(room.chunk, []);
+        byChunk.get(room.chunk).push(j);
+      });
+      const perCall = Math.max(1, Math.floor(2 ** 26 / nRollouts));     // the library's cap on entries x rollouts of one call
+      const out = new Array(rooms.length);
+      const seed = forecastSeed(this.seed);
+      for (const [chunk, js] of byChunk) {
+        for (let lo = 0; lo < js.length; lo += perCall) {
+          const part = js.slice(lo, lo + perCall);
+          const w = chunk.rolloutRooms(part.map((j) => rooms[j].slot), part.map((j) => forecastKey(rooms[j].key)), part.map((j) => rooms[j].turn),
+                                       nRollouts, maxTurns, seed);
+          part.forEach((j, k) => { out[j] = forecastOutput(rooms[j].table, rooms[j].names, threadIds[j], rooms[j].turn, nRollouts, maxTurns, w, 77 * k); });
+        }
+      }
       return out;
     });
   }

@@ -16,6 +16,16 @@ export interface AdoptOptions {
   /** a human seat's action already logged in this visit: {playerId: choice} */ visitActions?: Record<string, number>;
 }
 export interface TurnResult { state: AgentStateView; toolCalls: ToolCall[]; uiCalls: FrontendToolCall[]; }
+/** How a thread ends from where it stands, over `rollouts` playouts (JSON integers: divide by rollouts for odds). */
+export interface Forecast {
+  threadId: string; turn: number; rollouts: number; maxTurns: number;
+  /** playouts that reached a terminal phase; the sum of their end turns; those with an end turn */
+  finished: number; endTurnSum: number; ended: number;
+  /** Werewolf: finished playouts won by each side */
+  sides?: { villagers: number; werewolves: number };
+  /** Werewolf: {name, alive, wins}; Two-Truths: {name, scoreSum, topScore} */
+  players: Record<string, { name: string; alive?: number; wins?: number; scoreSum?: number; topScore?: number }>;
+}
 export class RoomService {
   constructor(opts?: { gamesDir?: string; seed?: bigint | number; device?: number });
   createRoom(opts: { threadId: string; gameName: string; players: RoomPlayer[]; dsl?: object; /** global room index the RNG is keyed by (default: hash of the thread id) */ roomIndex?: number | bigint }): AgentStateView;
@@ -30,6 +40,9 @@ export class RoomService {
   handleMessage(threadId: string, text: string, items?: { id: string; type: string }[]): Promise<TurnResult & { played: boolean; kind: 'chat' | 'control' | 'action' }>;
   /** items: the frontend's canvas items (AgentState.items), for clearCanvas's exemptList */
   continueRoom(threadId: string, items?: { id: string; type: string }[]): Promise<TurnResult>;
+  /** nRollouts playouts (<= 65 536) of the thread's room, every seat played by the policy, keyed (threadKey << 16) + r under seed
+   *  (service seed ^ 0x9E3779B97F4A7C15); the thread is not changed (INTEGRATION.md "Forecasting a thread"). */
+  forecast(threadId: string, nRollouts?: number, maxTurns?: number): Promise<Forecast>;
   /** Forget a thread and free its device memory; resolves false for an unknown thread. */
   close(threadId: string): Promise<boolean>;
   serve(port?: number): Promise<import('http').Server>;

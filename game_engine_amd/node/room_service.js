@@ -66,6 +66,32 @@ function prepareAdoption(table, { state, players, humanSeats, turn, visitActions
   return { view, hostSide, n, humanMask, turn: t, names, humanSeats: seats };
 }
 
+const FORECAST_SEED_XOR = 0x9e3779b97f4a7c15n;   // forecast seed = service seed ^ this: no forecast stream is a game stream
+const FORECAST_MAX_ROLLOUTS = 65536;             // replicas of a thread are keyed threadKey << 16 .. + (nRollouts - 1)
+const forecastKey = (threadKey) => BigInt.asUintN(64, BigInt(threadKey) << 16n);
+const forecastSeed = (seed) => BigInt.asUintN(64, BigInt(seed) ^ FORECAST_SEED_XOR);
+function checkForecastArgs(nRollouts, maxTurns) {
+  if (!(Number.isInteger(nRollouts) && nRollouts >= 1 && nRollouts <= FORECAST_MAX_ROLLOUTS))
+    throw new RangeError(`nRollouts must be 1 .. ${FORECAST_MAX_ROLLOUTS} (replica keys are threadKey << 16 + r)`);
+  if (!(Number.isInteger(maxTurns) && maxTurns >= 0 && maxTurns <= 4096)) throw new RangeError('maxTurns must be 0 .. 4096');
+}
+/** The forecast of one thread from its 77 ge_rollout_stats words (w[off ..]): JSON integers only, the bytes the Python hosts print. */
+function forecastOutput(table, names, threadId, turn, nRollouts, maxTurns, w, off = 0) {
+  const at = (i) => Number(w[off + i]);
+  let ended = 0;
+  for (let i = 6; i < 22; i++) ended += at(i);
+  const out = { threadId, turn: Number(turn), rollouts: nRollouts, maxTurns, finished: at(1), endTurnSum: at(5), ended };
+  const players = {};
+  if (table.info.pack === 1) {
+    out.sides = { villagers: at(2), werewolves: at(3) };
+    names.forEach((name, i) => { players[String(i + 1)] = { name, alive: at(41 + i), wins: at(53 + i) }; });
+  } else {
+    names.forEach((name, i) => { players[String(i + 1)] = { name, scoreSum: at(65 + i), topScore: at(53 + i) }; });
+  }
+  out.players = players;
+  return out;
+}
+
 class RoomService {
   constructor({ gamesDir = 'games', seed = 0n, device = 0 } = {}) {
     this.gamesDir = gamesDir; this.seed = BigInt(seed); this.device = device;
@@ -81,13 +107,14 @@ class RoomService {
   createRoom({ threadId, gameName, players, dsl, roomIndex }) {
     const table = this.table(gameName, dsl);
     const humanMask = players.reduce((m, p, i) => (p.isBot === false ? m | (1 << i) : m), 0);
+    const key = roomIndex === undefined ? roomIndexOf(threadId) : BigInt(roomIndex);
     const batch = new RoomBatch({ segments: [{ table, nPlayers: players.length, nRooms: 1, humanMask }], seed: this.seed,
-                                  firstRoom: roomIndex === undefined ? roomIndexOf(threadId) : BigInt(roomIndex),   // the RNG is keyed by it
+                                  firstRoom: key,   // the RNG is keyed by it
                                   device: this.device, maxFuse: 1, trace: true });
     if (this.rooms.has(threadId)) this.close(threadId);
     const names = players.map((p, i) => p.name || `Player ${i + 1}`);
     const humanSeats = players.map((p, i) => (p.isBot === false ? i + 1 : 0)).filter((x) => x);
-    const room = { batch, table, gameName, names, humanSeats, panel: null, state: batch.readRoom(0), log: new RoomLog(table, names, gameName), queue: Promise.resolve() };
+    const room = { batch, key, turn: 0, table, gameName, names, humanSeats, panel: null, state: batch.readRoom(0), log: new RoomLog(table, names, gameName), queue: Promise.resolve() };
     this.rooms.set(threadId, room);
     return this.agentState(room);
   }
@@ -102,15 +129,15 @@ class RoomService {
   adoptRoom({ threadId, gameName, state, players, humanSeats, dsl, roomIndex, turn, visitActions }) {
     const table = this.table(gameName, dsl);
     const a = prepareAdoption(table, { state, players, humanSeats, turn, visitActions });
+    const key = roomIndex === undefined ? roomIndexOf(threadId) : BigInt(roomIndex);
     const batch = new RoomBatch({ segments: [{ table, nPlayers: a.n, nRooms: 1, humanMask: a.humanMask }], seed: this.seed,
-                                  firstRoom: roomIndex === undefined ? roomIndexOf(threadId) : BigInt(roomIndex),
-                                  device: this.device, maxFuse: 1, trace: true });
+                                  firstRoom: key, device: this.device, maxFuse: 1, trace: true });
     try {
       batch.writeRoomsAt([0], [a.view]);
       batch.setTurn(a.turn);
     } catch (e) { batch.close(); throw e; }
     if (this.rooms.has(threadId)) this.close(threadId);
-    const room = { batch, table, gameName, names: a.names, humanSeats: a.humanSeats, panel: null, state: batch.readRoom(0),
+    const room = { batch, key, turn: a.turn, table, gameName, names: a.names, humanSeats: a.humanSeats, panel: null, state: batch.readRoom(0),
                    log: new RoomLog(table, a.names, gameName), queue: Promise.resolve() };
     room.log.adopt(state, Object.assign({}, a.hostSide, { names: Object.fromEntries(a.names.map((nm, i) => [String(i + 1), nm])) }));
     this.rooms.set(threadId, room);
@@ -124,6 +151,21 @@ class RoomService {
     const p = room.queue.then(fn);
     room.queue = p.catch(() => {});
     return p;
+  }
+  /** How the thread ends from where it stands (twin of the Python RoomService.forecast): nRollouts playouts of its room, each for
+   * up to maxTurns turns from its next turn, every seat - human seats too - played by the policy.  Replica r is global room
+   * (threadKey << 16) + r, so nRollouts <= 65 536 (RangeError above), under seed (service seed ^ 0x9E3779B97F4A7C15); two forecasts
+   * at the same turn are identical and the thread is not changed.  Resolves with JSON integers: threadId, turn, rollouts, maxTurns,
+   * finished, endTurnSum, ended, and per seat (Werewolf: sides {villagers, werewolves}, players {"1": {name, alive, wins}};
+   * Two-Truths: players {"1": {name, scoreSum, topScore}}). */
+  forecast(threadId, nRollouts = 4096, maxTurns = 1024) {
+    checkForecastArgs(nRollouts, maxTurns);
+    const room = this.rooms.get(threadId);
+    if (!room) return Promise.reject(new Error(`unknown thread ${threadId}`));
+    return this._serial(room, () => {
+      const w = room.batch.rolloutRooms([0], [forecastKey(room.key)], [room.turn], nRollouts, maxTurns, forecastSeed(this.seed));
+      return forecastOutput(room.table, room.names, threadId, room.turn, nRollouts, maxTurns, w);
+    });
   }
   /** Forget a thread and free its device memory (after queued requests have finished). */
   close(threadId) {
@@ -185,6 +227,7 @@ class RoomService {
     // turn's update_player_state calls, where the reference's Referee issues them
     const before = room.state;
     await room.batch.step(1);
+    room.turn += 1;
     const after = room.batch.readRoom(0);
     const event = room.batch.readEvents(0, 1)[0][0];
     const toolCalls = turnToolCalls(room.table, before, after, event);
@@ -221,4 +264,4 @@ class RoomService {
   }
 }
 
-module.exports = { RoomService, roomIndexOf, prepareAdoption, adoptedOutput };
+module.exports = { RoomService, roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput };

@@ -17,7 +17,8 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import messages as M
-from .room_service import adopted_output, prepare_adoption, room_index_of
+from .room_service import (adopted_output, check_forecast_args, forecast_key, forecast_output, forecast_seed, prepare_adoption,
+                           room_index_of)
 from .stepper import GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, load_dsl_by_gamename, slot_values
 from .toolcalls import WW_IS_ALIVE, RoomLog, turn_tool_calls
 from .ui_script import ui_tool_calls
@@ -248,6 +249,31 @@ class RoomPoolService:
         ui = ui_tool_calls(room["table"].dsl, state, room["table"], turn=int(event["turn"]), deaths=deaths, items=items)
         room["panel"] = M.newest_panel(ui)
         return {"state": state, "toolCalls": calls, "uiCalls": ui}
+
+    def forecast(self, thread_id: str, n_rollouts: int = 4096, max_turns: int = 1024) -> Dict[str, Any]:
+        """As RoomService.forecast (same keys, seed and output), from the thread's pool slot."""
+        return self.forecasts([thread_id], n_rollouts, max_turns)[0]
+
+    def forecasts(self, thread_ids: Sequence[str], n_rollouts: int = 4096, max_turns: int = 1024) -> List[Dict[str, Any]]:
+        """Forecasts of many threads, in order: one rollout_rooms call per chunk touched (replica r of a thread is global room
+        (thread_key << 16) + r under seed service seed ^ 0x9E3779B97F4A7C15, from the thread's own turn).  No thread changes."""
+        check_forecast_args(n_rollouts, max_turns)
+        rooms = [self._rooms[tid] for tid in thread_ids]          # KeyError for an unknown thread, before anything runs
+        by_chunk: Dict[int, List[int]] = {}
+        for j, room in enumerate(rooms):
+            by_chunk.setdefault(id(room["chunk"]), []).append(j)
+        words: List[Any] = [None] * len(rooms)
+        per_call = max(1, (1 << 26) // int(n_rollouts))          # the library's cap on entries x rollouts of one call
+        for js in by_chunk.values():
+            chunk = rooms[js[0]]["chunk"]
+            for lo in range(0, len(js), per_call):
+                part = js[lo:lo + per_call]
+                w = chunk.rollout_rooms([rooms[j]["slot"] for j in part], [forecast_key(rooms[j]["key"]) for j in part],
+                                        [rooms[j]["turn"] for j in part], n_rollouts, max_turns, seed=forecast_seed(self.seed))
+                for k, j in enumerate(part):
+                    words[j] = w[k]
+        return [forecast_output(room["table"], room["names"], tid, room["turn"], n_rollouts, max_turns, words[j])
+                for j, (tid, room) in enumerate(zip(thread_ids, rooms))]
 
     def close(self, thread_id: Optional[str] = None):
         """Close one thread (its slot goes back to the pool's free list) or, without an id, every thread and every chunk."""

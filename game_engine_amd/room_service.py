@@ -15,8 +15,8 @@ import re
 from typing import Any, Dict, List, Optional
 
 from . import messages as M
-from .stepper import (GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, agent_state_to_view, load_dsl_by_gamename, slot_values,
-                      view_to_agent_state)
+from .stepper import (GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, agent_state_to_view, load_dsl_by_gamename, rollout_to_dict,
+                      slot_values, view_to_agent_state)
 from .toolcalls import WW_IS_ALIVE, RoomLog, turn_tool_calls
 from .ui_script import ui_tool_calls
 
@@ -80,6 +80,41 @@ def adopted_output(room: Dict[str, Any], turn: int) -> Dict[str, Any]:
     return {"state": state, "toolCalls": [], "uiCalls": ui}
 
 
+FORECAST_SEED_XOR = 0x9E3779B97F4A7C15     # forecast seed = service seed ^ this: no forecast stream is ever a game stream
+FORECAST_MAX_ROLLOUTS = 1 << 16             # replicas of a thread are keyed thread_key << 16 .. + (n_rollouts - 1)
+
+
+def forecast_key(thread_key: int) -> int:
+    """Base key of a thread's forecast replicas: replica r is global room (thread_key << 16) + r (mod 2^64)."""
+    return (int(thread_key) << 16) & 0xFFFFFFFFFFFFFFFF
+
+
+def forecast_seed(seed: int) -> int:
+    return (int(seed) ^ FORECAST_SEED_XOR) & 0xFFFFFFFFFFFFFFFF
+
+
+def check_forecast_args(n_rollouts: int, max_turns: int) -> None:
+    if not 1 <= int(n_rollouts) <= FORECAST_MAX_ROLLOUTS:
+        raise ValueError(f"n_rollouts must be 1 .. {FORECAST_MAX_ROLLOUTS} (replica keys are thread_key << 16 + r)")
+    if not 0 <= int(max_turns) <= 4096:
+        raise ValueError("max_turns must be 0 .. 4096")
+
+
+def forecast_output(table: GameTable, names: List[str], thread_id: str, turn: int, n_rollouts: int, max_turns: int, words) -> Dict[str, Any]:
+    """The forecast of one thread from its ge_rollout_stats words: JSON integers only (clients divide by `rollouts`), the same
+    bytes as room_service.js / room_pool.js produce."""
+    d = rollout_to_dict(words)
+    sm = d["summary"]
+    out: Dict[str, Any] = {"threadId": thread_id, "turn": int(turn), "rollouts": int(n_rollouts), "maxTurns": int(max_turns),
+                           "finished": sm["finished"], "endTurnSum": sm["sum_end_turn"], "ended": sum(sm["end_turn_hist"])}
+    if table.pack == PACK_WEREWOLF:
+        out["sides"] = {"villagers": sm["village_wins"], "werewolves": sm["wolf_wins"]}
+        out["players"] = {str(i + 1): {"name": nm, "alive": d["seat_alive"][i], "wins": d["seat_wins"][i]} for i, nm in enumerate(names)}
+    else:
+        out["players"] = {str(i + 1): {"name": nm, "scoreSum": d["seat_score"][i], "topScore": d["seat_wins"][i]} for i, nm in enumerate(names)}
+    return out
+
+
 class RoomService:
     def __init__(self, games_dir: str = "games", seed: int = 0, device: int = 0):
         self.games_dir, self.seed, self.device = games_dir, seed, device
@@ -98,11 +133,12 @@ class RoomService:
         room_index: the global room index the RNG is keyed by (default: derived from the thread id)."""
         tb = self.table(game_name, dsl)
         human_mask = sum(1 << i for i, p in enumerate(players) if p.get("isBot") is False)
-        batch = self._new_batch(tb, len(players), human_mask, room_index_of(thread_id) if room_index is None else room_index)
+        key = room_index_of(thread_id) if room_index is None else int(room_index)
+        batch = self._new_batch(tb, len(players), human_mask, key)
         if thread_id in self._rooms:
             self.close(thread_id)
         names = [p.get("name") or f"Player {i + 1}" for i, p in enumerate(players)]
-        room = {"batch": batch, "table": tb, "gameName": game_name, "names": names, "panel": None,
+        room = {"batch": batch, "key": key, "table": tb, "gameName": game_name, "names": names, "panel": None,
                 "human_seats": [i + 1 for i in range(len(players)) if (human_mask >> i) & 1],
                 "view": batch.read_rooms(0, 1)[0], "log": RoomLog(tb, names, game_name)}
         self._rooms[thread_id] = room
@@ -121,7 +157,8 @@ class RoomService:
         A state that does not fit raises ValueError before anything is created."""
         tb = self.table(game_name, dsl)
         a = prepare_adoption(tb, state, players, human_seats, turn, visit_actions)
-        batch = self._new_batch(tb, a["n"], a["human_mask"], room_index_of(thread_id) if room_index is None else room_index)
+        key = room_index_of(thread_id) if room_index is None else int(room_index)
+        batch = self._new_batch(tb, a["n"], a["human_mask"], key)
         try:
             batch.write_rooms_at([0], [a["view"]])
             batch.set_turn(a["turn"])
@@ -131,7 +168,7 @@ class RoomService:
             raise
         if thread_id in self._rooms:                      # only now: a refused state leaves an existing thread of this id alone
             self.close(thread_id)
-        room = {"batch": batch, "table": tb, "gameName": game_name, "names": a["names"], "panel": None,
+        room = {"batch": batch, "key": key, "table": tb, "gameName": game_name, "names": a["names"], "panel": None,
                 "human_seats": a["human_seats"], "view": view, "log": RoomLog(tb, a["names"], game_name)}
         room["log"].adopt(state, a["host"])
         self._rooms[thread_id] = room
@@ -206,6 +243,21 @@ class RoomService:
         ui = ui_tool_calls(room["table"].dsl, state, room["table"], turn=int(event["turn"]), deaths=deaths, items=items)
         room["panel"] = M.newest_panel(ui)                # what a person's next vote message can answer
         return {"state": state, "toolCalls": calls, "uiCalls": ui}
+
+    def forecast(self, thread_id: str, n_rollouts: int = 4096, max_turns: int = 1024) -> Dict[str, Any]:
+        """How the thread ends from where it stands: n_rollouts playouts of its room (RoomBatch.rollout_rooms), each played for
+        up to max_turns turns from the thread's next turn, every seat - human seats too - played by the policy.  Replica r is
+        global room (thread_key << 16) + r, so n_rollouts <= 65 536 (ValueError above), under seed (service seed ^
+        0x9E3779B97F4A7C15): no forecast stream is a game stream, and two forecasts at the same turn are identical.  The thread
+        is not changed.  Returns JSON integers: threadId, turn, rollouts, maxTurns, finished, endTurnSum, ended, and per seat
+        (Werewolf: sides {villagers, werewolves}, players {"1": {name, alive, wins}}; Two-Truths: players {"1": {name,
+        scoreSum, topScore}}); divide by rollouts for odds."""
+        check_forecast_args(n_rollouts, max_turns)
+        room = self._rooms[thread_id]
+        batch = room["batch"]
+        turn = batch.turn
+        w = batch.rollout_rooms([0], [forecast_key(room["key"])], [turn], n_rollouts, max_turns, seed=forecast_seed(self.seed))[0]
+        return forecast_output(room["table"], room["names"], thread_id, turn, n_rollouts, max_turns, w)
 
     def close(self, thread_id: Optional[str] = None):
         for tid in ([thread_id] if thread_id else list(self._rooms)):

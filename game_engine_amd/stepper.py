@@ -312,6 +312,23 @@ class RoomBatch:
                 raise GeError(st, f"ge_batch_write_rooms_at: room {bad} does not fit its segment (nothing was written)")
         _check(st, "ge_batch_write_rooms_at")
 
+    def rollout_rooms(self, rooms, keys, turns, n_rollouts: int, max_turns: int = 1024, seed: Optional[int] = None) -> np.ndarray:
+        """Playouts: entry k is played n_rollouts times from room rooms[k] as it stands, replica r as global room keys[k] + r
+        (mod 2^64) under `seed` (None: the batch's seed) at turns turns[k] .. turns[k] + max_turns - 1, every seat played by the
+        policy and a finished game left finished.  Returns the raw (n, 77) uint64 words of ge_rollout_stats (rollout_to_dict reads
+        one row): row k's first 41 words are what summary_words() of a fresh batch of n_rollouts copies of the room, keyed from
+        keys[k], would give after set_turn(turns[k]) and step(max_turns).  The batch is only read.  Caps (GeError otherwise,
+        nothing run): 1 <= n_rollouts <= 2^20, n * n_rollouts <= 2^26, max_turns <= 4096, turns[k] + max_turns < 2^32."""
+        rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        turns = np.ascontiguousarray(turns, dtype=np.uint32)
+        if not (len(rooms) == len(keys) == len(turns)):
+            raise GeError(-1, "rollout_rooms: arrays differ in length")
+        out = np.zeros((len(rooms), _lib.ROLLOUT_WORDS), dtype=np.uint64)
+        _check(self._lib.ge_batch_rollout_rooms(self._h, len(rooms), rooms.ctypes.data, keys.ctypes.data, turns.ctypes.data, n_rollouts,
+                                                max_turns, self._seed if seed is None else seed, out.ctypes.data), "ge_batch_rollout_rooms")
+        return out
+
     def write_agent_state(self, room: int, state: Dict[str, Any], visit_actions: Optional[Dict[Any, int]] = None) -> Dict[str, Any]:
         """Adopt a reference AgentState into one room (agent_state_to_view); returns its host-side fields."""
         return self.write_agent_states([room], [state], None if visit_actions is None else [visit_actions])[0]
@@ -570,6 +587,12 @@ def summary_to_dict(w: np.ndarray) -> Dict[str, Any]:
     w = [int(x) for x in w]
     return {"rooms": w[0], "finished": w[1], "village_wins": w[2], "wolf_wins": w[3], "alive_players": w[4],
             "sum_end_turn": w[5], "end_turn_hist": w[6:22], "score_hist": w[22:38], "checksum": w[38], "turn": w[39], "games_recycled": w[40]}
+
+
+def rollout_to_dict(w: np.ndarray) -> Dict[str, Any]:
+    """One row of RoomBatch.rollout_rooms: {"summary": summary_to_dict(...), "seat_alive", "seat_wins", "seat_score"} (12 each)."""
+    w = [int(x) for x in w]
+    return {"summary": summary_to_dict(w[:_lib.SUMMARY_WORDS]), "seat_alive": w[41:53], "seat_wins": w[53:65], "seat_score": w[65:77]}
 
 
 def project_view(view, table: Optional["GameTable"] = None) -> List[int]:

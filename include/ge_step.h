@@ -39,7 +39,8 @@ extern "C" {
  *   5  ge_group_partition + ge_batch_create_shard (the group's sharding arithmetic for hosts that place shards themselves); ge_last_rejected_room;
  *      mixed and generic batches get single-turn kernel builds; the Werewolf x 12 deal side plane is allocated on first use;
  *      later additions, new symbols only (the version stays 5): ge_batch_step_rooms + ge_batch_read_rooms_at (many game threads
- *      in one resident batch, each room stepped under its own key and turn); ge_batch_write_rooms_at (the indexed write) */
+ *      in one resident batch, each room stepped under its own key and turn); ge_batch_write_rooms_at (the indexed write);
+ *      ge_batch_rollout_rooms + ge_rollout_stats (on-device playouts of listed rooms: win odds per side and per seat) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -316,6 +317,30 @@ int ge_batch_read_rooms_at(ge_batch *b, uint64_t n, const uint64_t *rooms, ge_ro
  * room lies in (as ge_batch_write_rooms checks it; ge_last_rejected_room() then names that entry's batch room); nothing is
  * written then.  n == 0: GE_OK.  One copy through the staging buffer, one device scatter.  Synchronises. */
 int ge_batch_write_rooms_at(ge_batch *b, uint64_t n, const uint64_t *rooms, const ge_room_view *src);
+
+/* Outcome of n_rollouts playouts of one room (ge_batch_rollout_rooms): 77 x u64 = 616 B. */
+typedef struct ge_rollout_stats {
+    ge_summary summary;                   /* ge_batch_summary of the composition below, word for word (rooms = n_rollouts) */
+    uint64_t seat_alive[12];              /* werewolf: playouts in which seat i+1 is alive at the end, finished or not */
+    uint64_t seat_wins[12];               /* werewolf: finished playouts won by seat i+1's team (no wolf alive: villagers, else
+                                             werewolves); two-truths: finished playouts in which seat i+1's total_score is the
+                                             highest (every tied seat counts) */
+    uint64_t seat_score[12];              /* two-truths: sum of seat i+1's total_score over the playouts */
+} ge_rollout_stats;                       /* seats at or above n_players read 0 */
+
+/* Playouts: entry k (rooms[k], keys[k], turns[k]) is played n_rollouts times from batch room rooms[k] as it stands, replica r
+ * as global room keys[k] + r (mod 2^64) under `seed`, at turns turns[k] .. turns[k] + max_turns - 1, every seat played by the
+ * policy (human mask 0) and without GE_FLAG_RESTART (a finished game stays finished); the segment's table and generic conditions
+ * apply.  Definition: create B' (seed, first_room = keys[k], flags 0, one segment: the same table and n_players, human mask 0,
+ * n_rollouts rooms), ge_batch_write_rooms(B', 0, n_rollouts, copies of room rooms[k]), ge_batch_set_turn(B', turns[k]),
+ * ge_batch_step(B', max_turns); out[k].summary = ge_batch_summary(B').  Prepared role deals of the source are ignored.
+ * No state of a replica is kept in device memory: each plays in registers and only its outcome is reduced.
+ * Every entry is checked before anything runs, and on an error *out is untouched: GE_ERR_ARG for a NULL pointer with n > 0,
+ * n_rollouts == 0 or > 2^20, n * n_rollouts > 2^26 or max_turns > 4096; GE_ERR_RANGE for a room outside the batch or
+ * turns[k] + max_turns > 0xFFFFFFFF.  Repeated rooms are allowed.  n == 0: GE_OK.  The batch is only read (records, deal
+ * caches, turn counter, GE_FLAG_TRACE buffer).  Ordered behind the previous step; synchronises. */
+int ge_batch_rollout_rooms(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
+                           uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, ge_rollout_stats *out);
 
 /* GE_FLAG_TRACE: events of the most recent ge_batch_step call, dst[(room - first) * *n_turns + t].
  * cap_bytes >= count * n_turns * sizeof(ge_turn_event).  Synchronises. */

@@ -36,6 +36,9 @@ def describe(mangled: str) -> dict:
     m = re.search(r"ge_pool_kernelILi(\d)ELi(\d)E", mangled)
     if m:
         return {"kernel": "ge_pool_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True}
+    m = re.search(r"ge_rollout_kernelILi(\d)ELi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_rollout_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True}
     m = re.search(r"N_1\d+(ge_[a-z_0-9]+?)E", mangled)
     return {"kernel": m.group(1) if m else mangled, "layout": "-", "lowocc": False, "generic": False, "single": False}
 
@@ -64,6 +67,8 @@ def collect(rebuild=True):
 def label(r):
     if r["kernel"] == "ge_pool_kernel":                          # ge_batch_step_rooms: one launch per segment present
         return f"{r['layout']}, indexed single-turn (ge_batch_step_rooms)" + (", GENERIC" if r["generic"] else "")
+    if r["kernel"] == "ge_rollout_kernel":                       # ge_batch_rollout_rooms: one launch per segment present
+        return f"{r['layout']}, playouts (ge_batch_rollout_rooms)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] not in ("ge_step_kernel", "ge_step_kernel_mixed"):
         return r["kernel"]
     form = "single-turn" if r["single"] else "fused"
