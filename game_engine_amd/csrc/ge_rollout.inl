@@ -26,6 +26,14 @@
 // n * R / 64 records (up to 600 B x 2^20 wavefronts at the caps) and a second launch, while the atomics are at most 75 per
 // wavefront after tens to hundreds of turns of work each.  Every field is an integer sum, so the result does not depend on the
 // order the wavefronts arrive in.
+//
+// Playouts after actions (ge_batch_rollout_actions, ACT = 1).  Entry e also carries actions first_action[e] ..
+// first_action[e + 1] - 1: the prologue logs them in the loaded source record with the inject_ww / inject_tt of
+// ge_batch_inject_actions (row and condition read in place, as inject_group_* does) before the record goes into registers.
+// The record and the actions are the same in every lane, so the verdict is wave-uniform; it is kept in a scalar register.
+// A refused action refuses the entry: lane 0 of the entry's first wavefront writes its status to status[e], and every
+// wavefront of the entry returns before the turn loop and adds nothing.  ge_batch_rollout_rooms launches ACT = 0, whose
+// code is the kernel's code before this form existed.
 
 namespace {
 
@@ -41,6 +49,14 @@ struct RolloutArgs {
     uint32_t n, seg, seed_key, n_rollouts, max_turns, waves;   // waves: wavefronts per entry (ceil(R / 64))
     uint32_t settle_mask;       // bit p = row p is terminal and its completion is not "action"
 };
+
+// the arguments of one form: ACT = 1 adds the entries' actions (CSR over this launch's entries) and their verdicts
+template <int ACT> struct RollArgs : RolloutArgs {
+    const uint32_t *first_action;   // entry e's actions are players / choices [first_action[e], first_action[e + 1])
+    const uint32_t *players, *choices;
+    int32_t *status;                // entry e refused: the refused action's status (written once, by the entry's first wavefront)
+};
+template <> struct RollArgs<0> : RolloutArgs {};
 
 struct RollLane {
     RoomStats q;                // (zero on lanes past R)
@@ -97,8 +113,41 @@ __device__ __forceinline__ uint64_t roll_ck(uint32_t h_words) {
 }
 __device__ __forceinline__ uint32_t roll_h0(uint64_t g) { return mix32((uint32_t)g ^ mix32((uint32_t)(g >> 32) ^ 0xA5A5A5A5u)); }
 
-template <int NB, int GENERIC>
-__device__ __forceinline__ void roll_ww(const SegDev &sg, const DevTable *__restrict__ tables, const RolloutArgs &a, void *lw, uint32_t e,
+// the entry's actions logged in its source record (ACT = 1 prologue); false (wave-uniform) = refused, status[e] written
+__device__ __forceinline__ bool roll_refuse(const RollArgs<1> &a, uint32_t e, uint32_t r_in, int st) {
+    st = __builtin_amdgcn_readfirstlane(st);
+    if (st == GE_OK) return true;
+    if (r_in == 0u) a.status[e] = st;                         // lane 0 of the entry's first wavefront
+    return false;
+}
+template <int NB>
+__device__ __forceinline__ bool roll_act_ww(const SegDev &sg, const DevTable *__restrict__ tables, const RollArgs<1> &a, uint32_t e, uint32_t r_in,
+                                            uint32_t *w) {
+    using L = WWLayout<NB>;
+    WW<NB> s;
+    L::unpack(w, s);
+    const DevRow &row = tables[sg.table_idx].rows[s.phase];
+    const DevCond &cond = tables[sg.table_idx].conds[s.phase];   // read in place, as inject_group_ww
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(a.first_action[e]), hi = __builtin_amdgcn_readfirstlane(a.first_action[e + 1u]);
+    int st = GE_OK;
+    for (uint32_t k = lo; k < hi && st == GE_OK; k++) st = inject_ww<NB>(s, row, cond, sg.n_players, a.players[k], a.choices[k]);
+    if (!roll_refuse(a, e, r_in, st)) return false;
+    L::pack(s, w);
+    return true;
+}
+template <int NB>
+__device__ __forceinline__ bool roll_act_tt(const SegDev &sg, const DevTable *__restrict__ tables, const RollArgs<1> &a, uint32_t e, uint32_t r_in,
+                                            TT<NB> &s) {
+    const DevRow &row = tables[sg.table_idx].rows[s.phase];
+    const DevCond &cond = tables[sg.table_idx].conds[s.phase];   // read in place, as inject_group_tt
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(a.first_action[e]), hi = __builtin_amdgcn_readfirstlane(a.first_action[e + 1u]);
+    int st = GE_OK;
+    for (uint32_t k = lo; k < hi && st == GE_OK; k++) st = inject_tt<NB>(s, row, cond, sg.n_players, a.players[k], a.choices[k]);
+    return roll_refuse(a, e, r_in, st);
+}
+
+template <int NB, int GENERIC, int ACT>
+__device__ __forceinline__ void roll_ww(const SegDev &sg, const DevTable *__restrict__ tables, const RollArgs<ACT> &a, void *lw, uint32_t e,
                                         uint32_t r_in, unsigned long long *part, uint32_t *h_end, uint32_t *h_score) {
     using L = WWLayout<NB>;
     const bool valid = r_in < a.n_rollouts;
@@ -107,6 +156,8 @@ __device__ __forceinline__ void roll_ww(const SegDev &sg, const DevTable *__rest
     const uint32_t turn0 = (uint32_t)__builtin_amdgcn_readfirstlane(a.turns[e]);
     uint32_t w[L::WORDS];
     load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+    if constexpr (ACT != 0)
+        if (!roll_act_ww<NB>(sg, tables, a, e, r_in, w)) return;
     const uint64_t g = key + r;
     const uint32_t rk = room_key_from(a.seed_key, g);
     const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
@@ -144,8 +195,8 @@ __device__ __forceinline__ void roll_ww(const SegDev &sg, const DevTable *__rest
     roll_reduce<NB>(l, valid, score, part, h_end, h_score, a.acc + (size_t)e * ROLL_STRIDE);
 }
 
-template <int NB, int GENERIC>
-__device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__restrict__ tables, const RolloutArgs &a, void *lw, uint32_t e,
+template <int NB, int GENERIC, int ACT>
+__device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__restrict__ tables, const RollArgs<ACT> &a, void *lw, uint32_t e,
                                         uint32_t r_in, unsigned long long *part, uint32_t *h_end, uint32_t *h_score) {
     using L = TTLayout<NB>;
     const bool valid = r_in < a.n_rollouts;
@@ -164,6 +215,8 @@ __device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__rest
     const uint32_t phase0 = __builtin_amdgcn_readfirstlane(sg.phase0_idx);
     TT<NB> s;
     L::unpack(w, s);
+    if constexpr (ACT != 0)
+        if (!roll_act_tt<NB>(sg, tables, a, e, r_in, s)) return;
     uint32_t done = tt_done_mask<NB>(s.rounds, sg.rounds);
     for (uint32_t t = 0; t < a.max_turns; t++) {
         DevRow row = lds_row<false>(rows, s.phase);
@@ -199,8 +252,8 @@ __device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__rest
 
 // one wavefront per block = one entry's 64 replicas; its action queue (WaveLdsLow) is the block's dynamic LDS (none for
 // Two-Truths x 4: no queue)
-template <int KIND, int GENERIC>
-__global__ void __launch_bounds__(64) ge_rollout_kernel(const SegDev *__restrict__ segs, const DevTable *__restrict__ tables, const RolloutArgs a) {
+template <int KIND, int GENERIC, int ACT>
+__global__ void __launch_bounds__(64) ge_rollout_kernel(const SegDev *__restrict__ segs, const DevTable *__restrict__ tables, const RollArgs<ACT> a) {
     __shared__ unsigned long long part[ROLL_FIELDS];
     __shared__ uint32_t h_end[16], h_score[16];
     const SegDev &sg = segs[a.seg];
@@ -209,21 +262,21 @@ __global__ void __launch_bounds__(64) ge_rollout_kernel(const SegDev *__restrict
     if (threadIdx.x < 16) { h_end[threadIdx.x] = 0; h_score[threadIdx.x] = 0; }
     __syncthreads();
     void *lw = ge_lds;
-    if (KIND == K_WW8) roll_ww<8, GENERIC>(sg, tables, a, lw, e, r, part, h_end, h_score);
-    else if (KIND == K_WW12) roll_ww<12, GENERIC>(sg, tables, a, lw, e, r, part, h_end, h_score);
-    else if (KIND == K_TT4) roll_tt<4, GENERIC>(sg, tables, a, lw, e, r, part, h_end, h_score);
-    else if (KIND == K_TT8) roll_tt<8, GENERIC>(sg, tables, a, lw, e, r, part, h_end, h_score);
-    else roll_tt<12, GENERIC>(sg, tables, a, lw, e, r, part, h_end, h_score);
+    if (KIND == K_WW8) roll_ww<8, GENERIC, ACT>(sg, tables, a, lw, e, r, part, h_end, h_score);
+    else if (KIND == K_WW12) roll_ww<12, GENERIC, ACT>(sg, tables, a, lw, e, r, part, h_end, h_score);
+    else if (KIND == K_TT4) roll_tt<4, GENERIC, ACT>(sg, tables, a, lw, e, r, part, h_end, h_score);
+    else if (KIND == K_TT8) roll_tt<8, GENERIC, ACT>(sg, tables, a, lw, e, r, part, h_end, h_score);
+    else roll_tt<12, GENERIC, ACT>(sg, tables, a, lw, e, r, part, h_end, h_score);
 }
 
-template <int GEN> hipError_t rollout_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const RolloutArgs &a) {
+template <int GEN, int ACT> hipError_t rollout_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const RollArgs<ACT> &a) {
     const uint32_t lds = (kind == K_TT4) ? 0u : (uint32_t)sizeof(WaveLdsLow);
     switch (kind) {
-    case K_WW8: hipLaunchKernelGGL((ge_rollout_kernel<K_WW8, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    case K_WW12: hipLaunchKernelGGL((ge_rollout_kernel<K_WW12, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    case K_TT4: hipLaunchKernelGGL((ge_rollout_kernel<K_TT4, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    case K_TT8: hipLaunchKernelGGL((ge_rollout_kernel<K_TT8, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    default: hipLaunchKernelGGL((ge_rollout_kernel<K_TT12, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
+    case K_WW8: hipLaunchKernelGGL((ge_rollout_kernel<K_WW8, GEN, ACT>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
+    case K_WW12: hipLaunchKernelGGL((ge_rollout_kernel<K_WW12, GEN, ACT>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
+    case K_TT4: hipLaunchKernelGGL((ge_rollout_kernel<K_TT4, GEN, ACT>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
+    case K_TT8: hipLaunchKernelGGL((ge_rollout_kernel<K_TT8, GEN, ACT>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
+    default: hipLaunchKernelGGL((ge_rollout_kernel<K_TT12, GEN, ACT>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
     }
     return hipGetLastError();
 }
@@ -238,8 +291,14 @@ uint32_t rollout_settle_mask(const Segment &sg) {
 
 }  // namespace
 
+// the actions of ge_batch_rollout_actions (CSR over the call's entries); null for ge_batch_rollout_rooms
+struct RollActions {
+    const uint32_t *first, *players, *choices;
+    int32_t *entry_status;
+};
+
 static int rollout_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, uint32_t n_rollouts,
-                              uint32_t max_turns, uint64_t seed, ge_rollout_stats *out) {
+                              uint32_t max_turns, uint64_t seed, ge_rollout_stats *out, const RollActions *act = nullptr) {
     GE_ON_DEVICE(b);
     int st = sync_impl(b);
     if (st != GE_OK) return st;
@@ -248,6 +307,7 @@ static int rollout_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, co
     const uint32_t seed_k = seed_key((uint32_t)seed, (uint32_t)(seed >> 32));
     std::vector<uint32_t> settle(n_seg);
     for (uint32_t g = 0; g < n_seg; g++) settle[g] = rollout_settle_mask(b->segs[g]);
+    int first_bad = GE_OK;                                  // ge_batch_rollout_actions: the status of the first refused entry
     // entries in chunks (bounded staging and accumulator memory); within a chunk a stable counting sort by segment, one launch
     // per segment present (a wavefront never mixes layouts)
     const uint64_t CHUNK = 65536;
@@ -260,8 +320,15 @@ static int rollout_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, co
             std::vector<uint32_t> at(begin.begin(), begin.end() - 1);
             for (uint32_t k = 0; k < cn; k++) order[at[seg_of[k]]++] = k;
         }
-        // one upload: [rooms u64 x cn][keys u64 x cn][turns u32 x cn (padded to 16 B)], then the accumulators 8 B x ROLL_STRIDE x cn
-        const size_t off_keys = 8 * (size_t)cn, off_turns = 16 * (size_t)cn, off_acc = (off_turns + 4 * (size_t)cn + 15u) & ~(size_t)15u;
+        // one upload: [rooms u64 x cn][keys u64 x cn][turns u32 x cn]; with actions [first u32 x (cn + 1)][players u32 x na]
+        // [choices u32 x na]; each array from a 16 B boundary.  Then the download: [status i32 x cn] (with actions), the
+        // accumulators 8 B x ROLL_STRIDE x cn
+        const uint32_t na = act ? act->first[c0 + cn] - act->first[c0] : 0u;
+        auto up16 = [](size_t x) { return (x + 15u) & ~(size_t)15u; };
+        const size_t off_keys = 8 * (size_t)cn, off_turns = 16 * (size_t)cn;
+        const size_t off_first = up16(off_turns + 4 * (size_t)cn), off_pl = up16(off_first + (act ? 4 * ((size_t)cn + 1u) : 0u));
+        const size_t off_ch = up16(off_pl + 4 * (size_t)na), off_st = up16(off_ch + 4 * (size_t)na);
+        const size_t off_acc = act ? up16(off_st + 4 * (size_t)cn) : off_first;
         const size_t acc_bytes = 8 * (size_t)ROLL_STRIDE * cn, total = off_acc + acc_bytes;
         uint32_t *host32 = nullptr;
         if ((st = io_stage(b, total, &host32)) != GE_OK) return st;
@@ -274,6 +341,18 @@ static int rollout_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, co
             h_keys[i] = keys[k];
             h_turns[i] = turns[k];
         }
+        if (act) {                                            // the actions in the sorted order, offsets from the chunk's first
+            uint32_t *h_first = reinterpret_cast<uint32_t *>(host + off_first), *h_pl = reinterpret_cast<uint32_t *>(host + off_pl);
+            uint32_t *h_ch = reinterpret_cast<uint32_t *>(host + off_ch);
+            uint32_t at = 0;
+            for (uint32_t i = 0; i < cn; i++) {
+                const uint64_t k = c0 + order[i];
+                h_first[i] = at;
+                for (uint32_t x = act->first[k]; x < act->first[k + 1]; x++, at++) { h_pl[at] = act->players[x]; h_ch[at] = act->choices[x]; }
+            }
+            h_first[cn] = at;
+            memset(host + off_st, 0, 4 * (size_t)cn);          // GE_OK unless the device refuses the entry
+        }
         char *dev = nullptr;
         if ((st = pool_scratch(b, total, &dev)) != GE_OK) return st;
         hipStream_t s = b->last_stream;
@@ -283,21 +362,43 @@ static int rollout_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, co
         for (uint32_t g = 0; g < n_seg; g++) {
             const uint32_t lo = begin[g], cnt = begin[g + 1u] - lo;
             if (!cnt) continue;
-            RolloutArgs a;
+            RollArgs<1> a;
             a.rooms = reinterpret_cast<const uint64_t *>(dev) + lo;
             a.keys = reinterpret_cast<const uint64_t *>(dev + off_keys) + lo;
             a.turns = reinterpret_cast<const uint32_t *>(dev + off_turns) + lo;
             a.acc = reinterpret_cast<unsigned long long *>(dev + off_acc) + (size_t)ROLL_STRIDE * lo;
             a.n = cnt; a.seg = g; a.seed_key = seed_k; a.n_rollouts = n_rollouts; a.max_turns = max_turns; a.waves = waves;
             a.settle_mask = settle[g];
+            a.first_action = reinterpret_cast<const uint32_t *>(dev + off_first) + lo;
+            a.players = reinterpret_cast<const uint32_t *>(dev + off_pl);
+            a.choices = reinterpret_cast<const uint32_t *>(dev + off_ch);
+            a.status = reinterpret_cast<int32_t *>(dev + off_st) + lo;
             const dim3 grid(cnt * waves);                         // <= 2^26 blocks (n * R <= 2^26)
-            HIP_TRY(b->generic ? rollout_launch<1>(b->segs[g].dev.kind, grid, s, b, a) : rollout_launch<0>(b->segs[g].dev.kind, grid, s, b, a));
+            const uint32_t kind = b->segs[g].dev.kind;
+            if (!act) {                                       // ge_batch_rollout_rooms: the form without actions
+                RollArgs<0> a0;
+                static_cast<RolloutArgs &>(a0) = a;
+                HIP_TRY((b->generic ? rollout_launch<1, 0>(kind, grid, s, b, a0) : rollout_launch<0, 0>(kind, grid, s, b, a0)));
+            } else {
+                HIP_TRY((b->generic ? rollout_launch<1, 1>(kind, grid, s, b, a) : rollout_launch<0, 1>(kind, grid, s, b, a)));
+            }
         }
+        const size_t off_down = act ? off_st : off_acc;
+        const int32_t *h_st = reinterpret_cast<const int32_t *>(host + off_st);
         const unsigned long long *h_acc = reinterpret_cast<const unsigned long long *>(host + off_acc);
-        HIP_TRY(hipMemcpyAsync(host + off_acc, dev + off_acc, acc_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(host + off_down, dev + off_down, total - off_down, hipMemcpyDeviceToHost, s));
         if ((st = sync_impl(b)) != GE_OK) return st;
+        if (act) {                                            // verdicts in input order: the first refused entry decides the result
+            std::vector<int32_t> v(cn);
+            for (uint32_t i = 0; i < cn; i++) v[order[i]] = h_st[i];
+            for (uint32_t k = 0; k < cn; k++) {
+                if (act->entry_status) act->entry_status[c0 + k] = v[k];
+                if (v[k] != GE_OK && first_bad == GE_OK) first_bad = v[k];
+            }
+        }
         for (uint32_t i = 0; i < cn; i++) {                      // scattered back into input order
             const uint64_t k = c0 + order[i];
+            if (act && h_st[i] != GE_OK) continue;               // a refused entry's record is left as it is
             const unsigned long long *h = h_acc + (size_t)ROLL_STRIDE * i;
             ge_rollout_stats &o = out[k];
             memset(&o, 0, sizeof o);
@@ -311,7 +412,7 @@ static int rollout_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, co
             for (int j = 0; j < 12; j++) { o.seat_alive[j] = h[39 + j]; o.seat_wins[j] = h[51 + j]; o.seat_score[j] = h[63 + j]; }
         }
     }
-    return GE_OK;
+    return first_bad;
 }
 
 extern "C" {
@@ -327,6 +428,24 @@ int ge_batch_rollout_rooms(ge_batch *b, uint64_t n, const uint64_t *rooms, const
     for (uint64_t k = 0; k < n; k++)
         if (rooms[k] >= b->n_rooms || (uint64_t)turns[k] + max_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;
     return guarded([&] { return rollout_rooms_impl(b, n, rooms, keys, turns, n_rollouts, max_turns, seed, out); });
+}
+
+int ge_batch_rollout_actions(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
+                             const uint32_t *first_action, const uint32_t *player_ids, const uint32_t *choices, int32_t *entry_status,
+                             uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, ge_rollout_stats *out) {
+    if (!b) return GE_ERR_ARG;
+    if (n == 0) return GE_OK;
+    // structural checks, all before anything runs (on an error *out and entry_status are untouched); legality is the device's
+    if (!rooms || !keys || !turns || !out || !first_action || !player_ids || !choices) return GE_ERR_ARG;
+    if (n_rollouts == 0 || n_rollouts > (1u << 20) || n > (1ull << 26) || n * (uint64_t)n_rollouts > (1ull << 26) || max_turns > 4096u)
+        return GE_ERR_ARG;
+    if (first_action[0] != 0) return GE_ERR_ARG;
+    for (uint64_t k = 0; k < n; k++)
+        if (first_action[k + 1] < first_action[k] || first_action[k + 1] - first_action[k] > GE_MAX_PLAYERS) return GE_ERR_ARG;
+    for (uint64_t k = 0; k < n; k++)
+        if (rooms[k] >= b->n_rooms || (uint64_t)turns[k] + max_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;
+    const RollActions act = {first_action, player_ids, choices, entry_status};
+    return guarded([&] { return rollout_rooms_impl(b, n, rooms, keys, turns, n_rollouts, max_turns, seed, out, &act); });
 }
 
 }  // extern "C"

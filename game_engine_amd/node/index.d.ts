@@ -72,6 +72,12 @@ export class RoomBatch {
    *  words of ge_rollout_stats (41 summary words, then seat_alive, seat_wins, seat_score x 12).  The batch is only read. */
   rolloutRooms(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, nRollouts: number,
                maxTurns?: number, seed?: bigint | number): BigUint64Array;
+  /** Playouts after given actions: entry k is rolloutRooms's entry with actions[k] ([playerId, choice] pairs) logged in every replica
+   *  before its first turn.  status[k] = 0 and entry k's 77 words, or the refused action's status (< 0) and 77 zero words.  Throws only
+   *  for a structural error.  The batch is only read. */
+  rolloutActions(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>,
+                 actions: ArrayLike<ArrayLike<[number, number]>>, nRollouts: number, maxTurns?: number,
+                 seed?: bigint | number): { words: BigUint64Array; status: Int32Array };
   /** out[k] = room rooms[k] (any order, repeats allowed). */
   readRoomsAt(rooms: ArrayLike<number | bigint>): RoomState[];
   readRoomsAtRaw(rooms: ArrayLike<number | bigint>): ArrayBuffer;

@@ -588,6 +588,20 @@ class RoomBatch {
     return addon.rolloutRooms(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r)), BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))),
                               Uint32Array.from(turns), nRollouts, maxTurns, seed === undefined ? this.seed : BigInt(seed));
   }
+  /** Playouts after given actions (twin of the Python RoomBatch.rollout_actions): entry k is rolloutRooms's entry (rooms[k], keys[k],
+   * turns[k]) with actions[k], an array of [playerId, choice] pairs, logged in every replica, in that order, before its first turn.
+   * Legality is decided per entry on the device.  Returns { words: BigUint64Array of rooms.length x 77, status: Int32Array }:
+   * status[k] = 0 and entry k's ge_rollout_stats, or the refused action's status (< 0) and 77 zero words.  Throws only for a
+   * structural error (rolloutRooms's caps, more than 12 actions in one entry).  The batch is only read.  Synchronous. */
+  rolloutActions(rooms, keys, turns, actions, nRollouts, maxTurns = 1024, seed) {
+    const acts = Array.from(actions, (a) => Array.from(a));
+    const first = new Uint32Array(acts.length + 1);
+    acts.forEach((a, k) => { first[k + 1] = first[k] + a.length; });
+    const flat = acts.flat();
+    return addon.rolloutActions(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r)), BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))),
+                                Uint32Array.from(turns), first, Uint32Array.from(flat, (pc) => pc[0]), Uint32Array.from(flat, (pc) => pc[1]),
+                                nRollouts, maxTurns, seed === undefined ? this.seed : BigInt(seed));
+  }
   /** The listed rooms' states, out[k] = room rooms[k] (any order, repeats allowed). */
   readRoomsAt(rooms) {
     const buf = this.readRoomsAtRaw(rooms);

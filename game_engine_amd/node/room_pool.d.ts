@@ -1,5 +1,5 @@
 // Types for room_pool.js — many game threads hosted in a few resident batches.
-import { AdoptOptions, AgentStateView, Forecast, RoomPlayer, TurnResult } from './room_service';
+import { AdoptOptions, Advice, AgentStateView, Forecast, RoomPlayer, TurnResult } from './room_service';
 
 export type MessageResult = TurnResult & { played: boolean; kind: 'chat' | 'control' | 'action' };
 export class RoomPoolService {
@@ -18,6 +18,10 @@ export class RoomPoolService {
   forecast(threadId: string, nRollouts?: number, maxTurns?: number): Promise<Forecast>;
   /** Forecasts of many threads in order: one rolloutRooms per chunk touched. */
   forecasts(threadIds: string[], nRollouts?: number, maxTurns?: number): Promise<Forecast[]>;
+  /** As RoomService.advise (same candidates, keys, seed and output), from the thread's slot. */
+  advise(threadId: string, playerId?: number, nRollouts?: number, maxTurns?: number): Promise<Advice>;
+  /** Advice for many threads in order (playerIds[j] absent: thread j's lowest human seat): one rolloutActions per chunk touched. */
+  advises(threadIds: string[], playerIds?: (number | undefined)[], nRollouts?: number, maxTurns?: number): Promise<Advice[]>;
   /** Forget a thread (its slot is reused); without an id, every thread and every chunk's device memory. */
   close(threadId?: string): Promise<boolean>;
 }

@@ -10,7 +10,8 @@
  * stepRooms and one readRoomsAt.  The chunks are shared, so every call of the service runs strictly one after the other.
  */
 const { GameTable, RoomBatch, RoomLog, decodeRoom, turnToolCalls, uiToolCalls } = require('./index.js');
-const { roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput } = require('./room_service.js');
+const { roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput, adviseCandidates, adviseSeat,
+        adviseEntries, adviseOutput } = require('./room_service.js');
 const M = require('./messages.js');
 
 const GE_ERR_ARG = -1;
@@ -187,6 +188,51 @@ class RoomPoolService {
   /** As RoomService.forecast (same keys, seed and output), from the thread's pool slot. */
   forecast(threadId, nRollouts = 4096, maxTurns = 1024) {
     return this.forecasts([threadId], nRollouts, maxTurns).then((o) => o[0]);
+  }
+  /** As RoomService.advise (same candidates, keys, seed and output), from the thread's pool slot. */
+  advise(threadId, playerId, nRollouts = 4096, maxTurns = 1024) {
+    return this.advises([threadId], [playerId], nRollouts, maxTurns).then((o) => o[0]);
+  }
+  /** Advice for many threads, in order (playerIds[j] undefined / null or no playerIds: thread j's lowest human seat): one
+   * rolloutActions call per chunk touched.  No thread changes. */
+  advises(threadIds, playerIds, nRollouts = 4096, maxTurns = 1024) {
+    checkForecastArgs(nRollouts, maxTurns);
+    return this._serial(() => {
+      const rooms = threadIds.map((t) => this._room(t));
+      const pids = playerIds || [];
+      const seats = rooms.map((room, j) => adviseSeat(threadIds[j], room.humanSeats, pids[j]));
+      const cands = rooms.map((room) => adviseCandidates(room.table, room.state));
+      const byChunk = new Map();
+      rooms.forEach((room, j) => {
+        if (!byChunk.has(room.chunk)) byChunk.set(room.chunk, []);
+        byChunk.get(room.chunk).push(j);
+      });
+      const out = new Array(rooms.length);
+      const seed = forecastSeed(this.seed);
+      const perCall = Math.max(1, Math.floor(2 ** 26 / nRollouts));     // the library's cap on entries x rollouts of one call
+      for (const [chunk, js] of byChunk) {
+        const parts = [[]];
+        let nEnt = 0;
+        for (const j of js) {                                             // one call per chunk, split only where the cap needs it
+          if (parts[parts.length - 1].length && nEnt + cands[j].length + 1 > perCall) { parts.push([]); nEnt = 0; }
+          parts[parts.length - 1].push(j);
+          nEnt += cands[j].length + 1;
+        }
+        for (const part of parts) {
+          const ent = [[], [], [], []], at = [];
+          for (const j of part) {
+            at.push(ent[0].length);
+            adviseEntries(rooms[j].slot, rooms[j].key, rooms[j].turn, seats[j], cands[j]).forEach((src, i) => ent[i].push(...src));
+          }
+          const res = chunk.rolloutActions(ent[0], ent[1], ent[2], ent[3], nRollouts, maxTurns, seed);
+          part.forEach((j, k) => {
+            out[j] = adviseOutput(rooms[j].table, rooms[j].names, threadIds[j], rooms[j].turn, seats[j], rooms[j].state, cands[j], nRollouts,
+                                  maxTurns, res, at[k]);
+          });
+        }
+      }
+      return out;
+    });
   }
   /** Forecasts of many threads, in order: one rolloutRooms per chunk touched.  No thread changes. */
   forecasts(threadIds, nRollouts = 4096, maxTurns = 1024) {

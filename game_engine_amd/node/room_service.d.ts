@@ -26,6 +26,14 @@ export interface Forecast {
   /** Werewolf: {name, alive, wins}; Two-Truths: {name, scoreSum, topScore} */
   players: Record<string, { name: string; alive?: number; wins?: number; scoreSum?: number; topScore?: number }>;
 }
+/** The forecast for each choice a seat can make now, beside the policy's (INTEGRATION.md "Advising a seat"). */
+export interface Advice {
+  threadId: string; turn: number; playerId: number; phaseId: number; rollouts: number; maxTurns: number;
+  /** the thread's forecast: the policy's own choice */
+  policy: Forecast;
+  /** the accepted candidates in ascending order; label = the seat's name (Werewolf) or the statement number (Two-Truths) */
+  options: { choice: number; label: string; forecast: Forecast }[];
+}
 export class RoomService {
   constructor(opts?: { gamesDir?: string; seed?: bigint | number; device?: number });
   createRoom(opts: { threadId: string; gameName: string; players: RoomPlayer[]; dsl?: object; /** global room index the RNG is keyed by (default: hash of the thread id) */ roomIndex?: number | bigint }): AgentStateView;
@@ -43,6 +51,9 @@ export class RoomService {
   /** nRollouts playouts (<= 65 536) of the thread's room, every seat played by the policy, keyed (threadKey << 16) + r under seed
    *  (service seed ^ 0x9E3779B97F4A7C15); the thread is not changed (INTEGRATION.md "Forecasting a thread"). */
   forecast(threadId: string, nRollouts?: number, maxTurns?: number): Promise<Forecast>;
+  /** For every choice playerId (default: the lowest human seat; RangeError if there is none) can make now, the forecast given
+   *  that choice, under forecast's keys and seed; the thread is not changed (INTEGRATION.md "Advising a seat"). */
+  advise(threadId: string, playerId?: number, nRollouts?: number, maxTurns?: number): Promise<Advice>;
   /** Forget a thread and free its device memory; resolves false for an unknown thread. */
   close(threadId: string): Promise<boolean>;
   serve(port?: number): Promise<import('http').Server>;

@@ -92,6 +92,36 @@ function forecastOutput(table, names, threadId, turn, nRollouts, maxTurns, w, of
   return out;
 }
 
+/** The choices a seat may make in the room's current phase, as messages.resolve can read them (twin of room_service.py
+ * advise_candidates): Werewolf every seat id 1..n, Two-Truths [1] in the statements phase and [1, 2, 3] otherwise. */
+function adviseCandidates(table, st) {
+  const n = st.slots.length;
+  if (st.pack === 1) return Array.from({ length: n }, (_, i) => i + 1);
+  const phase = table.info.phases.find((x) => x.id === st.current_phase_id);
+  return phase && phase.act === 5 ? [1] : [1, 2, 3];             // 5: GE_ACT_TT_STATEMENTS
+}
+function adviseSeat(threadId, humanSeats, playerId) {
+  if (playerId !== undefined && playerId !== null) return Number(playerId);
+  if (!humanSeats.length) throw new RangeError(`thread ${threadId} has no human seat: name the player to advise`);
+  return Math.min(...humanSeats);
+}
+/** rolloutActions entries of one advise: one per candidate, then the policy's (no action), all under the forecast key. */
+function adviseEntries(slot, threadKey, turn, seat, cands) {
+  const k = cands.length + 1;
+  return [new Array(k).fill(slot), new Array(k).fill(forecastKey(threadKey)), new Array(k).fill(turn), cands.map((c) => [[seat, c]]).concat([[]])];
+}
+/** advise's JSON from the words and verdicts of adviseEntries at entry offset `at`: the bytes the Python hosts print. */
+function adviseOutput(table, names, threadId, turn, seat, st, cands, nRollouts, maxTurns, res, at = 0) {
+  const options = [];
+  cands.forEach((c, j) => {
+    if (res.status[at + j] !== 0) return;
+    options.push({ choice: c, label: st.pack === 1 ? names[c - 1] : String(c),
+                   forecast: forecastOutput(table, names, threadId, turn, nRollouts, maxTurns, res.words, 77 * (at + j)) });
+  });
+  return { threadId, turn: Number(turn), playerId: seat, phaseId: st.current_phase_id, rollouts: nRollouts, maxTurns,
+           policy: forecastOutput(table, names, threadId, turn, nRollouts, maxTurns, res.words, 77 * (at + cands.length)), options };
+}
+
 class RoomService {
   constructor({ gamesDir = 'games', seed = 0n, device = 0 } = {}) {
     this.gamesDir = gamesDir; this.seed = BigInt(seed); this.device = device;
@@ -165,6 +195,23 @@ class RoomService {
     return this._serial(room, () => {
       const w = room.batch.rolloutRooms([0], [forecastKey(room.key)], [room.turn], nRollouts, maxTurns, forecastSeed(this.seed));
       return forecastOutput(room.table, room.names, threadId, room.turn, nRollouts, maxTurns, w);
+    });
+  }
+  /** What each choice the seat can make now leads to (twin of the Python RoomService.advise): for every candidate the forecast given
+   * that the seat logs it before the next turn, and the policy's own ("policy", equal to forecast(threadId)).  One rolloutActions
+   * call under forecast's keys and seed.  playerId defaults to the lowest human seat (RangeError if there is none).  Resolves with
+   * { threadId, turn, playerId, phaseId, rollouts, maxTurns, policy, options: [{ choice, label, forecast }] } for the accepted
+   * candidates in ascending order.  The thread is not changed. */
+  advise(threadId, playerId, nRollouts = 4096, maxTurns = 1024) {
+    checkForecastArgs(nRollouts, maxTurns);
+    const room = this.rooms.get(threadId);
+    if (!room) return Promise.reject(new Error(`unknown thread ${threadId}`));
+    const seat = adviseSeat(threadId, room.humanSeats, playerId);
+    return this._serial(room, () => {
+      const cands = adviseCandidates(room.table, room.state);
+      const [rooms, keys, turns, acts] = adviseEntries(0, room.key, room.turn, seat, cands);
+      const res = room.batch.rolloutActions(rooms, keys, turns, acts, nRollouts, maxTurns, forecastSeed(this.seed));
+      return adviseOutput(room.table, room.names, threadId, room.turn, seat, room.state, cands, nRollouts, maxTurns, res);
     });
   }
   /** Forget a thread and free its device memory (after queued requests have finished). */
@@ -264,4 +311,5 @@ class RoomService {
   }
 }
 
-module.exports = { RoomService, roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput };
+module.exports = { RoomService, roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput,
+                   adviseCandidates, adviseSeat, adviseEntries, adviseOutput };

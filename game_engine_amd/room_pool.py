@@ -17,8 +17,8 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import messages as M
-from .room_service import (adopted_output, check_forecast_args, forecast_key, forecast_output, forecast_seed, prepare_adoption,
-                           room_index_of)
+from .room_service import (adopted_output, advise_candidates, advise_entries, advise_output, advise_seat, check_forecast_args,
+                           forecast_key, forecast_output, forecast_seed, prepare_adoption, room_index_of)
 from .stepper import GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, load_dsl_by_gamename, slot_values
 from .toolcalls import WW_IS_ALIVE, RoomLog, turn_tool_calls
 from .ui_script import ui_tool_calls
@@ -274,6 +274,50 @@ class RoomPoolService:
                     words[j] = w[k]
         return [forecast_output(room["table"], room["names"], tid, room["turn"], n_rollouts, max_turns, words[j])
                 for j, (tid, room) in enumerate(zip(thread_ids, rooms))]
+
+    def advise(self, thread_id: str, player_id: Optional[int] = None, n_rollouts: int = 4096, max_turns: int = 1024) -> Dict[str, Any]:
+        """As RoomService.advise (same candidates, keys, seed and output), from the thread's pool slot."""
+        return self.advises([thread_id], None if player_id is None else [player_id], n_rollouts, max_turns)[0]
+
+    def advises(self, thread_ids: Sequence[str], player_ids: Optional[Sequence[Optional[int]]] = None, n_rollouts: int = 4096,
+                max_turns: int = 1024) -> List[Dict[str, Any]]:
+        """Advice for many threads, in order (player_ids[j] None or absent: thread j's lowest human seat): one rollout_actions
+        call per chunk touched, each thread's entries as RoomService.advise's.  No thread changes."""
+        check_forecast_args(n_rollouts, max_turns)
+        rooms = [self._rooms[tid] for tid in thread_ids]          # KeyError for an unknown thread, before anything runs
+        pids = list(player_ids) if player_ids is not None else [None] * len(rooms)
+        if len(pids) != len(rooms):
+            raise ValueError("advises: thread_ids and player_ids differ in length")
+        seats = [advise_seat(tid, room["human_seats"], pid) for tid, room, pid in zip(thread_ids, rooms, pids)]
+        cands = [advise_candidates(room["table"], room["view"]) for room in rooms]
+        by_chunk: Dict[int, List[int]] = {}
+        for j, room in enumerate(rooms):
+            by_chunk.setdefault(id(room["chunk"]), []).append(j)
+        res: List[Any] = [None] * len(rooms)
+        per_call = max(1, (1 << 26) // int(n_rollouts))          # the library's cap on entries x rollouts of one call
+        for js in by_chunk.values():
+            chunk = rooms[js[0]]["chunk"]
+            parts: List[List[int]] = [[]]
+            n_ent = 0
+            for j in js:                                          # one call per chunk, split only where the cap needs it
+                if parts[-1] and n_ent + len(cands[j]) + 1 > per_call:
+                    parts.append([])
+                    n_ent = 0
+                parts[-1].append(j)
+                n_ent += len(cands[j]) + 1
+            for part in parts:
+                ent: Tuple[list, list, list, list] = ([], [], [], [])
+                for j in part:
+                    for dst, src in zip(ent, advise_entries(rooms[j]["slot"], rooms[j]["key"], rooms[j]["turn"], seats[j], cands[j])):
+                        dst.extend(src)
+                words, status = chunk.rollout_actions(*ent, n_rollouts, max_turns, seed=forecast_seed(self.seed))
+                at = 0
+                for j in part:
+                    k = len(cands[j]) + 1
+                    res[j] = (words[at:at + k], status[at:at + k])
+                    at += k
+        return [advise_output(room["table"], room["names"], tid, room["turn"], seats[j], room["view"], cands[j], n_rollouts, max_turns,
+                              *res[j]) for j, (tid, room) in enumerate(zip(thread_ids, rooms))]
 
     def close(self, thread_id: Optional[str] = None):
         """Close one thread (its slot goes back to the pool's free list) or, without an id, every thread and every chunk."""

@@ -12,7 +12,7 @@ are folded from those calls exactly as the reference's `_execute_*` functions wo
 from __future__ import annotations
 
 import re
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, Optional, Tuple
 
 from . import messages as M
 from .stepper import (GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, agent_state_to_view, load_dsl_by_gamename, rollout_to_dict,
@@ -113,6 +113,46 @@ def forecast_output(table: GameTable, names: List[str], thread_id: str, turn: in
     else:
         out["players"] = {str(i + 1): {"name": nm, "scoreSum": d["seat_score"][i], "topScore": d["seat_wins"][i]} for i, nm in enumerate(names)}
     return out
+
+
+def advise_candidates(table: GameTable, view) -> List[int]:
+    """The choices a seat may make in the room's current phase, as messages.resolve can read them: Werewolf every seat id
+    1..n, Two-Truths [1] in the statements phase and [1, 2, 3] otherwise.  The device decides which are legal."""
+    n = int(view["n_players"])
+    if table.pack == PACK_WEREWOLF:
+        return list(range(1, n + 1))
+    pid = int(view["phase_id"])
+    act = next((r["act"] for r in table.rows() if r["phase_id"] == pid), 0)
+    return [1] if act == M.ACT_TT_STATEMENTS else [1, 2, 3]
+
+
+def advise_seat(thread_id: str, human_seats: List[int], player_id: Optional[int]) -> int:
+    if player_id is not None:
+        return int(player_id)
+    if not human_seats:
+        raise ValueError(f"thread {thread_id!r} has no human seat: name the player to advise")
+    return min(human_seats)
+
+
+def advise_entries(slot: int, thread_key: int, turn: int, seat: int, cands: List[int]) -> Tuple[list, list, list, list]:
+    """rollout_actions entries of one advise: one per candidate, then the policy's (no action), all under the forecast key."""
+    k = len(cands) + 1
+    return ([slot] * k, [forecast_key(thread_key)] * k, [turn] * k, [[(seat, c)] for c in cands] + [[]])
+
+
+def advise_output(table: GameTable, names: List[str], thread_id: str, turn: int, seat: int, view, cands: List[int], n_rollouts: int,
+                  max_turns: int, words, status) -> Dict[str, Any]:
+    """advise's JSON from the words and verdicts of advise_entries (the same bytes as room_service.js / room_pool.js)."""
+    options = []
+    for j, c in enumerate(cands):
+        if int(status[j]) != 0:
+            continue
+        label = names[c - 1] if table.pack == PACK_WEREWOLF else str(c)
+        options.append({"choice": c, "label": label,
+                        "forecast": forecast_output(table, names, thread_id, turn, n_rollouts, max_turns, words[j])})
+    return {"threadId": thread_id, "turn": int(turn), "playerId": int(seat), "phaseId": int(view["phase_id"]),
+            "rollouts": int(n_rollouts), "maxTurns": int(max_turns),
+            "policy": forecast_output(table, names, thread_id, turn, n_rollouts, max_turns, words[len(cands)]), "options": options}
 
 
 class RoomService:
@@ -258,6 +298,24 @@ class RoomService:
         turn = batch.turn
         w = batch.rollout_rooms([0], [forecast_key(room["key"])], [turn], n_rollouts, max_turns, seed=forecast_seed(self.seed))[0]
         return forecast_output(room["table"], room["names"], thread_id, turn, n_rollouts, max_turns, w)
+
+    def advise(self, thread_id: str, player_id: Optional[int] = None, n_rollouts: int = 4096, max_turns: int = 1024) -> Dict[str, Any]:
+        """What each choice the seat can make now leads to: for every candidate (advise_candidates) the forecast of the thread
+        given that the seat logs it before the next turn, and the forecast with the policy's own choice ("policy", equal to
+        forecast(thread_id)).  One rollout_actions call; every entry uses forecast's keys and seed, so replica r of every option
+        draws the same stream.  player_id defaults to the lowest human seat (ValueError if there is none).  Returns JSON
+        integers, names and labels: threadId, turn, playerId, phaseId, rollouts, maxTurns, policy, options [{choice, label,
+        forecast}] for the accepted candidates in ascending order ([] when the seat has nothing to do now).  The thread is not
+        changed."""
+        check_forecast_args(n_rollouts, max_turns)
+        room = self._rooms[thread_id]
+        seat = advise_seat(thread_id, room["human_seats"], player_id)
+        batch, view = room["batch"], room["view"]
+        turn = batch.turn
+        cands = advise_candidates(room["table"], view)
+        words, status = batch.rollout_actions(*advise_entries(0, room["key"], turn, seat, cands), n_rollouts, max_turns,
+                                              seed=forecast_seed(self.seed))
+        return advise_output(room["table"], room["names"], thread_id, turn, seat, view, cands, n_rollouts, max_turns, words, status)
 
     def close(self, thread_id: Optional[str] = None):
         for tid in ([thread_id] if thread_id else list(self._rooms)):

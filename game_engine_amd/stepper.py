@@ -329,6 +329,37 @@ class RoomBatch:
                                                 max_turns, self._seed if seed is None else seed, out.ctypes.data), "ge_batch_rollout_rooms")
         return out
 
+    def rollout_actions(self, rooms, keys, turns, actions, n_rollouts: int, max_turns: int = 1024,
+                        seed: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Playouts after given actions: entry k is rollout_rooms's entry (rooms[k], keys[k], turns[k]) with actions[k], a
+        sequence of (player_id, choice) pairs, logged in every replica, in that order, before its first turn (what
+        inject_actions would log).  Legality is decided per entry on the device: an entry any of whose actions is refused is not
+        played.  Returns (words (n, 77) uint64, status (n,) int32): status[k] = 0 and words[k] as rollout_rooms would give for
+        the room after those actions, or status[k] = the refused action's status and words[k] = 0.  An entry without actions is
+        rollout_rooms's entry word for word.  The batch is only read.  GeError only for a structural error (rollout_rooms's caps,
+        more than 12 actions in one entry), before anything runs."""
+        rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        turns = np.ascontiguousarray(turns, dtype=np.uint32)
+        actions = [list(a) for a in actions]
+        if not (len(rooms) == len(keys) == len(turns) == len(actions)):
+            raise GeError(-1, "rollout_actions: arrays differ in length")
+        first = np.zeros(len(actions) + 1, dtype=np.uint32)
+        first[1:] = np.cumsum([len(a) for a in actions])
+        flat = [pc for a in actions for pc in a]
+        players = np.ascontiguousarray([int(p) for p, _ in flat], dtype=np.uint32)
+        choices = np.ascontiguousarray([int(c) for _, c in flat], dtype=np.uint32)
+        out = np.zeros((len(rooms), _lib.ROLLOUT_WORDS), dtype=np.uint64)
+        status = np.full(len(rooms), 1, dtype=np.int32)          # 1: untouched (no ge_status is positive)
+        st = self._lib.ge_batch_rollout_actions(self._h, len(rooms), rooms.ctypes.data, keys.ctypes.data, turns.ctypes.data,
+                                                first.ctypes.data, players.ctypes.data, choices.ctypes.data, status.ctypes.data,
+                                                n_rollouts, max_turns, self._seed if seed is None else seed, out.ctypes.data)
+        # a refused entry returns its status with every entry's verdict written; a structural error or a failure of the call
+        # leaves the verdicts untouched
+        if st != 0 and (status == 1).any():
+            _check(st, "ge_batch_rollout_actions")
+        return out, status
+
     def write_agent_state(self, room: int, state: Dict[str, Any], visit_actions: Optional[Dict[Any, int]] = None) -> Dict[str, Any]:
         """Adopt a reference AgentState into one room (agent_state_to_view); returns its host-side fields."""
         return self.write_agent_states([room], [state], None if visit_actions is None else [visit_actions])[0]

@@ -40,7 +40,8 @@ extern "C" {
  *      mixed and generic batches get single-turn kernel builds; the Werewolf x 12 deal side plane is allocated on first use;
  *      later additions, new symbols only (the version stays 5): ge_batch_step_rooms + ge_batch_read_rooms_at (many game threads
  *      in one resident batch, each room stepped under its own key and turn); ge_batch_write_rooms_at (the indexed write);
- *      ge_batch_rollout_rooms + ge_rollout_stats (on-device playouts of listed rooms: win odds per side and per seat) */
+ *      ge_batch_rollout_rooms + ge_rollout_stats (on-device playouts of listed rooms: win odds per side and per seat);
+ *      ge_batch_rollout_actions (playouts that start from given actions: win odds per choice a seat can make now) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -341,6 +342,23 @@ typedef struct ge_rollout_stats {
  * caches, turn counter, GE_FLAG_TRACE buffer).  Ordered behind the previous step; synchronises. */
 int ge_batch_rollout_rooms(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
                            uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, ge_rollout_stats *out);
+
+/* Playouts after given actions.  Entry k is ge_batch_rollout_rooms's entry (rooms[k], keys[k], turns[k]) with the actions
+ * first_action[k] .. first_action[k+1]-1 (player_ids[a], choices[a]) logged in every replica, in that order, before its first
+ * turn.  Definition: the ge_batch_rollout_rooms composition with ge_batch_inject_actions(B', every replica x those actions)
+ * between write_rooms and set_turn.  An entry with no actions is ge_batch_rollout_rooms's entry, word for word.
+ * Structural errors are all-or-nothing, checked before anything runs, and leave *out and entry_status untouched: every cap and
+ * range check of ge_batch_rollout_rooms; GE_ERR_ARG for a NULL array with n > 0 (entry_status may be NULL), first_action[0] != 0,
+ * decreasing offsets, or more than GE_MAX_PLAYERS actions in one entry.
+ * Legality is decided per entry on the device, by the code of ge_batch_inject_actions (a living target of the current phase's
+ * condition, not yet acted this visit, a choice in range).  If an action of entry k is refused, entry_status[k] gets that
+ * action's status, the entry is not played and out[k] is untouched; every other entry is played and its entry_status[k] is
+ * GE_OK.  Returns GE_OK if every entry was played, else the status of the first refused entry.  The batch is only read.
+ * Ordered behind the previous step; synchronises. */
+int ge_batch_rollout_actions(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
+                             const uint32_t *first_action /* n + 1 offsets */, const uint32_t *player_ids, const uint32_t *choices,
+                             int32_t *entry_status /* n, may be NULL */, uint32_t n_rollouts, uint32_t max_turns, uint64_t seed,
+                             ge_rollout_stats *out);
 
 /* GE_FLAG_TRACE: events of the most recent ge_batch_step call, dst[(room - first) * *n_turns + t].
  * cap_bytes >= count * n_turns * sizeof(ge_turn_event).  Synchronises. */

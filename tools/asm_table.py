@@ -36,9 +36,10 @@ def describe(mangled: str) -> dict:
     m = re.search(r"ge_pool_kernelILi(\d)ELi(\d)E", mangled)
     if m:
         return {"kernel": "ge_pool_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True}
-    m = re.search(r"ge_rollout_kernelILi(\d)ELi(\d)E", mangled)
+    m = re.search(r"ge_rollout_kernelILi(\d)ELi(\d)E(?:Li(\d)E)?", mangled)
     if m:
-        return {"kernel": "ge_rollout_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True}
+        return {"kernel": "ge_rollout_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True,
+                "act": int(m.group(3) or 0)}
     m = re.search(r"N_1\d+(ge_[a-z_0-9]+?)E", mangled)
     return {"kernel": m.group(1) if m else mangled, "layout": "-", "lowocc": False, "generic": False, "single": False}
 
@@ -67,6 +68,8 @@ def collect(rebuild=True):
 def label(r):
     if r["kernel"] == "ge_pool_kernel":                          # ge_batch_step_rooms: one launch per segment present
         return f"{r['layout']}, indexed single-turn (ge_batch_step_rooms)" + (", GENERIC" if r["generic"] else "")
+    if r["kernel"] == "ge_rollout_kernel" and r.get("act"):      # ge_batch_rollout_actions: one launch per segment present
+        return f"{r['layout']}, playouts after actions (ge_batch_rollout_actions)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_rollout_kernel":                       # ge_batch_rollout_rooms: one launch per segment present
         return f"{r['layout']}, playouts (ge_batch_rollout_rooms)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] not in ("ge_step_kernel", "ge_step_kernel_mixed"):
