@@ -34,6 +34,14 @@
 // A refused action refuses the entry: lane 0 of the entry's first wavefront writes its status to status[e], and every
 // wavefront of the entry returns before the turn loop and adds nothing.  ge_batch_rollout_rooms launches ACT = 0, whose
 // code is the kernel's code before this form existed.
+//
+// Playouts from a seat's view (ge_batch_rollout_seats, ACT = 2; POLICY.md §3c).  After the actions, each lane re-deals what
+// seat seats[e] cannot see in its own copy of the record, from the view key of its replica, before the record goes into
+// registers.  The record is the same in every lane at that point, so it is taken into scalar registers (readfirstlane) and
+// everything that does not depend on the draws - the unknown seats, the known teams, the hidden tuples sorted by a
+// compare-exchange network, the wolf count still to place - is wave-uniform.  Per lane: at most 2 x NB picks (n-th set bit of
+// a shrinking mask, every count uniform) and, per tuple, its bits shifted from its uniform source seat to the lane's
+// destination seat in a few 64-bit bundles of bit-planes (no array indexed by seat: no scratch).  seats[e] = 0 skips it.
 
 namespace {
 
@@ -57,6 +65,10 @@ template <int ACT> struct RollArgs : RolloutArgs {
     int32_t *status;                // entry e refused: the refused action's status (written once, by the entry's first wavefront)
 };
 template <> struct RollArgs<0> : RolloutArgs {};
+// ACT = 2: the actions, then the view of seat seats[e] (1-based; 0 = the full view)
+template <> struct RollArgs<2> : RollArgs<1> {
+    const uint32_t *seats;
+};
 
 struct RollLane {
     RoomStats q;                // (zero on lanes past R)
@@ -146,6 +158,133 @@ __device__ __forceinline__ bool roll_act_tt(const SegDev &sg, const DevTable *__
     return roll_refuse(a, e, r_in, st);
 }
 
+// ---- the view re-deal (POLICY.md §3c).  vk = the replica's view key.
+__device__ __forceinline__ uint32_t view_key(uint32_t rk, uint32_t turn0) { return mix32(rk ^ 0x56494557u ^ (turn0 * GOLDEN)); }
+
+// Werewolf: the hidden tuples of the seats seat s cannot rule out, dealt again over the seats they may sit on.  `u` holds the
+// record (wave-uniform on entry); priv = the phase's action log is private (WOLF_TARGET / DOCTOR_PROTECT / DETECTIVE).
+template <int NB>
+__device__ __forceinline__ void view_redeal_ww(WW<NB> &u, uint32_t seat, uint32_t n, bool priv, uint32_t vk) {
+    constexpr int S = NB <= 8 ? 8 : 16;                      // bit-plane stride in a bundle
+    constexpr uint64_t REP = NB <= 8 ? 0x0101010101010101ull : 0x0001000100010001ull;
+    const uint32_t all = (1u << n) - 1u, me = 1u << (seat - 1u);
+    const uint32_t U = all & ~u.revealed & ~me;
+    const uint32_t team_w = u.team_w;
+    const bool s_wolf = (team_w & me) != 0u;
+    const bool s_det = (u.rb2 & me) && !(u.rb1 & me) && !(u.rb0 & me);
+    uint32_t Uw = s_wolf ? (U & team_w) : s_det ? (U & u.det_w) : 0u;
+    uint32_t Uv = s_wolf ? (U & ~team_w) : s_det ? (U & u.det_v) : 0u;
+    const uint32_t nA = popc(U & team_w), nB = popc(U & ~team_w);
+    {
+        const int need = (int)nA - (int)popc(Uw);
+        if (need < 0 || need > (int)popc(U & ~Uw & ~Uv)) { Uw = 0u; Uv = 0u; }   // the Detective's knowledge does not fit
+    }
+    const uint32_t Uq = U & ~Uw & ~Uv, need = nA - popc(Uw);
+    // the hidden tuples as sort keys: (team is werewolves, role, team, secret, elig, sub, sel[, acted, choice], seat), so the
+    // sorted list is B ascending, then A ascending; seats outside U sort last
+    uint32_t key[NB];
+#pragma unroll
+    for (int c = 0; c < NB; c++) {
+        const uint32_t role = ((u.rb0 >> c) & 1u) | ((u.rb1 >> c) & 1u) << 1 | ((u.rb2 >> c) & 1u) << 2;
+        const uint32_t team = ((u.team_v >> c) & 1u) | ((team_w >> c) & 1u) << 1;
+        const uint32_t sel = (uint32_t)(u.sel >> (4 * c)) & 15u, ch = priv ? (uint32_t)(u.choice >> (4 * c)) & 15u : 0u;
+        const uint32_t act = priv ? (u.acted >> c) & 1u : 0u;
+        const uint32_t k = ((team_w >> c) & 1u) << 27 | role << 24 | team << 22 | ((u.secret >> c) & 1u) << 21 | ((u.elig >> c) & 1u) << 20 |
+                           ((u.sub >> c) & 1u) << 19 | sel << 15 | act << 14 | ch << 10 | (uint32_t)c;
+        key[c] = ((U >> c) & 1u) ? k : 0xFFFFFFFFu;
+    }
+#pragma unroll
+    for (int i = 0; i < NB; i++)                             // compare-exchange network (odd-even transposition): static indices
+#pragma unroll
+        for (int j = i & 1; j + 1 < NB; j += 2) {
+            const uint32_t lo = key[j] < key[j + 1] ? key[j] : key[j + 1], hi = key[j] < key[j + 1] ? key[j + 1] : key[j];
+            key[j] = lo; key[j + 1] = hi;
+        }
+    // step 1: the wolf seats.  Every count is uniform, so no lane needs a popcount
+    uint32_t sw = Uw, rem = Uq;
+    for (uint32_t j = 0; j < need; j++) {
+        const uint32_t bit = 1u << nth_set_bit<NB>(rem, pick(draw(vk, 32u + j), popc(Uq) - j));
+        sw |= bit; rem &= ~bit;
+    }
+    uint32_t remW = sw, remV = U & ~sw;
+    // the moved fields as bundles of bit-planes (stride S) and of nibbles
+    const uint32_t acted_m = priv ? u.acted : 0u;
+    const uint64_t P0 = NB <= 8 ? ((uint64_t)u.rb0 | (uint64_t)u.rb1 << 8 | (uint64_t)u.rb2 << 16 | (uint64_t)u.team_v << 24 | (uint64_t)team_w << 32 |
+                                   (uint64_t)u.secret << 40 | (uint64_t)u.elig << 48 | (uint64_t)u.sub << 56)
+                                : ((uint64_t)u.rb0 | (uint64_t)u.rb1 << 16 | (uint64_t)u.rb2 << 32 | (uint64_t)u.team_v << 48);
+    const uint64_t P1 = NB <= 8 ? (uint64_t)acted_m
+                                : ((uint64_t)team_w | (uint64_t)u.secret << 16 | (uint64_t)u.elig << 32 | (uint64_t)u.sub << 48);
+    const uint64_t P2 = (uint64_t)acted_m;                   // (NB > 8 only)
+    const uint64_t ch_m = priv ? (uint64_t)u.choice : 0ull;
+    const uint64_t N0 = NB <= 8 ? ((uint64_t)u.sel | ch_m << 32) : (uint64_t)u.sel;
+    const uint64_t N1 = ch_m;                                // (NB > 8 only)
+    const uint64_t Urep = (uint64_t)U * REP;
+    uint64_t nU = 0;                                         // U as a nibble mask
+#pragma unroll
+    for (int c = 0; c < NB; c++) nU |= ((U >> c) & 1u) ? 15ull << (4 * c) : 0ull;
+    const uint64_t nUrep = NB <= 8 ? (nU | nU << 32) : nU;
+    uint64_t q0 = P0 & ~Urep, q1 = P1 & ~Urep, q2 = P2 & ~Urep, m0 = N0 & ~nUrep, m1 = N1 & ~nU;
+#pragma unroll
+    for (int q = 0; q < NB; q++) {                           // sorted position q: B[q] while q < nB, then A[q - nB]
+        if ((uint32_t)q < nA + nB) {
+            const bool inA = (uint32_t)q >= nB;
+            const uint32_t i = inA ? (uint32_t)q - nB : (uint32_t)q;
+            const uint32_t d = pick(draw(vk, (inA ? 48u : 64u) + i), (inA ? nA : nB) - i);
+            const uint32_t dst = nth_set_bit<NB>(inA ? remW : remV, d), bit = 1u << dst;
+            remW = inA ? remW & ~bit : remW;
+            remV = inA ? remV : remV & ~bit;
+            const uint32_t src = key[q] & 15u;
+            q0 |= ((P0 >> src) & REP) << dst;
+            q1 |= ((P1 >> src) & REP) << dst;
+            if (NB > 8) q2 |= ((P2 >> src) & 1ull) << dst;
+            m0 |= ((N0 >> (4 * src)) & (NB <= 8 ? 0x0000000F0000000Full : 15ull)) << (4 * dst);
+            if (NB > 8) m1 |= ((N1 >> (4 * src)) & 15ull) << (4 * dst);
+        }
+    }
+    constexpr uint32_t FM = (1u << NB) - 1u;
+    u.rb0 = (uint32_t)q0 & FM; u.rb1 = (uint32_t)(q0 >> S) & FM; u.rb2 = (uint32_t)(q0 >> (2 * S)) & FM; u.team_v = (uint32_t)(q0 >> (3 * S)) & FM;
+    if (NB <= 8) {
+        u.team_w = (uint32_t)(q0 >> 32) & FM; u.secret = (uint32_t)(q0 >> 40) & FM; u.elig = (uint32_t)(q0 >> 48) & FM; u.sub = (uint32_t)(q0 >> 56) & FM;
+        if (priv) { u.acted = (uint32_t)q1 & FM; u.choice = (typename WW<NB>::nib_t)(m0 >> 32); }
+        u.sel = (typename WW<NB>::nib_t)(uint32_t)m0;
+    } else {
+        u.team_w = (uint32_t)q1 & FM; u.secret = (uint32_t)(q1 >> 16) & FM; u.elig = (uint32_t)(q1 >> 32) & FM; u.sub = (uint32_t)(q1 >> 48) & FM;
+        if (priv) { u.acted = (uint32_t)q2 & FM; u.choice = (typename WW<NB>::nib_t)m1; }
+        u.sel = (typename WW<NB>::nib_t)m0;
+    }
+    if (!s_det) {                                            // the Detective's memory follows the new deal (2 werewolves, else 1)
+        const uint32_t K = U & (u.det_v | u.det_w);
+        u.det_w = (u.det_w & ~K) | (K & u.team_w);
+        u.det_v = (u.det_v & ~K) | (K & ~u.team_w);
+    }
+}
+
+// Two-Truths: the speaker's lie, drawn again for a seat that is not the speaker, before the reveal (`s` wave-uniform)
+template <int NB> __device__ __forceinline__ void view_redeal_tt(TT<NB> &s, uint32_t seat, uint32_t vk) {
+    const uint32_t spk = (uint32_t)__builtin_amdgcn_readfirstlane(s.speaker), lie = (uint32_t)__builtin_amdgcn_readfirstlane(s.lie);
+    const uint32_t rev = (uint32_t)__builtin_amdgcn_readfirstlane(s.revealed);
+    if (spk == 0u) return;
+    const uint32_t sp = ctz(spk);                            // the lowest speaker
+    if (sp == seat - 1u || ((rev >> sp) & 1u) || ((lie >> (2 * sp)) & 3u) == 0u) return;
+    s.lie = (lie & ~(3u << (2 * sp))) | (1u + pick(draw(vk, 80u), 3u)) << (2 * sp);
+}
+
+// the ACT = 2 prologue of a Werewolf entry: the record words after the actions, re-dealt for the entry's seat in this lane
+template <int NB>
+__device__ __forceinline__ void roll_view_ww(const SegDev &sg, const DevTable *__restrict__ tables, const RollArgs<2> &a, uint32_t e,
+                                             uint32_t rk, uint32_t turn0, uint32_t *w) {
+    using L = WWLayout<NB>;
+    const uint32_t seat = (uint32_t)__builtin_amdgcn_readfirstlane(a.seats[e]);
+    if (seat == 0u) return;
+#pragma unroll
+    for (int i = 0; i < L::WORDS; i++) w[i] = (uint32_t)__builtin_amdgcn_readfirstlane(w[i]);   // the same in every lane
+    WW<NB> u;
+    L::unpack(w, u);
+    const uint32_t act = (tables[sg.table_idx].rows[u.phase].r0 >> 2) & 7u;
+    view_redeal_ww<NB>(u, seat, sg.n_players, act == ACT_WOLF_TARGET || act == ACT_DOCTOR_PROTECT || act == ACT_DETECTIVE, view_key(rk, turn0));
+    L::pack(u, w);
+}
+
 template <int NB, int GENERIC, int ACT>
 __device__ __forceinline__ void roll_ww(const SegDev &sg, const DevTable *__restrict__ tables, const RollArgs<ACT> &a, void *lw, uint32_t e,
                                         uint32_t r_in, unsigned long long *part, uint32_t *h_end, uint32_t *h_score) {
@@ -160,6 +299,7 @@ __device__ __forceinline__ void roll_ww(const SegDev &sg, const DevTable *__rest
         if (!roll_act_ww<NB>(sg, tables, a, e, r_in, w)) return;
     const uint64_t g = key + r;
     const uint32_t rk = room_key_from(a.seed_key, g);
+    if constexpr (ACT == 2) roll_view_ww<NB>(sg, tables, a, e, rk, turn0, w);
     const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
     const DevRow *rows = reinterpret_cast<const DevRow *>(img);
     const CondShape cs = GENERIC ? pool_cond_shape(tables[sg.table_idx]) : CondShape{0u, 0u, 0u, 0u, 0u};
@@ -217,6 +357,10 @@ __device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__rest
     L::unpack(w, s);
     if constexpr (ACT != 0)
         if (!roll_act_tt<NB>(sg, tables, a, e, r_in, s)) return;
+    if constexpr (ACT == 2) {
+        const uint32_t seat = (uint32_t)__builtin_amdgcn_readfirstlane(a.seats[e]);
+        if (seat != 0u) view_redeal_tt<NB>(s, seat, view_key(rk, turn0));
+    }
     uint32_t done = tt_done_mask<NB>(s.rounds, sg.rounds);
     for (uint32_t t = 0; t < a.max_turns; t++) {
         DevRow row = lds_row<false>(rows, s.phase);
@@ -295,6 +439,7 @@ uint32_t rollout_settle_mask(const Segment &sg) {
 struct RollActions {
     const uint32_t *first, *players, *choices;
     int32_t *entry_status;
+    const uint32_t *seats;      // ge_batch_rollout_seats: the seat whose view entry k is played from (0 = full); else null
 };
 
 static int rollout_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, uint32_t n_rollouts,
@@ -321,13 +466,15 @@ static int rollout_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, co
             for (uint32_t k = 0; k < cn; k++) order[at[seg_of[k]]++] = k;
         }
         // one upload: [rooms u64 x cn][keys u64 x cn][turns u32 x cn]; with actions [first u32 x (cn + 1)][players u32 x na]
-        // [choices u32 x na]; each array from a 16 B boundary.  Then the download: [status i32 x cn] (with actions), the
-        // accumulators 8 B x ROLL_STRIDE x cn
+        // [choices u32 x na], with seats [seats u32 x cn]; each array from a 16 B boundary.  Then the download: [status i32 x cn]
+        // (with actions), the accumulators 8 B x ROLL_STRIDE x cn
         const uint32_t na = act ? act->first[c0 + cn] - act->first[c0] : 0u;
         auto up16 = [](size_t x) { return (x + 15u) & ~(size_t)15u; };
         const size_t off_keys = 8 * (size_t)cn, off_turns = 16 * (size_t)cn;
         const size_t off_first = up16(off_turns + 4 * (size_t)cn), off_pl = up16(off_first + (act ? 4 * ((size_t)cn + 1u) : 0u));
-        const size_t off_ch = up16(off_pl + 4 * (size_t)na), off_st = up16(off_ch + 4 * (size_t)na);
+        const bool view = act && act->seats;
+        const size_t off_ch = up16(off_pl + 4 * (size_t)na), off_seat = up16(off_ch + 4 * (size_t)na);
+        const size_t off_st = up16(off_seat + (view ? 4 * (size_t)cn : 0u));
         const size_t off_acc = act ? up16(off_st + 4 * (size_t)cn) : off_first;
         const size_t acc_bytes = 8 * (size_t)ROLL_STRIDE * cn, total = off_acc + acc_bytes;
         uint32_t *host32 = nullptr;
@@ -351,6 +498,10 @@ static int rollout_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, co
                 for (uint32_t x = act->first[k]; x < act->first[k + 1]; x++, at++) { h_pl[at] = act->players[x]; h_ch[at] = act->choices[x]; }
             }
             h_first[cn] = at;
+            if (view) {
+                uint32_t *h_seat = reinterpret_cast<uint32_t *>(host + off_seat);
+                for (uint32_t i = 0; i < cn; i++) h_seat[i] = act->seats[c0 + order[i]];
+            }
             memset(host + off_st, 0, 4 * (size_t)cn);          // GE_OK unless the device refuses the entry
         }
         char *dev = nullptr;
@@ -379,6 +530,11 @@ static int rollout_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, co
                 RollArgs<0> a0;
                 static_cast<RolloutArgs &>(a0) = a;
                 HIP_TRY((b->generic ? rollout_launch<1, 0>(kind, grid, s, b, a0) : rollout_launch<0, 0>(kind, grid, s, b, a0)));
+            } else if (view) {                                // ge_batch_rollout_seats: actions, then the seat's view
+                RollArgs<2> a2;
+                static_cast<RollArgs<1> &>(a2) = a;
+                a2.seats = reinterpret_cast<const uint32_t *>(dev + off_seat) + lo;
+                HIP_TRY((b->generic ? rollout_launch<1, 2>(kind, grid, s, b, a2) : rollout_launch<0, 2>(kind, grid, s, b, a2)));
             } else {
                 HIP_TRY((b->generic ? rollout_launch<1, 1>(kind, grid, s, b, a) : rollout_launch<0, 1>(kind, grid, s, b, a)));
             }
@@ -444,7 +600,35 @@ int ge_batch_rollout_actions(ge_batch *b, uint64_t n, const uint64_t *rooms, con
         if (first_action[k + 1] < first_action[k] || first_action[k + 1] - first_action[k] > GE_MAX_PLAYERS) return GE_ERR_ARG;
     for (uint64_t k = 0; k < n; k++)
         if (rooms[k] >= b->n_rooms || (uint64_t)turns[k] + max_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;
-    const RollActions act = {first_action, player_ids, choices, entry_status};
+    const RollActions act = {first_action, player_ids, choices, entry_status, nullptr};
+    return guarded([&] { return rollout_rooms_impl(b, n, rooms, keys, turns, n_rollouts, max_turns, seed, out, &act); });
+}
+
+int ge_batch_rollout_seats(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, const uint32_t *seats,
+                           const uint32_t *first_action, const uint32_t *player_ids, const uint32_t *choices, int32_t *entry_status,
+                           uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, ge_rollout_stats *out) {
+    if (!b) return GE_ERR_ARG;
+    if (n == 0) return GE_OK;
+    // ge_batch_rollout_actions's structural checks, plus the seats; all before anything runs (on an error *out and
+    // entry_status are untouched)
+    if (!rooms || !keys || !turns || !out || !seats) return GE_ERR_ARG;
+    if (first_action && (!player_ids || !choices)) return GE_ERR_ARG;
+    if (n_rollouts == 0 || n_rollouts > (1u << 20) || n > (1ull << 26) || n * (uint64_t)n_rollouts > (1ull << 26) || max_turns > 4096u)
+        return GE_ERR_ARG;
+    if (first_action) {
+        if (first_action[0] != 0) return GE_ERR_ARG;
+        for (uint64_t k = 0; k < n; k++)
+            if (first_action[k + 1] < first_action[k] || first_action[k + 1] - first_action[k] > GE_MAX_PLAYERS) return GE_ERR_ARG;
+    }
+    for (uint64_t k = 0; k < n; k++)
+        if (rooms[k] >= b->n_rooms || (uint64_t)turns[k] + max_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;
+    for (uint64_t k = 0; k < n; k++)                          // (rooms[k] is in range: its segment is known)
+        if (seats[k] > b->segs[pool_segment_of(b, rooms[k])].dev.n_players) return GE_ERR_ARG;
+    std::vector<uint32_t> none;                               // no actions: every entry's slice is empty
+    if (!first_action) none.assign(n + 1, 0u);
+    static const uint32_t nil = 0;
+    const RollActions act = {first_action ? first_action : none.data(), first_action ? player_ids : &nil, first_action ? choices : &nil,
+                             entry_status, seats};
     return guarded([&] { return rollout_rooms_impl(b, n, rooms, keys, turns, n_rollouts, max_turns, seed, out, &act); });
 }
 

@@ -536,6 +536,63 @@ napi_value RolloutActions(napi_env env, napi_callback_info info) {
     return res;
 }
 
+// rolloutSeats(batch, rooms: BigUint64Array, keys: BigUint64Array, turns: Uint32Array, seats: Uint32Array, firstAction: Uint32Array
+// (rooms.length + 1), playerIds: Uint32Array, choices: Uint32Array, nRollouts, maxTurns, seed: bigint): as rolloutActions, every
+// replica re-dealt from seat seats[k]'s view after the actions (seat 0: the full view)
+napi_value RolloutSeats(napi_env env, napi_callback_info info) {
+    size_t argc = 11;
+    napi_value argv[11];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
+    if (!b || argc < 11) return throw_status(env, GE_ERR_ARG, "rolloutSeats");
+    napi_typedarray_type tt[7];
+    size_t len[7];
+    void *data[7];
+    for (int k = 0; k < 7; k++) {
+        napi_value ab;
+        size_t off;
+        if (napi_get_typedarray_info(env, argv[1 + k], &tt[k], &len[k], &data[k], &ab, &off) != napi_ok)
+            return throw_status(env, GE_ERR_ARG, "rolloutSeats", "typed arrays expected");
+    }
+    if (tt[0] != napi_biguint64_array || tt[1] != napi_biguint64_array || tt[2] != napi_uint32_array || tt[3] != napi_uint32_array ||
+        tt[4] != napi_uint32_array || tt[5] != napi_uint32_array || tt[6] != napi_uint32_array || len[0] != len[1] || len[1] != len[2] ||
+        len[3] != len[0] || len[4] != len[0] + 1 || len[5] != len[6] || static_cast<const uint32_t *>(data[4])[len[0]] != len[5])
+        return throw_status(env, GE_ERR_ARG, "rolloutSeats",
+                            "BigUint64Array x 2, Uint32Array (turns, seats) of equal length; Uint32Array offsets (length + 1) ending at the "
+                            "length of the Uint32Array players and choices");
+    uint32_t n_rollouts = 0, max_turns = 0;
+    uint64_t seed = 0;
+    if (napi_get_value_uint32(env, argv[8], &n_rollouts) != napi_ok || napi_get_value_uint32(env, argv[9], &max_turns) != napi_ok ||
+        !get_u64(env, argv[10], &seed))
+        return throw_status(env, GE_ERR_ARG, "rolloutSeats", "nRollouts, maxTurns: numbers; seed: bigint");
+    const size_t words = sizeof(ge_rollout_stats) / 8;
+    void *out = nullptr, *st_data = nullptr;
+    napi_value buf, arr, st_buf, st_arr, res;
+    NAPI_OK(napi_create_arraybuffer(env, len[0] * sizeof(ge_rollout_stats), &out, &buf));
+    memset(out, 0, len[0] * sizeof(ge_rollout_stats));
+    NAPI_OK(napi_create_arraybuffer(env, len[0] * sizeof(int32_t), &st_data, &st_buf));
+    int32_t *status = static_cast<int32_t *>(st_data);
+    for (size_t k = 0; k < len[0]; k++) status[k] = 1;           // 1: untouched (no ge_status is positive)
+    const int st = ge_batch_rollout_seats(b, len[0], static_cast<const uint64_t *>(data[0]), static_cast<const uint64_t *>(data[1]),
+                                          static_cast<const uint32_t *>(data[2]), static_cast<const uint32_t *>(data[3]),
+                                          static_cast<const uint32_t *>(data[4]), static_cast<const uint32_t *>(data[5]),
+                                          static_cast<const uint32_t *>(data[6]), status, n_rollouts, max_turns, seed,
+                                          static_cast<ge_rollout_stats *>(out));
+    if (st != GE_OK) {
+        // a refused entry returns its status with every verdict written; a structural error or a failure of the call leaves
+        // the verdicts untouched
+        bool untouched = false;
+        for (size_t k = 0; k < len[0] && !untouched; k++) untouched = status[k] == 1;
+        if (untouched) return throw_status(env, st, "rolloutSeats");
+    }
+    NAPI_OK(napi_create_typedarray(env, napi_biguint64_array, len[0] * words, buf, 0, &arr));
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, len[0], st_buf, 0, &st_arr));
+    NAPI_OK(napi_create_object(env, &res));
+    NAPI_OK(napi_set_named_property(env, res, "words", arr));
+    NAPI_OK(napi_set_named_property(env, res, "status", st_arr));
+    return res;
+}
+
 // rolloutRooms(batch, rooms: BigUint64Array, keys: BigUint64Array, turns: Uint32Array, nRollouts, maxTurns, seed: bigint):
 // BigUint64Array of rooms.length x 77 words (ge_rollout_stats k at [77 k, 77 k + 77)) - playouts of each listed room
 napi_value RolloutRooms(napi_env env, napi_callback_info info) {
@@ -845,6 +902,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"readRoomsAt", nullptr, ReadRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"rolloutRooms", nullptr, RolloutRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"rolloutActions", nullptr, RolloutActions, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"rolloutSeats", nullptr, RolloutSeats, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"writeRoomsAt", nullptr, WriteRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"summary", nullptr, Summary, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"reset", nullptr, Reset, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -78,6 +78,11 @@ export class RoomBatch {
   rolloutActions(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>,
                  actions: ArrayLike<ArrayLike<[number, number]>>, nRollouts: number, maxTurns?: number,
                  seed?: bigint | number): { words: BigUint64Array; status: Int32Array };
+  /** Playouts from a seat's view (POLICY.md §3c): rolloutActions's entry k with every replica re-dealt, after the actions, over
+   *  what seat seats[k] cannot see; seats[k] = 0 is rolloutActions's entry word for word.  actions null: none.  The batch is only read. */
+  rolloutSeats(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, seats: ArrayLike<number>,
+               actions: ArrayLike<ArrayLike<[number, number]>> | null, nRollouts: number, maxTurns?: number,
+               seed?: bigint | number): { words: BigUint64Array; status: Int32Array };
   /** out[k] = room rooms[k] (any order, repeats allowed). */
   readRoomsAt(rooms: ArrayLike<number | bigint>): RoomState[];
   readRoomsAtRaw(rooms: ArrayLike<number | bigint>): ArrayBuffer;

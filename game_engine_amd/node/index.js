@@ -602,6 +602,20 @@ class RoomBatch {
                                 Uint32Array.from(turns), first, Uint32Array.from(flat, (pc) => pc[0]), Uint32Array.from(flat, (pc) => pc[1]),
                                 nRollouts, maxTurns, seed === undefined ? this.seed : BigInt(seed));
   }
+  /** Playouts from a seat's view (twin of the Python RoomBatch.rollout_seats, POLICY.md §3c): rolloutActions's entry k with every
+   * replica's copy re-dealt, after the actions, over what seat seats[k] (1-based) cannot see; seats[k] = 0: the full view,
+   * rolloutActions's entry word for word.  actions may be omitted (null: no actions).  Returns { words, status } as
+   * rolloutActions.  Throws only for a structural error (rolloutActions's, or a seat above its room's player count).  The batch
+   * is only read.  Synchronous. */
+  rolloutSeats(rooms, keys, turns, seats, actions, nRollouts, maxTurns = 1024, seed) {
+    const acts = actions == null ? Array.from(rooms, () => []) : Array.from(actions, (a) => Array.from(a));
+    const first = new Uint32Array(acts.length + 1);
+    acts.forEach((a, k) => { first[k + 1] = first[k] + a.length; });
+    const flat = acts.flat();
+    return addon.rolloutSeats(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r)), BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))),
+                              Uint32Array.from(turns), Uint32Array.from(seats), first, Uint32Array.from(flat, (pc) => pc[0]),
+                              Uint32Array.from(flat, (pc) => pc[1]), nRollouts, maxTurns, seed === undefined ? this.seed : BigInt(seed));
+  }
   /** The listed rooms' states, out[k] = room rooms[k] (any order, repeats allowed). */
   readRoomsAt(rooms) {
     const buf = this.readRoomsAtRaw(rooms);

@@ -10,8 +10,8 @@
  * stepRooms and one readRoomsAt.  The chunks are shared, so every call of the service runs strictly one after the other.
  */
 const { GameTable, RoomBatch, RoomLog, decodeRoom, turnToolCalls, uiToolCalls } = require('./index.js');
-const { roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput, adviseCandidates, adviseSeat,
-        adviseEntries, adviseOutput } = require('./room_service.js');
+const { roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, adviseCandidates, adviseSeat,
+        adviseEntries, adviseOutput, seatForecastOutput, checkForecastSeat, checkView } = require('./room_service.js');
 const M = require('./messages.js');
 
 const GE_ERR_ARG = -1;
@@ -185,18 +185,19 @@ class RoomPoolService {
       return out;
     });
   }
-  /** As RoomService.forecast (same keys, seed and output), from the thread's pool slot. */
-  forecast(threadId, nRollouts = 4096, maxTurns = 1024) {
-    return this.forecasts([threadId], nRollouts, maxTurns).then((o) => o[0]);
+  /** As RoomService.forecast (same keys, seed, seat view and output), from the thread's pool slot. */
+  forecast(threadId, nRollouts = 4096, maxTurns = 1024, seat) {
+    return this.forecasts([threadId], nRollouts, maxTurns, seat === undefined || seat === null ? undefined : [seat]).then((o) => o[0]);
   }
-  /** As RoomService.advise (same candidates, keys, seed and output), from the thread's pool slot. */
-  advise(threadId, playerId, nRollouts = 4096, maxTurns = 1024) {
-    return this.advises([threadId], [playerId], nRollouts, maxTurns).then((o) => o[0]);
+  /** As RoomService.advise (same candidates, keys, seed, views and output), from the thread's pool slot. */
+  advise(threadId, playerId, nRollouts = 4096, maxTurns = 1024, view = 'full') {
+    return this.advises([threadId], [playerId], nRollouts, maxTurns, view).then((o) => o[0]);
   }
   /** Advice for many threads, in order (playerIds[j] undefined / null or no playerIds: thread j's lowest human seat): one
-   * rolloutActions call per chunk touched.  No thread changes. */
-  advises(threadIds, playerIds, nRollouts = 4096, maxTurns = 1024) {
+   * rolloutActions call per chunk touched (rolloutSeats in the "seat" view).  No thread changes. */
+  advises(threadIds, playerIds, nRollouts = 4096, maxTurns = 1024, view = 'full') {
     checkForecastArgs(nRollouts, maxTurns);
+    const seatView = checkView(view);
     return this._serial(() => {
       const rooms = threadIds.map((t) => this._room(t));
       const pids = playerIds || [];
@@ -219,26 +220,31 @@ class RoomPoolService {
           nEnt += cands[j].length + 1;
         }
         for (const part of parts) {
-          const ent = [[], [], [], []], at = [];
+          const ent = [[], [], [], []], at = [], eseats = [];
           for (const j of part) {
             at.push(ent[0].length);
             adviseEntries(rooms[j].slot, rooms[j].key, rooms[j].turn, seats[j], cands[j]).forEach((src, i) => ent[i].push(...src));
+            for (let i = 0; i <= cands[j].length; i++) eseats.push(seats[j]);
           }
-          const res = chunk.rolloutActions(ent[0], ent[1], ent[2], ent[3], nRollouts, maxTurns, seed);
+          const res = seatView ? chunk.rolloutSeats(ent[0], ent[1], ent[2], eseats, ent[3], nRollouts, maxTurns, seed)
+                               : chunk.rolloutActions(ent[0], ent[1], ent[2], ent[3], nRollouts, maxTurns, seed);
           part.forEach((j, k) => {
             out[j] = adviseOutput(rooms[j].table, rooms[j].names, threadIds[j], rooms[j].turn, seats[j], rooms[j].state, cands[j], nRollouts,
-                                  maxTurns, res, at[k]);
+                                  maxTurns, res, at[k], seatView);
           });
         }
       }
       return out;
     });
   }
-  /** Forecasts of many threads, in order: one rolloutRooms per chunk touched.  No thread changes. */
-  forecasts(threadIds, nRollouts = 4096, maxTurns = 1024) {
+  /** Forecasts of many threads, in order: one rolloutRooms per chunk touched; with seats (seats[j] 1 .. n: thread j from that
+   * seat's view, undefined / null: the full view), one rolloutSeats per chunk touched.  No thread changes. */
+  forecasts(threadIds, nRollouts = 4096, maxTurns = 1024, seats) {
     checkForecastArgs(nRollouts, maxTurns);
     return this._serial(() => {
       const rooms = threadIds.map((t) => this._room(t));
+      const sv = seats || [];
+      rooms.forEach((room, j) => checkForecastSeat(threadIds[j], room.names.length, sv[j]));
       const byChunk = new Map();
       rooms.forEach((room, j) => {
         if (!byChunk.has(room.chunk)) byChunk.set(room.chunk, []);
@@ -250,9 +256,12 @@ class RoomPoolService {
       for (const [chunk, js] of byChunk) {
         for (let lo = 0; lo < js.length; lo += perCall) {
           const part = js.slice(lo, lo + perCall);
-          const w = chunk.rolloutRooms(part.map((j) => rooms[j].slot), part.map((j) => forecastKey(rooms[j].key)), part.map((j) => rooms[j].turn),
-                                       nRollouts, maxTurns, seed);
-          part.forEach((j, k) => { out[j] = forecastOutput(rooms[j].table, rooms[j].names, threadIds[j], rooms[j].turn, nRollouts, maxTurns, w, 77 * k); });
+          const ent = [part.map((j) => rooms[j].slot), part.map((j) => forecastKey(rooms[j].key)), part.map((j) => rooms[j].turn)];
+          const w = seats ? chunk.rolloutSeats(...ent, part.map((j) => sv[j] || 0), null, nRollouts, maxTurns, seed).words
+                          : chunk.rolloutRooms(...ent, nRollouts, maxTurns, seed);
+          part.forEach((j, k) => {
+            out[j] = seatForecastOutput(rooms[j].table, rooms[j].names, threadIds[j], rooms[j].turn, nRollouts, maxTurns, sv[j], w, 77 * k);
+          });
         }
       }
       return out;

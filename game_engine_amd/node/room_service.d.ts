@@ -21,6 +21,8 @@ export interface Forecast {
   threadId: string; turn: number; rollouts: number; maxTurns: number;
   /** playouts that reached a terminal phase; the sum of their end turns; those with an end turn */
   finished: number; endTurnSum: number; ended: number;
+  /** present when the forecast is from a seat's view */
+  seat?: number;
   /** Werewolf: finished playouts won by each side */
   sides?: { villagers: number; werewolves: number };
   /** Werewolf: {name, alive, wins}; Two-Truths: {name, scoreSum, topScore} */
@@ -33,6 +35,8 @@ export interface Advice {
   policy: Forecast;
   /** the accepted candidates in ascending order; label = the seat's name (Werewolf) or the statement number (Two-Truths) */
   options: { choice: number; label: string; forecast: Forecast }[];
+  /** "seat" when every playout started from what the advised seat knows */
+  view?: 'seat';
 }
 export class RoomService {
   constructor(opts?: { gamesDir?: string; seed?: bigint | number; device?: number });
@@ -49,11 +53,13 @@ export class RoomService {
   /** items: the frontend's canvas items (AgentState.items), for clearCanvas's exemptList */
   continueRoom(threadId: string, items?: { id: string; type: string }[]): Promise<TurnResult>;
   /** nRollouts playouts (<= 65 536) of the thread's room, every seat played by the policy, keyed (threadKey << 16) + r under seed
-   *  (service seed ^ 0x9E3779B97F4A7C15); the thread is not changed (INTEGRATION.md "Forecasting a thread"). */
-  forecast(threadId: string, nRollouts?: number, maxTurns?: number): Promise<Forecast>;
+   *  (service seed ^ 0x9E3779B97F4A7C15); the thread is not changed (INTEGRATION.md "Forecasting a thread").  seat: from what that
+   *  seat knows (hidden roles / the lie dealt again per replica); the JSON gains "seat". */
+  forecast(threadId: string, nRollouts?: number, maxTurns?: number, seat?: number): Promise<Forecast>;
   /** For every choice playerId (default: the lowest human seat; RangeError if there is none) can make now, the forecast given
-   *  that choice, under forecast's keys and seed; the thread is not changed (INTEGRATION.md "Advising a seat"). */
-  advise(threadId: string, playerId?: number, nRollouts?: number, maxTurns?: number): Promise<Advice>;
+   *  that choice, under forecast's keys and seed; the thread is not changed (INTEGRATION.md "Advising a seat").  view "seat": from
+   *  what that seat knows, the form to show a player (INTEGRATION.md "Advising a seat from what it knows"); the JSON gains "view". */
+  advise(threadId: string, playerId?: number, nRollouts?: number, maxTurns?: number, view?: 'full' | 'seat'): Promise<Advice>;
   /** Forget a thread and free its device memory; resolves false for an unknown thread. */
   close(threadId: string): Promise<boolean>;
   serve(port?: number): Promise<import('http').Server>;

@@ -92,6 +92,21 @@ function forecastOutput(table, names, threadId, turn, nRollouts, maxTurns, w, of
   return out;
 }
 
+/** forecast's JSON; from a seat's view it gains "seat" (twin of room_service.py seat_forecast_output). */
+function seatForecastOutput(table, names, threadId, turn, nRollouts, maxTurns, seat, w, off = 0) {
+  const out = forecastOutput(table, names, threadId, turn, nRollouts, maxTurns, w, off);
+  if (seat !== undefined && seat !== null) out.seat = Number(seat);
+  return out;
+}
+function checkForecastSeat(threadId, n, seat) {
+  if (seat !== undefined && seat !== null && !(Number.isInteger(seat) && seat >= 1 && seat <= n))
+    throw new RangeError(`thread ${threadId}: seat must be 1 .. ${n}`);
+}
+function checkView(view) {
+  if (view !== undefined && view !== 'full' && view !== 'seat') throw new RangeError('view must be "full" or "seat"');
+  return view === 'seat';
+}
+
 /** The choices a seat may make in the room's current phase, as messages.resolve can read them (twin of room_service.py
  * advise_candidates): Werewolf every seat id 1..n, Two-Truths [1] in the statements phase and [1, 2, 3] otherwise. */
 function adviseCandidates(table, st) {
@@ -111,15 +126,17 @@ function adviseEntries(slot, threadKey, turn, seat, cands) {
   return [new Array(k).fill(slot), new Array(k).fill(forecastKey(threadKey)), new Array(k).fill(turn), cands.map((c) => [[seat, c]]).concat([[]])];
 }
 /** advise's JSON from the words and verdicts of adviseEntries at entry offset `at`: the bytes the Python hosts print. */
-function adviseOutput(table, names, threadId, turn, seat, st, cands, nRollouts, maxTurns, res, at = 0) {
+function adviseOutput(table, names, threadId, turn, seat, st, cands, nRollouts, maxTurns, res, at = 0, seatView = false) {
   const options = [];
   cands.forEach((c, j) => {
     if (res.status[at + j] !== 0) return;
     options.push({ choice: c, label: st.pack === 1 ? names[c - 1] : String(c),
                    forecast: forecastOutput(table, names, threadId, turn, nRollouts, maxTurns, res.words, 77 * (at + j)) });
   });
-  return { threadId, turn: Number(turn), playerId: seat, phaseId: st.current_phase_id, rollouts: nRollouts, maxTurns,
-           policy: forecastOutput(table, names, threadId, turn, nRollouts, maxTurns, res.words, 77 * (at + cands.length)), options };
+  const out = { threadId, turn: Number(turn), playerId: seat, phaseId: st.current_phase_id, rollouts: nRollouts, maxTurns,
+                policy: forecastOutput(table, names, threadId, turn, nRollouts, maxTurns, res.words, 77 * (at + cands.length)), options };
+  if (seatView) out.view = 'seat';
+  return out;
 }
 
 class RoomService {
@@ -187,31 +204,39 @@ class RoomService {
    * (threadKey << 16) + r, so nRollouts <= 65 536 (RangeError above), under seed (service seed ^ 0x9E3779B97F4A7C15); two forecasts
    * at the same turn are identical and the thread is not changed.  Resolves with JSON integers: threadId, turn, rollouts, maxTurns,
    * finished, endTurnSum, ended, and per seat (Werewolf: sides {villagers, werewolves}, players {"1": {name, alive, wins}};
-   * Two-Truths: players {"1": {name, scoreSum, topScore}}). */
-  forecast(threadId, nRollouts = 4096, maxTurns = 1024) {
+   * Two-Truths: players {"1": {name, scoreSum, topScore}}).  seat (1 .. n): the playouts start from what that seat knows
+   * (rolloutSeats, POLICY.md §3c) and the JSON gains "seat" - the form to show a player; the default is the full view. */
+  forecast(threadId, nRollouts = 4096, maxTurns = 1024, seat) {
     checkForecastArgs(nRollouts, maxTurns);
     const room = this.rooms.get(threadId);
     if (!room) return Promise.reject(new Error(`unknown thread ${threadId}`));
+    checkForecastSeat(threadId, room.names.length, seat);
     return this._serial(room, () => {
-      const w = room.batch.rolloutRooms([0], [forecastKey(room.key)], [room.turn], nRollouts, maxTurns, forecastSeed(this.seed));
-      return forecastOutput(room.table, room.names, threadId, room.turn, nRollouts, maxTurns, w);
+      const w = seat === undefined || seat === null
+        ? room.batch.rolloutRooms([0], [forecastKey(room.key)], [room.turn], nRollouts, maxTurns, forecastSeed(this.seed))
+        : room.batch.rolloutSeats([0], [forecastKey(room.key)], [room.turn], [seat], null, nRollouts, maxTurns, forecastSeed(this.seed)).words;
+      return seatForecastOutput(room.table, room.names, threadId, room.turn, nRollouts, maxTurns, seat, w);
     });
   }
   /** What each choice the seat can make now leads to (twin of the Python RoomService.advise): for every candidate the forecast given
    * that the seat logs it before the next turn, and the policy's own ("policy", equal to forecast(threadId)).  One rolloutActions
    * call under forecast's keys and seed.  playerId defaults to the lowest human seat (RangeError if there is none).  Resolves with
    * { threadId, turn, playerId, phaseId, rollouts, maxTurns, policy, options: [{ choice, label, forecast }] } for the accepted
-   * candidates in ascending order.  The thread is not changed. */
-  advise(threadId, playerId, nRollouts = 4096, maxTurns = 1024) {
+   * candidates in ascending order.  The thread is not changed.  view "seat": every playout starts from what the advised seat knows
+   * (rolloutSeats) - the form to show that player - and the JSON gains "view": "seat"; "full" (the default) is for spectators. */
+  advise(threadId, playerId, nRollouts = 4096, maxTurns = 1024, view = 'full') {
     checkForecastArgs(nRollouts, maxTurns);
+    const seatView = checkView(view);
     const room = this.rooms.get(threadId);
     if (!room) return Promise.reject(new Error(`unknown thread ${threadId}`));
     const seat = adviseSeat(threadId, room.humanSeats, playerId);
     return this._serial(room, () => {
       const cands = adviseCandidates(room.table, room.state);
       const [rooms, keys, turns, acts] = adviseEntries(0, room.key, room.turn, seat, cands);
-      const res = room.batch.rolloutActions(rooms, keys, turns, acts, nRollouts, maxTurns, forecastSeed(this.seed));
-      return adviseOutput(room.table, room.names, threadId, room.turn, seat, room.state, cands, nRollouts, maxTurns, res);
+      const res = seatView
+        ? room.batch.rolloutSeats(rooms, keys, turns, new Array(rooms.length).fill(seat), acts, nRollouts, maxTurns, forecastSeed(this.seed))
+        : room.batch.rolloutActions(rooms, keys, turns, acts, nRollouts, maxTurns, forecastSeed(this.seed));
+      return adviseOutput(room.table, room.names, threadId, room.turn, seat, room.state, cands, nRollouts, maxTurns, res, 0, seatView);
     });
   }
   /** Forget a thread and free its device memory (after queued requests have finished). */
@@ -312,4 +337,4 @@ class RoomService {
 }
 
 module.exports = { RoomService, roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput,
-                   adviseCandidates, adviseSeat, adviseEntries, adviseOutput };
+                   adviseCandidates, adviseSeat, adviseEntries, adviseOutput, seatForecastOutput, checkForecastSeat, checkView };

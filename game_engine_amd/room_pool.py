@@ -18,7 +18,8 @@ import numpy as np
 
 from . import messages as M
 from .room_service import (adopted_output, advise_candidates, advise_entries, advise_output, advise_seat, check_forecast_args,
-                           forecast_key, forecast_output, forecast_seed, prepare_adoption, room_index_of)
+                           check_forecast_seat, check_view, forecast_key, forecast_seed, prepare_adoption, room_index_of,
+                           seat_forecast_output)
 from .stepper import GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, load_dsl_by_gamename, slot_values
 from .toolcalls import WW_IS_ALIVE, RoomLog, turn_tool_calls
 from .ui_script import ui_tool_calls
@@ -250,15 +251,23 @@ class RoomPoolService:
         room["panel"] = M.newest_panel(ui)
         return {"state": state, "toolCalls": calls, "uiCalls": ui}
 
-    def forecast(self, thread_id: str, n_rollouts: int = 4096, max_turns: int = 1024) -> Dict[str, Any]:
-        """As RoomService.forecast (same keys, seed and output), from the thread's pool slot."""
-        return self.forecasts([thread_id], n_rollouts, max_turns)[0]
+    def forecast(self, thread_id: str, n_rollouts: int = 4096, max_turns: int = 1024, seat: Optional[int] = None) -> Dict[str, Any]:
+        """As RoomService.forecast (same keys, seed, seat view and output), from the thread's pool slot."""
+        return self.forecasts([thread_id], n_rollouts, max_turns, None if seat is None else [seat])[0]
 
-    def forecasts(self, thread_ids: Sequence[str], n_rollouts: int = 4096, max_turns: int = 1024) -> List[Dict[str, Any]]:
+    def forecasts(self, thread_ids: Sequence[str], n_rollouts: int = 4096, max_turns: int = 1024,
+                  seats: Optional[Sequence[Optional[int]]] = None) -> List[Dict[str, Any]]:
         """Forecasts of many threads, in order: one rollout_rooms call per chunk touched (replica r of a thread is global room
-        (thread_key << 16) + r under seed service seed ^ 0x9E3779B97F4A7C15, from the thread's own turn).  No thread changes."""
+        (thread_key << 16) + r under seed service seed ^ 0x9E3779B97F4A7C15, from the thread's own turn).  seats[j] (1 .. n):
+        thread j's forecast from that seat's view, as RoomService.forecast(seat=...); with seats, one rollout_seats call per
+        chunk touched (seat 0 there for the threads without one: their full view).  No thread changes."""
         check_forecast_args(n_rollouts, max_turns)
         rooms = [self._rooms[tid] for tid in thread_ids]          # KeyError for an unknown thread, before anything runs
+        sv = list(seats) if seats is not None else [None] * len(rooms)
+        if len(sv) != len(rooms):
+            raise ValueError("forecasts: thread_ids and seats differ in length")
+        for tid, room, st in zip(thread_ids, rooms, sv):
+            check_forecast_seat(tid, len(room["names"]), st)
         by_chunk: Dict[int, List[int]] = {}
         for j, room in enumerate(rooms):
             by_chunk.setdefault(id(room["chunk"]), []).append(j)
@@ -268,22 +277,28 @@ class RoomPoolService:
             chunk = rooms[js[0]]["chunk"]
             for lo in range(0, len(js), per_call):
                 part = js[lo:lo + per_call]
-                w = chunk.rollout_rooms([rooms[j]["slot"] for j in part], [forecast_key(rooms[j]["key"]) for j in part],
-                                        [rooms[j]["turn"] for j in part], n_rollouts, max_turns, seed=forecast_seed(self.seed))
+                ent = ([rooms[j]["slot"] for j in part], [forecast_key(rooms[j]["key"]) for j in part], [rooms[j]["turn"] for j in part])
+                if seats is None:
+                    w = chunk.rollout_rooms(*ent, n_rollouts, max_turns, seed=forecast_seed(self.seed))
+                else:
+                    w = chunk.rollout_seats(*ent, [sv[j] or 0 for j in part], None, n_rollouts, max_turns, seed=forecast_seed(self.seed))[0]
                 for k, j in enumerate(part):
                     words[j] = w[k]
-        return [forecast_output(room["table"], room["names"], tid, room["turn"], n_rollouts, max_turns, words[j])
+        return [seat_forecast_output(room["table"], room["names"], tid, room["turn"], n_rollouts, max_turns, sv[j], words[j])
                 for j, (tid, room) in enumerate(zip(thread_ids, rooms))]
 
-    def advise(self, thread_id: str, player_id: Optional[int] = None, n_rollouts: int = 4096, max_turns: int = 1024) -> Dict[str, Any]:
-        """As RoomService.advise (same candidates, keys, seed and output), from the thread's pool slot."""
-        return self.advises([thread_id], None if player_id is None else [player_id], n_rollouts, max_turns)[0]
+    def advise(self, thread_id: str, player_id: Optional[int] = None, n_rollouts: int = 4096, max_turns: int = 1024,
+               view: str = "full") -> Dict[str, Any]:
+        """As RoomService.advise (same candidates, keys, seed, views and output), from the thread's pool slot."""
+        return self.advises([thread_id], None if player_id is None else [player_id], n_rollouts, max_turns, view)[0]
 
     def advises(self, thread_ids: Sequence[str], player_ids: Optional[Sequence[Optional[int]]] = None, n_rollouts: int = 4096,
-                max_turns: int = 1024) -> List[Dict[str, Any]]:
+                max_turns: int = 1024, view: str = "full") -> List[Dict[str, Any]]:
         """Advice for many threads, in order (player_ids[j] None or absent: thread j's lowest human seat): one rollout_actions
-        call per chunk touched, each thread's entries as RoomService.advise's.  No thread changes."""
+        call per chunk touched - rollout_seats in the "seat" view, every thread from its advised seat's view - each thread's
+        entries as RoomService.advise's.  No thread changes."""
         check_forecast_args(n_rollouts, max_turns)
+        seat_view = check_view(view)
         rooms = [self._rooms[tid] for tid in thread_ids]          # KeyError for an unknown thread, before anything runs
         pids = list(player_ids) if player_ids is not None else [None] * len(rooms)
         if len(pids) != len(rooms):
@@ -307,17 +322,23 @@ class RoomPoolService:
                 n_ent += len(cands[j]) + 1
             for part in parts:
                 ent: Tuple[list, list, list, list] = ([], [], [], [])
+                eseats: List[int] = []
                 for j in part:
                     for dst, src in zip(ent, advise_entries(rooms[j]["slot"], rooms[j]["key"], rooms[j]["turn"], seats[j], cands[j])):
                         dst.extend(src)
-                words, status = chunk.rollout_actions(*ent, n_rollouts, max_turns, seed=forecast_seed(self.seed))
+                    eseats += [seats[j]] * (len(cands[j]) + 1)
+                if seat_view:
+                    words, status = chunk.rollout_seats(ent[0], ent[1], ent[2], eseats, ent[3], n_rollouts, max_turns,
+                                                        seed=forecast_seed(self.seed))
+                else:
+                    words, status = chunk.rollout_actions(*ent, n_rollouts, max_turns, seed=forecast_seed(self.seed))
                 at = 0
                 for j in part:
                     k = len(cands[j]) + 1
                     res[j] = (words[at:at + k], status[at:at + k])
                     at += k
         return [advise_output(room["table"], room["names"], tid, room["turn"], seats[j], room["view"], cands[j], n_rollouts, max_turns,
-                              *res[j]) for j, (tid, room) in enumerate(zip(thread_ids, rooms))]
+                              *res[j], seat_view) for j, (tid, room) in enumerate(zip(thread_ids, rooms))]
 
     def close(self, thread_id: Optional[str] = None):
         """Close one thread (its slot goes back to the pool's free list) or, without an id, every thread and every chunk."""

@@ -115,6 +115,28 @@ def forecast_output(table: GameTable, names: List[str], thread_id: str, turn: in
     return out
 
 
+def check_view(view: str) -> bool:
+    """advise's `view`: "full" (every playout from the true record) or "seat" (from what the advised seat knows, POLICY.md
+    §3c); True for the seat view."""
+    if view not in ("full", "seat"):
+        raise ValueError('view must be "full" or "seat"')
+    return view == "seat"
+
+
+def check_forecast_seat(thread_id: str, n_players: int, seat: Optional[int]) -> None:
+    if seat is not None and not 1 <= int(seat) <= int(n_players):
+        raise ValueError(f"thread {thread_id!r}: seat must be 1 .. {n_players}")
+
+
+def seat_forecast_output(table: GameTable, names: List[str], thread_id: str, turn: int, n_rollouts: int, max_turns: int, seat: Optional[int],
+                         words) -> Dict[str, Any]:
+    """forecast's JSON; from a seat's view it gains "seat" (the default output is unchanged)."""
+    out = forecast_output(table, names, thread_id, turn, n_rollouts, max_turns, words)
+    if seat is not None:
+        out["seat"] = int(seat)
+    return out
+
+
 def advise_candidates(table: GameTable, view) -> List[int]:
     """The choices a seat may make in the room's current phase, as messages.resolve can read them: Werewolf every seat id
     1..n, Two-Truths [1] in the statements phase and [1, 2, 3] otherwise.  The device decides which are legal."""
@@ -141,8 +163,9 @@ def advise_entries(slot: int, thread_key: int, turn: int, seat: int, cands: List
 
 
 def advise_output(table: GameTable, names: List[str], thread_id: str, turn: int, seat: int, view, cands: List[int], n_rollouts: int,
-                  max_turns: int, words, status) -> Dict[str, Any]:
-    """advise's JSON from the words and verdicts of advise_entries (the same bytes as room_service.js / room_pool.js)."""
+                  max_turns: int, words, status, seat_view: bool = False) -> Dict[str, Any]:
+    """advise's JSON from the words and verdicts of advise_entries (the same bytes as room_service.js / room_pool.js); from the
+    seat's view it gains "view": "seat"."""
     options = []
     for j, c in enumerate(cands):
         if int(status[j]) != 0:
@@ -152,7 +175,8 @@ def advise_output(table: GameTable, names: List[str], thread_id: str, turn: int,
                         "forecast": forecast_output(table, names, thread_id, turn, n_rollouts, max_turns, words[j])})
     return {"threadId": thread_id, "turn": int(turn), "playerId": int(seat), "phaseId": int(view["phase_id"]),
             "rollouts": int(n_rollouts), "maxTurns": int(max_turns),
-            "policy": forecast_output(table, names, thread_id, turn, n_rollouts, max_turns, words[len(cands)]), "options": options}
+            "policy": forecast_output(table, names, thread_id, turn, n_rollouts, max_turns, words[len(cands)]), "options": options,
+            **({"view": "seat"} if seat_view else {})}
 
 
 class RoomService:
@@ -284,38 +308,54 @@ class RoomService:
         room["panel"] = M.newest_panel(ui)                # what a person's next vote message can answer
         return {"state": state, "toolCalls": calls, "uiCalls": ui}
 
-    def forecast(self, thread_id: str, n_rollouts: int = 4096, max_turns: int = 1024) -> Dict[str, Any]:
+    def forecast(self, thread_id: str, n_rollouts: int = 4096, max_turns: int = 1024, seat: Optional[int] = None) -> Dict[str, Any]:
         """How the thread ends from where it stands: n_rollouts playouts of its room (RoomBatch.rollout_rooms), each played for
         up to max_turns turns from the thread's next turn, every seat - human seats too - played by the policy.  Replica r is
         global room (thread_key << 16) + r, so n_rollouts <= 65 536 (ValueError above), under seed (service seed ^
         0x9E3779B97F4A7C15): no forecast stream is a game stream, and two forecasts at the same turn are identical.  The thread
         is not changed.  Returns JSON integers: threadId, turn, rollouts, maxTurns, finished, endTurnSum, ended, and per seat
         (Werewolf: sides {villagers, werewolves}, players {"1": {name, alive, wins}}; Two-Truths: players {"1": {name,
-        scoreSum, topScore}}); divide by rollouts for odds."""
+        scoreSum, topScore}}); divide by rollouts for odds.  seat (1 .. n): the playouts start from what that seat knows
+        (RoomBatch.rollout_seats, POLICY.md §3c: what it cannot see is dealt again in every replica), and the JSON gains
+        "seat" - the form to show a player; the default is the full view."""
         check_forecast_args(n_rollouts, max_turns)
         room = self._rooms[thread_id]
+        check_forecast_seat(thread_id, len(room["names"]), seat)
         batch = room["batch"]
         turn = batch.turn
-        w = batch.rollout_rooms([0], [forecast_key(room["key"])], [turn], n_rollouts, max_turns, seed=forecast_seed(self.seed))[0]
-        return forecast_output(room["table"], room["names"], thread_id, turn, n_rollouts, max_turns, w)
+        if seat is None:
+            w = batch.rollout_rooms([0], [forecast_key(room["key"])], [turn], n_rollouts, max_turns, seed=forecast_seed(self.seed))[0]
+        else:
+            w = batch.rollout_seats([0], [forecast_key(room["key"])], [turn], [seat], None, n_rollouts, max_turns,
+                                    seed=forecast_seed(self.seed))[0][0]
+        return seat_forecast_output(room["table"], room["names"], thread_id, turn, n_rollouts, max_turns, seat, w)
 
-    def advise(self, thread_id: str, player_id: Optional[int] = None, n_rollouts: int = 4096, max_turns: int = 1024) -> Dict[str, Any]:
+    def advise(self, thread_id: str, player_id: Optional[int] = None, n_rollouts: int = 4096, max_turns: int = 1024,
+               view: str = "full") -> Dict[str, Any]:
         """What each choice the seat can make now leads to: for every candidate (advise_candidates) the forecast of the thread
         given that the seat logs it before the next turn, and the forecast with the policy's own choice ("policy", equal to
         forecast(thread_id)).  One rollout_actions call; every entry uses forecast's keys and seed, so replica r of every option
         draws the same stream.  player_id defaults to the lowest human seat (ValueError if there is none).  Returns JSON
         integers, names and labels: threadId, turn, playerId, phaseId, rollouts, maxTurns, policy, options [{choice, label,
         forecast}] for the accepted candidates in ascending order ([] when the seat has nothing to do now).  The thread is not
-        changed."""
+        changed.  view "seat": every playout starts from what the advised seat knows (RoomBatch.rollout_seats, POLICY.md §3c)
+        - the form to show that player - and the JSON gains "view": "seat"; "full" (the default) plays from the true record and
+        is for spectators and debugging."""
         check_forecast_args(n_rollouts, max_turns)
+        seat_view = check_view(view)
         room = self._rooms[thread_id]
         seat = advise_seat(thread_id, room["human_seats"], player_id)
-        batch, view = room["batch"], room["view"]
+        batch, rv = room["batch"], room["view"]
         turn = batch.turn
-        cands = advise_candidates(room["table"], view)
-        words, status = batch.rollout_actions(*advise_entries(0, room["key"], turn, seat, cands), n_rollouts, max_turns,
-                                              seed=forecast_seed(self.seed))
-        return advise_output(room["table"], room["names"], thread_id, turn, seat, view, cands, n_rollouts, max_turns, words, status)
+        cands = advise_candidates(room["table"], rv)
+        ent = advise_entries(0, room["key"], turn, seat, cands)
+        if seat_view:
+            words, status = batch.rollout_seats(ent[0], ent[1], ent[2], [seat] * len(ent[0]), ent[3], n_rollouts, max_turns,
+                                                seed=forecast_seed(self.seed))
+        else:
+            words, status = batch.rollout_actions(*ent, n_rollouts, max_turns, seed=forecast_seed(self.seed))
+        return advise_output(room["table"], room["names"], thread_id, turn, seat, rv, cands, n_rollouts, max_turns, words, status,
+                             seat_view)
 
     def close(self, thread_id: Optional[str] = None):
         for tid in ([thread_id] if thread_id else list(self._rooms)):

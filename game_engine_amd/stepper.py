@@ -360,6 +360,41 @@ class RoomBatch:
             _check(st, "ge_batch_rollout_actions")
         return out, status
 
+    def rollout_seats(self, rooms, keys, turns, seats, actions=None, n_rollouts: int = 4096, max_turns: int = 1024,
+                      seed: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Playouts from a seat's view (POLICY.md §3c): entry k is rollout_actions's entry (rooms[k], keys[k], turns[k],
+        actions[k]) with every replica's copy re-dealt, after the actions, over what seat seats[k] (1-based) cannot see - the
+        hidden roles of the seats it cannot rule out (Werewolf), the speaker's unrevealed lie (Two-Truths).  seats[k] = 0: the
+        full view, rollout_actions's entry word for word.  actions None: no actions in any entry.  Returns (words (n, 77)
+        uint64, status (n,) int32) as rollout_actions.  The batch is only read.  GeError only for a structural error
+        (rollout_actions's, or a seat above its room's player count), before anything runs."""
+        rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        turns = np.ascontiguousarray(turns, dtype=np.uint32)
+        seats = np.ascontiguousarray(seats, dtype=np.uint32)
+        if not (len(rooms) == len(keys) == len(turns) == len(seats)):
+            raise GeError(-1, "rollout_seats: arrays differ in length")
+        out = np.zeros((len(rooms), _lib.ROLLOUT_WORDS), dtype=np.uint64)
+        status = np.full(len(rooms), 1, dtype=np.int32)          # 1: untouched (no ge_status is positive)
+        first = players = choices = None
+        if actions is not None:
+            actions = [list(a) for a in actions]
+            if len(actions) != len(rooms):
+                raise GeError(-1, "rollout_seats: arrays differ in length")
+            first = np.zeros(len(actions) + 1, dtype=np.uint32)
+            first[1:] = np.cumsum([len(a) for a in actions])
+            flat = [pc for a in actions for pc in a]
+            players = np.ascontiguousarray([int(p) for p, _ in flat], dtype=np.uint32)
+            choices = np.ascontiguousarray([int(c) for _, c in flat], dtype=np.uint32)
+        st = self._lib.ge_batch_rollout_seats(self._h, len(rooms), rooms.ctypes.data, keys.ctypes.data, turns.ctypes.data,
+                                              seats.ctypes.data, None if first is None else first.ctypes.data,
+                                              None if players is None else players.ctypes.data,
+                                              None if choices is None else choices.ctypes.data, status.ctypes.data,
+                                              n_rollouts, max_turns, self._seed if seed is None else seed, out.ctypes.data)
+        if st != 0 and (status == 1).any():
+            _check(st, "ge_batch_rollout_seats")
+        return out, status
+
     def write_agent_state(self, room: int, state: Dict[str, Any], visit_actions: Optional[Dict[Any, int]] = None) -> Dict[str, Any]:
         """Adopt a reference AgentState into one room (agent_state_to_view); returns its host-side fields."""
         return self.write_agent_states([room], [state], None if visit_actions is None else [visit_actions])[0]

@@ -41,7 +41,8 @@ extern "C" {
  *      later additions, new symbols only (the version stays 5): ge_batch_step_rooms + ge_batch_read_rooms_at (many game threads
  *      in one resident batch, each room stepped under its own key and turn); ge_batch_write_rooms_at (the indexed write);
  *      ge_batch_rollout_rooms + ge_rollout_stats (on-device playouts of listed rooms: win odds per side and per seat);
- *      ge_batch_rollout_actions (playouts that start from given actions: win odds per choice a seat can make now) */
+ *      ge_batch_rollout_actions (playouts that start from given actions: win odds per choice a seat can make now);
+ *      ge_batch_rollout_seats (the same playouts from what one seat knows: hidden roles / the lie dealt again per replica) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -359,6 +360,19 @@ int ge_batch_rollout_actions(ge_batch *b, uint64_t n, const uint64_t *rooms, con
                              const uint32_t *first_action /* n + 1 offsets */, const uint32_t *player_ids, const uint32_t *choices,
                              int32_t *entry_status /* n, may be NULL */, uint32_t n_rollouts, uint32_t max_turns, uint64_t seed,
                              ge_rollout_stats *out);
+
+/* Playouts from a seat's view (POLICY.md §3c).  Entry k is ge_batch_rollout_actions's entry with one more step between the
+ * actions and set_turn: replica r's copy has what seat seats[k] (1-based) cannot see dealt again - Werewolf: the hidden tuples
+ * of the seats it cannot rule out, uniformly over the deals consistent with its own role, the revealed roles, its wolf
+ * partners and (a Detective) its investigations; Two-Truths: the speaker's lie while it is not revealed - from the view key
+ * mix32(room_key(seed, keys[k] + r) ^ 0x56494557 ^ turns[k] * 0x9E3779B9).  seats[k] = 0: no re-deal, the entry is
+ * ge_batch_rollout_actions's word for word.  first_action may be NULL (no actions; player_ids / choices are then not read).
+ * Structural errors as ge_batch_rollout_actions, plus GE_ERR_ARG for seats NULL with n > 0 or seats[k] > the n_players of
+ * room rooms[k]'s segment; refusals per entry as there.  The batch is only read.  Ordered behind the previous step; synchronises. */
+int ge_batch_rollout_seats(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
+                           const uint32_t *seats /* n */, const uint32_t *first_action /* n + 1, may be NULL: no actions */,
+                           const uint32_t *player_ids, const uint32_t *choices, int32_t *entry_status /* may be NULL */,
+                           uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, ge_rollout_stats *out);
 
 /* GE_FLAG_TRACE: events of the most recent ge_batch_step call, dst[(room - first) * *n_turns + t].
  * cap_bytes >= count * n_turns * sizeof(ge_turn_event).  Synchronises. */

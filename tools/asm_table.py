@@ -68,6 +68,8 @@ def collect(rebuild=True):
 def label(r):
     if r["kernel"] == "ge_pool_kernel":                          # ge_batch_step_rooms: one launch per segment present
         return f"{r['layout']}, indexed single-turn (ge_batch_step_rooms)" + (", GENERIC" if r["generic"] else "")
+    if r["kernel"] == "ge_rollout_kernel" and r.get("act") == 2:  # ge_batch_rollout_seats: one launch per segment present
+        return f"{r['layout']}, playouts from a seat's view (ge_batch_rollout_seats)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_rollout_kernel" and r.get("act"):      # ge_batch_rollout_actions: one launch per segment present
         return f"{r['layout']}, playouts after actions (ge_batch_rollout_actions)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_rollout_kernel":                       # ge_batch_rollout_rooms: one launch per segment present
