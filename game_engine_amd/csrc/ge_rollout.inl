@@ -435,120 +435,134 @@ uint32_t rollout_settle_mask(const Segment &sg) {
 
 }  // namespace
 
-// the actions of ge_batch_rollout_actions (CSR over the call's entries); null for ge_batch_rollout_rooms
-struct RollActions {
-    const uint32_t *first, *players, *choices;
+// one call of the three entry points.  first_action null: every entry's slice is empty; seats null: the full view.  act is the
+// kernel form the call launches: 0 = ge_batch_rollout_rooms, 1 = ge_batch_rollout_actions, 2 = ge_batch_rollout_seats
+struct RollRequest {
+    uint64_t n;
+    const uint64_t *rooms, *keys;
+    const uint32_t *turns, *seats, *first_action, *players, *choices;
     int32_t *entry_status;
-    const uint32_t *seats;      // ge_batch_rollout_seats: the seat whose view entry k is played from (0 = full); else null
+    uint32_t n_rollouts, max_turns;
+    uint64_t seed;
+    ge_rollout_stats *out;
+    int act;
 };
 
-static int rollout_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, uint32_t n_rollouts,
-                              uint32_t max_turns, uint64_t seed, ge_rollout_stats *out, const RollActions *act = nullptr) {
+// one chunk's staging: the upload [rooms u64 x cn][keys u64 x cn][turns u32 x cn]; with actions [first u32 x (cn + 1)]
+// [players u32 x na][choices u32 x na], with seats [seats u32 x cn]; each array from a 16 B boundary.  Then the download:
+// [status i32 x cn] (with actions), the accumulators 8 B x ROLL_STRIDE x cn
+struct RollStage {
+    size_t keys, turns, first, players, choices, seats, status, acc, total;
+};
+
+// segment g's entries [lo, lo + cnt) of the chunk staged at dev, as form ACT
+template <int ACT>
+hipError_t rollout_launch_form(const ge_batch *b, hipStream_t s, const RolloutArgs &base, char *dev, const RollStage &o, uint32_t lo) {
+    RollArgs<ACT> a;
+    static_cast<RolloutArgs &>(a) = base;
+    if constexpr (ACT >= 1) {
+        a.first_action = reinterpret_cast<const uint32_t *>(dev + o.first) + lo;
+        a.players = reinterpret_cast<const uint32_t *>(dev + o.players);
+        a.choices = reinterpret_cast<const uint32_t *>(dev + o.choices);
+        a.status = reinterpret_cast<int32_t *>(dev + o.status) + lo;
+    }
+    if constexpr (ACT == 2) a.seats = reinterpret_cast<const uint32_t *>(dev + o.seats) + lo;
+    const dim3 grid(base.n * base.waves);                   // <= 2^26 blocks (n * R <= 2^26)
+    const uint32_t kind = b->segs[base.seg].dev.kind;
+    return b->generic ? rollout_launch<1, ACT>(kind, grid, s, b, a) : rollout_launch<0, ACT>(kind, grid, s, b, a);
+}
+
+static int rollout_rooms_impl(ge_batch *b, const RollRequest &r) {
     GE_ON_DEVICE(b);
     int st = sync_impl(b);
     if (st != GE_OK) return st;
+    const bool act = r.act >= 1, view = r.act == 2;
     const uint32_t n_seg = (uint32_t)b->segs.size();
-    const uint32_t waves = (n_rollouts + 63u) / 64u;
-    const uint32_t seed_k = seed_key((uint32_t)seed, (uint32_t)(seed >> 32));
+    const uint32_t waves = (r.n_rollouts + 63u) / 64u;
+    const uint32_t seed_k = seed_key((uint32_t)r.seed, (uint32_t)(r.seed >> 32));
     std::vector<uint32_t> settle(n_seg);
     for (uint32_t g = 0; g < n_seg; g++) settle[g] = rollout_settle_mask(b->segs[g]);
-    int first_bad = GE_OK;                                  // ge_batch_rollout_actions: the status of the first refused entry
+    int first_bad = GE_OK;                                  // with actions: the status of the first refused entry
     // entries in chunks (bounded staging and accumulator memory); within a chunk a stable counting sort by segment, one launch
     // per segment present (a wavefront never mixes layouts)
     const uint64_t CHUNK = 65536;
-    for (uint64_t c0 = 0; c0 < n; c0 += CHUNK) {
-        const uint32_t cn = (uint32_t)std::min<uint64_t>(CHUNK, n - c0);
+    for (uint64_t c0 = 0; c0 < r.n; c0 += CHUNK) {
+        const uint32_t cn = (uint32_t)std::min<uint64_t>(CHUNK, r.n - c0);
         std::vector<uint32_t> seg_of(cn), begin(n_seg + 1u, 0u), order(cn);
-        for (uint32_t k = 0; k < cn; k++) { seg_of[k] = pool_segment_of(b, rooms[c0 + k]); begin[seg_of[k] + 1u]++; }
+        for (uint32_t k = 0; k < cn; k++) { seg_of[k] = pool_segment_of(b, r.rooms[c0 + k]); begin[seg_of[k] + 1u]++; }
         for (uint32_t s = 0; s < n_seg; s++) begin[s + 1u] += begin[s];
         {
             std::vector<uint32_t> at(begin.begin(), begin.end() - 1);
             for (uint32_t k = 0; k < cn; k++) order[at[seg_of[k]]++] = k;
         }
-        // one upload: [rooms u64 x cn][keys u64 x cn][turns u32 x cn]; with actions [first u32 x (cn + 1)][players u32 x na]
-        // [choices u32 x na], with seats [seats u32 x cn]; each array from a 16 B boundary.  Then the download: [status i32 x cn]
-        // (with actions), the accumulators 8 B x ROLL_STRIDE x cn
-        const uint32_t na = act ? act->first[c0 + cn] - act->first[c0] : 0u;
+        const uint32_t na = r.first_action ? r.first_action[c0 + cn] - r.first_action[c0] : 0u;
         auto up16 = [](size_t x) { return (x + 15u) & ~(size_t)15u; };
-        const size_t off_keys = 8 * (size_t)cn, off_turns = 16 * (size_t)cn;
-        const size_t off_first = up16(off_turns + 4 * (size_t)cn), off_pl = up16(off_first + (act ? 4 * ((size_t)cn + 1u) : 0u));
-        const bool view = act && act->seats;
-        const size_t off_ch = up16(off_pl + 4 * (size_t)na), off_seat = up16(off_ch + 4 * (size_t)na);
-        const size_t off_st = up16(off_seat + (view ? 4 * (size_t)cn : 0u));
-        const size_t off_acc = act ? up16(off_st + 4 * (size_t)cn) : off_first;
-        const size_t acc_bytes = 8 * (size_t)ROLL_STRIDE * cn, total = off_acc + acc_bytes;
+        RollStage o;
+        o.keys = 8 * (size_t)cn; o.turns = 16 * (size_t)cn;
+        o.first = up16(o.turns + 4 * (size_t)cn); o.players = up16(o.first + (act ? 4 * ((size_t)cn + 1u) : 0u));
+        o.choices = up16(o.players + 4 * (size_t)na); o.seats = up16(o.choices + 4 * (size_t)na);
+        o.status = up16(o.seats + (view ? 4 * (size_t)cn : 0u));
+        o.acc = act ? up16(o.status + 4 * (size_t)cn) : o.first;
+        const size_t acc_bytes = 8 * (size_t)ROLL_STRIDE * cn;
+        o.total = o.acc + acc_bytes;
         uint32_t *host32 = nullptr;
-        if ((st = io_stage(b, total, &host32)) != GE_OK) return st;
+        if ((st = io_stage(b, o.total, &host32)) != GE_OK) return st;
         unsigned char *host = reinterpret_cast<unsigned char *>(host32);
-        uint64_t *h_rooms = reinterpret_cast<uint64_t *>(host), *h_keys = reinterpret_cast<uint64_t *>(host + off_keys);
-        uint32_t *h_turns = reinterpret_cast<uint32_t *>(host + off_turns);
+        uint64_t *h_rooms = reinterpret_cast<uint64_t *>(host), *h_keys = reinterpret_cast<uint64_t *>(host + o.keys);
+        uint32_t *h_turns = reinterpret_cast<uint32_t *>(host + o.turns);
         for (uint32_t i = 0; i < cn; i++) {
             const uint64_t k = c0 + order[i];
-            h_rooms[i] = rooms[k] - b->segs[seg_of[order[i]]].local_first;
-            h_keys[i] = keys[k];
-            h_turns[i] = turns[k];
+            h_rooms[i] = r.rooms[k] - b->segs[seg_of[order[i]]].local_first;
+            h_keys[i] = r.keys[k];
+            h_turns[i] = r.turns[k];
         }
         if (act) {                                            // the actions in the sorted order, offsets from the chunk's first
-            uint32_t *h_first = reinterpret_cast<uint32_t *>(host + off_first), *h_pl = reinterpret_cast<uint32_t *>(host + off_pl);
-            uint32_t *h_ch = reinterpret_cast<uint32_t *>(host + off_ch);
+            uint32_t *h_first = reinterpret_cast<uint32_t *>(host + o.first), *h_pl = reinterpret_cast<uint32_t *>(host + o.players);
+            uint32_t *h_ch = reinterpret_cast<uint32_t *>(host + o.choices);
             uint32_t at = 0;
             for (uint32_t i = 0; i < cn; i++) {
                 const uint64_t k = c0 + order[i];
                 h_first[i] = at;
-                for (uint32_t x = act->first[k]; x < act->first[k + 1]; x++, at++) { h_pl[at] = act->players[x]; h_ch[at] = act->choices[x]; }
+                if (!r.first_action) continue;
+                for (uint32_t x = r.first_action[k]; x < r.first_action[k + 1]; x++, at++) { h_pl[at] = r.players[x]; h_ch[at] = r.choices[x]; }
             }
             h_first[cn] = at;
             if (view) {
-                uint32_t *h_seat = reinterpret_cast<uint32_t *>(host + off_seat);
-                for (uint32_t i = 0; i < cn; i++) h_seat[i] = act->seats[c0 + order[i]];
+                uint32_t *h_seat = reinterpret_cast<uint32_t *>(host + o.seats);
+                for (uint32_t i = 0; i < cn; i++) h_seat[i] = r.seats[c0 + order[i]];
             }
-            memset(host + off_st, 0, 4 * (size_t)cn);          // GE_OK unless the device refuses the entry
+            memset(host + o.status, 0, 4 * (size_t)cn);         // GE_OK unless the device refuses the entry
         }
         char *dev = nullptr;
-        if ((st = pool_scratch(b, total, &dev)) != GE_OK) return st;
+        if ((st = pool_scratch(b, o.total, &dev)) != GE_OK) return st;
         hipStream_t s = b->last_stream;
         if ((st = order_after_previous(b, s)) != GE_OK) return st;
-        HIP_TRY(hipMemcpyAsync(dev, host, off_acc, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(dev + off_acc, 0, acc_bytes, s));
+        HIP_TRY(hipMemcpyAsync(dev, host, o.acc, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(dev + o.acc, 0, acc_bytes, s));
         for (uint32_t g = 0; g < n_seg; g++) {
             const uint32_t lo = begin[g], cnt = begin[g + 1u] - lo;
             if (!cnt) continue;
-            RollArgs<1> a;
+            RolloutArgs a;
             a.rooms = reinterpret_cast<const uint64_t *>(dev) + lo;
-            a.keys = reinterpret_cast<const uint64_t *>(dev + off_keys) + lo;
-            a.turns = reinterpret_cast<const uint32_t *>(dev + off_turns) + lo;
-            a.acc = reinterpret_cast<unsigned long long *>(dev + off_acc) + (size_t)ROLL_STRIDE * lo;
-            a.n = cnt; a.seg = g; a.seed_key = seed_k; a.n_rollouts = n_rollouts; a.max_turns = max_turns; a.waves = waves;
+            a.keys = reinterpret_cast<const uint64_t *>(dev + o.keys) + lo;
+            a.turns = reinterpret_cast<const uint32_t *>(dev + o.turns) + lo;
+            a.acc = reinterpret_cast<unsigned long long *>(dev + o.acc) + (size_t)ROLL_STRIDE * lo;
+            a.n = cnt; a.seg = g; a.seed_key = seed_k; a.n_rollouts = r.n_rollouts; a.max_turns = r.max_turns; a.waves = waves;
             a.settle_mask = settle[g];
-            a.first_action = reinterpret_cast<const uint32_t *>(dev + off_first) + lo;
-            a.players = reinterpret_cast<const uint32_t *>(dev + off_pl);
-            a.choices = reinterpret_cast<const uint32_t *>(dev + off_ch);
-            a.status = reinterpret_cast<int32_t *>(dev + off_st) + lo;
-            const dim3 grid(cnt * waves);                         // <= 2^26 blocks (n * R <= 2^26)
-            const uint32_t kind = b->segs[g].dev.kind;
-            if (!act) {                                       // ge_batch_rollout_rooms: the form without actions
-                RollArgs<0> a0;
-                static_cast<RolloutArgs &>(a0) = a;
-                HIP_TRY((b->generic ? rollout_launch<1, 0>(kind, grid, s, b, a0) : rollout_launch<0, 0>(kind, grid, s, b, a0)));
-            } else if (view) {                                // ge_batch_rollout_seats: actions, then the seat's view
-                RollArgs<2> a2;
-                static_cast<RollArgs<1> &>(a2) = a;
-                a2.seats = reinterpret_cast<const uint32_t *>(dev + off_seat) + lo;
-                HIP_TRY((b->generic ? rollout_launch<1, 2>(kind, grid, s, b, a2) : rollout_launch<0, 2>(kind, grid, s, b, a2)));
-            } else {
-                HIP_TRY((b->generic ? rollout_launch<1, 1>(kind, grid, s, b, a) : rollout_launch<0, 1>(kind, grid, s, b, a)));
-            }
+            HIP_TRY((r.act == 0 ? rollout_launch_form<0>(b, s, a, dev, o, lo)
+                     : view     ? rollout_launch_form<2>(b, s, a, dev, o, lo)
+                                : rollout_launch_form<1>(b, s, a, dev, o, lo)));
         }
-        const size_t off_down = act ? off_st : off_acc;
-        const int32_t *h_st = reinterpret_cast<const int32_t *>(host + off_st);
-        const unsigned long long *h_acc = reinterpret_cast<const unsigned long long *>(host + off_acc);
-        HIP_TRY(hipMemcpyAsync(host + off_down, dev + off_down, total - off_down, hipMemcpyDeviceToHost, s));
+        const size_t off_down = act ? o.status : o.acc;
+        const int32_t *h_st = reinterpret_cast<const int32_t *>(host + o.status);
+        const unsigned long long *h_acc = reinterpret_cast<const unsigned long long *>(host + o.acc);
+        HIP_TRY(hipMemcpyAsync(host + off_down, dev + off_down, o.total - off_down, hipMemcpyDeviceToHost, s));
         if ((st = sync_impl(b)) != GE_OK) return st;
         if (act) {                                            // verdicts in input order: the first refused entry decides the result
             std::vector<int32_t> v(cn);
             for (uint32_t i = 0; i < cn; i++) v[order[i]] = h_st[i];
             for (uint32_t k = 0; k < cn; k++) {
-                if (act->entry_status) act->entry_status[c0 + k] = v[k];
+                if (r.entry_status) r.entry_status[c0 + k] = v[k];
                 if (v[k] != GE_OK && first_bad == GE_OK) first_bad = v[k];
             }
         }
@@ -556,80 +570,63 @@ static int rollout_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, co
             const uint64_t k = c0 + order[i];
             if (act && h_st[i] != GE_OK) continue;               // a refused entry's record is left as it is
             const unsigned long long *h = h_acc + (size_t)ROLL_STRIDE * i;
-            ge_rollout_stats &o = out[k];
-            memset(&o, 0, sizeof o);
-            o.summary.rooms = n_rollouts;
-            o.summary.finished = h[0]; o.summary.village_wins = h[1]; o.summary.wolf_wins = h[2]; o.summary.alive_players = h[3];
-            o.summary.sum_end_turn = h[4];
-            for (int j = 0; j < 16; j++) { o.summary.end_turn_hist[j] = h[5 + j]; o.summary.score_hist[j] = h[21 + j]; }
-            o.summary.checksum = h[37];
-            o.summary.turn = (uint64_t)turns[k] + max_turns;
-            o.summary.games_recycled = h[38];
-            for (int j = 0; j < 12; j++) { o.seat_alive[j] = h[39 + j]; o.seat_wins[j] = h[51 + j]; o.seat_score[j] = h[63 + j]; }
+            ge_rollout_stats &out = r.out[k];
+            memset(&out, 0, sizeof out);
+            out.summary.rooms = r.n_rollouts;
+            out.summary.finished = h[0]; out.summary.village_wins = h[1]; out.summary.wolf_wins = h[2]; out.summary.alive_players = h[3];
+            out.summary.sum_end_turn = h[4];
+            for (int j = 0; j < 16; j++) { out.summary.end_turn_hist[j] = h[5 + j]; out.summary.score_hist[j] = h[21 + j]; }
+            out.summary.checksum = h[37];
+            out.summary.turn = (uint64_t)r.turns[k] + r.max_turns;
+            out.summary.games_recycled = h[38];
+            for (int j = 0; j < 12; j++) { out.seat_alive[j] = h[39 + j]; out.seat_wins[j] = h[51 + j]; out.seat_score[j] = h[63 + j]; }
         }
     }
     return first_bad;
+}
+
+// the three entry points: structural checks, all before anything runs (on an error *out and entry_status are untouched), then
+// the playouts; legality is the device's.  The order of the checks is part of the ABI's behaviour: pointers, caps and the action
+// offsets (GE_ERR_ARG), then rooms and turns (GE_ERR_RANGE), then the seats (GE_ERR_ARG, after the rooms: a seat's bound is its
+// room's segment)
+static int rollout_call(ge_batch *b, const RollRequest &r) {
+    if (!b) return GE_ERR_ARG;
+    if (r.n == 0) return GE_OK;
+    const uint64_t n = r.n;
+    if (!r.rooms || !r.keys || !r.turns || !r.out) return GE_ERR_ARG;
+    if ((r.act == 1 && !r.first_action) || (r.act == 2 && !r.seats) || (r.first_action && (!r.players || !r.choices))) return GE_ERR_ARG;
+    if (r.n_rollouts == 0 || r.n_rollouts > (1u << 20) || n > (1ull << 26) || n * (uint64_t)r.n_rollouts > (1ull << 26) || r.max_turns > 4096u)
+        return GE_ERR_ARG;
+    if (r.first_action) {
+        if (r.first_action[0] != 0) return GE_ERR_ARG;
+        for (uint64_t k = 0; k < n; k++)
+            if (r.first_action[k + 1] < r.first_action[k] || r.first_action[k + 1] - r.first_action[k] > GE_MAX_PLAYERS) return GE_ERR_ARG;
+    }
+    for (uint64_t k = 0; k < n; k++)
+        if (r.rooms[k] >= b->n_rooms || (uint64_t)r.turns[k] + r.max_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;
+    if (r.seats)
+        for (uint64_t k = 0; k < n; k++)                      // (rooms[k] is in range: its segment is known)
+            if (r.seats[k] > b->segs[pool_segment_of(b, r.rooms[k])].dev.n_players) return GE_ERR_ARG;
+    return guarded([&] { return rollout_rooms_impl(b, r); });
 }
 
 extern "C" {
 
 int ge_batch_rollout_rooms(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, uint32_t n_rollouts,
                            uint32_t max_turns, uint64_t seed, ge_rollout_stats *out) {
-    if (!b) return GE_ERR_ARG;
-    if (n == 0) return GE_OK;
-    // every entry is checked before anything runs; on an error *out is untouched
-    if (!rooms || !keys || !turns || !out) return GE_ERR_ARG;
-    if (n_rollouts == 0 || n_rollouts > (1u << 20) || n > (1ull << 26) || n * (uint64_t)n_rollouts > (1ull << 26) || max_turns > 4096u)
-        return GE_ERR_ARG;
-    for (uint64_t k = 0; k < n; k++)
-        if (rooms[k] >= b->n_rooms || (uint64_t)turns[k] + max_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;
-    return guarded([&] { return rollout_rooms_impl(b, n, rooms, keys, turns, n_rollouts, max_turns, seed, out); });
+    return rollout_call(b, {n, rooms, keys, turns, nullptr, nullptr, nullptr, nullptr, nullptr, n_rollouts, max_turns, seed, out, 0});
 }
 
 int ge_batch_rollout_actions(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
                              const uint32_t *first_action, const uint32_t *player_ids, const uint32_t *choices, int32_t *entry_status,
                              uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, ge_rollout_stats *out) {
-    if (!b) return GE_ERR_ARG;
-    if (n == 0) return GE_OK;
-    // structural checks, all before anything runs (on an error *out and entry_status are untouched); legality is the device's
-    if (!rooms || !keys || !turns || !out || !first_action || !player_ids || !choices) return GE_ERR_ARG;
-    if (n_rollouts == 0 || n_rollouts > (1u << 20) || n > (1ull << 26) || n * (uint64_t)n_rollouts > (1ull << 26) || max_turns > 4096u)
-        return GE_ERR_ARG;
-    if (first_action[0] != 0) return GE_ERR_ARG;
-    for (uint64_t k = 0; k < n; k++)
-        if (first_action[k + 1] < first_action[k] || first_action[k + 1] - first_action[k] > GE_MAX_PLAYERS) return GE_ERR_ARG;
-    for (uint64_t k = 0; k < n; k++)
-        if (rooms[k] >= b->n_rooms || (uint64_t)turns[k] + max_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;
-    const RollActions act = {first_action, player_ids, choices, entry_status, nullptr};
-    return guarded([&] { return rollout_rooms_impl(b, n, rooms, keys, turns, n_rollouts, max_turns, seed, out, &act); });
+    return rollout_call(b, {n, rooms, keys, turns, nullptr, first_action, player_ids, choices, entry_status, n_rollouts, max_turns, seed, out, 1});
 }
 
 int ge_batch_rollout_seats(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, const uint32_t *seats,
                            const uint32_t *first_action, const uint32_t *player_ids, const uint32_t *choices, int32_t *entry_status,
                            uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, ge_rollout_stats *out) {
-    if (!b) return GE_ERR_ARG;
-    if (n == 0) return GE_OK;
-    // ge_batch_rollout_actions's structural checks, plus the seats; all before anything runs (on an error *out and
-    // entry_status are untouched)
-    if (!rooms || !keys || !turns || !out || !seats) return GE_ERR_ARG;
-    if (first_action && (!player_ids || !choices)) return GE_ERR_ARG;
-    if (n_rollouts == 0 || n_rollouts > (1u << 20) || n > (1ull << 26) || n * (uint64_t)n_rollouts > (1ull << 26) || max_turns > 4096u)
-        return GE_ERR_ARG;
-    if (first_action) {
-        if (first_action[0] != 0) return GE_ERR_ARG;
-        for (uint64_t k = 0; k < n; k++)
-            if (first_action[k + 1] < first_action[k] || first_action[k + 1] - first_action[k] > GE_MAX_PLAYERS) return GE_ERR_ARG;
-    }
-    for (uint64_t k = 0; k < n; k++)
-        if (rooms[k] >= b->n_rooms || (uint64_t)turns[k] + max_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;
-    for (uint64_t k = 0; k < n; k++)                          // (rooms[k] is in range: its segment is known)
-        if (seats[k] > b->segs[pool_segment_of(b, rooms[k])].dev.n_players) return GE_ERR_ARG;
-    std::vector<uint32_t> none;                               // no actions: every entry's slice is empty
-    if (!first_action) none.assign(n + 1, 0u);
-    static const uint32_t nil = 0;
-    const RollActions act = {first_action ? first_action : none.data(), first_action ? player_ids : &nil, first_action ? choices : &nil,
-                             entry_status, seats};
-    return guarded([&] { return rollout_rooms_impl(b, n, rooms, keys, turns, n_rollouts, max_turns, seed, out, &act); });
+    return rollout_call(b, {n, rooms, keys, turns, seats, first_action, player_ids, choices, entry_status, n_rollouts, max_turns, seed, out, 2});
 }
 
 }  // extern "C"

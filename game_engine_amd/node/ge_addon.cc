@@ -480,91 +480,51 @@ napi_value StepRooms(napi_env env, napi_callback_info info) {
     return out;
 }
 
-// rolloutActions(batch, rooms: BigUint64Array, keys: BigUint64Array, turns: Uint32Array, firstAction: Uint32Array (rooms.length + 1),
-// playerIds: Uint32Array, choices: Uint32Array, nRollouts, maxTurns, seed: bigint): { words: BigUint64Array of rooms.length x 77,
-// status: Int32Array of rooms.length } - playouts after given actions; a refused entry's words are 0 and its status < 0
-napi_value RolloutActions(napi_env env, napi_callback_info info) {
-    size_t argc = 10;
-    napi_value argv[10];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
-    if (!b || argc < 10) return throw_status(env, GE_ERR_ARG, "rolloutActions");
-    napi_typedarray_type tt[6];
-    size_t len[6];
-    void *data[6];
-    for (int k = 0; k < 6; k++) {
-        napi_value ab;
-        size_t off;
-        if (napi_get_typedarray_info(env, argv[1 + k], &tt[k], &len[k], &data[k], &ab, &off) != napi_ok)
-            return throw_status(env, GE_ERR_ARG, "rolloutActions", "typed arrays expected");
-    }
-    if (tt[0] != napi_biguint64_array || tt[1] != napi_biguint64_array || tt[2] != napi_uint32_array || tt[3] != napi_uint32_array ||
-        tt[4] != napi_uint32_array || tt[5] != napi_uint32_array || len[0] != len[1] || len[1] != len[2] || len[3] != len[0] + 1 ||
-        len[4] != len[5] || static_cast<const uint32_t *>(data[3])[len[0]] != len[4])
-        return throw_status(env, GE_ERR_ARG, "rolloutActions",
-                            "BigUint64Array x 2, Uint32Array (turns) of equal length; Uint32Array offsets (length + 1) ending at the "
-                            "length of the Uint32Array players and choices");
-    uint32_t n_rollouts = 0, max_turns = 0;
-    uint64_t seed = 0;
-    if (napi_get_value_uint32(env, argv[7], &n_rollouts) != napi_ok || napi_get_value_uint32(env, argv[8], &max_turns) != napi_ok ||
-        !get_u64(env, argv[9], &seed))
-        return throw_status(env, GE_ERR_ARG, "rolloutActions", "nRollouts, maxTurns: numbers; seed: bigint");
-    const size_t words = sizeof(ge_rollout_stats) / 8;
-    void *out = nullptr, *st_data = nullptr;
-    napi_value buf, arr, st_buf, st_arr, res;
-    NAPI_OK(napi_create_arraybuffer(env, len[0] * sizeof(ge_rollout_stats), &out, &buf));
-    memset(out, 0, len[0] * sizeof(ge_rollout_stats));
-    NAPI_OK(napi_create_arraybuffer(env, len[0] * sizeof(int32_t), &st_data, &st_buf));
-    int32_t *status = static_cast<int32_t *>(st_data);
-    for (size_t k = 0; k < len[0]; k++) status[k] = 1;           // 1: untouched (no ge_status is positive)
-    const int st = ge_batch_rollout_actions(b, len[0], static_cast<const uint64_t *>(data[0]), static_cast<const uint64_t *>(data[1]),
-                                            static_cast<const uint32_t *>(data[2]), static_cast<const uint32_t *>(data[3]),
-                                            static_cast<const uint32_t *>(data[4]), static_cast<const uint32_t *>(data[5]), status,
-                                            n_rollouts, max_turns, seed, static_cast<ge_rollout_stats *>(out));
-    if (st != GE_OK) {
-        // a refused entry returns its status with every verdict written; a structural error or a failure of the call leaves
-        // the verdicts untouched
-        bool untouched = false;
-        for (size_t k = 0; k < len[0] && !untouched; k++) untouched = status[k] == 1;
-        if (untouched) return throw_status(env, st, "rolloutActions");
-    }
-    NAPI_OK(napi_create_typedarray(env, napi_biguint64_array, len[0] * words, buf, 0, &arr));
-    NAPI_OK(napi_create_typedarray(env, napi_int32_array, len[0], st_buf, 0, &st_arr));
-    NAPI_OK(napi_create_object(env, &res));
-    NAPI_OK(napi_set_named_property(env, res, "words", arr));
-    NAPI_OK(napi_set_named_property(env, res, "status", st_arr));
-    return res;
+bool is_nullish(napi_env env, napi_value v) {
+    napi_valuetype t;
+    return napi_typeof(env, v, &t) == napi_ok && (t == napi_null || t == napi_undefined);
 }
 
-// rolloutSeats(batch, rooms: BigUint64Array, keys: BigUint64Array, turns: Uint32Array, seats: Uint32Array, firstAction: Uint32Array
-// (rooms.length + 1), playerIds: Uint32Array, choices: Uint32Array, nRollouts, maxTurns, seed: bigint): as rolloutActions, every
-// replica re-dealt from seat seats[k]'s view after the actions (seat 0: the full view)
-napi_value RolloutSeats(napi_env env, napi_callback_info info) {
+// rollout(batch, rooms: BigUint64Array, keys: BigUint64Array, turns: Uint32Array, seats: Uint32Array | null, firstAction: Uint32Array
+// (rooms.length + 1) | null, playerIds: Uint32Array | null, choices: Uint32Array | null, nRollouts, maxTurns, seed: bigint):
+// { words: BigUint64Array of rooms.length x 77 (ge_rollout_stats k at [77 k, 77 k + 77)), status: Int32Array of rooms.length } -
+// index.js's rolloutRooms / rolloutActions / rolloutSeats: ge_batch_rollout_seats with seats, else ge_batch_rollout_actions with
+// actions, else ge_batch_rollout_rooms.  A refused entry's words are 0 and its status < 0
+napi_value Rollout(napi_env env, napi_callback_info info) {
     size_t argc = 11;
     napi_value argv[11];
     NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    const bool seats = argc > 4 && !is_nullish(env, argv[4]), acts = argc > 5 && !is_nullish(env, argv[5]);
+    const char *what = seats ? "rolloutSeats" : acts ? "rolloutActions" : "rolloutRooms";
     ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
-    if (!b || argc < 11) return throw_status(env, GE_ERR_ARG, "rolloutSeats");
-    napi_typedarray_type tt[7];
-    size_t len[7];
-    void *data[7];
+    if (!b || argc < 11) return throw_status(env, GE_ERR_ARG, what);
+    // rooms, keys, turns, then seats and firstAction, playerIds, choices where given
+    napi_typedarray_type tt[7] = {};
+    size_t len[7] = {0};
+    void *data[7] = {nullptr};
     for (int k = 0; k < 7; k++) {
+        if ((k == 3 && !seats) || (k > 3 && !acts)) continue;
         napi_value ab;
         size_t off;
         if (napi_get_typedarray_info(env, argv[1 + k], &tt[k], &len[k], &data[k], &ab, &off) != napi_ok)
-            return throw_status(env, GE_ERR_ARG, "rolloutSeats", "typed arrays expected");
+            return throw_status(env, GE_ERR_ARG, what, "typed arrays expected");
     }
-    if (tt[0] != napi_biguint64_array || tt[1] != napi_biguint64_array || tt[2] != napi_uint32_array || tt[3] != napi_uint32_array ||
-        tt[4] != napi_uint32_array || tt[5] != napi_uint32_array || tt[6] != napi_uint32_array || len[0] != len[1] || len[1] != len[2] ||
-        len[3] != len[0] || len[4] != len[0] + 1 || len[5] != len[6] || static_cast<const uint32_t *>(data[4])[len[0]] != len[5])
-        return throw_status(env, GE_ERR_ARG, "rolloutSeats",
-                            "BigUint64Array x 2, Uint32Array (turns, seats) of equal length; Uint32Array offsets (length + 1) ending at the "
-                            "length of the Uint32Array players and choices");
+    const bool shape = tt[0] == napi_biguint64_array && tt[1] == napi_biguint64_array && tt[2] == napi_uint32_array && len[0] == len[1] &&
+                       len[1] == len[2] && (!seats || (tt[3] == napi_uint32_array && len[3] == len[0])) &&
+                       (!acts || (tt[4] == napi_uint32_array && tt[5] == napi_uint32_array && tt[6] == napi_uint32_array &&
+                                  len[4] == len[0] + 1 && len[5] == len[6] && static_cast<const uint32_t *>(data[4])[len[0]] == len[5]));
+    if (!shape)
+        return throw_status(env, GE_ERR_ARG, what,
+                            !seats && !acts ? "BigUint64Array, BigUint64Array, Uint32Array of equal length"
+                            : seats ? "BigUint64Array x 2, Uint32Array (turns, seats) of equal length; Uint32Array offsets (length + 1) ending "
+                                      "at the length of the Uint32Array players and choices"
+                                    : "BigUint64Array x 2, Uint32Array (turns) of equal length; Uint32Array offsets (length + 1) ending at the "
+                                      "length of the Uint32Array players and choices");
     uint32_t n_rollouts = 0, max_turns = 0;
     uint64_t seed = 0;
     if (napi_get_value_uint32(env, argv[8], &n_rollouts) != napi_ok || napi_get_value_uint32(env, argv[9], &max_turns) != napi_ok ||
         !get_u64(env, argv[10], &seed))
-        return throw_status(env, GE_ERR_ARG, "rolloutSeats", "nRollouts, maxTurns: numbers; seed: bigint");
+        return throw_status(env, GE_ERR_ARG, what, "nRollouts, maxTurns: numbers; seed: bigint");
     const size_t words = sizeof(ge_rollout_stats) / 8;
     void *out = nullptr, *st_data = nullptr;
     napi_value buf, arr, st_buf, st_arr, res;
@@ -573,17 +533,20 @@ napi_value RolloutSeats(napi_env env, napi_callback_info info) {
     NAPI_OK(napi_create_arraybuffer(env, len[0] * sizeof(int32_t), &st_data, &st_buf));
     int32_t *status = static_cast<int32_t *>(st_data);
     for (size_t k = 0; k < len[0]; k++) status[k] = 1;           // 1: untouched (no ge_status is positive)
-    const int st = ge_batch_rollout_seats(b, len[0], static_cast<const uint64_t *>(data[0]), static_cast<const uint64_t *>(data[1]),
-                                          static_cast<const uint32_t *>(data[2]), static_cast<const uint32_t *>(data[3]),
-                                          static_cast<const uint32_t *>(data[4]), static_cast<const uint32_t *>(data[5]),
-                                          static_cast<const uint32_t *>(data[6]), status, n_rollouts, max_turns, seed,
-                                          static_cast<ge_rollout_stats *>(out));
+    const uint64_t *rooms = static_cast<const uint64_t *>(data[0]), *keys = static_cast<const uint64_t *>(data[1]);
+    const uint32_t *turns = static_cast<const uint32_t *>(data[2]), *sv = static_cast<const uint32_t *>(data[3]);
+    const uint32_t *first = static_cast<const uint32_t *>(data[4]), *pl = static_cast<const uint32_t *>(data[5]);
+    const uint32_t *ch = static_cast<const uint32_t *>(data[6]);
+    ge_rollout_stats *o = static_cast<ge_rollout_stats *>(out);
+    const int st = seats ? ge_batch_rollout_seats(b, len[0], rooms, keys, turns, sv, first, pl, ch, status, n_rollouts, max_turns, seed, o)
+                   : acts ? ge_batch_rollout_actions(b, len[0], rooms, keys, turns, first, pl, ch, status, n_rollouts, max_turns, seed, o)
+                          : ge_batch_rollout_rooms(b, len[0], rooms, keys, turns, n_rollouts, max_turns, seed, o);
     if (st != GE_OK) {
         // a refused entry returns its status with every verdict written; a structural error or a failure of the call leaves
-        // the verdicts untouched
+        // the verdicts untouched (ge_batch_rollout_rooms writes none)
         bool untouched = false;
         for (size_t k = 0; k < len[0] && !untouched; k++) untouched = status[k] == 1;
-        if (untouched) return throw_status(env, st, "rolloutSeats");
+        if (untouched) return throw_status(env, st, what);
     }
     NAPI_OK(napi_create_typedarray(env, napi_biguint64_array, len[0] * words, buf, 0, &arr));
     NAPI_OK(napi_create_typedarray(env, napi_int32_array, len[0], st_buf, 0, &st_arr));
@@ -591,42 +554,6 @@ napi_value RolloutSeats(napi_env env, napi_callback_info info) {
     NAPI_OK(napi_set_named_property(env, res, "words", arr));
     NAPI_OK(napi_set_named_property(env, res, "status", st_arr));
     return res;
-}
-
-// rolloutRooms(batch, rooms: BigUint64Array, keys: BigUint64Array, turns: Uint32Array, nRollouts, maxTurns, seed: bigint):
-// BigUint64Array of rooms.length x 77 words (ge_rollout_stats k at [77 k, 77 k + 77)) - playouts of each listed room
-napi_value RolloutRooms(napi_env env, napi_callback_info info) {
-    size_t argc = 7;
-    napi_value argv[7];
-    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
-    if (!b || argc < 7) return throw_status(env, GE_ERR_ARG, "rolloutRooms");
-    napi_typedarray_type tt[3];
-    size_t len[3];
-    void *data[3];
-    for (int k = 0; k < 3; k++) {
-        napi_value ab;
-        size_t off;
-        if (napi_get_typedarray_info(env, argv[1 + k], &tt[k], &len[k], &data[k], &ab, &off) != napi_ok)
-            return throw_status(env, GE_ERR_ARG, "rolloutRooms", "typed arrays expected");
-    }
-    if (tt[0] != napi_biguint64_array || tt[1] != napi_biguint64_array || tt[2] != napi_uint32_array || len[0] != len[1] || len[1] != len[2])
-        return throw_status(env, GE_ERR_ARG, "rolloutRooms", "BigUint64Array, BigUint64Array, Uint32Array of equal length");
-    uint32_t n_rollouts = 0, max_turns = 0;
-    uint64_t seed = 0;
-    if (napi_get_value_uint32(env, argv[4], &n_rollouts) != napi_ok || napi_get_value_uint32(env, argv[5], &max_turns) != napi_ok ||
-        !get_u64(env, argv[6], &seed))
-        return throw_status(env, GE_ERR_ARG, "rolloutRooms", "nRollouts, maxTurns: numbers; seed: bigint");
-    const size_t words = sizeof(ge_rollout_stats) / 8;
-    void *out = nullptr;
-    napi_value buf, arr;
-    NAPI_OK(napi_create_arraybuffer(env, len[0] * sizeof(ge_rollout_stats), &out, &buf));
-    const int st = ge_batch_rollout_rooms(b, len[0], static_cast<const uint64_t *>(data[0]), static_cast<const uint64_t *>(data[1]),
-                                          static_cast<const uint32_t *>(data[2]), n_rollouts, max_turns, seed,
-                                          static_cast<ge_rollout_stats *>(out));
-    if (st != GE_OK) return throw_status(env, st, "rolloutRooms");
-    NAPI_OK(napi_create_typedarray(env, napi_biguint64_array, len[0] * words, buf, 0, &arr));
-    return arr;
 }
 
 // readRoomsAt(batch, rooms: BigUint64Array): ArrayBuffer of rooms.length ge_room_view, view k = room rooms[k]
@@ -900,9 +827,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"readEvents", nullptr, ReadEvents, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"stepRooms", nullptr, StepRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"readRoomsAt", nullptr, ReadRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"rolloutRooms", nullptr, RolloutRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"rolloutActions", nullptr, RolloutActions, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"rolloutSeats", nullptr, RolloutSeats, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"rollout", nullptr, Rollout, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"writeRoomsAt", nullptr, WriteRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"summary", nullptr, Summary, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"reset", nullptr, Reset, nullptr, nullptr, nullptr, napi_default, nullptr},

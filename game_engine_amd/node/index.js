@@ -585,8 +585,7 @@ class RoomBatch {
    * every seat played by the policy and a finished game left finished.  Returns a BigUint64Array of rooms.length x 77 words
    * (ge_rollout_stats: the 41 summary words, then seat_alive, seat_wins, seat_score x 12).  The batch is only read.  Synchronous. */
   rolloutRooms(rooms, keys, turns, nRollouts, maxTurns = 1024, seed) {
-    return addon.rolloutRooms(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r)), BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))),
-                              Uint32Array.from(turns), nRollouts, maxTurns, seed === undefined ? this.seed : BigInt(seed));
+    return this._rollout(rooms, keys, turns, null, null, nRollouts, maxTurns, seed).words;
   }
   /** Playouts after given actions (twin of the Python RoomBatch.rollout_actions): entry k is rolloutRooms's entry (rooms[k], keys[k],
    * turns[k]) with actions[k], an array of [playerId, choice] pairs, logged in every replica, in that order, before its first turn.
@@ -594,13 +593,7 @@ class RoomBatch {
    * status[k] = 0 and entry k's ge_rollout_stats, or the refused action's status (< 0) and 77 zero words.  Throws only for a
    * structural error (rolloutRooms's caps, more than 12 actions in one entry).  The batch is only read.  Synchronous. */
   rolloutActions(rooms, keys, turns, actions, nRollouts, maxTurns = 1024, seed) {
-    const acts = Array.from(actions, (a) => Array.from(a));
-    const first = new Uint32Array(acts.length + 1);
-    acts.forEach((a, k) => { first[k + 1] = first[k] + a.length; });
-    const flat = acts.flat();
-    return addon.rolloutActions(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r)), BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))),
-                                Uint32Array.from(turns), first, Uint32Array.from(flat, (pc) => pc[0]), Uint32Array.from(flat, (pc) => pc[1]),
-                                nRollouts, maxTurns, seed === undefined ? this.seed : BigInt(seed));
+    return this._rollout(rooms, keys, turns, null, Array.from(actions), nRollouts, maxTurns, seed);
   }
   /** Playouts from a seat's view (twin of the Python RoomBatch.rollout_seats, POLICY.md §3c): rolloutActions's entry k with every
    * replica's copy re-dealt, after the actions, over what seat seats[k] (1-based) cannot see; seats[k] = 0: the full view,
@@ -608,13 +601,22 @@ class RoomBatch {
    * rolloutActions.  Throws only for a structural error (rolloutActions's, or a seat above its room's player count).  The batch
    * is only read.  Synchronous. */
   rolloutSeats(rooms, keys, turns, seats, actions, nRollouts, maxTurns = 1024, seed) {
-    const acts = actions == null ? Array.from(rooms, () => []) : Array.from(actions, (a) => Array.from(a));
-    const first = new Uint32Array(acts.length + 1);
-    acts.forEach((a, k) => { first[k + 1] = first[k] + a.length; });
-    const flat = acts.flat();
-    return addon.rolloutSeats(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r)), BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))),
-                              Uint32Array.from(turns), Uint32Array.from(seats), first, Uint32Array.from(flat, (pc) => pc[0]),
-                              Uint32Array.from(flat, (pc) => pc[1]), nRollouts, maxTurns, seed === undefined ? this.seed : BigInt(seed));
+    return this._rollout(rooms, keys, turns, Uint32Array.from(seats), actions == null ? null : Array.from(actions), nRollouts, maxTurns, seed);
+  }
+  /** The three rollout* methods: one native call (ge_batch_rollout_seats with seats, else ge_batch_rollout_actions with actions -
+   * [playerId, choice] pairs per entry, flattened to CSR - else ge_batch_rollout_rooms).  Returns { words, status }. */
+  _rollout(rooms, keys, turns, seats, actions, nRollouts, maxTurns, seed) {
+    let first = null, players = null, choices = null;
+    if (actions) {
+      const acts = actions.map((a) => Array.from(a));
+      first = new Uint32Array(acts.length + 1);
+      acts.forEach((a, k) => { first[k + 1] = first[k] + a.length; });
+      const flat = acts.flat();
+      players = Uint32Array.from(flat, (pc) => pc[0]);
+      choices = Uint32Array.from(flat, (pc) => pc[1]);
+    }
+    return addon.rollout(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r)), BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))),
+                         Uint32Array.from(turns), seats, first, players, choices, nRollouts, maxTurns, seed === undefined ? this.seed : BigInt(seed));
   }
   /** The listed rooms' states, out[k] = room rooms[k] (any order, repeats allowed). */
   readRoomsAt(rooms) {

@@ -10,8 +10,8 @@
  * stepRooms and one readRoomsAt.  The chunks are shared, so every call of the service runs strictly one after the other.
  */
 const { GameTable, RoomBatch, RoomLog, decodeRoom, turnToolCalls, uiToolCalls } = require('./index.js');
-const { roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, adviseCandidates, adviseSeat,
-        adviseEntries, adviseOutput, seatForecastOutput, checkForecastSeat, checkView } = require('./room_service.js');
+const { roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, adviseCandidates, adviseSeat, runRollouts, adviseOutput,
+        seatForecastOutput, checkForecastSeat, checkView } = require('./room_service.js');
 const M = require('./messages.js');
 
 const GE_ERR_ARG = -1;
@@ -203,38 +203,10 @@ class RoomPoolService {
       const pids = playerIds || [];
       const seats = rooms.map((room, j) => adviseSeat(threadIds[j], room.humanSeats, pids[j]));
       const cands = rooms.map((room) => adviseCandidates(room.table, room.state));
-      const byChunk = new Map();
-      rooms.forEach((room, j) => {
-        if (!byChunk.has(room.chunk)) byChunk.set(room.chunk, []);
-        byChunk.get(room.chunk).push(j);
-      });
-      const out = new Array(rooms.length);
-      const seed = forecastSeed(this.seed);
-      const perCall = Math.max(1, Math.floor(2 ** 26 / nRollouts));     // the library's cap on entries x rollouts of one call
-      for (const [chunk, js] of byChunk) {
-        const parts = [[]];
-        let nEnt = 0;
-        for (const j of js) {                                             // one call per chunk, split only where the cap needs it
-          if (parts[parts.length - 1].length && nEnt + cands[j].length + 1 > perCall) { parts.push([]); nEnt = 0; }
-          parts[parts.length - 1].push(j);
-          nEnt += cands[j].length + 1;
-        }
-        for (const part of parts) {
-          const ent = [[], [], [], []], at = [], eseats = [];
-          for (const j of part) {
-            at.push(ent[0].length);
-            adviseEntries(rooms[j].slot, rooms[j].key, rooms[j].turn, seats[j], cands[j]).forEach((src, i) => ent[i].push(...src));
-            for (let i = 0; i <= cands[j].length; i++) eseats.push(seats[j]);
-          }
-          const res = seatView ? chunk.rolloutSeats(ent[0], ent[1], ent[2], eseats, ent[3], nRollouts, maxTurns, seed)
-                               : chunk.rolloutActions(ent[0], ent[1], ent[2], ent[3], nRollouts, maxTurns, seed);
-          part.forEach((j, k) => {
-            out[j] = adviseOutput(rooms[j].table, rooms[j].names, threadIds[j], rooms[j].turn, seats[j], rooms[j].state, cands[j], nRollouts,
-                                  maxTurns, res, at[k], seatView);
-          });
-        }
-      }
-      return out;
+      const res = runRollouts(rooms.map((room, j) => ({ batch: room.chunk, slot: room.slot, key: room.key, turn: room.turn, seat: seats[j], cands: cands[j] })),
+                              seatView, nRollouts, maxTurns, this.seed);
+      return rooms.map((room, j) => adviseOutput(room.table, room.names, threadIds[j], room.turn, seats[j], room.state, cands[j], nRollouts, maxTurns,
+                                                 res[j], 0, seatView));
     });
   }
   /** Forecasts of many threads, in order: one rolloutRooms per chunk touched; with seats (seats[j] 1 .. n: thread j from that
@@ -245,26 +217,9 @@ class RoomPoolService {
       const rooms = threadIds.map((t) => this._room(t));
       const sv = seats || [];
       rooms.forEach((room, j) => checkForecastSeat(threadIds[j], room.names.length, sv[j]));
-      const byChunk = new Map();
-      rooms.forEach((room, j) => {
-        if (!byChunk.has(room.chunk)) byChunk.set(room.chunk, []);
-        byChunk.get(room.chunk).push(j);
-      });
-      const perCall = Math.max(1, Math.floor(2 ** 26 / nRollouts));     // the library's cap on entries x rollouts of one call
-      const out = new Array(rooms.length);
-      const seed = forecastSeed(this.seed);
-      for (const [chunk, js] of byChunk) {
-        for (let lo = 0; lo < js.length; lo += perCall) {
-          const part = js.slice(lo, lo + perCall);
-          const ent = [part.map((j) => rooms[j].slot), part.map((j) => forecastKey(rooms[j].key)), part.map((j) => rooms[j].turn)];
-          const w = seats ? chunk.rolloutSeats(...ent, part.map((j) => sv[j] || 0), null, nRollouts, maxTurns, seed).words
-                          : chunk.rolloutRooms(...ent, nRollouts, maxTurns, seed);
-          part.forEach((j, k) => {
-            out[j] = seatForecastOutput(rooms[j].table, rooms[j].names, threadIds[j], rooms[j].turn, nRollouts, maxTurns, sv[j], w, 77 * k);
-          });
-        }
-      }
-      return out;
+      const res = runRollouts(rooms.map((room, j) => ({ batch: room.chunk, slot: room.slot, key: room.key, turn: room.turn, seat: sv[j] })),
+                              !!seats, nRollouts, maxTurns, this.seed);
+      return rooms.map((room, j) => seatForecastOutput(room.table, room.names, threadIds[j], room.turn, nRollouts, maxTurns, sv[j], res[j].words));
     });
   }
   /** One turn of each room (distinct threads): one stepRooms and one readRoomsAt per chunk touched. */

@@ -120,12 +120,54 @@ function adviseSeat(threadId, humanSeats, playerId) {
   if (!humanSeats.length) throw new RangeError(`thread ${threadId} has no human seat: name the player to advise`);
   return Math.min(...humanSeats);
 }
-/** rolloutActions entries of one advise: one per candidate, then the policy's (no action), all under the forecast key. */
-function adviseEntries(slot, threadKey, turn, seat, cands) {
-  const k = cands.length + 1;
-  return [new Array(k).fill(slot), new Array(k).fill(forecastKey(threadKey)), new Array(k).fill(turn), cands.map((c) => [[seat, c]]).concat([[]])];
+/** The playouts of a forecast or advise call (twin of room_service.py run_rollouts): reqs [{ batch, slot, key, turn, seat, cands }]
+ * - seat: the advised seat, or the seat a forecast is seen from (undefined / null: the full view); cands: advise's candidates
+ * (undefined: a forecast).  A forecast is one entry, an advise one per candidate then the policy's (no action), all under the
+ * thread's forecast key and the forecast seed.  One call per batch, in the order the batches first appear, split only where the
+ * library's cap on entries x rollouts needs it: rolloutRooms for a forecast, rolloutActions for an advise, rolloutSeats in the
+ * seat view (seat 0 for a thread without a seat: its full view).  Returns per request { words, status } (status null after
+ * rolloutRooms), views into the call's results. */
+function runRollouts(reqs, seatView, nRollouts, maxTurns, seed) {
+  const byBatch = new Map();
+  reqs.forEach((r, j) => {
+    if (!byBatch.has(r.batch)) byBatch.set(r.batch, []);
+    byBatch.get(r.batch).push(j);
+  });
+  const size = reqs.map((r) => (r.cands ? r.cands.length + 1 : 1));
+  const perCall = Math.max(1, Math.floor(2 ** 26 / nRollouts));
+  const parts = [];
+  for (const js of byBatch.values()) {
+    let nEnt = 0;
+    parts.push([]);
+    for (const j of js) {
+      if (parts[parts.length - 1].length && nEnt + size[j] > perCall) { parts.push([]); nEnt = 0; }
+      parts[parts.length - 1].push(j);
+      nEnt += size[j];
+    }
+  }
+  const out = new Array(reqs.length);
+  const fseed = forecastSeed(seed);
+  for (const part of parts) {
+    const rooms = [], keys = [], turns = [], seats = [];
+    const acts = part.some((j) => reqs[j].cands) ? [] : null;
+    for (const j of part) {
+      const r = reqs[j];
+      for (let i = 0; i < size[j]; i++) { rooms.push(r.slot); keys.push(forecastKey(r.key)); turns.push(r.turn); seats.push(r.seat || 0); }
+      if (acts) acts.push(...r.cands.map((c) => [[r.seat, c]]), []);
+    }
+    const batch = reqs[part[0]].batch;
+    const res = seatView ? batch.rolloutSeats(rooms, keys, turns, seats, acts, nRollouts, maxTurns, fseed)
+      : acts ? batch.rolloutActions(rooms, keys, turns, acts, nRollouts, maxTurns, fseed)
+        : { words: batch.rolloutRooms(rooms, keys, turns, nRollouts, maxTurns, fseed), status: null };
+    let at = 0;
+    for (const j of part) {
+      out[j] = { words: res.words.subarray(77 * at, 77 * (at + size[j])), status: res.status && res.status.subarray(at, at + size[j]) };
+      at += size[j];
+    }
+  }
+  return out;
 }
-/** advise's JSON from the words and verdicts of adviseEntries at entry offset `at`: the bytes the Python hosts print. */
+/** advise's JSON from the words and verdicts of an advise's entries (runRollouts) at entry offset `at`: the bytes the Python hosts print. */
 function adviseOutput(table, names, threadId, turn, seat, st, cands, nRollouts, maxTurns, res, at = 0, seatView = false) {
   const options = [];
   cands.forEach((c, j) => {
@@ -212,10 +254,9 @@ class RoomService {
     if (!room) return Promise.reject(new Error(`unknown thread ${threadId}`));
     checkForecastSeat(threadId, room.names.length, seat);
     return this._serial(room, () => {
-      const w = seat === undefined || seat === null
-        ? room.batch.rolloutRooms([0], [forecastKey(room.key)], [room.turn], nRollouts, maxTurns, forecastSeed(this.seed))
-        : room.batch.rolloutSeats([0], [forecastKey(room.key)], [room.turn], [seat], null, nRollouts, maxTurns, forecastSeed(this.seed)).words;
-      return seatForecastOutput(room.table, room.names, threadId, room.turn, nRollouts, maxTurns, seat, w);
+      const [res] = runRollouts([{ batch: room.batch, slot: 0, key: room.key, turn: room.turn, seat }], seat !== undefined && seat !== null,
+                                nRollouts, maxTurns, this.seed);
+      return seatForecastOutput(room.table, room.names, threadId, room.turn, nRollouts, maxTurns, seat, res.words);
     });
   }
   /** What each choice the seat can make now leads to (twin of the Python RoomService.advise): for every candidate the forecast given
@@ -232,10 +273,8 @@ class RoomService {
     const seat = adviseSeat(threadId, room.humanSeats, playerId);
     return this._serial(room, () => {
       const cands = adviseCandidates(room.table, room.state);
-      const [rooms, keys, turns, acts] = adviseEntries(0, room.key, room.turn, seat, cands);
-      const res = seatView
-        ? room.batch.rolloutSeats(rooms, keys, turns, new Array(rooms.length).fill(seat), acts, nRollouts, maxTurns, forecastSeed(this.seed))
-        : room.batch.rolloutActions(rooms, keys, turns, acts, nRollouts, maxTurns, forecastSeed(this.seed));
+      const [res] = runRollouts([{ batch: room.batch, slot: 0, key: room.key, turn: room.turn, seat, cands }], seatView, nRollouts, maxTurns,
+                                this.seed);
       return adviseOutput(room.table, room.names, threadId, room.turn, seat, room.state, cands, nRollouts, maxTurns, res, 0, seatView);
     });
   }
@@ -337,4 +376,4 @@ class RoomService {
 }
 
 module.exports = { RoomService, roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput,
-                   adviseCandidates, adviseSeat, adviseEntries, adviseOutput, seatForecastOutput, checkForecastSeat, checkView };
+                   adviseCandidates, adviseSeat, runRollouts, adviseOutput, seatForecastOutput, checkForecastSeat, checkView };

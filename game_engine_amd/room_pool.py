@@ -17,9 +17,8 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import messages as M
-from .room_service import (adopted_output, advise_candidates, advise_entries, advise_output, advise_seat, check_forecast_args,
-                           check_forecast_seat, check_view, forecast_key, forecast_seed, prepare_adoption, room_index_of,
-                           seat_forecast_output)
+from .room_service import (RolloutRequest, adopted_output, advise_candidates, advise_output, advise_seat, check_forecast_args,
+                           check_forecast_seat, check_view, prepare_adoption, room_index_of, run_rollouts, seat_forecast_output)
 from .stepper import GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, load_dsl_by_gamename, slot_values
 from .toolcalls import WW_IS_ALIVE, RoomLog, turn_tool_calls
 from .ui_script import ui_tool_calls
@@ -268,23 +267,9 @@ class RoomPoolService:
             raise ValueError("forecasts: thread_ids and seats differ in length")
         for tid, room, st in zip(thread_ids, rooms, sv):
             check_forecast_seat(tid, len(room["names"]), st)
-        by_chunk: Dict[int, List[int]] = {}
-        for j, room in enumerate(rooms):
-            by_chunk.setdefault(id(room["chunk"]), []).append(j)
-        words: List[Any] = [None] * len(rooms)
-        per_call = max(1, (1 << 26) // int(n_rollouts))          # the library's cap on entries x rollouts of one call
-        for js in by_chunk.values():
-            chunk = rooms[js[0]]["chunk"]
-            for lo in range(0, len(js), per_call):
-                part = js[lo:lo + per_call]
-                ent = ([rooms[j]["slot"] for j in part], [forecast_key(rooms[j]["key"]) for j in part], [rooms[j]["turn"] for j in part])
-                if seats is None:
-                    w = chunk.rollout_rooms(*ent, n_rollouts, max_turns, seed=forecast_seed(self.seed))
-                else:
-                    w = chunk.rollout_seats(*ent, [sv[j] or 0 for j in part], None, n_rollouts, max_turns, seed=forecast_seed(self.seed))[0]
-                for k, j in enumerate(part):
-                    words[j] = w[k]
-        return [seat_forecast_output(room["table"], room["names"], tid, room["turn"], n_rollouts, max_turns, sv[j], words[j])
+        res = run_rollouts([RolloutRequest(room["chunk"], room["slot"], room["key"], room["turn"], st) for room, st in zip(rooms, sv)],
+                           seats is not None, n_rollouts, max_turns, self.seed)
+        return [seat_forecast_output(room["table"], room["names"], tid, room["turn"], n_rollouts, max_turns, sv[j], res[j][0][0])
                 for j, (tid, room) in enumerate(zip(thread_ids, rooms))]
 
     def advise(self, thread_id: str, player_id: Optional[int] = None, n_rollouts: int = 4096, max_turns: int = 1024,
@@ -305,38 +290,8 @@ class RoomPoolService:
             raise ValueError("advises: thread_ids and player_ids differ in length")
         seats = [advise_seat(tid, room["human_seats"], pid) for tid, room, pid in zip(thread_ids, rooms, pids)]
         cands = [advise_candidates(room["table"], room["view"]) for room in rooms]
-        by_chunk: Dict[int, List[int]] = {}
-        for j, room in enumerate(rooms):
-            by_chunk.setdefault(id(room["chunk"]), []).append(j)
-        res: List[Any] = [None] * len(rooms)
-        per_call = max(1, (1 << 26) // int(n_rollouts))          # the library's cap on entries x rollouts of one call
-        for js in by_chunk.values():
-            chunk = rooms[js[0]]["chunk"]
-            parts: List[List[int]] = [[]]
-            n_ent = 0
-            for j in js:                                          # one call per chunk, split only where the cap needs it
-                if parts[-1] and n_ent + len(cands[j]) + 1 > per_call:
-                    parts.append([])
-                    n_ent = 0
-                parts[-1].append(j)
-                n_ent += len(cands[j]) + 1
-            for part in parts:
-                ent: Tuple[list, list, list, list] = ([], [], [], [])
-                eseats: List[int] = []
-                for j in part:
-                    for dst, src in zip(ent, advise_entries(rooms[j]["slot"], rooms[j]["key"], rooms[j]["turn"], seats[j], cands[j])):
-                        dst.extend(src)
-                    eseats += [seats[j]] * (len(cands[j]) + 1)
-                if seat_view:
-                    words, status = chunk.rollout_seats(ent[0], ent[1], ent[2], eseats, ent[3], n_rollouts, max_turns,
-                                                        seed=forecast_seed(self.seed))
-                else:
-                    words, status = chunk.rollout_actions(*ent, n_rollouts, max_turns, seed=forecast_seed(self.seed))
-                at = 0
-                for j in part:
-                    k = len(cands[j]) + 1
-                    res[j] = (words[at:at + k], status[at:at + k])
-                    at += k
+        res = run_rollouts([RolloutRequest(room["chunk"], room["slot"], room["key"], room["turn"], seat, c)
+                            for room, seat, c in zip(rooms, seats, cands)], seat_view, n_rollouts, max_turns, self.seed)
         return [advise_output(room["table"], room["names"], tid, room["turn"], seats[j], room["view"], cands[j], n_rollouts, max_turns,
                               *res[j], seat_view) for j, (tid, room) in enumerate(zip(thread_ids, rooms))]
 

@@ -12,7 +12,7 @@ are folded from those calls exactly as the reference's `_execute_*` functions wo
 from __future__ import annotations
 
 import re
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 from . import messages as M
 from .stepper import (GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, agent_state_to_view, load_dsl_by_gamename, rollout_to_dict,
@@ -156,16 +156,72 @@ def advise_seat(thread_id: str, human_seats: List[int], player_id: Optional[int]
     return min(human_seats)
 
 
-def advise_entries(slot: int, thread_key: int, turn: int, seat: int, cands: List[int]) -> Tuple[list, list, list, list]:
-    """rollout_actions entries of one advise: one per candidate, then the policy's (no action), all under the forecast key."""
-    k = len(cands) + 1
-    return ([slot] * k, [forecast_key(thread_key)] * k, [turn] * k, [[(seat, c)] for c in cands] + [[]])
+class RolloutRequest(NamedTuple):
+    """One thread of a forecast or advise call: its batch, slot, thread key and turn; seat: the advised seat, or the seat a
+    forecast is seen from (None: the full view); cands: advise's candidates (None: a forecast)."""
+    batch: Any
+    slot: int
+    key: int
+    turn: int
+    seat: Optional[int] = None
+    cands: Optional[List[int]] = None
+
+
+def run_rollouts(reqs: Sequence[RolloutRequest], seat_view: bool, n_rollouts: int, max_turns: int, seed: int) -> List[Tuple[Any, Any]]:
+    """The playouts of a forecast or advise call, as (words, status) per request (status None after rollout_rooms).  A forecast
+    is one entry, an advise one per candidate then the policy's (no action), all under the thread's forecast key and the forecast
+    seed.  One call per batch, in the order the batches first appear, split only where the library's cap on entries x rollouts
+    needs it: rollout_rooms for a forecast, rollout_actions for an advise, rollout_seats in the seat view (seat 0 for a thread
+    without a seat: its full view)."""
+    per_call = max(1, (1 << 26) // int(n_rollouts))
+    calls: Dict[int, List[List[int]]] = {}                 # per batch, in first-appearance order: its calls' requests
+    n_ent: Dict[int, int] = {}                             # entries in the batch's last call
+    for j, r in enumerate(reqs):
+        k = 1 if r.cands is None else len(r.cands) + 1
+        b = id(r.batch)
+        if b not in calls:
+            calls[b], n_ent[b] = [[]], 0
+        elif n_ent[b] + k > per_call:
+            calls[b].append([])
+            n_ent[b] = 0
+        calls[b][-1].append(j)
+        n_ent[b] += k
+    seed = forecast_seed(seed)
+    out: List[Tuple[Any, Any]] = [(None, None)] * len(reqs)
+    for part in (part for parts in calls.values() for part in parts):
+        rooms: list = []
+        keys: list = []
+        turns: list = []
+        seats: list = []
+        acts: list = []
+        for j in part:
+            r = reqs[j]
+            k = 1 if r.cands is None else len(r.cands) + 1
+            rooms += [r.slot] * k
+            keys += [forecast_key(r.key)] * k
+            turns += [r.turn] * k
+            seats += [r.seat or 0] * k
+            if r.cands is not None:
+                acts += [[(r.seat, c)] for c in r.cands] + [[]]
+        batch = reqs[part[0]].batch
+        if seat_view:
+            words, status = batch.rollout_seats(rooms, keys, turns, seats, acts or None, n_rollouts, max_turns, seed=seed)
+        elif acts:
+            words, status = batch.rollout_actions(rooms, keys, turns, acts, n_rollouts, max_turns, seed=seed)
+        else:
+            words, status = batch.rollout_rooms(rooms, keys, turns, n_rollouts, max_turns, seed=seed), None
+        at = 0
+        for j in part:
+            k = 1 if reqs[j].cands is None else len(reqs[j].cands) + 1
+            out[j] = (words[at:at + k], None if status is None else status[at:at + k])
+            at += k
+    return out
 
 
 def advise_output(table: GameTable, names: List[str], thread_id: str, turn: int, seat: int, view, cands: List[int], n_rollouts: int,
                   max_turns: int, words, status, seat_view: bool = False) -> Dict[str, Any]:
-    """advise's JSON from the words and verdicts of advise_entries (the same bytes as room_service.js / room_pool.js); from the
-    seat's view it gains "view": "seat"."""
+    """advise's JSON from the words and verdicts of an advise's entries (run_rollouts; the same bytes as room_service.js /
+    room_pool.js); from the seat's view it gains "view": "seat"."""
     options = []
     for j, c in enumerate(cands):
         if int(status[j]) != 0:
@@ -321,14 +377,10 @@ class RoomService:
         check_forecast_args(n_rollouts, max_turns)
         room = self._rooms[thread_id]
         check_forecast_seat(thread_id, len(room["names"]), seat)
-        batch = room["batch"]
-        turn = batch.turn
-        if seat is None:
-            w = batch.rollout_rooms([0], [forecast_key(room["key"])], [turn], n_rollouts, max_turns, seed=forecast_seed(self.seed))[0]
-        else:
-            w = batch.rollout_seats([0], [forecast_key(room["key"])], [turn], [seat], None, n_rollouts, max_turns,
-                                    seed=forecast_seed(self.seed))[0][0]
-        return seat_forecast_output(room["table"], room["names"], thread_id, turn, n_rollouts, max_turns, seat, w)
+        turn = room["batch"].turn
+        (words, _), = run_rollouts([RolloutRequest(room["batch"], 0, room["key"], turn, seat)], seat is not None, n_rollouts, max_turns,
+                                   self.seed)
+        return seat_forecast_output(room["table"], room["names"], thread_id, turn, n_rollouts, max_turns, seat, words[0])
 
     def advise(self, thread_id: str, player_id: Optional[int] = None, n_rollouts: int = 4096, max_turns: int = 1024,
                view: str = "full") -> Dict[str, Any]:
@@ -345,15 +397,10 @@ class RoomService:
         seat_view = check_view(view)
         room = self._rooms[thread_id]
         seat = advise_seat(thread_id, room["human_seats"], player_id)
-        batch, rv = room["batch"], room["view"]
-        turn = batch.turn
+        rv, turn = room["view"], room["batch"].turn
         cands = advise_candidates(room["table"], rv)
-        ent = advise_entries(0, room["key"], turn, seat, cands)
-        if seat_view:
-            words, status = batch.rollout_seats(ent[0], ent[1], ent[2], [seat] * len(ent[0]), ent[3], n_rollouts, max_turns,
-                                                seed=forecast_seed(self.seed))
-        else:
-            words, status = batch.rollout_actions(*ent, n_rollouts, max_turns, seed=forecast_seed(self.seed))
+        (words, status), = run_rollouts([RolloutRequest(room["batch"], 0, room["key"], turn, seat, cands)], seat_view, n_rollouts,
+                                        max_turns, self.seed)
         return advise_output(room["table"], room["names"], thread_id, turn, seat, rv, cands, n_rollouts, max_turns, words, status,
                              seat_view)
 

@@ -319,15 +319,7 @@ class RoomBatch:
         one row): row k's first 41 words are what summary_words() of a fresh batch of n_rollouts copies of the room, keyed from
         keys[k], would give after set_turn(turns[k]) and step(max_turns).  The batch is only read.  Caps (GeError otherwise,
         nothing run): 1 <= n_rollouts <= 2^20, n * n_rollouts <= 2^26, max_turns <= 4096, turns[k] + max_turns < 2^32."""
-        rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
-        keys = np.ascontiguousarray(keys, dtype=np.uint64)
-        turns = np.ascontiguousarray(turns, dtype=np.uint32)
-        if not (len(rooms) == len(keys) == len(turns)):
-            raise GeError(-1, "rollout_rooms: arrays differ in length")
-        out = np.zeros((len(rooms), _lib.ROLLOUT_WORDS), dtype=np.uint64)
-        _check(self._lib.ge_batch_rollout_rooms(self._h, len(rooms), rooms.ctypes.data, keys.ctypes.data, turns.ctypes.data, n_rollouts,
-                                                max_turns, self._seed if seed is None else seed, out.ctypes.data), "ge_batch_rollout_rooms")
-        return out
+        return self._rollout("rollout_rooms", rooms, keys, turns, None, None, n_rollouts, max_turns, seed)[0]
 
     def rollout_actions(self, rooms, keys, turns, actions, n_rollouts: int, max_turns: int = 1024,
                         seed: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
@@ -338,27 +330,7 @@ class RoomBatch:
         the room after those actions, or status[k] = the refused action's status and words[k] = 0.  An entry without actions is
         rollout_rooms's entry word for word.  The batch is only read.  GeError only for a structural error (rollout_rooms's caps,
         more than 12 actions in one entry), before anything runs."""
-        rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
-        keys = np.ascontiguousarray(keys, dtype=np.uint64)
-        turns = np.ascontiguousarray(turns, dtype=np.uint32)
-        actions = [list(a) for a in actions]
-        if not (len(rooms) == len(keys) == len(turns) == len(actions)):
-            raise GeError(-1, "rollout_actions: arrays differ in length")
-        first = np.zeros(len(actions) + 1, dtype=np.uint32)
-        first[1:] = np.cumsum([len(a) for a in actions])
-        flat = [pc for a in actions for pc in a]
-        players = np.ascontiguousarray([int(p) for p, _ in flat], dtype=np.uint32)
-        choices = np.ascontiguousarray([int(c) for _, c in flat], dtype=np.uint32)
-        out = np.zeros((len(rooms), _lib.ROLLOUT_WORDS), dtype=np.uint64)
-        status = np.full(len(rooms), 1, dtype=np.int32)          # 1: untouched (no ge_status is positive)
-        st = self._lib.ge_batch_rollout_actions(self._h, len(rooms), rooms.ctypes.data, keys.ctypes.data, turns.ctypes.data,
-                                                first.ctypes.data, players.ctypes.data, choices.ctypes.data, status.ctypes.data,
-                                                n_rollouts, max_turns, self._seed if seed is None else seed, out.ctypes.data)
-        # a refused entry returns its status with every entry's verdict written; a structural error or a failure of the call
-        # leaves the verdicts untouched
-        if st != 0 and (status == 1).any():
-            _check(st, "ge_batch_rollout_actions")
-        return out, status
+        return self._rollout("rollout_actions", rooms, keys, turns, None, actions, n_rollouts, max_turns, seed)
 
     def rollout_seats(self, rooms, keys, turns, seats, actions=None, n_rollouts: int = 4096, max_turns: int = 1024,
                       seed: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
@@ -368,31 +340,40 @@ class RoomBatch:
         full view, rollout_actions's entry word for word.  actions None: no actions in any entry.  Returns (words (n, 77)
         uint64, status (n,) int32) as rollout_actions.  The batch is only read.  GeError only for a structural error
         (rollout_actions's, or a seat above its room's player count), before anything runs."""
+        return self._rollout("rollout_seats", rooms, keys, turns, seats, actions, n_rollouts, max_turns, seed)
+
+    def _rollout(self, method: str, rooms, keys, turns, seats, actions, n_rollouts: int, max_turns: int,
+                 seed: Optional[int]) -> Tuple[np.ndarray, np.ndarray]:
+        """The three rollout_* methods: one call of ge_batch_<method> (seats and actions are read where the method has them;
+        actions None: every entry's slice empty, passed as NULL).  Returns (words, status); GeError naming the method when
+        the lengths differ, or naming the symbol when it fails without a verdict written."""
         rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
-        keys = np.ascontiguousarray(keys, dtype=np.uint64)
-        turns = np.ascontiguousarray(turns, dtype=np.uint32)
-        seats = np.ascontiguousarray(seats, dtype=np.uint32)
-        if not (len(rooms) == len(keys) == len(turns) == len(seats)):
-            raise GeError(-1, "rollout_seats: arrays differ in length")
-        out = np.zeros((len(rooms), _lib.ROLLOUT_WORDS), dtype=np.uint64)
-        status = np.full(len(rooms), 1, dtype=np.int32)          # 1: untouched (no ge_status is positive)
-        first = players = choices = None
-        if actions is not None:
+        args = [rooms, np.ascontiguousarray(keys, dtype=np.uint64), np.ascontiguousarray(turns, dtype=np.uint32)]
+        if method == "rollout_seats":
+            args.append(np.ascontiguousarray(seats, dtype=np.uint32))
+        if method == "rollout_actions" or actions is not None:
             actions = [list(a) for a in actions]
-            if len(actions) != len(rooms):
-                raise GeError(-1, "rollout_seats: arrays differ in length")
-            first = np.zeros(len(actions) + 1, dtype=np.uint32)
-            first[1:] = np.cumsum([len(a) for a in actions])
-            flat = [pc for a in actions for pc in a]
-            players = np.ascontiguousarray([int(p) for p, _ in flat], dtype=np.uint32)
-            choices = np.ascontiguousarray([int(c) for _, c in flat], dtype=np.uint32)
-        st = self._lib.ge_batch_rollout_seats(self._h, len(rooms), rooms.ctypes.data, keys.ctypes.data, turns.ctypes.data,
-                                              seats.ctypes.data, None if first is None else first.ctypes.data,
-                                              None if players is None else players.ctypes.data,
-                                              None if choices is None else choices.ctypes.data, status.ctypes.data,
-                                              n_rollouts, max_turns, self._seed if seed is None else seed, out.ctypes.data)
-        if st != 0 and (status == 1).any():
-            _check(st, "ge_batch_rollout_seats")
+        if len({len(x) for x in args} | ({len(rooms)} if actions is None else {len(actions)})) > 1:
+            raise GeError(-1, f"{method}: arrays differ in length")
+        out = np.zeros((len(rooms), _lib.ROLLOUT_WORDS), dtype=np.uint64)
+        status = None
+        if method != "rollout_rooms":
+            first = players = choices = None
+            if actions is not None:                              # CSR: entry k's actions are [first[k], first[k + 1])
+                first = np.zeros(len(actions) + 1, dtype=np.uint32)
+                first[1:] = np.cumsum([len(a) for a in actions])
+                flat = [pc for a in actions for pc in a]
+                players = np.ascontiguousarray([int(p) for p, _ in flat], dtype=np.uint32)
+                choices = np.ascontiguousarray([int(c) for _, c in flat], dtype=np.uint32)
+            status = np.full(len(rooms), 1, dtype=np.int32)      # 1: untouched (no ge_status is positive)
+            args += [first, players, choices, status]
+        sym = "ge_batch_" + method
+        st = getattr(self._lib, sym)(self._h, len(rooms), *[x if x is None else x.ctypes.data for x in args], n_rollouts, max_turns,
+                                     self._seed if seed is None else seed, out.ctypes.data)
+        # a refused entry returns its status with every entry's verdict written; a structural error or a failure of the call
+        # leaves the verdicts untouched (ge_batch_rollout_rooms writes none)
+        if st != 0 and (status is None or (status == 1).any()):
+            _check(st, sym)
         return out, status
 
     def write_agent_state(self, room: int, state: Dict[str, Any], visit_actions: Optional[Dict[Any, int]] = None) -> Dict[str, Any]:
