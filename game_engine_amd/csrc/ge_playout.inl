@@ -1,0 +1,453 @@
+// ge_playout.inl — playout seats (ge_batch_step_rooms_playout, POLICY.md §3d): ge_batch_step_rooms with some bot seats choosing
+// their action by their own seat-view playouts (included at the end of ge_step.hip, behind ge_rollout.inl: the existing kernels
+// keep their code-object offsets; it needs ge_pool.inl's and ge_rollout.inl's helpers).
+//
+// Per listed room, on the device, with no room record crossing to the host:
+//   1. ge_playout_plan: one lane per room.  It unpacks the record and finds the seats of its playout mask that decide in this
+//      turn (a due bot of §1 step 1 with at least 2 candidates; none at all in a restart-terminal or phase-0-guard turn).  A
+//      seat is a target exactly when ge_batch_inject_actions would accept an action of it (inject_ww / inject_tt on a copy of
+//      the record: the same condition, liveness and "not yet acted" tests).  Each (seat, candidate) becomes one entry of
+//      ge_batch_rollout_seats in the form RollArgs<2> reads; a room takes a contiguous run of entries from its unit's atomic
+//      counter, seat-major and candidates ascending.
+//   2. The host reads the units' entry counts back (4 bytes each) and launches ge_rollout_kernel<.., ACT = 2> on the
+//      device-resident entries through rollout_launch_form: the playout kernel is ge_batch_rollout_seats's own, unchanged.
+//   3. ge_playout_decide: one lane per room.  Per deciding seat, the argmax of seat_wins over its entries with the tie-break
+//      pick(d, m) (d = the seat's draw of this turn); the chosen actions are logged by inject_ww / inject_tt and the record is
+//      stored as ge_inject_kernel stores it.
+//   4. ge_pool_kernel plays the turn exactly as ge_batch_step_rooms launches it: the injected seats have acted, so the policy
+//      skips them; the host ORs them into the turn's events.
+// A room's entries depend only on its own record, keys and turn, never on where the atomic counter put them, so the result is
+// deterministic.
+
+namespace {
+
+struct PlanArgs {
+    const uint64_t *rooms, *keys, *pkeys;   // this unit's listed rooms (segment-local), their turn keys and playout keys
+    const uint32_t *turns, *masks;
+    uint32_t *room_first, *room_cnt;        // per listed room: its entries [first, first + cnt) of the pass
+    uint32_t *counter;                      // the unit's entry counter (zeroed by the host)
+    uint64_t *e_rooms, *e_keys;             // the pass's entries (RollArgs<2>'s arrays)
+    uint32_t *e_turns, *e_seats, *e_first, *e_players, *e_choices;
+    int32_t *e_status;
+    uint32_t n, seg, seed_key, restart, full_view, e_base;   // e_base: the unit's first entry in the pass
+};
+
+struct DecideArgs {
+    const uint64_t *rooms, *keys;
+    const uint32_t *turns, *room_first, *room_cnt;
+    const uint32_t *e_players, *e_choices;
+    const unsigned long long *acc;          // the pass's accumulators, ROLL_STRIDE words per entry
+    u32x4 *out;                             // per listed room: decided mask, choice nibbles (low, high)
+    uint32_t n, seg, seed_key;
+};
+
+// the policy's candidate set of seat i (0-based) in a Werewolf phase of action kind `act` (POLICY.md §3 table; ww_choose's)
+template <int NB> __device__ __forceinline__ uint32_t playout_cand_ww(const WW<NB> &s, uint32_t act, uint32_t i) {
+    const uint32_t me = 1u << i, alive = s.alive, team_w = s.team_w;
+    const uint32_t others = alive & ~me, non_wolf = alive & ~team_w, fresh = others & ~(s.det_v | s.det_w);
+    const uint32_t r_det = s.rb2 & ~s.rb1 & ~s.rb0;          // role class Detective
+    const uint32_t kw = s.det_w & alive, lo_kw = kw & (0u - kw);
+    uint32_t cand = alive;                                    // ACT_DOCTOR_PROTECT
+    if (act == ACT_WOLF_TARGET) cand = non_wolf;
+    else if (act == ACT_DETECTIVE) cand = fresh ? fresh : others;
+    else if (act == ACT_DAY_VOTE) cand = (team_w & me) ? non_wolf : (((r_det & me) && lo_kw) ? lo_kw : others);
+    return cand ? cand : alive;
+}
+
+// Two-Truths: statement 1 in a statements phase, else 1..3 (as bits 0..2)
+__device__ __forceinline__ uint32_t playout_cand_tt(uint32_t act) { return act == ACT_TT_STATEMENTS ? 1u : 7u; }
+
+// the seats of `mask` that decide in this turn, and the number of entries they need
+template <int NB, bool WWP, class S>
+__device__ __forceinline__ uint32_t playout_deciders(const S &s, const DevRow &row, const DevCond &cond, uint32_t n, uint32_t mask, uint32_t tk,
+                                                     uint32_t &n_entries) {
+    const uint32_t act = (row.r0 >> 2) & 7u;
+    uint32_t dec = 0, cnt = 0;
+    for (uint32_t m = mask; m; m &= m - 1u) {
+        const uint32_t i = ctz(m);
+        if ((draw(tk, i) & 3u) == 0u) continue;              // not due in this turn
+        uint32_t cand;
+        int st;
+        S t = s;                                              // a target exactly when an injected action would be accepted
+        if constexpr (WWP) {
+            cand = playout_cand_ww<NB>(s, act, i);
+            st = cand ? inject_ww<NB>(t, row, cond, n, i + 1u, ctz(cand) + 1u) : GE_ERR_ARG;
+        } else {
+            cand = playout_cand_tt(act);
+            st = inject_tt<NB>(t, row, cond, n, i + 1u, 1u);
+        }
+        if (st != GE_OK || popc(cand) < 2u) continue;
+        dec |= 1u << i;
+        cnt += popc(cand);
+    }
+    n_entries = cnt;
+    return dec;
+}
+
+template <int NB, bool WWP>
+__device__ __forceinline__ void playout_plan_room(const SegDev &sg, const DevTable *__restrict__ tables, const PlanArgs &a, uint32_t k) {
+    const uint64_t room = a.rooms[k];
+    const uint32_t turn = a.turns[k];
+    const uint32_t tk = turn_key(room_key_from(a.seed_key, a.keys[k]), turn);
+    uint32_t dec = 0, cnt = 0, act = 0;
+    uint32_t w[12];
+    if constexpr (WWP) {
+        using L = WWLayout<NB>;
+        load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+        WW<NB> s;
+        L::unpack(w, s);
+        const DevRow &row = tables[sg.table_idx].rows[s.phase];
+        act = (row.r0 >> 2) & 7u;
+        const bool skip = (a.restart && ((sg.term_mask >> s.phase) & 1u)) || (s.phase == sg.phase0_idx && !(s.flags & FLAG_PHASE0_DONE));
+        if (!skip) dec = playout_deciders<NB, true>(s, row, tables[sg.table_idx].conds[s.phase], sg.n_players, a.masks[k], tk, cnt);
+        uint32_t first = cnt ? atomicAdd(a.counter, cnt) + a.e_base : 0u;
+        a.room_first[k] = first;
+        a.room_cnt[k] = cnt;
+        for (uint32_t m = dec; m; m &= m - 1u) {
+            const uint32_t i = ctz(m);
+            for (uint32_t c = playout_cand_ww<NB>(s, act, i); c; c &= c - 1u, first++) {
+                a.e_rooms[first] = room; a.e_keys[first] = a.pkeys[k]; a.e_turns[first] = turn;
+                a.e_seats[first] = a.full_view ? 0u : i + 1u;
+                a.e_first[first] = first; a.e_first[first + 1u] = first + 1u;
+                a.e_players[first] = i + 1u; a.e_choices[first] = ctz(c) + 1u;
+                a.e_status[first] = GE_OK;
+            }
+        }
+    } else {
+        using L = TTLayout<NB>;
+        load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+        TT<NB> s;
+        L::unpack(w, s);
+        const DevRow &row = tables[sg.table_idx].rows[s.phase];
+        act = (row.r0 >> 2) & 7u;
+        const bool skip = (a.restart && ((sg.term_mask >> s.phase) & 1u)) || (s.phase == sg.phase0_idx && !(s.flags & FLAG_PHASE0_DONE));
+        if (!skip) dec = playout_deciders<NB, false>(s, row, tables[sg.table_idx].conds[s.phase], sg.n_players, a.masks[k], tk, cnt);
+        uint32_t first = cnt ? atomicAdd(a.counter, cnt) + a.e_base : 0u;
+        a.room_first[k] = first;
+        a.room_cnt[k] = cnt;
+        for (uint32_t m = dec; m; m &= m - 1u) {
+            const uint32_t i = ctz(m);
+            for (uint32_t c = playout_cand_tt(act); c; c &= c - 1u, first++) {
+                a.e_rooms[first] = room; a.e_keys[first] = a.pkeys[k]; a.e_turns[first] = turn;
+                a.e_seats[first] = a.full_view ? 0u : i + 1u;
+                a.e_first[first] = first; a.e_first[first + 1u] = first + 1u;
+                a.e_players[first] = i + 1u; a.e_choices[first] = ctz(c) + 1u;
+                a.e_status[first] = GE_OK;
+            }
+        }
+    }
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(64) ge_playout_plan(const SegDev *__restrict__ segs, const DevTable *__restrict__ tables, const PlanArgs a) {
+    const uint32_t k = blockIdx.x * 64u + threadIdx.x;
+    if (k >= a.n) return;
+    const SegDev &sg = segs[a.seg];
+    if (KIND == K_WW8) playout_plan_room<8, true>(sg, tables, a, k);
+    else if (KIND == K_WW12) playout_plan_room<12, true>(sg, tables, a, k);
+    else if (KIND == K_TT4) playout_plan_room<4, false>(sg, tables, a, k);
+    else if (KIND == K_TT8) playout_plan_room<8, false>(sg, tables, a, k);
+    else playout_plan_room<12, false>(sg, tables, a, k);
+}
+
+// per deciding seat of room k: argmax of seat_wins with the pick(d, m) tie-break, logged in `s` by `inject`
+template <class INJ>
+__device__ __forceinline__ void playout_choose(const DecideArgs &a, uint32_t k, uint32_t tk, INJ &&inject) {
+    const uint32_t lo = a.room_first[k], hi = lo + a.room_cnt[k];
+    uint32_t cur = 0, tie = 0, decided = 0;
+    uint64_t nib = 0;
+    unsigned long long best = 0;
+    for (uint32_t j = lo;; j++) {
+        const bool end = j == hi;
+        const uint32_t seat = end ? 0u : a.e_players[j];
+        if (cur != 0u && seat != cur) {                       // seat cur's entries are complete
+            const uint32_t c = nth_set_bit<16>(tie, pick(draw(tk, cur - 1u), popc(tie))) + 1u;
+            if (inject(cur, c) == GE_OK) {                    // (always: the candidates are the policy's own)
+                decided |= 1u << (cur - 1u);
+                nib |= (uint64_t)c << (4u * (cur - 1u));
+            }
+        }
+        if (end) break;
+        const uint32_t c = a.e_choices[j];
+        const unsigned long long v = a.acc[(size_t)j * ROLL_STRIDE + 51u + (seat - 1u)];   // seat_wins[seat - 1]
+        if (seat != cur || v > best) { cur = seat; best = v; tie = 1u << (c - 1u); }
+        else if (v == best) tie |= 1u << (c - 1u);
+    }
+    u32x4 o;
+    o.x = decided; o.y = (uint32_t)nib; o.z = (uint32_t)(nib >> 32); o.w = 0u;
+    a.out[k] = o;
+}
+
+template <int NB, bool WWP>
+__device__ __forceinline__ void playout_decide_room(const SegDev &sg, const DevTable *__restrict__ tables, const DecideArgs &a, uint32_t k) {
+    const uint64_t room = a.rooms[k];
+    const uint32_t tk = turn_key(room_key_from(a.seed_key, a.keys[k]), a.turns[k]);
+    uint32_t w[12];
+    if constexpr (WWP) {
+        using L = WWLayout<NB>;
+        load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+        WW<NB> s;
+        L::unpack(w, s);
+        const DevRow &row = tables[sg.table_idx].rows[s.phase];
+        const DevCond &cond = tables[sg.table_idx].conds[s.phase];   // read in place, as inject_group_ww
+        playout_choose(a, k, tk, [&](uint32_t p, uint32_t c) { return inject_ww<NB>(s, row, cond, sg.n_players, p, c); });
+        L::pack(s, w);
+        store_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+    } else {
+        using L = TTLayout<NB>;
+        load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+        TT<NB> s;
+        L::unpack(w, s);
+        const DevRow &row = tables[sg.table_idx].rows[s.phase];
+        const DevCond &cond = tables[sg.table_idx].conds[s.phase];   // read in place, as inject_group_tt
+        playout_choose(a, k, tk, [&](uint32_t p, uint32_t c) { return inject_tt<NB>(s, row, cond, sg.n_players, p, c); });
+        L::pack(s, w);
+        store_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+    }
+}
+
+// one lane per listed room of a unit with entries (a room without any stores nothing: its output was zeroed by the host)
+template <int KIND>
+__global__ void __launch_bounds__(64) ge_playout_decide(const SegDev *__restrict__ segs, const DevTable *__restrict__ tables, const DecideArgs a) {
+    const uint32_t k = blockIdx.x * 64u + threadIdx.x;
+    if (k >= a.n || a.room_cnt[k] == 0u) return;
+    const SegDev &sg = segs[a.seg];
+    if (KIND == K_WW8) playout_decide_room<8, true>(sg, tables, a, k);
+    else if (KIND == K_WW12) playout_decide_room<12, true>(sg, tables, a, k);
+    else if (KIND == K_TT4) playout_decide_room<4, false>(sg, tables, a, k);
+    else if (KIND == K_TT8) playout_decide_room<8, false>(sg, tables, a, k);
+    else playout_decide_room<12, false>(sg, tables, a, k);
+}
+
+// most candidates one deciding seat of a segment can have: Werewolf a subset of the n seats, Two-Truths at most statements 1..3
+// (a Two-Truths segment may have 2 players).  The entry space and the cost cap reserve this per playout seat.
+uint32_t playout_max_cands(const SegDev &d) { return (d.kind == K_WW8 || d.kind == K_WW12) ? d.n_players : std::max(d.n_players, 3u); }
+
+template <class A>
+hipError_t playout_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const A &a) {
+#define GE_PLAYOUT_LAUNCH(K)                                                                                                          \
+    if constexpr (std::is_same<A, PlanArgs>::value) hipLaunchKernelGGL((ge_playout_plan<K>), grid, dim3(64), 0, st, b->segs_dev, b->tables, a); \
+    else hipLaunchKernelGGL((ge_playout_decide<K>), grid, dim3(64), 0, st, b->segs_dev, b->tables, a);
+    switch (kind) {
+    case K_WW8: { GE_PLAYOUT_LAUNCH(K_WW8) } break;
+    case K_WW12: { GE_PLAYOUT_LAUNCH(K_WW12) } break;
+    case K_TT4: { GE_PLAYOUT_LAUNCH(K_TT4) } break;
+    case K_TT8: { GE_PLAYOUT_LAUNCH(K_TT8) } break;
+    default: { GE_PLAYOUT_LAUNCH(K_TT12) } break;
+    }
+#undef GE_PLAYOUT_LAUNCH
+    return hipGetLastError();
+}
+
+}  // namespace
+
+// a run of sorted listed rooms of one segment whose entries share one pass's arrays
+struct PlayoutUnit {
+    uint32_t seg, lo, cnt;          // sorted positions [lo, lo + cnt)
+    uint32_t e_base, e_cap;         // its entries within the pass: [e_base, e_base + e_cap) at most
+    uint32_t pass;
+};
+
+static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, const uint32_t *masks,
+                             const uint64_t *pkeys, uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, uint32_t flags, ge_turn_event *events,
+                             uint32_t *decided) {
+    GE_ON_DEVICE(b);
+    int st = sync_impl(b);
+    if (st != GE_OK) return st;
+    const uint32_t n_seg = (uint32_t)b->segs.size();
+    std::vector<uint32_t> seg_of((size_t)n), begin(n_seg + 1u, 0u), order((size_t)n);
+    for (uint64_t k = 0; k < n; k++) { seg_of[k] = pool_segment_of(b, rooms[k]); begin[seg_of[k] + 1u]++; }
+    for (uint32_t s = 0; s < n_seg; s++) begin[s + 1u] += begin[s];
+    {
+        std::vector<uint32_t> at(begin.begin(), begin.end() - 1);
+        for (uint64_t k = 0; k < n; k++) order[at[seg_of[k]]++] = (uint32_t)k;
+    }
+    // units: runs of one segment with at most CHUNK entries' room (a room needs popcount(mask) x playout_max_cands at most); passes:
+    // consecutive units whose room fits in CHUNK entries together.  A pass's entries are planned, played and decided together.
+    const uint32_t CHUNK = 65536;
+    std::vector<PlayoutUnit> units;
+    uint32_t n_pass = 0, pass_cap = 0, max_cap = 0;
+    for (uint32_t g = 0; g < n_seg; g++) {
+        const uint32_t np = playout_max_cands(b->segs[g].dev);
+        for (uint32_t i = begin[g]; i < begin[g + 1u]; i++) {
+            const uint32_t cap = (uint32_t)__builtin_popcount(masks[order[i]]) * np;
+            if (!cap) continue;                               // no playout seat: only the turn (step 4)
+            const bool fresh = units.empty() || units.back().seg != g || units.back().lo + units.back().cnt != i || units.back().e_cap + cap > CHUNK;
+            if (fresh) {
+                if (units.empty() || pass_cap + cap > CHUNK) { n_pass++; pass_cap = 0; }
+                units.push_back(PlayoutUnit{g, i, 0u, pass_cap, 0u, n_pass - 1u});
+            }
+            units.back().cnt++;
+            units.back().e_cap += cap;
+            pass_cap += cap;
+            max_cap = std::max(max_cap, pass_cap);
+        }
+    }
+    const uint32_t n_units = (uint32_t)units.size();
+    // one scratch layout, each array from a 16 B boundary.  Upload: [rooms u64][keys u64][pkeys u64][turns u32][masks u32]
+    // [unit counters u32][per-room outputs 16 B, zeroed].  Then [room_first u32][room_cnt u32][events 16 B] and the pass's
+    // entries: [rooms u64][keys u64][turns u32][seats u32][first u32 (+1)][players u32][choices u32][status i32][acc]
+    auto up16 = [](size_t x) { return (x + 15u) & ~(size_t)15u; };
+    const size_t N = (size_t)n, C = max_cap;
+    const size_t o_keys = 8 * N, o_pkeys = 16 * N, o_turns = 24 * N, o_masks = up16(o_turns + 4 * N), o_ctr = up16(o_masks + 4 * N);
+    const size_t o_out = up16(o_ctr + 4 * (size_t)n_units), o_up_end = o_out + 16 * N;
+    const size_t o_rfirst = o_up_end, o_rcnt = up16(o_rfirst + 4 * N), o_ev = up16(o_rcnt + 4 * N);
+    RollStage o;
+    const size_t o_erooms = o_ev + 16 * N, o_ekeys = o_erooms + 8 * C, o_eturns = o_ekeys + 8 * C;
+    o.keys = o.turns = 0;
+    o.seats = up16(o_eturns + 4 * C);
+    o.first = up16(o.seats + 4 * C);
+    o.players = up16(o.first + 4 * (C + 1u));
+    o.choices = up16(o.players + 4 * C);
+    o.status = up16(o.choices + 4 * C);
+    o.acc = up16(o.status + 4 * C);
+    o.total = o.acc + 8 * (size_t)ROLL_STRIDE * C;
+    uint32_t *host32 = nullptr;
+    if ((st = io_stage(b, o.total, &host32)) != GE_OK) return st;
+    unsigned char *host = reinterpret_cast<unsigned char *>(host32);
+    uint64_t *h_rooms = reinterpret_cast<uint64_t *>(host), *h_keys = reinterpret_cast<uint64_t *>(host + o_keys);
+    uint64_t *h_pkeys = reinterpret_cast<uint64_t *>(host + o_pkeys);
+    uint32_t *h_turns = reinterpret_cast<uint32_t *>(host + o_turns), *h_masks = reinterpret_cast<uint32_t *>(host + o_masks);
+    for (size_t i = 0; i < N; i++) {
+        const uint32_t k = order[i];
+        h_rooms[i] = rooms[k] - b->segs[seg_of[k]].local_first;
+        h_keys[i] = keys[k]; h_pkeys[i] = pkeys[k]; h_turns[i] = turns[k]; h_masks[i] = masks[k];
+    }
+    memset(host + o_ctr, 0, o_up_end - o_ctr);
+    char *dev = nullptr;
+    if ((st = pool_scratch(b, o.total, &dev)) != GE_OK) return st;
+    hipStream_t s = b->last_stream;
+    if ((st = order_after_previous(b, s)) != GE_OK) return st;
+    HIP_TRY(hipMemcpyAsync(dev, host, o_up_end, hipMemcpyHostToDevice, s));
+    const uint32_t seed_b = seed_key((uint32_t)b->seed, (uint32_t)(b->seed >> 32));
+    const uint32_t restart = (b->flags & GE_FLAG_RESTART) ? 1u : 0u;
+    const uint32_t *h_ctr = reinterpret_cast<const uint32_t *>(host + o_ctr);
+    for (uint32_t p = 0; p < n_pass; p++) {
+        // 1. plan every unit of the pass
+        for (const PlayoutUnit &u : units) {
+            if (u.pass != p) continue;
+            PlanArgs a;
+            a.rooms = reinterpret_cast<const uint64_t *>(dev) + u.lo;
+            a.keys = reinterpret_cast<const uint64_t *>(dev + o_keys) + u.lo;
+            a.pkeys = reinterpret_cast<const uint64_t *>(dev + o_pkeys) + u.lo;
+            a.turns = reinterpret_cast<const uint32_t *>(dev + o_turns) + u.lo;
+            a.masks = reinterpret_cast<const uint32_t *>(dev + o_masks) + u.lo;
+            a.room_first = reinterpret_cast<uint32_t *>(dev + o_rfirst) + u.lo;
+            a.room_cnt = reinterpret_cast<uint32_t *>(dev + o_rcnt) + u.lo;
+            a.counter = reinterpret_cast<uint32_t *>(dev + o_ctr) + (&u - units.data());
+            a.e_rooms = reinterpret_cast<uint64_t *>(dev + o_erooms); a.e_keys = reinterpret_cast<uint64_t *>(dev + o_ekeys);
+            a.e_turns = reinterpret_cast<uint32_t *>(dev + o_eturns); a.e_seats = reinterpret_cast<uint32_t *>(dev + o.seats);
+            a.e_first = reinterpret_cast<uint32_t *>(dev + o.first); a.e_players = reinterpret_cast<uint32_t *>(dev + o.players);
+            a.e_choices = reinterpret_cast<uint32_t *>(dev + o.choices); a.e_status = reinterpret_cast<int32_t *>(dev + o.status);
+            a.n = u.cnt; a.seg = u.seg; a.seed_key = seed_b; a.restart = restart;
+            a.full_view = (flags & GE_PLAYOUT_FULL_VIEW) ? 1u : 0u; a.e_base = u.e_base;
+            HIP_TRY(playout_launch(b->segs[u.seg].dev.kind, dim3((u.cnt + 63u) / 64u), s, b, a));
+        }
+        // 2. the entry counts (the one host round trip), then the playouts of each unit
+        HIP_TRY(hipMemcpyAsync(host + o_ctr, dev + o_ctr, 4 * (size_t)n_units, hipMemcpyDeviceToHost, s));
+        if ((st = sync_impl(b)) != GE_OK) return st;
+        if ((st = order_after_previous(b, s)) != GE_OK) return st;
+        const uint32_t waves = (n_rollouts + 63u) / 64u;
+        for (const PlayoutUnit &u : units) {
+            const uint32_t cnt = h_ctr[&u - units.data()];
+            if (u.pass != p || !cnt) continue;
+            HIP_TRY(hipMemsetAsync(dev + o.acc + 8 * (size_t)ROLL_STRIDE * u.e_base, 0, 8 * (size_t)ROLL_STRIDE * cnt, s));
+            RolloutArgs a;
+            a.rooms = reinterpret_cast<const uint64_t *>(dev + o_erooms) + u.e_base;
+            a.keys = reinterpret_cast<const uint64_t *>(dev + o_ekeys) + u.e_base;
+            a.turns = reinterpret_cast<const uint32_t *>(dev + o_eturns) + u.e_base;
+            a.acc = reinterpret_cast<unsigned long long *>(dev + o.acc) + (size_t)ROLL_STRIDE * u.e_base;
+            a.n = cnt; a.seg = u.seg; a.seed_key = seed_key((uint32_t)seed, (uint32_t)(seed >> 32));
+            a.n_rollouts = n_rollouts; a.max_turns = max_turns; a.waves = waves;
+            a.settle_mask = rollout_settle_mask(b->segs[u.seg]);
+            HIP_TRY(rollout_launch_form<2>(b, s, a, dev, o, u.e_base));
+        }
+        // 3. decide and log
+        for (const PlayoutUnit &u : units) {
+            if (u.pass != p || !h_ctr[&u - units.data()]) continue;
+            DecideArgs a;
+            a.rooms = reinterpret_cast<const uint64_t *>(dev) + u.lo;
+            a.keys = reinterpret_cast<const uint64_t *>(dev + o_keys) + u.lo;
+            a.turns = reinterpret_cast<const uint32_t *>(dev + o_turns) + u.lo;
+            a.room_first = reinterpret_cast<const uint32_t *>(dev + o_rfirst) + u.lo;
+            a.room_cnt = reinterpret_cast<const uint32_t *>(dev + o_rcnt) + u.lo;
+            a.e_players = reinterpret_cast<const uint32_t *>(dev + o.players);
+            a.e_choices = reinterpret_cast<const uint32_t *>(dev + o.choices);
+            a.acc = reinterpret_cast<const unsigned long long *>(dev + o.acc);
+            a.out = reinterpret_cast<u32x4 *>(dev + o_out) + u.lo;
+            a.n = u.cnt; a.seg = u.seg; a.seed_key = seed_b;
+            HIP_TRY(playout_launch(b->segs[u.seg].dev.kind, dim3((u.cnt + 63u) / 64u), s, b, a));
+        }
+    }
+    // 4. the turn, as step_rooms_impl launches it
+    for (uint32_t g = 0; g < n_seg; g++) {
+        const uint32_t lo = begin[g], cnt = begin[g + 1u] - lo;
+        if (!cnt) continue;
+        PoolArgs a;
+        a.rooms = reinterpret_cast<const uint64_t *>(dev) + lo;
+        a.keys = reinterpret_cast<const uint64_t *>(dev + o_keys) + lo;
+        a.turns = reinterpret_cast<const uint32_t *>(dev + o_turns) + lo;
+        a.events = reinterpret_cast<uint32_t *>(dev + o_ev) + 4u * (size_t)lo;
+        a.n = cnt; a.seg = g; a.seed_key = seed_b; a.restart = restart;
+        const dim3 grid((cnt + 63u) / 64u);
+        HIP_TRY(b->generic ? pool_launch<1>(b->segs[g].dev.kind, grid, s, b, a) : pool_launch<0>(b->segs[g].dev.kind, grid, s, b, a));
+    }
+    HIP_TRY(hipMemcpyAsync(host + o_out, dev + o_out, 16 * N, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(host + o_ev, dev + o_ev, 16 * N, hipMemcpyDeviceToHost, s));
+    if ((st = sync_impl(b)) != GE_OK) return st;
+    const uint32_t *h_out = reinterpret_cast<const uint32_t *>(host + o_out), *h_ev = reinterpret_cast<const uint32_t *>(host + o_ev);
+    for (size_t i = 0; i < N; i++) {
+        const uint32_t k = order[i];
+        const uint32_t dmask = h_out[4 * i];
+        const uint64_t dnib = (uint64_t)h_out[4 * i + 1] | ((uint64_t)h_out[4 * i + 2] << 32);
+        if (decided) decided[k] = dmask;
+        if (!events) continue;
+        const uint32_t *w = h_ev + 4 * i;                     // as step_rooms_impl decodes it, with the decided seats acted
+        const ge_game_table &tb = b->segs[seg_of[k]].table;
+        ge_turn_event &e = events[k];
+        memset(&e, 0, sizeof e);
+        e.turn = w[0];
+        e.from_phase_id = tb.rows[w[1] & 255u].phase_id;
+        e.to_phase_id = tb.rows[(w[1] >> 8) & 255u].phase_id;
+        e.restarted = (w[1] >> 16) & 1u;
+        e.acted_now = (uint16_t)((w[1] >> 20) | dmask);
+        const uint64_t ch = (uint64_t)w[2] | ((uint64_t)w[3] << 32) | dnib;
+        for (int c = 0; c < 16; c++) e.choice[c] = (uint8_t)((ch >> (4 * c)) & 15u);
+    }
+    return GE_OK;
+}
+
+extern "C" {
+
+int ge_batch_step_rooms_playout(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
+                                const uint32_t *playout_masks, const uint64_t *playout_keys, uint32_t n_rollouts, uint32_t max_turns,
+                                uint64_t seed, uint32_t flags, ge_turn_event *events, uint32_t *decided) {
+    if (!b) return GE_ERR_ARG;
+    if (n == 0) return GE_OK;
+    // ge_batch_step_rooms's checks, in its order
+    if (!rooms || !keys || !turns || n > 0x7FFFFFFFull) return GE_ERR_ARG;
+    for (uint64_t k = 0; k < n; k++)
+        if (rooms[k] >= b->n_rooms || turns[k] == 0xFFFFFFFFu) return GE_ERR_RANGE;
+    {
+        std::vector<uint64_t> sorted(rooms, rooms + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return GE_ERR_ARG;
+    }
+    // then the playouts': ge_batch_rollout_seats's caps, the masks and the cost cap
+    if (!playout_masks || !playout_keys || (flags & ~GE_PLAYOUT_FULL_VIEW)) return GE_ERR_ARG;
+    if (n_rollouts == 0 || n_rollouts > (1u << 20) || max_turns > 4096u) return GE_ERR_ARG;
+    for (uint64_t k = 0; k < n; k++)
+        if ((uint64_t)turns[k] + max_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;
+    uint64_t cost = 0;
+    for (uint64_t k = 0; k < n; k++) {
+        const SegDev &sg = b->segs[pool_segment_of(b, rooms[k])].dev;
+        const uint32_t m = playout_masks[k];
+        if ((m >> sg.n_players) != 0u || (m & sg.human_mask) != 0u) return GE_ERR_ARG;
+        cost += (uint64_t)__builtin_popcount(m) * playout_max_cands(sg) * n_rollouts;
+        if (cost > (1ull << 26)) return GE_ERR_ARG;
+    }
+    return guarded([&] { return step_playout_impl(b, n, rooms, keys, turns, playout_masks, playout_keys, n_rollouts, max_turns, seed, flags,
+                                                  events, decided); });
+}
+
+}  // extern "C"

@@ -480,6 +480,49 @@ napi_value StepRooms(napi_env env, napi_callback_info info) {
     return out;
 }
 
+// stepRoomsPlayout(batch, rooms: BigUint64Array, keys: BigUint64Array, turns: Uint32Array, masks: Uint32Array,
+// playoutKeys: BigUint64Array, nRollouts, maxTurns, seed: BigInt, flags): { buffer: ArrayBuffer of rooms.length ge_turn_event,
+// decided: Uint32Array } - stepRooms with playout seats (ge_batch_step_rooms_playout, POLICY.md §3d)
+napi_value StepRoomsPlayout(napi_env env, napi_callback_info info) {
+    size_t argc = 10;
+    napi_value argv[10];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
+    if (!b || argc < 10) return throw_status(env, GE_ERR_ARG, "stepRoomsPlayout");
+    napi_typedarray_type tt[5];
+    size_t len[5];
+    void *data[5];
+    for (int k = 0; k < 5; k++) {
+        napi_value ab;
+        size_t off;
+        if (napi_get_typedarray_info(env, argv[1 + k], &tt[k], &len[k], &data[k], &ab, &off) != napi_ok)
+            return throw_status(env, GE_ERR_ARG, "stepRoomsPlayout", "typed arrays expected");
+    }
+    if (tt[0] != napi_biguint64_array || tt[1] != napi_biguint64_array || tt[2] != napi_uint32_array || tt[3] != napi_uint32_array ||
+        tt[4] != napi_biguint64_array || len[0] != len[1] || len[1] != len[2] || len[2] != len[3] || len[3] != len[4])
+        return throw_status(env, GE_ERR_ARG, "stepRoomsPlayout", "BigUint64Array x 2, Uint32Array x 2, BigUint64Array of equal length");
+    uint32_t n_rollouts = 0, max_turns = 0, flags = 0;
+    uint64_t seed = 0;
+    bool lossless = true;
+    if (napi_get_value_uint32(env, argv[6], &n_rollouts) != napi_ok || napi_get_value_uint32(env, argv[7], &max_turns) != napi_ok ||
+        napi_get_value_bigint_uint64(env, argv[8], &seed, &lossless) != napi_ok || napi_get_value_uint32(env, argv[9], &flags) != napi_ok)
+        return throw_status(env, GE_ERR_ARG, "stepRoomsPlayout", "nRollouts, maxTurns (numbers), seed (BigInt), flags expected");
+    void *ev = nullptr, *dec = nullptr;
+    napi_value buf, dbuf, darr, out;
+    NAPI_OK(napi_create_arraybuffer(env, len[0] * sizeof(ge_turn_event), &ev, &buf));
+    NAPI_OK(napi_create_arraybuffer(env, len[0] * sizeof(uint32_t), &dec, &dbuf));
+    const int st = ge_batch_step_rooms_playout(b, len[0], static_cast<const uint64_t *>(data[0]), static_cast<const uint64_t *>(data[1]),
+                                               static_cast<const uint32_t *>(data[2]), static_cast<const uint32_t *>(data[3]),
+                                               static_cast<const uint64_t *>(data[4]), n_rollouts, max_turns, seed, flags,
+                                               static_cast<ge_turn_event *>(ev), static_cast<uint32_t *>(dec));
+    if (st != GE_OK) return throw_status(env, st, "stepRoomsPlayout");
+    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, len[0], dbuf, 0, &darr));
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_set_named_property(env, out, "buffer", buf));
+    NAPI_OK(napi_set_named_property(env, out, "decided", darr));
+    return out;
+}
+
 bool is_nullish(napi_env env, napi_value v) {
     napi_valuetype t;
     return napi_typeof(env, v, &t) == napi_ok && (t == napi_null || t == napi_undefined);
@@ -826,6 +869,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"destroyBatch", nullptr, DestroyBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"readEvents", nullptr, ReadEvents, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"stepRooms", nullptr, StepRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"stepRoomsPlayout", nullptr, StepRoomsPlayout, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"readRoomsAt", nullptr, ReadRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"rollout", nullptr, Rollout, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"writeRoomsAt", nullptr, WriteRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},

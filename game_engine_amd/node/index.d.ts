@@ -68,6 +68,9 @@ export class RoomBatch {
   readEvents(first: number, count: number): TurnEvent[][];
   /** One turn of each listed room (local, pairwise distinct), room k keyed as global room keys[k] at turn turns[k]; event k of room k. */
   stepRooms(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>): TurnEvent[];
+  stepRoomsPlayout(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, masks: ArrayLike<number>,
+                   playoutKeys: ArrayLike<number | bigint>, nRollouts: number, maxTurns?: number, seed?: number | bigint,
+                   fullView?: boolean): { events: TurnEvent[]; decided: Uint32Array };
   /** Playouts of each listed room (replica r of entry k = global room keys[k] + r under seed, default the batch's): rooms.length x 77
    *  words of ge_rollout_stats (41 summary words, then seat_alive, seat_wins, seat_score x 12).  The batch is only read. */
   rolloutRooms(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, nRollouts: number,

@@ -580,6 +580,21 @@ class RoomBatch {
     for (let k = 0; k < rooms.length; k++) out.push(decodeEvent(buffer, k * EVENT_SIZE));
     return out;
   }
+  /** stepRooms with playout seats (twin of the Python RoomBatch.step_rooms_playout, POLICY.md §3d): bit i of masks[k] makes seat
+   * i+1 of room k a playout bot, which - when the policy has it act with at least 2 candidates - takes the candidate whose
+   * rolloutSeats entry (room k as it stands, playoutKeys[k], turns[k], the seat or 0 with fullView, that one action, nRollouts,
+   * maxTurns, seed) has the most seat_wins of the seat; ties go to the policy's own pick among the tied.  Returns
+   * { events, decided }: stepRooms's events (the decided seats listed as acted) and decided[k] (bit i = seat i+1 chose by
+   * playouts).  All-or-nothing.  Synchronous. */
+  stepRoomsPlayout(rooms, keys, turns, masks, playoutKeys, nRollouts, maxTurns = 256, seed, fullView = false) {
+    const { buffer, decided } = addon.stepRoomsPlayout(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r)),
+      BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))), Uint32Array.from(turns), Uint32Array.from(masks),
+      BigUint64Array.from(playoutKeys, (k) => BigInt.asUintN(64, BigInt(k))), nRollouts, maxTurns,
+      seed === undefined ? this.seed : BigInt.asUintN(64, BigInt(seed)), fullView ? 1 : 0);
+    const events = [];
+    for (let k = 0; k < rooms.length; k++) events.push(decodeEvent(buffer, k * EVENT_SIZE));
+    return { events, decided };
+  }
   /** Playouts (twin of the Python RoomBatch.rollout_rooms): entry k is played nRollouts times from room rooms[k] as it stands,
    * replica r as global room keys[k] + r (mod 2^64) under `seed` (default: the batch's) at turns turns[k] .. turns[k] + maxTurns - 1,
    * every seat played by the policy and a finished game left finished.  Returns a BigUint64Array of rooms.length x 77 words

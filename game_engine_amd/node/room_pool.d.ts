@@ -1,12 +1,12 @@
 // Types for room_pool.js — many game threads hosted in a few resident batches.
-import { AdoptOptions, Advice, AgentStateView, Forecast, RoomPlayer, TurnResult } from './room_service';
+import { AdoptOptions, Advice, AgentStateView, Forecast, PlayoutOptions, RoomPlayer, TurnResult } from './room_service';
 
 export type MessageResult = TurnResult & { played: boolean; kind: 'chat' | 'control' | 'action' };
 export class RoomPoolService {
   /** chunkRooms: slots per batch chunk of a pool (one pool per game, player count and human seats) */
-  constructor(opts?: { gamesDir?: string; seed?: bigint | number; device?: number; chunkRooms?: number });
+  constructor(opts?: { gamesDir?: string; seed?: bigint | number; device?: number; chunkRooms?: number } & PlayoutOptions);
   /** As RoomService.createRoom: the thread's RNG is keyed by roomIndex (default: hash of the thread id), its turn counter starts at 0. */
-  createRoom(opts: { threadId: string; gameName: string; players: RoomPlayer[]; dsl?: object; roomIndex?: number | bigint }): AgentStateView;
+  createRoom(opts: { threadId: string; gameName: string; players: RoomPlayer[]; dsl?: object; roomIndex?: number | bigint; playoutSeats?: number[] }): AgentStateView;
   /** As RoomService.adoptRoom for many threads: every state is converted before a slot is taken, then one writeRoomsAt per chunk. */
   adoptRooms(entries: AdoptOptions[]): Promise<TurnResult[]>;
   humanAction(threadId: string, playerId: number, choice: number): Promise<AgentStateView>;

@@ -11,13 +11,17 @@
  */
 const { GameTable, RoomBatch, RoomLog, decodeRoom, turnToolCalls, uiToolCalls } = require('./index.js');
 const { roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, adviseCandidates, adviseSeat, runRollouts, adviseOutput,
-        seatForecastOutput, checkForecastSeat, checkView } = require('./room_service.js');
+        seatForecastOutput, checkForecastSeat, checkView, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, forecastKey, forecastSeed } = require('./room_service.js');
+const popcount = (m) => { let c = 0; for (let x = m; x; x &= x - 1) c++; return c; };
 const M = require('./messages.js');
 
 const GE_ERR_ARG = -1;
 
 class RoomPoolService {
-  constructor({ gamesDir = 'games', seed = 0n, device = 0, chunkRooms = 1024 } = {}) {
+  /** playoutRollouts / playoutMaxTurns / playoutView: as RoomService's. */
+  constructor({ gamesDir = 'games', seed = 0n, device = 0, chunkRooms = 1024, playoutRollouts = 256, playoutMaxTurns = 256, playoutView = 'seat' } = {}) {
+    this.playoutFull = checkPlayoutOptions(playoutRollouts, playoutMaxTurns, playoutView);
+    this.playoutRollouts = playoutRollouts; this.playoutMaxTurns = playoutMaxTurns;
     if (!(chunkRooms >= 1)) throw new RangeError('chunkRooms must be >= 1');
     this.gamesDir = gamesDir; this.seed = BigInt(seed); this.device = device; this.chunkRooms = chunkRooms;
     this.tables = new Map();       // gameName -> GameTable
@@ -51,9 +55,10 @@ class RoomPoolService {
     return { chunk, ci, slot };
   }
   /** As RoomService.createRoom: players[i].isBot === false marks a human seat; roomIndex = the global room index the RNG is keyed by. */
-  createRoom({ threadId, gameName, players, dsl, roomIndex }) {
+  createRoom({ threadId, gameName, players, dsl, roomIndex, playoutSeats }) {
     const table = this.table(gameName, dsl);
     const humanMask = players.reduce((m, p, i) => (p.isBot === false ? m | (1 << i) : m), 0);
+    const playoutMask = playoutMaskOf(players.length, humanMask, playoutSeats);
     if (this.rooms.has(threadId)) this._release(threadId);
     const pk = `${gameName}/${players.length}/${humanMask}`;
     if (!this.pools.has(pk)) this.pools.set(pk, { table, nPlayers: players.length, humanMask, chunks: [], free: [], used: new Set(), templateRaw: null });
@@ -62,7 +67,7 @@ class RoomPoolService {
     const names = players.map((p, i) => p.name || `Player ${i + 1}`);
     const humanSeats = players.map((p, i) => (p.isBot === false ? i + 1 : 0)).filter((x) => x);
     const room = { pool, chunk, ci, slot, key: roomIndex === undefined ? roomIndexOf(threadId) : BigInt(roomIndex), turn: 0,
-                   table, gameName, names, humanSeats, panel: null, state: decodeRoom(table, pool.templateRaw, 0), log: new RoomLog(table, names, gameName) };
+                   table, gameName, names, humanSeats, playoutMask, panel: null, state: decodeRoom(table, pool.templateRaw, 0), log: new RoomLog(table, names, gameName) };
     this.rooms.set(threadId, room);
     return this.agentState(room);
   }
@@ -79,7 +84,8 @@ class RoomPoolService {
         if (seen.has(e.threadId)) throw new Error(`thread ${e.threadId} is named twice`);
         seen.add(e.threadId);
         const table = this.table(e.gameName, e.dsl);
-        return Object.assign({ e, table }, prepareAdoption(table, e));
+        const a = prepareAdoption(table, e);
+        return Object.assign({ e, table, playoutMask: playoutMaskOf(a.n, a.humanMask, e.playoutSeats) }, a);
       });
       const taken = [];
       try {
@@ -101,7 +107,7 @@ class RoomPoolService {
           const { pool, chunk, ci, slot } = taken[k];
           if (this.rooms.has(p.e.threadId)) this._release(p.e.threadId);
           const room = { pool, chunk, ci, slot, key: p.e.roomIndex === undefined ? roomIndexOf(p.e.threadId) : BigInt(p.e.roomIndex), turn: p.turn,
-                         table: p.table, gameName: p.e.gameName, names: p.names, humanSeats: p.humanSeats, panel: null, state: states[k],
+                         table: p.table, gameName: p.e.gameName, names: p.names, humanSeats: p.humanSeats, playoutMask: p.playoutMask, panel: null, state: states[k],
                          log: new RoomLog(p.table, p.names, p.e.gameName) };
           room.log.adopt(p.e.state, Object.assign({}, p.hostSide, { names: Object.fromEntries(p.names.map((nm, i) => [String(i + 1), nm])) }));
           this.rooms.set(p.e.threadId, room);
@@ -222,7 +228,9 @@ class RoomPoolService {
       return rooms.map((room, j) => seatForecastOutput(room.table, room.names, threadIds[j], room.turn, nRollouts, maxTurns, sv[j], res[j].words));
     });
   }
-  /** One turn of each room (distinct threads): one stepRooms and one readRoomsAt per chunk touched. */
+  /** One turn of each room (distinct threads): one stepRooms and one readRoomsAt per chunk touched; a chunk holding a thread
+   * with playout seats is stepped by stepRoomsPlayout instead (mask 0 for its other threads; more calls only when the
+   * playouts would pass the call's cap). */
   _turns(rooms, items) {
     const byChunk = new Map();
     rooms.forEach((room, j) => {
@@ -232,11 +240,31 @@ class RoomPoolService {
     const events = new Array(rooms.length), afters = new Array(rooms.length);
     for (const [chunk, js] of byChunk) {
       const slots = js.map((j) => rooms[j].slot);
-      const ev = chunk.stepRooms(slots, js.map((j) => rooms[j].key), js.map((j) => rooms[j].turn));
+      const ev = js.some((j) => rooms[j].playoutMask) ? this._stepPlayout(chunk, js.map((j) => rooms[j]))
+        : chunk.stepRooms(slots, js.map((j) => rooms[j].key), js.map((j) => rooms[j].turn));
       const views = chunk.readRoomsAt(slots);
       js.forEach((j, k) => { events[j] = ev[k]; afters[j] = views[k]; rooms[j].turn += 1; });
     }
     return rooms.map((room, j) => this._finish(room, afters[j], events[j], items[j]));
+  }
+  /** stepRoomsPlayout of one chunk's rooms under advise's keys and seed, in runs under the call's cap. */
+  _stepPlayout(chunk, rooms) {
+    const cost = rooms.map((r) => popcount(r.playoutMask) * playoutMaxCands(r.table.info.pack, r.pool.nPlayers) * this.playoutRollouts);
+    const parts = [];
+    let lo = 0, acc = 0;
+    cost.forEach((c, k) => {
+      if (acc + c > PLAYOUT_CAP && k > lo) { parts.push([lo, k]); lo = k; acc = 0; }
+      acc += c;
+    });
+    parts.push([lo, rooms.length]);
+    const out = [];
+    for (const [a, b] of parts) {
+      const rs = rooms.slice(a, b);
+      out.push(...chunk.stepRoomsPlayout(rs.map((r) => r.slot), rs.map((r) => r.key), rs.map((r) => r.turn), rs.map((r) => r.playoutMask),
+                                         rs.map((r) => forecastKey(r.key)), this.playoutRollouts, this.playoutMaxTurns, forecastSeed(this.seed),
+                                         this.playoutFull).events);
+    }
+    return out;
   }
   _finish(room, after, event, items) {
     // as RoomService._continue: `before` is the state before any action injected with this message

@@ -14,7 +14,11 @@ export interface AdoptOptions {
   threadId: string; gameName: string; state: AgentStateInput; players?: RoomPlayer[]; /** player ids of human seats */ humanSeats?: number[];
   dsl?: object; roomIndex?: number | bigint; /** the thread's next turn (default phase_history.length) */ turn?: number;
   /** a human seat's action already logged in this visit: {playerId: choice} */ visitActions?: Record<string, number>;
+  /** bot seats that choose each action by playouts (POLICY.md §3d) */ playoutSeats?: number[];
 }
+/** How the playout bots of threads created with playoutSeats choose (POLICY.md §3d): nRollouts (default 256) and maxTurns (256)
+ * of each candidate's playouts, from the bot's own view ("seat", the default) or the true record ("full": a cheating bot). */
+export interface PlayoutOptions { playoutRollouts?: number; playoutMaxTurns?: number; playoutView?: 'seat' | 'full'; }
 export interface TurnResult { state: AgentStateView; toolCalls: ToolCall[]; uiCalls: FrontendToolCall[]; }
 /** How a thread ends from where it stands, over `rollouts` playouts (JSON integers: divide by rollouts for odds). */
 export interface Forecast {
@@ -39,8 +43,9 @@ export interface Advice {
   view?: 'seat';
 }
 export class RoomService {
-  constructor(opts?: { gamesDir?: string; seed?: bigint | number; device?: number });
-  createRoom(opts: { threadId: string; gameName: string; players: RoomPlayer[]; dsl?: object; /** global room index the RNG is keyed by (default: hash of the thread id) */ roomIndex?: number | bigint }): AgentStateView;
+  constructor(opts?: { gamesDir?: string; seed?: bigint | number; device?: number } & PlayoutOptions);
+  createRoom(opts: { threadId: string; gameName: string; players: RoomPlayer[]; dsl?: object; /** global room index the RNG is keyed by (default: hash of the thread id) */ roomIndex?: number | bigint;
+                     /** bot seats that choose each action by playouts (POLICY.md §3d; RangeError for a human seat or an id outside 1..n) */ playoutSeats?: number[] }): AgentStateView;
   /** Take over a thread that is already mid-game (INTEGRATION.md "Handing a running thread to the stepper"): toolCalls is empty,
    *  uiCalls the UI of the phase now showing.  Throws TypeError / RangeError for a state that does not fit, before anything changes. */
   adoptRoom(opts: AdoptOptions): TurnResult;

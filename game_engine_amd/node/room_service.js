@@ -102,6 +102,25 @@ function checkForecastSeat(threadId, n, seat) {
   if (seat !== undefined && seat !== null && !(Number.isInteger(seat) && seat >= 1 && seat <= n))
     throw new RangeError(`thread ${threadId}: seat must be 1 .. ${n}`);
 }
+/** bit i = seat i+1 is a playout bot (POLICY.md §3d); a playout seat must be a bot seat 1..n (RangeError otherwise) */
+function playoutMaskOf(n, humanMask, playoutSeats) {
+  let mask = 0;
+  for (const seat of playoutSeats || []) {
+    if (!(Number.isInteger(seat) && seat >= 1 && seat <= n)) throw new RangeError(`playout seat ${seat} is not a player 1..${n}`);
+    if ((humanMask >> (seat - 1)) & 1) throw new RangeError(`playout seat ${seat} is a human seat`);
+    mask |= 1 << (seat - 1);
+  }
+  return mask;
+}
+/** the services' playout-bot options (twin of room_service.py check_playout_options); returns true for the full view */
+function checkPlayoutOptions(nRollouts, maxTurns, view) {
+  checkForecastArgs(nRollouts, maxTurns);
+  if (view !== 'full' && view !== 'seat') throw new RangeError('playoutView must be "full" or "seat"');
+  return view === 'full';
+}
+const PLAYOUT_CAP = 1 << 26;                     // stepRoomsPlayout: sum of popcount(mask) x maxCands x nRollouts per call
+/** the most candidates one playout seat can have (the call's cost unit): Werewolf n, Two-Truths max(n, 3) */
+const playoutMaxCands = (pack, n) => (pack === 1 ? n : Math.max(n, 3));
 function checkView(view) {
   if (view !== undefined && view !== 'full' && view !== 'seat') throw new RangeError('view must be "full" or "seat"');
   return view === 'seat';
@@ -182,7 +201,12 @@ function adviseOutput(table, names, threadId, turn, seat, st, cands, nRollouts, 
 }
 
 class RoomService {
-  constructor({ gamesDir = 'games', seed = 0n, device = 0 } = {}) {
+  /** playoutRollouts / playoutMaxTurns / playoutView: how the playout bots of threads created with playoutSeats choose
+   * (POLICY.md §3d): nRollouts and maxTurns of each candidate's playouts, and "seat" (from what the bot knows) or "full" (from
+   * the true record - a cheating bot in a game with people). */
+  constructor({ gamesDir = 'games', seed = 0n, device = 0, playoutRollouts = 256, playoutMaxTurns = 256, playoutView = 'seat' } = {}) {
+    this.playoutFull = checkPlayoutOptions(playoutRollouts, playoutMaxTurns, playoutView);
+    this.playoutRollouts = playoutRollouts; this.playoutMaxTurns = playoutMaxTurns;
     this.gamesDir = gamesDir; this.seed = BigInt(seed); this.device = device;
     this.tables = new Map();       // gameName -> GameTable
     this.rooms = new Map();        // threadId -> { batch, table, state, phaseHistory, playerActions, gameNotes, names }
@@ -193,9 +217,12 @@ class RoomService {
   }
   /** roomSession.players as the lobby builds it (src/app/game-library/[game]/room/page.tsx:261-369). */
   /** players[i].isBot === false marks a human seat: the bot policy never acts for it (humanAction does). */
-  createRoom({ threadId, gameName, players, dsl, roomIndex }) {
+  /** playoutSeats: bot seats that choose each action by playouts (RangeError for a human seat or an id outside 1..n, before
+   * anything is created). */
+  createRoom({ threadId, gameName, players, dsl, roomIndex, playoutSeats }) {
     const table = this.table(gameName, dsl);
     const humanMask = players.reduce((m, p, i) => (p.isBot === false ? m | (1 << i) : m), 0);
+    const playoutMask = playoutMaskOf(players.length, humanMask, playoutSeats);
     const key = roomIndex === undefined ? roomIndexOf(threadId) : BigInt(roomIndex);
     const batch = new RoomBatch({ segments: [{ table, nPlayers: players.length, nRooms: 1, humanMask }], seed: this.seed,
                                   firstRoom: key,   // the RNG is keyed by it
@@ -203,7 +230,7 @@ class RoomService {
     if (this.rooms.has(threadId)) this.close(threadId);
     const names = players.map((p, i) => p.name || `Player ${i + 1}`);
     const humanSeats = players.map((p, i) => (p.isBot === false ? i + 1 : 0)).filter((x) => x);
-    const room = { batch, key, turn: 0, table, gameName, names, humanSeats, panel: null, state: batch.readRoom(0), log: new RoomLog(table, names, gameName), queue: Promise.resolve() };
+    const room = { batch, key, turn: 0, table, gameName, names, humanSeats, playoutMask, panel: null, state: batch.readRoom(0), log: new RoomLog(table, names, gameName), queue: Promise.resolve() };
     this.rooms.set(threadId, room);
     return this.agentState(room);
   }
@@ -215,9 +242,10 @@ class RoomService {
    * { state, toolCalls: [], uiCalls } - the UI of the phase now showing, as the last turn rendered it.  A state that does not
    * fit throws (TypeError / RangeError) before anything is created or closed.
    */
-  adoptRoom({ threadId, gameName, state, players, humanSeats, dsl, roomIndex, turn, visitActions }) {
+  adoptRoom({ threadId, gameName, state, players, humanSeats, dsl, roomIndex, turn, visitActions, playoutSeats }) {
     const table = this.table(gameName, dsl);
     const a = prepareAdoption(table, { state, players, humanSeats, turn, visitActions });
+    const playoutMask = playoutMaskOf(a.n, a.humanMask, playoutSeats);
     const key = roomIndex === undefined ? roomIndexOf(threadId) : BigInt(roomIndex);
     const batch = new RoomBatch({ segments: [{ table, nPlayers: a.n, nRooms: 1, humanMask: a.humanMask }], seed: this.seed,
                                   firstRoom: key, device: this.device, maxFuse: 1, trace: true });
@@ -226,7 +254,7 @@ class RoomService {
       batch.setTurn(a.turn);
     } catch (e) { batch.close(); throw e; }
     if (this.rooms.has(threadId)) this.close(threadId);
-    const room = { batch, key, turn: a.turn, table, gameName, names: a.names, humanSeats: a.humanSeats, panel: null, state: batch.readRoom(0),
+    const room = { batch, key, turn: a.turn, table, gameName, names: a.names, humanSeats: a.humanSeats, playoutMask, panel: null, state: batch.readRoom(0),
                    log: new RoomLog(table, a.names, gameName), queue: Promise.resolve() };
     room.log.adopt(state, Object.assign({}, a.hostSide, { names: Object.fromEntries(a.names.map((nm, i) => [String(i + 1), nm])) }));
     this.rooms.set(threadId, room);
@@ -337,10 +365,18 @@ class RoomService {
     // `before` is the state BEFORE any injected action of this message: the person's record writes then show up among the
     // turn's update_player_state calls, where the reference's Referee issues them
     const before = room.state;
-    await room.batch.step(1);
+    let event;
+    if (room.playoutMask) {                            // playout bots: advise's keys and seed, so a bot's values are its advice
+      const { events } = room.batch.stepRoomsPlayout([0], [room.key], [room.turn], [room.playoutMask], [forecastKey(room.key)],
+                                                     this.playoutRollouts, this.playoutMaxTurns, forecastSeed(this.seed), this.playoutFull);
+      room.batch.setTurn(room.turn + 1);
+      event = events[0];
+    } else {
+      await room.batch.step(1);
+      event = room.batch.readEvents(0, 1)[0][0];
+    }
     room.turn += 1;
     const after = room.batch.readRoom(0);
-    const event = room.batch.readEvents(0, 1)[0][0];
     const toolCalls = turnToolCalls(room.table, before, after, event);
     // fold the calls into the log-shaped parts of AgentState the packed state does not carry
     // (playerActions / game_notes / phase_history, as backend_tools.py:163-202, 285-344 would)
@@ -375,5 +411,5 @@ class RoomService {
   }
 }
 
-module.exports = { RoomService, roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput,
+module.exports = { RoomService, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput,
                    adviseCandidates, adviseSeat, runRollouts, adviseOutput, seatForecastOutput, checkForecastSeat, checkView };

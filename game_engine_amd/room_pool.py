@@ -17,8 +17,9 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import messages as M
-from .room_service import (RolloutRequest, adopted_output, advise_candidates, advise_output, advise_seat, check_forecast_args,
-                           check_forecast_seat, check_view, prepare_adoption, room_index_of, run_rollouts, seat_forecast_output)
+from .room_service import (PLAYOUT_CAP, RolloutRequest, adopted_output, advise_candidates, advise_output, advise_seat,
+                           check_forecast_args, check_forecast_seat, check_playout_options, check_view, forecast_key, forecast_seed,
+                           playout_mask, playout_max_cands, prepare_adoption, room_index_of, run_rollouts, seat_forecast_output)
 from .stepper import GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, load_dsl_by_gamename, slot_values
 from .toolcalls import WW_IS_ALIVE, RoomLog, turn_tool_calls
 from .ui_script import ui_tool_calls
@@ -36,9 +37,13 @@ class _Pool:
 
 
 class RoomPoolService:
-    def __init__(self, games_dir: str = "games", seed: int = 0, device: int = 0, chunk_rooms: int = 1024):
+    def __init__(self, games_dir: str = "games", seed: int = 0, device: int = 0, chunk_rooms: int = 1024, playout_rollouts: int = 256,
+                 playout_max_turns: int = 256, playout_view: str = "seat"):
+        """playout_*: as RoomService's."""
         if chunk_rooms < 1:
             raise ValueError("chunk_rooms must be >= 1")
+        self.playout_full = check_playout_options(playout_rollouts, playout_max_turns, playout_view)
+        self.playout_rollouts, self.playout_max_turns = int(playout_rollouts), int(playout_max_turns)
         self.games_dir, self.seed, self.device, self.chunk_rooms = games_dir, seed, device, chunk_rooms
         self._tables: Dict[str, GameTable] = {}
         self._pools: Dict[Tuple[str, int, int], _Pool] = {}
@@ -70,11 +75,12 @@ class RoomPoolService:
         return chunk, ci, slot
 
     def create_room(self, thread_id: str, game_name: str, players: List[Dict[str, Any]], dsl: Optional[dict] = None,
-                    room_index: Optional[int] = None) -> Dict[str, Any]:
+                    room_index: Optional[int] = None, playout_seats=()) -> Dict[str, Any]:
         """As RoomService.create_room: `isBot: False` marks a human seat; room_index = the global room index the thread's RNG
-        is keyed by (default: derived from the thread id)."""
+        is keyed by (default: derived from the thread id); playout_seats = bot seats that choose by playouts."""
         tb = self.table(game_name, dsl)
         human_mask = sum(1 << i for i, p in enumerate(players) if p.get("isBot") is False)
+        pmask = playout_mask(len(players), human_mask, playout_seats)
         if thread_id in self._rooms:
             self.close(thread_id)
         key = (game_name, len(players), human_mask)
@@ -86,7 +92,7 @@ class RoomPoolService:
         room = {"pool": pool, "chunk": chunk, "ci": ci, "slot": slot, "turn": 0,
                 "key": room_index_of(thread_id) if room_index is None else int(room_index),
                 "table": tb, "gameName": game_name, "names": names, "panel": None,
-                "human_seats": [i + 1 for i in range(len(players)) if (human_mask >> i) & 1],
+                "human_seats": [i + 1 for i in range(len(players)) if (human_mask >> i) & 1], "playout_mask": pmask,
                 "view": pool.template.copy(), "log": RoomLog(tb, names, game_name)}
         self._rooms[thread_id] = room
         return self._agent_state(room)
@@ -97,7 +103,7 @@ class RoomPoolService:
 
     def adopt_rooms(self, entries: Sequence[Tuple]) -> List[Dict[str, Any]]:
         """Take over many threads that are already mid-game: [(thread_id, game_name, state[, options]), ...] with the options of
-        RoomService.adopt_room as a dict (players, human_seats, dsl, room_index, turn, visit_actions).  Every state is converted
+        RoomService.adopt_room as a dict (players, human_seats, dsl, room_index, turn, visit_actions, playout_seats).  Every state is converted
         first (ValueError, before any slot is taken); then one write_rooms_at per chunk touched.  A reused slot is written over
         directly (no template write first).  Returns, in order, what RoomService.adopt_room returns for each."""
         prepared, seen = [], set()
@@ -109,6 +115,7 @@ class RoomPoolService:
             seen.add(tid)
             tb = self.table(game, kw.get("dsl"))
             a = prepare_adoption(tb, state, kw.get("players"), kw.get("human_seats", ()), kw.get("turn"), kw.get("visit_actions"))
+            a["playout_mask"] = playout_mask(a["n"], a["human_mask"], kw.get("playout_seats", ()))
             prepared.append((tid, game, tb, state, kw, a))
         # slots next (new chunks may be created); a failure gives them back, and no thread has been touched yet
         taken: List[Tuple[_Pool, Any, int, int]] = []
@@ -139,7 +146,7 @@ class RoomPoolService:
             room = {"pool": pool, "chunk": chunk, "ci": ci, "slot": slot, "turn": a["turn"],
                     "key": room_index_of(tid) if kw.get("room_index") is None else int(kw["room_index"]),
                     "table": tb, "gameName": game, "names": a["names"], "panel": None,
-                    "human_seats": a["human_seats"], "view": view, "log": RoomLog(tb, a["names"], game)}
+                    "human_seats": a["human_seats"], "playout_mask": a["playout_mask"], "view": view, "log": RoomLog(tb, a["names"], game)}
             room["log"].adopt(state, a["host"])
             self._rooms[tid] = room
             rooms.append(room)
@@ -221,7 +228,9 @@ class RoomPoolService:
         return out
 
     def _turns(self, rooms: List[Dict[str, Any]], items: List[Optional[List[Dict[str, Any]]]]) -> List[Dict[str, Any]]:
-        """One turn of each room (distinct threads): one step_rooms and one read_rooms_at per chunk touched."""
+        """One turn of each room (distinct threads): one step_rooms and one read_rooms_at per chunk touched; a chunk holding a
+        thread with playout seats is stepped by step_rooms_playout instead (mask 0 for its other threads; more calls only when
+        the playouts would pass the call's cap)."""
         by_chunk: Dict[int, List[int]] = {}
         for j, room in enumerate(rooms):
             by_chunk.setdefault(id(room["chunk"]), []).append(j)
@@ -229,13 +238,34 @@ class RoomPoolService:
         for js in by_chunk.values():
             chunk = rooms[js[0]]["chunk"]
             slots = np.array([rooms[j]["slot"] for j in js], dtype=np.uint64)
-            ev = chunk.step_rooms(slots, np.array([rooms[j]["key"] for j in js], dtype=np.uint64),
-                                  np.array([rooms[j]["turn"] for j in js], dtype=np.uint32))
+            keys = np.array([rooms[j]["key"] for j in js], dtype=np.uint64)
+            turns = np.array([rooms[j]["turn"] for j in js], dtype=np.uint32)
+            if any(rooms[j]["playout_mask"] for j in js):
+                ev = self._step_playout(chunk, [rooms[j] for j in js], slots, keys, turns)
+            else:
+                ev = chunk.step_rooms(slots, keys, turns)
             views = chunk.read_rooms_at(slots)
             for k, j in enumerate(js):
                 events[j], afters[j] = ev[k], views[k]
                 rooms[j]["turn"] += 1
         return [self._finish(room, afters[j], events[j], items[j]) for j, room in enumerate(rooms)]
+
+    def _step_playout(self, chunk, rooms: List[Dict[str, Any]], slots, keys, turns) -> np.ndarray:
+        """step_rooms_playout of one chunk's rooms under advise's keys and seed, in runs under the call's cap."""
+        masks = np.array([r["playout_mask"] for r in rooms], dtype=np.uint32)
+        pkeys = np.array([forecast_key(r["key"]) for r in rooms], dtype=np.uint64)
+        cost = [bin(int(m)).count("1") * playout_max_cands(r["table"].pack, r["pool"].n_players) * self.playout_rollouts
+                for m, r in zip(masks, rooms)]
+        parts, lo, acc = [], 0, 0
+        for k, c in enumerate(cost):
+            if acc + c > PLAYOUT_CAP and k > lo:
+                parts.append((lo, k)); lo, acc = k, 0
+            acc += c
+        parts.append((lo, len(rooms)))
+        evs = [chunk.step_rooms_playout(slots[a:b], keys[a:b], turns[a:b], masks[a:b], pkeys[a:b], self.playout_rollouts,
+                                        self.playout_max_turns, seed=forecast_seed(self.seed), full_view=self.playout_full)[0]
+               for a, b in parts]
+        return np.concatenate(evs)
 
     def _finish(self, room: Dict[str, Any], after, event, items) -> Dict[str, Any]:
         # as RoomService._turn: `before` is the view before any action injected with this message

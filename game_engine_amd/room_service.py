@@ -93,6 +93,32 @@ def forecast_seed(seed: int) -> int:
     return (int(seed) ^ FORECAST_SEED_XOR) & 0xFFFFFFFFFFFFFFFF
 
 
+def playout_mask(n_players: int, human_mask: int, playout_seats) -> int:
+    """Bit i = seat i+1 is a playout bot (POLICY.md §3d).  A playout seat must be a bot seat 1..n (ValueError otherwise)."""
+    mask = 0
+    for seat in playout_seats or ():
+        if not 1 <= int(seat) <= n_players:
+            raise ValueError(f"playout seat {seat} is not a player 1..{n_players}")
+        if (human_mask >> (int(seat) - 1)) & 1:
+            raise ValueError(f"playout seat {seat} is a human seat")
+        mask |= 1 << (int(seat) - 1)
+    return mask
+
+
+def check_playout_options(n_rollouts: int, max_turns: int, view: str) -> bool:
+    """The services' playout-bot options; returns True for the full view."""
+    check_forecast_args(n_rollouts, max_turns)
+    return not check_view(view)
+
+
+PLAYOUT_CAP = 1 << 26                       # ge_batch_step_rooms_playout: sum of popcount(mask) x max_cands x n_rollouts per call
+
+
+def playout_max_cands(pack: int, n_players: int) -> int:
+    """The most candidates one playout seat can have (the call's cost unit): Werewolf n, Two-Truths max(n, 3)."""
+    return n_players if pack == PACK_WEREWOLF else max(n_players, 3)
+
+
 def check_forecast_args(n_rollouts: int, max_turns: int) -> None:
     if not 1 <= int(n_rollouts) <= FORECAST_MAX_ROLLOUTS:
         raise ValueError(f"n_rollouts must be 1 .. {FORECAST_MAX_ROLLOUTS} (replica keys are thread_key << 16 + r)")
@@ -236,7 +262,13 @@ def advise_output(table: GameTable, names: List[str], thread_id: str, turn: int,
 
 
 class RoomService:
-    def __init__(self, games_dir: str = "games", seed: int = 0, device: int = 0):
+    def __init__(self, games_dir: str = "games", seed: int = 0, device: int = 0, playout_rollouts: int = 256,
+                 playout_max_turns: int = 256, playout_view: str = "seat"):
+        """playout_*: how the playout bots of threads created with playout_seats choose (POLICY.md §3d): n_rollouts and
+        max_turns of each candidate's playouts, and "seat" (from what the bot knows) or "full" (from the true record - a
+        cheating bot in a game with people)."""
+        self.playout_full = check_playout_options(playout_rollouts, playout_max_turns, playout_view)
+        self.playout_rollouts, self.playout_max_turns = int(playout_rollouts), int(playout_max_turns)
         self.games_dir, self.seed, self.device = games_dir, seed, device
         self._tables: Dict[str, GameTable] = {}
         self._rooms: Dict[str, Dict[str, Any]] = {}
@@ -247,26 +279,29 @@ class RoomService:
         return self._tables[game_name]
 
     def create_room(self, thread_id: str, game_name: str, players: List[Dict[str, Any]], dsl: Optional[dict] = None,
-                    room_index: Optional[int] = None) -> Dict[str, Any]:
+                    room_index: Optional[int] = None, playout_seats=()) -> Dict[str, Any]:
         """players: roomSession.players as the lobby builds it; `isBot: False` marks a human seat, which
         the bot policy never acts for (bot_behavior_system_prompt.txt:3) — use human_action for it.
-        room_index: the global room index the RNG is keyed by (default: derived from the thread id)."""
+        room_index: the global room index the RNG is keyed by (default: derived from the thread id).
+        playout_seats: bot seats that choose each action by playouts (POLICY.md §3d; ValueError for a human seat or an id
+        outside 1..n, before anything is created)."""
         tb = self.table(game_name, dsl)
         human_mask = sum(1 << i for i, p in enumerate(players) if p.get("isBot") is False)
+        pmask = playout_mask(len(players), human_mask, playout_seats)
         key = room_index_of(thread_id) if room_index is None else int(room_index)
         batch = self._new_batch(tb, len(players), human_mask, key)
         if thread_id in self._rooms:
             self.close(thread_id)
         names = [p.get("name") or f"Player {i + 1}" for i, p in enumerate(players)]
         room = {"batch": batch, "key": key, "table": tb, "gameName": game_name, "names": names, "panel": None,
-                "human_seats": [i + 1 for i in range(len(players)) if (human_mask >> i) & 1],
+                "human_seats": [i + 1 for i in range(len(players)) if (human_mask >> i) & 1], "playout_mask": pmask,
                 "view": batch.read_rooms(0, 1)[0], "log": RoomLog(tb, names, game_name)}
         self._rooms[thread_id] = room
         return self._agent_state(room)
 
     def adopt_room(self, thread_id: str, game_name: str, state: Dict[str, Any], players: Optional[List[Dict[str, Any]]] = None,
                    human_seats=(), dsl: Optional[dict] = None, room_index: Optional[int] = None, turn: Optional[int] = None,
-                   visit_actions: Optional[Dict[Any, int]] = None) -> Dict[str, Any]:
+                   visit_actions: Optional[Dict[Any, int]] = None, playout_seats=()) -> Dict[str, Any]:
         """Take over a thread that is already mid-game: `state` is its AgentState (current_phase_id, player_states, playerActions,
         phase_history, game_notes - what update_complete_player_states replaces wholesale in the reference).  The room continues
         from it exactly as the thread would have gone on.  players (optional, roomSession.players): `isBot: False` marks a human
@@ -274,9 +309,11 @@ class RoomService:
         len(phase_history), one entry per run); visit_actions={player_id: choice}: a human seat's action already logged in this
         visit (see stepper.agent_state_to_view).  Returns {"state", "toolCalls": [], "uiCalls"}: the UI of the phase now showing,
         rendered for the last turn, so that a person's next vote resolves against the panel the thread showed.
-        A state that does not fit raises ValueError before anything is created."""
+        A state that does not fit raises ValueError before anything is created, as do playout_seats (see create_room) that
+        are not bot seats."""
         tb = self.table(game_name, dsl)
         a = prepare_adoption(tb, state, players, human_seats, turn, visit_actions)
+        pmask = playout_mask(a["n"], a["human_mask"], playout_seats)
         key = room_index_of(thread_id) if room_index is None else int(room_index)
         batch = self._new_batch(tb, a["n"], a["human_mask"], key)
         try:
@@ -289,7 +326,7 @@ class RoomService:
         if thread_id in self._rooms:                      # only now: a refused state leaves an existing thread of this id alone
             self.close(thread_id)
         room = {"batch": batch, "key": key, "table": tb, "gameName": game_name, "names": a["names"], "panel": None,
-                "human_seats": a["human_seats"], "view": view, "log": RoomLog(tb, a["names"], game_name)}
+                "human_seats": a["human_seats"], "playout_mask": pmask, "view": view, "log": RoomLog(tb, a["names"], game_name)}
         room["log"].adopt(state, a["host"])
         self._rooms[thread_id] = room
         return adopted_output(room, a["turn"])
@@ -351,9 +388,17 @@ class RoomService:
         # `before` is the view BEFORE any injected action of this message: the person's record writes (night target, vote
         # choice, ...) then show up among the turn's update_player_state calls, where the reference's Referee issues them
         batch, before = room["batch"], room["view"]
-        batch.step(1)
+        if room["playout_mask"]:                            # playout bots: advise's keys and seed, so a bot's values are its advice
+            turn = batch.turn
+            ev, _ = batch.step_rooms_playout([0], [room["key"]], [turn], [room["playout_mask"]], [forecast_key(room["key"])],
+                                             self.playout_rollouts, self.playout_max_turns, seed=forecast_seed(self.seed),
+                                             full_view=self.playout_full)
+            batch.set_turn(turn + 1)
+            event = ev[0]
+        else:
+            batch.step(1)
+            event = batch.read_events(0, 1)[0][0]
         after = batch.read_rooms(0, 1)[0]
-        event = batch.read_events(0, 1)[0][0]
         calls = turn_tool_calls(room["table"], before, after, event)
         room["log"].fold(calls, after)                      # playerActions / game_notes / phase_history, as bt:163-202, 285-344 would
         room["view"] = after

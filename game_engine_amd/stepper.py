@@ -289,6 +289,32 @@ class RoomBatch:
                                              out.ctypes.data), "ge_batch_step_rooms")
         return out
 
+    def step_rooms_playout(self, rooms, keys, turns, masks, playout_keys, n_rollouts: int, max_turns: int = 256,
+                           seed: Optional[int] = None, full_view: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """step_rooms with playout seats (POLICY.md §3d): bit i of masks[k] makes seat i+1 of room k a playout bot.  Such a seat,
+        when the policy has it act in this turn with at least 2 candidates, takes the candidate whose rollout_seats entry
+        (room k as it stands, playout_keys[k], turns[k], the seat - or 0 with full_view -, that one action, n_rollouts,
+        max_turns, seed) has the highest seat_wins of the seat; ties go to the policy's own pick among the tied.  Returns
+        (events, decided): events as step_rooms (the decided seats listed as acted), decided[k] bit i = seat i+1 chose by
+        playouts.  seed None: the batch's seed.  All-or-nothing (GeError, nothing run): step_rooms's checks, rollout_seats's
+        caps, a mask bit at or above the room's player count or on a host-driven seat, or sum of popcount(mask) x n_players x
+        n_rollouts over the rooms above 2^26."""
+        rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        turns = np.ascontiguousarray(turns, dtype=np.uint32)
+        masks = np.ascontiguousarray(masks, dtype=np.uint32)
+        pkeys = np.ascontiguousarray(playout_keys, dtype=np.uint64)
+        if not (len(rooms) == len(keys) == len(turns) == len(masks) == len(pkeys)):
+            raise GeError(-1, "step_rooms_playout: arrays differ in length")
+        events = np.zeros(len(rooms), dtype=EVENT_DTYPE)
+        decided = np.zeros(len(rooms), dtype=np.uint32)
+        flags = 1 if full_view else 0                            # GE_PLAYOUT_FULL_VIEW
+        _check(self._lib.ge_batch_step_rooms_playout(self._h, len(rooms), rooms.ctypes.data, keys.ctypes.data, turns.ctypes.data,
+                                                     masks.ctypes.data, pkeys.ctypes.data, n_rollouts, max_turns,
+                                                     self._seed if seed is None else seed, flags, events.ctypes.data,
+                                                     decided.ctypes.data), "ge_batch_step_rooms_playout")
+        return events, decided
+
     def read_rooms_at(self, rooms) -> np.ndarray:
         """Canonical views of the listed rooms, out[k] = room rooms[k] (any order, repeats allowed)."""
         rooms = np.ascontiguousarray(rooms, dtype=np.uint64)

@@ -42,7 +42,8 @@ extern "C" {
  *      in one resident batch, each room stepped under its own key and turn); ge_batch_write_rooms_at (the indexed write);
  *      ge_batch_rollout_rooms + ge_rollout_stats (on-device playouts of listed rooms: win odds per side and per seat);
  *      ge_batch_rollout_actions (playouts that start from given actions: win odds per choice a seat can make now);
- *      ge_batch_rollout_seats (the same playouts from what one seat knows: hidden roles / the lie dealt again per replica) */
+ *      ge_batch_rollout_seats (the same playouts from what one seat knows: hidden roles / the lie dealt again per replica);
+ *      ge_batch_step_rooms_playout + GE_PLAYOUT_FULL_VIEW (playout seats: bots that choose each action by their own playouts) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -373,6 +374,25 @@ int ge_batch_rollout_seats(ge_batch *b, uint64_t n, const uint64_t *rooms, const
                            const uint32_t *seats /* n */, const uint32_t *first_action /* n + 1, may be NULL: no actions */,
                            const uint32_t *player_ids, const uint32_t *choices, int32_t *entry_status /* may be NULL */,
                            uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, ge_rollout_stats *out);
+
+/* Playout seats (POLICY.md §3d): ge_batch_step_rooms with some bot seats choosing their action by playouts.  Room k is stepped
+ * as ge_batch_step_rooms's entry (rooms[k], keys[k], turns[k]), except that every seat s of playout_masks[k] (bit i = seat
+ * i+1) that the policy would make act in this turn, with at least 2 candidates, takes the candidate with the highest
+ * seat_wins[s-1] of ge_batch_rollout_seats's entry (room k at node entry, playout_keys[k], turns[k], seat s - or 0 under
+ * GE_PLAYOUT_FULL_VIEW -, actions [(s, c)], n_rollouts, max_turns, seed); a tie goes to the pick(d, m)-th of the m tied
+ * candidates, d being the seat's own draw, so a full tie is the policy's own choice.  The chosen actions are logged as
+ * ge_batch_inject_actions logs them, then the turn is played; events[k] lists them as acted in the turn.  No decision is made
+ * in a turn that starts from a terminal phase under GE_FLAG_RESTART, takes the phase-0 guard, or whose phase's completion is not
+ * player_action.  decided[k] (may be NULL): bit i = seat i+1's action was chosen by playouts.  Unlisted rooms, the turn
+ * counter and the GE_FLAG_TRACE buffer are untouched.  All-or-nothing, nothing runs on an error: ge_batch_step_rooms's checks;
+ * GE_ERR_ARG for NULL masks / playout keys with n > 0, unknown flags, n_rollouts == 0 or > 2^20, max_turns > 4096, a mask bit
+ * at or above the room's player count or on a host-driven seat of its segment, or sum_k popcount(mask_k) * c_k * n_rollouts >
+ * 2^26, c_k = the most candidates a seat of room k can have (Werewolf: n_players, Two-Truths: max(n_players, 3)); GE_ERR_RANGE for turns[k] + max_turns > 0xFFFFFFFF.  Ordered behind the previous step; synchronises. */
+#define GE_PLAYOUT_FULL_VIEW 1u   /* value candidates from the true record (seat 0) instead of the seat's view */
+int ge_batch_step_rooms_playout(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
+                                const uint32_t *playout_masks /* n: bit i = seat i+1 */, const uint64_t *playout_keys /* n */,
+                                uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, uint32_t flags,
+                                ge_turn_event *events /* n, may be NULL */, uint32_t *decided /* n, may be NULL */);
 
 /* GE_FLAG_TRACE: events of the most recent ge_batch_step call, dst[(room - first) * *n_turns + t].
  * cap_bytes >= count * n_turns * sizeof(ge_turn_event).  Synchronises. */

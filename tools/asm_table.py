@@ -40,6 +40,9 @@ def describe(mangled: str) -> dict:
     if m:
         return {"kernel": "ge_rollout_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True,
                 "act": int(m.group(3) or 0)}
+    m = re.search(r"ge_playout_(plan|decide)ILi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_playout_" + m.group(1), "layout": KINDS[int(m.group(2))], "lowocc": False, "generic": False, "single": True}
     m = re.search(r"N_1\d+(ge_[a-z_0-9]+?)E", mangled)
     return {"kernel": m.group(1) if m else mangled, "layout": "-", "lowocc": False, "generic": False, "single": False}
 
@@ -74,6 +77,8 @@ def label(r):
         return f"{r['layout']}, playouts after actions (ge_batch_rollout_actions)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_rollout_kernel":                       # ge_batch_rollout_rooms: one launch per segment present
         return f"{r['layout']}, playouts (ge_batch_rollout_rooms)" + (", GENERIC" if r["generic"] else "")
+    if r["kernel"] in ("ge_playout_plan", "ge_playout_decide"):  # ge_batch_step_rooms_playout: one launch per unit of rooms
+        return f"{r['layout']}, playout seats, {r['kernel'][11:]} (ge_batch_step_rooms_playout)"
     if r["kernel"] not in ("ge_step_kernel", "ge_step_kernel_mixed"):
         return r["kernel"]
     form = "single-turn" if r["single"] else "fused"
