@@ -42,6 +42,11 @@
 // compare-exchange network, the wolf count still to place - is wave-uniform.  Per lane: at most 2 x NB picks (n-th set bit of
 // a shrinking mask, every count uniform) and, per tuple, its bits shifted from its uniform source seat to the lane's
 // destination seat in a few 64-bit bundles of bit-planes (no array indexed by seat: no scratch).  seats[e] = 0 skips it.
+//
+// Playouts that keep their outcome (ge_batch_rollout_compare, ACT = 3; ge_compare.inl).  Everything ACT = 2 does; then each lane
+// stores the outcome X of its replica for seat subjects[e] - Werewolf: the seat's team has won, Two-Truths: the seat's
+// total_score - as one byte of the entry's row of the outcome plane (waves * 64 bytes per row: a wavefront's lanes write 64
+// consecutive bytes; a lane past R writes 0).  A refused entry writes nothing: its row is never read.
 
 namespace {
 
@@ -68,6 +73,11 @@ template <> struct RollArgs<0> : RolloutArgs {};
 // ACT = 2: the actions, then the view of seat seats[e] (1-based; 0 = the full view)
 template <> struct RollArgs<2> : RollArgs<1> {
     const uint32_t *seats;
+};
+// ACT = 3: the same, and the outcome of every replica for seat subjects[e] (1-based) into row e of the outcome plane
+template <> struct RollArgs<3> : RollArgs<2> {
+    const uint32_t *subjects;
+    unsigned char *plane;           // [n] rows of waves * 64 bytes
 };
 
 struct RollLane {
@@ -124,6 +134,11 @@ __device__ __forceinline__ uint64_t roll_ck(uint32_t h_words) {
     return (uint64_t)h_words | ((uint64_t)mix32(h_words ^ 0x5BD1E995u) << 32);
 }
 __device__ __forceinline__ uint32_t roll_h0(uint64_t g) { return mix32((uint32_t)g ^ mix32((uint32_t)(g >> 32) ^ 0xA5A5A5A5u)); }
+
+// the replica's outcome byte into the entry's row of the outcome plane (ACT = 3): lane r_in of the entry, a plain vector store
+__device__ __forceinline__ void roll_keep(const RollArgs<3> &a, uint32_t e, uint32_t r_in, uint32_t x) {
+    a.plane[(size_t)e * ((size_t)a.waves * 64u) + r_in] = (unsigned char)x;
+}
 
 // the entry's actions logged in its source record (ACT = 1 prologue); false (wave-uniform) = refused, status[e] written
 __device__ __forceinline__ bool roll_refuse(const RollArgs<1> &a, uint32_t e, uint32_t r_in, int st) {
@@ -299,7 +314,7 @@ __device__ __forceinline__ void roll_ww(const SegDev &sg, const DevTable *__rest
         if (!roll_act_ww<NB>(sg, tables, a, e, r_in, w)) return;
     const uint64_t g = key + r;
     const uint32_t rk = room_key_from(a.seed_key, g);
-    if constexpr (ACT == 2) roll_view_ww<NB>(sg, tables, a, e, rk, turn0, w);
+    if constexpr (ACT >= 2) roll_view_ww<NB>(sg, tables, a, e, rk, turn0, w);
     const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
     const DevRow *rows = reinterpret_cast<const DevRow *>(img);
     const CondShape cs = GENERIC ? pool_cond_shape(tables[sg.table_idx]) : CondShape{0u, 0u, 0u, 0u, 0u};
@@ -332,6 +347,10 @@ __device__ __forceinline__ void roll_ww(const SegDev &sg, const DevTable *__rest
     uint32_t score[NB];
 #pragma unroll
     for (int i = 0; i < NB; i++) score[i] = 0u;
+    if constexpr (ACT == 3) {
+        const uint32_t subj = (uint32_t)__builtin_amdgcn_readfirstlane(a.subjects[e]) - 1u;
+        roll_keep(a, e, r_in, valid ? (l.win_mask >> subj) & 1u : 0u);
+    }
     roll_reduce<NB>(l, valid, score, part, h_end, h_score, a.acc + (size_t)e * ROLL_STRIDE);
 }
 
@@ -357,7 +376,7 @@ __device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__rest
     L::unpack(w, s);
     if constexpr (ACT != 0)
         if (!roll_act_tt<NB>(sg, tables, a, e, r_in, s)) return;
-    if constexpr (ACT == 2) {
+    if constexpr (ACT >= 2) {
         const uint32_t seat = (uint32_t)__builtin_amdgcn_readfirstlane(a.seats[e]);
         if (seat != 0u) view_redeal_tt<NB>(s, seat, view_key(rk, turn0));
     }
@@ -390,6 +409,13 @@ __device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__rest
         l.q = RoomStats{0, 0, 0, 0, 0, 0}; l.ck = 0;
 #pragma unroll
         for (int i = 0; i < NB; i++) score[i] = 0u;
+    }
+    if constexpr (ACT == 3) {
+        const uint32_t subj = (uint32_t)__builtin_amdgcn_readfirstlane(a.subjects[e]) - 1u;
+        uint32_t x = 0;
+#pragma unroll
+        for (int i = 0; i < NB; i++) x = (uint32_t)i == subj ? score[i] : x;   // static indices: no scratch
+        roll_keep(a, e, r_in, x);
     }
     roll_reduce<NB>(l, valid, score, part, h_end, h_score, a.acc + (size_t)e * ROLL_STRIDE);
 }
@@ -436,7 +462,8 @@ uint32_t rollout_settle_mask(const Segment &sg) {
 }  // namespace
 
 // one call of the three entry points.  first_action null: every entry's slice is empty; seats null: the full view.  act is the
-// kernel form the call launches: 0 = ge_batch_rollout_rooms, 1 = ge_batch_rollout_actions, 2 = ge_batch_rollout_seats
+// kernel form the call launches: 0 = ge_batch_rollout_rooms, 1 = ge_batch_rollout_actions, 2 = ge_batch_rollout_seats,
+// 3 = ge_batch_rollout_compare (ge_compare.inl; baseline / subjects / cmp are its own)
 struct RollRequest {
     uint64_t n;
     const uint64_t *rooms, *keys;
@@ -446,14 +473,22 @@ struct RollRequest {
     uint64_t seed;
     ge_rollout_stats *out;
     int act;
+    const uint32_t *baseline = nullptr, *subjects = nullptr;
+    ge_compare_stats *cmp = nullptr;
 };
 
 // one chunk's staging: the upload [rooms u64 x cn][keys u64 x cn][turns u32 x cn]; with actions [first u32 x (cn + 1)]
 // [players u32 x na][choices u32 x na], with seats [seats u32 x cn]; each array from a 16 B boundary.  Then the download:
-// [status i32 x cn] (with actions), the accumulators 8 B x ROLL_STRIDE x cn
+// [status i32 x cn] (with actions), the accumulators 8 B x ROLL_STRIDE x cn.  A comparing call (act 3) uploads [subjects u32 x cn]
+// [baseline u32 x cn] (sorted positions) behind the seats and downloads [ge_compare_stats x cn] behind the accumulators; its
+// outcome plane lies behind `total` on the device only (dev_total), so the pinned host buffer does not grow by it
 struct RollStage {
     size_t keys, turns, first, players, choices, seats, status, acc, total;
+    size_t subjects, baseline, cmp, plane, dev_total;
 };
+
+// ge_compare.inl: the paired sums of a comparing call's chunk staged at dev, behind its playouts on stream s
+static hipError_t compare_launch(hipStream_t s, char *dev, const RollStage &o, uint32_t cn, uint32_t n_rollouts, uint32_t waves);
 
 // segment g's entries [lo, lo + cnt) of the chunk staged at dev, as form ACT
 template <int ACT>
@@ -466,7 +501,11 @@ hipError_t rollout_launch_form(const ge_batch *b, hipStream_t s, const RolloutAr
         a.choices = reinterpret_cast<const uint32_t *>(dev + o.choices);
         a.status = reinterpret_cast<int32_t *>(dev + o.status) + lo;
     }
-    if constexpr (ACT == 2) a.seats = reinterpret_cast<const uint32_t *>(dev + o.seats) + lo;
+    if constexpr (ACT >= 2) a.seats = reinterpret_cast<const uint32_t *>(dev + o.seats) + lo;
+    if constexpr (ACT == 3) {
+        a.subjects = reinterpret_cast<const uint32_t *>(dev + o.subjects) + lo;
+        a.plane = reinterpret_cast<unsigned char *>(dev + o.plane) + (size_t)lo * ((size_t)base.waves * 64u);
+    }
     const dim3 grid(base.n * base.waves);                   // <= 2^26 blocks (n * R <= 2^26)
     const uint32_t kind = b->segs[base.seg].dev.kind;
     return b->generic ? rollout_launch<1, ACT>(kind, grid, s, b, a) : rollout_launch<0, ACT>(kind, grid, s, b, a);
@@ -476,7 +515,7 @@ static int rollout_rooms_impl(ge_batch *b, const RollRequest &r) {
     GE_ON_DEVICE(b);
     int st = sync_impl(b);
     if (st != GE_OK) return st;
-    const bool act = r.act >= 1, view = r.act == 2;
+    const bool act = r.act >= 1, view = r.act >= 2, cmp = r.act == 3;
     const uint32_t n_seg = (uint32_t)b->segs.size();
     const uint32_t waves = (r.n_rollouts + 63u) / 64u;
     const uint32_t seed_k = seed_key((uint32_t)r.seed, (uint32_t)(r.seed >> 32));
@@ -501,10 +540,15 @@ static int rollout_rooms_impl(ge_batch *b, const RollRequest &r) {
         o.keys = 8 * (size_t)cn; o.turns = 16 * (size_t)cn;
         o.first = up16(o.turns + 4 * (size_t)cn); o.players = up16(o.first + (act ? 4 * ((size_t)cn + 1u) : 0u));
         o.choices = up16(o.players + 4 * (size_t)na); o.seats = up16(o.choices + 4 * (size_t)na);
-        o.status = up16(o.seats + (view ? 4 * (size_t)cn : 0u));
+        o.subjects = up16(o.seats + (view ? 4 * (size_t)cn : 0u));
+        o.baseline = up16(o.subjects + (cmp ? 4 * (size_t)cn : 0u));
+        o.status = up16(o.baseline + (cmp ? 4 * (size_t)cn : 0u));
         o.acc = act ? up16(o.status + 4 * (size_t)cn) : o.first;
         const size_t acc_bytes = 8 * (size_t)ROLL_STRIDE * cn;
-        o.total = o.acc + acc_bytes;
+        o.cmp = o.acc + acc_bytes;
+        o.total = o.cmp + (cmp ? sizeof(ge_compare_stats) * (size_t)cn : 0u);
+        o.plane = (o.total + 255u) & ~(size_t)255u;
+        o.dev_total = cmp ? o.plane + (size_t)cn * waves * 64u : o.total;
         uint32_t *host32 = nullptr;
         if ((st = io_stage(b, o.total, &host32)) != GE_OK) return st;
         unsigned char *host = reinterpret_cast<unsigned char *>(host32);
@@ -531,10 +575,16 @@ static int rollout_rooms_impl(ge_batch *b, const RollRequest &r) {
                 uint32_t *h_seat = reinterpret_cast<uint32_t *>(host + o.seats);
                 for (uint32_t i = 0; i < cn; i++) h_seat[i] = r.seats[c0 + order[i]];
             }
+            if (cmp) {                                        // the baselines follow the sort: input index -> sorted position
+                uint32_t *h_subj = reinterpret_cast<uint32_t *>(host + o.subjects), *h_base = reinterpret_cast<uint32_t *>(host + o.baseline);
+                std::vector<uint32_t> pos(cn);
+                for (uint32_t i = 0; i < cn; i++) pos[order[i]] = i;
+                for (uint32_t i = 0; i < cn; i++) { h_subj[i] = r.subjects[c0 + order[i]]; h_base[i] = pos[r.baseline[c0 + order[i]]]; }
+            }
             memset(host + o.status, 0, 4 * (size_t)cn);         // GE_OK unless the device refuses the entry
         }
         char *dev = nullptr;
-        if ((st = pool_scratch(b, o.total, &dev)) != GE_OK) return st;
+        if ((st = pool_scratch(b, o.dev_total, &dev)) != GE_OK) return st;
         hipStream_t s = b->last_stream;
         if ((st = order_after_previous(b, s)) != GE_OK) return st;
         HIP_TRY(hipMemcpyAsync(dev, host, o.acc, hipMemcpyHostToDevice, s));
@@ -550,9 +600,11 @@ static int rollout_rooms_impl(ge_batch *b, const RollRequest &r) {
             a.n = cnt; a.seg = g; a.seed_key = seed_k; a.n_rollouts = r.n_rollouts; a.max_turns = r.max_turns; a.waves = waves;
             a.settle_mask = settle[g];
             HIP_TRY((r.act == 0 ? rollout_launch_form<0>(b, s, a, dev, o, lo)
+                     : cmp      ? rollout_launch_form<3>(b, s, a, dev, o, lo)
                      : view     ? rollout_launch_form<2>(b, s, a, dev, o, lo)
                                 : rollout_launch_form<1>(b, s, a, dev, o, lo)));
         }
+        if (cmp) HIP_TRY(compare_launch(s, dev, o, cn, r.n_rollouts, waves));   // behind every segment's playouts, over the whole chunk
         const size_t off_down = act ? o.status : o.acc;
         const int32_t *h_st = reinterpret_cast<const int32_t *>(host + o.status);
         const unsigned long long *h_acc = reinterpret_cast<const unsigned long long *>(host + o.acc);
@@ -568,6 +620,7 @@ static int rollout_rooms_impl(ge_batch *b, const RollRequest &r) {
         }
         for (uint32_t i = 0; i < cn; i++) {                      // scattered back into input order
             const uint64_t k = c0 + order[i];
+            if (cmp) memcpy(&r.cmp[k], host + o.cmp + sizeof(ge_compare_stats) * (size_t)i, sizeof(ge_compare_stats));
             if (act && h_st[i] != GE_OK) continue;               // a refused entry's record is left as it is
             const unsigned long long *h = h_acc + (size_t)ROLL_STRIDE * i;
             ge_rollout_stats &out = r.out[k];
@@ -594,7 +647,7 @@ static int rollout_call(ge_batch *b, const RollRequest &r) {
     if (r.n == 0) return GE_OK;
     const uint64_t n = r.n;
     if (!r.rooms || !r.keys || !r.turns || !r.out) return GE_ERR_ARG;
-    if ((r.act == 1 && !r.first_action) || (r.act == 2 && !r.seats) || (r.first_action && (!r.players || !r.choices))) return GE_ERR_ARG;
+    if ((r.act == 1 && !r.first_action) || (r.act >= 2 && !r.seats) || (r.first_action && (!r.players || !r.choices))) return GE_ERR_ARG;
     if (r.n_rollouts == 0 || r.n_rollouts > (1u << 20) || n > (1ull << 26) || n * (uint64_t)r.n_rollouts > (1ull << 26) || r.max_turns > 4096u)
         return GE_ERR_ARG;
     if (r.first_action) {
@@ -607,6 +660,15 @@ static int rollout_call(ge_batch *b, const RollRequest &r) {
     if (r.seats)
         for (uint64_t k = 0; k < n; k++)                      // (rooms[k] is in range: its segment is known)
             if (r.seats[k] > b->segs[pool_segment_of(b, r.rooms[k])].dev.n_players) return GE_ERR_ARG;
+    if (r.act == 3) {                                         // ge_batch_rollout_compare's own, behind ge_batch_rollout_seats's
+        if (!r.baseline || !r.subjects || !r.cmp || n > 65536u) return GE_ERR_ARG;   // one staging chunk: an entry and its baseline are resident together
+        for (uint64_t k = 0; k < n; k++)
+            if (r.baseline[k] >= n) return GE_ERR_ARG;
+        for (uint64_t k = 0; k < n; k++)
+            if (r.rooms[r.baseline[k]] != r.rooms[k]) return GE_ERR_ARG;
+        for (uint64_t k = 0; k < n; k++)
+            if (r.subjects[k] == 0u || r.subjects[k] > b->segs[pool_segment_of(b, r.rooms[k])].dev.n_players) return GE_ERR_ARG;
+    }
     return guarded([&] { return rollout_rooms_impl(b, r); });
 }
 

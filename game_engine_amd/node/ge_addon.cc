@@ -532,13 +532,16 @@ bool is_nullish(napi_env env, napi_value v) {
 // (rooms.length + 1) | null, playerIds: Uint32Array | null, choices: Uint32Array | null, nRollouts, maxTurns, seed: bigint):
 // { words: BigUint64Array of rooms.length x 77 (ge_rollout_stats k at [77 k, 77 k + 77)), status: Int32Array of rooms.length } -
 // index.js's rolloutRooms / rolloutActions / rolloutSeats: ge_batch_rollout_seats with seats, else ge_batch_rollout_actions with
-// actions, else ge_batch_rollout_rooms.  A refused entry's words are 0 and its status < 0
+// actions, else ge_batch_rollout_rooms.  A refused entry's words are 0 and its status < 0.  Two more arguments, baseline and
+// subjects (Uint32Array of rooms.length each, with seats): index.js's rolloutCompare, ge_batch_rollout_compare; the result gains
+// cmp: BigUint64Array of rooms.length x 6 (ge_compare_stats k at [6 k, 6 k + 6))
 napi_value Rollout(napi_env env, napi_callback_info info) {
-    size_t argc = 11;
-    napi_value argv[11];
+    size_t argc = 13;
+    napi_value argv[13];
     NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
     const bool seats = argc > 4 && !is_nullish(env, argv[4]), acts = argc > 5 && !is_nullish(env, argv[5]);
-    const char *what = seats ? "rolloutSeats" : acts ? "rolloutActions" : "rolloutRooms";
+    const bool compare = argc > 12 && !is_nullish(env, argv[11]) && !is_nullish(env, argv[12]);
+    const char *what = compare ? "rolloutCompare" : seats ? "rolloutSeats" : acts ? "rolloutActions" : "rolloutRooms";
     ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
     if (!b || argc < 11) return throw_status(env, GE_ERR_ARG, what);
     // rooms, keys, turns, then seats and firstAction, playerIds, choices where given
@@ -563,11 +566,33 @@ napi_value Rollout(napi_env env, napi_callback_info info) {
                                       "at the length of the Uint32Array players and choices"
                                     : "BigUint64Array x 2, Uint32Array (turns) of equal length; Uint32Array offsets (length + 1) ending at the "
                                       "length of the Uint32Array players and choices");
+    const uint32_t *base = nullptr, *subj = nullptr;
+    if (compare) {
+        napi_typedarray_type ct[2];
+        size_t cl[2];
+        void *cd[2];
+        for (int k = 0; k < 2; k++) {
+            napi_value ab;
+            size_t off;
+            if (napi_get_typedarray_info(env, argv[11 + k], &ct[k], &cl[k], &cd[k], &ab, &off) != napi_ok)
+                return throw_status(env, GE_ERR_ARG, what, "typed arrays expected");
+        }
+        if (!seats || ct[0] != napi_uint32_array || ct[1] != napi_uint32_array || cl[0] != len[0] || cl[1] != len[0])
+            return throw_status(env, GE_ERR_ARG, what, "seats, baseline, subjects: Uint32Array of the entries' length");
+        base = static_cast<const uint32_t *>(cd[0]);
+        subj = static_cast<const uint32_t *>(cd[1]);
+    }
     uint32_t n_rollouts = 0, max_turns = 0;
     uint64_t seed = 0;
     if (napi_get_value_uint32(env, argv[8], &n_rollouts) != napi_ok || napi_get_value_uint32(env, argv[9], &max_turns) != napi_ok ||
         !get_u64(env, argv[10], &seed))
         return throw_status(env, GE_ERR_ARG, what, "nRollouts, maxTurns: numbers; seed: bigint");
+    void *cmp_data = nullptr;
+    napi_value cmp_buf, cmp_arr;
+    if (compare) {
+        NAPI_OK(napi_create_arraybuffer(env, len[0] * sizeof(ge_compare_stats), &cmp_data, &cmp_buf));
+        memset(cmp_data, 0, len[0] * sizeof(ge_compare_stats));
+    }
     const size_t words = sizeof(ge_rollout_stats) / 8;
     void *out = nullptr, *st_data = nullptr;
     napi_value buf, arr, st_buf, st_arr, res;
@@ -581,7 +606,9 @@ napi_value Rollout(napi_env env, napi_callback_info info) {
     const uint32_t *first = static_cast<const uint32_t *>(data[4]), *pl = static_cast<const uint32_t *>(data[5]);
     const uint32_t *ch = static_cast<const uint32_t *>(data[6]);
     ge_rollout_stats *o = static_cast<ge_rollout_stats *>(out);
-    const int st = seats ? ge_batch_rollout_seats(b, len[0], rooms, keys, turns, sv, first, pl, ch, status, n_rollouts, max_turns, seed, o)
+    const int st = compare ? ge_batch_rollout_compare(b, len[0], rooms, keys, turns, sv, first, pl, ch, status, n_rollouts, max_turns, seed, o,
+                                                      base, subj, static_cast<ge_compare_stats *>(cmp_data))
+                   : seats ? ge_batch_rollout_seats(b, len[0], rooms, keys, turns, sv, first, pl, ch, status, n_rollouts, max_turns, seed, o)
                    : acts ? ge_batch_rollout_actions(b, len[0], rooms, keys, turns, first, pl, ch, status, n_rollouts, max_turns, seed, o)
                           : ge_batch_rollout_rooms(b, len[0], rooms, keys, turns, n_rollouts, max_turns, seed, o);
     if (st != GE_OK) {
@@ -596,6 +623,10 @@ napi_value Rollout(napi_env env, napi_callback_info info) {
     NAPI_OK(napi_create_object(env, &res));
     NAPI_OK(napi_set_named_property(env, res, "words", arr));
     NAPI_OK(napi_set_named_property(env, res, "status", st_arr));
+    if (compare) {
+        NAPI_OK(napi_create_typedarray(env, napi_biguint64_array, len[0] * (sizeof(ge_compare_stats) / 8), cmp_buf, 0, &cmp_arr));
+        NAPI_OK(napi_set_named_property(env, res, "cmp", cmp_arr));
+    }
     return res;
 }
 

@@ -86,6 +86,12 @@ export class RoomBatch {
   rolloutSeats(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, seats: ArrayLike<number>,
                actions: ArrayLike<ArrayLike<[number, number]>> | null, nRollouts: number, maxTurns?: number,
                seed?: bigint | number): { words: BigUint64Array; status: Int32Array };
+  /** rolloutSeats with every entry also compared, playout by playout, against entry baseline[k] of the same call (the same room) for
+   *  seat subjects[k] (POLICY.md §3e): cmp holds 6 words per entry (compared, better, worse, gain, loss, diff_sq), all zero when the
+   *  entry or its baseline was refused.  At most 65 536 entries.  The batch is only read. */
+  rolloutCompare(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, seats: ArrayLike<number>,
+                 actions: ArrayLike<ArrayLike<[number, number]>> | null, baseline: ArrayLike<number>, subjects: ArrayLike<number>,
+                 nRollouts?: number, maxTurns?: number, seed?: bigint | number): { words: BigUint64Array; status: Int32Array; cmp: BigUint64Array };
   /** out[k] = room rooms[k] (any order, repeats allowed). */
   readRoomsAt(rooms: ArrayLike<number | bigint>): RoomState[];
   readRoomsAtRaw(rooms: ArrayLike<number | bigint>): ArrayBuffer;

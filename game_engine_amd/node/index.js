@@ -618,9 +618,18 @@ class RoomBatch {
   rolloutSeats(rooms, keys, turns, seats, actions, nRollouts, maxTurns = 1024, seed) {
     return this._rollout(rooms, keys, turns, Uint32Array.from(seats), actions == null ? null : Array.from(actions), nRollouts, maxTurns, seed);
   }
-  /** The three rollout* methods: one native call (ge_batch_rollout_seats with seats, else ge_batch_rollout_actions with actions -
+  /** rolloutSeats with every entry also compared, playout by playout, against its baseline entry (twin of the Python
+   * RoomBatch.rollout_compare, POLICY.md §3e): baseline[k] is an index into this call (the same room), subjects[k] the seat
+   * (1-based) whose outcome is compared.  Returns { words, status, cmp }: words and status as rolloutSeats for the same entries,
+   * cmp a BigUint64Array of 6 words per entry (compared, better, worse, gain, loss, diff_sq of ge_compare_stats; all zero when the
+   * entry or its baseline was refused).  At most 65 536 entries.  The batch is only read.  Synchronous. */
+  rolloutCompare(rooms, keys, turns, seats, actions, baseline, subjects, nRollouts = 4096, maxTurns = 1024, seed) {
+    return this._rollout(rooms, keys, turns, Uint32Array.from(seats), actions == null ? null : Array.from(actions), nRollouts, maxTurns, seed,
+                         Uint32Array.from(baseline), Uint32Array.from(subjects));
+  }
+  /** The rollout* methods: one native call (ge_batch_rollout_seats with seats, else ge_batch_rollout_actions with actions -
    * [playerId, choice] pairs per entry, flattened to CSR - else ge_batch_rollout_rooms).  Returns { words, status }. */
-  _rollout(rooms, keys, turns, seats, actions, nRollouts, maxTurns, seed) {
+  _rollout(rooms, keys, turns, seats, actions, nRollouts, maxTurns, seed, baseline = null, subjects = null) {
     let first = null, players = null, choices = null;
     if (actions) {
       const acts = actions.map((a) => Array.from(a));
@@ -631,7 +640,8 @@ class RoomBatch {
       choices = Uint32Array.from(flat, (pc) => pc[1]);
     }
     return addon.rollout(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r)), BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))),
-                         Uint32Array.from(turns), seats, first, players, choices, nRollouts, maxTurns, seed === undefined ? this.seed : BigInt(seed));
+                         Uint32Array.from(turns), seats, first, players, choices, nRollouts, maxTurns, seed === undefined ? this.seed : BigInt(seed),
+                         baseline, subjects);
   }
   /** The listed rooms' states, out[k] = room rooms[k] (any order, repeats allowed). */
   readRoomsAt(rooms) {

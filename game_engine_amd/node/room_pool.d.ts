@@ -19,10 +19,11 @@ export class RoomPoolService {
   /** Forecasts of many threads in order: one rolloutRooms per chunk touched. */
   forecasts(threadIds: string[], nRollouts?: number, maxTurns?: number, seats?: (number | undefined)[]): Promise<Forecast[]>;
   /** As RoomService.advise (same candidates, keys, seed and output), from the thread's slot. */
-  advise(threadId: string, playerId?: number, nRollouts?: number, maxTurns?: number, view?: 'full' | 'seat'): Promise<Advice>;
-  /** Advice for many threads in order (playerIds[j] absent: thread j's lowest human seat): one rolloutActions per chunk touched. */
+  advise(threadId: string, playerId?: number, nRollouts?: number, maxTurns?: number, view?: 'full' | 'seat', compare?: boolean): Promise<Advice>;
+  /** Advice for many threads in order (playerIds[j] absent: thread j's lowest human seat): one rolloutActions per chunk touched
+   *  (with compare one rolloutCompare, and every option gains "versus"). */
   advises(threadIds: string[], playerIds?: (number | undefined)[], nRollouts?: number, maxTurns?: number,
-          view?: 'full' | 'seat'): Promise<Advice[]>;
+          view?: 'full' | 'seat', compare?: boolean): Promise<Advice[]>;
   /** Forget a thread (its slot is reused); without an id, every thread and every chunk's device memory. */
   close(threadId?: string): Promise<boolean>;
 }

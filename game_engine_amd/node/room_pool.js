@@ -195,13 +195,14 @@ class RoomPoolService {
   forecast(threadId, nRollouts = 4096, maxTurns = 1024, seat) {
     return this.forecasts([threadId], nRollouts, maxTurns, seat === undefined || seat === null ? undefined : [seat]).then((o) => o[0]);
   }
-  /** As RoomService.advise (same candidates, keys, seed, views and output), from the thread's pool slot. */
-  advise(threadId, playerId, nRollouts = 4096, maxTurns = 1024, view = 'full') {
-    return this.advises([threadId], [playerId], nRollouts, maxTurns, view).then((o) => o[0]);
+  /** As RoomService.advise (same candidates, keys, seed, views, compare and output), from the thread's pool slot. */
+  advise(threadId, playerId, nRollouts = 4096, maxTurns = 1024, view = 'full', compare = false) {
+    return this.advises([threadId], [playerId], nRollouts, maxTurns, view, compare).then((o) => o[0]);
   }
   /** Advice for many threads, in order (playerIds[j] undefined / null or no playerIds: thread j's lowest human seat): one
-   * rolloutActions call per chunk touched (rolloutSeats in the "seat" view).  No thread changes. */
-  advises(threadIds, playerIds, nRollouts = 4096, maxTurns = 1024, view = 'full') {
+   * rolloutActions call per chunk touched (rolloutSeats in the "seat" view; with compare one rolloutCompare, and every option
+   * gains "versus" as RoomService.advise's).  No thread changes. */
+  advises(threadIds, playerIds, nRollouts = 4096, maxTurns = 1024, view = 'full', compare = false) {
     checkForecastArgs(nRollouts, maxTurns);
     const seatView = checkView(view);
     return this._serial(() => {
@@ -210,7 +211,7 @@ class RoomPoolService {
       const seats = rooms.map((room, j) => adviseSeat(threadIds[j], room.humanSeats, pids[j]));
       const cands = rooms.map((room) => adviseCandidates(room.table, room.state));
       const res = runRollouts(rooms.map((room, j) => ({ batch: room.chunk, slot: room.slot, key: room.key, turn: room.turn, seat: seats[j], cands: cands[j] })),
-                              seatView, nRollouts, maxTurns, this.seed);
+                              seatView, nRollouts, maxTurns, this.seed, !!compare);
       return rooms.map((room, j) => adviseOutput(room.table, room.names, threadIds[j], room.turn, seats[j], room.state, cands[j], nRollouts, maxTurns,
                                                  res[j], 0, seatView));
     });

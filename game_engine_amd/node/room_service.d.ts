@@ -38,9 +38,13 @@ export interface Advice {
   /** the thread's forecast: the policy's own choice */
   policy: Forecast;
   /** the accepted candidates in ascending order; label = the seat's name (Werewolf) or the statement number (Two-Truths) */
-  options: { choice: number; label: string; forecast: Forecast }[];
+  options: { choice: number; label: string; forecast: Forecast;
+             /** with compare: the option against the policy's entry, playout by playout, for the advised seat (POLICY.md §3e) */
+             versus?: { compared: number; better: number; worse: number; gain: number; loss: number; diffSq: number } }[];
   /** "seat" when every playout started from what the advised seat knows */
   view?: 'seat';
+  /** true when the options carry "versus" */
+  compare?: true;
 }
 export class RoomService {
   constructor(opts?: { gamesDir?: string; seed?: bigint | number; device?: number } & PlayoutOptions);
@@ -63,8 +67,9 @@ export class RoomService {
   forecast(threadId: string, nRollouts?: number, maxTurns?: number, seat?: number): Promise<Forecast>;
   /** For every choice playerId (default: the lowest human seat; RangeError if there is none) can make now, the forecast given
    *  that choice, under forecast's keys and seed; the thread is not changed (INTEGRATION.md "Advising a seat").  view "seat": from
-   *  what that seat knows, the form to show a player (INTEGRATION.md "Advising a seat from what it knows"); the JSON gains "view". */
-  advise(threadId: string, playerId?: number, nRollouts?: number, maxTurns?: number, view?: 'full' | 'seat'): Promise<Advice>;
+   *  what that seat knows, the form to show a player (INTEGRATION.md "Advising a seat from what it knows"); the JSON gains "view".
+   *  compare: every option gains "versus" and the JSON "compare": true (INTEGRATION.md "Is this choice really better?"); the rest is unchanged. */
+  advise(threadId: string, playerId?: number, nRollouts?: number, maxTurns?: number, view?: 'full' | 'seat', compare?: boolean): Promise<Advice>;
   /** Forget a thread and free its device memory; resolves false for an unknown thread. */
   close(threadId: string): Promise<boolean>;
   serve(port?: number): Promise<import('http').Server>;

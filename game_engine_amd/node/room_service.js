@@ -145,15 +145,17 @@ function adviseSeat(threadId, humanSeats, playerId) {
  * thread's forecast key and the forecast seed.  One call per batch, in the order the batches first appear, split only where the
  * library's cap on entries x rollouts needs it: rolloutRooms for a forecast, rolloutActions for an advise, rolloutSeats in the
  * seat view (seat 0 for a thread without a seat: its full view).  Returns per request { words, status } (status null after
- * rolloutRooms), views into the call's results. */
-function runRollouts(reqs, seatView, nRollouts, maxTurns, seed) {
+ * rolloutRooms), views into the call's results.  compare (an advise): the one call is rolloutCompare instead (seat 0 entries in
+ * the full view) - every entry's baseline is its thread's policy entry, the subject the advised seat - and each result gains
+ * cmp; a thread's entries stay in one call and a call at or below 65 536 entries. */
+function runRollouts(reqs, seatView, nRollouts, maxTurns, seed, compare = false) {
   const byBatch = new Map();
   reqs.forEach((r, j) => {
     if (!byBatch.has(r.batch)) byBatch.set(r.batch, []);
     byBatch.get(r.batch).push(j);
   });
   const size = reqs.map((r) => (r.cands ? r.cands.length + 1 : 1));
-  const perCall = Math.max(1, Math.floor(2 ** 26 / nRollouts));
+  const perCall = Math.min(Math.max(1, Math.floor(2 ** 26 / nRollouts)), compare ? 65536 : Infinity);
   const parts = [];
   for (const js of byBatch.values()) {
     let nEnt = 0;
@@ -167,20 +169,23 @@ function runRollouts(reqs, seatView, nRollouts, maxTurns, seed) {
   const out = new Array(reqs.length);
   const fseed = forecastSeed(seed);
   for (const part of parts) {
-    const rooms = [], keys = [], turns = [], seats = [];
+    const rooms = [], keys = [], turns = [], seats = [], base = [], subj = [];
     const acts = part.some((j) => reqs[j].cands) ? [] : null;
     for (const j of part) {
       const r = reqs[j];
+      for (let i = 0; i < size[j]; i++) { base.push(rooms.length + size[j] - 1); subj.push(r.seat); }
       for (let i = 0; i < size[j]; i++) { rooms.push(r.slot); keys.push(forecastKey(r.key)); turns.push(r.turn); seats.push(r.seat || 0); }
       if (acts) acts.push(...r.cands.map((c) => [[r.seat, c]]), []);
     }
     const batch = reqs[part[0]].batch;
-    const res = seatView ? batch.rolloutSeats(rooms, keys, turns, seats, acts, nRollouts, maxTurns, fseed)
+    const res = compare ? batch.rolloutCompare(rooms, keys, turns, seatView ? seats : seats.map(() => 0), acts, base, subj, nRollouts, maxTurns, fseed)
+      : seatView ? batch.rolloutSeats(rooms, keys, turns, seats, acts, nRollouts, maxTurns, fseed)
       : acts ? batch.rolloutActions(rooms, keys, turns, acts, nRollouts, maxTurns, fseed)
         : { words: batch.rolloutRooms(rooms, keys, turns, nRollouts, maxTurns, fseed), status: null };
     let at = 0;
     for (const j of part) {
       out[j] = { words: res.words.subarray(77 * at, 77 * (at + size[j])), status: res.status && res.status.subarray(at, at + size[j]) };
+      if (res.cmp) out[j].cmp = res.cmp.subarray(6 * at, 6 * (at + size[j]));
       at += size[j];
     }
   }
@@ -193,10 +198,15 @@ function adviseOutput(table, names, threadId, turn, seat, st, cands, nRollouts, 
     if (res.status[at + j] !== 0) return;
     options.push({ choice: c, label: st.pack === 1 ? names[c - 1] : String(c),
                    forecast: forecastOutput(table, names, threadId, turn, nRollouts, maxTurns, res.words, 77 * (at + j)) });
+    if (res.cmp) {                                           // the option against the policy's entry, for the advised seat
+      const v = (i) => Number(res.cmp[6 * (at + j) + i]);
+      options[options.length - 1].versus = { compared: v(0), better: v(1), worse: v(2), gain: v(3), loss: v(4), diffSq: v(5) };
+    }
   });
   const out = { threadId, turn: Number(turn), playerId: seat, phaseId: st.current_phase_id, rollouts: nRollouts, maxTurns,
                 policy: forecastOutput(table, names, threadId, turn, nRollouts, maxTurns, res.words, 77 * (at + cands.length)), options };
   if (seatView) out.view = 'seat';
+  if (res.cmp) out.compare = true;
   return out;
 }
 
@@ -292,8 +302,10 @@ class RoomService {
    * call under forecast's keys and seed.  playerId defaults to the lowest human seat (RangeError if there is none).  Resolves with
    * { threadId, turn, playerId, phaseId, rollouts, maxTurns, policy, options: [{ choice, label, forecast }] } for the accepted
    * candidates in ascending order.  The thread is not changed.  view "seat": every playout starts from what the advised seat knows
-   * (rolloutSeats) - the form to show that player - and the JSON gains "view": "seat"; "full" (the default) is for spectators. */
-  advise(threadId, playerId, nRollouts = 4096, maxTurns = 1024, view = 'full') {
+   * (rolloutSeats) - the form to show that player - and the JSON gains "view": "seat"; "full" (the default) is for spectators.
+   * compare: the one call is rolloutCompare; the JSON gains "compare": true and per option "versus" { compared, better, worse, gain,
+   * loss, diffSq }: the option against the policy's entry, playout by playout, for the advised seat; the rest is the same bytes. */
+  advise(threadId, playerId, nRollouts = 4096, maxTurns = 1024, view = 'full', compare = false) {
     checkForecastArgs(nRollouts, maxTurns);
     const seatView = checkView(view);
     const room = this.rooms.get(threadId);
@@ -302,7 +314,7 @@ class RoomService {
     return this._serial(room, () => {
       const cands = adviseCandidates(room.table, room.state);
       const [res] = runRollouts([{ batch: room.batch, slot: 0, key: room.key, turn: room.turn, seat, cands }], seatView, nRollouts, maxTurns,
-                                this.seed);
+                                this.seed, !!compare);
       return adviseOutput(room.table, room.names, threadId, room.turn, seat, room.state, cands, nRollouts, maxTurns, res, 0, seatView);
     });
   }

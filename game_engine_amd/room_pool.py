@@ -303,15 +303,16 @@ class RoomPoolService:
                 for j, (tid, room) in enumerate(zip(thread_ids, rooms))]
 
     def advise(self, thread_id: str, player_id: Optional[int] = None, n_rollouts: int = 4096, max_turns: int = 1024,
-               view: str = "full") -> Dict[str, Any]:
-        """As RoomService.advise (same candidates, keys, seed, views and output), from the thread's pool slot."""
-        return self.advises([thread_id], None if player_id is None else [player_id], n_rollouts, max_turns, view)[0]
+               view: str = "full", compare: bool = False) -> Dict[str, Any]:
+        """As RoomService.advise (same candidates, keys, seed, views, compare and output), from the thread's pool slot."""
+        return self.advises([thread_id], None if player_id is None else [player_id], n_rollouts, max_turns, view, compare)[0]
 
     def advises(self, thread_ids: Sequence[str], player_ids: Optional[Sequence[Optional[int]]] = None, n_rollouts: int = 4096,
-                max_turns: int = 1024, view: str = "full") -> List[Dict[str, Any]]:
+                max_turns: int = 1024, view: str = "full", compare: bool = False) -> List[Dict[str, Any]]:
         """Advice for many threads, in order (player_ids[j] None or absent: thread j's lowest human seat): one rollout_actions
         call per chunk touched - rollout_seats in the "seat" view, every thread from its advised seat's view - each thread's
-        entries as RoomService.advise's.  No thread changes."""
+        entries as RoomService.advise's.  compare: one rollout_compare call per chunk touched instead, and every option gains
+        "versus" as RoomService.advise's.  No thread changes."""
         check_forecast_args(n_rollouts, max_turns)
         seat_view = check_view(view)
         rooms = [self._rooms[tid] for tid in thread_ids]          # KeyError for an unknown thread, before anything runs
@@ -321,9 +322,10 @@ class RoomPoolService:
         seats = [advise_seat(tid, room["human_seats"], pid) for tid, room, pid in zip(thread_ids, rooms, pids)]
         cands = [advise_candidates(room["table"], room["view"]) for room in rooms]
         res = run_rollouts([RolloutRequest(room["chunk"], room["slot"], room["key"], room["turn"], seat, c)
-                            for room, seat, c in zip(rooms, seats, cands)], seat_view, n_rollouts, max_turns, self.seed)
+                            for room, seat, c in zip(rooms, seats, cands)], seat_view, n_rollouts, max_turns, self.seed, compare)
         return [advise_output(room["table"], room["names"], tid, room["turn"], seats[j], room["view"], cands[j], n_rollouts, max_turns,
-                              *res[j], seat_view) for j, (tid, room) in enumerate(zip(thread_ids, rooms))]
+                              res[j][0], res[j][1], seat_view, res[j][2] if compare else None)
+                for j, (tid, room) in enumerate(zip(thread_ids, rooms))]
 
     def close(self, thread_id: Optional[str] = None):
         """Close one thread (its slot goes back to the pool's free list) or, without an id, every thread and every chunk."""

@@ -193,13 +193,18 @@ class RolloutRequest(NamedTuple):
     cands: Optional[List[int]] = None
 
 
-def run_rollouts(reqs: Sequence[RolloutRequest], seat_view: bool, n_rollouts: int, max_turns: int, seed: int) -> List[Tuple[Any, Any]]:
+def run_rollouts(reqs: Sequence[RolloutRequest], seat_view: bool, n_rollouts: int, max_turns: int, seed: int,
+                 compare: bool = False) -> List[Tuple[Any, ...]]:
     """The playouts of a forecast or advise call, as (words, status) per request (status None after rollout_rooms).  A forecast
     is one entry, an advise one per candidate then the policy's (no action), all under the thread's forecast key and the forecast
     seed.  One call per batch, in the order the batches first appear, split only where the library's cap on entries x rollouts
     needs it: rollout_rooms for a forecast, rollout_actions for an advise, rollout_seats in the seat view (seat 0 for a thread
-    without a seat: its full view)."""
+    without a seat: its full view).  compare (an advise): the one call is rollout_compare instead (seat 0 entries in the full
+    view) - every entry's baseline is its thread's policy entry, the subject the advised seat - and each result is (words, status,
+    cmp); a thread's entries stay in one call and a call at or below 65 536 entries."""
     per_call = max(1, (1 << 26) // int(n_rollouts))
+    if compare:
+        per_call = min(per_call, 65536)
     calls: Dict[int, List[List[int]]] = {}                 # per batch, in first-appearance order: its calls' requests
     n_ent: Dict[int, int] = {}                             # entries in the batch's last call
     for j, r in enumerate(reqs):
@@ -220,9 +225,13 @@ def run_rollouts(reqs: Sequence[RolloutRequest], seat_view: bool, n_rollouts: in
         turns: list = []
         seats: list = []
         acts: list = []
+        base: list = []
+        subj: list = []
         for j in part:
             r = reqs[j]
             k = 1 if r.cands is None else len(r.cands) + 1
+            base += [len(rooms) + k - 1] * k
+            subj += [r.seat] * k
             rooms += [r.slot] * k
             keys += [forecast_key(r.key)] * k
             turns += [r.turn] * k
@@ -230,7 +239,11 @@ def run_rollouts(reqs: Sequence[RolloutRequest], seat_view: bool, n_rollouts: in
             if r.cands is not None:
                 acts += [[(r.seat, c)] for c in r.cands] + [[]]
         batch = reqs[part[0]].batch
-        if seat_view:
+        cmp = None
+        if compare:
+            words, status, cmp = batch.rollout_compare(rooms, keys, turns, seats if seat_view else [0] * len(rooms), acts, base, subj,
+                                                       n_rollouts, max_turns, seed=seed)
+        elif seat_view:
             words, status = batch.rollout_seats(rooms, keys, turns, seats, acts or None, n_rollouts, max_turns, seed=seed)
         elif acts:
             words, status = batch.rollout_actions(rooms, keys, turns, acts, n_rollouts, max_turns, seed=seed)
@@ -239,15 +252,16 @@ def run_rollouts(reqs: Sequence[RolloutRequest], seat_view: bool, n_rollouts: in
         at = 0
         for j in part:
             k = 1 if reqs[j].cands is None else len(reqs[j].cands) + 1
-            out[j] = (words[at:at + k], None if status is None else status[at:at + k])
+            out[j] = (words[at:at + k], None if status is None else status[at:at + k]) + (() if cmp is None else (cmp[at:at + k],))
             at += k
     return out
 
 
 def advise_output(table: GameTable, names: List[str], thread_id: str, turn: int, seat: int, view, cands: List[int], n_rollouts: int,
-                  max_turns: int, words, status, seat_view: bool = False) -> Dict[str, Any]:
+                  max_turns: int, words, status, seat_view: bool = False, cmp=None) -> Dict[str, Any]:
     """advise's JSON from the words and verdicts of an advise's entries (run_rollouts; the same bytes as room_service.js /
-    room_pool.js); from the seat's view it gains "view": "seat"."""
+    room_pool.js); from the seat's view it gains "view": "seat"; with cmp (the entries' ge_compare_stats words) "compare": true
+    and per option "versus": the option against the policy's entry, playout by playout, for the advised seat."""
     options = []
     for j, c in enumerate(cands):
         if int(status[j]) != 0:
@@ -255,10 +269,12 @@ def advise_output(table: GameTable, names: List[str], thread_id: str, turn: int,
         label = names[c - 1] if table.pack == PACK_WEREWOLF else str(c)
         options.append({"choice": c, "label": label,
                         "forecast": forecast_output(table, names, thread_id, turn, n_rollouts, max_turns, words[j])})
+        if cmp is not None:
+            options[-1]["versus"] = dict(zip(("compared", "better", "worse", "gain", "loss", "diffSq"), (int(x) for x in cmp[j])))
     return {"threadId": thread_id, "turn": int(turn), "playerId": int(seat), "phaseId": int(view["phase_id"]),
             "rollouts": int(n_rollouts), "maxTurns": int(max_turns),
             "policy": forecast_output(table, names, thread_id, turn, n_rollouts, max_turns, words[len(cands)]), "options": options,
-            **({"view": "seat"} if seat_view else {})}
+            **({"view": "seat"} if seat_view else {}), **({"compare": True} if cmp is not None else {})}
 
 
 class RoomService:
@@ -428,7 +444,7 @@ class RoomService:
         return seat_forecast_output(room["table"], room["names"], thread_id, turn, n_rollouts, max_turns, seat, words[0])
 
     def advise(self, thread_id: str, player_id: Optional[int] = None, n_rollouts: int = 4096, max_turns: int = 1024,
-               view: str = "full") -> Dict[str, Any]:
+               view: str = "full", compare: bool = False) -> Dict[str, Any]:
         """What each choice the seat can make now leads to: for every candidate (advise_candidates) the forecast of the thread
         given that the seat logs it before the next turn, and the forecast with the policy's own choice ("policy", equal to
         forecast(thread_id)).  One rollout_actions call; every entry uses forecast's keys and seed, so replica r of every option
@@ -437,17 +453,19 @@ class RoomService:
         forecast}] for the accepted candidates in ascending order ([] when the seat has nothing to do now).  The thread is not
         changed.  view "seat": every playout starts from what the advised seat knows (RoomBatch.rollout_seats, POLICY.md §3c)
         - the form to show that player - and the JSON gains "view": "seat"; "full" (the default) plays from the true record and
-        is for spectators and debugging."""
+        is for spectators and debugging.  compare: the one call is rollout_compare; the JSON gains "compare": true and per option
+        "versus" {compared, better, worse, gain, loss, diffSq}: the option against the policy's entry, playout by playout, for
+        the advised seat (INTEGRATION.md "Is this choice really better?"); everything else is byte for byte the same."""
         check_forecast_args(n_rollouts, max_turns)
         seat_view = check_view(view)
         room = self._rooms[thread_id]
         seat = advise_seat(thread_id, room["human_seats"], player_id)
         rv, turn = room["view"], room["batch"].turn
         cands = advise_candidates(room["table"], rv)
-        (words, status), = run_rollouts([RolloutRequest(room["batch"], 0, room["key"], turn, seat, cands)], seat_view, n_rollouts,
-                                        max_turns, self.seed)
-        return advise_output(room["table"], room["names"], thread_id, turn, seat, rv, cands, n_rollouts, max_turns, words, status,
-                             seat_view)
+        res, = run_rollouts([RolloutRequest(room["batch"], 0, room["key"], turn, seat, cands)], seat_view, n_rollouts, max_turns,
+                            self.seed, compare)
+        return advise_output(room["table"], room["names"], thread_id, turn, seat, rv, cands, n_rollouts, max_turns, res[0], res[1],
+                             seat_view, res[2] if compare else None)
 
     def close(self, thread_id: Optional[str] = None):
         for tid in ([thread_id] if thread_id else list(self._rooms)):

@@ -368,18 +368,32 @@ class RoomBatch:
         (rollout_actions's, or a seat above its room's player count), before anything runs."""
         return self._rollout("rollout_seats", rooms, keys, turns, seats, actions, n_rollouts, max_turns, seed)
 
+    def rollout_compare(self, rooms, keys, turns, seats, actions, baseline, subjects, n_rollouts: int = 4096, max_turns: int = 1024,
+                        seed: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """rollout_seats with every entry also compared, playout by playout, against its baseline entry (POLICY.md §3e):
+        baseline[k] is an index into this call (the same room), subjects[k] the seat (1-based) whose outcome is compared -
+        Werewolf: its team has won, Two-Truths: its total_score.  Returns (words (n, 77) uint64, status (n,) int32, cmp (n, 6)
+        uint64): words and status are rollout_seats's for the same entries word for word; cmp[k] = (compared, better, worse,
+        gain, loss, diff_sq) of ge_compare_stats, all zero when entry k or its baseline was refused.  Only equal keys, turns
+        and seats of an entry and its baseline make it a comparison on common random numbers.  At most 65 536 entries.  The
+        batch is only read.  GeError only for a structural error (rollout_seats's, a baseline outside the call or of another
+        room, a subject outside 1 .. n_players), before anything runs."""
+        extra = (np.ascontiguousarray(baseline, dtype=np.uint32), np.ascontiguousarray(subjects, dtype=np.uint32))
+        return self._rollout("rollout_compare", rooms, keys, turns, seats, actions, n_rollouts, max_turns, seed, extra)
+
     def _rollout(self, method: str, rooms, keys, turns, seats, actions, n_rollouts: int, max_turns: int,
-                 seed: Optional[int]) -> Tuple[np.ndarray, np.ndarray]:
-        """The three rollout_* methods: one call of ge_batch_<method> (seats and actions are read where the method has them;
-        actions None: every entry's slice empty, passed as NULL).  Returns (words, status); GeError naming the method when
-        the lengths differ, or naming the symbol when it fails without a verdict written."""
+                 seed: Optional[int], compare=None):
+        """The rollout_* methods: one call of ge_batch_<method> (seats and actions are read where the method has them;
+        actions None: every entry's slice empty, passed as NULL).  Returns (words, status) - with compare, rollout_compare's
+        (baseline, subjects), (words, status, cmp); GeError naming the method when the lengths differ, or naming the symbol when
+        it fails without a verdict written."""
         rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
         args = [rooms, np.ascontiguousarray(keys, dtype=np.uint64), np.ascontiguousarray(turns, dtype=np.uint32)]
-        if method == "rollout_seats":
+        if method in ("rollout_seats", "rollout_compare"):
             args.append(np.ascontiguousarray(seats, dtype=np.uint32))
         if method == "rollout_actions" or actions is not None:
             actions = [list(a) for a in actions]
-        if len({len(x) for x in args} | ({len(rooms)} if actions is None else {len(actions)})) > 1:
+        if len({len(x) for x in args + list(compare or ())} | ({len(rooms)} if actions is None else {len(actions)})) > 1:
             raise GeError(-1, f"{method}: arrays differ in length")
         out = np.zeros((len(rooms), _lib.ROLLOUT_WORDS), dtype=np.uint64)
         status = None
@@ -394,12 +408,18 @@ class RoomBatch:
             status = np.full(len(rooms), 1, dtype=np.int32)      # 1: untouched (no ge_status is positive)
             args += [first, players, choices, status]
         sym = "ge_batch_" + method
+        tail = []
+        if compare is not None:
+            cmp = np.zeros((len(rooms), _lib.COMPARE_WORDS), dtype=np.uint64)
+            tail = [compare[0].ctypes.data, compare[1].ctypes.data, cmp.ctypes.data]
         st = getattr(self._lib, sym)(self._h, len(rooms), *[x if x is None else x.ctypes.data for x in args], n_rollouts, max_turns,
-                                     self._seed if seed is None else seed, out.ctypes.data)
+                                     self._seed if seed is None else seed, out.ctypes.data, *tail)
         # a refused entry returns its status with every entry's verdict written; a structural error or a failure of the call
         # leaves the verdicts untouched (ge_batch_rollout_rooms writes none)
         if st != 0 and (status is None or (status == 1).any()):
             _check(st, sym)
+        if compare is not None:
+            return out, status, cmp
         return out, status
 
     def write_agent_state(self, room: int, state: Dict[str, Any], visit_actions: Optional[Dict[Any, int]] = None) -> Dict[str, Any]:

@@ -43,7 +43,8 @@ extern "C" {
  *      ge_batch_rollout_rooms + ge_rollout_stats (on-device playouts of listed rooms: win odds per side and per seat);
  *      ge_batch_rollout_actions (playouts that start from given actions: win odds per choice a seat can make now);
  *      ge_batch_rollout_seats (the same playouts from what one seat knows: hidden roles / the lie dealt again per replica);
- *      ge_batch_step_rooms_playout + GE_PLAYOUT_FULL_VIEW (playout seats: bots that choose each action by their own playouts) */
+ *      ge_batch_step_rooms_playout + GE_PLAYOUT_FULL_VIEW (playout seats: bots that choose each action by their own playouts);
+ *      ge_batch_rollout_compare + ge_compare_stats (an entry against a baseline entry, playout by playout: the paired counts) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -374,6 +375,36 @@ int ge_batch_rollout_seats(ge_batch *b, uint64_t n, const uint64_t *rooms, const
                            const uint32_t *seats /* n */, const uint32_t *first_action /* n + 1, may be NULL: no actions */,
                            const uint32_t *player_ids, const uint32_t *choices, int32_t *entry_status /* may be NULL */,
                            uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, ge_rollout_stats *out);
+
+/* Paired comparison of playout entries (POLICY.md §3e).  For an entry k of a call and a subject seat s, the outcome X_k(r) of
+ * replica r is - Werewolf: 1 if the replica is finished and seat s's team has won, else 0 (the bit seat_wins[s-1] counts);
+ * Two-Truths: seat s's total_score at the end of the playout, finished or not (the value seat_score[s-1] sums).  For entry k
+ * with baseline entry b = baseline[k], over r = 0 .. n_rollouts-1: */
+typedef struct ge_compare_stats {         /* 6 x u64 = 48 B; all zero when entry k or its baseline was refused */
+    uint64_t compared;                    /* playouts compared: n_rollouts, or 0 */
+    uint64_t better, worse;               /* playouts with X_k(r) > X_b(r), with X_k(r) < X_b(r) */
+    uint64_t gain, loss;                  /* sum of max(X_k - X_b, 0), sum of max(X_b - X_k, 0) */
+    uint64_t diff_sq;                     /* sum of (X_k - X_b)^2 */
+} ge_compare_stats;
+/* So gain - loss = seat_wins[s-1] (Werewolf) / seat_score[s-1] (Two-Truths) of entry k minus that of entry b; in Werewolf
+ * gain == better, loss == worse and diff_sq == better + worse; baseline[k] == k gives compared = n_rollouts and zeros elsewhere.
+ *
+ * ge_batch_rollout_compare is ge_batch_rollout_seats, arguments and meaning unchanged - out[k] and entry_status[k] are what it
+ * gives for the same entries, word for word - plus, per entry, baseline[k] (an index into the same call), subjects[k] (the
+ * subject seat, 1-based) and cmp[k].  Replica r of an entry is compared with replica r of its baseline.  Keys, turns and seats
+ * of an entry and its baseline need not be equal - the counts are defined either way - but only equal keys, turns and seats
+ * make it a comparison on common random numbers: replica r of both then draws the same stream and the same re-deal, and the
+ * two differ only by what their actions change.  Structural errors, all before anything runs and with nothing touched, in this
+ * order: ge_batch_rollout_seats's own; then GE_ERR_ARG for baseline, subjects or cmp NULL with n > 0, n > 65 536 (an entry and
+ * its baseline are staged together), a baseline[k] >= n, rooms[baseline[k]] != rooms[k] (the same room, hence the same seat
+ * numbering), subjects[k] == 0 or above the n_players of room rooms[k]'s segment.  Refusals per entry as
+ * ge_batch_rollout_seats; cmp[k] is all zero when entry k or its baseline was refused.  Each playout's outcome takes one byte
+ * of device memory and none crosses to the host.  The batch is only read.  Ordered behind the previous step; synchronises. */
+int ge_batch_rollout_compare(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
+                             const uint32_t *seats /* n */, const uint32_t *first_action /* n + 1, may be NULL: no actions */,
+                             const uint32_t *player_ids, const uint32_t *choices, int32_t *entry_status /* may be NULL */,
+                             uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, ge_rollout_stats *out,
+                             const uint32_t *baseline /* n */, const uint32_t *subjects /* n, 1-based */, ge_compare_stats *cmp /* n */);
 
 /* Playout seats (POLICY.md §3d): ge_batch_step_rooms with some bot seats choosing their action by playouts.  Room k is stepped
  * as ge_batch_step_rooms's entry (rooms[k], keys[k], turns[k]), except that every seat s of playout_masks[k] (bit i = seat

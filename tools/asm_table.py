@@ -71,6 +71,8 @@ def collect(rebuild=True):
 def label(r):
     if r["kernel"] == "ge_pool_kernel":                          # ge_batch_step_rooms: one launch per segment present
         return f"{r['layout']}, indexed single-turn (ge_batch_step_rooms)" + (", GENERIC" if r["generic"] else "")
+    if r["kernel"] == "ge_rollout_kernel" and r.get("act") == 3:  # ge_batch_rollout_compare: one launch per segment present
+        return f"{r['layout']}, playouts that keep their outcome (ge_batch_rollout_compare)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_rollout_kernel" and r.get("act") == 2:  # ge_batch_rollout_seats: one launch per segment present
         return f"{r['layout']}, playouts from a seat's view (ge_batch_rollout_seats)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_rollout_kernel" and r.get("act"):      # ge_batch_rollout_actions: one launch per segment present
@@ -79,6 +81,8 @@ def label(r):
         return f"{r['layout']}, playouts (ge_batch_rollout_rooms)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] in ("ge_playout_plan", "ge_playout_decide"):  # ge_batch_step_rooms_playout: one launch per unit of rooms
         return f"{r['layout']}, playout seats, {r['kernel'][11:]} (ge_batch_step_rooms_playout)"
+    if r["kernel"] == "ge_compare_kernel":                       # ge_batch_rollout_compare: one launch per chunk, behind the playouts
+        return "ge_compare_kernel (ge_batch_rollout_compare: an entry against its baseline)"
     if r["kernel"] not in ("ge_step_kernel", "ge_step_kernel_mixed"):
         return r["kernel"]
     form = "single-turn" if r["single"] else "fused"
