@@ -236,28 +236,49 @@ template <int GEN> hipError_t pool_launch(uint32_t kind, dim3 grid, hipStream_t 
 
 }  // namespace
 
-static int step_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, ge_turn_event *events) {
-    if (n == 0) return GE_OK;
+// the entry checks of ge_batch_step_rooms (n > 0), all before anything runs: shared with ge_batch_run_rooms (ge_run.inl)
+static int pool_check_entries(const ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns) {
     if (!rooms || !keys || !turns || n > 0x7FFFFFFFull) return GE_ERR_ARG;
     for (uint64_t k = 0; k < n; k++)                              // all-or-nothing: every entry is checked before anything runs
         if (rooms[k] >= b->n_rooms || turns[k] == 0xFFFFFFFFu) return GE_ERR_RANGE;
-    {
-        std::vector<uint64_t> sorted(rooms, rooms + n);
-        std::sort(sorted.begin(), sorted.end());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return GE_ERR_ARG;
-    }
-    GE_ON_DEVICE(b);
-    int st = sync_impl(b);
-    if (st != GE_OK) return st;
-    // stable counting sort by segment: entry order[i] goes to position i; segment s holds [begin[s], begin[s + 1])
+    std::vector<uint64_t> sorted(rooms, rooms + n);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return GE_ERR_ARG;
+    return GE_OK;
+}
+
+// stable counting sort by segment: entry order[i] goes to position i; segment s holds [begin[s], begin[s + 1])
+static void pool_group_entries(const ge_batch *b, uint64_t n, const uint64_t *rooms, std::vector<uint32_t> &seg_of, std::vector<uint32_t> &begin,
+                               std::vector<uint32_t> &order) {
     const uint32_t n_seg = (uint32_t)b->segs.size();
-    std::vector<uint32_t> seg_of((size_t)n), begin(n_seg + 1u, 0u), order((size_t)n);
+    seg_of.assign((size_t)n, 0u); begin.assign(n_seg + 1u, 0u); order.assign((size_t)n, 0u);
     for (uint64_t k = 0; k < n; k++) { seg_of[k] = pool_segment_of(b, rooms[k]); begin[seg_of[k] + 1u]++; }
     for (uint32_t s = 0; s < n_seg; s++) begin[s + 1u] += begin[s];
-    {
-        std::vector<uint32_t> at(begin.begin(), begin.end() - 1);
-        for (uint64_t k = 0; k < n; k++) order[at[seg_of[k]]++] = (uint32_t)k;
-    }
+    std::vector<uint32_t> at(begin.begin(), begin.end() - 1);
+    for (uint64_t k = 0; k < n; k++) order[at[seg_of[k]]++] = (uint32_t)k;
+}
+
+// the four event words of a turn (pool_event) as read_events_impl decodes the trace record
+static void pool_decode_event(const uint32_t *w, const ge_game_table &tb, ge_turn_event &e) {
+    memset(&e, 0, sizeof e);
+    e.turn = w[0];
+    e.from_phase_id = tb.rows[w[1] & 255u].phase_id;
+    e.to_phase_id = tb.rows[(w[1] >> 8) & 255u].phase_id;
+    e.restarted = (w[1] >> 16) & 1u;
+    e.acted_now = (uint16_t)(w[1] >> 20);
+    const uint64_t ch = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
+    for (int c = 0; c < 16; c++) e.choice[c] = (uint8_t)((ch >> (4 * c)) & 15u);
+}
+
+static int step_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, ge_turn_event *events) {
+    if (n == 0) return GE_OK;
+    int st = pool_check_entries(b, n, rooms, keys, turns);
+    if (st != GE_OK) return st;
+    GE_ON_DEVICE(b);
+    if ((st = sync_impl(b)) != GE_OK) return st;
+    const uint32_t n_seg = (uint32_t)b->segs.size();
+    std::vector<uint32_t> seg_of, begin, order;
+    pool_group_entries(b, n, rooms, seg_of, begin, order);
     // one upload: [rooms u64 x n][keys u64 x n][turns u32 x n (padded to 16 B)], then events 16 B x n
     const size_t off_keys = 8 * (size_t)n, off_turns = 16 * (size_t)n, off_ev = (off_turns + 4 * (size_t)n + 15u) & ~(size_t)15u;
     const size_t total = off_ev + 16 * (size_t)n;
@@ -294,21 +315,8 @@ static int step_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const
     uint32_t *h_ev = reinterpret_cast<uint32_t *>(host + off_ev);
     HIP_TRY(hipMemcpyAsync(h_ev, dev + off_ev, 16 * (size_t)n, hipMemcpyDeviceToHost, s));
     if ((st = sync_impl(b)) != GE_OK) return st;
-    if (events) {
-        for (size_t i = 0; i < n; i++) {                          // as read_events_impl decodes the trace record
-            const uint32_t *w = h_ev + 4 * i;
-            const ge_game_table &tb = b->segs[seg_of[order[i]]].table;
-            ge_turn_event &e = events[order[i]];
-            memset(&e, 0, sizeof e);
-            e.turn = w[0];
-            e.from_phase_id = tb.rows[w[1] & 255u].phase_id;
-            e.to_phase_id = tb.rows[(w[1] >> 8) & 255u].phase_id;
-            e.restarted = (w[1] >> 16) & 1u;
-            e.acted_now = (uint16_t)(w[1] >> 20);
-            const uint64_t ch = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
-            for (int c = 0; c < 16; c++) e.choice[c] = (uint8_t)((ch >> (4 * c)) & 15u);
-        }
-    }
+    if (events)
+        for (size_t i = 0; i < n; i++) pool_decode_event(h_ev + 4 * i, b->segs[seg_of[order[i]]].table, events[order[i]]);
     return GE_OK;
 }
 

@@ -523,6 +523,57 @@ napi_value StepRoomsPlayout(napi_env env, napi_callback_info info) {
     return out;
 }
 
+// runRooms(batch, rooms: BigUint64Array, keys: BigUint64Array, turns: Uint32Array, maxTurns, until: GE_RUN_UNTIL_* bits, views: boolean):
+// { played: Uint32Array, stopped: Uint32Array, events: ArrayBuffer of rooms.length x maxTurns ge_turn_event, views: ArrayBuffer of
+// rooms.length x maxTurns ge_room_view | null } - listed rooms played on until a person is needed (ge_batch_run_rooms, POLICY.md
+// §3f); entry k's turn t is at k * maxTurns + t, filled below played[k] (zero above).  Synchronous, as stepRoomsPlayout is.
+napi_value RunRooms(napi_env env, napi_callback_info info) {
+    size_t argc = 7;
+    napi_value argv[7];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
+    if (!b || argc < 7) return throw_status(env, GE_ERR_ARG, "runRooms");
+    napi_typedarray_type tt[3];
+    size_t len[3];
+    void *data[3];
+    for (int k = 0; k < 3; k++) {
+        napi_value ab;
+        size_t off;
+        if (napi_get_typedarray_info(env, argv[1 + k], &tt[k], &len[k], &data[k], &ab, &off) != napi_ok)
+            return throw_status(env, GE_ERR_ARG, "runRooms", "typed arrays expected");
+    }
+    if (tt[0] != napi_biguint64_array || tt[1] != napi_biguint64_array || tt[2] != napi_uint32_array || len[0] != len[1] || len[1] != len[2])
+        return throw_status(env, GE_ERR_ARG, "runRooms", "BigUint64Array, BigUint64Array, Uint32Array of equal length");
+    uint32_t max_turns = 0, until = 0;
+    bool want_views = true;
+    if (napi_get_value_uint32(env, argv[4], &max_turns) != napi_ok || napi_get_value_uint32(env, argv[5], &until) != napi_ok ||
+        napi_get_value_bool(env, argv[6], &want_views) != napi_ok)
+        return throw_status(env, GE_ERR_ARG, "runRooms", "maxTurns, until (numbers), views (boolean) expected");
+    const size_t n = len[0];
+    // the library refuses a call past its caps (after its entry checks): no buffers for it (ArrayBuffers are created zero-filled)
+    const size_t slots = (max_turns <= 4096u && (uint64_t)n * max_turns <= (1ull << 20)) ? n * max_turns : 0;
+    void *pl = nullptr, *sp = nullptr, *ev = nullptr, *vw = nullptr;
+    napi_value pbuf, sbuf, ebuf, vbuf, parr, sarr, out;
+    NAPI_OK(napi_create_arraybuffer(env, n * sizeof(uint32_t), &pl, &pbuf));
+    NAPI_OK(napi_create_arraybuffer(env, n * sizeof(uint32_t), &sp, &sbuf));
+    NAPI_OK(napi_create_arraybuffer(env, slots * sizeof(ge_turn_event), &ev, &ebuf));
+    if (want_views) NAPI_OK(napi_create_arraybuffer(env, slots * sizeof(ge_room_view), &vw, &vbuf));
+    else NAPI_OK(napi_get_null(env, &vbuf));
+    const int st = ge_batch_run_rooms(b, n, static_cast<const uint64_t *>(data[0]), static_cast<const uint64_t *>(data[1]),
+                                      static_cast<const uint32_t *>(data[2]), max_turns, until, static_cast<uint32_t *>(pl),
+                                      static_cast<uint32_t *>(sp), static_cast<ge_turn_event *>(ev),
+                                      want_views && slots ? static_cast<ge_room_view *>(vw) : nullptr, want_views ? slots * sizeof(ge_room_view) : 0);
+    if (st != GE_OK) return throw_status(env, st, "runRooms");
+    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, n, pbuf, 0, &parr));
+    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, n, sbuf, 0, &sarr));
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_set_named_property(env, out, "played", parr));
+    NAPI_OK(napi_set_named_property(env, out, "stopped", sarr));
+    NAPI_OK(napi_set_named_property(env, out, "events", ebuf));
+    NAPI_OK(napi_set_named_property(env, out, "views", vbuf));
+    return out;
+}
+
 bool is_nullish(napi_env env, napi_value v) {
     napi_valuetype t;
     return napi_typeof(env, v, &t) == napi_ok && (t == napi_null || t == napi_undefined);
@@ -901,6 +952,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"readEvents", nullptr, ReadEvents, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"stepRooms", nullptr, StepRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"stepRoomsPlayout", nullptr, StepRoomsPlayout, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"runRooms", nullptr, RunRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"readRoomsAt", nullptr, ReadRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"rollout", nullptr, Rollout, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"writeRoomsAt", nullptr, WriteRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},

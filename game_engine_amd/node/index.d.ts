@@ -32,6 +32,9 @@ export interface Summary {
 export interface TurnEvent {
   turn: number; from_phase_id: number; to_phase_id: number; acted_now: number; restarted: number; choice: number[];
 }
+export type RunUntil = 'person' | 'end' | 'phase';
+export function runUntilBits(until: RunUntil[] | RunUntil | number): number;
+export function runUntilNames(bits: number): RunUntil[];
 export interface ToolCall { name: 'update_player_actions' | 'set_next_phase' | 'update_player_state' | 'add_game_note'; args: Record<string, unknown>; }
 export interface PhaseInfo { id: number; name: string; completion: number; act: number; effect: number; nBranches: number; }
 
@@ -71,6 +74,13 @@ export class RoomBatch {
   stepRoomsPlayout(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, masks: ArrayLike<number>,
                    playoutKeys: ArrayLike<number | bigint>, nRollouts: number, maxTurns?: number, seed?: number | bigint,
                    fullView?: boolean): { events: TurnEvent[]; decided: Uint32Array };
+  /** Play each listed room on until a person is needed (POLICY.md §3f): stepRooms's entries (rooms[k], keys[k], turns[k] + t) until the
+   *  turn leaves a state named in `until` ("person" | "end" | "phase", or the ABI's bits) or maxTurns turns are played.  events[k] /
+   *  views[k] hold one entry per played turn (views: false -> null); stopped[k] = the bits that held after the last turn (0: the limit).
+   *  Synchronous; GE_BUSY while an async step() is in flight. */
+  runRooms(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, maxTurns?: number,
+           until?: RunUntil[] | RunUntil | number, views?: boolean):
+    { played: Uint32Array; stopped: Uint32Array; events: TurnEvent[][]; views: RoomState[][] | null };
   /** Playouts of each listed room (replica r of entry k = global room keys[k] + r under seed, default the batch's): rooms.length x 77
    *  words of ge_rollout_stats (41 summary words, then seat_alive, seat_wins, seat_score x 12).  The batch is only read. */
   rolloutRooms(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, nRollouts: number,

@@ -499,6 +499,20 @@ class RoomLog {
   }
 }
 
+// include/ge_step.h GE_RUN_UNTIL_*
+const RUN_UNTIL = { person: 1, end: 2, phase: 4 };
+/** `until` of runRooms / runRoom as the ABI's bit set: an array of "person" / "end" / "phase", one of them, or the bits. */
+function runUntilBits(until) {
+  if (typeof until === 'number') return until;
+  let bits = 0;
+  for (const name of typeof until === 'string' ? [until] : until) {
+    if (!Object.prototype.hasOwnProperty.call(RUN_UNTIL, name)) throw new RangeError(`until: unknown stop condition ${JSON.stringify(name)}`);
+    bits |= RUN_UNTIL[name];
+  }
+  return bits;
+}
+function runUntilNames(bits) { return Object.keys(RUN_UNTIL).filter((name) => bits & RUN_UNTIL[name]); }
+
 function decodeEvent(buffer, off) {
   const dv = new DataView(buffer, off, EVENT_SIZE);
   return { turn: dv.getUint32(0, true), from_phase_id: dv.getInt32(4, true), to_phase_id: dv.getInt32(8, true),
@@ -594,6 +608,31 @@ class RoomBatch {
     const events = [];
     for (let k = 0; k < rooms.length; k++) events.push(decodeEvent(buffer, k * EVENT_SIZE));
     return { events, decided };
+  }
+  /** Play each listed room on until a person is needed (twin of the Python RoomBatch.run_rooms, POLICY.md §3f): room k takes
+   * stepRooms's entries (rooms[k], keys[k], turns[k] + t), t = 0, 1, ..., and stops after the first turn that leaves it in a state
+   * named in `until` - "person": a host-driven seat of its segment is a pending target (an injectAction of it would be accepted);
+   * "end": a terminal phase; "phase": the turn moved the phase - or after maxTurns turns; the first turn is always played.  `until`
+   * is an array of those names or the ABI's bit set.  Returns { played, stopped, events, views }: played[k] turns were played,
+   * stopped[k] has the RUN_UNTIL bits that held after the last one (0: the limit), events[k] / views[k] hold one stepRooms event
+   * and one readRoomsAt state per played turn (views: false -> null).  All-or-nothing like stepRooms; maxTurns outside 1 .. 4096,
+   * rooms.length * maxTurns above 2^20 or turns[k] + maxTurns above 0xFFFFFFFF throw and run nothing.  Synchronous; GE_BUSY while
+   * an async step() is in flight. */
+  runRooms(rooms, keys, turns, maxTurns = 64, until = ['person', 'end'], views = true) {
+    const bits = runUntilBits(until);
+    const r = addon.runRooms(this.handle, BigUint64Array.from(rooms, (x) => BigInt(x)), BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))),
+                             Uint32Array.from(turns), maxTurns, bits, !!views);
+    const events = [], states = views ? [] : null;
+    for (let k = 0; k < rooms.length; k++) {
+      const ev = [], vw = [];
+      for (let t = 0; t < r.played[k]; t++) {
+        ev.push(decodeEvent(r.events, (k * maxTurns + t) * EVENT_SIZE));
+        if (views) vw.push(decodeRoom(this.tableOf(Number(rooms[k])), r.views, (k * maxTurns + t) * VIEW.size));
+      }
+      events.push(ev);
+      if (views) states.push(vw);
+    }
+    return { played: r.played, stopped: r.stopped, events, views: states };
   }
   /** Playouts (twin of the Python RoomBatch.rollout_rooms): entry k is played nRollouts times from room rooms[k] as it stands,
    * replica r as global room keys[k] + r (mod 2^64) under `seed` (default: the batch's) at turns turns[k] .. turns[k] + maxTurns - 1,
@@ -803,5 +842,5 @@ class DeviceGroup {
 
 const { compileCriteria, audienceGroups, uiToolCalls } = require('./ui_script.js');
 
-module.exports = { GameTable, RoomBatch, decodeRoom, agentStateToView, ShardedBatch, DeviceGroup, locateInShards, RoomLog, formatNote, loadDslByGamename, findGameFile, initializePlayers, turnToolCalls, compileCriteria, audienceGroups, uiToolCalls,
+module.exports = { GameTable, RoomBatch, runUntilBits, runUntilNames, decodeRoom, agentStateToView, ShardedBatch, DeviceGroup, locateInShards, RoomLog, formatNote, loadDslByGamename, findGameFile, initializePlayers, turnToolCalls, compileCriteria, audienceGroups, uiToolCalls,
                    deviceCount: addon.deviceCount, addon };

@@ -11,7 +11,7 @@
  */
 const { GameTable, RoomBatch, RoomLog, decodeRoom, turnToolCalls, uiToolCalls } = require('./index.js');
 const { roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, adviseCandidates, adviseSeat, runRollouts, adviseOutput,
-        seatForecastOutput, checkForecastSeat, checkView, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, forecastKey, forecastSeed } = require('./room_service.js');
+        seatForecastOutput, checkForecastSeat, checkView, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, forecastKey, forecastSeed, checkRunArgs, checkRunThread, runTurn, runOutput } = require('./room_service.js');
 const popcount = (m) => { let c = 0; for (let x = m; x; x &= x - 1) c++; return c; };
 const M = require('./messages.js');
 
@@ -189,6 +189,46 @@ class RoomPoolService {
       const res = this._turns(play.map(([i]) => entries[i].room), play.map(([i]) => entries[i].items));
       play.forEach(([i, kind], k) => { out[i] = Object.assign(res[k], { played: true, kind }); });
       return out;
+    });
+  }
+  /** As RoomService.runRoom (same turns and output), from the thread's pool slot. */
+  runRoom(threadId, maxTurns = 64, until = ['person', 'end'], items) {
+    return this.runRooms([threadId], maxTurns, until, items === undefined || items === null ? undefined : [items]).then((o) => o[0]);
+  }
+  /** Play many threads on, each until a person is needed in it (RoomService.runRoom's conditions and output, in order): one
+   * RoomBatch.runRooms call per chunk touched, every thread under its own key and from its own turn.  items[j]: thread j's canvas
+   * items.  A thread named twice, an unknown thread, a thread with playout seats and bad arguments are refused before anything
+   * runs.  Every chunk's call is made before any turn is folded: if one of them fails (a device error), the threads of the chunks
+   * already run have moved on the device while no thread's turn or log has - such a service is to be closed, not continued. */
+  runRooms(threadIds, maxTurns = 64, until = ['person', 'end'], items) {
+    return this._serial(() => {
+      const bits = checkRunArgs(maxTurns, until);
+      if (new Set(threadIds).size !== threadIds.length) throw new RangeError('runRooms: a thread is named twice');
+      const rooms = Array.from(threadIds, (t) => this._room(t));
+      const its = items || [];
+      if (items && its.length !== rooms.length) throw new RangeError('runRooms: threadIds and items differ in length');
+      rooms.forEach((room, j) => {
+        checkRunThread(threadIds[j], room);
+        if (room.turn + maxTurns > 0xFFFFFFFF) throw new RangeError(`thread ${threadIds[j]}: the turn counter would overflow`);
+      });
+      const byChunk = new Map();
+      rooms.forEach((room, j) => {
+        if (!byChunk.has(room.chunk)) byChunk.set(room.chunk, []);
+        byChunk.get(room.chunk).push(j);
+      });
+      const perCall = Math.max(1, Math.floor((1 << 20) / maxTurns));   // the call's cap on n x maxTurns
+      const got = new Array(rooms.length);
+      for (const [chunk, all] of byChunk) {
+        for (let lo = 0; lo < all.length; lo += perCall) {
+          const js = all.slice(lo, lo + perCall);
+          const r = chunk.runRooms(js.map((j) => rooms[j].slot), js.map((j) => rooms[j].key), js.map((j) => rooms[j].turn), maxTurns, bits);
+          js.forEach((j, k) => { got[j] = { events: r.events[k], views: r.views[k], stopped: r.stopped[k] }; });
+        }
+      }
+      return rooms.map((room, j) => {
+        room.turn += got[j].events.length;
+        return runOutput(got[j].events.map((ev, t) => runTurn(this._finish(room, got[j].views[t], ev, its[j]))), got[j].stopped);
+      });
     });
   }
   /** As RoomService.forecast (same keys, seed, seat view and output), from the thread's pool slot. */

@@ -20,6 +20,9 @@ export interface AdoptOptions {
  * of each candidate's playouts, from the bot's own view ("seat", the default) or the true record ("full": a cheating bot). */
 export interface PlayoutOptions { playoutRollouts?: number; playoutMaxTurns?: number; playoutView?: 'seat' | 'full'; }
 export interface TurnResult { state: AgentStateView; toolCalls: ToolCall[]; uiCalls: FrontendToolCall[]; }
+/** runRoom: one TurnResult per played turn; stopped: the conditions that held after the last one ([]: the limit). */
+export type RunUntil = 'person' | 'end' | 'phase';
+export interface RunResult { turns: TurnResult[]; played: number; stopped: RunUntil[]; }
 /** How a thread ends from where it stands, over `rollouts` playouts (JSON integers: divide by rollouts for odds). */
 export interface Forecast {
   threadId: string; turn: number; rollouts: number; maxTurns: number;
@@ -61,6 +64,9 @@ export class RoomService {
   handleMessage(threadId: string, text: string, items?: { id: string; type: string }[]): Promise<TurnResult & { played: boolean; kind: 'chat' | 'control' | 'action' }>;
   /** items: the frontend's canvas items (AgentState.items), for clearCanvas's exemptList */
   continueRoom(threadId: string, items?: { id: string; type: string }[]): Promise<TurnResult>;
+  /** The thread played on until a person is needed (POLICY.md §3f): turns[t] is what continueRoom would have resolved for that turn.
+   *  Rejects with a RangeError, before anything runs, for a thread with playout seats, maxTurns outside 1 .. 4096 or an unknown condition. */
+  runRoom(threadId: string, maxTurns?: number, until?: RunUntil[], items?: { id: string; type: string }[]): Promise<RunResult>;
   /** nRollouts playouts (<= 65 536) of the thread's room, every seat played by the policy, keyed (threadKey << 16) + r under seed
    *  (service seed ^ 0x9E3779B97F4A7C15); the thread is not changed (INTEGRATION.md "Forecasting a thread").  seat: from what that
    *  seat knows (hidden roles / the lie dealt again per replica); the JSON gains "seat". */

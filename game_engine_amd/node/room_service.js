@@ -13,7 +13,7 @@
  * LangGraphAgent (route.ts:30-39); `serve()` exposes the same over plain HTTP for a quick try.
  */
 const http = require('http');
-const { GameTable, RoomBatch, RoomLog, agentStateToView, loadDslByGamename, turnToolCalls, uiToolCalls } = require('./index.js');
+const { GameTable, RoomBatch, RoomLog, agentStateToView, loadDslByGamename, turnToolCalls, uiToolCalls, runUntilBits, runUntilNames } = require('./index.js');
 const M = require('./messages.js');
 
 /** stable 48-bit room index from a thread id (the RNG is keyed by it) */
@@ -210,6 +210,24 @@ function adviseOutput(table, names, threadId, turn, seat, st, cands, nRollouts, 
   return out;
 }
 
+const RUN_MAX_TURNS = 4096;                         // ge_batch_run_rooms's cap on maxTurns
+/** runRoom's maxTurns and until, before anything runs; returns `until` as ge_batch_run_rooms's bit set. */
+function checkRunArgs(maxTurns, until) {
+  if (!Number.isInteger(maxTurns) || maxTurns < 1 || maxTurns > RUN_MAX_TURNS) throw new RangeError(`maxTurns must be 1 .. ${RUN_MAX_TURNS}`);
+  return runUntilBits(until);
+}
+function checkRunThread(threadId, room) {
+  if (room.playoutMask) throw new RangeError(`thread ${threadId} has playout seats: runRoom does not run playout bots, use continueRoom`);
+}
+/** One turn's output as runRoom keeps it: the state of a continueRoom output shares the thread's growing log (playerActions,
+ * phase_history, game_notes), and here later turns are folded before the caller sees the earlier ones - so those three are copied. */
+function runTurn(out) {
+  const st = out.state;
+  out.state = Object.assign({}, st, JSON.parse(JSON.stringify({ playerActions: st.playerActions, phase_history: st.phase_history, game_notes: st.game_notes })));
+  return out;
+}
+function runOutput(turns, stopped) { return { turns, played: turns.length, stopped: runUntilNames(stopped) }; }
+
 class RoomService {
   /** playoutRollouts / playoutMaxTurns / playoutView: how the playout bots of threads created with playoutSeats choose
    * (POLICY.md §3d): nRollouts and maxTurns of each candidate's playouts, and "seat" (from what the bot knows) or "full" (from
@@ -342,6 +360,26 @@ class RoomService {
     if (!room) return Promise.reject(new Error(`unknown thread ${threadId}`));
     return this._serial(room, () => this._continue(room, items));
   }
+  /** Play the thread on until a person is needed (twin of the Python RoomService.run_room): one RoomBatch.runRooms call (POLICY.md
+   * §3f) instead of a continueRoom per turn.  until: "person" (a human seat of the thread has an action to give), "end" (the game
+   * is over), "phase" (the turn moved the phase); the first turn is always played, at most maxTurns are.  Resolves { turns:
+   * [{ state, toolCalls, uiCalls }, ...], played, stopped }: element t is exactly what continueRoom would have resolved for that
+   * turn (items goes to every turn's UI builder as given), stopped names the conditions that held after the last turn ([]: the
+   * limit), and the thread's turn and panel end where `played` calls of continueRoom would have left them.  A thread with playout
+   * seats or bad arguments are refused (RangeError) before anything runs.  Every turn's state carries its own copy of the thread's
+   * log (runTurn): host work that grows with the log, per turn. */
+  runRoom(threadId, maxTurns = 64, until = ['person', 'end'], items) {
+    const room = this.rooms.get(threadId);
+    if (!room) return Promise.reject(new Error(`unknown thread ${threadId}`));
+    return this._serial(room, () => {
+      const bits = checkRunArgs(maxTurns, until);
+      checkRunThread(threadId, room);
+      const r = room.batch.runRooms([0], [room.key], [room.turn], maxTurns, bits);
+      room.turn += r.played[0];
+      room.batch.setTurn(room.turn);
+      return runOutput(r.events[0].map((ev, t) => runTurn(this._finish(room, r.views[0][t], ev, items))), r.stopped[0]);
+    });
+  }
   /**
    * The drop-in's message-level entry: what the reference's graph does with ONE message of the browser
    * (src/app/page.tsx:183-259 -> agent/game_agent_v2.py:198-349, agent/tools/utils.py:310-358; POLICY.md 3b).
@@ -388,7 +426,11 @@ class RoomService {
       event = room.batch.readEvents(0, 1)[0][0];
     }
     room.turn += 1;
-    const after = room.batch.readRoom(0);
+    return this._finish(room, room.batch.readRoom(0), event, items);
+  }
+  /** Fold one played turn - its event and the state after it - into the thread: the turn's tool calls, log, state and UI. */
+  _finish(room, after, event, items) {
+    const before = room.state;
     const toolCalls = turnToolCalls(room.table, before, after, event);
     // fold the calls into the log-shaped parts of AgentState the packed state does not carry
     // (playerActions / game_notes / phase_history, as backend_tools.py:163-202, 285-344 would)
@@ -410,6 +452,7 @@ class RoomService {
           let out;
           if (req.method === 'POST' && req.url === '/rooms') out = this.createRoom(msg);
           else if (req.method === 'POST' && req.url === '/continue') out = await this.continueRoom(msg.threadId, msg.items);
+          else if (req.method === 'POST' && req.url === '/run') out = await this.runRoom(msg.threadId, msg.maxTurns, msg.until, msg.items);
           else if (req.method === 'POST' && req.url === '/message') out = await this.handleMessage(msg.threadId, msg.text, msg.items);
           else if (req.method === 'POST' && req.url === '/action') out = await this.humanAction(msg.threadId, msg.playerId, msg.choice);
           else if (req.method === 'POST' && req.url === '/close') out = { closed: await this.close(msg.threadId) };
@@ -424,4 +467,4 @@ class RoomService {
 }
 
 module.exports = { RoomService, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput,
-                   adviseCandidates, adviseSeat, runRollouts, adviseOutput, seatForecastOutput, checkForecastSeat, checkView };
+                   adviseCandidates, adviseSeat, runRollouts, adviseOutput, seatForecastOutput, checkForecastSeat, checkView, checkRunArgs, checkRunThread, runTurn, runOutput };

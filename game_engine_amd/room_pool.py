@@ -18,8 +18,9 @@ import numpy as np
 
 from . import messages as M
 from .room_service import (PLAYOUT_CAP, RolloutRequest, adopted_output, advise_candidates, advise_output, advise_seat,
-                           check_forecast_args, check_forecast_seat, check_playout_options, check_view, forecast_key, forecast_seed,
-                           playout_mask, playout_max_cands, prepare_adoption, room_index_of, run_rollouts, seat_forecast_output)
+                           check_forecast_args, check_forecast_seat, check_playout_options, check_run_args, check_run_thread, check_view,
+                           forecast_key, forecast_seed, playout_mask, playout_max_cands, prepare_adoption, room_index_of, run_output,
+                           run_rollouts, run_turn, seat_forecast_output)
 from .stepper import GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, load_dsl_by_gamename, slot_values
 from .toolcalls import WW_IS_ALIVE, RoomLog, turn_tool_calls
 from .ui_script import ui_tool_calls
@@ -249,6 +250,48 @@ class RoomPoolService:
                 events[j], afters[j] = ev[k], views[k]
                 rooms[j]["turn"] += 1
         return [self._finish(room, afters[j], events[j], items[j]) for j, room in enumerate(rooms)]
+
+    def run_room(self, thread_id: str, max_turns: int = 64, until=("person", "end"),
+                 items: Optional[List[Dict[str, Any]]] = None) -> Dict[str, Any]:
+        """As RoomService.run_room (same turns and output), from the thread's pool slot."""
+        return self.run_rooms([thread_id], max_turns, until, None if items is None else [items])[0]
+
+    def run_rooms(self, thread_ids: Sequence[str], max_turns: int = 64, until=("person", "end"),
+                  items: Optional[Sequence[Optional[List[Dict[str, Any]]]]] = None) -> List[Dict[str, Any]]:
+        """Play many threads on, each until a person is needed in it (RoomService.run_room's conditions and output, in order):
+        one RoomBatch.run_rooms call per chunk touched, every thread under its own key and from its own turn.  items[j]: thread
+        j's canvas items.  A thread may be named once (ValueError); unknown threads (KeyError), threads with playout seats and
+        bad arguments (ValueError) are refused before anything runs.  Every chunk's call is made before any turn is folded: if
+        one of them raises (a device error), the threads of the chunks already run have moved on the device while no thread's
+        turn or log has - such a service is to be closed, not continued."""
+        bits = check_run_args(max_turns, until)
+        if len(set(thread_ids)) != len(thread_ids):
+            raise ValueError("run_rooms: a thread is named twice")
+        rooms = [self._rooms[tid] for tid in thread_ids]          # KeyError for an unknown thread, before anything runs
+        its = list(items) if items is not None else [None] * len(rooms)
+        if len(its) != len(rooms):
+            raise ValueError("run_rooms: thread_ids and items differ in length")
+        for tid, room in zip(thread_ids, rooms):
+            check_run_thread(tid, room)
+            if int(room["turn"]) + int(max_turns) > 0xFFFFFFFF:
+                raise ValueError(f"thread {tid!r}: the turn counter would overflow")
+        by_chunk: Dict[int, List[int]] = {}
+        for j, room in enumerate(rooms):
+            by_chunk.setdefault(id(room["chunk"]), []).append(j)
+        per_call = max(1, (1 << 20) // int(max_turns))             # the call's cap on n x max_turns
+        got: List[Any] = [None] * len(rooms)
+        for all_js in by_chunk.values():
+            for lo in range(0, len(all_js), per_call):
+                js = all_js[lo:lo + per_call]
+                played, stopped, events, views = rooms[js[0]]["chunk"].run_rooms(
+                    [rooms[j]["slot"] for j in js], [rooms[j]["key"] for j in js], [rooms[j]["turn"] for j in js], max_turns, bits)
+                for k, j in enumerate(js):
+                    got[j] = (int(played[k]), int(stopped[k]), events[k], views[k])
+        out = []
+        for room, (played, stopped, events, views), it in zip(rooms, got, its):
+            room["turn"] += played
+            out.append(run_output([run_turn(self._finish(room, views[t], events[t], it)) for t in range(played)], stopped))
+        return out
 
     def _step_playout(self, chunk, rooms: List[Dict[str, Any]], slots, keys, turns) -> np.ndarray:
         """step_rooms_playout of one chunk's rooms under advise's keys and seed, in runs under the call's cap."""

@@ -11,12 +11,13 @@ are folded from those calls exactly as the reference's `_execute_*` functions wo
 """
 from __future__ import annotations
 
+import copy
 import re
 from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 from . import messages as M
 from .stepper import (GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, agent_state_to_view, load_dsl_by_gamename, rollout_to_dict,
-                      slot_values, view_to_agent_state)
+                      run_until_bits, run_until_names, slot_values, view_to_agent_state)
 from .toolcalls import WW_IS_ALIVE, RoomLog, turn_tool_calls
 from .ui_script import ui_tool_calls
 
@@ -277,6 +278,33 @@ def advise_output(table: GameTable, names: List[str], thread_id: str, turn: int,
             **({"view": "seat"} if seat_view else {}), **({"compare": True} if cmp is not None else {})}
 
 
+RUN_MAX_TURNS = 4096                                        # ge_batch_run_rooms's cap on max_turns
+
+
+def check_run_args(max_turns: int, until) -> int:
+    """run_room's max_turns and until, before anything runs; returns `until` as ge_batch_run_rooms's bit set."""
+    if not 1 <= int(max_turns) <= RUN_MAX_TURNS:
+        raise ValueError(f"max_turns must be 1 .. {RUN_MAX_TURNS}")
+    return run_until_bits(until)
+
+
+def check_run_thread(thread_id: str, room: Dict[str, Any]) -> None:
+    if room["playout_mask"]:
+        raise ValueError(f"thread {thread_id!r} has playout seats: run_room does not run playout bots, use continue_room")
+
+
+def run_turn(out: Dict[str, Any]) -> Dict[str, Any]:
+    """One turn's output as run_room keeps it: the state of a continue_room output shares the thread's growing log
+    (playerActions, phase_history, game_notes), and here later turns are folded before the caller sees the earlier ones - so
+    those three are copied.  The copy grows with the log: host work per turn that a continue_room caller does not pay."""
+    out["state"] = {**out["state"], **{k: copy.deepcopy(out["state"][k]) for k in ("playerActions", "phase_history", "game_notes")}}
+    return out
+
+
+def run_output(turns: List[Dict[str, Any]], stopped: int) -> Dict[str, Any]:
+    return {"turns": turns, "played": len(turns), "stopped": run_until_names(stopped)}
+
+
 class RoomService:
     def __init__(self, games_dir: str = "games", seed: int = 0, device: int = 0, playout_rollouts: int = 256,
                  playout_max_turns: int = 256, playout_view: str = "seat"):
@@ -414,7 +442,11 @@ class RoomService:
         else:
             batch.step(1)
             event = batch.read_events(0, 1)[0][0]
-        after = batch.read_rooms(0, 1)[0]
+        return self._finish(room, batch.read_rooms(0, 1)[0], event, items)
+
+    def _finish(self, room: Dict[str, Any], after, event, items) -> Dict[str, Any]:
+        """Fold one played turn - its event and the view after it - into the thread: the turn's tool calls, log, state and UI."""
+        before = room["view"]
         calls = turn_tool_calls(room["table"], before, after, event)
         room["log"].fold(calls, after)                      # playerActions / game_notes / phase_history, as bt:163-202, 285-344 would
         room["view"] = after
@@ -424,6 +456,24 @@ class RoomService:
         ui = ui_tool_calls(room["table"].dsl, state, room["table"], turn=int(event["turn"]), deaths=deaths, items=items)
         room["panel"] = M.newest_panel(ui)                # what a person's next vote message can answer
         return {"state": state, "toolCalls": calls, "uiCalls": ui}
+
+    def run_room(self, thread_id: str, max_turns: int = 64, until=("person", "end"),
+                 items: Optional[List[Dict[str, Any]]] = None) -> Dict[str, Any]:
+        """Play the thread on until a person is needed: one RoomBatch.run_rooms call (POLICY.md §3f) instead of a continue_room
+        per turn.  until: "person" (a human seat of the thread has an action to give), "end" (the game is over), "phase" (the
+        turn moved the phase); the first turn is always played, at most max_turns are.  Returns {"turns": [{state, toolCalls,
+        uiCalls}, ...], "played": p, "stopped": [...]}: element t is exactly what continue_room would have returned for that
+        turn (items goes to every turn's UI builder as given), "stopped" names the conditions that held after the last turn
+        ([]: the limit), and the thread's turn and panel end where p calls of continue_room would have left them.  A thread
+        with playout seats is refused (ValueError) before anything runs.  Every turn's state carries its own copy of the thread's
+        log (run_turn): host work that grows with the log, per turn."""
+        room = self._rooms[thread_id]
+        bits = check_run_args(max_turns, until)
+        check_run_thread(thread_id, room)
+        batch, turn = room["batch"], room["batch"].turn
+        played, stopped, events, views = batch.run_rooms([0], [room["key"]], [turn], max_turns, bits)
+        batch.set_turn(turn + int(played[0]))
+        return run_output([run_turn(self._finish(room, views[0, t], events[0, t], items)) for t in range(int(played[0]))], int(stopped[0]))
 
     def forecast(self, thread_id: str, n_rollouts: int = 4096, max_turns: int = 1024, seat: Optional[int] = None) -> Dict[str, Any]:
         """How the thread ends from where it stands: n_rollouts playouts of its room (RoomBatch.rollout_rooms), each played for

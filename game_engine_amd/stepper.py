@@ -40,6 +40,27 @@ GE_ERR_ARG = -1                           # include/ge_step.h ge_status
 GE_MAX_PLAYERS = 12                       # include/ge_step.h
 
 
+RUN_UNTIL = {"person": 1, "end": 2, "phase": 4}   # include/ge_step.h GE_RUN_UNTIL_*
+
+
+def run_until_bits(until) -> int:
+    """`until` of run_rooms / run_room as the ABI's bit set: a sequence of "person" / "end" / "phase", or the bits themselves."""
+    if isinstance(until, (int, np.integer)):
+        return int(until)
+    if isinstance(until, str):
+        until = (until,)
+    bits = 0
+    for name in until:
+        if name not in RUN_UNTIL:
+            raise ValueError(f"until: unknown stop condition {name!r}")
+        bits |= RUN_UNTIL[name]
+    return bits
+
+
+def run_until_names(bits: int) -> List[str]:
+    return [name for name, bit in RUN_UNTIL.items() if bits & bit]
+
+
 class GeError(RuntimeError):
     def __init__(self, status: int, what: str = ""):
         msg = _lib.load().ge_strerror(status).decode()
@@ -314,6 +335,37 @@ class RoomBatch:
                                                      self._seed if seed is None else seed, flags, events.ctypes.data,
                                                      decided.ctypes.data), "ge_batch_step_rooms_playout")
         return events, decided
+
+    def run_rooms(self, rooms, keys, turns, max_turns: int = 64, until=("person", "end"),
+                  views: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """Play each listed room on until a person is needed (POLICY.md §3f): room k takes step_rooms's entries (rooms[k], keys[k],
+        turns[k] + t), t = 0, 1, ..., and stops after the first turn that leaves it in a state named in `until` - "person": a
+        host-driven seat of its segment is a pending target (an inject_action of it would be accepted); "end": a terminal phase;
+        "phase": the turn moved the phase - or after max_turns turns; the first turn is always played.  `until` is a sequence of
+        those names or the ABI's bit set.  Returns (played, stopped, events, views): played[k] turns were played, stopped[k] has
+        the RUN_UNTIL bits that held after the last one (0: the limit), events / views have shape (n, max_turns) and hold, below
+        played[k], each turn's step_rooms event and the read_rooms_at view after it (index them only there; views=False: None).
+        All-or-nothing like step_rooms; also max_turns outside 1 .. 4096, n * max_turns above 2^20 or turns[k] + max_turns
+        above 0xFFFFFFFF raise and run nothing."""
+        rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        turns = np.ascontiguousarray(turns, dtype=np.uint32)
+        if not (len(rooms) == len(keys) == len(turns)):
+            raise GeError(-1, "run_rooms: arrays differ in length")
+        bits = run_until_bits(until)
+        if int(max_turns) < 0 or int(max_turns) > 0xFFFFFFFF:   # no uint32 at all (0 and values above the cap go to the library's checks)
+            raise GeError(GE_ERR_ARG, "run_rooms: max_turns")
+        n, cap = len(rooms), int(max_turns)
+        if n * cap > 1 << 20 or cap > 4096:                      # the library refuses these (after its entry checks): no arrays for them
+            cap = 0
+        played = np.zeros(n, dtype=np.uint32)
+        stopped = np.zeros(n, dtype=np.uint32)
+        events = np.zeros((n, cap), dtype=EVENT_DTYPE)
+        out = np.zeros((n, cap), dtype=ROOM_VIEW_DTYPE) if views else None
+        _check(self._lib.ge_batch_run_rooms(self._h, n, rooms.ctypes.data, keys.ctypes.data, turns.ctypes.data, max_turns, bits,
+                                            played.ctypes.data, stopped.ctypes.data, events.ctypes.data,
+                                            out.ctypes.data if views else None, out.nbytes if views else 0), "ge_batch_run_rooms")
+        return played, stopped, events, out
 
     def read_rooms_at(self, rooms) -> np.ndarray:
         """Canonical views of the listed rooms, out[k] = room rooms[k] (any order, repeats allowed)."""

@@ -44,7 +44,8 @@ extern "C" {
  *      ge_batch_rollout_actions (playouts that start from given actions: win odds per choice a seat can make now);
  *      ge_batch_rollout_seats (the same playouts from what one seat knows: hidden roles / the lie dealt again per replica);
  *      ge_batch_step_rooms_playout + GE_PLAYOUT_FULL_VIEW (playout seats: bots that choose each action by their own playouts);
- *      ge_batch_rollout_compare + ge_compare_stats (an entry against a baseline entry, playout by playout: the paired counts) */
+ *      ge_batch_rollout_compare + ge_compare_stats (an entry against a baseline entry, playout by playout: the paired counts);
+ *      ge_batch_run_rooms + GE_RUN_UNTIL_* (listed rooms played on until a person is needed: many turns per call, every turn traced) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -424,6 +425,35 @@ int ge_batch_step_rooms_playout(ge_batch *b, uint64_t n, const uint64_t *rooms, 
                                 const uint32_t *playout_masks /* n: bit i = seat i+1 */, const uint64_t *playout_keys /* n */,
                                 uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, uint32_t flags,
                                 ge_turn_event *events /* n, may be NULL */, uint32_t *decided /* n, may be NULL */);
+
+/* Listed rooms played on until a person is needed (POLICY.md §3f).  Room k is stepped by ge_batch_step_rooms's entries (rooms[k],
+ * keys[k], turns[k] + t) for t = 0, 1, ...  The first turn is always played (a "Continue" plays a turn whatever the state); after
+ * each played turn the conditions named in `until` are tested on the record it left, and the room stops after the first turn for
+ * which one holds, or after max_turns turns:
+ *   GE_RUN_UNTIL_PERSON  the phase's completion is player_action and some seat of the segment's human_mask is a pending target:
+ *                        ge_batch_inject_action(room, seat, c) would be accepted for at least one choice c
+ *   GE_RUN_UNTIL_END     the phase is terminal (with or without GE_FLAG_RESTART; under restart the next call's first turn recycles
+ *                        the room, as ge_batch_step_rooms does)
+ *   GE_RUN_UNTIL_PHASE   the turn's event has to_phase_id != from_phase_id
+ * played[k] = turns played; stopped[k] (may be NULL) = the bits of the named conditions that held after the last played turn (0: the
+ * limit was hit).  events[k * max_turns + t] and views[k * max_turns + t] (either may be NULL), t < played[k], are exactly that
+ * turn's ge_batch_step_rooms event and the ge_batch_read_rooms_at view taken after it; slots at t >= played[k] are untouched.  The
+ * stored record is the one after the last played turn, without a prepared deal; unlisted rooms, the turn counter and the
+ * GE_FLAG_TRACE buffer are untouched.  So max_turns = 1 is ge_batch_step_rooms word for word, and until = 0 is max_turns calls of it.
+ * All-or-nothing, nothing runs on an error, in this order: ge_batch_step_rooms's checks; GE_ERR_ARG for played NULL with n > 0,
+ * max_turns == 0 or > 4096, n * max_turns > 2^20, unknown `until` bits, or views with views_cap_bytes < n * max_turns *
+ * sizeof(ge_room_view); GE_ERR_RANGE for turns[k] + max_turns > 0xFFFFFFFF.  n == 0: GE_OK.  One launch per segment present; each
+ * turn's event and packed record go to a device trace plane (64 B per room-turn), and only the turns somebody played cross to the
+ * host.  With ge_batch_set_timing on, ge_batch_kernel_time includes the call's launches.  Ordered behind the previous step;
+ * synchronises. */
+#define GE_RUN_UNTIL_PERSON 1u   /* stop after a turn that leaves the room waiting for a host-driven seat */
+#define GE_RUN_UNTIL_END    2u   /* ... in a terminal phase */
+#define GE_RUN_UNTIL_PHASE  4u   /* ... after a turn whose event has to_phase_id != from_phase_id */
+int ge_batch_run_rooms(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
+                       uint32_t max_turns, uint32_t until,
+                       uint32_t *played /* n */, uint32_t *stopped /* n, may be NULL */,
+                       ge_turn_event *events /* n * max_turns, may be NULL */,
+                       ge_room_view *views /* n * max_turns, may be NULL */, size_t views_cap_bytes);
 
 /* GE_FLAG_TRACE: events of the most recent ge_batch_step call, dst[(room - first) * *n_turns + t].
  * cap_bytes >= count * n_turns * sizeof(ge_turn_event).  Synchronises. */

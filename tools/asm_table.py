@@ -36,6 +36,9 @@ def describe(mangled: str) -> dict:
     m = re.search(r"ge_pool_kernelILi(\d)ELi(\d)E", mangled)
     if m:
         return {"kernel": "ge_pool_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True}
+    m = re.search(r"ge_run_kernelILi(\d)ELi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_run_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True}
     m = re.search(r"ge_rollout_kernelILi(\d)ELi(\d)E(?:Li(\d)E)?", mangled)
     if m:
         return {"kernel": "ge_rollout_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True,
@@ -71,6 +74,8 @@ def collect(rebuild=True):
 def label(r):
     if r["kernel"] == "ge_pool_kernel":                          # ge_batch_step_rooms: one launch per segment present
         return f"{r['layout']}, indexed single-turn (ge_batch_step_rooms)" + (", GENERIC" if r["generic"] else "")
+    if r["kernel"] == "ge_run_kernel":                           # ge_batch_run_rooms: one launch per segment present
+        return f"{r['layout']}, indexed turn loop (ge_batch_run_rooms)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_rollout_kernel" and r.get("act") == 3:  # ge_batch_rollout_compare: one launch per segment present
         return f"{r['layout']}, playouts that keep their outcome (ge_batch_rollout_compare)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_rollout_kernel" and r.get("act") == 2:  # ge_batch_rollout_seats: one launch per segment present
