@@ -100,6 +100,10 @@ template <int NB, bool LOWOCC, bool SINGLE = false> struct WwBuild {
     static constexpr int DEAL_FORM = SINGLE ? 2 : LOWOCC ? 0 : NB <= 8 ? 1 : 2;   // DEAL_PACKED / DEAL_MASKS / DEAL_WORDS, see struct Deal
     static constexpr bool DEAL_EARLY = GE_DEAL_EARLY && !LOWOCC && !SINGLE;   // the deal is prepared at the head of the turn, not in the queue's second LDS shadow (see ww_turn)
     static constexpr bool TABLE = !LOWOCC;                  // n-th-set-bit through the 2 KB LDS table instead of ~15 VALU instructions
+    // the fused lone-wavefront turn of Werewolf x 8 may recycle a finished room where it enters its terminal row (ww_apply_effect,
+    // WwRestart) instead of by a divergent block at the head of the next turn: run_ww takes that loop for the single-game, non-generic
+    // kernel.  (The Detective's result without compares, ww_queue_actions, is not governed by this: every fused ONEHOT build has it)
+    static constexpr bool LONE = LOWOCC && NB <= 8 && !SINGLE;
 };
 
 // ---- POLICY.md §RNG: stateless 32-bit counter hash
@@ -398,6 +402,14 @@ __device__ __forceinline__ uint32_t bit_mask(uint32_t x, uint32_t pos) {
     return m;
 }
 __device__ __forceinline__ uint32_t bfi(uint32_t m, uint32_t a, uint32_t b) { return (m & a) | (~m & b); }
+// the same with `a` wave-uniform, as ONE instruction: left to itself the compiler ANDs the scalar operand into a register first
+// (two instructions per select; peephole.sed then turns this one into the v_bitop3_b32 of the same table).  `a` MUST be wave-uniform:
+// nothing checks it, and for a per-lane value the "s" constraint makes the compiler take lane 0's through v_readfirstlane, silently
+__device__ __forceinline__ uint32_t bfi_uniform(uint32_t m, uint32_t a, uint32_t b) {
+    uint32_t r;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(m), "s"(a), "v"(b));
+    return r;
+}
 
 // ww_choose for a queue slot of the lone-wavefront build, N <= 8 (WwBuild::ONEHOT).  x = alive | team_w << 16 | kind << 28 with
 // the action kind ONE-HOT (bit 28 wolf target, 29 doctor, 30 detective, 31 day vote); `det_voter`: by day, the Detective's
@@ -787,6 +799,18 @@ struct WwCtx {
     uint32_t term_mask;        // bit r = row r is terminal (no next_phase branch): all a single-turn launch needs of the row it moves to
 };
 
+// Recycling at the tail of a turn (WwBuild::LONE; the caller's turn loop passes one with TAILR = true).  A room that enters a
+// terminal row on a turn that is not the launch's last is, for every later turn, the fresh room with one more game: so the
+// move itself writes the fresh room - one bit-select per state word by a lane mask, and the fresh room's row through the
+// one LDS read the move issues anyway - and the turn loop's head has no restart block.  A room that is ALREADY terminal when
+// the launch loads it is recycled in front of the loop (run_ww); a table whose first phase is terminal keeps the head form.
+template <int NB> struct WwRestart {
+    const WWR<NB> *s0;         // the fresh room (wave-uniform: scalar registers)
+    uint32_t term_rs;          // in: the table's terminal-row mask if a room may be recycled at the end of this turn, else 0
+    uint32_t restarted;        // out: 1 = the lane was recycled at the end of this turn (the next turn's `restarted` trace bit)
+    uint32_t q;                // out: the row the turn moved to (a recycled lane's terminal row: what the trace records)
+};
+
 // ---- who must act: target_players.condition AND alive, all players at once.
 // The 12 base predicates live packed in s.W; the row carries byte-permute selectors that pull each term's mask out of
 // the word pairs (0xFF where the term is elsewhere / absent), so the condition is 2-3 v_perm + AND, XOR with the
@@ -873,7 +897,7 @@ __device__ __forceinline__ void ww_prepare_deal(const WWR<NB> &s, const WwCtx &c
 // read (WwBuild::SHADOW), else run after the queue.
 struct WwActs { uint32_t newly, det_v, det_w; };   // who acted now; the Detective's new knowledge (villager / werewolf)
 
-template <int NB, bool LOWOCC, typename S1, typename S2>
+template <int NB, bool LOWOCC, bool FUSED = false, typename S1, typename S2>
 __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uint32_t T, uint32_t act, bool night, uint32_t alive, uint32_t team_w,
                                                  uint32_t r_det, uint32_t tk, WwActs &out, S1 &&shadow1, S2 &&shadow2, Stamps *stamps) {
     using nib_t = typename WWR<NB>::nib_t;
@@ -1027,7 +1051,15 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
     s.choice = (s.choice & ~m15) | got;
     // RefereeNode (A): record the action (bt:204-225 update_player_state)
     s.sel = night ? ((s.sel & ~m15) | got) : s.sel;
-    {
+    if (B::ONEHOT && FUSED) {
+        // the lowest non-zero choice nibble is the first new actor's (a choice is >= 1); no actor: nibble 7 = 0, and (1 << 0) >> 1 = 0.
+        // `act == ACT_DETECTIVE` is bit 2 of the one-hot kind: a mask, no compare
+        const uint32_t g = (uint32_t)got;
+        const uint32_t ch = (g >> ((uint32_t)__builtin_ctz(g | 0x80000000u) & 28u)) & 15u;
+        const uint32_t tb = ((1u << ch) >> 1) & bit_mask(kind, 2u);
+        out.det_w = tb & team_w;
+        out.det_v = tb & ~team_w;
+    } else {
         const uint32_t ch = (uint32_t)(got >> (4u * ctz(newly | 0x80000000u))) & 15u;
         const uint32_t tb = (act == ACT_DETECTIVE && newly) ? (1u << ((ch - 1u) & 15u)) : 0u;
         out.det_w = tb & team_w;
@@ -1050,13 +1082,18 @@ __device__ __forceinline__ uint32_t ww_decide(const WWR<NB> &s, uint32_t comp, u
 }
 
 // ---- RefereeNode (B): the effect of entering row q = qe & 31 (qe >> 5 = its entry effect), then the move itself
-template <int NB, bool LOWOCC, bool SINGLE>
+// TAILR: lanes of `rmask` (0 / ~0 per lane) entered a terminal row and are recycled here: they leave as the fresh room *s0 with one
+// more game (WwRestart; `qrow` is then already the fresh room's row).  That form runs for EVERY lane, not inside a divergent block
+// of the lanes that move: `moved` (0 / ~0) masks the entry effect and the few unconditional writes instead.  Some room of 64 moves
+// on every turn, so the block never skipped anything; it cost its exec-mask sequence, two branches, and a dozen register copies
+// per turn where the values it had and had not changed met again
+template <int NB, bool LOWOCC, bool SINGLE, bool TAILR = false>
 __device__ __forceinline__ void ww_apply_effect(WWR<NB> &s, const DevRow &row, const DevRow &qrow, const WwCtx &c, uint32_t qe, uint32_t alive, uint32_t ALL, uint32_t turn,
-                                                Deal &deal, WWR<NB> &dealt) {
+                                                Deal &deal, WWR<NB> &dealt, uint32_t rmask = 0u, const WWR<NB> *s0 = nullptr, uint32_t moved = ~0u) {
     using R = WWR<NB>;
     using nib_t = typename R::nib_t;
     using B = WwBuild<NB, LOWOCC, SINGLE>;
-    const uint32_t q = qe & 31u, eff = qe >> 5, p_eff = (row.r0 >> 5) & 7u;
+    const uint32_t q = qe & 31u, eff = TAILR ? (qe >> 5) & moved : qe >> 5, p_eff = (row.r0 >> 5) & 7u;
     // night / day resolution: the plurality victim dies unless the (highest-id living) Doctor guards it
     auto resolve = [&](bool on, bool day) {
         const uint32_t voters = day ? (alive & s.acted) : (alive & s.template get<F_WOLF>());
@@ -1107,21 +1144,43 @@ __device__ __forceinline__ void ww_apply_effect(WWR<NB> &s, const DevRow &row, c
     const bool nbeg = eff == EFF_NIGHT_BEGIN;
     s.template clear<F_SUB>(nbeg ? R::FM : 0u);
     s.sel = nbeg ? nib_t(0) : s.sel;
-    s.acted = 0; s.choice = 0;
-    s.flags = (s.flags & FLAG_PHASE0_DONE) | (p_eff << 1);
-    s.prev = s.phase;
-    s.phase = q;
-    const bool terminal = SINGLE ? ((c.term_mask >> q) & 1u) != 0u : ((qrow.r0 >> 11) & 7u) == 0u;
-    s.end_turn = (terminal && s.end_turn == END_NONE) ? (turn < 0xFFFEu ? turn : 0xFFFEu) : s.end_turn;
+    if (!TAILR) {
+        s.acted = 0; s.choice = 0;
+        s.flags = (s.flags & FLAG_PHASE0_DONE) | (p_eff << 1);
+        s.prev = s.phase;
+        s.phase = q;
+        const bool terminal = SINGLE ? ((c.term_mask >> q) & 1u) != 0u : ((qrow.r0 >> 11) & 7u) == 0u;
+        s.end_turn = (terminal && s.end_turn == END_NONE) ? (turn < 0xFFFEu ? turn : 0xFFFEu) : s.end_turn;
+    } else {
+        s.acted &= ~moved; s.choice &= (nib_t)~moved;
+        s.flags = bfi(moved, (s.flags & FLAG_PHASE0_DONE) | (p_eff << 1), s.flags);
+        s.prev = bfi(moved, s.phase, s.prev);
+        s.phase = q;                                           // (a lane that stays has q == s.phase)
+        const bool terminal = ((qrow.r0 >> 11) & 7u) == 0u;
+        s.end_turn = (terminal && moved != 0u && s.end_turn == END_NONE) ? (turn < 0xFFFEu ? turn : 0xFFFEu) : s.end_turn;
+    }
+    if (TAILR) {
+#pragma unroll
+        for (int k = 0; k < R::NW; k++) s.W[k] = bfi_uniform(rmask, s0->W[k], s.W[k]);
+        s.acted |= rmask & s0->acted; s.choice |= (nib_t)rmask & s0->choice;      // (both were just cleared)
+        s.det_v = bfi_uniform(rmask, s0->det_v, s.det_v); s.det_w = bfi_uniform(rmask, s0->det_w, s.det_w);
+        s.sel = (nib_t)bfi_uniform(rmask, (uint32_t)s0->sel, (uint32_t)s.sel);
+        s.phase = bfi_uniform(rmask, s0->phase, s.phase); s.prev = bfi_uniform(rmask, s0->prev, s.prev);
+        s.flags = bfi_uniform(rmask, s0->flags, s.flags); s.end_turn = bfi_uniform(rmask, s0->end_turn, s.end_turn);
+        const uint32_t g = s.games - rmask;                                       // + 1 for a recycled lane, saturating (games <= 0xFFFF)
+        s.games = g < 0xFFFFu ? g : 0xFFFFu;
+    }
 }
 
 // `row` is the table row of s.phase, kept in registers across turns: LDS is read only on a transition (a single-turn
 // build leaves it as it is: nobody reads it after the turn).
 // tk_io: in = turn_key(rkey, turn), out = the next turn's key (computed in an LDS wait shadow; not in a single-turn build).
 // ev_*: this turn's logged actions (who acted, what they chose) for the optional event trace.
-template <int NB, bool LOWOCC, int GENERIC = false, bool SINGLE = false>
+// TAILR: rooms that finish are recycled at the end of the turn (`rst`, WwRestart)
+template <int NB, bool LOWOCC, int GENERIC = false, bool SINGLE = false, bool TAILR = false>
 __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c, uint32_t turn, uint32_t &tk_io, bool trace, Deal &deal, bool deal_now,
-                                        uint32_t &ev_newly, uint64_t &ev_choice, Stamps *stamps = nullptr) {
+                                        uint32_t &ev_newly, uint64_t &ev_choice, Stamps *stamps = nullptr, WwRestart<NB> *rst = nullptr) {
+    static_assert(!TAILR || (NB <= 8 && LOWOCC && !SINGLE), "tail recycling is the fused lone-wavefront Werewolf x 8 form");
     using R = WWR<NB>;
     using B = WwBuild<NB, LOWOCC, SINGLE>;
     const uint32_t ALL = (1u << c.n) - 1u;
@@ -1137,7 +1196,7 @@ __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c,
     if (B::DEAL_EARLY) ww_prepare_deal<NB, LOWOCC, SINGLE>(s, c, deal, deal_now, ALL, dealt);
     uint32_t tk_next = 0;
     WwActs acts;
-    ww_queue_actions<NB, LOWOCC>(s, c, T, act, night, alive, team_w, r_det, tk_io, acts,
+    ww_queue_actions<NB, LOWOCC, !SINGLE>(s, c, T, act, night, alive, team_w, r_det, tk_io, acts,
         [&]() {
             ww_phase_branch<NB>(s, row, c.phase0_idx, alive, team_w, br);
             if (B::SHADOW) asm volatile("" : "+v"(br.qe));     // stays in the shadow: not sunk below the queue loop
@@ -1174,6 +1233,18 @@ __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c,
     }
     if (SINGLE) {
         if ((qe & 31u) != s.phase) ww_apply_effect<NB, LOWOCC, true>(s, row, row, c, qe, alive, ALL, turn, deal, dealt);
+    } else if (TAILR) {
+        // every lane, no divergent block (ww_apply_effect); a lane that stays reads its own row again
+        const uint32_t q = qe & 31u;
+        const uint32_t moved = 0u - (uint32_t)(q != s.phase);
+        // ~0: the lane enters a terminal row and is recycled.  (A lane that STAYS in a terminal row has term_rs == 0: it was loaded
+        // terminal and recycled in front of the loop unless restart is off, and the first phase is not terminal - run_ww)
+        const uint32_t rmask = bit_mask(rst->term_rs, q);
+        const DevRow qrow = lds_row<false>(c.rows, bfi_uniform(rmask, c.phase0_idx, q));   // (the fresh room's row for those)
+        ww_apply_effect<NB, LOWOCC, false, true>(s, row, qrow, c, qe, alive, ALL, turn, deal, dealt, rmask, rst->s0, moved);
+        row = qrow;
+        rst->q = q;
+        rst->restarted = rmask & 1u;
     } else if ((qe & 31u) != s.phase) {
         const DevRow qrow = lds_row<!LOWOCC>(c.rows, qe & 31u);         // LDS read in flight during the effect: first used at its end
         ww_apply_effect<NB, LOWOCC, false>(s, row, qrow, c, qe, alive, ALL, turn, deal, dealt);

@@ -179,7 +179,8 @@ __device__ __forceinline__ void load_init_regs(const SegDev &sg, uint32_t *ir) {
 // (profiles/r03_ab_deal_period_12.txt: every 16th / 32nd / 64th turn = 18.37 / 18.21 / 19.53 us per turn at 2 M x 12)
 template <int NB> constexpr uint32_t deal_period() { return NB <= 8 ? GE_DEAL_PERIOD : 2u * GE_DEAL_PERIOD; }
 
-template <int NB, bool LOWOCC, int GENERIC, bool SINGLE, int LD = 0>
+// MIXED: called from the mixed-batch kernel (which keeps the head form of the restart: see the turn loop below)
+template <int NB, bool LOWOCC, int GENERIC, bool SINGLE, int LD = 0, bool MIXED = false>
 __device__ __forceinline__ void run_ww(const SegDev *__restrict__ sgp, const StepArgs &a, DevRow *rows, void *lw,
                                        uint8_t *nth8, const DevTable *__restrict__ tables, uint64_t room_in) {
     const SegDev &sg = *sgp;
@@ -307,13 +308,29 @@ __device__ __forceinline__ void run_ww(const SegDev *__restrict__ sgp, const Ste
         DevRow row0 = row;
         if (LOWOCC) { s0 = fresh_room(); row0 = lds_row<!LOWOCC && !SINGLE>(rows, sg.phase0_idx); }
         // the turn loop; the lone-wavefront build compiles it once per trace setting: the event-trace branches (two per turn,
-        // both wave-uniform and almost always taken) cost a lone wavefront an instruction-fetch bubble each
-        auto turns = [&](auto trace_c) {
+        // both wave-uniform and almost always taken) cost a lone wavefront an instruction-fetch bubble each.
+        // TAILR (the lone-wavefront Werewolf x 8 build, WwBuild::LONE): a room that finishes is recycled by the move into its
+        // terminal row (ge_device.h WwRestart), not by a divergent block at the head of the next turn - that block was two dozen
+        // register moves on four turns of five (some room of 64 finishes) and a branch on every turn.  Rooms that are terminal
+        // as loaded are recycled once, in front of the loop
+        auto turns = [&](auto trace_c, auto tail_c) {
             constexpr bool KNOWN = decltype(trace_c)::value != 2;
+            constexpr bool TAILR = decltype(tail_c)::value;
             const bool trace = KNOWN ? decltype(trace_c)::value == 1 : a.trace != 0u;
+            uint32_t restarted_in = 0;
+            WwRestart<NB> rst = {&s0, 0u, 0u, 0u};
+            uint32_t term_r = a.restart ? term_mask : 0u;
+            if (TAILR) asm volatile("" : "+s"(term_r));          // one scalar across the loop, not the test of a.restart again on every turn
+            if (TAILR && a.restart && a.n_turns != 0u && ((row.r0 >> 11) & 7u) == 0u) {   // finished as loaded
+                const uint32_t g = s.games;
+                s = s0;
+                s.games = g < 0xFFFFu ? g + 1u : g;
+                row = row0;
+                restarted_in = 1;
+            }
             for (uint32_t t = 0; t < a.n_turns; t++) {
-                uint32_t restarted = 0;
-                if (a.restart && ((row.r0 >> 11) & 7u) == 0u) {      // recycle a finished room
+                uint32_t restarted = TAILR ? restarted_in : 0u;
+                if (!TAILR && a.restart && ((row.r0 >> 11) & 7u) == 0u) {      // recycle a finished room
                     const uint32_t g = s.games;
                     s = LOWOCC ? s0 : fresh_room();
                     s.games = g < 0xFFFFu ? g + 1u : g;
@@ -324,14 +341,21 @@ __device__ __forceinline__ void run_ww(const SegDev *__restrict__ sgp, const Ste
                 uint32_t ev_newly = 0;
                 uint64_t ev_choice = 0;
                 const bool deal_now = ahead && ((deal_phase + t) & (deal_period<NB>() - 1u)) == 0u;    // wave-uniform
-                ww_turn<NB, LOWOCC, GENERIC, false>(s, row, ctx, turn0 + t, tk, trace, deal, deal_now, ev_newly, ev_choice, (GE_STAMPS && a.stamps) ? &stamps : nullptr);
-                if (trace && valid) store_event(sg.trace, sg.rooms_padded, t, room, turn0 + t, p, s.phase, restarted, ev_newly, ev_choice);
+                if (TAILR) rst.term_rs = t + 1u < a.n_turns ? term_r : 0u;           // (the launch's last turn stores terminal rooms as they are)
+                ww_turn<NB, LOWOCC, GENERIC, false, TAILR>(s, row, ctx, turn0 + t, tk, trace, deal, deal_now, ev_newly, ev_choice, (GE_STAMPS && a.stamps) ? &stamps : nullptr, &rst);
+                if (trace && valid) store_event(sg.trace, sg.rooms_padded, t, room, turn0 + t, p, TAILR ? rst.q : s.phase, restarted, ev_newly, ev_choice);
+                if (TAILR) restarted_in = rst.restarted;
             }
         };
-        if (B::TPL_TRACE) {                                       // (two copies of the loop cost the large-batch build registers)
-            if (a.trace) turns(std::integral_constant<int, 1>{}); else turns(std::integral_constant<int, 0>{});
+        if constexpr (B::LONE && !GENERIC && !MIXED) {             // (the generic and the mixed kernels hold their scalar registers to the limit already: the fresh room would spill)
+            // a table whose first phase is itself terminal recycles its rooms on every turn without ever moving: the head form
+            const bool tail = ((term_mask >> sg.phase0_idx) & 1u) == 0u;                               // wave-uniform
+            if (tail) { if (a.trace) turns(std::integral_constant<int, 1>{}, std::true_type{}); else turns(std::integral_constant<int, 0>{}, std::true_type{}); }
+            else { if (a.trace) turns(std::integral_constant<int, 1>{}, std::false_type{}); else turns(std::integral_constant<int, 0>{}, std::false_type{}); }
+        } else if (B::TPL_TRACE) {                                // (two copies of the loop cost the large-batch build registers)
+            if (a.trace) turns(std::integral_constant<int, 1>{}, std::false_type{}); else turns(std::integral_constant<int, 0>{}, std::false_type{});
         } else {
-            turns(std::integral_constant<int, 2>{});
+            turns(std::integral_constant<int, 2>{}, std::false_type{});
         }
     }
     if (GE_STAMPS && a.stamps && (threadIdx.x & 63u) == 0u) {
@@ -464,10 +488,10 @@ __device__ __forceinline__ void run_tt(const SegDev *__restrict__ sgp, const Ste
 // Two-Truths batch diverges per block, never inside a wavefront.  Segment descriptors live in
 // device memory and are read with a block-uniform index (scalar loads): indexing the kernel
 // arguments dynamically would push them through scratch.
-template <int KIND, bool LOWOCC, int GENERIC, bool SINGLE = false, int LD = 0>
+template <int KIND, bool LOWOCC, int GENERIC, bool SINGLE = false, int LD = 0, bool MIXED = false>
 __device__ __forceinline__ void run_kind(const SegDev *__restrict__ sg, const StepArgs &a, DevRow *rows, void *lw,
                                          uint8_t *nth8, const DevTable *__restrict__ tables, uint64_t room) {
-    if (KIND == K_WW8) run_ww<8, LOWOCC, GENERIC, SINGLE, LD>(sg, a, rows, lw, nth8, tables, room);
+    if (KIND == K_WW8) run_ww<8, LOWOCC, GENERIC, SINGLE, LD, MIXED>(sg, a, rows, lw, nth8, tables, room);
     else if (KIND == K_WW12) run_ww<12, LOWOCC, GENERIC, SINGLE, LD>(sg, a, rows, lw, nth8, tables, room);
     else if (KIND == K_TT4) run_tt<4, LOWOCC, GENERIC, SINGLE, LD>(sg, a, rows, lw, nth8, tables, room);
     else if (KIND == K_TT8) run_tt<8, LOWOCC, GENERIC, SINGLE, LD>(sg, a, rows, lw, nth8, tables, room);
@@ -540,7 +564,7 @@ __global__ void __launch_bounds__(256, SINGLE ? 8 : !LOWOCC ? (GENERIC ? GE_GENE
     const uint64_t room = (uint64_t)(bid - a.block_begin[si]) * blockDim.x + threadIdx.x;
     void *lw = &wl[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];    // wave-uniform: kept in a scalar register across the kind switch
     switch (sg->kind) {
-    case K_WW8: run_kind<K_WW8, LOWOCC, GENERIC, SINGLE, (SINGLE && !LOWOCC) ? 2 : 0>(sg, a, rows, lw, nth8, tables, room); break;   // streaming record loads (load_words)
+    case K_WW8: run_kind<K_WW8, LOWOCC, GENERIC, SINGLE, (SINGLE && !LOWOCC) ? 2 : 0, true>(sg, a, rows, lw, nth8, tables, room); break;   // streaming record loads (load_words)
     case K_WW12: run_kind<K_WW12, LOWOCC, GENERIC, SINGLE>(sg, a, rows, lw, nth8, tables, room); break;
     case K_TT4: run_kind<K_TT4, LOWOCC, GENERIC, SINGLE>(sg, a, rows, lw, nth8, tables, room); break;
     case K_TT8: run_kind<K_TT8, LOWOCC, GENERIC, SINGLE>(sg, a, rows, lw, nth8, tables, room); break;
