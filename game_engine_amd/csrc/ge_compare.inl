@@ -1,6 +1,7 @@
 // ge_compare.inl — paired comparison of playout entries (ge_batch_rollout_compare, POLICY.md §3e): entry k against its baseline
 // entry, playout by playout (included at the end of ge_step.hip, behind ge_playout.inl: the existing kernels keep their
-// code-object offsets; it needs ge_rollout.inl's staging and launch path).
+// code-object offsets).  The call is rollout_call of ge_rollout.inl with act = 3: its checks, its chunk staging over ge_pool.inl's
+// PoolEntries and its launch by kind; what this file adds is the comparison kernel behind the playouts and the entry point.
 //
 // The playouts are ge_batch_rollout_seats's, launched as form ACT = 3 of ge_rollout_kernel (ge_rollout.inl): the same turns and
 // the same reduction, and one byte more per lane - the outcome X of its replica for the entry's subject seat - stored into the

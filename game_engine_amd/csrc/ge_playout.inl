@@ -1,6 +1,8 @@
 // ge_playout.inl — playout seats (ge_batch_step_rooms_playout, POLICY.md §3d): ge_batch_step_rooms with some bot seats choosing
 // their action by their own seat-view playouts (included at the end of ge_step.hip, behind ge_rollout.inl: the existing kernels
-// keep their code-object offsets; it needs ge_pool.inl's and ge_rollout.inl's helpers).
+// keep their code-object offsets).  The entry checks, the grouping and staging of the listed rooms, the turn launch (step 4) and
+// the event decoding are ge_pool.inl's (pool_check_entries, PoolEntries, launch_pool_turn, pool_decode_event); the playouts are
+// ge_rollout.inl's.  What this file adds is the plan and decide kernels - one body each over PlayoutGame - and the passes.
 //
 // Per listed room, on the device, with no room record crossing to the host:
 //   1. ge_playout_plan: one lane per room.  It unpacks the record and finds the seats of its playout mask that decide in this
@@ -57,25 +59,37 @@ template <int NB> __device__ __forceinline__ uint32_t playout_cand_ww(const WW<N
 // Two-Truths: statement 1 in a statements phase, else 1..3 (as bits 0..2)
 __device__ __forceinline__ uint32_t playout_cand_tt(uint32_t act) { return act == ACT_TT_STATEMENTS ? 1u : 7u; }
 
+// what the two games' rooms differ in here: the record, the candidate set of seat i and the injection
+template <int NB, bool WWP> struct PlayoutGame;
+template <int NB> struct PlayoutGame<NB, true> {
+    using S = WW<NB>;
+    using L = WWLayout<NB>;
+    static __device__ __forceinline__ uint32_t cand(const S &s, uint32_t act, uint32_t i) { return playout_cand_ww<NB>(s, act, i); }
+    static __device__ __forceinline__ int inject(S &s, const DevRow &row, const DevCond &cond, uint32_t n, uint32_t p, uint32_t c) {
+        return inject_ww<NB>(s, row, cond, n, p, c);
+    }
+};
+template <int NB> struct PlayoutGame<NB, false> {
+    using S = TT<NB>;
+    using L = TTLayout<NB>;
+    static __device__ __forceinline__ uint32_t cand(const S &, uint32_t act, uint32_t) { return playout_cand_tt(act); }
+    static __device__ __forceinline__ int inject(S &s, const DevRow &row, const DevCond &cond, uint32_t n, uint32_t p, uint32_t c) {
+        return inject_tt<NB>(s, row, cond, n, p, c);
+    }
+};
+
 // the seats of `mask` that decide in this turn, and the number of entries they need
-template <int NB, bool WWP, class S>
-__device__ __forceinline__ uint32_t playout_deciders(const S &s, const DevRow &row, const DevCond &cond, uint32_t n, uint32_t mask, uint32_t tk,
+template <class G>
+__device__ __forceinline__ uint32_t playout_deciders(const typename G::S &s, const DevRow &row, const DevCond &cond, uint32_t n, uint32_t mask, uint32_t tk,
                                                      uint32_t &n_entries) {
     const uint32_t act = (row.r0 >> 2) & 7u;
     uint32_t dec = 0, cnt = 0;
     for (uint32_t m = mask; m; m &= m - 1u) {
         const uint32_t i = ctz(m);
         if ((draw(tk, i) & 3u) == 0u) continue;              // not due in this turn
-        uint32_t cand;
-        int st;
-        S t = s;                                              // a target exactly when an injected action would be accepted
-        if constexpr (WWP) {
-            cand = playout_cand_ww<NB>(s, act, i);
-            st = cand ? inject_ww<NB>(t, row, cond, n, i + 1u, ctz(cand) + 1u) : GE_ERR_ARG;
-        } else {
-            cand = playout_cand_tt(act);
-            st = inject_tt<NB>(t, row, cond, n, i + 1u, 1u);
-        }
+        const uint32_t cand = G::cand(s, act, i);
+        typename G::S t = s;                                  // a target exactly when an injected action would be accepted
+        const int st = cand ? G::inject(t, row, cond, n, i + 1u, ctz(cand) + 1u) : GE_ERR_ARG;
         if (st != GE_OK || popc(cand) < 2u) continue;
         dec |= 1u << i;
         cnt += popc(cand);
@@ -86,54 +100,31 @@ __device__ __forceinline__ uint32_t playout_deciders(const S &s, const DevRow &r
 
 template <int NB, bool WWP>
 __device__ __forceinline__ void playout_plan_room(const SegDev &sg, const DevTable *__restrict__ tables, const PlanArgs &a, uint32_t k) {
+    using G = PlayoutGame<NB, WWP>;
+    using L = typename G::L;
     const uint64_t room = a.rooms[k];
     const uint32_t turn = a.turns[k];
     const uint32_t tk = turn_key(room_key_from(a.seed_key, a.keys[k]), turn);
-    uint32_t dec = 0, cnt = 0, act = 0;
+    uint32_t dec = 0, cnt = 0;
     uint32_t w[12];
-    if constexpr (WWP) {
-        using L = WWLayout<NB>;
-        load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
-        WW<NB> s;
-        L::unpack(w, s);
-        const DevRow &row = tables[sg.table_idx].rows[s.phase];
-        act = (row.r0 >> 2) & 7u;
-        const bool skip = (a.restart && ((sg.term_mask >> s.phase) & 1u)) || (s.phase == sg.phase0_idx && !(s.flags & FLAG_PHASE0_DONE));
-        if (!skip) dec = playout_deciders<NB, true>(s, row, tables[sg.table_idx].conds[s.phase], sg.n_players, a.masks[k], tk, cnt);
-        uint32_t first = cnt ? atomicAdd(a.counter, cnt) + a.e_base : 0u;
-        a.room_first[k] = first;
-        a.room_cnt[k] = cnt;
-        for (uint32_t m = dec; m; m &= m - 1u) {
-            const uint32_t i = ctz(m);
-            for (uint32_t c = playout_cand_ww<NB>(s, act, i); c; c &= c - 1u, first++) {
-                a.e_rooms[first] = room; a.e_keys[first] = a.pkeys[k]; a.e_turns[first] = turn;
-                a.e_seats[first] = a.full_view ? 0u : i + 1u;
-                a.e_first[first] = first; a.e_first[first + 1u] = first + 1u;
-                a.e_players[first] = i + 1u; a.e_choices[first] = ctz(c) + 1u;
-                a.e_status[first] = GE_OK;
-            }
-        }
-    } else {
-        using L = TTLayout<NB>;
-        load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
-        TT<NB> s;
-        L::unpack(w, s);
-        const DevRow &row = tables[sg.table_idx].rows[s.phase];
-        act = (row.r0 >> 2) & 7u;
-        const bool skip = (a.restart && ((sg.term_mask >> s.phase) & 1u)) || (s.phase == sg.phase0_idx && !(s.flags & FLAG_PHASE0_DONE));
-        if (!skip) dec = playout_deciders<NB, false>(s, row, tables[sg.table_idx].conds[s.phase], sg.n_players, a.masks[k], tk, cnt);
-        uint32_t first = cnt ? atomicAdd(a.counter, cnt) + a.e_base : 0u;
-        a.room_first[k] = first;
-        a.room_cnt[k] = cnt;
-        for (uint32_t m = dec; m; m &= m - 1u) {
-            const uint32_t i = ctz(m);
-            for (uint32_t c = playout_cand_tt(act); c; c &= c - 1u, first++) {
-                a.e_rooms[first] = room; a.e_keys[first] = a.pkeys[k]; a.e_turns[first] = turn;
-                a.e_seats[first] = a.full_view ? 0u : i + 1u;
-                a.e_first[first] = first; a.e_first[first + 1u] = first + 1u;
-                a.e_players[first] = i + 1u; a.e_choices[first] = ctz(c) + 1u;
-                a.e_status[first] = GE_OK;
-            }
+    load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+    typename G::S s;
+    L::unpack(w, s);
+    const DevRow &row = tables[sg.table_idx].rows[s.phase];
+    const uint32_t act = (row.r0 >> 2) & 7u;
+    const bool skip = (a.restart && ((sg.term_mask >> s.phase) & 1u)) || (s.phase == sg.phase0_idx && !(s.flags & FLAG_PHASE0_DONE));
+    if (!skip) dec = playout_deciders<G>(s, row, tables[sg.table_idx].conds[s.phase], sg.n_players, a.masks[k], tk, cnt);
+    uint32_t first = cnt ? atomicAdd(a.counter, cnt) + a.e_base : 0u;
+    a.room_first[k] = first;
+    a.room_cnt[k] = cnt;
+    for (uint32_t m = dec; m; m &= m - 1u) {
+        const uint32_t i = ctz(m);
+        for (uint32_t c = G::cand(s, act, i); c; c &= c - 1u, first++) {
+            a.e_rooms[first] = room; a.e_keys[first] = a.pkeys[k]; a.e_turns[first] = turn;
+            a.e_seats[first] = a.full_view ? 0u : i + 1u;
+            a.e_first[first] = first; a.e_first[first + 1u] = first + 1u;
+            a.e_players[first] = i + 1u; a.e_choices[first] = ctz(c) + 1u;
+            a.e_status[first] = GE_OK;
         }
     }
 }
@@ -143,11 +134,7 @@ __global__ void __launch_bounds__(64) ge_playout_plan(const SegDev *__restrict__
     const uint32_t k = blockIdx.x * 64u + threadIdx.x;
     if (k >= a.n) return;
     const SegDev &sg = segs[a.seg];
-    if (KIND == K_WW8) playout_plan_room<8, true>(sg, tables, a, k);
-    else if (KIND == K_WW12) playout_plan_room<12, true>(sg, tables, a, k);
-    else if (KIND == K_TT4) playout_plan_room<4, false>(sg, tables, a, k);
-    else if (KIND == K_TT8) playout_plan_room<8, false>(sg, tables, a, k);
-    else playout_plan_room<12, false>(sg, tables, a, k);
+    playout_plan_room<KindOf<KIND>::NB, KindOf<KIND>::WW>(sg, tables, a, k);
 }
 
 // per deciding seat of room k: argmax of seat_wins with the pick(d, m) tie-break, logged in `s` by `inject`
@@ -180,30 +167,19 @@ __device__ __forceinline__ void playout_choose(const DecideArgs &a, uint32_t k, 
 
 template <int NB, bool WWP>
 __device__ __forceinline__ void playout_decide_room(const SegDev &sg, const DevTable *__restrict__ tables, const DecideArgs &a, uint32_t k) {
+    using G = PlayoutGame<NB, WWP>;
+    using L = typename G::L;
     const uint64_t room = a.rooms[k];
     const uint32_t tk = turn_key(room_key_from(a.seed_key, a.keys[k]), a.turns[k]);
     uint32_t w[12];
-    if constexpr (WWP) {
-        using L = WWLayout<NB>;
-        load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
-        WW<NB> s;
-        L::unpack(w, s);
-        const DevRow &row = tables[sg.table_idx].rows[s.phase];
-        const DevCond &cond = tables[sg.table_idx].conds[s.phase];   // read in place, as inject_group_ww
-        playout_choose(a, k, tk, [&](uint32_t p, uint32_t c) { return inject_ww<NB>(s, row, cond, sg.n_players, p, c); });
-        L::pack(s, w);
-        store_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
-    } else {
-        using L = TTLayout<NB>;
-        load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
-        TT<NB> s;
-        L::unpack(w, s);
-        const DevRow &row = tables[sg.table_idx].rows[s.phase];
-        const DevCond &cond = tables[sg.table_idx].conds[s.phase];   // read in place, as inject_group_tt
-        playout_choose(a, k, tk, [&](uint32_t p, uint32_t c) { return inject_tt<NB>(s, row, cond, sg.n_players, p, c); });
-        L::pack(s, w);
-        store_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
-    }
+    load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+    typename G::S s;
+    L::unpack(w, s);
+    const DevRow &row = tables[sg.table_idx].rows[s.phase];
+    const DevCond &cond = tables[sg.table_idx].conds[s.phase];   // read in place, as inject_group_ww / inject_group_tt
+    playout_choose(a, k, tk, [&](uint32_t p, uint32_t c) { return G::inject(s, row, cond, sg.n_players, p, c); });
+    L::pack(s, w);
+    store_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
 }
 
 // one lane per listed room of a unit with entries (a room without any stores nothing: its output was zeroed by the host)
@@ -212,31 +188,18 @@ __global__ void __launch_bounds__(64) ge_playout_decide(const SegDev *__restrict
     const uint32_t k = blockIdx.x * 64u + threadIdx.x;
     if (k >= a.n || a.room_cnt[k] == 0u) return;
     const SegDev &sg = segs[a.seg];
-    if (KIND == K_WW8) playout_decide_room<8, true>(sg, tables, a, k);
-    else if (KIND == K_WW12) playout_decide_room<12, true>(sg, tables, a, k);
-    else if (KIND == K_TT4) playout_decide_room<4, false>(sg, tables, a, k);
-    else if (KIND == K_TT8) playout_decide_room<8, false>(sg, tables, a, k);
-    else playout_decide_room<12, false>(sg, tables, a, k);
+    playout_decide_room<KindOf<KIND>::NB, KindOf<KIND>::WW>(sg, tables, a, k);
 }
 
 // most candidates one deciding seat of a segment can have: Werewolf a subset of the n seats, Two-Truths at most statements 1..3
 // (a Two-Truths segment may have 2 players).  The entry space and the cost cap reserve this per playout seat.
 uint32_t playout_max_cands(const SegDev &d) { return (d.kind == K_WW8 || d.kind == K_WW12) ? d.n_players : std::max(d.n_players, 3u); }
 
-template <class A>
-hipError_t playout_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const A &a) {
-#define GE_PLAYOUT_LAUNCH(K)                                                                                                          \
-    if constexpr (std::is_same<A, PlanArgs>::value) hipLaunchKernelGGL((ge_playout_plan<K>), grid, dim3(64), 0, st, b->segs_dev, b->tables, a); \
-    else hipLaunchKernelGGL((ge_playout_decide<K>), grid, dim3(64), 0, st, b->segs_dev, b->tables, a);
-    switch (kind) {
-    case K_WW8: { GE_PLAYOUT_LAUNCH(K_WW8) } break;
-    case K_WW12: { GE_PLAYOUT_LAUNCH(K_WW12) } break;
-    case K_TT4: { GE_PLAYOUT_LAUNCH(K_TT4) } break;
-    case K_TT8: { GE_PLAYOUT_LAUNCH(K_TT8) } break;
-    default: { GE_PLAYOUT_LAUNCH(K_TT12) } break;
-    }
-#undef GE_PLAYOUT_LAUNCH
-    return hipGetLastError();
+hipError_t playout_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const PlanArgs &a) {
+    return by_kind(kind, [&](auto K) { hipLaunchKernelGGL((ge_playout_plan<K()>), grid, dim3(64), 0, st, b->segs_dev, b->tables, a); });
+}
+hipError_t playout_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const DecideArgs &a) {
+    return by_kind(kind, [&](auto K) { hipLaunchKernelGGL((ge_playout_decide<K()>), grid, dim3(64), 0, st, b->segs_dev, b->tables, a); });
 }
 
 }  // namespace
@@ -255,13 +218,8 @@ static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
     int st = sync_impl(b);
     if (st != GE_OK) return st;
     const uint32_t n_seg = (uint32_t)b->segs.size();
-    std::vector<uint32_t> seg_of((size_t)n), begin(n_seg + 1u, 0u), order((size_t)n);
-    for (uint64_t k = 0; k < n; k++) { seg_of[k] = pool_segment_of(b, rooms[k]); begin[seg_of[k] + 1u]++; }
-    for (uint32_t s = 0; s < n_seg; s++) begin[s + 1u] += begin[s];
-    {
-        std::vector<uint32_t> at(begin.begin(), begin.end() - 1);
-        for (uint64_t k = 0; k < n; k++) order[at[seg_of[k]]++] = (uint32_t)k;
-    }
+    const PoolEntries en(b, n, rooms);
+    const std::vector<uint32_t> &begin = en.begin, &order = en.order;
     // units: runs of one segment with at most CHUNK entries' room (a room needs popcount(mask) x playout_max_cands at most); passes:
     // consecutive units whose room fits in CHUNK entries together.  A pass's entries are planned, played and decided together.
     const uint32_t CHUNK = 65536;
@@ -287,7 +245,6 @@ static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
     // one scratch layout, each array from a 16 B boundary.  Upload: [rooms u64][keys u64][pkeys u64][turns u32][masks u32]
     // [unit counters u32][per-room outputs 16 B, zeroed].  Then [room_first u32][room_cnt u32][events 16 B] and the pass's
     // entries: [rooms u64][keys u64][turns u32][seats u32][first u32 (+1)][players u32][choices u32][status i32][acc]
-    auto up16 = [](size_t x) { return (x + 15u) & ~(size_t)15u; };
     const size_t N = (size_t)n, C = max_cap;
     const size_t o_keys = 8 * N, o_pkeys = 16 * N, o_turns = 24 * N, o_masks = up16(o_turns + 4 * N), o_ctr = up16(o_masks + 4 * N);
     const size_t o_out = up16(o_ctr + 4 * (size_t)n_units), o_up_end = o_out + 16 * N;
@@ -305,14 +262,10 @@ static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
     uint32_t *host32 = nullptr;
     if ((st = io_stage(b, o.total, &host32)) != GE_OK) return st;
     unsigned char *host = reinterpret_cast<unsigned char *>(host32);
-    uint64_t *h_rooms = reinterpret_cast<uint64_t *>(host), *h_keys = reinterpret_cast<uint64_t *>(host + o_keys);
+    en.stage(b, rooms, keys, turns, host, o_keys, o_turns);
     uint64_t *h_pkeys = reinterpret_cast<uint64_t *>(host + o_pkeys);
-    uint32_t *h_turns = reinterpret_cast<uint32_t *>(host + o_turns), *h_masks = reinterpret_cast<uint32_t *>(host + o_masks);
-    for (size_t i = 0; i < N; i++) {
-        const uint32_t k = order[i];
-        h_rooms[i] = rooms[k] - b->segs[seg_of[k]].local_first;
-        h_keys[i] = keys[k]; h_pkeys[i] = pkeys[k]; h_turns[i] = turns[k]; h_masks[i] = masks[k];
-    }
+    uint32_t *h_masks = reinterpret_cast<uint32_t *>(host + o_masks);
+    for (size_t i = 0; i < N; i++) { h_pkeys[i] = pkeys[order[i]]; h_masks[i] = masks[order[i]]; }
     memset(host + o_ctr, 0, o_up_end - o_ctr);
     char *dev = nullptr;
     if ((st = pool_scratch(b, o.total, &dev)) != GE_OK) return st;
@@ -380,18 +333,7 @@ static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
         }
     }
     // 4. the turn, as step_rooms_impl launches it
-    for (uint32_t g = 0; g < n_seg; g++) {
-        const uint32_t lo = begin[g], cnt = begin[g + 1u] - lo;
-        if (!cnt) continue;
-        PoolArgs a;
-        a.rooms = reinterpret_cast<const uint64_t *>(dev) + lo;
-        a.keys = reinterpret_cast<const uint64_t *>(dev + o_keys) + lo;
-        a.turns = reinterpret_cast<const uint32_t *>(dev + o_turns) + lo;
-        a.events = reinterpret_cast<uint32_t *>(dev + o_ev) + 4u * (size_t)lo;
-        a.n = cnt; a.seg = g; a.seed_key = seed_b; a.restart = restart;
-        const dim3 grid((cnt + 63u) / 64u);
-        HIP_TRY(b->generic ? pool_launch<1>(b->segs[g].dev.kind, grid, s, b, a) : pool_launch<0>(b->segs[g].dev.kind, grid, s, b, a));
-    }
+    if ((st = launch_pool_turn(b, s, en, dev, o_keys, o_turns, o_ev)) != GE_OK) return st;
     HIP_TRY(hipMemcpyAsync(host + o_out, dev + o_out, 16 * N, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(host + o_ev, dev + o_ev, 16 * N, hipMemcpyDeviceToHost, s));
     if ((st = sync_impl(b)) != GE_OK) return st;
@@ -402,17 +344,10 @@ static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
         const uint64_t dnib = (uint64_t)h_out[4 * i + 1] | ((uint64_t)h_out[4 * i + 2] << 32);
         if (decided) decided[k] = dmask;
         if (!events) continue;
-        const uint32_t *w = h_ev + 4 * i;                     // as step_rooms_impl decodes it, with the decided seats acted
-        const ge_game_table &tb = b->segs[seg_of[k]].table;
-        ge_turn_event &e = events[k];
-        memset(&e, 0, sizeof e);
-        e.turn = w[0];
-        e.from_phase_id = tb.rows[w[1] & 255u].phase_id;
-        e.to_phase_id = tb.rows[(w[1] >> 8) & 255u].phase_id;
-        e.restarted = (w[1] >> 16) & 1u;
-        e.acted_now = (uint16_t)((w[1] >> 20) | dmask);
-        const uint64_t ch = (uint64_t)w[2] | ((uint64_t)w[3] << 32) | dnib;
-        for (int c = 0; c < 16; c++) e.choice[c] = (uint8_t)((ch >> (4 * c)) & 15u);
+        ge_turn_event &e = events[k];                         // as step_rooms_impl decodes it, with the decided seats acted
+        pool_decode_event(h_ev + 4 * i, b->segs[en.seg_of[k]].table, e);
+        e.acted_now |= (uint16_t)dmask;
+        for (int c = 0; c < 16; c++) e.choice[c] |= (uint8_t)((dnib >> (4 * c)) & 15u);
     }
     return GE_OK;
 }
@@ -424,15 +359,8 @@ int ge_batch_step_rooms_playout(ge_batch *b, uint64_t n, const uint64_t *rooms, 
                                 uint64_t seed, uint32_t flags, ge_turn_event *events, uint32_t *decided) {
     if (!b) return GE_ERR_ARG;
     if (n == 0) return GE_OK;
-    // ge_batch_step_rooms's checks, in its order
-    if (!rooms || !keys || !turns || n > 0x7FFFFFFFull) return GE_ERR_ARG;
-    for (uint64_t k = 0; k < n; k++)
-        if (rooms[k] >= b->n_rooms || turns[k] == 0xFFFFFFFFu) return GE_ERR_RANGE;
-    {
-        std::vector<uint64_t> sorted(rooms, rooms + n);
-        std::sort(sorted.begin(), sorted.end());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return GE_ERR_ARG;
-    }
+    const int st = pool_check_entries(b, n, rooms, keys, turns);   // ge_batch_step_rooms's checks, in its order
+    if (st != GE_OK) return st;
     // then the playouts': ge_batch_rollout_seats's caps, the masks and the cost cap
     if (!playout_masks || !playout_keys || (flags & ~GE_PLAYOUT_FULL_VIEW)) return GE_ERR_ARG;
     if (n_rollouts == 0 || n_rollouts > (1u << 20) || max_turns > 4096u) return GE_ERR_ARG;

@@ -28,29 +28,100 @@
 // deal (Werewolf x 8: word 7's upper half is 0) - and ge_pool_scatter stores it plane by plane.  The Werewolf x 12 side plane is not
 // touched, as ge_batch_write_rooms does not touch it: a deal there is a function of the slot's own key and the game index alone, so
 // it stays right for whatever record is written over the slot.
+//
+// Shared with the other indexed files (ge_rollout.inl, ge_playout.inl, ge_run.inl), each written here once: KindOf (a compile-time
+// KIND as players' bound and game), by_kind + lane_lds (the launch of a segment's kind and its LDS size), up16, the entry checks
+// (pool_check_rooms / pool_check_entries: their order and their errors are ABI behaviour), PoolEntries (the listed rooms grouped by
+// segment and their staging as [rooms][keys][turns]), launch_pool_turn and pool_decode_event.  On the device: the indexed lane's
+// context (lane_cond_ctx, lane_ww_ctx), recycle rule (lane_recycle), turn call (lane_ww_turn, lane_tt_turn) and event words (lane_event).
 
 namespace {
 
-struct PoolArgs {
-    const uint64_t *rooms;     // segment-local room of each entry of this launch
-    const uint64_t *keys;      // global room index its RNG stream is keyed by
-    const uint32_t *turns;     // its turn number
-    uint32_t *events;          // [n] x 4 words: turn | from, to, restarted, acted (as the GE_FLAG_TRACE record) | choice nibbles
-    uint32_t n, seg, seed_key, restart;
+// a compile-time KIND as (players' bound NB, is Werewolf)
+template <int KIND> struct KindOf {
+    static constexpr int NB = KIND == K_TT4 ? 4 : KIND == K_WW8 || KIND == K_TT8 ? 8 : 12;
+    static constexpr bool WW = KIND == K_WW8 || KIND == K_WW12;
 };
 
-__device__ __forceinline__ void pool_event(uint32_t *events, uint32_t k, uint32_t turn, uint32_t p, uint32_t q, uint32_t restarted,
-                                           uint32_t newly, uint64_t choice) {
-    u32x4 v;
-    v.x = turn; v.y = p | (q << 8) | (restarted << 16) | (newly << 20);
-    v.z = (uint32_t)choice; v.w = (uint32_t)(choice >> 32);
-    reinterpret_cast<u32x4 *>(events)[k] = v;
-}
+// ---- the indexed lane, shared by ge_pool_kernel, ge_run_kernel (ge_run.inl) and ge_rollout_kernel (ge_rollout.inl): one lane plays
+// single turns of one room in the lone-wavefront single-turn build, tables read in place, its key and turn its own
 
 __device__ __forceinline__ CondShape pool_cond_shape(const DevTable &tb) {
     return CondShape{(uint32_t)__builtin_amdgcn_readfirstlane(tb.cond_shape), (uint32_t)__builtin_amdgcn_readfirstlane(tb.cond_g[0]), (uint32_t)__builtin_amdgcn_readfirstlane(tb.cond_g[1]),
                      (uint32_t)__builtin_amdgcn_readfirstlane(tb.cond_fields[0]), (uint32_t)__builtin_amdgcn_readfirstlane(tb.cond_fields[1])};
 }
+
+// the segment's generic target conditions, read in place
+template <int GENERIC> __device__ __forceinline__ CondCtx lane_cond_ctx(const SegDev &sg, const DevTable *__restrict__ tables) {
+    return CondCtx{reinterpret_cast<const unsigned char *>(tables[sg.table_idx].cond_img),
+                   GENERIC ? pool_cond_shape(tables[sg.table_idx]) : CondShape{0u, 0u, 0u, 0u, 0u}};
+}
+
+// Werewolf: what the lane's turns keep constant.  PEOPLE: the segment's human seats are left to people (else the policy plays every
+// seat: the playouts); valid: the lane holds a real entry (else it shadows one and never acts)
+template <int GENERIC, bool PEOPLE> __device__ __forceinline__ WwCtx lane_ww_ctx(const SegDev &sg, const DevTable *__restrict__ tables, void *lw, uint32_t rk, bool valid) {
+    const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
+    const CondCtx cc = lane_cond_ctx<GENERIC>(sg, tables);
+    const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
+    return WwCtx{reinterpret_cast<const DevRow *>(img), cc, lw, img + IMG_NTH8, reinterpret_cast<const uint32_t *>(img + IMG_ORD8), valid, sg.n_players, sg.nw,
+                 sg.phase0_idx, rk, PEOPLE ? sg.human_mask : 0u, term_mask};
+}
+
+// a finished room of a restarting batch becomes the init template with one more game, saturating (Two-Truths: the caller reloads
+// `done` from sg.done0)
+template <class S> __device__ __forceinline__ uint32_t lane_recycle(const SegDev &sg, S &s, uint32_t restart, uint32_t term_mask) {
+    if (!(restart && ((term_mask >> s.phase) & 1u))) return 0u;
+    uint32_t ir[20];
+    load_init_regs<S::NREGS>(sg, ir);
+    const uint32_t g = s.games;
+    S s0;
+    s0.from_regs(ir);
+    s = s0;
+    s.games = g < 0xFFFFu ? g + 1u : g;
+    return 1u;
+}
+
+// what a turn logged: the phase it started in, who acted, what they chose
+struct LaneTurn { uint32_t p, newly; uint64_t choice; };
+
+template <int NB, int GENERIC> __device__ __forceinline__ LaneTurn lane_ww_turn(WWR<NB> &s, const WwCtx &ctx, uint32_t turn, bool log) {
+    DevRow row = lds_row<false>(ctx.rows, s.phase);
+    LaneTurn t = {s.phase, 0u, 0ull};
+    Deal deal = {0u, 0u, 0u, 0u, 0u};                         // no prepared deal (gv = 0): an assignment deals on the spot
+    uint32_t tk = turn_key(ctx.rkey, turn);
+    ww_turn<NB, true, GENERIC, true>(s, row, ctx, turn, tk, log, deal, false, t.newly, t.choice, nullptr);
+    return t;
+}
+
+template <int NB, int GENERIC, bool PEOPLE>
+__device__ __forceinline__ LaneTurn lane_tt_turn(TT<NB> &s, uint32_t &done, const SegDev &sg, const DevTable *__restrict__ tables, const CondCtx &cc, void *lw,
+                                                 bool valid, uint32_t rk, uint32_t turn, bool log, uint32_t term_mask) {
+    const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
+    const DevRow *rows = reinterpret_cast<const DevRow *>(img);
+    DevRow row = lds_row<false>(rows, s.phase);
+    LaneTurn t = {s.phase, 0u, 0ull};
+    tt_turn<NB, tt_uses_queue(NB, true), false, GENERIC, true>(s, done, row, rows, cc, lw, img + IMG_NTH8, valid, sg.n_players, sg.rounds, sg.phase0_idx, rk,
+                                                             turn, log, PEOPLE ? sg.human_mask : 0u, term_mask, t.newly, t.choice);
+    return t;
+}
+
+// the four event words of a turn: turn | from, to, restarted, acted (as the GE_FLAG_TRACE record) | choice nibbles
+__device__ __forceinline__ u32x4 lane_event(uint32_t turn, const LaneTurn &t, uint32_t q, uint32_t restarted) {
+    u32x4 v;
+    v.x = turn; v.y = t.p | (q << 8) | (restarted << 16) | (t.newly << 20);
+    v.z = (uint32_t)t.choice; v.w = (uint32_t)(t.choice >> 32);
+    return v;
+}
+
+// ---- ge_pool_kernel: one turn of each listed room
+
+struct PoolArgs {
+    const uint64_t *rooms;     // segment-local room of each entry of this launch
+    const uint64_t *keys;      // global room index its RNG stream is keyed by
+    const uint32_t *turns;     // its turn number
+    uint32_t *events;          // [n] x 4 words: lane_event
+    uint32_t n, seg, seed_key, restart;
+};
 
 template <int NB, int GENERIC>
 __device__ __forceinline__ void pool_ww(const SegDev &sg, const DevTable *__restrict__ tables, const PoolArgs &a, void *lw, uint32_t k_in) {
@@ -63,35 +134,14 @@ __device__ __forceinline__ void pool_ww(const SegDev &sg, const DevTable *__rest
     load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
     const uint32_t rk = room_key_from(a.seed_key, a.keys[k]);
     const uint32_t turn = a.turns[k];
-    const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
-    const DevRow *rows = reinterpret_cast<const DevRow *>(img);
-    const CondShape cs = GENERIC ? pool_cond_shape(tables[sg.table_idx]) : CondShape{0u, 0u, 0u, 0u, 0u};
-    const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
-    const WwCtx ctx = {rows, CondCtx{reinterpret_cast<const unsigned char *>(tables[sg.table_idx].cond_img), cs}, lw, img + IMG_NTH8,
-                       reinterpret_cast<const uint32_t *>(img + IMG_ORD8), valid, sg.n_players, sg.nw, sg.phase0_idx, rk, sg.human_mask, term_mask};
+    const WwCtx ctx = lane_ww_ctx<GENERIC, true>(sg, tables, lw, rk, valid);
     WWR<NB> s;
     uint32_t cache;                                           // the record's prepared deal: not of this key, never used
     ww_load_regs<NB>(w, s, cache);
-    uint32_t restarted = 0;
-    if (a.restart && ((term_mask >> s.phase) & 1u)) {         // recycle a finished room (run_ww's single-turn form)
-        uint32_t ir[20];
-        load_init_regs<WWR<NB>::NREGS>(sg, ir);
-        const uint32_t g = s.games;
-        WWR<NB> s0;
-        s0.from_regs(ir);
-        s = s0;
-        s.games = g < 0xFFFFu ? g + 1u : g;
-        restarted = 1;
-    }
-    DevRow row = lds_row<false>(rows, s.phase);
-    const uint32_t p = s.phase;
-    Deal deal = {0u, 0u, 0u, 0u, 0u};                         // no prepared deal (gv = 0): an assignment deals on the spot
-    uint32_t tk = turn_key(rk, turn);
-    uint32_t ev_newly = 0;
-    uint64_t ev_choice = 0;
-    ww_turn<NB, true, GENERIC, true>(s, row, ctx, turn, tk, true, deal, false, ev_newly, ev_choice, nullptr);
+    const uint32_t restarted = lane_recycle(sg, s, a.restart, ctx.term_mask);
+    const LaneTurn t = lane_ww_turn<NB, GENERIC>(s, ctx, turn, true);
     if (!valid) return;
-    pool_event(a.events, k, turn, p, s.phase, restarted, ev_newly, ev_choice);
+    reinterpret_cast<u32x4 *>(a.events)[k] = lane_event(turn, t, s.phase, restarted);
     ww_store_regs<NB>(s, 0u, w);                              // stored without a prepared deal
     store_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
 }
@@ -106,34 +156,16 @@ __device__ __forceinline__ void pool_tt(const SegDev &sg, const DevTable *__rest
     load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
     const uint32_t rk = room_key_from(a.seed_key, a.keys[k]);
     const uint32_t turn = a.turns[k];
-    const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
-    const DevRow *rows = reinterpret_cast<const DevRow *>(img);
-    const CondShape cs = GENERIC ? pool_cond_shape(tables[sg.table_idx]) : CondShape{0u, 0u, 0u, 0u, 0u};
-    const CondCtx cc = {reinterpret_cast<const unsigned char *>(tables[sg.table_idx].cond_img), cs};
+    const CondCtx cc = lane_cond_ctx<GENERIC>(sg, tables);
     const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
     TT<NB> s;
     L::unpack(w, s);
     uint32_t done = tt_done_mask<NB>(s.rounds, sg.rounds);
-    uint32_t restarted = 0;
-    if (a.restart && ((term_mask >> s.phase) & 1u)) {
-        uint32_t ir[20];
-        load_init_regs<TT<NB>::NREGS>(sg, ir);
-        const uint32_t g = s.games;
-        TT<NB> s0;
-        s0.from_regs(ir);
-        s = s0;
-        s.games = g < 0xFFFFu ? g + 1u : g;
-        done = __builtin_amdgcn_readfirstlane(sg.done0);
-        restarted = 1;
-    }
-    DevRow row = lds_row<false>(rows, s.phase);
-    const uint32_t p = s.phase;
-    uint32_t ev_newly = 0;
-    uint64_t ev_choice = 0;
-    tt_turn<NB, tt_uses_queue(NB, true), false, GENERIC, true>(s, done, row, rows, cc, lw, img + IMG_NTH8, valid, sg.n_players, sg.rounds, sg.phase0_idx,
-                                                             rk, turn, true, sg.human_mask, term_mask, ev_newly, ev_choice);
+    const uint32_t restarted = lane_recycle(sg, s, a.restart, term_mask);
+    if (restarted) done = __builtin_amdgcn_readfirstlane(sg.done0);
+    const LaneTurn t = lane_tt_turn<NB, GENERIC, true>(s, done, sg, tables, cc, lw, valid, rk, turn, true, term_mask);
     if (!valid) return;
-    pool_event(a.events, k, turn, p, s.phase, restarted, ev_newly, ev_choice);
+    reinterpret_cast<u32x4 *>(a.events)[k] = lane_event(turn, t, s.phase, restarted);
     L::pack(s, w);
     store_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
 }
@@ -144,11 +176,8 @@ __global__ void __launch_bounds__(64) ge_pool_kernel(const SegDev *__restrict__ 
     const SegDev &sg = segs[a.seg];
     const uint32_t k = blockIdx.x * 64u + threadIdx.x;
     void *lw = ge_lds;
-    if (KIND == K_WW8) pool_ww<8, GENERIC>(sg, tables, a, lw, k);
-    else if (KIND == K_WW12) pool_ww<12, GENERIC>(sg, tables, a, lw, k);
-    else if (KIND == K_TT4) pool_tt<4, GENERIC>(sg, tables, a, lw, k);
-    else if (KIND == K_TT8) pool_tt<8, GENERIC>(sg, tables, a, lw, k);
-    else pool_tt<12, GENERIC>(sg, tables, a, lw, k);
+    if constexpr (KindOf<KIND>::WW) pool_ww<KindOf<KIND>::NB, GENERIC>(sg, tables, a, lw, k);
+    else pool_tt<KindOf<KIND>::NB, GENERIC>(sg, tables, a, lw, k);
 }
 
 // ge_batch_read_rooms_at: the packed record of batch room rooms[k] -> out[k * 12 ..] (its segment's words; the rest untouched)
@@ -222,43 +251,78 @@ uint32_t pool_segment_of(const ge_batch *b, uint64_t room) {
     return si;
 }
 
-template <int GEN> hipError_t pool_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const PoolArgs &a) {
-    const uint32_t lds = (kind == K_TT4) ? 0u : (uint32_t)sizeof(WaveLdsLow);
+// the action queue of a lone wavefront as dynamic LDS: Two-Truths x 4 has no queue
+uint32_t lane_lds(uint32_t kind) { return kind == K_TT4 ? 0u : (uint32_t)sizeof(WaveLdsLow); }
+
+// a segment's kind as a compile-time KIND: f(std::integral_constant<int, KIND>) launches that kernel
+template <class F> hipError_t by_kind(uint32_t kind, F &&f) {
     switch (kind) {
-    case K_WW8: hipLaunchKernelGGL((ge_pool_kernel<K_WW8, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    case K_WW12: hipLaunchKernelGGL((ge_pool_kernel<K_WW12, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    case K_TT4: hipLaunchKernelGGL((ge_pool_kernel<K_TT4, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    case K_TT8: hipLaunchKernelGGL((ge_pool_kernel<K_TT8, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    default: hipLaunchKernelGGL((ge_pool_kernel<K_TT12, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
+    case K_WW8: f(std::integral_constant<int, K_WW8>{}); break;
+    case K_WW12: f(std::integral_constant<int, K_WW12>{}); break;
+    case K_TT4: f(std::integral_constant<int, K_TT4>{}); break;
+    case K_TT8: f(std::integral_constant<int, K_TT8>{}); break;
+    default: f(std::integral_constant<int, K_TT12>{}); break;
     }
     return hipGetLastError();
 }
 
+template <int GEN> hipError_t pool_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const PoolArgs &a) {
+    return by_kind(kind, [&](auto K) { hipLaunchKernelGGL((ge_pool_kernel<K(), GEN>), grid, dim3(64), lane_lds(kind), st, b->segs_dev, b->tables, a); });
+}
+
+size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
+
 }  // namespace
 
-// the entry checks of ge_batch_step_rooms (n > 0), all before anything runs: shared with ge_batch_run_rooms (ge_run.inl)
-static int pool_check_entries(const ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns) {
-    if (!rooms || !keys || !turns || n > 0x7FFFFFFFull) return GE_ERR_ARG;
+// the rooms of an indexed call (n > 0), all before anything runs: every room in the batch (GE_ERR_RANGE), none listed twice (GE_ERR_ARG)
+static int pool_check_rooms(const ge_batch *b, uint64_t n, const uint64_t *rooms) {
     for (uint64_t k = 0; k < n; k++)                              // all-or-nothing: every entry is checked before anything runs
-        if (rooms[k] >= b->n_rooms || turns[k] == 0xFFFFFFFFu) return GE_ERR_RANGE;
+        if (rooms[k] >= b->n_rooms) return GE_ERR_RANGE;
     std::vector<uint64_t> sorted(rooms, rooms + n);
     std::sort(sorted.begin(), sorted.end());
     if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return GE_ERR_ARG;
     return GE_OK;
 }
 
-// stable counting sort by segment: entry order[i] goes to position i; segment s holds [begin[s], begin[s + 1])
-static void pool_group_entries(const ge_batch *b, uint64_t n, const uint64_t *rooms, std::vector<uint32_t> &seg_of, std::vector<uint32_t> &begin,
-                               std::vector<uint32_t> &order) {
-    const uint32_t n_seg = (uint32_t)b->segs.size();
-    seg_of.assign((size_t)n, 0u); begin.assign(n_seg + 1u, 0u); order.assign((size_t)n, 0u);
-    for (uint64_t k = 0; k < n; k++) { seg_of[k] = pool_segment_of(b, rooms[k]); begin[seg_of[k] + 1u]++; }
-    for (uint32_t s = 0; s < n_seg; s++) begin[s + 1u] += begin[s];
-    std::vector<uint32_t> at(begin.begin(), begin.end() - 1);
-    for (uint64_t k = 0; k < n; k++) order[at[seg_of[k]]++] = (uint32_t)k;
+// the entry checks of ge_batch_step_rooms (n > 0): shared with ge_batch_step_rooms_playout (ge_playout.inl) and ge_batch_run_rooms
+// (ge_run.inl).  A turn out of range answers as a room out of range does, so which of the two loops finds it first does not show
+static int pool_check_entries(const ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns) {
+    if (!rooms || !keys || !turns || n > 0x7FFFFFFFull) return GE_ERR_ARG;
+    for (uint64_t k = 0; k < n; k++)
+        if (turns[k] == 0xFFFFFFFFu) return GE_ERR_RANGE;
+    return pool_check_rooms(b, n, rooms);
 }
 
-// the four event words of a turn (pool_event) as read_events_impl decodes the trace record
+// n listed rooms grouped by segment (a stable counting sort): the entry at sorted position i is order[i], of segment seg_of[order[i]];
+// segment g holds the sorted positions [begin[g], begin[g + 1]).  Every indexed call stages and launches in this order: one launch
+// per segment with entries
+struct PoolEntries {
+    std::vector<uint32_t> seg_of, begin, order;
+    PoolEntries(const ge_batch *b, uint64_t n, const uint64_t *rooms)
+        : seg_of((size_t)n), begin(b->segs.size() + 1u, 0u), order((size_t)n) {
+        const uint32_t n_seg = (uint32_t)b->segs.size();
+        for (uint64_t k = 0; k < n; k++) { seg_of[k] = pool_segment_of(b, rooms[k]); begin[seg_of[k] + 1u]++; }
+        for (uint32_t s = 0; s < n_seg; s++) begin[s + 1u] += begin[s];
+        std::vector<uint32_t> at(begin.begin(), begin.end() - 1);
+        for (uint64_t k = 0; k < n; k++) order[at[seg_of[k]]++] = (uint32_t)k;
+    }
+    size_t size() const { return order.size(); }
+    uint32_t seg_at(size_t i) const { return seg_of[order[i]]; }
+    // [rooms u64 x n] at host, [keys u64 x n] at host + off_keys, [turns u32 x n] at host + off_turns, sorted, rooms segment-local
+    void stage(const ge_batch *b, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, unsigned char *host, size_t off_keys,
+               size_t off_turns) const {
+        uint64_t *h_rooms = reinterpret_cast<uint64_t *>(host), *h_keys = reinterpret_cast<uint64_t *>(host + off_keys);
+        uint32_t *h_turns = reinterpret_cast<uint32_t *>(host + off_turns);
+        for (size_t i = 0; i < size(); i++) {
+            const uint32_t k = order[i];
+            h_rooms[i] = rooms[k] - b->segs[seg_of[k]].local_first;
+            h_keys[i] = keys[k];
+            h_turns[i] = turns[k];
+        }
+    }
+};
+
+// the four event words of a turn (lane_event) as read_events_impl decodes the trace record
 static void pool_decode_event(const uint32_t *w, const ge_game_table &tb, ge_turn_event &e) {
     memset(&e, 0, sizeof e);
     e.turn = w[0];
@@ -270,37 +334,11 @@ static void pool_decode_event(const uint32_t *w, const ge_game_table &tb, ge_tur
     for (int c = 0; c < 16; c++) e.choice[c] = (uint8_t)((ch >> (4 * c)) & 15u);
 }
 
-static int step_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, ge_turn_event *events) {
-    if (n == 0) return GE_OK;
-    int st = pool_check_entries(b, n, rooms, keys, turns);
-    if (st != GE_OK) return st;
-    GE_ON_DEVICE(b);
-    if ((st = sync_impl(b)) != GE_OK) return st;
-    const uint32_t n_seg = (uint32_t)b->segs.size();
-    std::vector<uint32_t> seg_of, begin, order;
-    pool_group_entries(b, n, rooms, seg_of, begin, order);
-    // one upload: [rooms u64 x n][keys u64 x n][turns u32 x n (padded to 16 B)], then events 16 B x n
-    const size_t off_keys = 8 * (size_t)n, off_turns = 16 * (size_t)n, off_ev = (off_turns + 4 * (size_t)n + 15u) & ~(size_t)15u;
-    const size_t total = off_ev + 16 * (size_t)n;
-    uint32_t *host32 = nullptr;
-    if ((st = io_stage(b, total, &host32)) != GE_OK) return st;
-    unsigned char *host = reinterpret_cast<unsigned char *>(host32);
-    uint64_t *h_rooms = reinterpret_cast<uint64_t *>(host), *h_keys = reinterpret_cast<uint64_t *>(host + off_keys);
-    uint32_t *h_turns = reinterpret_cast<uint32_t *>(host + off_turns);
-    for (size_t i = 0; i < n; i++) {
-        const uint32_t k = order[i];
-        h_rooms[i] = rooms[k] - b->segs[seg_of[k]].local_first;
-        h_keys[i] = keys[k];
-        h_turns[i] = turns[k];
-    }
-    char *dev = nullptr;
-    if ((st = pool_scratch(b, total, &dev)) != GE_OK) return st;
-    hipStream_t s = b->last_stream;
-    if ((st = order_after_previous(b, s)) != GE_OK) return st;
-    HIP_TRY(hipMemcpyAsync(dev, host, off_ev, hipMemcpyHostToDevice, s));
+// one turn of the entries staged at dev (rooms at 0, keys, turns), a launch per segment present; events: 16 B per sorted entry
+static int launch_pool_turn(ge_batch *b, hipStream_t s, const PoolEntries &en, char *dev, size_t off_keys, size_t off_turns, size_t off_ev) {
     const uint32_t seed_k = seed_key((uint32_t)b->seed, (uint32_t)(b->seed >> 32));
-    for (uint32_t g = 0; g < n_seg; g++) {
-        const uint32_t lo = begin[g], cnt = begin[g + 1u] - lo;
+    for (uint32_t g = 0; g < (uint32_t)b->segs.size(); g++) {
+        const uint32_t lo = en.begin[g], cnt = en.begin[g + 1u] - lo;
         if (!cnt) continue;
         PoolArgs a;
         a.rooms = reinterpret_cast<const uint64_t *>(dev) + lo;
@@ -312,11 +350,34 @@ static int step_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const
         const dim3 grid((cnt + 63u) / 64u);
         HIP_TRY(b->generic ? pool_launch<1>(b->segs[g].dev.kind, grid, s, b, a) : pool_launch<0>(b->segs[g].dev.kind, grid, s, b, a));
     }
+    return GE_OK;
+}
+
+static int step_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, ge_turn_event *events) {
+    if (n == 0) return GE_OK;
+    int st = pool_check_entries(b, n, rooms, keys, turns);
+    if (st != GE_OK) return st;
+    GE_ON_DEVICE(b);
+    if ((st = sync_impl(b)) != GE_OK) return st;
+    const PoolEntries en(b, n, rooms);
+    // one upload: [rooms u64 x n][keys u64 x n][turns u32 x n (padded to 16 B)], then events 16 B x n
+    const size_t off_keys = 8 * (size_t)n, off_turns = 16 * (size_t)n, off_ev = up16(off_turns + 4 * (size_t)n);
+    const size_t total = off_ev + 16 * (size_t)n;
+    uint32_t *host32 = nullptr;
+    if ((st = io_stage(b, total, &host32)) != GE_OK) return st;
+    unsigned char *host = reinterpret_cast<unsigned char *>(host32);
+    en.stage(b, rooms, keys, turns, host, off_keys, off_turns);
+    char *dev = nullptr;
+    if ((st = pool_scratch(b, total, &dev)) != GE_OK) return st;
+    hipStream_t s = b->last_stream;
+    if ((st = order_after_previous(b, s)) != GE_OK) return st;
+    HIP_TRY(hipMemcpyAsync(dev, host, off_ev, hipMemcpyHostToDevice, s));
+    if ((st = launch_pool_turn(b, s, en, dev, off_keys, off_turns, off_ev)) != GE_OK) return st;
     uint32_t *h_ev = reinterpret_cast<uint32_t *>(host + off_ev);
     HIP_TRY(hipMemcpyAsync(h_ev, dev + off_ev, 16 * (size_t)n, hipMemcpyDeviceToHost, s));
     if ((st = sync_impl(b)) != GE_OK) return st;
     if (events)
-        for (size_t i = 0; i < n; i++) pool_decode_event(h_ev + 4 * i, b->segs[seg_of[order[i]]].table, events[order[i]]);
+        for (size_t i = 0; i < n; i++) pool_decode_event(h_ev + 4 * i, b->segs[en.seg_at(i)].table, events[en.order[i]]);
     return GE_OK;
 }
 
@@ -355,13 +416,8 @@ static int read_rooms_at_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, ge
 
 static int write_rooms_at_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const ge_room_view *src) {
     if (n == 0) return GE_OK;
-    for (uint64_t k = 0; k < n; k++)                              // all-or-nothing: every entry is checked before anything is written
-        if (rooms[k] >= b->n_rooms) return GE_ERR_RANGE;
-    {
-        std::vector<uint64_t> sorted(rooms, rooms + n);
-        std::sort(sorted.begin(), sorted.end());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return GE_ERR_ARG;
-    }
+    int st = pool_check_rooms(b, n, rooms);                       // all-or-nothing: every entry is checked before anything is written
+    if (st != GE_OK) return st;
     std::vector<uint32_t> seg_of((size_t)n);
     for (uint64_t k = 0; k < n; k++) {
         seg_of[k] = pool_segment_of(b, rooms[k]);
@@ -369,10 +425,9 @@ static int write_rooms_at_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, c
         if (!view_fits(src[k], sg.table, sg.dev.n_players)) { g_last_rejected_room = rooms[k]; return GE_ERR_ARG; }
     }
     GE_ON_DEVICE(b);
-    int st = sync_impl(b);
-    if (st != GE_OK) return st;
+    if ((st = sync_impl(b)) != GE_OK) return st;
     // one upload: [rooms u64 x n (padded to 16 B)][records 12 words x n]
-    const size_t off_rec = (8 * (size_t)n + 15u) & ~(size_t)15u, total = off_rec + 48 * (size_t)n;
+    const size_t off_rec = up16(8 * (size_t)n), total = off_rec + 48 * (size_t)n;
     uint32_t *host32 = nullptr;
     if ((st = io_stage(b, total, &host32)) != GE_OK) return st;
     unsigned char *host = reinterpret_cast<unsigned char *>(host32);

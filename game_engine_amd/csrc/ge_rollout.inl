@@ -1,6 +1,7 @@
 // ge_rollout.inl — on-device playouts (ge_batch_rollout_rooms): from where a room stands, R replicas of it are played to the end
 // (or for M turns) and only their outcome is reduced (included at the end of ge_step.hip, behind ge_pool.inl: the existing kernels
-// keep their code-object offsets; it needs ge_batch's internals and ge_pool.inl's helpers).
+// keep their code-object offsets).  Each chunk's entries are grouped, staged and launched by ge_pool.inl's PoolEntries and by_kind;
+// what this file adds is the replica lane, the action and view prologues, the reduction and the chunked staging of a call.
 //
 // Replica r of entry k is what a lone batch B' (seed, first_room = keys[k], flags 0, one segment of R rooms with human mask 0)
 // does to a copy of batch room rooms[k] under set_turn(turns[k]) + step(M): global room keys[k] + r at turns turns[k] ..
@@ -9,7 +10,7 @@
 //
 // One wavefront per (entry, 64 replicas); the lane is the replica.  Nothing of a replica lives in HBM: the source record is loaded
 // once (the same address in every lane), unpacked into registers and stepped there with the single-turn ww_turn / tt_turn of the
-// lone-wavefront build (tables read where they lie in global memory, as ge_pool_kernel does).  Lanes past R stay in the wavefront
+// lone-wavefront build through ge_pool.inl's indexed lane (lane_ww_ctx / lane_cond_ctx, lane_ww_turn / lane_tt_turn).  Lanes past R stay in the wavefront
 // (the action queue is a wave-wide collective): they play replica 0's game again, acting as it does, so that they settle when it
 // does, and add nothing.  Prepared role deals are never used (Deal
 // {0}: an assignment deals on the spot), so neither the record's deal cache nor the Werewolf x 12 side plane is read.
@@ -315,23 +316,14 @@ __device__ __forceinline__ void roll_ww(const SegDev &sg, const DevTable *__rest
     const uint64_t g = key + r;
     const uint32_t rk = room_key_from(a.seed_key, g);
     if constexpr (ACT >= 2) roll_view_ww<NB>(sg, tables, a, e, rk, turn0, w);
-    const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
-    const DevRow *rows = reinterpret_cast<const DevRow *>(img);
-    const CondShape cs = GENERIC ? pool_cond_shape(tables[sg.table_idx]) : CondShape{0u, 0u, 0u, 0u, 0u};
-    const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
     const uint32_t phase0 = __builtin_amdgcn_readfirstlane(sg.phase0_idx);
-    const WwCtx ctx = {rows, CondCtx{reinterpret_cast<const unsigned char *>(tables[sg.table_idx].cond_img), cs}, lw, img + IMG_NTH8,
-                       reinterpret_cast<const uint32_t *>(img + IMG_ORD8), true, sg.n_players, sg.nw, sg.phase0_idx, rk, 0u, term_mask};
+    const WwCtx ctx = lane_ww_ctx<GENERIC, false>(sg, tables, lw, rk, true);   // every seat played by the policy
+    const DevRow *rows = ctx.rows;
     WWR<NB> s;
     uint32_t cache;                                           // the record's prepared deal: not of these keys, never used
     ww_load_regs<NB>(w, s, cache);
     for (uint32_t t = 0; t < a.max_turns; t++) {
-        DevRow row = lds_row<false>(rows, s.phase);
-        Deal deal = {0u, 0u, 0u, 0u, 0u};
-        uint32_t tk = turn_key(rk, turn0 + t);
-        uint32_t ev_newly = 0;
-        uint64_t ev_choice = 0;
-        ww_turn<NB, true, GENERIC, true>(s, row, ctx, turn0 + t, tk, false, deal, false, ev_newly, ev_choice, nullptr);
+        lane_ww_turn<NB, GENERIC>(s, ctx, turn0 + t, false);
         const bool settled = ((a.settle_mask >> s.phase) & 1u) && (s.phase != phase0 || (s.flags & FLAG_PHASE0_DONE));
         if (__ballot(!settled) == 0ull) break;
     }
@@ -368,8 +360,7 @@ __device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__rest
     const uint32_t rk = room_key_from(a.seed_key, g);
     const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
     const DevRow *rows = reinterpret_cast<const DevRow *>(img);
-    const CondShape cs = GENERIC ? pool_cond_shape(tables[sg.table_idx]) : CondShape{0u, 0u, 0u, 0u, 0u};
-    const CondCtx cc = {reinterpret_cast<const unsigned char *>(tables[sg.table_idx].cond_img), cs};
+    const CondCtx cc = lane_cond_ctx<GENERIC>(sg, tables);
     const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
     const uint32_t phase0 = __builtin_amdgcn_readfirstlane(sg.phase0_idx);
     TT<NB> s;
@@ -382,11 +373,7 @@ __device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__rest
     }
     uint32_t done = tt_done_mask<NB>(s.rounds, sg.rounds);
     for (uint32_t t = 0; t < a.max_turns; t++) {
-        DevRow row = lds_row<false>(rows, s.phase);
-        uint32_t ev_newly = 0;
-        uint64_t ev_choice = 0;
-        tt_turn<NB, tt_uses_queue(NB, true), false, GENERIC, true>(s, done, row, rows, cc, lw, img + IMG_NTH8, true, sg.n_players, sg.rounds,
-                                                                 sg.phase0_idx, rk, turn0 + t, false, 0u, term_mask, ev_newly, ev_choice);
+        lane_tt_turn<NB, GENERIC, false>(s, done, sg, tables, cc, lw, true, rk, turn0 + t, false, term_mask);
         const bool settled = ((a.settle_mask >> s.phase) & 1u) && (s.phase != phase0 || (s.flags & FLAG_PHASE0_DONE));
         if (__ballot(!settled) == 0ull) break;
     }
@@ -432,23 +419,12 @@ __global__ void __launch_bounds__(64) ge_rollout_kernel(const SegDev *__restrict
     if (threadIdx.x < 16) { h_end[threadIdx.x] = 0; h_score[threadIdx.x] = 0; }
     __syncthreads();
     void *lw = ge_lds;
-    if (KIND == K_WW8) roll_ww<8, GENERIC, ACT>(sg, tables, a, lw, e, r, part, h_end, h_score);
-    else if (KIND == K_WW12) roll_ww<12, GENERIC, ACT>(sg, tables, a, lw, e, r, part, h_end, h_score);
-    else if (KIND == K_TT4) roll_tt<4, GENERIC, ACT>(sg, tables, a, lw, e, r, part, h_end, h_score);
-    else if (KIND == K_TT8) roll_tt<8, GENERIC, ACT>(sg, tables, a, lw, e, r, part, h_end, h_score);
-    else roll_tt<12, GENERIC, ACT>(sg, tables, a, lw, e, r, part, h_end, h_score);
+    if constexpr (KindOf<KIND>::WW) roll_ww<KindOf<KIND>::NB, GENERIC, ACT>(sg, tables, a, lw, e, r, part, h_end, h_score);
+    else roll_tt<KindOf<KIND>::NB, GENERIC, ACT>(sg, tables, a, lw, e, r, part, h_end, h_score);
 }
 
 template <int GEN, int ACT> hipError_t rollout_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const RollArgs<ACT> &a) {
-    const uint32_t lds = (kind == K_TT4) ? 0u : (uint32_t)sizeof(WaveLdsLow);
-    switch (kind) {
-    case K_WW8: hipLaunchKernelGGL((ge_rollout_kernel<K_WW8, GEN, ACT>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    case K_WW12: hipLaunchKernelGGL((ge_rollout_kernel<K_WW12, GEN, ACT>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    case K_TT4: hipLaunchKernelGGL((ge_rollout_kernel<K_TT4, GEN, ACT>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    case K_TT8: hipLaunchKernelGGL((ge_rollout_kernel<K_TT8, GEN, ACT>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    default: hipLaunchKernelGGL((ge_rollout_kernel<K_TT12, GEN, ACT>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    }
-    return hipGetLastError();
+    return by_kind(kind, [&](auto K) { hipLaunchKernelGGL((ge_rollout_kernel<K(), GEN, ACT>), grid, dim3(64), lane_lds(kind), st, b->segs_dev, b->tables, a); });
 }
 
 // bit p = row p of the segment's table is terminal and no bot acts in it (see "Early exit" above)
@@ -522,20 +498,14 @@ static int rollout_rooms_impl(ge_batch *b, const RollRequest &r) {
     std::vector<uint32_t> settle(n_seg);
     for (uint32_t g = 0; g < n_seg; g++) settle[g] = rollout_settle_mask(b->segs[g]);
     int first_bad = GE_OK;                                  // with actions: the status of the first refused entry
-    // entries in chunks (bounded staging and accumulator memory); within a chunk a stable counting sort by segment, one launch
+    // entries in chunks (bounded staging and accumulator memory); within a chunk grouped by segment (PoolEntries), one launch
     // per segment present (a wavefront never mixes layouts)
     const uint64_t CHUNK = 65536;
     for (uint64_t c0 = 0; c0 < r.n; c0 += CHUNK) {
         const uint32_t cn = (uint32_t)std::min<uint64_t>(CHUNK, r.n - c0);
-        std::vector<uint32_t> seg_of(cn), begin(n_seg + 1u, 0u), order(cn);
-        for (uint32_t k = 0; k < cn; k++) { seg_of[k] = pool_segment_of(b, r.rooms[c0 + k]); begin[seg_of[k] + 1u]++; }
-        for (uint32_t s = 0; s < n_seg; s++) begin[s + 1u] += begin[s];
-        {
-            std::vector<uint32_t> at(begin.begin(), begin.end() - 1);
-            for (uint32_t k = 0; k < cn; k++) order[at[seg_of[k]]++] = k;
-        }
+        const PoolEntries en(b, cn, r.rooms + c0);
+        const std::vector<uint32_t> &order = en.order;
         const uint32_t na = r.first_action ? r.first_action[c0 + cn] - r.first_action[c0] : 0u;
-        auto up16 = [](size_t x) { return (x + 15u) & ~(size_t)15u; };
         RollStage o;
         o.keys = 8 * (size_t)cn; o.turns = 16 * (size_t)cn;
         o.first = up16(o.turns + 4 * (size_t)cn); o.players = up16(o.first + (act ? 4 * ((size_t)cn + 1u) : 0u));
@@ -552,14 +522,7 @@ static int rollout_rooms_impl(ge_batch *b, const RollRequest &r) {
         uint32_t *host32 = nullptr;
         if ((st = io_stage(b, o.total, &host32)) != GE_OK) return st;
         unsigned char *host = reinterpret_cast<unsigned char *>(host32);
-        uint64_t *h_rooms = reinterpret_cast<uint64_t *>(host), *h_keys = reinterpret_cast<uint64_t *>(host + o.keys);
-        uint32_t *h_turns = reinterpret_cast<uint32_t *>(host + o.turns);
-        for (uint32_t i = 0; i < cn; i++) {
-            const uint64_t k = c0 + order[i];
-            h_rooms[i] = r.rooms[k] - b->segs[seg_of[order[i]]].local_first;
-            h_keys[i] = r.keys[k];
-            h_turns[i] = r.turns[k];
-        }
+        en.stage(b, r.rooms + c0, r.keys + c0, r.turns + c0, host, o.keys, o.turns);
         if (act) {                                            // the actions in the sorted order, offsets from the chunk's first
             uint32_t *h_first = reinterpret_cast<uint32_t *>(host + o.first), *h_pl = reinterpret_cast<uint32_t *>(host + o.players);
             uint32_t *h_ch = reinterpret_cast<uint32_t *>(host + o.choices);
@@ -590,7 +553,7 @@ static int rollout_rooms_impl(ge_batch *b, const RollRequest &r) {
         HIP_TRY(hipMemcpyAsync(dev, host, o.acc, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemsetAsync(dev + o.acc, 0, acc_bytes, s));
         for (uint32_t g = 0; g < n_seg; g++) {
-            const uint32_t lo = begin[g], cnt = begin[g + 1u] - lo;
+            const uint32_t lo = en.begin[g], cnt = en.begin[g + 1u] - lo;
             if (!cnt) continue;
             RolloutArgs a;
             a.rooms = reinterpret_cast<const uint64_t *>(dev) + lo;

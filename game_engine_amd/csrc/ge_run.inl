@@ -1,6 +1,8 @@
 // ge_run.inl — listed rooms played on until a person is needed (ge_batch_run_rooms, POLICY.md §3f): ge_batch_step_rooms turn
 // after turn inside one launch, each turn's event and record traced (included at the end of ge_step.hip, behind ge_compare.inl:
-// the existing kernels keep their code-object offsets; it needs ge_pool.inl's helpers).
+// the existing kernels keep their code-object offsets).  Checks, grouping, staging and the launch by kind are ge_pool.inl's
+// (pool_check_entries, PoolEntries, by_kind), and so is the lane that plays a turn; the timed interval is ge_step.hip's
+// timing_begin.  What this file adds is the turn loop in the kernel, its stop tests and the trace plane.
 //
 // A game thread spends most of its turns in phases where no person has anything to do - timers, UI phases, other roles' night
 // phases, "waiting" turns in which a bot acts with probability 3/4.  Played through ge_batch_step_rooms + ge_batch_read_rooms_at
@@ -8,8 +10,8 @@
 // until the record the turn left meets a condition of `until` or max_turns turns are played; what every turn logged and left
 // goes into a device trace plane and crosses to the host once.
 //
-// ge_run_kernel follows ge_pool_kernel: one lane per entry, one wavefront per block, the lone-wavefront single-turn ww_turn /
-// tt_turn, tables read in place, key and turn per lane.  The turn loop holds the per-lane restart check, the turn, the trace
+// ge_run_kernel: one lane per entry, one wavefront per block, the indexed lane of ge_pool.inl (lane_ww_ctx / lane_cond_ctx,
+// lane_recycle, lane_ww_turn / lane_tt_turn, lane_event).  The turn loop holds the per-lane restart check, the turn, the trace
 // store and the stop test.  The action queue is a wave-wide collective, so a lane whose room has stopped cannot leave the loop:
 // it stores its record, its turn count and its stop bits at that moment and stays on as a shadow that never acts and stores
 // nothing - what a lane past the end of the list is from the start.  The wavefront leaves when no lane is live.
@@ -38,13 +40,9 @@ struct RunArgs {
 
 // turn t of sorted entry i: event words, then the record's WORDS words (a 16-byte store per started group of four)
 template <int WORDS>
-__device__ __forceinline__ void run_trace(const RunArgs &a, uint32_t t, uint32_t k, uint32_t turn, uint32_t p, uint32_t q, uint32_t restarted,
-                                          uint32_t newly, uint64_t choice, const uint32_t *w) {
+__device__ __forceinline__ void run_trace(const RunArgs &a, uint32_t t, uint32_t k, const u32x4 &event, const uint32_t *w) {
     u32x4 *slot = a.trace + 4u * ((size_t)t * a.n_all + a.first + k);
-    u32x4 v;
-    v.x = turn; v.y = p | (q << 8) | (restarted << 16) | (newly << 20);
-    v.z = (uint32_t)choice; v.w = (uint32_t)(choice >> 32);
-    slot[0] = v;
+    slot[0] = event;
 #pragma unroll
     for (int j = 0; j < (WORDS + 3) / 4; j++) {
         u32x4 r;
@@ -65,41 +63,23 @@ __device__ __forceinline__ void run_ww(const SegDev &sg, const DevTable *__restr
     load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
     const uint32_t rk = room_key_from(a.seed_key, a.keys[k]);
     const uint32_t turn0 = a.turns[k];
-    const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
-    const DevRow *rows = reinterpret_cast<const DevRow *>(img);
-    const CondShape cs = GENERIC ? pool_cond_shape(tables[sg.table_idx]) : CondShape{0u, 0u, 0u, 0u, 0u};
-    const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
+    WwCtx ctx = lane_ww_ctx<GENERIC, true>(sg, tables, lw, rk, live);
+    const DevRow *rows = ctx.rows;
+    const uint32_t term_mask = ctx.term_mask;
     const uint32_t ALL = (1u << sg.n_players) - 1u;
-    WwCtx ctx = {rows, CondCtx{reinterpret_cast<const unsigned char *>(tables[sg.table_idx].cond_img), cs}, lw, img + IMG_NTH8,
-                 reinterpret_cast<const uint32_t *>(img + IMG_ORD8), live, sg.n_players, sg.nw, sg.phase0_idx, rk, sg.human_mask, term_mask};
     WWR<NB> s;
     uint32_t cache;                                           // the record's prepared deal: not of this key, never used
     ww_load_regs<NB>(w, s, cache);
     for (uint32_t t = 0;;) {
         const uint32_t turn = turn0 + t;
-        uint32_t restarted = 0;
-        if (a.restart && ((term_mask >> s.phase) & 1u)) {     // recycle a finished room (pool_ww's check, every turn)
-            uint32_t ir[20];
-            load_init_regs<WWR<NB>::NREGS>(sg, ir);
-            const uint32_t g = s.games;
-            WWR<NB> s0;
-            s0.from_regs(ir);
-            s = s0;
-            s.games = g < 0xFFFFu ? g + 1u : g;
-            restarted = 1;
-        }
-        DevRow row = lds_row<false>(rows, s.phase);
-        const uint32_t p = s.phase;
-        Deal deal = {0u, 0u, 0u, 0u, 0u};                     // no prepared deal, as every ge_batch_step_rooms call starts
-        uint32_t tk = turn_key(rk, turn);
-        uint32_t ev_newly = 0;
-        uint64_t ev_choice = 0;
-        ctx.valid = live;
-        ww_turn<NB, true, GENERIC, true>(s, row, ctx, turn, tk, true, deal, false, ev_newly, ev_choice, nullptr);
+        const uint32_t restarted = lane_recycle(sg, s, a.restart, term_mask);   // every turn
+        ctx.valid = live;                                     // a stopped lane is a shadow from here on
+        const LaneTurn ev = lane_ww_turn<NB, GENERIC>(s, ctx, turn, true);
+        const uint32_t p = ev.p;
         t++;
         if (live) {
             ww_store_regs<NB>(s, 0u, w);                      // without a prepared deal
-            run_trace<L::WORDS>(a, t - 1u, k, turn, p, s.phase, restarted, ev_newly, ev_choice, w);
+            run_trace<L::WORDS>(a, t - 1u, k, lane_event(turn, ev, s.phase, restarted), w);
             uint32_t why = 0;
             if (a.until & GE_RUN_UNTIL_PERSON) {
                 const DevRow nrow = lds_row<false>(rows, s.phase);
@@ -129,10 +109,7 @@ __device__ __forceinline__ void run_tt(const SegDev &sg, const DevTable *__restr
     load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
     const uint32_t rk = room_key_from(a.seed_key, a.keys[k]);
     const uint32_t turn0 = a.turns[k];
-    const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
-    const DevRow *rows = reinterpret_cast<const DevRow *>(img);
-    const CondShape cs = GENERIC ? pool_cond_shape(tables[sg.table_idx]) : CondShape{0u, 0u, 0u, 0u, 0u};
-    const CondCtx cc = {reinterpret_cast<const unsigned char *>(tables[sg.table_idx].cond_img), cs};
+    const CondCtx cc = lane_cond_ctx<GENERIC>(sg, tables);
     const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
     const uint32_t human = __builtin_amdgcn_readfirstlane(sg.human_mask) & ((1u << sg.n_players) - 1u);
     TT<NB> s;
@@ -140,28 +117,14 @@ __device__ __forceinline__ void run_tt(const SegDev &sg, const DevTable *__restr
     uint32_t done = tt_done_mask<NB>(s.rounds, sg.rounds);
     for (uint32_t t = 0;;) {
         const uint32_t turn = turn0 + t;
-        uint32_t restarted = 0;
-        if (a.restart && ((term_mask >> s.phase) & 1u)) {     // pool_tt's check, every turn
-            uint32_t ir[20];
-            load_init_regs<TT<NB>::NREGS>(sg, ir);
-            const uint32_t g = s.games;
-            TT<NB> s0;
-            s0.from_regs(ir);
-            s = s0;
-            s.games = g < 0xFFFFu ? g + 1u : g;
-            done = __builtin_amdgcn_readfirstlane(sg.done0);
-            restarted = 1;
-        }
-        DevRow row = lds_row<false>(rows, s.phase);
-        const uint32_t p = s.phase;
-        uint32_t ev_newly = 0;
-        uint64_t ev_choice = 0;
-        tt_turn<NB, tt_uses_queue(NB, true), false, GENERIC, true>(s, done, row, rows, cc, lw, img + IMG_NTH8, live, sg.n_players, sg.rounds, sg.phase0_idx,
-                                                                 rk, turn, true, sg.human_mask, term_mask, ev_newly, ev_choice);
+        const uint32_t restarted = lane_recycle(sg, s, a.restart, term_mask);   // every turn
+        if (restarted) done = __builtin_amdgcn_readfirstlane(sg.done0);
+        const LaneTurn ev = lane_tt_turn<NB, GENERIC, true>(s, done, sg, tables, cc, lw, live, rk, turn, true, term_mask);
+        const uint32_t p = ev.p;
         t++;
         if (live) {
             L::pack(s, w);
-            run_trace<L::WORDS>(a, t - 1u, k, turn, p, s.phase, restarted, ev_newly, ev_choice, w);
+            run_trace<L::WORDS>(a, t - 1u, k, lane_event(turn, ev, s.phase, restarted), w);
             uint32_t why = 0;
             if ((a.until & GE_RUN_UNTIL_PERSON) && human != 0u) {   // (wave-uniform)
                 const DevRow &nrow = tables[sg.table_idx].rows[s.phase];
@@ -190,23 +153,12 @@ __global__ void __launch_bounds__(64) ge_run_kernel(const SegDev *__restrict__ s
     const SegDev &sg = segs[a.seg];
     const uint32_t k = blockIdx.x * 64u + threadIdx.x;
     void *lw = ge_lds;
-    if (KIND == K_WW8) run_ww<8, GENERIC>(sg, tables, a, lw, k);
-    else if (KIND == K_WW12) run_ww<12, GENERIC>(sg, tables, a, lw, k);
-    else if (KIND == K_TT4) run_tt<4, GENERIC>(sg, tables, a, lw, k);
-    else if (KIND == K_TT8) run_tt<8, GENERIC>(sg, tables, a, lw, k);
-    else run_tt<12, GENERIC>(sg, tables, a, lw, k);
+    if constexpr (KindOf<KIND>::WW) run_ww<KindOf<KIND>::NB, GENERIC>(sg, tables, a, lw, k);
+    else run_tt<KindOf<KIND>::NB, GENERIC>(sg, tables, a, lw, k);
 }
 
 template <int GEN> hipError_t run_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const RunArgs &a) {
-    const uint32_t lds = (kind == K_TT4) ? 0u : (uint32_t)sizeof(WaveLdsLow);
-    switch (kind) {
-    case K_WW8: hipLaunchKernelGGL((ge_run_kernel<K_WW8, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    case K_WW12: hipLaunchKernelGGL((ge_run_kernel<K_WW12, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    case K_TT4: hipLaunchKernelGGL((ge_run_kernel<K_TT4, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    case K_TT8: hipLaunchKernelGGL((ge_run_kernel<K_TT8, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    default: hipLaunchKernelGGL((ge_run_kernel<K_TT12, GEN>), grid, dim3(64), lds, st, b->segs_dev, b->tables, a); break;
-    }
-    return hipGetLastError();
+    return by_kind(kind, [&](auto K) { hipLaunchKernelGGL((ge_run_kernel<K(), GEN>), grid, dim3(64), lane_lds(kind), st, b->segs_dev, b->tables, a); });
 }
 
 constexpr uint32_t RUN_MAX_TURNS = 4096u, RUN_MAX_SLOTS = 1u << 20;
@@ -226,43 +178,25 @@ static int run_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const 
         if ((uint64_t)turns[k] + max_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;
     GE_ON_DEVICE(b);
     if ((st = sync_impl(b)) != GE_OK) return st;
-    const uint32_t n_seg = (uint32_t)b->segs.size();
-    std::vector<uint32_t> seg_of, begin, order;
-    pool_group_entries(b, n, rooms, seg_of, begin, order);
+    const PoolEntries en(b, n, rooms);
     // one upload: [rooms u64 x n][keys u64 x n][turns u32 x n (padded to 16 B)]; then [played, stopped] x n (padded) and the trace plane
-    const size_t off_keys = 8 * (size_t)n, off_turns = 16 * (size_t)n, off_out = (off_turns + 4 * (size_t)n + 15u) & ~(size_t)15u;
-    const size_t off_trace = (off_out + 8 * (size_t)n + 15u) & ~(size_t)15u, row_bytes = 64 * (size_t)n;
+    const size_t off_keys = 8 * (size_t)n, off_turns = 16 * (size_t)n, off_out = up16(off_turns + 4 * (size_t)n);
+    const size_t off_trace = up16(off_out + 8 * (size_t)n), row_bytes = 64 * (size_t)n;
     const size_t total = off_trace + row_bytes * max_turns;
     uint32_t *host32 = nullptr;
     if ((st = io_stage(b, total, &host32)) != GE_OK) return st;
     unsigned char *host = reinterpret_cast<unsigned char *>(host32);
-    uint64_t *h_rooms = reinterpret_cast<uint64_t *>(host), *h_keys = reinterpret_cast<uint64_t *>(host + off_keys);
-    uint32_t *h_turns = reinterpret_cast<uint32_t *>(host + off_turns);
-    for (size_t i = 0; i < n; i++) {
-        const uint32_t k = order[i];
-        h_rooms[i] = rooms[k] - b->segs[seg_of[k]].local_first;
-        h_keys[i] = keys[k];
-        h_turns[i] = turns[k];
-    }
+    en.stage(b, rooms, keys, turns, host, off_keys, off_turns);
     char *dev = nullptr;
     if ((st = pool_scratch(b, total, &dev)) != GE_OK) return st;
     hipStream_t s = b->last_stream;
     if ((st = order_after_previous(b, s)) != GE_OK) return st;
     HIP_TRY(hipMemcpyAsync(dev, host, off_out, hipMemcpyHostToDevice, s));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (b->timing) {                                              // ge_batch_kernel_time counts the launches of this call as one interval
-        if (b->events_used == b->events.size()) {
-            HIP_TRY(hipEventCreate(&e0));
-            HIP_TRY(hipEventCreate(&e1));
-            b->events.emplace_back(e0, e1);
-        }
-        e0 = b->events[b->events_used].first; e1 = b->events[b->events_used].second;
-        b->events_used++;
-        HIP_TRY(hipEventRecord(e0, s));
-    }
+    hipEvent_t e1 = nullptr;                                      // ge_batch_kernel_time counts the launches of this call as one interval
+    if ((st = timing_begin(b, s, &e1)) != GE_OK) return st;
     const uint32_t seed_k = seed_key((uint32_t)b->seed, (uint32_t)(b->seed >> 32));
-    for (uint32_t g = 0; g < n_seg; g++) {
-        const uint32_t lo = begin[g], cnt = begin[g + 1u] - lo;
+    for (uint32_t g = 0; g < (uint32_t)b->segs.size(); g++) {
+        const uint32_t lo = en.begin[g], cnt = en.begin[g + 1u] - lo;
         if (!cnt) continue;
         RunArgs a;
         a.rooms = reinterpret_cast<const uint64_t *>(dev) + lo;
@@ -276,7 +210,7 @@ static int run_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const 
         const dim3 grid((cnt + 63u) / 64u);
         HIP_TRY(b->generic ? run_launch<1>(b->segs[g].dev.kind, grid, s, b, a) : run_launch<0>(b->segs[g].dev.kind, grid, s, b, a));
     }
-    if (b->timing) HIP_TRY(hipEventRecord(e1, s));
+    if (e1) HIP_TRY(hipEventRecord(e1, s));
     // the turn counts first: only the rows of turns somebody played are copied - unless the whole plane is small
     const uint32_t *h_out = reinterpret_cast<const uint32_t *>(host + off_out);
     const bool whole = row_bytes * max_turns <= RUN_ONE_COPY;
@@ -288,8 +222,8 @@ static int run_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const 
         const uint32_t p = h_out[2 * i];
         prefix[i + 1u] = prefix[i] + p;
         rows_played = std::max(rows_played, p);
-        played[order[i]] = p;
-        if (stopped) stopped[order[i]] = h_out[2 * i + 1u];
+        played[en.order[i]] = p;
+        if (stopped) stopped[en.order[i]] = h_out[2 * i + 1u];
     }
     if (!events && !views) return GE_OK;
     if (!whole) {
@@ -303,9 +237,9 @@ static int run_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const 
         for (uint64_t x = lo; x < hi; x++) {
             while (x >= prefix[i + 1u]) i++;
             const uint32_t t = (uint32_t)(x - prefix[i]);
-            const Segment &sg = b->segs[seg_of[order[i]]];
+            const Segment &sg = b->segs[en.seg_at(i)];
             const uint32_t *slot = h_trace + 16u * ((size_t)t * n + i);
-            const size_t at = (size_t)order[i] * max_turns + t;
+            const size_t at = (size_t)en.order[i] * max_turns + t;
             if (events) pool_decode_event(slot, sg.table, events[at]);
             if (views) {
                 uint32_t w[12] = {0};

@@ -560,6 +560,25 @@ static hipGraphExec_t graph_for(ge_batch *b, uint32_t n_turns) {
     return exec;
 }
 
+// a timed interval opens on stream st: the batch's next event pair (created when none is left over from before the last
+// ge_batch_kernel_time), its first event recorded; *e1 is the one to record behind the interval's last launch.  Timing off: null
+static int timing_begin(ge_batch *b, hipStream_t st, hipEvent_t *e1) {
+    *e1 = nullptr;
+    if (!b->timing) return GE_OK;
+    if (b->events_used == b->events.size()) {
+        hipEvent_t n0 = nullptr, n1 = nullptr;
+        HIP_TRY(hipEventCreate(&n0));
+        const hipError_t e = hipEventCreate(&n1);
+        if (e != hipSuccess) { (void)hipEventDestroy(n0); HIP_TRY(e); }
+        b->events.emplace_back(n0, n1);
+    }
+    const hipEvent_t e0 = b->events[b->events_used].first;
+    *e1 = b->events[b->events_used].second;
+    b->events_used++;
+    HIP_TRY(hipEventRecord(e0, st));
+    return GE_OK;
+}
+
 static int step_impl(ge_batch *b, uint32_t n_turns, void *hip_stream) {
     if (b->turn + n_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;
     if ((b->flags & GE_FLAG_TRACE) && n_turns > b->max_fuse) return GE_ERR_RANGE;   // the trace holds one launch
@@ -593,19 +612,11 @@ static int step_impl(ge_batch *b, uint32_t n_turns, void *hip_stream) {
         const uint32_t k = left < b->max_fuse ? left : b->max_fuse;
         StepArgs a;
         fill_args(b, a, (uint32_t)b->turn, k);
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (b->timing) {
-            if (b->events_used == b->events.size()) {
-                HIP_TRY(hipEventCreate(&e0));
-                HIP_TRY(hipEventCreate(&e1));
-                b->events.emplace_back(e0, e1);
-            }
-            e0 = b->events[b->events_used].first; e1 = b->events[b->events_used].second;
-            b->events_used++;
-            HIP_TRY(hipEventRecord(e0, st));
-        }
+        hipEvent_t e1 = nullptr;
+        int tb = timing_begin(b, st, &e1);
+        if (tb != GE_OK) return tb;
         HIP_TRY(launch_step(b, a, st));
-        if (b->timing) HIP_TRY(hipEventRecord(e1, st));
+        if (e1) HIP_TRY(hipEventRecord(e1, st));
         b->launches++;
         b->turn += k;
         left -= k;
