@@ -211,20 +211,16 @@ struct PlayoutUnit {
     uint32_t pass;
 };
 
-static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, const uint32_t *masks,
-                             const uint64_t *pkeys, uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, uint32_t flags, ge_turn_event *events,
-                             uint32_t *decided) {
-    GE_ON_DEVICE(b);
-    int st = sync_impl(b);
-    if (st != GE_OK) return st;
+// units: runs of one segment with at most CHUNK entries' room (a room needs popcount(mask) x playout_max_cands at most); passes:
+// consecutive units whose room fits in CHUNK entries together.  A pass's entries are planned, played and decided together.
+// max_cap: the most entries a pass has room for
+static void playout_units(const ge_batch *b, const PoolEntries &en, const uint32_t *masks, std::vector<PlayoutUnit> &units, uint32_t &n_pass,
+                          uint32_t &max_cap) {
     const uint32_t n_seg = (uint32_t)b->segs.size();
-    const PoolEntries en(b, n, rooms);
     const std::vector<uint32_t> &begin = en.begin, &order = en.order;
-    // units: runs of one segment with at most CHUNK entries' room (a room needs popcount(mask) x playout_max_cands at most); passes:
-    // consecutive units whose room fits in CHUNK entries together.  A pass's entries are planned, played and decided together.
     const uint32_t CHUNK = 65536;
-    std::vector<PlayoutUnit> units;
-    uint32_t n_pass = 0, pass_cap = 0, max_cap = 0;
+    uint32_t pass_cap = 0;
+    n_pass = 0; max_cap = 0;
     for (uint32_t g = 0; g < n_seg; g++) {
         const uint32_t np = playout_max_cands(b->segs[g].dev);
         for (uint32_t i = begin[g]; i < begin[g + 1u]; i++) {
@@ -241,6 +237,19 @@ static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
             max_cap = std::max(max_cap, pass_cap);
         }
     }
+}
+
+static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, const uint32_t *masks,
+                             const uint64_t *pkeys, uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, uint32_t flags, ge_turn_event *events,
+                             uint32_t *decided) {
+    GE_ON_DEVICE(b);
+    int st = sync_impl(b);
+    if (st != GE_OK) return st;
+    const PoolEntries en(b, n, rooms);
+    const std::vector<uint32_t> &order = en.order;
+    std::vector<PlayoutUnit> units;
+    uint32_t n_pass = 0, max_cap = 0;
+    playout_units(b, en, masks, units, n_pass, max_cap);
     const uint32_t n_units = (uint32_t)units.size();
     // one scratch layout, each array from a 16 B boundary.  Upload: [rooms u64][keys u64][pkeys u64][turns u32][masks u32]
     // [unit counters u32][per-room outputs 16 B, zeroed].  Then [room_first u32][room_cnt u32][events 16 B] and the pass's
@@ -352,6 +361,26 @@ static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
     return GE_OK;
 }
 
+// the playout checks of ge_batch_step_rooms_playout, behind ge_batch_step_rooms's (the rooms are in range): ge_batch_rollout_seats's
+// caps, the turn range of the playouts, the masks and the cost cap.  more_turns: the turns a room is played on before its last turn's
+// playouts (ge_batch_run_rooms_playout: max_turns - 1); the cost cap is per turn, as only one turn's playouts exist at a time
+static int playout_check(const ge_batch *b, uint64_t n, const uint64_t *rooms, const uint32_t *turns, const uint32_t *playout_masks,
+                         const uint64_t *playout_keys, uint32_t n_rollouts, uint32_t max_turns, uint32_t flags, uint32_t more_turns) {
+    if (!playout_masks || !playout_keys || (flags & ~GE_PLAYOUT_FULL_VIEW)) return GE_ERR_ARG;
+    if (n_rollouts == 0 || n_rollouts > (1u << 20) || max_turns > 4096u) return GE_ERR_ARG;
+    for (uint64_t k = 0; k < n; k++)
+        if ((uint64_t)turns[k] + more_turns + max_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;
+    uint64_t cost = 0;
+    for (uint64_t k = 0; k < n; k++) {
+        const SegDev &sg = b->segs[pool_segment_of(b, rooms[k])].dev;
+        const uint32_t m = playout_masks[k];
+        if ((m >> sg.n_players) != 0u || (m & sg.human_mask) != 0u) return GE_ERR_ARG;
+        cost += (uint64_t)__builtin_popcount(m) * playout_max_cands(sg) * n_rollouts;
+        if (cost > (1ull << 26)) return GE_ERR_ARG;
+    }
+    return GE_OK;
+}
+
 extern "C" {
 
 int ge_batch_step_rooms_playout(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
@@ -361,19 +390,8 @@ int ge_batch_step_rooms_playout(ge_batch *b, uint64_t n, const uint64_t *rooms, 
     if (n == 0) return GE_OK;
     const int st = pool_check_entries(b, n, rooms, keys, turns);   // ge_batch_step_rooms's checks, in its order
     if (st != GE_OK) return st;
-    // then the playouts': ge_batch_rollout_seats's caps, the masks and the cost cap
-    if (!playout_masks || !playout_keys || (flags & ~GE_PLAYOUT_FULL_VIEW)) return GE_ERR_ARG;
-    if (n_rollouts == 0 || n_rollouts > (1u << 20) || max_turns > 4096u) return GE_ERR_ARG;
-    for (uint64_t k = 0; k < n; k++)
-        if ((uint64_t)turns[k] + max_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;
-    uint64_t cost = 0;
-    for (uint64_t k = 0; k < n; k++) {
-        const SegDev &sg = b->segs[pool_segment_of(b, rooms[k])].dev;
-        const uint32_t m = playout_masks[k];
-        if ((m >> sg.n_players) != 0u || (m & sg.human_mask) != 0u) return GE_ERR_ARG;
-        cost += (uint64_t)__builtin_popcount(m) * playout_max_cands(sg) * n_rollouts;
-        if (cost > (1ull << 26)) return GE_ERR_ARG;
-    }
+    const int pst = playout_check(b, n, rooms, turns, playout_masks, playout_keys, n_rollouts, max_turns, flags, 0u);
+    if (pst != GE_OK) return pst;
     return guarded([&] { return step_playout_impl(b, n, rooms, keys, turns, playout_masks, playout_keys, n_rollouts, max_turns, seed, flags,
                                                   events, decided); });
 }

@@ -466,9 +466,8 @@ struct RollStage {
 // ge_compare.inl: the paired sums of a comparing call's chunk staged at dev, behind its playouts on stream s
 static hipError_t compare_launch(hipStream_t s, char *dev, const RollStage &o, uint32_t cn, uint32_t n_rollouts, uint32_t waves);
 
-// segment g's entries [lo, lo + cnt) of the chunk staged at dev, as form ACT
-template <int ACT>
-hipError_t rollout_launch_form(const ge_batch *b, hipStream_t s, const RolloutArgs &base, char *dev, const RollStage &o, uint32_t lo) {
+// the arguments of form ACT for segment g's entries [lo, lo + cnt) of the chunk staged at dev
+template <int ACT> RollArgs<ACT> rollout_form_args(const RolloutArgs &base, char *dev, const RollStage &o, uint32_t lo) {
     RollArgs<ACT> a;
     static_cast<RolloutArgs &>(a) = base;
     if constexpr (ACT >= 1) {
@@ -482,6 +481,13 @@ hipError_t rollout_launch_form(const ge_batch *b, hipStream_t s, const RolloutAr
         a.subjects = reinterpret_cast<const uint32_t *>(dev + o.subjects) + lo;
         a.plane = reinterpret_cast<unsigned char *>(dev + o.plane) + (size_t)lo * ((size_t)base.waves * 64u);
     }
+    return a;
+}
+
+// segment g's entries [lo, lo + cnt) of the chunk staged at dev, as form ACT
+template <int ACT>
+hipError_t rollout_launch_form(const ge_batch *b, hipStream_t s, const RolloutArgs &base, char *dev, const RollStage &o, uint32_t lo) {
+    const RollArgs<ACT> a = rollout_form_args<ACT>(base, dev, o, lo);
     const dim3 grid(base.n * base.waves);                   // <= 2^26 blocks (n * R <= 2^26)
     const uint32_t kind = b->segs[base.seg].dev.kind;
     return b->generic ? rollout_launch<1, ACT>(kind, grid, s, b, a) : rollout_launch<0, ACT>(kind, grid, s, b, a);

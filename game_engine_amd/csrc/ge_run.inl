@@ -166,16 +166,74 @@ constexpr size_t RUN_ONE_COPY = 256u << 10;   // a trace plane up to this size c
 
 }  // namespace
 
-static int run_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, uint32_t max_turns,
-                          uint32_t until, uint32_t *played, uint32_t *stopped, ge_turn_event *events, ge_room_view *views, size_t views_cap_bytes) {
-    if (n == 0) return GE_OK;
-    int st = pool_check_entries(b, n, rooms, keys, turns);
+// the checks of ge_batch_run_rooms (n > 0), all before anything runs: ge_batch_step_rooms's first; shared with
+// ge_batch_run_rooms_playout (ge_run_playout.inl)
+static int run_check(const ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, uint32_t max_turns,
+                     uint32_t until, const uint32_t *played, const ge_room_view *views, size_t views_cap_bytes) {
+    const int st = pool_check_entries(b, n, rooms, keys, turns);
     if (st != GE_OK) return st;
     if (!played || max_turns == 0u || max_turns > RUN_MAX_TURNS || n * (uint64_t)max_turns > RUN_MAX_SLOTS) return GE_ERR_ARG;
     if (until & ~(uint32_t)(GE_RUN_UNTIL_PERSON | GE_RUN_UNTIL_END | GE_RUN_UNTIL_PHASE)) return GE_ERR_ARG;
     if (views && views_cap_bytes / sizeof(ge_room_view) < n * (uint64_t)max_turns) return GE_ERR_ARG;
     for (uint64_t k = 0; k < n; k++)
         if ((uint64_t)turns[k] + max_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;
+    return GE_OK;
+}
+
+// the turn counts and stop bits of the sorted entries (h_out: [played, stopped] x n) into input order; prefix[i] = played turns in
+// front of sorted entry i; returns the most turns anybody played
+static uint32_t run_counts(const PoolEntries &en, const uint32_t *h_out, uint32_t *played, uint32_t *stopped, std::vector<uint64_t> &prefix) {
+    const size_t n = en.size();
+    prefix.assign(n + 1u, 0u);
+    uint32_t rows_played = 0;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t p = h_out[2 * i];
+        prefix[i + 1u] = prefix[i] + p;
+        rows_played = std::max(rows_played, p);
+        played[en.order[i]] = p;
+        if (stopped) stopped[en.order[i]] = h_out[2 * i + 1u];
+    }
+    return rows_played;
+}
+
+// the played turns of a trace plane (h_trace: 64 B per room-turn, turn-major) as events and views in input order, split over the
+// host threads of ge_batch_read_rooms.  h_dec (ge_run_playout.inl; may be null): 16 B per room-turn, turn-major - the turn's decided
+// mask and choice nibbles, ORed into the event as ge_batch_step_rooms_playout does
+static void run_decode(const ge_batch *b, const PoolEntries &en, uint32_t max_turns, const std::vector<uint64_t> &prefix, const uint32_t *h_trace,
+                       const uint32_t *h_dec, ge_turn_event *events, ge_room_view *views, uint32_t *decided) {
+    const size_t n = en.size();
+    for_room_ranges(prefix[n], [&](uint64_t lo, uint64_t hi) {
+        size_t i = (size_t)(std::upper_bound(prefix.begin(), prefix.end(), lo) - prefix.begin()) - 1u;
+        for (uint64_t x = lo; x < hi; x++) {
+            while (x >= prefix[i + 1u]) i++;
+            const uint32_t t = (uint32_t)(x - prefix[i]);
+            const Segment &sg = b->segs[en.seg_at(i)];
+            const uint32_t *slot = h_trace + 16u * ((size_t)t * n + i);
+            const size_t at = (size_t)en.order[i] * max_turns + t;
+            const uint32_t *d = h_dec ? h_dec + 4u * ((size_t)t * n + i) : nullptr;
+            if (decided && d) decided[at] = d[0];
+            if (events) {
+                pool_decode_event(slot, sg.table, events[at]);
+                if (d) {
+                    const uint64_t dnib = (uint64_t)d[1] | ((uint64_t)d[2] << 32);
+                    events[at].acted_now |= (uint16_t)d[0];
+                    for (int c = 0; c < 16; c++) events[at].choice[c] |= (uint8_t)((dnib >> (4 * c)) & 15u);
+                }
+            }
+            if (views) {
+                uint32_t w[12] = {0};
+                for (uint32_t j = 0; j < sg.dev.words; j++) w[j] = slot[4u + j];
+                words_to_view(sg.dev.kind, w, sg.table, (int)sg.dev.n_players, views[at]);
+            }
+        }
+    });
+}
+
+static int run_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, uint32_t max_turns,
+                          uint32_t until, uint32_t *played, uint32_t *stopped, ge_turn_event *events, ge_room_view *views, size_t views_cap_bytes) {
+    if (n == 0) return GE_OK;
+    int st = run_check(b, n, rooms, keys, turns, max_turns, until, played, views, views_cap_bytes);
+    if (st != GE_OK) return st;
     GE_ON_DEVICE(b);
     if ((st = sync_impl(b)) != GE_OK) return st;
     const PoolEntries en(b, n, rooms);
@@ -216,38 +274,14 @@ static int run_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const 
     const bool whole = row_bytes * max_turns <= RUN_ONE_COPY;
     HIP_TRY(hipMemcpyAsync(host + off_out, dev + off_out, whole ? total - off_out : off_trace - off_out, hipMemcpyDeviceToHost, s));
     if ((st = sync_impl(b)) != GE_OK) return st;
-    std::vector<uint64_t> prefix((size_t)n + 1u, 0u);            // played turns in front of sorted entry i
-    uint32_t rows_played = 0;
-    for (size_t i = 0; i < n; i++) {
-        const uint32_t p = h_out[2 * i];
-        prefix[i + 1u] = prefix[i] + p;
-        rows_played = std::max(rows_played, p);
-        played[en.order[i]] = p;
-        if (stopped) stopped[en.order[i]] = h_out[2 * i + 1u];
-    }
+    std::vector<uint64_t> prefix;                                // played turns in front of sorted entry i
+    const uint32_t rows_played = run_counts(en, h_out, played, stopped, prefix);
     if (!events && !views) return GE_OK;
     if (!whole) {
         HIP_TRY(hipMemcpyAsync(host + off_trace, dev + off_trace, row_bytes * rows_played, hipMemcpyDeviceToHost, s));
         if ((st = sync_impl(b)) != GE_OK) return st;
     }
-    // played turns only, split over the host threads of ge_batch_read_rooms
-    const uint32_t *h_trace = reinterpret_cast<const uint32_t *>(host + off_trace);
-    for_room_ranges(prefix[n], [&](uint64_t lo, uint64_t hi) {
-        size_t i = (size_t)(std::upper_bound(prefix.begin(), prefix.end(), lo) - prefix.begin()) - 1u;
-        for (uint64_t x = lo; x < hi; x++) {
-            while (x >= prefix[i + 1u]) i++;
-            const uint32_t t = (uint32_t)(x - prefix[i]);
-            const Segment &sg = b->segs[en.seg_at(i)];
-            const uint32_t *slot = h_trace + 16u * ((size_t)t * n + i);
-            const size_t at = (size_t)en.order[i] * max_turns + t;
-            if (events) pool_decode_event(slot, sg.table, events[at]);
-            if (views) {
-                uint32_t w[12] = {0};
-                for (uint32_t j = 0; j < sg.dev.words; j++) w[j] = slot[4u + j];
-                words_to_view(sg.dev.kind, w, sg.table, (int)sg.dev.n_players, views[at]);
-            }
-        }
-    });
+    run_decode(b, en, max_turns, prefix, reinterpret_cast<const uint32_t *>(host + off_trace), nullptr, events, views, nullptr);
     return GE_OK;
 }
 

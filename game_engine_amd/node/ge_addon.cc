@@ -574,6 +574,67 @@ napi_value RunRooms(napi_env env, napi_callback_info info) {
     return out;
 }
 
+// runRoomsPlayout(batch, rooms: BigUint64Array, keys: BigUint64Array, turns: Uint32Array, masks: Uint32Array, playoutKeys:
+// BigUint64Array, nRollouts, playoutMaxTurns, seed: BigInt, flags, maxTurns, until: GE_RUN_UNTIL_* bits, views: boolean): runRooms's
+// result plus decided: Uint32Array of rooms.length x maxTurns - runRooms with playout seats (ge_batch_run_rooms_playout, POLICY.md
+// §3g); entry k's turn t is at k * maxTurns + t, filled below played[k] (zero above).  Synchronous; GE_BUSY from batch_arg.
+napi_value RunRoomsPlayout(napi_env env, napi_callback_info info) {
+    size_t argc = 13;
+    napi_value argv[13];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
+    if (!b || argc < 13) return throw_status(env, GE_ERR_ARG, "runRoomsPlayout");
+    napi_typedarray_type tt[5];
+    size_t len[5];
+    void *data[5];
+    for (int k = 0; k < 5; k++) {
+        napi_value ab;
+        size_t off;
+        if (napi_get_typedarray_info(env, argv[1 + k], &tt[k], &len[k], &data[k], &ab, &off) != napi_ok)
+            return throw_status(env, GE_ERR_ARG, "runRoomsPlayout", "typed arrays expected");
+    }
+    if (tt[0] != napi_biguint64_array || tt[1] != napi_biguint64_array || tt[2] != napi_uint32_array || tt[3] != napi_uint32_array ||
+        tt[4] != napi_biguint64_array || len[0] != len[1] || len[1] != len[2] || len[2] != len[3] || len[3] != len[4])
+        return throw_status(env, GE_ERR_ARG, "runRoomsPlayout", "BigUint64Array x 2, Uint32Array x 2, BigUint64Array of equal length");
+    uint32_t n_rollouts = 0, pmax = 0, flags = 0, max_turns = 0, until = 0;
+    uint64_t seed = 0;
+    bool lossless = true, want_views = true;
+    if (napi_get_value_uint32(env, argv[6], &n_rollouts) != napi_ok || napi_get_value_uint32(env, argv[7], &pmax) != napi_ok ||
+        napi_get_value_bigint_uint64(env, argv[8], &seed, &lossless) != napi_ok || napi_get_value_uint32(env, argv[9], &flags) != napi_ok ||
+        napi_get_value_uint32(env, argv[10], &max_turns) != napi_ok || napi_get_value_uint32(env, argv[11], &until) != napi_ok ||
+        napi_get_value_bool(env, argv[12], &want_views) != napi_ok)
+        return throw_status(env, GE_ERR_ARG, "runRoomsPlayout",
+                            "nRollouts, playoutMaxTurns (numbers), seed (BigInt), flags, maxTurns, until (numbers), views (boolean) expected");
+    const size_t n = len[0];
+    // the library refuses a call past its caps (after its entry checks): no buffers for it (ArrayBuffers are created zero-filled)
+    const size_t slots = (max_turns <= 4096u && (uint64_t)n * max_turns <= (1ull << 20)) ? n * max_turns : 0;
+    void *pl = nullptr, *sp = nullptr, *dc = nullptr, *ev = nullptr, *vw = nullptr;
+    napi_value pbuf, sbuf, dbuf, ebuf, vbuf, parr, sarr, darr, out;
+    NAPI_OK(napi_create_arraybuffer(env, n * sizeof(uint32_t), &pl, &pbuf));
+    NAPI_OK(napi_create_arraybuffer(env, n * sizeof(uint32_t), &sp, &sbuf));
+    NAPI_OK(napi_create_arraybuffer(env, slots * sizeof(uint32_t), &dc, &dbuf));
+    NAPI_OK(napi_create_arraybuffer(env, slots * sizeof(ge_turn_event), &ev, &ebuf));
+    if (want_views) NAPI_OK(napi_create_arraybuffer(env, slots * sizeof(ge_room_view), &vw, &vbuf));
+    else NAPI_OK(napi_get_null(env, &vbuf));
+    const int st = ge_batch_run_rooms_playout(b, n, static_cast<const uint64_t *>(data[0]), static_cast<const uint64_t *>(data[1]),
+                                              static_cast<const uint32_t *>(data[2]), static_cast<const uint32_t *>(data[3]),
+                                              static_cast<const uint64_t *>(data[4]), n_rollouts, pmax, seed, flags, max_turns, until,
+                                              static_cast<uint32_t *>(pl), static_cast<uint32_t *>(sp), static_cast<uint32_t *>(dc),
+                                              static_cast<ge_turn_event *>(ev), want_views && slots ? static_cast<ge_room_view *>(vw) : nullptr,
+                                              want_views ? slots * sizeof(ge_room_view) : 0);
+    if (st != GE_OK) return throw_status(env, st, "runRoomsPlayout");
+    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, n, pbuf, 0, &parr));
+    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, n, sbuf, 0, &sarr));
+    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, slots, dbuf, 0, &darr));
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_set_named_property(env, out, "played", parr));
+    NAPI_OK(napi_set_named_property(env, out, "stopped", sarr));
+    NAPI_OK(napi_set_named_property(env, out, "decided", darr));
+    NAPI_OK(napi_set_named_property(env, out, "events", ebuf));
+    NAPI_OK(napi_set_named_property(env, out, "views", vbuf));
+    return out;
+}
+
 bool is_nullish(napi_env env, napi_value v) {
     napi_valuetype t;
     return napi_typeof(env, v, &t) == napi_ok && (t == napi_null || t == napi_undefined);
@@ -953,6 +1014,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"stepRooms", nullptr, StepRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"stepRoomsPlayout", nullptr, StepRoomsPlayout, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"runRooms", nullptr, RunRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"runRoomsPlayout", nullptr, RunRoomsPlayout, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"readRoomsAt", nullptr, ReadRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"rollout", nullptr, Rollout, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"writeRoomsAt", nullptr, WriteRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -81,6 +81,13 @@ export class RoomBatch {
   runRooms(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, maxTurns?: number,
            until?: RunUntil[] | RunUntil | number, views?: boolean):
     { played: Uint32Array; stopped: Uint32Array; events: TurnEvent[][]; views: RoomState[][] | null };
+  /** runRooms with playout seats (POLICY.md §3g): stepRoomsPlayout's entries (rooms[k], keys[k], turns[k] + t, masks[k], playoutKeys[k])
+   *  turn after turn, stopped as runRooms stops them, without a host wait between the turns.  decided[k][t]: turn t's decided mask.
+   *  Synchronous; GE_BUSY while an async step() is in flight. */
+  runRoomsPlayout(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, masks: ArrayLike<number>,
+                  playoutKeys: ArrayLike<number | bigint>, nRollouts: number, playoutMaxTurns?: number, seed?: bigint | number,
+                  fullView?: boolean, maxTurns?: number, until?: RunUntil[] | RunUntil | number, views?: boolean):
+    { played: Uint32Array; stopped: Uint32Array; events: TurnEvent[][]; views: RoomState[][] | null; decided: number[][] };
   /** Playouts of each listed room (replica r of entry k = global room keys[k] + r under seed, default the batch's): rooms.length x 77
    *  words of ge_rollout_stats (41 summary words, then seat_alive, seat_wins, seat_score x 12).  The batch is only read. */
   rolloutRooms(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, nRollouts: number,

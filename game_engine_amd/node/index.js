@@ -634,6 +634,33 @@ class RoomBatch {
     }
     return { played: r.played, stopped: r.stopped, events, views: states };
   }
+  /** runRooms with playout seats (twin of the Python RoomBatch.run_rooms_playout, POLICY.md §3g): room k takes stepRoomsPlayout's
+   * entries (rooms[k], keys[k], turns[k] + t, masks[k], playoutKeys[k]; nRollouts, playoutMaxTurns, seed, fullView), t = 0, 1, ...,
+   * and stops as runRooms stops it; between the turns of the call the host does not wait for the device.  Returns { played, stopped,
+   * events, views, decided }: the first four as runRooms returns them, events being stepRoomsPlayout's (the decided seats listed as
+   * acted); decided[k][t] is turn t's decided mask.  All-or-nothing: runRooms's checks, then stepRoomsPlayout's, with the cost cap
+   * per turn and turns[k] + maxTurns - 1 + playoutMaxTurns within 0xFFFFFFFF.  Synchronous; GE_BUSY while an async step() is in
+   * flight. */
+  runRoomsPlayout(rooms, keys, turns, masks, playoutKeys, nRollouts, playoutMaxTurns = 256, seed, fullView = false, maxTurns = 64,
+                  until = ['person', 'end'], views = true) {
+    const bits = runUntilBits(until);
+    const r = addon.runRoomsPlayout(this.handle, BigUint64Array.from(rooms, (x) => BigInt(x)), BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))),
+                                    Uint32Array.from(turns), Uint32Array.from(masks), BigUint64Array.from(playoutKeys, (k) => BigInt.asUintN(64, BigInt(k))),
+                                    nRollouts, playoutMaxTurns, seed === undefined ? this.seed : BigInt.asUintN(64, BigInt(seed)), fullView ? 1 : 0,
+                                    maxTurns, bits, !!views);
+    const events = [], states = views ? [] : null, decided = [];
+    for (let k = 0; k < rooms.length; k++) {
+      const ev = [], vw = [];
+      for (let t = 0; t < r.played[k]; t++) {
+        ev.push(decodeEvent(r.events, (k * maxTurns + t) * EVENT_SIZE));
+        if (views) vw.push(decodeRoom(this.tableOf(Number(rooms[k])), r.views, (k * maxTurns + t) * VIEW.size));
+      }
+      events.push(ev);
+      if (views) states.push(vw);
+      decided.push(Array.from(r.decided.subarray(k * maxTurns, k * maxTurns + r.played[k])));
+    }
+    return { played: r.played, stopped: r.stopped, events, views: states, decided };
+  }
   /** Playouts (twin of the Python RoomBatch.rollout_rooms): entry k is played nRollouts times from room rooms[k] as it stands,
    * replica r as global room keys[k] + r (mod 2^64) under `seed` (default: the batch's) at turns turns[k] .. turns[k] + maxTurns - 1,
    * every seat played by the policy and a finished game left finished.  Returns a BigUint64Array of rooms.length x 77 words

@@ -1,5 +1,5 @@
 // Types for room_pool.js — many game threads hosted in a few resident batches.
-import { AdoptOptions, Advice, AgentStateView, Forecast, PlayoutOptions, RoomPlayer, RunResult, RunUntil, TurnResult } from './room_service';
+import { AdoptOptions, Advice, AgentStateView, Forecast, PlayoutOptions, RoomPlayer, RunOptions, RunResult, RunUntil, TurnResult } from './room_service';
 
 export type MessageResult = TurnResult & { played: boolean; kind: 'chat' | 'control' | 'action' };
 export class RoomPoolService {
@@ -12,9 +12,10 @@ export class RoomPoolService {
   humanAction(threadId: string, playerId: number, choice: number): Promise<AgentStateView>;
   continueRoom(threadId: string, items?: { id: string; type: string }[]): Promise<TurnResult>;
   /** As RoomService.runRoom, from the thread's pool slot. */
-  runRoom(threadId: string, maxTurns?: number, until?: RunUntil[], items?: { id: string; type: string }[]): Promise<RunResult>;
+  runRoom(threadId: string, maxTurns?: number, until?: RunUntil[], items?: { id: string; type: string }[], options?: RunOptions): Promise<RunResult>;
   /** runRoom for many threads, in order: one runRooms call per chunk touched; a thread may be named once.  items[j]: thread j's items. */
-  runRooms(threadIds: string[], maxTurns?: number, until?: RunUntil[], items?: ({ id: string; type: string }[] | undefined)[]): Promise<RunResult[]>;
+  runRooms(threadIds: string[], maxTurns?: number, until?: RunUntil[], items?: ({ id: string; type: string }[] | undefined)[],
+           options?: RunOptions): Promise<RunResult[]>;
   handleMessage(threadId: string, text: string, items?: { id: string; type: string }[]): Promise<MessageResult>;
   /** One tick for many threads (each at most once): per chunk touched one stepRooms and one readRoomsAt; outputs in input order. */
   handleMessages(msgs: [string, string, { id: string; type: string }[]?][]): Promise<MessageResult[]>;

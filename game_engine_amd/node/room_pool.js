@@ -192,24 +192,27 @@ class RoomPoolService {
     });
   }
   /** As RoomService.runRoom (same turns and output), from the thread's pool slot. */
-  runRoom(threadId, maxTurns = 64, until = ['person', 'end'], items) {
-    return this.runRooms([threadId], maxTurns, until, items === undefined || items === null ? undefined : [items]).then((o) => o[0]);
+  runRoom(threadId, maxTurns = 64, until = ['person', 'end'], items, options) {
+    return this.runRooms([threadId], maxTurns, until, items === undefined || items === null ? undefined : [items], options).then((o) => o[0]);
   }
   /** Play many threads on, each until a person is needed in it (RoomService.runRoom's conditions and output, in order): one
    * RoomBatch.runRooms call per chunk touched, every thread under its own key and from its own turn.  items[j]: thread j's canvas
    * items.  A thread named twice, an unknown thread, a thread with playout seats and bad arguments are refused before anything
-   * runs.  Every chunk's call is made before any turn is folded: if one of them fails (a device error), the threads of the chunks
+   * runs.  options { playout: true }: threads with playout seats are run too - a chunk holding one takes one RoomBatch.runRoomsPlayout
+   * call (POLICY.md §3g; mask 0 for its other threads; more calls only where the playouts of one turn would pass the call's cap).
+   * Every chunk's call is made before any turn is folded: if one of them fails (a device error), the threads of the chunks
    * already run have moved on the device while no thread's turn or log has - such a service is to be closed, not continued. */
-  runRooms(threadIds, maxTurns = 64, until = ['person', 'end'], items) {
+  runRooms(threadIds, maxTurns = 64, until = ['person', 'end'], items, options) {
     return this._serial(() => {
       const bits = checkRunArgs(maxTurns, until);
+      const playout = !!(options && options.playout);
       if (new Set(threadIds).size !== threadIds.length) throw new RangeError('runRooms: a thread is named twice');
       const rooms = Array.from(threadIds, (t) => this._room(t));
       const its = items || [];
       if (items && its.length !== rooms.length) throw new RangeError('runRooms: threadIds and items differ in length');
       rooms.forEach((room, j) => {
-        checkRunThread(threadIds[j], room);
-        if (room.turn + maxTurns > 0xFFFFFFFF) throw new RangeError(`thread ${threadIds[j]}: the turn counter would overflow`);
+        checkRunThread(threadIds[j], room, playout);
+        if (room.turn + maxTurns + (room.playoutMask ? this.playoutMaxTurns - 1 : 0) > 0xFFFFFFFF) throw new RangeError(`thread ${threadIds[j]}: the turn counter would overflow`);
       });
       const byChunk = new Map();
       rooms.forEach((room, j) => {
@@ -219,9 +222,17 @@ class RoomPoolService {
       const perCall = Math.max(1, Math.floor((1 << 20) / maxTurns));   // the call's cap on n x maxTurns
       const got = new Array(rooms.length);
       for (const [chunk, all] of byChunk) {
-        for (let lo = 0; lo < all.length; lo += perCall) {
-          const js = all.slice(lo, lo + perCall);
-          const r = chunk.runRooms(js.map((j) => rooms[j].slot), js.map((j) => rooms[j].key), js.map((j) => rooms[j].turn), maxTurns, bits);
+        const withBots = all.some((j) => rooms[j].playoutMask);
+        const parts = [];
+        if (withBots) parts.push(...this._playoutParts(all.map((j) => rooms[j]), perCall));
+        else for (let lo = 0; lo < all.length; lo += perCall) parts.push([lo, Math.min(lo + perCall, all.length)]);
+        for (const [a, b] of parts) {
+          const js = all.slice(a, b);
+          const slots = js.map((j) => rooms[j].slot), keys = js.map((j) => rooms[j].key), turns = js.map((j) => rooms[j].turn);
+          const r = withBots
+            ? chunk.runRoomsPlayout(slots, keys, turns, js.map((j) => rooms[j].playoutMask), keys.map((k) => forecastKey(k)), this.playoutRollouts,
+                                    this.playoutMaxTurns, forecastSeed(this.seed), this.playoutFull, maxTurns, bits)
+            : chunk.runRooms(slots, keys, turns, maxTurns, bits);
           js.forEach((j, k) => { got[j] = { events: r.events[k], views: r.views[k], stopped: r.stopped[k] }; });
         }
       }
@@ -288,16 +299,21 @@ class RoomPoolService {
     }
     return rooms.map((room, j) => this._finish(room, afters[j], events[j], items[j]));
   }
-  /** stepRoomsPlayout of one chunk's rooms under advise's keys and seed, in runs under the call's cap. */
-  _stepPlayout(chunk, rooms) {
+  /** Runs [a, b) of one chunk's rooms whose playouts of one turn stay under the call's cap (and of at most `most` rooms). */
+  _playoutParts(rooms, most) {
     const cost = rooms.map((r) => popcount(r.playoutMask) * playoutMaxCands(r.table.info.pack, r.pool.nPlayers) * this.playoutRollouts);
     const parts = [];
     let lo = 0, acc = 0;
     cost.forEach((c, k) => {
-      if (acc + c > PLAYOUT_CAP && k > lo) { parts.push([lo, k]); lo = k; acc = 0; }
+      if ((acc + c > PLAYOUT_CAP || (most !== undefined && k - lo >= most)) && k > lo) { parts.push([lo, k]); lo = k; acc = 0; }
       acc += c;
     });
     parts.push([lo, rooms.length]);
+    return parts;
+  }
+  /** stepRoomsPlayout of one chunk's rooms under advise's keys and seed, in runs under the call's cap. */
+  _stepPlayout(chunk, rooms) {
+    const parts = this._playoutParts(rooms);
     const out = [];
     for (const [a, b] of parts) {
       const rs = rooms.slice(a, b);

@@ -22,6 +22,9 @@ export interface PlayoutOptions { playoutRollouts?: number; playoutMaxTurns?: nu
 export interface TurnResult { state: AgentStateView; toolCalls: ToolCall[]; uiCalls: FrontendToolCall[]; }
 /** runRoom: one TurnResult per played turn; stopped: the conditions that held after the last one ([]: the limit). */
 export type RunUntil = 'person' | 'end' | 'phase';
+/** runRoom / runRooms options.  playout: run threads with playout seats too, by one runRoomsPlayout call (POLICY.md §3g); without
+ *  it such a thread is refused. */
+export interface RunOptions { playout?: boolean; }
 export interface RunResult { turns: TurnResult[]; played: number; stopped: RunUntil[]; }
 /** How a thread ends from where it stands, over `rollouts` playouts (JSON integers: divide by rollouts for odds). */
 export interface Forecast {
@@ -66,7 +69,7 @@ export class RoomService {
   continueRoom(threadId: string, items?: { id: string; type: string }[]): Promise<TurnResult>;
   /** The thread played on until a person is needed (POLICY.md §3f): turns[t] is what continueRoom would have resolved for that turn.
    *  Rejects with a RangeError, before anything runs, for a thread with playout seats, maxTurns outside 1 .. 4096 or an unknown condition. */
-  runRoom(threadId: string, maxTurns?: number, until?: RunUntil[], items?: { id: string; type: string }[]): Promise<RunResult>;
+  runRoom(threadId: string, maxTurns?: number, until?: RunUntil[], items?: { id: string; type: string }[], options?: RunOptions): Promise<RunResult>;
   /** nRollouts playouts (<= 65 536) of the thread's room, every seat played by the policy, keyed (threadKey << 16) + r under seed
    *  (service seed ^ 0x9E3779B97F4A7C15); the thread is not changed (INTEGRATION.md "Forecasting a thread").  seat: from what that
    *  seat knows (hidden roles / the lie dealt again per replica); the JSON gains "seat". */

@@ -216,8 +216,10 @@ function checkRunArgs(maxTurns, until) {
   if (!Number.isInteger(maxTurns) || maxTurns < 1 || maxTurns > RUN_MAX_TURNS) throw new RangeError(`maxTurns must be 1 .. ${RUN_MAX_TURNS}`);
   return runUntilBits(until);
 }
-function checkRunThread(threadId, room) {
-  if (room.playoutMask) throw new RangeError(`thread ${threadId} has playout seats: runRoom does not run playout bots, use continueRoom`);
+function checkRunThread(threadId, room, playout) {
+  if (room.playoutMask && !playout) {
+    throw new RangeError(`thread ${threadId} has playout seats: runRoom does not run playout bots, use continueRoom (or run it with { playout: true })`);
+  }
 }
 /** One turn's output as runRoom keeps it: the state of a continueRoom output shares the thread's growing log (playerActions,
  * phase_history, game_notes), and here later turns are folded before the caller sees the earlier ones - so those three are copied. */
@@ -366,15 +368,19 @@ class RoomService {
    * [{ state, toolCalls, uiCalls }, ...], played, stopped }: element t is exactly what continueRoom would have resolved for that
    * turn (items goes to every turn's UI builder as given), stopped names the conditions that held after the last turn ([]: the
    * limit), and the thread's turn and panel end where `played` calls of continueRoom would have left them.  A thread with playout
-   * seats or bad arguments are refused (RangeError) before anything runs.  Every turn's state carries its own copy of the thread's
-   * log (runTurn): host work that grows with the log, per turn. */
-  runRoom(threadId, maxTurns = 64, until = ['person', 'end'], items) {
+   * seats or bad arguments are refused (RangeError) before anything runs; with options { playout: true } a thread with playout seats
+   * is run by one RoomBatch.runRoomsPlayout call (POLICY.md §3g) under the keys, seed and options continueRoom gives its playout
+   * bots.  Every turn's state carries its own copy of the thread's log (runTurn): host work that grows with the log, per turn. */
+  runRoom(threadId, maxTurns = 64, until = ['person', 'end'], items, options) {
     const room = this.rooms.get(threadId);
     if (!room) return Promise.reject(new Error(`unknown thread ${threadId}`));
     return this._serial(room, () => {
       const bits = checkRunArgs(maxTurns, until);
-      checkRunThread(threadId, room);
-      const r = room.batch.runRooms([0], [room.key], [room.turn], maxTurns, bits);
+      checkRunThread(threadId, room, !!(options && options.playout));
+      const r = room.playoutMask
+        ? room.batch.runRoomsPlayout([0], [room.key], [room.turn], [room.playoutMask], [forecastKey(room.key)], this.playoutRollouts,
+                                     this.playoutMaxTurns, forecastSeed(this.seed), this.playoutFull, maxTurns, bits)
+        : room.batch.runRooms([0], [room.key], [room.turn], maxTurns, bits);
       room.turn += r.played[0];
       room.batch.setTurn(room.turn);
       return runOutput(r.events[0].map((ev, t) => runTurn(this._finish(room, r.views[0][t], ev, items))), r.stopped[0]);
@@ -452,7 +458,7 @@ class RoomService {
           let out;
           if (req.method === 'POST' && req.url === '/rooms') out = this.createRoom(msg);
           else if (req.method === 'POST' && req.url === '/continue') out = await this.continueRoom(msg.threadId, msg.items);
-          else if (req.method === 'POST' && req.url === '/run') out = await this.runRoom(msg.threadId, msg.maxTurns, msg.until, msg.items);
+          else if (req.method === 'POST' && req.url === '/run') out = await this.runRoom(msg.threadId, msg.maxTurns, msg.until, msg.items, { playout: !!msg.playout });
           else if (req.method === 'POST' && req.url === '/message') out = await this.handleMessage(msg.threadId, msg.text, msg.items);
           else if (req.method === 'POST' && req.url === '/action') out = await this.humanAction(msg.threadId, msg.playerId, msg.choice);
           else if (req.method === 'POST' && req.url === '/close') out = { closed: await this.close(msg.threadId) };

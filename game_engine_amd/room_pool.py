@@ -252,16 +252,19 @@ class RoomPoolService:
         return [self._finish(room, afters[j], events[j], items[j]) for j, room in enumerate(rooms)]
 
     def run_room(self, thread_id: str, max_turns: int = 64, until=("person", "end"),
-                 items: Optional[List[Dict[str, Any]]] = None) -> Dict[str, Any]:
+                 items: Optional[List[Dict[str, Any]]] = None, playout: bool = False) -> Dict[str, Any]:
         """As RoomService.run_room (same turns and output), from the thread's pool slot."""
-        return self.run_rooms([thread_id], max_turns, until, None if items is None else [items])[0]
+        return self.run_rooms([thread_id], max_turns, until, None if items is None else [items], playout)[0]
 
     def run_rooms(self, thread_ids: Sequence[str], max_turns: int = 64, until=("person", "end"),
-                  items: Optional[Sequence[Optional[List[Dict[str, Any]]]]] = None) -> List[Dict[str, Any]]:
+                  items: Optional[Sequence[Optional[List[Dict[str, Any]]]]] = None, playout: bool = False) -> List[Dict[str, Any]]:
         """Play many threads on, each until a person is needed in it (RoomService.run_room's conditions and output, in order):
         one RoomBatch.run_rooms call per chunk touched, every thread under its own key and from its own turn.  items[j]: thread
         j's canvas items.  A thread may be named once (ValueError); unknown threads (KeyError), threads with playout seats and
-        bad arguments (ValueError) are refused before anything runs.  Every chunk's call is made before any turn is folded: if
+        bad arguments (ValueError) are refused before anything runs.  playout=True: threads with playout seats are run too - a
+        chunk holding one takes one RoomBatch.run_rooms_playout call (POLICY.md §3g; mask 0 for its other threads; more calls
+        only where the playouts of one turn would pass the call's cap), under the keys, seed and options continue_room gives
+        its playout bots.  Every chunk's call is made before any turn is folded: if
         one of them raises (a device error), the threads of the chunks already run have moved on the device while no thread's
         turn or log has - such a service is to be closed, not continued."""
         bits = check_run_args(max_turns, until)
@@ -272,8 +275,8 @@ class RoomPoolService:
         if len(its) != len(rooms):
             raise ValueError("run_rooms: thread_ids and items differ in length")
         for tid, room in zip(thread_ids, rooms):
-            check_run_thread(tid, room)
-            if int(room["turn"]) + int(max_turns) > 0xFFFFFFFF:
+            check_run_thread(tid, room, playout)
+            if int(room["turn"]) + int(max_turns) + (self.playout_max_turns - 1 if room["playout_mask"] else 0) > 0xFFFFFFFF:
                 raise ValueError(f"thread {tid!r}: the turn counter would overflow")
         by_chunk: Dict[int, List[int]] = {}
         for j, room in enumerate(rooms):
@@ -281,10 +284,19 @@ class RoomPoolService:
         per_call = max(1, (1 << 20) // int(max_turns))             # the call's cap on n x max_turns
         got: List[Any] = [None] * len(rooms)
         for all_js in by_chunk.values():
-            for lo in range(0, len(all_js), per_call):
-                js = all_js[lo:lo + per_call]
-                played, stopped, events, views = rooms[js[0]]["chunk"].run_rooms(
-                    [rooms[j]["slot"] for j in js], [rooms[j]["key"] for j in js], [rooms[j]["turn"] for j in js], max_turns, bits)
+            with_bots = any(rooms[j]["playout_mask"] for j in all_js)
+            parts = self._playout_parts([rooms[j] for j in all_js], per_call) if with_bots else \
+                [(lo, min(lo + per_call, len(all_js))) for lo in range(0, len(all_js), per_call)]
+            for a, b in parts:
+                js = all_js[a:b]
+                chunk, slots, keys = rooms[js[0]]["chunk"], [rooms[j]["slot"] for j in js], [rooms[j]["key"] for j in js]
+                turns = [rooms[j]["turn"] for j in js]
+                if with_bots:
+                    played, stopped, events, views, _ = chunk.run_rooms_playout(
+                        slots, keys, turns, [rooms[j]["playout_mask"] for j in js], [forecast_key(k) for k in keys], self.playout_rollouts,
+                        self.playout_max_turns, seed=forecast_seed(self.seed), full_view=self.playout_full, max_turns=max_turns, until=bits)
+                else:
+                    played, stopped, events, views = chunk.run_rooms(slots, keys, turns, max_turns, bits)
                 for k, j in enumerate(js):
                     got[j] = (int(played[k]), int(stopped[k]), events[k], views[k])
         out = []
@@ -293,18 +305,23 @@ class RoomPoolService:
             out.append(run_output([run_turn(self._finish(room, views[t], events[t], it)) for t in range(played)], stopped))
         return out
 
+    def _playout_parts(self, rooms: List[Dict[str, Any]], most: Optional[int] = None) -> List[Tuple[int, int]]:
+        """Runs [a, b) of one chunk's rooms whose playouts of one turn stay under the call's cap (and of at most `most` rooms)."""
+        cost = [bin(int(r["playout_mask"])).count("1") * playout_max_cands(r["table"].pack, r["pool"].n_players) * self.playout_rollouts
+                for r in rooms]
+        parts, lo, acc = [], 0, 0
+        for k, c in enumerate(cost):
+            if (acc + c > PLAYOUT_CAP or (most is not None and k - lo >= most)) and k > lo:
+                parts.append((lo, k)); lo, acc = k, 0
+            acc += c
+        parts.append((lo, len(rooms)))
+        return parts
+
     def _step_playout(self, chunk, rooms: List[Dict[str, Any]], slots, keys, turns) -> np.ndarray:
         """step_rooms_playout of one chunk's rooms under advise's keys and seed, in runs under the call's cap."""
         masks = np.array([r["playout_mask"] for r in rooms], dtype=np.uint32)
         pkeys = np.array([forecast_key(r["key"]) for r in rooms], dtype=np.uint64)
-        cost = [bin(int(m)).count("1") * playout_max_cands(r["table"].pack, r["pool"].n_players) * self.playout_rollouts
-                for m, r in zip(masks, rooms)]
-        parts, lo, acc = [], 0, 0
-        for k, c in enumerate(cost):
-            if acc + c > PLAYOUT_CAP and k > lo:
-                parts.append((lo, k)); lo, acc = k, 0
-            acc += c
-        parts.append((lo, len(rooms)))
+        parts = self._playout_parts(rooms)
         evs = [chunk.step_rooms_playout(slots[a:b], keys[a:b], turns[a:b], masks[a:b], pkeys[a:b], self.playout_rollouts,
                                         self.playout_max_turns, seed=forecast_seed(self.seed), full_view=self.playout_full)[0]
                for a, b in parts]

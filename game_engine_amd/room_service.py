@@ -288,9 +288,10 @@ def check_run_args(max_turns: int, until) -> int:
     return run_until_bits(until)
 
 
-def check_run_thread(thread_id: str, room: Dict[str, Any]) -> None:
-    if room["playout_mask"]:
-        raise ValueError(f"thread {thread_id!r} has playout seats: run_room does not run playout bots, use continue_room")
+def check_run_thread(thread_id: str, room: Dict[str, Any], playout: bool = False) -> None:
+    if room["playout_mask"] and not playout:
+        raise ValueError(f"thread {thread_id!r} has playout seats: run_room does not run playout bots, use continue_room "
+                         "(or run it with playout=True)")
 
 
 def run_turn(out: Dict[str, Any]) -> Dict[str, Any]:
@@ -458,20 +459,26 @@ class RoomService:
         return {"state": state, "toolCalls": calls, "uiCalls": ui}
 
     def run_room(self, thread_id: str, max_turns: int = 64, until=("person", "end"),
-                 items: Optional[List[Dict[str, Any]]] = None) -> Dict[str, Any]:
+                 items: Optional[List[Dict[str, Any]]] = None, playout: bool = False) -> Dict[str, Any]:
         """Play the thread on until a person is needed: one RoomBatch.run_rooms call (POLICY.md §3f) instead of a continue_room
         per turn.  until: "person" (a human seat of the thread has an action to give), "end" (the game is over), "phase" (the
         turn moved the phase); the first turn is always played, at most max_turns are.  Returns {"turns": [{state, toolCalls,
         uiCalls}, ...], "played": p, "stopped": [...]}: element t is exactly what continue_room would have returned for that
         turn (items goes to every turn's UI builder as given), "stopped" names the conditions that held after the last turn
         ([]: the limit), and the thread's turn and panel end where p calls of continue_room would have left them.  A thread
-        with playout seats is refused (ValueError) before anything runs.  Every turn's state carries its own copy of the thread's
-        log (run_turn): host work that grows with the log, per turn."""
+        with playout seats is refused (ValueError) before anything runs, unless playout=True: then it is run by one
+        RoomBatch.run_rooms_playout call (POLICY.md §3g) with the keys, seed and options continue_room gives its playout bots.
+        Every turn's state carries its own copy of the thread's log (run_turn): host work that grows with the log, per turn."""
         room = self._rooms[thread_id]
         bits = check_run_args(max_turns, until)
-        check_run_thread(thread_id, room)
+        check_run_thread(thread_id, room, playout)
         batch, turn = room["batch"], room["batch"].turn
-        played, stopped, events, views = batch.run_rooms([0], [room["key"]], [turn], max_turns, bits)
+        if room["playout_mask"]:
+            played, stopped, events, views, _ = batch.run_rooms_playout(
+                [0], [room["key"]], [turn], [room["playout_mask"]], [forecast_key(room["key"])], self.playout_rollouts, self.playout_max_turns,
+                seed=forecast_seed(self.seed), full_view=self.playout_full, max_turns=max_turns, until=bits)
+        else:
+            played, stopped, events, views = batch.run_rooms([0], [room["key"]], [turn], max_turns, bits)
         batch.set_turn(turn + int(played[0]))
         return run_output([run_turn(self._finish(room, views[0, t], events[0, t], items)) for t in range(int(played[0]))], int(stopped[0]))
 

@@ -367,6 +367,41 @@ class RoomBatch:
                                             out.ctypes.data if views else None, out.nbytes if views else 0), "ge_batch_run_rooms")
         return played, stopped, events, out
 
+    def run_rooms_playout(self, rooms, keys, turns, masks, playout_keys, n_rollouts: int, playout_max_turns: int = 256,
+                          seed: Optional[int] = None, full_view: bool = False, max_turns: int = 64, until=("person", "end"),
+                          views: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray], np.ndarray]:
+        """run_rooms with playout seats (POLICY.md §3g): room k takes step_rooms_playout's entries (rooms[k], keys[k], turns[k] + t,
+        masks[k], playout_keys[k]; n_rollouts, playout_max_turns, seed, full_view), t = 0, 1, ..., and stops as run_rooms stops it.
+        Between the turns of the call the host does not wait for the device.  Returns (played, stopped, events, views, decided):
+        the first four as run_rooms returns them, events being step_rooms_playout's (the decided seats listed as acted);
+        decided has shape (n, max_turns) and holds, below played[k], each turn's decided mask.  All-or-nothing: run_rooms's checks,
+        then step_rooms_playout's, with the cost cap per turn and turns[k] + max_turns - 1 + playout_max_turns within 0xFFFFFFFF."""
+        rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        turns = np.ascontiguousarray(turns, dtype=np.uint32)
+        masks = np.ascontiguousarray(masks, dtype=np.uint32)
+        pkeys = np.ascontiguousarray(playout_keys, dtype=np.uint64)
+        if not (len(rooms) == len(keys) == len(turns) == len(masks) == len(pkeys)):
+            raise GeError(-1, "run_rooms_playout: arrays differ in length")
+        bits = run_until_bits(until)
+        if int(max_turns) < 0 or int(max_turns) > 0xFFFFFFFF:   # no uint32 at all (0 and values above the cap go to the library's checks)
+            raise GeError(GE_ERR_ARG, "run_rooms_playout: max_turns")
+        n, cap = len(rooms), int(max_turns)
+        if n * cap > 1 << 20 or cap > 4096:                      # the library refuses these (after its entry checks): no arrays for them
+            cap = 0
+        played = np.zeros(n, dtype=np.uint32)
+        stopped = np.zeros(n, dtype=np.uint32)
+        decided = np.zeros((n, cap), dtype=np.uint32)
+        events = np.zeros((n, cap), dtype=EVENT_DTYPE)
+        out = np.zeros((n, cap), dtype=ROOM_VIEW_DTYPE) if views else None
+        flags = 1 if full_view else 0                            # GE_PLAYOUT_FULL_VIEW
+        _check(self._lib.ge_batch_run_rooms_playout(self._h, n, rooms.ctypes.data, keys.ctypes.data, turns.ctypes.data, masks.ctypes.data,
+                                                    pkeys.ctypes.data, n_rollouts, playout_max_turns, self._seed if seed is None else seed,
+                                                    flags, max_turns, bits, played.ctypes.data, stopped.ctypes.data, decided.ctypes.data,
+                                                    events.ctypes.data, out.ctypes.data if views else None, out.nbytes if views else 0),
+               "ge_batch_run_rooms_playout")
+        return played, stopped, events, out, decided
+
     def read_rooms_at(self, rooms) -> np.ndarray:
         """Canonical views of the listed rooms, out[k] = room rooms[k] (any order, repeats allowed)."""
         rooms = np.ascontiguousarray(rooms, dtype=np.uint64)

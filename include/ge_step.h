@@ -45,7 +45,8 @@ extern "C" {
  *      ge_batch_rollout_seats (the same playouts from what one seat knows: hidden roles / the lie dealt again per replica);
  *      ge_batch_step_rooms_playout + GE_PLAYOUT_FULL_VIEW (playout seats: bots that choose each action by their own playouts);
  *      ge_batch_rollout_compare + ge_compare_stats (an entry against a baseline entry, playout by playout: the paired counts);
- *      ge_batch_run_rooms + GE_RUN_UNTIL_* (listed rooms played on until a person is needed: many turns per call, every turn traced) */
+ *      ge_batch_run_rooms + GE_RUN_UNTIL_* (listed rooms played on until a person is needed: many turns per call, every turn traced);
+ *      ge_batch_run_rooms_playout (the same with playout seats: the playouts of every turn enqueued without the host in between) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -454,6 +455,35 @@ int ge_batch_run_rooms(ge_batch *b, uint64_t n, const uint64_t *rooms, const uin
                        uint32_t *played /* n */, uint32_t *stopped /* n, may be NULL */,
                        ge_turn_event *events /* n * max_turns, may be NULL */,
                        ge_room_view *views /* n * max_turns, may be NULL */, size_t views_cap_bytes);
+
+/* Listed rooms with playout seats played on until a person is needed (POLICY.md §3g): ge_batch_run_rooms_playout is to
+ * ge_batch_step_rooms_playout what ge_batch_run_rooms is to ge_batch_step_rooms.  Room k is stepped by ge_batch_step_rooms_playout's
+ * entries (rooms[k], keys[k], turns[k] + t, playout_masks[k], playout_keys[k]; the call's n_rollouts, playout_max_turns, seed and
+ * flags) for t = 0, 1, ...; the first turn is always played, after each played turn `until` is tested as ge_batch_run_rooms tests it,
+ * and the room stops after the first turn for which a named condition holds, or after max_turns turns.  played / stopped as
+ * ge_batch_run_rooms; for t < played[k], events[k * max_turns + t] is that turn's ge_batch_step_rooms_playout event (the decided
+ * seats listed as acted), views[k * max_turns + t] the ge_batch_read_rooms_at view after it and decided[k * max_turns + t] its
+ * decided mask; slots at t >= played[k] are untouched.  The stored record is the one after the last played turn, without a prepared
+ * deal; unlisted rooms, the turn counter and the GE_FLAG_TRACE buffer are untouched.  So all masks 0, or playout_max_turns = 0, is
+ * ge_batch_run_rooms word for word (the latter with decisions made: a full tie is the policy's own choice), and max_turns = 1 is
+ * ge_batch_step_rooms_playout followed by ge_batch_read_rooms_at.
+ * All-or-nothing, nothing runs on an error, in this order: with n > 0 ge_batch_run_rooms's checks in its order (ge_batch_step_rooms's,
+ * played, max_turns, n * max_turns <= 2^20, `until`, the views' capacity, turns[k] + max_turns <= 0xFFFFFFFF); then
+ * ge_batch_step_rooms_playout's playout checks in its order, where the turn range (GE_ERR_RANGE) is turns[k] + (max_turns - 1) +
+ * playout_max_turns <= 0xFFFFFFFF - the last turn's playouts must fit - and the cost cap sum_k popcount(mask_k) * c_k * n_rollouts <=
+ * 2^26 is per turn, because only one turn's playouts exist at a time; then n == 0: GE_OK.
+ * Between the turns of a call the host does not wait for the device: per turn the plan, the playouts (their number read from device
+ * memory), the decision and the turn are enqueued for the rooms still live, in groups of turns with one 4-byte read of the live
+ * count between groups; only the rows of the turns enqueued cross to the host.  With ge_batch_set_timing on, ge_batch_kernel_time
+ * includes the call's launches.  Ordered behind the previous step; synchronises. */
+int ge_batch_run_rooms_playout(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
+                               const uint32_t *playout_masks /* n: bit i = seat i+1 */, const uint64_t *playout_keys /* n */,
+                               uint32_t n_rollouts, uint32_t playout_max_turns, uint64_t seed, uint32_t flags /* GE_PLAYOUT_FULL_VIEW */,
+                               uint32_t max_turns, uint32_t until,
+                               uint32_t *played /* n */, uint32_t *stopped /* n, may be NULL */,
+                               uint32_t *decided /* n * max_turns, may be NULL */,
+                               ge_turn_event *events /* n * max_turns, may be NULL */,
+                               ge_room_view *views /* n * max_turns, may be NULL */, size_t views_cap_bytes);
 
 /* GE_FLAG_TRACE: events of the most recent ge_batch_step call, dst[(room - first) * *n_turns + t].
  * cap_bytes >= count * n_turns * sizeof(ge_turn_event).  Synchronises. */

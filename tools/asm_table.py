@@ -46,6 +46,12 @@ def describe(mangled: str) -> dict:
     m = re.search(r"ge_playout_(plan|decide)ILi(\d)E", mangled)
     if m:
         return {"kernel": "ge_playout_" + m.group(1), "layout": KINDS[int(m.group(2))], "lowocc": False, "generic": False, "single": True}
+    m = re.search(r"ge_runp_(rollout|turn)ILi(\d)ELi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_runp_" + m.group(1), "layout": KINDS[int(m.group(2))], "lowocc": True, "generic": int(m.group(3)), "single": True}
+    m = re.search(r"ge_runp_planILi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_runp_plan", "layout": KINDS[int(m.group(1))], "lowocc": False, "generic": False, "single": True}
     m = re.search(r"N_1\d+(ge_[a-z_0-9]+?)E", mangled)
     return {"kernel": m.group(1) if m else mangled, "layout": "-", "lowocc": False, "generic": False, "single": False}
 
@@ -86,6 +92,9 @@ def label(r):
         return f"{r['layout']}, playouts (ge_batch_rollout_rooms)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] in ("ge_playout_plan", "ge_playout_decide"):  # ge_batch_step_rooms_playout: one launch per unit of rooms
         return f"{r['layout']}, playout seats, {r['kernel'][11:]} (ge_batch_step_rooms_playout)"
+    if r["kernel"] in ("ge_runp_plan", "ge_runp_rollout", "ge_runp_turn"):   # ge_batch_run_rooms_playout: enqueued per turn
+        what = {"ge_runp_plan": "plan of the live rooms", "ge_runp_rollout": "playouts counted on the device", "ge_runp_turn": "turn of the live rooms"}[r["kernel"]]
+        return f"{r['layout']}, run-on with playout seats, {what} (ge_batch_run_rooms_playout)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_compare_kernel":                       # ge_batch_rollout_compare: one launch per chunk, behind the playouts
         return "ge_compare_kernel (ge_batch_rollout_compare: an entry against its baseline)"
     if r["kernel"] not in ("ge_step_kernel", "ge_step_kernel_mixed"):
