@@ -20,6 +20,11 @@
 //      skips them; the host ORs them into the turn's events.
 // A room's entries depend only on its own record, keys and turn, never on where the atomic counter put them, so the result is
 // deterministic.
+//
+// Under GE_PLAYOUT_HALVING (POLICY.md §3h) step 2 becomes rounds: each entry carries a replica range (8 bytes), the plan writes
+// round 0's, ge_rollout_kernel<.., ACT = 4> plays the ranges into accumulators that are zeroed once and add up across the rounds,
+// and between two rounds ge_playout_halve cuts each seat's entries to the better half and hands the survivors their next range.
+// Steps 1, 3 and 4 are the same code; without the flag the launches are the ones above.
 
 namespace {
 
@@ -41,6 +46,19 @@ struct DecideArgs {
     const unsigned long long *acc;          // the pass's accumulators, ROLL_STRIDE words per entry
     u32x4 *out;                             // per listed room: decided mask, choice nibbles (low, high)
     uint32_t n, seg, seed_key;
+};
+
+// ---- sequential halving (POLICY.md §3h): rounds of a seat with c >= 2 candidates, and the replica offset o_j of n playouts
+__host__ __device__ inline uint32_t halving_rounds(uint32_t c) { return 32u - (uint32_t)__builtin_clz(c - 1u); }
+__host__ __device__ inline uint32_t halving_offset(uint32_t n, uint32_t R, uint32_t j) { return n * ((1u << j) - 1u) / ((1u << R) - 1u); }   // n <= 2^20, factor <= 15
+
+// what the ranged plan and ge_playout_halve add to a pass: the entries' replica ranges
+struct HalveArgs {
+    const uint32_t *room_first, *room_cnt;  // this unit's listed rooms: their entries of the pass
+    const uint32_t *e_players;
+    const unsigned long long *acc;
+    u32x2 *e_range;                         // per entry [lo, hi) of the coming round; lo > hi: eliminated
+    uint32_t n, n_rollouts, round;          // round: the one that has just been played
 };
 
 // the policy's candidate set of seat i (0-based) in a Werewolf phase of action kind `act` (POLICY.md §3 table; ww_choose's)
@@ -98,8 +116,10 @@ __device__ __forceinline__ uint32_t playout_deciders(const typename G::S &s, con
     return dec;
 }
 
-template <int NB, bool WWP>
-__device__ __forceinline__ void playout_plan_room(const SegDev &sg, const DevTable *__restrict__ tables, const PlanArgs &a, uint32_t k) {
+// HALVE: each entry also gets round 0's replica range [0, o_1) of its seat's candidate count (§3h)
+template <int NB, bool WWP, bool HALVE = false>
+__device__ __forceinline__ void playout_plan_room(const SegDev &sg, const DevTable *__restrict__ tables, const PlanArgs &a, uint32_t k,
+                                                  u32x2 *e_range = nullptr, uint32_t n_rollouts = 0u) {
     using G = PlayoutGame<NB, WWP>;
     using L = typename G::L;
     const uint64_t room = a.rooms[k];
@@ -119,7 +139,10 @@ __device__ __forceinline__ void playout_plan_room(const SegDev &sg, const DevTab
     a.room_cnt[k] = cnt;
     for (uint32_t m = dec; m; m &= m - 1u) {
         const uint32_t i = ctz(m);
+        u32x2 rg; rg.x = 0u; rg.y = 0u;
+        if constexpr (HALVE) rg.y = halving_offset(n_rollouts, halving_rounds(popc(G::cand(s, act, i))), 1u);
         for (uint32_t c = G::cand(s, act, i); c; c &= c - 1u, first++) {
+            if constexpr (HALVE) e_range[first] = rg;
             a.e_rooms[first] = room; a.e_keys[first] = a.pkeys[k]; a.e_turns[first] = turn;
             a.e_seats[first] = a.full_view ? 0u : i + 1u;
             a.e_first[first] = first; a.e_first[first + 1u] = first + 1u;
@@ -135,6 +158,53 @@ __global__ void __launch_bounds__(64) ge_playout_plan(const SegDev *__restrict__
     if (k >= a.n) return;
     const SegDev &sg = segs[a.seg];
     playout_plan_room<KindOf<KIND>::NB, KindOf<KIND>::WW>(sg, tables, a, k);
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(64) ge_playout_plan_ranged(const SegDev *__restrict__ segs, const DevTable *__restrict__ tables, const PlanArgs a,
+                                                             u32x2 *e_range, uint32_t n_rollouts) {
+    const uint32_t k = blockIdx.x * 64u + threadIdx.x;
+    if (k >= a.n) return;
+    const SegDev &sg = segs[a.seg];
+    playout_plan_room<KindOf<KIND>::NB, KindOf<KIND>::WW, true>(sg, tables, a, k, e_range, n_rollouts);
+}
+
+// Between two rounds of §3h: one lane per listed room, whatever its game - only entry arrays and accumulators are read.  Per seat
+// (its entries are consecutive, as playout_choose walks them) with c candidates and R rounds: when round + 1 < R, a live entry
+// survives iff fewer than k = ceil(c / 2^(round + 1)) live entries of the seat have a strictly larger V (ties at the cut all
+// stay), and the survivors get the next round's range; a seat whose rounds are done gets the empty range [n, n).  An eliminated
+// entry gets (0xFFFFFFFF, 0): lo > hi, which no live entry has, even when its round is empty (lo == hi).
+__global__ void __launch_bounds__(64) ge_playout_halve(const HalveArgs a) {
+    const uint32_t k = blockIdx.x * 64u + threadIdx.x;
+    if (k >= a.n) return;
+    const uint32_t lo = a.room_first[k], hi = lo + a.room_cnt[k];
+    for (uint32_t f = lo; f < hi;) {
+        const uint32_t seat = a.e_players[f];
+        uint32_t g = f + 1u;
+        while (g < hi && a.e_players[g] == seat) g++;
+        const uint32_t c = g - f, R = halving_rounds(c), j1 = a.round + 1u;   // c <= 12 entries [f, g) of this seat
+        const bool cut = j1 < R;
+        const uint32_t keep = cut ? (c + (1u << j1) - 1u) >> j1 : c;
+        u32x2 next, out;
+        next.x = cut ? halving_offset(a.n_rollouts, R, j1) : a.n_rollouts;
+        next.y = cut ? halving_offset(a.n_rollouts, R, j1 + 1u) : a.n_rollouts;
+        out.x = 0xFFFFFFFFu; out.y = 0u;
+        uint32_t live = 0, stay = 0;                           // bit x - f
+        for (uint32_t x = f; x < g; x++) {
+            const u32x2 r = a.e_range[x];
+            live |= (r.x <= r.y ? 1u : 0u) << (x - f);
+        }
+        for (uint32_t x = f; x < g; x++) {
+            const unsigned long long v = a.acc[(size_t)x * ROLL_STRIDE + 51u + (seat - 1u)];
+            uint32_t above = 0;
+            for (uint32_t y = f; y < g; y++)
+                above += ((live >> (y - f)) & 1u) && a.acc[(size_t)y * ROLL_STRIDE + 51u + (seat - 1u)] > v ? 1u : 0u;
+            stay |= (above < keep ? 1u : 0u) << (x - f);
+        }
+        stay &= live;
+        for (uint32_t x = f; x < g; x++) a.e_range[x] = ((stay >> (x - f)) & 1u) ? next : out;
+        f = g;
+    }
 }
 
 // per deciding seat of room k: argmax of seat_wins with the pick(d, m) tie-break, logged in `s` by `inject`
@@ -195,8 +265,27 @@ __global__ void __launch_bounds__(64) ge_playout_decide(const SegDev *__restrict
 // (a Two-Truths segment may have 2 players).  The entry space and the cost cap reserve this per playout seat.
 uint32_t playout_max_cands(const SegDev &d) { return (d.kind == K_WW8 || d.kind == K_WW12) ? d.n_players : std::max(d.n_players, 3u); }
 
+// §3h on the host: the rounds a segment's seats can need, and the wavefronts per entry of round j - the longest range any seat of
+// 2 .. max_cands candidates has in that round (0: no seat plays anything in it)
+uint32_t halving_max_rounds(const SegDev &d) { return halving_rounds(std::max(playout_max_cands(d), 2u)); }
+uint32_t halving_waves(uint32_t n_rollouts, uint32_t max_cands, uint32_t j) {
+    uint32_t longest = 0;
+    for (uint32_t c = 2; c <= max_cands; c++) {
+        const uint32_t R = halving_rounds(c);
+        if (j < R) longest = std::max(longest, halving_offset(n_rollouts, R, j + 1u) - halving_offset(n_rollouts, R, j));
+    }
+    return (longest + 63u) / 64u;
+}
+
 hipError_t playout_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const PlanArgs &a) {
     return by_kind(kind, [&](auto K) { hipLaunchKernelGGL((ge_playout_plan<K()>), grid, dim3(64), 0, st, b->segs_dev, b->tables, a); });
+}
+hipError_t playout_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const PlanArgs &a, u32x2 *e_range, uint32_t n_rollouts) {
+    return by_kind(kind, [&](auto K) { hipLaunchKernelGGL((ge_playout_plan_ranged<K()>), grid, dim3(64), 0, st, b->segs_dev, b->tables, a, e_range, n_rollouts); });
+}
+hipError_t playout_launch(dim3 grid, hipStream_t st, const HalveArgs &a) {
+    hipLaunchKernelGGL(ge_playout_halve, grid, dim3(64), 0, st, a);
+    return hipGetLastError();
 }
 hipError_t playout_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const DecideArgs &a) {
     return by_kind(kind, [&](auto K) { hipLaunchKernelGGL((ge_playout_decide<K()>), grid, dim3(64), 0, st, b->segs_dev, b->tables, a); });
@@ -267,7 +356,9 @@ static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
     o.choices = up16(o.players + 4 * C);
     o.status = up16(o.choices + 4 * C);
     o.acc = up16(o.status + 4 * C);
-    o.total = o.acc + 8 * (size_t)ROLL_STRIDE * C;
+    const bool halving = (flags & GE_PLAYOUT_HALVING) != 0u;
+    const size_t o_range = o.acc + 8 * (size_t)ROLL_STRIDE * C;   // (halving only) the entries' replica ranges, 8 B each
+    o.total = o_range + (halving ? 8 * C : 0u);
     uint32_t *host32 = nullptr;
     if ((st = io_stage(b, o.total, &host32)) != GE_OK) return st;
     unsigned char *host = reinterpret_cast<unsigned char *>(host32);
@@ -303,7 +394,9 @@ static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
             a.e_choices = reinterpret_cast<uint32_t *>(dev + o.choices); a.e_status = reinterpret_cast<int32_t *>(dev + o.status);
             a.n = u.cnt; a.seg = u.seg; a.seed_key = seed_b; a.restart = restart;
             a.full_view = (flags & GE_PLAYOUT_FULL_VIEW) ? 1u : 0u; a.e_base = u.e_base;
-            HIP_TRY(playout_launch(b->segs[u.seg].dev.kind, dim3((u.cnt + 63u) / 64u), s, b, a));
+            const dim3 grid((u.cnt + 63u) / 64u);
+            HIP_TRY(halving ? playout_launch(b->segs[u.seg].dev.kind, grid, s, b, a, reinterpret_cast<u32x2 *>(dev + o_range), n_rollouts)
+                            : playout_launch(b->segs[u.seg].dev.kind, grid, s, b, a));
         }
         // 2. the entry counts (the one host round trip), then the playouts of each unit
         HIP_TRY(hipMemcpyAsync(host + o_ctr, dev + o_ctr, 4 * (size_t)n_units, hipMemcpyDeviceToHost, s));
@@ -322,7 +415,31 @@ static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
             a.n = cnt; a.seg = u.seg; a.seed_key = seed_key((uint32_t)seed, (uint32_t)(seed >> 32));
             a.n_rollouts = n_rollouts; a.max_turns = max_turns; a.waves = waves;
             a.settle_mask = rollout_settle_mask(b->segs[u.seg]);
-            HIP_TRY(rollout_launch_form<2>(b, s, a, dev, o, u.e_base));
+            if (!halving) {
+                HIP_TRY(rollout_launch_form<2>(b, s, a, dev, o, u.e_base));
+                continue;
+            }
+            // §3h: the rounds of this unit's segment, the accumulators adding up; no cut behind the last round
+            const SegDev &sd = b->segs[u.seg].dev;
+            const uint32_t kind = sd.kind, r_max = halving_max_rounds(sd);
+            for (uint32_t j = 0; j < r_max; j++) {
+                a.waves = halving_waves(n_rollouts, playout_max_cands(sd), j);
+                if (a.waves) {
+                    RollArgs<4> ra = rollout_form_args<4>(a, dev, o, u.e_base);
+                    ra.range = reinterpret_cast<const u32x2 *>(dev + o_range) + u.e_base;
+                    const dim3 grid(cnt * a.waves);           // <= 2^26 blocks: no round is longer than n_rollouts
+                    HIP_TRY((b->generic ? rollout_launch<1, 4>(kind, grid, s, b, ra) : rollout_launch<0, 4>(kind, grid, s, b, ra)));
+                }
+                if (j + 1u == r_max) break;
+                HalveArgs h;
+                h.room_first = reinterpret_cast<const uint32_t *>(dev + o_rfirst) + u.lo;
+                h.room_cnt = reinterpret_cast<const uint32_t *>(dev + o_rcnt) + u.lo;
+                h.e_players = reinterpret_cast<const uint32_t *>(dev + o.players);
+                h.acc = reinterpret_cast<const unsigned long long *>(dev + o.acc);
+                h.e_range = reinterpret_cast<u32x2 *>(dev + o_range);
+                h.n = u.cnt; h.n_rollouts = n_rollouts; h.round = j;
+                HIP_TRY(playout_launch(dim3((u.cnt + 63u) / 64u), s, h));
+            }
         }
         // 3. decide and log
         for (const PlayoutUnit &u : units) {
@@ -366,7 +483,7 @@ static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
 // playouts (ge_batch_run_rooms_playout: max_turns - 1); the cost cap is per turn, as only one turn's playouts exist at a time
 static int playout_check(const ge_batch *b, uint64_t n, const uint64_t *rooms, const uint32_t *turns, const uint32_t *playout_masks,
                          const uint64_t *playout_keys, uint32_t n_rollouts, uint32_t max_turns, uint32_t flags, uint32_t more_turns) {
-    if (!playout_masks || !playout_keys || (flags & ~GE_PLAYOUT_FULL_VIEW)) return GE_ERR_ARG;
+    if (!playout_masks || !playout_keys || (flags & ~(GE_PLAYOUT_FULL_VIEW | GE_PLAYOUT_HALVING))) return GE_ERR_ARG;
     if (n_rollouts == 0 || n_rollouts > (1u << 20) || max_turns > 4096u) return GE_ERR_ARG;
     for (uint64_t k = 0; k < n; k++)
         if ((uint64_t)turns[k] + more_turns + max_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;

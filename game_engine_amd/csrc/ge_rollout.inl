@@ -44,6 +44,12 @@
 // a shrinking mask, every count uniform) and, per tuple, its bits shifted from its uniform source seat to the lane's
 // destination seat in a few 64-bit bundles of bit-planes (no array indexed by seat: no scratch).  seats[e] = 0 skips it.
 //
+// Playouts over a replica range (playout seats under GE_PLAYOUT_HALVING, ACT = 4; POLICY.md §3h; launched by ge_playout.inl and
+// ge_run_playout.inl).  Everything ACT = 2 does, for the replicas [lo, hi) of the entry's range instead of [0, R): the lane is
+// replica lo + r_in, a lane past hi plays replica lo's game again and adds nothing, and a wavefront whose first lane is past hi
+// returns before it loads, writes a status or reduces anything.  The accumulators are not zeroed between rounds: an entry's
+// words are the sums over every replica it has played.
+//
 // Playouts that keep their outcome (ge_batch_rollout_compare, ACT = 3; ge_compare.inl).  Everything ACT = 2 does; then each lane
 // stores the outcome X of its replica for seat subjects[e] - Werewolf: the seat's team has won, Two-Truths: the seat's
 // total_score - as one byte of the entry's row of the outcome plane (waves * 64 bytes per row: a wavefront's lanes write 64
@@ -79,6 +85,11 @@ template <> struct RollArgs<2> : RollArgs<1> {
 template <> struct RollArgs<3> : RollArgs<2> {
     const uint32_t *subjects;
     unsigned char *plane;           // [n] rows of waves * 64 bytes
+};
+// ACT = 4: ACT = 2 over a replica range per entry (POLICY.md §3h): entry e plays replicas [range[e].x, range[e].y), lane r_in of
+// the entry the replica range[e].x + r_in; x > y marks an entry that plays no more (ge_playout_halve)
+template <> struct RollArgs<4> : RollArgs<2> {
+    const u32x2 *range;
 };
 
 struct RollLane {
@@ -305,8 +316,15 @@ template <int NB, int GENERIC, int ACT>
 __device__ __forceinline__ void roll_ww(const SegDev &sg, const DevTable *__restrict__ tables, const RollArgs<ACT> &a, void *lw, uint32_t e,
                                         uint32_t r_in, unsigned long long *part, uint32_t *h_end, uint32_t *h_score) {
     using L = WWLayout<NB>;
-    const bool valid = r_in < a.n_rollouts;
-    const uint32_t r = valid ? r_in : 0u;
+    uint32_t r_lo = 0u, r_hi = a.n_rollouts;
+    if constexpr (ACT == 4) {                                 // the entry's replica range: wave-uniform
+        const u32x2 rg = a.range[e];
+        r_lo = (uint32_t)__builtin_amdgcn_readfirstlane(rg.x); r_hi = (uint32_t)__builtin_amdgcn_readfirstlane(rg.y);
+        const uint32_t r_first = (uint32_t)__builtin_amdgcn_readfirstlane(r_in);
+        if (r_lo > r_hi || r_first >= r_hi - r_lo) return;    // nothing of the range in this wavefront: it touches nothing
+    }
+    const bool valid = r_in < r_hi - r_lo;
+    const uint32_t r = r_lo + (valid ? r_in : 0u);
     const uint64_t room = uniform_u64(a.rooms[e]), key = uniform_u64(a.keys[e]);
     const uint32_t turn0 = (uint32_t)__builtin_amdgcn_readfirstlane(a.turns[e]);
     uint32_t w[L::WORDS];
@@ -350,8 +368,15 @@ template <int NB, int GENERIC, int ACT>
 __device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__restrict__ tables, const RollArgs<ACT> &a, void *lw, uint32_t e,
                                         uint32_t r_in, unsigned long long *part, uint32_t *h_end, uint32_t *h_score) {
     using L = TTLayout<NB>;
-    const bool valid = r_in < a.n_rollouts;
-    const uint32_t r = valid ? r_in : 0u;
+    uint32_t r_lo = 0u, r_hi = a.n_rollouts;
+    if constexpr (ACT == 4) {                                 // the entry's replica range: wave-uniform
+        const u32x2 rg = a.range[e];
+        r_lo = (uint32_t)__builtin_amdgcn_readfirstlane(rg.x); r_hi = (uint32_t)__builtin_amdgcn_readfirstlane(rg.y);
+        const uint32_t r_first = (uint32_t)__builtin_amdgcn_readfirstlane(r_in);
+        if (r_lo > r_hi || r_first >= r_hi - r_lo) return;    // nothing of the range in this wavefront: it touches nothing
+    }
+    const bool valid = r_in < r_hi - r_lo;
+    const uint32_t r = r_lo + (valid ? r_in : 0u);
     const uint64_t room = uniform_u64(a.rooms[e]), key = uniform_u64(a.keys[e]);
     const uint32_t turn0 = (uint32_t)__builtin_amdgcn_readfirstlane(a.turns[e]);
     uint32_t w[L::WORDS];

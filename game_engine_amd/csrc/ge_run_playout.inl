@@ -42,18 +42,30 @@ struct RunpRooms {
     uint32_t t, max_turns;
 };
 
-template <int KIND>
-__global__ void __launch_bounds__(64) ge_runp_plan(const SegDev *__restrict__ segs, const DevTable *__restrict__ tables, const PlanArgs a,
-                                                   const uint32_t *__restrict__ live, u32x4 *acc) {
+// HALVE (GE_PLAYOUT_HALVING, POLICY.md §3h): each entry taken also gets round 0's replica range
+template <int KIND, bool HALVE>
+__device__ __forceinline__ void runp_plan_lane(const SegDev *__restrict__ segs, const DevTable *__restrict__ tables, const PlanArgs &a,
+                                               const uint32_t *__restrict__ live, u32x4 *acc, u32x2 *e_range, uint32_t n_rollouts) {
     const uint32_t k = blockIdx.x * 64u + threadIdx.x;
     if (k >= a.n) return;
     if (live[k] == 0u) { a.room_cnt[k] = 0u; return; }
     const SegDev &sg = segs[a.seg];
-    playout_plan_room<KindOf<KIND>::NB, KindOf<KIND>::WW>(sg, tables, a, k);
+    playout_plan_room<KindOf<KIND>::NB, KindOf<KIND>::WW, HALVE>(sg, tables, a, k, e_range, n_rollouts);
     const uint32_t cnt = a.room_cnt[k];                       // the entries this lane has just taken start from zero
     u32x4 *z = acc + (size_t)a.room_first[k] * (ROLL_STRIDE / 2u);
     u32x4 zero; zero.x = 0u; zero.y = 0u; zero.z = 0u; zero.w = 0u;
     for (uint32_t j = 0; j < cnt * (ROLL_STRIDE / 2u); j++) z[j] = zero;
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(64) ge_runp_plan(const SegDev *__restrict__ segs, const DevTable *__restrict__ tables, const PlanArgs a,
+                                                   const uint32_t *__restrict__ live, u32x4 *acc) {
+    runp_plan_lane<KIND, false>(segs, tables, a, live, acc, nullptr, 0u);
+}
+template <int KIND>
+__global__ void __launch_bounds__(64) ge_runp_plan_ranged(const SegDev *__restrict__ segs, const DevTable *__restrict__ tables, const PlanArgs a,
+                                                          const uint32_t *__restrict__ live, u32x4 *acc, u32x2 *e_range, uint32_t n_rollouts) {
+    runp_plan_lane<KIND, true>(segs, tables, a, live, acc, e_range, n_rollouts);
 }
 
 // ge_rollout_kernel<.., ACT = 2> with the number of entries taken from device memory
@@ -73,6 +85,28 @@ __global__ void __launch_bounds__(64) ge_runp_rollout(const SegDev *__restrict__
         if constexpr (KindOf<KIND>::WW) roll_ww<KindOf<KIND>::NB, GENERIC, 2>(sg, tables, a, lw, e, r, part, h_end, h_score);
         else roll_tt<KindOf<KIND>::NB, GENERIC, 2>(sg, tables, a, lw, e, r, part, h_end, h_score);
         __syncthreads();                                      // the reduction has read `part` before the next pair clears it
+    }
+}
+
+// ge_rollout_kernel<.., ACT = 4> in the same shape: one round of §3h over the entries' replica ranges, `waves` that round's.  A
+// copy of the loop above and not a shared body: with the loop in a function of both (by reference or by value) the compiler
+// emits other instructions for the unflagged kernel, which has to stay as it was
+template <int KIND, int GENERIC>
+__global__ void __launch_bounds__(64) ge_runp_rollout_ranged(const SegDev *__restrict__ segs, const DevTable *__restrict__ tables, const RollArgs<4> a,
+                                                             const uint32_t *__restrict__ count) {
+    __shared__ unsigned long long part[ROLL_FIELDS];
+    __shared__ uint32_t h_end[16], h_score[16];
+    const SegDev &sg = segs[a.seg];
+    const uint32_t pairs = (uint32_t)__builtin_amdgcn_readfirstlane(*count) * a.waves;
+    void *lw = ge_lds;
+    for (uint32_t x = blockIdx.x; x < pairs; x += gridDim.x) {
+        const uint32_t e = x / a.waves, r = (x - e * a.waves) * 64u + threadIdx.x;
+        if (threadIdx.x < ROLL_FIELDS) part[threadIdx.x] = 0;
+        if (threadIdx.x < 16) { h_end[threadIdx.x] = 0; h_score[threadIdx.x] = 0; }
+        __syncthreads();
+        if constexpr (KindOf<KIND>::WW) roll_ww<KindOf<KIND>::NB, GENERIC, 4>(sg, tables, a, lw, e, r, part, h_end, h_score);
+        else roll_tt<KindOf<KIND>::NB, GENERIC, 4>(sg, tables, a, lw, e, r, part, h_end, h_score);
+        __syncthreads();
     }
 }
 
@@ -107,6 +141,15 @@ hipError_t runp_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch 
 }
 template <int GEN> hipError_t runp_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const RollArgs<2> &a, const uint32_t *count) {
     return by_kind(kind, [&](auto K) { hipLaunchKernelGGL((ge_runp_rollout<K(), GEN>), grid, dim3(64), lane_lds(kind), st, b->segs_dev, b->tables, a, count); });
+}
+hipError_t runp_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const PlanArgs &a, const uint32_t *live, u32x4 *acc, u32x2 *e_range,
+                       uint32_t n_rollouts) {
+    return by_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL((ge_runp_plan_ranged<K()>), grid, dim3(64), 0, st, b->segs_dev, b->tables, a, live, acc, e_range, n_rollouts);
+    });
+}
+template <int GEN> hipError_t runp_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const RollArgs<4> &a, const uint32_t *count) {
+    return by_kind(kind, [&](auto K) { hipLaunchKernelGGL((ge_runp_rollout_ranged<K(), GEN>), grid, dim3(64), lane_lds(kind), st, b->segs_dev, b->tables, a, count); });
 }
 template <int GEN> hipError_t runp_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const RunArgs &a, const RunpRooms &x) {
     return by_kind(kind, [&](auto K) { hipLaunchKernelGGL((ge_runp_turn<K(), GEN>), grid, dim3(64), lane_lds(kind), st, b->segs_dev, b->tables, a, x); });
@@ -157,7 +200,9 @@ static int run_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, cons
     o.choices = up16(o.players + 4 * C);
     o.status = up16(o.choices + 4 * C);
     o.acc = up16(o.status + 4 * C);
-    o.total = o.acc + 8 * (size_t)ROLL_STRIDE * C;
+    const bool halving = (flags & GE_PLAYOUT_HALVING) != 0u;
+    const size_t o_range = o.acc + 8 * (size_t)ROLL_STRIDE * C;   // (halving only) the entries' replica ranges, 8 B each
+    o.total = o_range + (halving ? 8 * C : 0u);
     uint32_t *host32 = nullptr;
     if ((st = io_stage(b, host_total, &host32)) != GE_OK) return st;
     unsigned char *host = reinterpret_cast<unsigned char *>(host32);
@@ -201,7 +246,10 @@ static int run_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, cons
                     a.e_choices = reinterpret_cast<uint32_t *>(dev + o.choices); a.e_status = reinterpret_cast<int32_t *>(dev + o.status);
                     a.n = u.cnt; a.seg = u.seg; a.seed_key = seed_b; a.restart = restart;
                     a.full_view = (flags & GE_PLAYOUT_FULL_VIEW) ? 1u : 0u; a.e_base = u.e_base;
-                    HIP_TRY(runp_launch(b->segs[u.seg].dev.kind, dim3((u.cnt + 63u) / 64u), s, b, a, d_live + u.lo, reinterpret_cast<u32x4 *>(dev + o.acc)));
+                    const dim3 grid((u.cnt + 63u) / 64u);
+                    u32x4 *acc = reinterpret_cast<u32x4 *>(dev + o.acc);
+                    HIP_TRY(halving ? runp_launch(b->segs[u.seg].dev.kind, grid, s, b, a, d_live + u.lo, acc, reinterpret_cast<u32x2 *>(dev + o_range), n_rollouts)
+                                    : runp_launch(b->segs[u.seg].dev.kind, grid, s, b, a, d_live + u.lo, acc));
                 }
                 for (const PlayoutUnit &u : units) {              // 2. the playouts, their number read on the device
                     if (u.pass != p) continue;
@@ -213,12 +261,37 @@ static int run_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, cons
                     a.n = u.e_cap; a.seg = u.seg; a.seed_key = seed_key((uint32_t)seed, (uint32_t)(seed >> 32));
                     a.n_rollouts = n_rollouts; a.max_turns = pmax; a.waves = waves;
                     a.settle_mask = rollout_settle_mask(b->segs[u.seg]);
-                    const RollArgs<2> ra = rollout_form_args<2>(a, dev, o, u.e_base);
-                    const uint64_t cap_pairs = (uint64_t)u.e_cap * waves;   // <= 2^26: the cost cap
-                    const dim3 grid((uint32_t)(runp_capacity_grid() ? cap_pairs : std::min<uint64_t>(cap_pairs, RUNP_GRID_BLOCKS)));
                     const uint32_t *cnt = reinterpret_cast<const uint32_t *>(dev + o_ctr) + (size_t)(&u - units.data()) * T + t;
                     const uint32_t kind = b->segs[u.seg].dev.kind;
-                    HIP_TRY(b->generic ? runp_launch<1>(kind, grid, s, b, ra, cnt) : runp_launch<0>(kind, grid, s, b, ra, cnt));
+                    if (!halving) {
+                        const RollArgs<2> ra = rollout_form_args<2>(a, dev, o, u.e_base);
+                        const uint64_t cap_pairs = (uint64_t)u.e_cap * waves;   // <= 2^26: the cost cap
+                        const dim3 grid((uint32_t)(runp_capacity_grid() ? cap_pairs : std::min<uint64_t>(cap_pairs, RUNP_GRID_BLOCKS)));
+                        HIP_TRY(b->generic ? runp_launch<1>(kind, grid, s, b, ra, cnt) : runp_launch<0>(kind, grid, s, b, ra, cnt));
+                        continue;
+                    }
+                    // §3h: the rounds of this unit's segment, each in the same two grid shapes; no cut behind the last round
+                    const SegDev &sd = b->segs[u.seg].dev;
+                    const uint32_t r_max = halving_max_rounds(sd);
+                    for (uint32_t j = 0; j < r_max; j++) {
+                        a.waves = halving_waves(n_rollouts, playout_max_cands(sd), j);
+                        if (a.waves) {
+                            RollArgs<4> ra = rollout_form_args<4>(a, dev, o, u.e_base);
+                            ra.range = reinterpret_cast<const u32x2 *>(dev + o_range) + u.e_base;
+                            const uint64_t cap_pairs = (uint64_t)u.e_cap * a.waves;   // <= 2^26: no round is longer than n_rollouts
+                            const dim3 grid((uint32_t)(runp_capacity_grid() ? cap_pairs : std::min<uint64_t>(cap_pairs, RUNP_GRID_BLOCKS)));
+                            HIP_TRY(b->generic ? runp_launch<1>(kind, grid, s, b, ra, cnt) : runp_launch<0>(kind, grid, s, b, ra, cnt));
+                        }
+                        if (j + 1u == r_max) break;
+                        HalveArgs h;
+                        h.room_first = reinterpret_cast<const uint32_t *>(dev + o_rfirst) + u.lo;
+                        h.room_cnt = reinterpret_cast<const uint32_t *>(dev + o_rcnt) + u.lo;
+                        h.e_players = reinterpret_cast<const uint32_t *>(dev + o.players);
+                        h.acc = reinterpret_cast<const unsigned long long *>(dev + o.acc);
+                        h.e_range = reinterpret_cast<u32x2 *>(dev + o_range);
+                        h.n = u.cnt; h.n_rollouts = n_rollouts; h.round = j;
+                        HIP_TRY(playout_launch(dim3((u.cnt + 63u) / 64u), s, h));
+                    }
                 }
                 for (const PlayoutUnit &u : units) {              // 3. decide and log
                     if (u.pass != p) continue;

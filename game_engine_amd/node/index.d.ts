@@ -73,7 +73,8 @@ export class RoomBatch {
   stepRooms(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>): TurnEvent[];
   stepRoomsPlayout(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, masks: ArrayLike<number>,
                    playoutKeys: ArrayLike<number | bigint>, nRollouts: number, maxTurns?: number, seed?: number | bigint,
-                   fullView?: boolean): { events: TurnEvent[]; decided: Uint32Array };
+                   fullView?: boolean, /** sequential halving of each decision's playouts (POLICY.md §3h) */ halving?: boolean):
+    { events: TurnEvent[]; decided: Uint32Array };
   /** Play each listed room on until a person is needed (POLICY.md §3f): stepRooms's entries (rooms[k], keys[k], turns[k] + t) until the
    *  turn leaves a state named in `until` ("person" | "end" | "phase", or the ABI's bits) or maxTurns turns are played.  events[k] /
    *  views[k] hold one entry per played turn (views: false -> null); stopped[k] = the bits that held after the last turn (0: the limit).
@@ -86,7 +87,7 @@ export class RoomBatch {
    *  Synchronous; GE_BUSY while an async step() is in flight. */
   runRoomsPlayout(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, masks: ArrayLike<number>,
                   playoutKeys: ArrayLike<number | bigint>, nRollouts: number, playoutMaxTurns?: number, seed?: bigint | number,
-                  fullView?: boolean, maxTurns?: number, until?: RunUntil[] | RunUntil | number, views?: boolean):
+                  fullView?: boolean, maxTurns?: number, until?: RunUntil[] | RunUntil | number, views?: boolean, halving?: boolean):
     { played: Uint32Array; stopped: Uint32Array; events: TurnEvent[][]; views: RoomState[][] | null; decided: number[][] };
   /** Playouts of each listed room (replica r of entry k = global room keys[k] + r under seed, default the batch's): rooms.length x 77
    *  words of ge_rollout_stats (41 summary words, then seat_alive, seat_wins, seat_score x 12).  The batch is only read. */

@@ -599,12 +599,14 @@ class RoomBatch {
    * rolloutSeats entry (room k as it stands, playoutKeys[k], turns[k], the seat or 0 with fullView, that one action, nRollouts,
    * maxTurns, seed) has the most seat_wins of the seat; ties go to the policy's own pick among the tied.  Returns
    * { events, decided }: stepRooms's events (the decided seats listed as acted) and decided[k] (bit i = seat i+1 chose by
-   * playouts).  All-or-nothing.  Synchronous. */
-  stepRoomsPlayout(rooms, keys, turns, masks, playoutKeys, nRollouts, maxTurns = 256, seed, fullView = false) {
+   * playouts).  halving (GE_PLAYOUT_HALVING, POLICY.md §3h): a seat's candidates are valued in ceil(log2 c) rounds of growing
+   * replica ranges, the worse half leaving after each - fewer playouts, more launches per turn, and slower at every shape measured on an MI355X (x 0.38 .. 0.71 of the unflagged call's speed).
+   * All-or-nothing.  Synchronous. */
+  stepRoomsPlayout(rooms, keys, turns, masks, playoutKeys, nRollouts, maxTurns = 256, seed, fullView = false, halving = false) {
     const { buffer, decided } = addon.stepRoomsPlayout(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r)),
       BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))), Uint32Array.from(turns), Uint32Array.from(masks),
       BigUint64Array.from(playoutKeys, (k) => BigInt.asUintN(64, BigInt(k))), nRollouts, maxTurns,
-      seed === undefined ? this.seed : BigInt.asUintN(64, BigInt(seed)), fullView ? 1 : 0);
+      seed === undefined ? this.seed : BigInt.asUintN(64, BigInt(seed)), (fullView ? 1 : 0) | (halving ? 4 : 0));
     const events = [];
     for (let k = 0; k < rooms.length; k++) events.push(decodeEvent(buffer, k * EVENT_SIZE));
     return { events, decided };
@@ -639,15 +641,15 @@ class RoomBatch {
    * and stops as runRooms stops it; between the turns of the call the host does not wait for the device.  Returns { played, stopped,
    * events, views, decided }: the first four as runRooms returns them, events being stepRoomsPlayout's (the decided seats listed as
    * acted); decided[k][t] is turn t's decided mask.  All-or-nothing: runRooms's checks, then stepRoomsPlayout's, with the cost cap
-   * per turn and turns[k] + maxTurns - 1 + playoutMaxTurns within 0xFFFFFFFF.  Synchronous; GE_BUSY while an async step() is in
-   * flight. */
+   * per turn and turns[k] + maxTurns - 1 + playoutMaxTurns within 0xFFFFFFFF.  halving: every turn's decisions as
+   * stepRoomsPlayout's under it.  Synchronous; GE_BUSY while an async step() is in flight. */
   runRoomsPlayout(rooms, keys, turns, masks, playoutKeys, nRollouts, playoutMaxTurns = 256, seed, fullView = false, maxTurns = 64,
-                  until = ['person', 'end'], views = true) {
+                  until = ['person', 'end'], views = true, halving = false) {
     const bits = runUntilBits(until);
     const r = addon.runRoomsPlayout(this.handle, BigUint64Array.from(rooms, (x) => BigInt(x)), BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))),
                                     Uint32Array.from(turns), Uint32Array.from(masks), BigUint64Array.from(playoutKeys, (k) => BigInt.asUintN(64, BigInt(k))),
-                                    nRollouts, playoutMaxTurns, seed === undefined ? this.seed : BigInt.asUintN(64, BigInt(seed)), fullView ? 1 : 0,
-                                    maxTurns, bits, !!views);
+                                    nRollouts, playoutMaxTurns, seed === undefined ? this.seed : BigInt.asUintN(64, BigInt(seed)),
+                                    (fullView ? 1 : 0) | (halving ? 4 : 0), maxTurns, bits, !!views);
     const events = [], states = views ? [] : null, decided = [];
     for (let k = 0; k < rooms.length; k++) {
       const ev = [], vw = [];

@@ -18,9 +18,11 @@ const M = require('./messages.js');
 const GE_ERR_ARG = -1;
 
 class RoomPoolService {
-  /** playoutRollouts / playoutMaxTurns / playoutView: as RoomService's. */
-  constructor({ gamesDir = 'games', seed = 0n, device = 0, chunkRooms = 1024, playoutRollouts = 256, playoutMaxTurns = 256, playoutView = 'seat' } = {}) {
-    this.playoutFull = checkPlayoutOptions(playoutRollouts, playoutMaxTurns, playoutView);
+  /** playoutRollouts / playoutMaxTurns / playoutView / playoutHalving: as RoomService's. */
+  constructor({ gamesDir = 'games', seed = 0n, device = 0, chunkRooms = 1024, playoutRollouts = 256, playoutMaxTurns = 256, playoutView = 'seat',
+                playoutHalving = false } = {}) {
+    this.playoutFull = checkPlayoutOptions(playoutRollouts, playoutMaxTurns, playoutView, playoutHalving);
+    this.playoutHalving = playoutHalving;
     this.playoutRollouts = playoutRollouts; this.playoutMaxTurns = playoutMaxTurns;
     if (!(chunkRooms >= 1)) throw new RangeError('chunkRooms must be >= 1');
     this.gamesDir = gamesDir; this.seed = BigInt(seed); this.device = device; this.chunkRooms = chunkRooms;
@@ -231,7 +233,7 @@ class RoomPoolService {
           const slots = js.map((j) => rooms[j].slot), keys = js.map((j) => rooms[j].key), turns = js.map((j) => rooms[j].turn);
           const r = withBots
             ? chunk.runRoomsPlayout(slots, keys, turns, js.map((j) => rooms[j].playoutMask), keys.map((k) => forecastKey(k)), this.playoutRollouts,
-                                    this.playoutMaxTurns, forecastSeed(this.seed), this.playoutFull, maxTurns, bits)
+                                    this.playoutMaxTurns, forecastSeed(this.seed), this.playoutFull, maxTurns, bits, true, this.playoutHalving)
             : chunk.runRooms(slots, keys, turns, maxTurns, bits);
           js.forEach((j, k) => { got[j] = { events: r.events[k], views: r.views[k], stopped: r.stopped[k] }; });
         }
@@ -319,7 +321,7 @@ class RoomPoolService {
       const rs = rooms.slice(a, b);
       out.push(...chunk.stepRoomsPlayout(rs.map((r) => r.slot), rs.map((r) => r.key), rs.map((r) => r.turn), rs.map((r) => r.playoutMask),
                                          rs.map((r) => forecastKey(r.key)), this.playoutRollouts, this.playoutMaxTurns, forecastSeed(this.seed),
-                                         this.playoutFull).events);
+                                         this.playoutFull, this.playoutHalving).events);
     }
     return out;
   }

@@ -17,8 +17,10 @@ export interface AdoptOptions {
   /** bot seats that choose each action by playouts (POLICY.md §3d) */ playoutSeats?: number[];
 }
 /** How the playout bots of threads created with playoutSeats choose (POLICY.md §3d): nRollouts (default 256) and maxTurns (256)
- * of each candidate's playouts, from the bot's own view ("seat", the default) or the true record ("full": a cheating bot). */
-export interface PlayoutOptions { playoutRollouts?: number; playoutMaxTurns?: number; playoutView?: 'seat' | 'full'; }
+ * of each candidate's playouts, from the bot's own view ("seat", the default) or the true record ("full": a cheating bot).
+ * playoutHalving (default false): sequential halving of each decision's playouts (POLICY.md §3h) - fewer playouts, more launches
+ * per turn, and slower at every shape measured (DESIGN.md §4); a bot's candidate values are then advise's option forecasts for the finalists only. */
+export interface PlayoutOptions { playoutRollouts?: number; playoutMaxTurns?: number; playoutView?: 'seat' | 'full'; playoutHalving?: boolean; }
 export interface TurnResult { state: AgentStateView; toolCalls: ToolCall[]; uiCalls: FrontendToolCall[]; }
 /** runRoom: one TurnResult per played turn; stopped: the conditions that held after the last one ([]: the limit). */
 export type RunUntil = 'person' | 'end' | 'phase';

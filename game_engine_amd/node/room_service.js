@@ -113,8 +113,9 @@ function playoutMaskOf(n, humanMask, playoutSeats) {
   return mask;
 }
 /** the services' playout-bot options (twin of room_service.py check_playout_options); returns true for the full view */
-function checkPlayoutOptions(nRollouts, maxTurns, view) {
+function checkPlayoutOptions(nRollouts, maxTurns, view, halving = false) {
   checkForecastArgs(nRollouts, maxTurns);
+  if (typeof halving !== 'boolean') throw new RangeError('playoutHalving must be true or false');
   if (view !== 'full' && view !== 'seat') throw new RangeError('playoutView must be "full" or "seat"');
   return view === 'full';
 }
@@ -233,9 +234,13 @@ function runOutput(turns, stopped) { return { turns, played: turns.length, stopp
 class RoomService {
   /** playoutRollouts / playoutMaxTurns / playoutView: how the playout bots of threads created with playoutSeats choose
    * (POLICY.md §3d): nRollouts and maxTurns of each candidate's playouts, and "seat" (from what the bot knows) or "full" (from
-   * the true record - a cheating bot in a game with people). */
-  constructor({ gamesDir = 'games', seed = 0n, device = 0, playoutRollouts = 256, playoutMaxTurns = 256, playoutView = 'seat' } = {}) {
-    this.playoutFull = checkPlayoutOptions(playoutRollouts, playoutMaxTurns, playoutView);
+   * the true record - a cheating bot in a game with people).  playoutHalving: the bots spend each decision's playouts by
+   * sequential halving (POLICY.md §3h): fewer playouts but more launches per turn, and slower at every shape measured on an MI355X (x 0.38 .. 0.71 of the unflagged call's speed), so off by default; a
+   * bot's candidate values are then advise's option forecasts for the finalists only. */
+  constructor({ gamesDir = 'games', seed = 0n, device = 0, playoutRollouts = 256, playoutMaxTurns = 256, playoutView = 'seat',
+                playoutHalving = false } = {}) {
+    this.playoutFull = checkPlayoutOptions(playoutRollouts, playoutMaxTurns, playoutView, playoutHalving);
+    this.playoutHalving = playoutHalving;
     this.playoutRollouts = playoutRollouts; this.playoutMaxTurns = playoutMaxTurns;
     this.gamesDir = gamesDir; this.seed = BigInt(seed); this.device = device;
     this.tables = new Map();       // gameName -> GameTable
@@ -379,7 +384,8 @@ class RoomService {
       checkRunThread(threadId, room, !!(options && options.playout));
       const r = room.playoutMask
         ? room.batch.runRoomsPlayout([0], [room.key], [room.turn], [room.playoutMask], [forecastKey(room.key)], this.playoutRollouts,
-                                     this.playoutMaxTurns, forecastSeed(this.seed), this.playoutFull, maxTurns, bits)
+                                     this.playoutMaxTurns, forecastSeed(this.seed), this.playoutFull, maxTurns, bits, true,
+                                     this.playoutHalving)
         : room.batch.runRooms([0], [room.key], [room.turn], maxTurns, bits);
       room.turn += r.played[0];
       room.batch.setTurn(room.turn);
@@ -424,7 +430,8 @@ class RoomService {
     let event;
     if (room.playoutMask) {                            // playout bots: advise's keys and seed, so a bot's values are its advice
       const { events } = room.batch.stepRoomsPlayout([0], [room.key], [room.turn], [room.playoutMask], [forecastKey(room.key)],
-                                                     this.playoutRollouts, this.playoutMaxTurns, forecastSeed(this.seed), this.playoutFull);
+                                                     this.playoutRollouts, this.playoutMaxTurns, forecastSeed(this.seed), this.playoutFull,
+                                                     this.playoutHalving);
       room.batch.setTurn(room.turn + 1);
       event = events[0];
     } else {

@@ -39,11 +39,13 @@ class _Pool:
 
 class RoomPoolService:
     def __init__(self, games_dir: str = "games", seed: int = 0, device: int = 0, chunk_rooms: int = 1024, playout_rollouts: int = 256,
-                 playout_max_turns: int = 256, playout_view: str = "seat"):
+                 playout_max_turns: int = 256, playout_view: str = "seat", playout_halving: bool = False):
         """playout_*: as RoomService's."""
         if chunk_rooms < 1:
             raise ValueError("chunk_rooms must be >= 1")
-        self.playout_full = check_playout_options(playout_rollouts, playout_max_turns, playout_view)
+        self.playout_full = check_playout_options(playout_rollouts, playout_max_turns, playout_view, playout_halving)
+        self.playout_halving = playout_halving
+        self._halving_kw = {"halving": True} if playout_halving else {}   # (off: no keyword, so a stand-in batch written before the option existed still serves)
         self.playout_rollouts, self.playout_max_turns = int(playout_rollouts), int(playout_max_turns)
         self.games_dir, self.seed, self.device, self.chunk_rooms = games_dir, seed, device, chunk_rooms
         self._tables: Dict[str, GameTable] = {}
@@ -294,7 +296,8 @@ class RoomPoolService:
                 if with_bots:
                     played, stopped, events, views, _ = chunk.run_rooms_playout(
                         slots, keys, turns, [rooms[j]["playout_mask"] for j in js], [forecast_key(k) for k in keys], self.playout_rollouts,
-                        self.playout_max_turns, seed=forecast_seed(self.seed), full_view=self.playout_full, max_turns=max_turns, until=bits)
+                        self.playout_max_turns, seed=forecast_seed(self.seed), full_view=self.playout_full, max_turns=max_turns, until=bits,
+                        **self._halving_kw)
                 else:
                     played, stopped, events, views = chunk.run_rooms(slots, keys, turns, max_turns, bits)
                 for k, j in enumerate(js):
@@ -323,7 +326,8 @@ class RoomPoolService:
         pkeys = np.array([forecast_key(r["key"]) for r in rooms], dtype=np.uint64)
         parts = self._playout_parts(rooms)
         evs = [chunk.step_rooms_playout(slots[a:b], keys[a:b], turns[a:b], masks[a:b], pkeys[a:b], self.playout_rollouts,
-                                        self.playout_max_turns, seed=forecast_seed(self.seed), full_view=self.playout_full)[0]
+                                        self.playout_max_turns, seed=forecast_seed(self.seed), full_view=self.playout_full,
+                                        **self._halving_kw)[0]
                for a, b in parts]
         return np.concatenate(evs)
 

@@ -106,9 +106,11 @@ def playout_mask(n_players: int, human_mask: int, playout_seats) -> int:
     return mask
 
 
-def check_playout_options(n_rollouts: int, max_turns: int, view: str) -> bool:
+def check_playout_options(n_rollouts: int, max_turns: int, view: str, halving: bool = False) -> bool:
     """The services' playout-bot options; returns True for the full view."""
     check_forecast_args(n_rollouts, max_turns)
+    if not isinstance(halving, bool):
+        raise ValueError("playout_halving must be True or False")
     return not check_view(view)
 
 
@@ -308,11 +310,15 @@ def run_output(turns: List[Dict[str, Any]], stopped: int) -> Dict[str, Any]:
 
 class RoomService:
     def __init__(self, games_dir: str = "games", seed: int = 0, device: int = 0, playout_rollouts: int = 256,
-                 playout_max_turns: int = 256, playout_view: str = "seat"):
+                 playout_max_turns: int = 256, playout_view: str = "seat", playout_halving: bool = False):
         """playout_*: how the playout bots of threads created with playout_seats choose (POLICY.md §3d): n_rollouts and
         max_turns of each candidate's playouts, and "seat" (from what the bot knows) or "full" (from the true record - a
-        cheating bot in a game with people)."""
-        self.playout_full = check_playout_options(playout_rollouts, playout_max_turns, playout_view)
+        cheating bot in a game with people).  playout_halving: the bots spend each decision's playouts by sequential halving
+        (POLICY.md §3h): 1.3 - 2.5 x fewer playouts, but more launches per turn, and slower at every shape measured on an MI355X (x 0.38 .. 0.71 of the unflagged call's speed): DESIGN.md §4; off by default;
+        a bot's candidate values are then advise's option forecasts for the finalists only."""
+        self.playout_full = check_playout_options(playout_rollouts, playout_max_turns, playout_view, playout_halving)
+        self.playout_halving = playout_halving
+        self._halving_kw = {"halving": True} if playout_halving else {}   # (off: no keyword, so a stand-in batch written before the option existed still serves)
         self.playout_rollouts, self.playout_max_turns = int(playout_rollouts), int(playout_max_turns)
         self.games_dir, self.seed, self.device = games_dir, seed, device
         self._tables: Dict[str, GameTable] = {}
@@ -437,7 +443,7 @@ class RoomService:
             turn = batch.turn
             ev, _ = batch.step_rooms_playout([0], [room["key"]], [turn], [room["playout_mask"]], [forecast_key(room["key"])],
                                              self.playout_rollouts, self.playout_max_turns, seed=forecast_seed(self.seed),
-                                             full_view=self.playout_full)
+                                             full_view=self.playout_full, **self._halving_kw)
             batch.set_turn(turn + 1)
             event = ev[0]
         else:
@@ -476,7 +482,7 @@ class RoomService:
         if room["playout_mask"]:
             played, stopped, events, views, _ = batch.run_rooms_playout(
                 [0], [room["key"]], [turn], [room["playout_mask"]], [forecast_key(room["key"])], self.playout_rollouts, self.playout_max_turns,
-                seed=forecast_seed(self.seed), full_view=self.playout_full, max_turns=max_turns, until=bits)
+                seed=forecast_seed(self.seed), full_view=self.playout_full, max_turns=max_turns, until=bits, **self._halving_kw)
         else:
             played, stopped, events, views = batch.run_rooms([0], [room["key"]], [turn], max_turns, bits)
         batch.set_turn(turn + int(played[0]))

@@ -311,7 +311,7 @@ class RoomBatch:
         return out
 
     def step_rooms_playout(self, rooms, keys, turns, masks, playout_keys, n_rollouts: int, max_turns: int = 256,
-                           seed: Optional[int] = None, full_view: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+                           seed: Optional[int] = None, full_view: bool = False, halving: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         """step_rooms with playout seats (POLICY.md §3d): bit i of masks[k] makes seat i+1 of room k a playout bot.  Such a seat,
         when the policy has it act in this turn with at least 2 candidates, takes the candidate whose rollout_seats entry
         (room k as it stands, playout_keys[k], turns[k], the seat - or 0 with full_view -, that one action, n_rollouts,
@@ -319,7 +319,9 @@ class RoomBatch:
         (events, decided): events as step_rooms (the decided seats listed as acted), decided[k] bit i = seat i+1 chose by
         playouts.  seed None: the batch's seed.  All-or-nothing (GeError, nothing run): step_rooms's checks, rollout_seats's
         caps, a mask bit at or above the room's player count or on a host-driven seat, or sum of popcount(mask) x n_players x
-        n_rollouts over the rooms above 2^26."""
+        n_rollouts over the rooms above 2^26.  halving (GE_PLAYOUT_HALVING, POLICY.md §3h): a seat's candidates are valued in
+        ceil(log2 c) rounds of growing replica ranges, the worse half leaving after each, so that only the finalists play all
+        n_rollouts playouts; fewer playouts but more launches per turn, and slower at every shape measured on an MI355X (x 0.38 .. 0.71 of the unflagged call's speed): DESIGN.md §4."""
         rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         turns = np.ascontiguousarray(turns, dtype=np.uint32)
@@ -329,7 +331,7 @@ class RoomBatch:
             raise GeError(-1, "step_rooms_playout: arrays differ in length")
         events = np.zeros(len(rooms), dtype=EVENT_DTYPE)
         decided = np.zeros(len(rooms), dtype=np.uint32)
-        flags = 1 if full_view else 0                            # GE_PLAYOUT_FULL_VIEW
+        flags = (1 if full_view else 0) | (4 if halving else 0)  # GE_PLAYOUT_FULL_VIEW | GE_PLAYOUT_HALVING
         _check(self._lib.ge_batch_step_rooms_playout(self._h, len(rooms), rooms.ctypes.data, keys.ctypes.data, turns.ctypes.data,
                                                      masks.ctypes.data, pkeys.ctypes.data, n_rollouts, max_turns,
                                                      self._seed if seed is None else seed, flags, events.ctypes.data,
@@ -369,9 +371,9 @@ class RoomBatch:
 
     def run_rooms_playout(self, rooms, keys, turns, masks, playout_keys, n_rollouts: int, playout_max_turns: int = 256,
                           seed: Optional[int] = None, full_view: bool = False, max_turns: int = 64, until=("person", "end"),
-                          views: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray], np.ndarray]:
+                          views: bool = True, halving: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray], np.ndarray]:
         """run_rooms with playout seats (POLICY.md §3g): room k takes step_rooms_playout's entries (rooms[k], keys[k], turns[k] + t,
-        masks[k], playout_keys[k]; n_rollouts, playout_max_turns, seed, full_view), t = 0, 1, ..., and stops as run_rooms stops it.
+        masks[k], playout_keys[k]; n_rollouts, playout_max_turns, seed, full_view, halving), t = 0, 1, ..., and stops as run_rooms stops it.
         Between the turns of the call the host does not wait for the device.  Returns (played, stopped, events, views, decided):
         the first four as run_rooms returns them, events being step_rooms_playout's (the decided seats listed as acted);
         decided has shape (n, max_turns) and holds, below played[k], each turn's decided mask.  All-or-nothing: run_rooms's checks,
@@ -394,7 +396,7 @@ class RoomBatch:
         decided = np.zeros((n, cap), dtype=np.uint32)
         events = np.zeros((n, cap), dtype=EVENT_DTYPE)
         out = np.zeros((n, cap), dtype=ROOM_VIEW_DTYPE) if views else None
-        flags = 1 if full_view else 0                            # GE_PLAYOUT_FULL_VIEW
+        flags = (1 if full_view else 0) | (4 if halving else 0)  # GE_PLAYOUT_FULL_VIEW | GE_PLAYOUT_HALVING
         _check(self._lib.ge_batch_run_rooms_playout(self._h, n, rooms.ctypes.data, keys.ctypes.data, turns.ctypes.data, masks.ctypes.data,
                                                     pkeys.ctypes.data, n_rollouts, playout_max_turns, self._seed if seed is None else seed,
                                                     flags, max_turns, bits, played.ctypes.data, stopped.ctypes.data, decided.ctypes.data,

@@ -46,7 +46,9 @@ extern "C" {
  *      ge_batch_step_rooms_playout + GE_PLAYOUT_FULL_VIEW (playout seats: bots that choose each action by their own playouts);
  *      ge_batch_rollout_compare + ge_compare_stats (an entry against a baseline entry, playout by playout: the paired counts);
  *      ge_batch_run_rooms + GE_RUN_UNTIL_* (listed rooms played on until a person is needed: many turns per call, every turn traced);
- *      ge_batch_run_rooms_playout (the same with playout seats: the playouts of every turn enqueued without the host in between) */
+ *      ge_batch_run_rooms_playout (the same with playout seats: the playouts of every turn enqueued without the host in between);
+ *      GE_PLAYOUT_HALVING (a new flag of both playout-seat calls, no new symbol: sequential halving of each decision's playout
+ *      budget; a library from before it refuses the bit with GE_ERR_ARG) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -421,7 +423,22 @@ int ge_batch_rollout_compare(ge_batch *b, uint64_t n, const uint64_t *rooms, con
  * GE_ERR_ARG for NULL masks / playout keys with n > 0, unknown flags, n_rollouts == 0 or > 2^20, max_turns > 4096, a mask bit
  * at or above the room's player count or on a host-driven seat of its segment, or sum_k popcount(mask_k) * c_k * n_rollouts >
  * 2^26, c_k = the most candidates a seat of room k can have (Werewolf: n_players, Two-Truths: max(n_players, 3)); GE_ERR_RANGE for turns[k] + max_turns > 0xFFFFFFFF.  Ordered behind the previous step; synchronises. */
+/* Under GE_PLAYOUT_HALVING (POLICY.md §3h) a deciding seat with c candidates does not play n = n_rollouts playouts for each of them
+ * but R = ceil(log2 c) rounds: with o_j = floor(n * (2^j - 1) / (2^R - 1)), round j plays replicas o_j .. o_{j+1} - 1 of the entry
+ * above (key playout_keys[k] + o_j, n_rollouts o_{j+1} - o_j; nothing when that is 0) for every candidate still in, adds its
+ * seat_wins[s-1] to the candidate's running value V, and - except after the last round - keeps the candidates whose V is at
+ * least the ceil(c / 2^(j+1))-th largest (a tie at the cut keeps every tied candidate).  The choice is the highest V among the
+ * candidates of the last round, ties to the pick(d, m)-th as above.  All survivors have played the same replicas, on common
+ * random numbers; a finalist has played replicas 0 .. n - 1, so its V is the value it has without the flag; no candidate plays
+ * more than n playouts, so the cost cap and the turn range are checked unchanged, as upper bounds.  c = 2, or an n so small that
+ * o_{R-1} = 0 (n = 1), is the call without the flag; mask 0 and max_turns = 0 are ge_batch_step_rooms word for word with the
+ * flag as without it.  The flag adds launches per turn (R rounds of playouts and R - 1 cuts instead of one launch), and on an
+ * MI355X the flagged call was SLOWER at every shape measured, x 0.38 .. 0.71 of the unflagged call's speed while playing 1.3 .. 2.5 x fewer
+ * playouts (profiles/halving_probe.txt): the flag saves playouts, not time.  It is off unless asked for.
+ * Its value is 4u, not 2u: flags = 2 has been refused with GE_ERR_ARG since the call exists, hosts' tests pin that, and it stays
+ * refused, as does every bit from 8u up. */
 #define GE_PLAYOUT_FULL_VIEW 1u   /* value candidates from the true record (seat 0) instead of the seat's view */
+#define GE_PLAYOUT_HALVING   4u   /* sequential halving of each decision's playout budget (POLICY.md §3h); 2u stays refused */
 int ge_batch_step_rooms_playout(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
                                 const uint32_t *playout_masks /* n: bit i = seat i+1 */, const uint64_t *playout_keys /* n */,
                                 uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, uint32_t flags,
@@ -475,10 +492,12 @@ int ge_batch_run_rooms(ge_batch *b, uint64_t n, const uint64_t *rooms, const uin
  * Between the turns of a call the host does not wait for the device: per turn the plan, the playouts (their number read from device
  * memory), the decision and the turn are enqueued for the rooms still live, in groups of turns with one 4-byte read of the live
  * count between groups; only the rows of the turns enqueued cross to the host.  With ge_batch_set_timing on, ge_batch_kernel_time
- * includes the call's launches.  Ordered behind the previous step; synchronises. */
+ * includes the call's launches.  Under GE_PLAYOUT_HALVING (above; POLICY.md §3h) every turn's decisions are
+ * ge_batch_step_rooms_playout's under that flag: per turn the rounds of playouts and the cuts between them are enqueued like the
+ * rest, with no host wait added.  Ordered behind the previous step; synchronises. */
 int ge_batch_run_rooms_playout(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
                                const uint32_t *playout_masks /* n: bit i = seat i+1 */, const uint64_t *playout_keys /* n */,
-                               uint32_t n_rollouts, uint32_t playout_max_turns, uint64_t seed, uint32_t flags /* GE_PLAYOUT_FULL_VIEW */,
+                               uint32_t n_rollouts, uint32_t playout_max_turns, uint64_t seed, uint32_t flags /* GE_PLAYOUT_FULL_VIEW | GE_PLAYOUT_HALVING */,
                                uint32_t max_turns, uint32_t until,
                                uint32_t *played /* n */, uint32_t *stopped /* n, may be NULL */,
                                uint32_t *decided /* n * max_turns, may be NULL */,

@@ -43,6 +43,15 @@ def describe(mangled: str) -> dict:
     if m:
         return {"kernel": "ge_rollout_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True,
                 "act": int(m.group(3) or 0)}
+    m = re.search(r"ge_playout_plan_rangedILi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_playout_plan_ranged", "layout": KINDS[int(m.group(1))], "lowocc": False, "generic": False, "single": True}
+    m = re.search(r"ge_runp_plan_rangedILi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_runp_plan_ranged", "layout": KINDS[int(m.group(1))], "lowocc": False, "generic": False, "single": True}
+    m = re.search(r"ge_runp_rollout_rangedILi(\d)ELi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_runp_rollout_ranged", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True}
     m = re.search(r"ge_playout_(plan|decide)ILi(\d)E", mangled)
     if m:
         return {"kernel": "ge_playout_" + m.group(1), "layout": KINDS[int(m.group(2))], "lowocc": False, "generic": False, "single": True}
@@ -82,6 +91,16 @@ def label(r):
         return f"{r['layout']}, indexed single-turn (ge_batch_step_rooms)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_run_kernel":                           # ge_batch_run_rooms: one launch per segment present
         return f"{r['layout']}, indexed turn loop (ge_batch_run_rooms)" + (", GENERIC" if r["generic"] else "")
+    if r["kernel"] == "ge_rollout_kernel" and r.get("act") == 4:  # GE_PLAYOUT_HALVING: one launch per unit and round
+        return f"{r['layout']}, playouts over a replica range (GE_PLAYOUT_HALVING)" + (", GENERIC" if r["generic"] else "")
+    if r["kernel"] == "ge_playout_plan_ranged":
+        return f"{r['layout']}, playout seats, plan with replica ranges (GE_PLAYOUT_HALVING)"
+    if r["kernel"] == "ge_runp_plan_ranged":
+        return f"{r['layout']}, run-on with playout seats, plan with replica ranges (GE_PLAYOUT_HALVING)"
+    if r["kernel"] == "ge_runp_rollout_ranged":
+        return f"{r['layout']}, run-on with playout seats, playouts over a replica range (GE_PLAYOUT_HALVING)" + (", GENERIC" if r["generic"] else "")
+    if r["kernel"] == "ge_playout_halve":
+        return "ge_playout_halve (GE_PLAYOUT_HALVING: the cut between two rounds)"
     if r["kernel"] == "ge_rollout_kernel" and r.get("act") == 3:  # ge_batch_rollout_compare: one launch per segment present
         return f"{r['layout']}, playouts that keep their outcome (ge_batch_rollout_compare)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_rollout_kernel" and r.get("act") == 2:  # ge_batch_rollout_seats: one launch per segment present
