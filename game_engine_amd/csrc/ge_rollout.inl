@@ -50,6 +50,12 @@
 // returns before it loads, writes a status or reduces anything.  The accumulators are not zeroed between rounds: an entry's
 // words are the sums over every replica it has played.
 //
+// Playouts from a traced turn (ge_batch_run_rooms_forecast, ACT = 5; POLICY.md §3i; launched by ge_timeline.inl behind the run
+// kernel).  Everything ACT = 2 does without actions, for a block that is (turn t, entry i) of the run in front of it: the source
+// record is words 4.. of trace slot t * n_all + first + i instead of a batch room, the first turn is turns[i] + t + 1 and the
+// accumulator row is t * n_all + i (turn-major, as the trace plane).  A block whose t is not below the run's played[i] - read
+// from device memory, wave-uniform - returns before it loads or reduces anything.
+//
 // Playouts that keep their outcome (ge_batch_rollout_compare, ACT = 3; ge_compare.inl).  Everything ACT = 2 does; then each lane
 // stores the outcome X of its replica for seat subjects[e] - Werewolf: the seat's team has won, Two-Truths: the seat's
 // total_score - as one byte of the entry's row of the outcome plane (waves * 64 bytes per row: a wavefront's lanes write 64
@@ -90,6 +96,14 @@ template <> struct RollArgs<3> : RollArgs<2> {
 // the entry the replica range[e].x + r_in; x > y marks an entry that plays no more (ge_playout_halve)
 template <> struct RollArgs<4> : RollArgs<2> {
     const u32x2 *range;
+};
+
+// ACT = 5: ACT = 2 without actions from a turn of the run traced in front of it (POLICY.md §3i): entry e = t * n + i is turn t of
+// this launch's entry i (keys, turns, seats and run_out are indexed by i; rooms and the action arrays are not read)
+template <> struct RollArgs<5> : RollArgs<2> {
+    const u32x4 *trace;             // the run's trace plane (64 B per room-turn, turn-major over n_all entries)
+    const u32x2 *run_out;           // [n]: the run's (played, stop bits)
+    uint32_t n_all, first;          // this launch's entries are the plane's entries first .. first + n - 1
 };
 
 struct RollLane {
@@ -150,6 +164,19 @@ __device__ __forceinline__ uint32_t roll_h0(uint64_t g) { return mix32((uint32_t
 // the replica's outcome byte into the entry's row of the outcome plane (ACT = 3): lane r_in of the entry, a plain vector store
 __device__ __forceinline__ void roll_keep(const RollArgs<3> &a, uint32_t e, uint32_t r_in, uint32_t x) {
     a.plane[(size_t)e * ((size_t)a.waves * 64u) + r_in] = (unsigned char)x;
+}
+
+// the source record of ACT = 5: the packed record of turn t of entry i, as run_trace stored it behind the event's four words
+template <int WORDS>
+__device__ __forceinline__ void roll_load_trace(const RollArgs<5> &a, uint32_t t, uint32_t i, uint32_t *w) {
+    const u32x4 *slot = a.trace + 4u * ((size_t)t * a.n_all + a.first + i);
+#pragma unroll
+    for (int j = 0; j < (WORDS + 3) / 4; j++) {
+        const u32x4 v = slot[1 + j];
+        w[4 * j] = v.x; w[4 * j + 1] = v.y;
+        if (4 * j + 2 < WORDS) w[4 * j + 2] = v.z;
+        if (4 * j + 3 < WORDS) w[4 * j + 3] = v.w;
+    }
 }
 
 // the entry's actions logged in its source record (ACT = 1 prologue); false (wave-uniform) = refused, status[e] written
@@ -323,13 +350,22 @@ __device__ __forceinline__ void roll_ww(const SegDev &sg, const DevTable *__rest
         const uint32_t r_first = (uint32_t)__builtin_amdgcn_readfirstlane(r_in);
         if (r_lo > r_hi || r_first >= r_hi - r_lo) return;    // nothing of the range in this wavefront: it touches nothing
     }
+    uint32_t row = e, t_src = 0u;                             // the accumulator row; ACT = 5: the traced turn the block starts from
+    if constexpr (ACT == 5) {                                 // block = (turn, entry) of the run: wave-uniform
+        t_src = e / a.n; e -= t_src * a.n;
+        if (t_src >= (uint32_t)__builtin_amdgcn_readfirstlane(a.run_out[e].x)) return;   // a turn nobody played: it touches nothing
+        row = t_src * a.n_all + e;
+    }
     const bool valid = r_in < r_hi - r_lo;
     const uint32_t r = r_lo + (valid ? r_in : 0u);
-    const uint64_t room = uniform_u64(a.rooms[e]), key = uniform_u64(a.keys[e]);
-    const uint32_t turn0 = (uint32_t)__builtin_amdgcn_readfirstlane(a.turns[e]);
+    uint64_t room = 0;
+    if constexpr (ACT != 5) room = uniform_u64(a.rooms[e]);
+    const uint64_t key = uniform_u64(a.keys[e]);
+    const uint32_t turn0 = (uint32_t)__builtin_amdgcn_readfirstlane(a.turns[e]) + (ACT == 5 ? t_src + 1u : 0u);
     uint32_t w[L::WORDS];
-    load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
-    if constexpr (ACT != 0)
+    if constexpr (ACT == 5) roll_load_trace<L::WORDS>(a, t_src, e, w);
+    else load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+    if constexpr (ACT != 0 && ACT != 5)
         if (!roll_act_ww<NB>(sg, tables, a, e, r_in, w)) return;
     const uint64_t g = key + r;
     const uint32_t rk = room_key_from(a.seed_key, g);
@@ -361,7 +397,7 @@ __device__ __forceinline__ void roll_ww(const SegDev &sg, const DevTable *__rest
         const uint32_t subj = (uint32_t)__builtin_amdgcn_readfirstlane(a.subjects[e]) - 1u;
         roll_keep(a, e, r_in, valid ? (l.win_mask >> subj) & 1u : 0u);
     }
-    roll_reduce<NB>(l, valid, score, part, h_end, h_score, a.acc + (size_t)e * ROLL_STRIDE);
+    roll_reduce<NB>(l, valid, score, part, h_end, h_score, a.acc + (size_t)row * ROLL_STRIDE);
 }
 
 template <int NB, int GENERIC, int ACT>
@@ -375,12 +411,21 @@ __device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__rest
         const uint32_t r_first = (uint32_t)__builtin_amdgcn_readfirstlane(r_in);
         if (r_lo > r_hi || r_first >= r_hi - r_lo) return;    // nothing of the range in this wavefront: it touches nothing
     }
+    uint32_t row = e, t_src = 0u;                             // the accumulator row; ACT = 5: the traced turn the block starts from
+    if constexpr (ACT == 5) {                                 // block = (turn, entry) of the run: wave-uniform
+        t_src = e / a.n; e -= t_src * a.n;
+        if (t_src >= (uint32_t)__builtin_amdgcn_readfirstlane(a.run_out[e].x)) return;   // a turn nobody played: it touches nothing
+        row = t_src * a.n_all + e;
+    }
     const bool valid = r_in < r_hi - r_lo;
     const uint32_t r = r_lo + (valid ? r_in : 0u);
-    const uint64_t room = uniform_u64(a.rooms[e]), key = uniform_u64(a.keys[e]);
-    const uint32_t turn0 = (uint32_t)__builtin_amdgcn_readfirstlane(a.turns[e]);
+    uint64_t room = 0;
+    if constexpr (ACT != 5) room = uniform_u64(a.rooms[e]);
+    const uint64_t key = uniform_u64(a.keys[e]);
+    const uint32_t turn0 = (uint32_t)__builtin_amdgcn_readfirstlane(a.turns[e]) + (ACT == 5 ? t_src + 1u : 0u);
     uint32_t w[L::WORDS];
-    load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+    if constexpr (ACT == 5) roll_load_trace<L::WORDS>(a, t_src, e, w);
+    else load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
     const uint64_t g = key + r;
     const uint32_t rk = room_key_from(a.seed_key, g);
     const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
@@ -390,7 +435,7 @@ __device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__rest
     const uint32_t phase0 = __builtin_amdgcn_readfirstlane(sg.phase0_idx);
     TT<NB> s;
     L::unpack(w, s);
-    if constexpr (ACT != 0)
+    if constexpr (ACT != 0 && ACT != 5)
         if (!roll_act_tt<NB>(sg, tables, a, e, r_in, s)) return;
     if constexpr (ACT >= 2) {
         const uint32_t seat = (uint32_t)__builtin_amdgcn_readfirstlane(a.seats[e]);
@@ -429,7 +474,7 @@ __device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__rest
         for (int i = 0; i < NB; i++) x = (uint32_t)i == subj ? score[i] : x;   // static indices: no scratch
         roll_keep(a, e, r_in, x);
     }
-    roll_reduce<NB>(l, valid, score, part, h_end, h_score, a.acc + (size_t)e * ROLL_STRIDE);
+    roll_reduce<NB>(l, valid, score, part, h_end, h_score, a.acc + (size_t)row * ROLL_STRIDE);
 }
 
 // one wavefront per block = one entry's 64 replicas; its action queue (WaveLdsLow) is the block's dynamic LDS (none for
@@ -516,6 +561,19 @@ hipError_t rollout_launch_form(const ge_batch *b, hipStream_t s, const RolloutAr
     const dim3 grid(base.n * base.waves);                   // <= 2^26 blocks (n * R <= 2^26)
     const uint32_t kind = b->segs[base.seg].dev.kind;
     return b->generic ? rollout_launch<1, ACT>(kind, grid, s, b, a) : rollout_launch<0, ACT>(kind, grid, s, b, a);
+}
+
+// an entry's accumulator words as its ge_rollout_stats; turn_end = its first turn + max_turns
+static void rollout_stats_from(const unsigned long long *h, uint32_t n_rollouts, uint64_t turn_end, ge_rollout_stats &out) {
+    memset(&out, 0, sizeof out);
+    out.summary.rooms = n_rollouts;
+    out.summary.finished = h[0]; out.summary.village_wins = h[1]; out.summary.wolf_wins = h[2]; out.summary.alive_players = h[3];
+    out.summary.sum_end_turn = h[4];
+    for (int j = 0; j < 16; j++) { out.summary.end_turn_hist[j] = h[5 + j]; out.summary.score_hist[j] = h[21 + j]; }
+    out.summary.checksum = h[37];
+    out.summary.turn = turn_end;
+    out.summary.games_recycled = h[38];
+    for (int j = 0; j < 12; j++) { out.seat_alive[j] = h[39 + j]; out.seat_wins[j] = h[51 + j]; out.seat_score[j] = h[63 + j]; }
 }
 
 static int rollout_rooms_impl(ge_batch *b, const RollRequest &r) {
@@ -616,17 +674,7 @@ static int rollout_rooms_impl(ge_batch *b, const RollRequest &r) {
             const uint64_t k = c0 + order[i];
             if (cmp) memcpy(&r.cmp[k], host + o.cmp + sizeof(ge_compare_stats) * (size_t)i, sizeof(ge_compare_stats));
             if (act && h_st[i] != GE_OK) continue;               // a refused entry's record is left as it is
-            const unsigned long long *h = h_acc + (size_t)ROLL_STRIDE * i;
-            ge_rollout_stats &out = r.out[k];
-            memset(&out, 0, sizeof out);
-            out.summary.rooms = r.n_rollouts;
-            out.summary.finished = h[0]; out.summary.village_wins = h[1]; out.summary.wolf_wins = h[2]; out.summary.alive_players = h[3];
-            out.summary.sum_end_turn = h[4];
-            for (int j = 0; j < 16; j++) { out.summary.end_turn_hist[j] = h[5 + j]; out.summary.score_hist[j] = h[21 + j]; }
-            out.summary.checksum = h[37];
-            out.summary.turn = (uint64_t)r.turns[k] + r.max_turns;
-            out.summary.games_recycled = h[38];
-            for (int j = 0; j < 12; j++) { out.seat_alive[j] = h[39 + j]; out.seat_wins[j] = h[51 + j]; out.seat_score[j] = h[63 + j]; }
+            rollout_stats_from(h_acc + (size_t)ROLL_STRIDE * i, r.n_rollouts, (uint64_t)r.turns[k] + r.max_turns, r.out[k]);
         }
     }
     return first_bad;

@@ -1026,3 +1026,4 @@ void ge_batch_destroy(ge_batch *b) {
 #include "ge_compare.inl"       // behind ge_playout.inl: paired comparison of playout entries (ge_batch_rollout_compare)
 #include "ge_run.inl"           // behind ge_compare.inl: listed rooms played on until a person is needed (ge_batch_run_rooms)
 #include "ge_run_playout.inl"   // behind ge_run.inl: the same with playout seats (ge_batch_run_rooms_playout)
+#include "ge_timeline.inl"      // behind ge_run_playout.inl: a run-on with a forecast of every turn (ge_batch_run_rooms_forecast)

@@ -635,6 +635,73 @@ napi_value RunRoomsPlayout(napi_env env, napi_callback_info info) {
     return out;
 }
 
+// runRoomsForecast(batch, rooms: BigUint64Array, keys: BigUint64Array, turns: Uint32Array, forecastKeys: BigUint64Array, seats:
+// Uint32Array, nRollouts, playoutMaxTurns, seed: BigInt, maxTurns, until: GE_RUN_UNTIL_* bits): runRooms's result (with views) plus
+// stats: BigUint64Array of rooms.length x (maxTurns + 1) x 77 - runRooms with the forecast of every turn it played
+// (ge_batch_run_rooms_forecast, POLICY.md §3i); entry k's point p is at (k * (maxTurns + 1) + p) * 77, filled up to played[k] (zero
+// above).  Synchronous; GE_BUSY from batch_arg.
+napi_value RunRoomsForecast(napi_env env, napi_callback_info info) {
+    size_t argc = 11;
+    napi_value argv[11];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
+    if (!b || argc < 11) return throw_status(env, GE_ERR_ARG, "runRoomsForecast");
+    napi_typedarray_type tt[5];
+    size_t len[5];
+    void *data[5];
+    for (int k = 0; k < 5; k++) {
+        napi_value ab;
+        size_t off;
+        if (napi_get_typedarray_info(env, argv[1 + k], &tt[k], &len[k], &data[k], &ab, &off) != napi_ok)
+            return throw_status(env, GE_ERR_ARG, "runRoomsForecast", "typed arrays expected");
+    }
+    if (tt[0] != napi_biguint64_array || tt[1] != napi_biguint64_array || tt[2] != napi_uint32_array || tt[3] != napi_biguint64_array ||
+        tt[4] != napi_uint32_array || len[0] != len[1] || len[1] != len[2] || len[2] != len[3] || len[3] != len[4])
+        return throw_status(env, GE_ERR_ARG, "runRoomsForecast", "BigUint64Array x 2, Uint32Array, BigUint64Array, Uint32Array of equal length");
+    uint32_t n_rollouts = 0, pmax = 0, max_turns = 0, until = 0;
+    uint64_t seed = 0;
+    bool lossless = true;
+    if (napi_get_value_uint32(env, argv[6], &n_rollouts) != napi_ok || napi_get_value_uint32(env, argv[7], &pmax) != napi_ok ||
+        napi_get_value_bigint_uint64(env, argv[8], &seed, &lossless) != napi_ok || napi_get_value_uint32(env, argv[9], &max_turns) != napi_ok ||
+        napi_get_value_uint32(env, argv[10], &until) != napi_ok)
+        return throw_status(env, GE_ERR_ARG, "runRoomsForecast", "nRollouts, playoutMaxTurns (numbers), seed (BigInt), maxTurns, until (numbers) expected");
+    const size_t n = len[0];
+    // the library refuses a call past its caps (after its entry checks): no buffers for it (ArrayBuffers are created zero-filled)
+    const size_t slots = (max_turns <= 4096u && (uint64_t)n * max_turns <= (1ull << 20)) ? n * max_turns : 0;
+    const size_t points = (max_turns <= 4096u && (uint64_t)n * (max_turns + 1u) <= (1ull << 16)) ? n * (max_turns + 1u) : 0;
+    const size_t words = sizeof(ge_rollout_stats) / 8;
+    void *pl = nullptr, *sp = nullptr, *ev = nullptr, *vw = nullptr, *fs = nullptr;
+    napi_value pbuf, sbuf, ebuf, vbuf, fbuf, parr, sarr, farr, out;
+    NAPI_OK(napi_create_arraybuffer(env, n * sizeof(uint32_t), &pl, &pbuf));
+    NAPI_OK(napi_create_arraybuffer(env, n * sizeof(uint32_t), &sp, &sbuf));
+    NAPI_OK(napi_create_arraybuffer(env, slots * sizeof(ge_turn_event), &ev, &ebuf));
+    NAPI_OK(napi_create_arraybuffer(env, slots * sizeof(ge_room_view), &vw, &vbuf));
+    NAPI_OK(napi_create_arraybuffer(env, points * sizeof(ge_rollout_stats), &fs, &fbuf));
+    // an empty list: N-API may give no data pointer for an empty buffer, and the library refuses forecast_keys or stats NULL before
+    // it answers n == 0 - neither is read or written then
+    static const uint64_t no_keys = 0;
+    static ge_rollout_stats no_stats;
+    if (!data[3]) data[3] = const_cast<uint64_t *>(&no_keys);
+    if (!fs) fs = &no_stats;
+    const int st = ge_batch_run_rooms_forecast(b, n, static_cast<const uint64_t *>(data[0]), static_cast<const uint64_t *>(data[1]),
+                                               static_cast<const uint32_t *>(data[2]), max_turns, until, static_cast<const uint64_t *>(data[3]),
+                                               static_cast<const uint32_t *>(data[4]), n_rollouts, pmax, seed, static_cast<uint32_t *>(pl),
+                                               static_cast<uint32_t *>(sp), static_cast<ge_turn_event *>(ev),
+                                               slots ? static_cast<ge_room_view *>(vw) : nullptr, slots * sizeof(ge_room_view),
+                                               static_cast<ge_rollout_stats *>(fs), points * sizeof(ge_rollout_stats));
+    if (st != GE_OK) return throw_status(env, st, "runRoomsForecast");
+    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, n, pbuf, 0, &parr));
+    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, n, sbuf, 0, &sarr));
+    NAPI_OK(napi_create_typedarray(env, napi_biguint64_array, points * words, fbuf, 0, &farr));
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_set_named_property(env, out, "played", parr));
+    NAPI_OK(napi_set_named_property(env, out, "stopped", sarr));
+    NAPI_OK(napi_set_named_property(env, out, "events", ebuf));
+    NAPI_OK(napi_set_named_property(env, out, "views", vbuf));
+    NAPI_OK(napi_set_named_property(env, out, "stats", farr));
+    return out;
+}
+
 bool is_nullish(napi_env env, napi_value v) {
     napi_valuetype t;
     return napi_typeof(env, v, &t) == napi_ok && (t == napi_null || t == napi_undefined);
@@ -1015,6 +1082,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"stepRoomsPlayout", nullptr, StepRoomsPlayout, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"runRooms", nullptr, RunRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"runRoomsPlayout", nullptr, RunRoomsPlayout, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"runRoomsForecast", nullptr, RunRoomsForecast, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"readRoomsAt", nullptr, ReadRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"rollout", nullptr, Rollout, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"writeRoomsAt", nullptr, WriteRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},

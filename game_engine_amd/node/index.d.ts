@@ -89,6 +89,14 @@ export class RoomBatch {
                   playoutKeys: ArrayLike<number | bigint>, nRollouts: number, playoutMaxTurns?: number, seed?: bigint | number,
                   fullView?: boolean, maxTurns?: number, until?: RunUntil[] | RunUntil | number, views?: boolean, halving?: boolean):
     { played: Uint32Array; stopped: Uint32Array; events: TurnEvent[][]; views: RoomState[][] | null; decided: number[][] };
+  /** runRooms with a forecast of every turn it played (POLICY.md §3i): runRooms's result (with views) and stats[k][p], p = 0 ..
+   *  played[k]: the 77 rolloutSeats words of room k as it stood at point p (0: before the call; p: after its turn p - 1) under
+   *  (forecastKeys[k], turns[k] + p, seats[k], no actions; nRollouts, playoutMaxTurns, seed).  seats null: the full view.
+   *  Synchronous; GE_BUSY while an async step() is in flight. */
+  runRoomsForecast(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>,
+                   forecastKeys: ArrayLike<number | bigint>, nRollouts: number, playoutMaxTurns?: number, seats?: ArrayLike<number> | null,
+                   seed?: bigint | number, maxTurns?: number, until?: RunUntil[] | RunUntil | number):
+    { played: Uint32Array; stopped: Uint32Array; events: TurnEvent[][]; views: RoomState[][]; stats: BigUint64Array[][] };
   /** Playouts of each listed room (replica r of entry k = global room keys[k] + r under seed, default the batch's): rooms.length x 77
    *  words of ge_rollout_stats (41 summary words, then seat_alive, seat_wins, seat_score x 12).  The batch is only read. */
   rolloutRooms(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, nRollouts: number,

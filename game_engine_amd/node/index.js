@@ -663,6 +663,31 @@ class RoomBatch {
     }
     return { played: r.played, stopped: r.stopped, events, views: states, decided };
   }
+  /** runRooms with a forecast of every turn it played (twin of the Python RoomBatch.run_rooms_forecast, POLICY.md §3i): played,
+   * stopped, events and views are runRooms's for the same (rooms, keys, turns, maxTurns, until), and stats[k][p], p = 0 ..
+   * played[k], is a BigUint64Array of the 77 rolloutSeats words of room k as it stood at point p - point 0 before the call, point p
+   * after its turn p - 1 - under (forecastKeys[k], turns[k] + p, seats[k], no actions; nRollouts, playoutMaxTurns, seed).  seats
+   * null: the full view for every entry; seed undefined: the batch's.  All-or-nothing: runRooms's checks, then 1 <= nRollouts <=
+   * 2^20, playoutMaxTurns <= 4096, n * (maxTurns + 1) <= 2^16, n * (maxTurns + 1) * nRollouts <= 2^26, seats within their rooms'
+   * player counts, turns[k] + maxTurns + playoutMaxTurns within 0xFFFFFFFF.  Synchronous; GE_BUSY while an async step() is in flight. */
+  runRoomsForecast(rooms, keys, turns, forecastKeys, nRollouts, playoutMaxTurns = 1024, seats = null, seed, maxTurns = 64, until = ['person', 'end']) {
+    const bits = runUntilBits(until);
+    const r = addon.runRoomsForecast(this.handle, BigUint64Array.from(rooms, (x) => BigInt(x)), BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))),
+                                     Uint32Array.from(turns), BigUint64Array.from(forecastKeys, (k) => BigInt.asUintN(64, BigInt(k))),
+                                     seats == null ? new Uint32Array(rooms.length) : Uint32Array.from(seats), nRollouts, playoutMaxTurns,
+                                     seed === undefined ? this.seed : BigInt.asUintN(64, BigInt(seed)), maxTurns, bits);
+    const events = [], states = [], stats = [];
+    for (let k = 0; k < rooms.length; k++) {
+      const ev = [], vw = [], fc = [];
+      for (let t = 0; t < r.played[k]; t++) {
+        ev.push(decodeEvent(r.events, (k * maxTurns + t) * EVENT_SIZE));
+        vw.push(decodeRoom(this.tableOf(Number(rooms[k])), r.views, (k * maxTurns + t) * VIEW.size));
+      }
+      for (let p = 0; p <= r.played[k]; p++) fc.push(r.stats.subarray(77 * (k * (maxTurns + 1) + p), 77 * (k * (maxTurns + 1) + p + 1)));
+      events.push(ev); states.push(vw); stats.push(fc);
+    }
+    return { played: r.played, stopped: r.stopped, events, views: states, stats };
+  }
   /** Playouts (twin of the Python RoomBatch.rollout_rooms): entry k is played nRollouts times from room rooms[k] as it stands,
    * replica r as global room keys[k] + r (mod 2^64) under `seed` (default: the batch's) at turns turns[k] .. turns[k] + maxTurns - 1,
    * every seat played by the policy and a finished game left finished.  Returns a BigUint64Array of rooms.length x 77 words

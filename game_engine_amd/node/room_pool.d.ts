@@ -13,7 +13,8 @@ export class RoomPoolService {
   continueRoom(threadId: string, items?: { id: string; type: string }[]): Promise<TurnResult>;
   /** As RoomService.runRoom, from the thread's pool slot. */
   runRoom(threadId: string, maxTurns?: number, until?: RunUntil[], items?: { id: string; type: string }[], options?: RunOptions): Promise<RunResult>;
-  /** runRoom for many threads, in order: one runRooms call per chunk touched; a thread may be named once.  items[j]: thread j's items. */
+  /** runRoom for many threads, in order: one runRooms call per chunk touched; a thread may be named once.  items[j]: thread j's items.
+   *  options.forecast: one runRoomsForecast call per chunk touched instead, and every result gains forecasts (options.seats[j]: thread j's seat). */
   runRooms(threadIds: string[], maxTurns?: number, until?: RunUntil[], items?: ({ id: string; type: string }[] | undefined)[],
            options?: RunOptions): Promise<RunResult[]>;
   handleMessage(threadId: string, text: string, items?: { id: string; type: string }[]): Promise<MessageResult>;

@@ -11,7 +11,8 @@
  */
 const { GameTable, RoomBatch, RoomLog, decodeRoom, turnToolCalls, uiToolCalls } = require('./index.js');
 const { roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, adviseCandidates, adviseSeat, runRollouts, adviseOutput,
-        seatForecastOutput, checkForecastSeat, checkView, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, forecastKey, forecastSeed, checkRunArgs, checkRunThread, runTurn, runOutput } = require('./room_service.js');
+        seatForecastOutput, checkForecastSeat, checkView, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, forecastKey, forecastSeed, checkRunArgs, checkRunThread, runTurn, runOutput,
+        checkRunForecast, runForecastPerCall, runForecasts } = require('./room_service.js');
 const popcount = (m) => { let c = 0; for (let x = m; x; x &= x - 1) c++; return c; };
 const M = require('./messages.js');
 
@@ -203,7 +204,10 @@ class RoomPoolService {
    * runs.  options { playout: true }: threads with playout seats are run too - a chunk holding one takes one RoomBatch.runRoomsPlayout
    * call (POLICY.md §3g; mask 0 for its other threads; more calls only where the playouts of one turn would pass the call's cap).
    * Every chunk's call is made before any turn is folded: if one of them fails (a device error), the threads of the chunks
-   * already run have moved on the device while no thread's turn or log has - such a service is to be closed, not continued. */
+   * already run have moved on the device while no thread's turn or log has - such a service is to be closed, not continued.
+   * options { forecast: true, rollouts, maxTurns, seat | seats }: every thread's result gains forecasts (RoomService.runRoom's;
+   * seats[j]: the seat thread j's are seen from, seat: one seat for all), from one RoomBatch.runRoomsForecast call per chunk touched
+   * (POLICY.md §3i; more calls only where one call's points would pass its caps); threads with playout seats are refused. */
   runRooms(threadIds, maxTurns = 64, until = ['person', 'end'], items, options) {
     return this._serial(() => {
       const bits = checkRunArgs(maxTurns, until);
@@ -212,6 +216,10 @@ class RoomPoolService {
       const rooms = Array.from(threadIds, (t) => this._room(t));
       const its = items || [];
       if (items && its.length !== rooms.length) throw new RangeError('runRooms: threadIds and items differ in length');
+      const seats = options && options.forecast && Array.isArray(options.seats) ? options.seats : null;   // per thread; else options.seat for all
+      if (seats && seats.length !== rooms.length) throw new RangeError('runRooms: threadIds and seats differ in length');
+      const fcs = rooms.map((room, j) => checkRunForecast(threadIds[j], room, maxTurns, seats ? Object.assign({}, options, { seat: seats[j] }) : options));
+      const fc = fcs[0] || null;
       rooms.forEach((room, j) => {
         checkRunThread(threadIds[j], room, playout);
         if (room.turn + maxTurns + (room.playoutMask ? this.playoutMaxTurns - 1 : 0) > 0xFFFFFFFF) throw new RangeError(`thread ${threadIds[j]}: the turn counter would overflow`);
@@ -221,7 +229,7 @@ class RoomPoolService {
         if (!byChunk.has(room.chunk)) byChunk.set(room.chunk, []);
         byChunk.get(room.chunk).push(j);
       });
-      const perCall = Math.max(1, Math.floor((1 << 20) / maxTurns));   // the call's cap on n x maxTurns
+      const perCall = fc ? runForecastPerCall(maxTurns, fc.rollouts) : Math.max(1, Math.floor((1 << 20) / maxTurns));   // the call's cap on n x maxTurns
       const got = new Array(rooms.length);
       for (const [chunk, all] of byChunk) {
         const withBots = all.some((j) => rooms[j].playoutMask);
@@ -231,16 +239,20 @@ class RoomPoolService {
         for (const [a, b] of parts) {
           const js = all.slice(a, b);
           const slots = js.map((j) => rooms[j].slot), keys = js.map((j) => rooms[j].key), turns = js.map((j) => rooms[j].turn);
-          const r = withBots
+          const r = fc
+            ? chunk.runRoomsForecast(slots, keys, turns, keys.map((k) => forecastKey(k)), fc.rollouts, fc.maxTurns, js.map((j) => fcs[j].seat || 0),
+                                     forecastSeed(this.seed), maxTurns, bits)
+            : withBots
             ? chunk.runRoomsPlayout(slots, keys, turns, js.map((j) => rooms[j].playoutMask), keys.map((k) => forecastKey(k)), this.playoutRollouts,
                                     this.playoutMaxTurns, forecastSeed(this.seed), this.playoutFull, maxTurns, bits, true, this.playoutHalving)
             : chunk.runRooms(slots, keys, turns, maxTurns, bits);
-          js.forEach((j, k) => { got[j] = { events: r.events[k], views: r.views[k], stopped: r.stopped[k] }; });
+          js.forEach((j, k) => { got[j] = { events: r.events[k], views: r.views[k], stopped: r.stopped[k], stats: fc ? r.stats[k] : null }; });
         }
       }
       return rooms.map((room, j) => {
+        const forecasts = fc ? runForecasts(room.table, room.names, threadIds[j], room.turn, fcs[j], got[j].stats) : undefined;
         room.turn += got[j].events.length;
-        return runOutput(got[j].events.map((ev, t) => runTurn(this._finish(room, got[j].views[t], ev, its[j]))), got[j].stopped);
+        return runOutput(got[j].events.map((ev, t) => runTurn(this._finish(room, got[j].views[t], ev, its[j]))), got[j].stopped, forecasts);
       });
     });
   }

@@ -26,8 +26,17 @@ export interface TurnResult { state: AgentStateView; toolCalls: ToolCall[]; uiCa
 export type RunUntil = 'person' | 'end' | 'phase';
 /** runRoom / runRooms options.  playout: run threads with playout seats too, by one runRoomsPlayout call (POLICY.md §3g); without
  *  it such a thread is refused. */
-export interface RunOptions { playout?: boolean; }
-export interface RunResult { turns: TurnResult[]; played: number; stopped: RunUntil[]; }
+export interface RunOptions {
+  playout?: boolean;
+  /** a win-odds timeline of the run (POLICY.md §3i): the result gains forecasts, one Forecast per point 0 .. played, each what
+   *  forecast(threadId, rollouts, maxTurns, seat) would have resolved at that moment; a thread with playout seats is refused */
+  forecast?: boolean;
+  /** forecast's nRollouts (default 4096), maxTurns (default 1024) and seat (default: the full view) */
+  rollouts?: number; maxTurns?: number; seat?: number;
+  /** RoomPoolService.runRooms: the seat of each thread's forecasts (instead of one seat for all) */
+  seats?: (number | undefined)[];
+}
+export interface RunResult { turns: TurnResult[]; played: number; stopped: RunUntil[]; forecasts?: Forecast[]; }
 /** How a thread ends from where it stands, over `rollouts` playouts (JSON integers: divide by rollouts for odds). */
 export interface Forecast {
   threadId: string; turn: number; rollouts: number; maxTurns: number;

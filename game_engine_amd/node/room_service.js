@@ -229,7 +229,34 @@ function runTurn(out) {
   out.state = Object.assign({}, st, JSON.parse(JSON.stringify({ playerActions: st.playerActions, phase_history: st.phase_history, game_notes: st.game_notes })));
   return out;
 }
-function runOutput(turns, stopped) { return { turns, played: turns.length, stopped: runUntilNames(stopped) }; }
+function runOutput(turns, stopped, forecasts) {
+  const out = { turns, played: turns.length, stopped: runUntilNames(stopped) };
+  if (forecasts) out.forecasts = forecasts;
+  return out;
+}
+const TIMELINE_MAX_POINTS = 1 << 16, TIMELINE_CAP = 2 ** 26;    // ge_batch_run_rooms_forecast: n x (maxTurns + 1) per call, and x nRollouts
+/** runRoom's forecast options { forecast: true, rollouts = 4096, maxTurns = 1024, seat } (POLICY.md §3i; twin of room_service.py
+ * check_run_forecast), before anything runs; returns null without `forecast`. */
+function checkRunForecast(threadId, room, maxTurns, options) {
+  if (!options || !options.forecast) return null;
+  const f = { rollouts: options.rollouts === undefined ? 4096 : options.rollouts, maxTurns: options.maxTurns === undefined ? 1024 : options.maxTurns,
+              seat: options.seat === null ? undefined : options.seat };
+  checkForecastArgs(f.rollouts, f.maxTurns);
+  checkForecastSeat(threadId, room.names.length, f.seat);
+  if (room.playoutMask) throw new RangeError(`thread ${threadId} has playout seats: runRoom gives no forecasts of a run with playout bots`);
+  if ((maxTurns + 1) * f.rollouts > TIMELINE_CAP) throw new RangeError(`(maxTurns + 1) x rollouts must be at most ${TIMELINE_CAP}`);
+  if (room.turn + maxTurns + f.maxTurns > 0xFFFFFFFF) throw new RangeError(`thread ${threadId}: the turn counter would overflow`);
+  return f;
+}
+/** The most threads one runRoomsForecast call takes under the library's caps. */
+function runForecastPerCall(maxTurns, nRollouts) {
+  const pts = maxTurns + 1;
+  return Math.max(1, Math.min(Math.floor((1 << 20) / maxTurns), Math.floor(TIMELINE_MAX_POINTS / pts), Math.floor(TIMELINE_CAP / (pts * nRollouts))));
+}
+/** runRoom's "forecasts": element p is forecast()'s JSON of the thread as it stood after p of the call's turns. */
+function runForecasts(table, names, threadId, turn, f, stats) {
+  return stats.map((w, p) => seatForecastOutput(table, names, threadId, turn + p, f.rollouts, f.maxTurns, f.seat, w));
+}
 
 class RoomService {
   /** playoutRollouts / playoutMaxTurns / playoutView: how the playout bots of threads created with playoutSeats choose
@@ -375,13 +402,27 @@ class RoomService {
    * limit), and the thread's turn and panel end where `played` calls of continueRoom would have left them.  A thread with playout
    * seats or bad arguments are refused (RangeError) before anything runs; with options { playout: true } a thread with playout seats
    * is run by one RoomBatch.runRoomsPlayout call (POLICY.md §3g) under the keys, seed and options continueRoom gives its playout
-   * bots.  Every turn's state carries its own copy of the thread's log (runTurn): host work that grows with the log, per turn. */
+   * bots.  Every turn's state carries its own copy of the thread's log (runTurn): host work that grows with the log, per turn.
+   * options { forecast: true, rollouts, maxTurns, seat }: a win-odds timeline of the run (POLICY.md §3i), from one
+   * RoomBatch.runRoomsForecast call instead - the result gains forecasts, played + 1 objects: element p is exactly what
+   * forecast(threadId, rollouts, maxTurns, seat) would have resolved after p of the call's turns, every point under the same keys
+   * and seed.  The options are checked as forecast checks them and a thread with playout seats is refused, before anything runs. */
   runRoom(threadId, maxTurns = 64, until = ['person', 'end'], items, options) {
     const room = this.rooms.get(threadId);
     if (!room) return Promise.reject(new Error(`unknown thread ${threadId}`));
     return this._serial(room, () => {
       const bits = checkRunArgs(maxTurns, until);
       checkRunThread(threadId, room, !!(options && options.playout));
+      const f = checkRunForecast(threadId, room, maxTurns, options);
+      if (f) {
+        const turn = room.turn;
+        const q = room.batch.runRoomsForecast([0], [room.key], [turn], [forecastKey(room.key)], f.rollouts, f.maxTurns, [f.seat || 0],
+                                              forecastSeed(this.seed), maxTurns, bits);
+        room.turn += q.played[0];
+        room.batch.setTurn(room.turn);
+        return runOutput(q.events[0].map((ev, t) => runTurn(this._finish(room, q.views[0][t], ev, items))), q.stopped[0],
+                         runForecasts(room.table, room.names, threadId, turn, f, q.stats[0]));
+      }
       const r = room.playoutMask
         ? room.batch.runRoomsPlayout([0], [room.key], [room.turn], [room.playoutMask], [forecastKey(room.key)], this.playoutRollouts,
                                      this.playoutMaxTurns, forecastSeed(this.seed), this.playoutFull, maxTurns, bits, true,
@@ -465,7 +506,7 @@ class RoomService {
           let out;
           if (req.method === 'POST' && req.url === '/rooms') out = this.createRoom(msg);
           else if (req.method === 'POST' && req.url === '/continue') out = await this.continueRoom(msg.threadId, msg.items);
-          else if (req.method === 'POST' && req.url === '/run') out = await this.runRoom(msg.threadId, msg.maxTurns, msg.until, msg.items, { playout: !!msg.playout });
+          else if (req.method === 'POST' && req.url === '/run') out = await this.runRoom(msg.threadId, msg.maxTurns, msg.until, msg.items, Object.assign({ playout: !!msg.playout }, msg.forecast && typeof msg.forecast === 'object' ? Object.assign({ forecast: true }, msg.forecast) : { forecast: !!msg.forecast }));
           else if (req.method === 'POST' && req.url === '/message') out = await this.handleMessage(msg.threadId, msg.text, msg.items);
           else if (req.method === 'POST' && req.url === '/action') out = await this.humanAction(msg.threadId, msg.playerId, msg.choice);
           else if (req.method === 'POST' && req.url === '/close') out = { closed: await this.close(msg.threadId) };
@@ -480,4 +521,5 @@ class RoomService {
 }
 
 module.exports = { RoomService, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput,
-                   adviseCandidates, adviseSeat, runRollouts, adviseOutput, seatForecastOutput, checkForecastSeat, checkView, checkRunArgs, checkRunThread, runTurn, runOutput };
+                   adviseCandidates, adviseSeat, runRollouts, adviseOutput, seatForecastOutput, checkForecastSeat, checkView, checkRunArgs, checkRunThread, runTurn, runOutput,
+                   checkRunForecast, runForecastPerCall, runForecasts };

@@ -18,9 +18,9 @@ import numpy as np
 
 from . import messages as M
 from .room_service import (PLAYOUT_CAP, RolloutRequest, adopted_output, advise_candidates, advise_output, advise_seat,
-                           check_forecast_args, check_forecast_seat, check_playout_options, check_run_args, check_run_thread, check_view,
-                           forecast_key, forecast_seed, playout_mask, playout_max_cands, prepare_adoption, room_index_of, run_output,
-                           run_rollouts, run_turn, seat_forecast_output)
+                           check_forecast_args, check_forecast_seat, check_playout_options, check_run_args, check_run_forecast, check_run_thread, check_view,
+                           forecast_key, forecast_seed, playout_mask, playout_max_cands, prepare_adoption, room_index_of, run_forecast_per_call,
+                           run_forecasts, run_output, run_rollouts, run_turn, seat_forecast_output)
 from .stepper import GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, load_dsl_by_gamename, slot_values
 from .toolcalls import WW_IS_ALIVE, RoomLog, turn_tool_calls
 from .ui_script import ui_tool_calls
@@ -254,12 +254,16 @@ class RoomPoolService:
         return [self._finish(room, afters[j], events[j], items[j]) for j, room in enumerate(rooms)]
 
     def run_room(self, thread_id: str, max_turns: int = 64, until=("person", "end"),
-                 items: Optional[List[Dict[str, Any]]] = None, playout: bool = False) -> Dict[str, Any]:
-        """As RoomService.run_room (same turns and output), from the thread's pool slot."""
-        return self.run_rooms([thread_id], max_turns, until, None if items is None else [items], playout)[0]
+                 items: Optional[List[Dict[str, Any]]] = None, playout: bool = False, forecast: bool = False, forecast_rollouts: int = 4096,
+                 forecast_max_turns: int = 1024, forecast_seat: Optional[int] = None) -> Dict[str, Any]:
+        """As RoomService.run_room (same turns, forecasts and output), from the thread's pool slot."""
+        return self.run_rooms([thread_id], max_turns, until, None if items is None else [items], playout, forecast, forecast_rollouts,
+                              forecast_max_turns, None if forecast_seat is None else [forecast_seat])[0]
 
     def run_rooms(self, thread_ids: Sequence[str], max_turns: int = 64, until=("person", "end"),
-                  items: Optional[Sequence[Optional[List[Dict[str, Any]]]]] = None, playout: bool = False) -> List[Dict[str, Any]]:
+                  items: Optional[Sequence[Optional[List[Dict[str, Any]]]]] = None, playout: bool = False, forecast: bool = False,
+                  forecast_rollouts: int = 4096, forecast_max_turns: int = 1024,
+                  forecast_seats: Optional[Sequence[Optional[int]]] = None) -> List[Dict[str, Any]]:
         """Play many threads on, each until a person is needed in it (RoomService.run_room's conditions and output, in order):
         one RoomBatch.run_rooms call per chunk touched, every thread under its own key and from its own turn.  items[j]: thread
         j's canvas items.  A thread may be named once (ValueError); unknown threads (KeyError), threads with playout seats and
@@ -268,7 +272,11 @@ class RoomPoolService:
         only where the playouts of one turn would pass the call's cap), under the keys, seed and options continue_room gives
         its playout bots.  Every chunk's call is made before any turn is folded: if
         one of them raises (a device error), the threads of the chunks already run have moved on the device while no thread's
-        turn or log has - such a service is to be closed, not continued."""
+        turn or log has - such a service is to be closed, not continued.
+        forecast=True: every thread's output gains "forecasts" (RoomService.run_room's; forecast_seats[j]: the seat thread j's
+        are seen from, None: the full view), from one RoomBatch.run_rooms_forecast call per chunk touched (POLICY.md §3i; more
+        calls only where the points of one call would pass its caps); the options are checked as forecasts checks them and a
+        thread with playout seats is refused (ValueError), before anything runs."""
         bits = check_run_args(max_turns, until)
         if len(set(thread_ids)) != len(thread_ids):
             raise ValueError("run_rooms: a thread is named twice")
@@ -276,14 +284,21 @@ class RoomPoolService:
         its = list(items) if items is not None else [None] * len(rooms)
         if len(its) != len(rooms):
             raise ValueError("run_rooms: thread_ids and items differ in length")
-        for tid, room in zip(thread_ids, rooms):
+        fseats = list(forecast_seats) if forecast_seats is not None else [None] * len(rooms)
+        if len(fseats) != len(rooms):
+            raise ValueError("run_rooms: thread_ids and forecast_seats differ in length")
+        for tid, room, fs in zip(thread_ids, rooms, fseats):
             check_run_thread(tid, room, playout)
+            if forecast:
+                check_run_forecast(tid, room, max_turns, forecast_rollouts, forecast_max_turns, fs, room["turn"])
             if int(room["turn"]) + int(max_turns) + (self.playout_max_turns - 1 if room["playout_mask"] else 0) > 0xFFFFFFFF:
                 raise ValueError(f"thread {tid!r}: the turn counter would overflow")
         by_chunk: Dict[int, List[int]] = {}
         for j, room in enumerate(rooms):
             by_chunk.setdefault(id(room["chunk"]), []).append(j)
         per_call = max(1, (1 << 20) // int(max_turns))             # the call's cap on n x max_turns
+        if forecast:
+            per_call = run_forecast_per_call(max_turns, forecast_rollouts)
         got: List[Any] = [None] * len(rooms)
         for all_js in by_chunk.values():
             with_bots = any(rooms[j]["playout_mask"] for j in all_js)
@@ -293,7 +308,12 @@ class RoomPoolService:
                 js = all_js[a:b]
                 chunk, slots, keys = rooms[js[0]]["chunk"], [rooms[j]["slot"] for j in js], [rooms[j]["key"] for j in js]
                 turns = [rooms[j]["turn"] for j in js]
-                if with_bots:
+                stats = None
+                if forecast:
+                    played, stopped, events, views, stats = chunk.run_rooms_forecast(
+                        slots, keys, turns, [forecast_key(k) for k in keys], forecast_rollouts, forecast_max_turns,
+                        seats=[fseats[j] or 0 for j in js], seed=forecast_seed(self.seed), max_turns=max_turns, until=bits)
+                elif with_bots:
                     played, stopped, events, views, _ = chunk.run_rooms_playout(
                         slots, keys, turns, [rooms[j]["playout_mask"] for j in js], [forecast_key(k) for k in keys], self.playout_rollouts,
                         self.playout_max_turns, seed=forecast_seed(self.seed), full_view=self.playout_full, max_turns=max_turns, until=bits,
@@ -301,11 +321,13 @@ class RoomPoolService:
                 else:
                     played, stopped, events, views = chunk.run_rooms(slots, keys, turns, max_turns, bits)
                 for k, j in enumerate(js):
-                    got[j] = (int(played[k]), int(stopped[k]), events[k], views[k])
+                    got[j] = (int(played[k]), int(stopped[k]), events[k], views[k], None if stats is None else stats[k])
         out = []
-        for room, (played, stopped, events, views), it in zip(rooms, got, its):
+        for tid, room, (played, stopped, events, views, stats), it, fs in zip(thread_ids, rooms, got, its, fseats):
+            fc = None if stats is None else run_forecasts(room["table"], room["names"], tid, room["turn"], played, forecast_rollouts,
+                                                          forecast_max_turns, fs, stats)
             room["turn"] += played
-            out.append(run_output([run_turn(self._finish(room, views[t], events[t], it)) for t in range(played)], stopped))
+            out.append(run_output([run_turn(self._finish(room, views[t], events[t], it)) for t in range(played)], stopped, fc))
         return out
 
     def _playout_parts(self, rooms: List[Dict[str, Any]], most: Optional[int] = None) -> List[Tuple[int, int]]:

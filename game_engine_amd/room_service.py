@@ -296,6 +296,35 @@ def check_run_thread(thread_id: str, room: Dict[str, Any], playout: bool = False
                          "(or run it with playout=True)")
 
 
+TIMELINE_MAX_POINTS = 1 << 16                               # ge_batch_run_rooms_forecast: n x (max_turns + 1) per call
+TIMELINE_CAP = 1 << 26                                      # ... and n x (max_turns + 1) x n_rollouts
+
+
+def check_run_forecast(thread_id: str, room: Dict[str, Any], max_turns: int, n_rollouts: int, forecast_max_turns: int,
+                       seat: Optional[int], turn: int) -> None:
+    """run_room's forecast options for one thread standing at `turn` (POLICY.md §3i), before anything runs."""
+    check_forecast_args(n_rollouts, forecast_max_turns)
+    check_forecast_seat(thread_id, len(room["names"]), seat)
+    if room["playout_mask"]:
+        raise ValueError(f"thread {thread_id!r} has playout seats: run_room gives no forecasts of a run with playout bots")
+    if (int(max_turns) + 1) * int(n_rollouts) > TIMELINE_CAP:
+        raise ValueError(f"(max_turns + 1) x forecast_rollouts must be at most {TIMELINE_CAP}")
+    if int(turn) + int(max_turns) + int(forecast_max_turns) > 0xFFFFFFFF:
+        raise ValueError(f"thread {thread_id!r}: the turn counter would overflow")
+
+
+def run_forecast_per_call(max_turns: int, n_rollouts: int) -> int:
+    """The most threads one run_rooms_forecast call takes under the library's caps."""
+    pts = int(max_turns) + 1
+    return max(1, min((1 << 20) // int(max_turns), TIMELINE_MAX_POINTS // pts, TIMELINE_CAP // (pts * int(n_rollouts))))
+
+
+def run_forecasts(table: GameTable, names: List[str], thread_id: str, turn: int, played: int, n_rollouts: int, max_turns: int,
+                  seat: Optional[int], stats) -> List[Dict[str, Any]]:
+    """run_room's "forecasts": element p is forecast()'s JSON of the thread as it stood after p of the call's turns."""
+    return [seat_forecast_output(table, names, thread_id, int(turn) + p, n_rollouts, max_turns, seat, stats[p]) for p in range(int(played) + 1)]
+
+
 def run_turn(out: Dict[str, Any]) -> Dict[str, Any]:
     """One turn's output as run_room keeps it: the state of a continue_room output shares the thread's growing log
     (playerActions, phase_history, game_notes), and here later turns are folded before the caller sees the earlier ones - so
@@ -304,8 +333,8 @@ def run_turn(out: Dict[str, Any]) -> Dict[str, Any]:
     return out
 
 
-def run_output(turns: List[Dict[str, Any]], stopped: int) -> Dict[str, Any]:
-    return {"turns": turns, "played": len(turns), "stopped": run_until_names(stopped)}
+def run_output(turns: List[Dict[str, Any]], stopped: int, forecasts: Optional[List[Dict[str, Any]]] = None) -> Dict[str, Any]:
+    return {"turns": turns, "played": len(turns), "stopped": run_until_names(stopped), **({} if forecasts is None else {"forecasts": forecasts})}
 
 
 class RoomService:
@@ -465,7 +494,8 @@ class RoomService:
         return {"state": state, "toolCalls": calls, "uiCalls": ui}
 
     def run_room(self, thread_id: str, max_turns: int = 64, until=("person", "end"),
-                 items: Optional[List[Dict[str, Any]]] = None, playout: bool = False) -> Dict[str, Any]:
+                 items: Optional[List[Dict[str, Any]]] = None, playout: bool = False, forecast: bool = False, forecast_rollouts: int = 4096,
+                 forecast_max_turns: int = 1024, forecast_seat: Optional[int] = None) -> Dict[str, Any]:
         """Play the thread on until a person is needed: one RoomBatch.run_rooms call (POLICY.md §3f) instead of a continue_room
         per turn.  until: "person" (a human seat of the thread has an action to give), "end" (the game is over), "phase" (the
         turn moved the phase); the first turn is always played, at most max_turns are.  Returns {"turns": [{state, toolCalls,
@@ -474,11 +504,25 @@ class RoomService:
         ([]: the limit), and the thread's turn and panel end where p calls of continue_room would have left them.  A thread
         with playout seats is refused (ValueError) before anything runs, unless playout=True: then it is run by one
         RoomBatch.run_rooms_playout call (POLICY.md §3g) with the keys, seed and options continue_room gives its playout bots.
-        Every turn's state carries its own copy of the thread's log (run_turn): host work that grows with the log, per turn."""
+        Every turn's state carries its own copy of the thread's log (run_turn): host work that grows with the log, per turn.
+        forecast=True: a win-odds timeline of the run (POLICY.md §3i), from one RoomBatch.run_rooms_forecast call instead: the
+        output gains "forecasts", a list of played + 1 objects - element p is exactly what forecast(thread_id, forecast_rollouts,
+        forecast_max_turns, forecast_seat) would have returned after p of the call's turns (element 0: before the call), every
+        point under the same keys and seed, so the difference of two neighbours is that turn's effect on the odds.  The forecast
+        options are checked as forecast checks them, before anything runs; a thread with playout seats is refused (ValueError)."""
         room = self._rooms[thread_id]
         bits = check_run_args(max_turns, until)
         check_run_thread(thread_id, room, playout)
         batch, turn = room["batch"], room["batch"].turn
+        if forecast:
+            check_run_forecast(thread_id, room, max_turns, forecast_rollouts, forecast_max_turns, forecast_seat, turn)
+            played, stopped, events, views, stats = batch.run_rooms_forecast(
+                [0], [room["key"]], [turn], [forecast_key(room["key"])], forecast_rollouts, forecast_max_turns, seats=[forecast_seat or 0],
+                seed=forecast_seed(self.seed), max_turns=max_turns, until=bits)
+            batch.set_turn(turn + int(played[0]))
+            turns = [run_turn(self._finish(room, views[0, t], events[0, t], items)) for t in range(int(played[0]))]
+            return run_output(turns, int(stopped[0]), run_forecasts(room["table"], room["names"], thread_id, turn, int(played[0]), forecast_rollouts,
+                                                                    forecast_max_turns, forecast_seat, stats[0]))
         if room["playout_mask"]:
             played, stopped, events, views, _ = batch.run_rooms_playout(
                 [0], [room["key"]], [turn], [room["playout_mask"]], [forecast_key(room["key"])], self.playout_rollouts, self.playout_max_turns,

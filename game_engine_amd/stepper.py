@@ -404,6 +404,41 @@ class RoomBatch:
                "ge_batch_run_rooms_playout")
         return played, stopped, events, out, decided
 
+    def run_rooms_forecast(self, rooms, keys, turns, forecast_keys, n_rollouts: int, playout_max_turns: int = 1024, seats=None,
+                           seed: Optional[int] = 0, max_turns: int = 64, until=("person", "end")):
+        """run_rooms with a forecast of every turn it played (POLICY.md §3i): (played, stopped, events, views) are run_rooms's for
+        the same (rooms, keys, turns, max_turns, until), and stats, a (n, max_turns + 1, 77) uint64 array, holds for point
+        p = 0 .. played[k] the rollout_seats words of room k as it stood there - point 0 before the call, point p after its turn
+        p - 1 - under (forecast_keys[k], turns[k] + p, seats[k], no actions; n_rollouts, playout_max_turns, seed).  seats None: the
+        full view for every entry; seed None: the batch's seed.  Rows past played[k] are not written (zero here).  All-or-nothing:
+        run_rooms's checks, then 1 <= n_rollouts <= 2^20, playout_max_turns <= 4096, n * (max_turns + 1) <= 2^16, n * (max_turns + 1)
+        * n_rollouts <= 2^26, seats within their rooms' player counts, turns[k] + max_turns + playout_max_turns within 0xFFFFFFFF."""
+        rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        turns = np.ascontiguousarray(turns, dtype=np.uint32)
+        fkeys = np.ascontiguousarray(forecast_keys, dtype=np.uint64)
+        seat_arr = None if seats is None else np.ascontiguousarray(seats, dtype=np.uint32)
+        if not (len(rooms) == len(keys) == len(turns) == len(fkeys)) or (seat_arr is not None and len(seat_arr) != len(rooms)):
+            raise GeError(-1, "run_rooms_forecast: arrays differ in length")
+        bits = run_until_bits(until)
+        if int(max_turns) < 0 or int(max_turns) > 0xFFFFFFFF:   # no uint32 at all (0 and values above the cap go to the library's checks)
+            raise GeError(GE_ERR_ARG, "run_rooms_forecast: max_turns")
+        n, cap = len(rooms), int(max_turns)
+        if n * cap > 1 << 20 or cap > 4096:                      # the library refuses these (after its entry checks): no arrays for them
+            cap = 0
+        pts = cap + 1 if n * (cap + 1) <= 1 << 16 else 0         # (likewise)
+        played = np.zeros(n, dtype=np.uint32)
+        stopped = np.zeros(n, dtype=np.uint32)
+        events = np.zeros((n, cap), dtype=EVENT_DTYPE)
+        out = np.zeros((n, cap), dtype=ROOM_VIEW_DTYPE)
+        stats = np.zeros((n, pts, _lib.ROLLOUT_WORDS), dtype=np.uint64)
+        _check(self._lib.ge_batch_run_rooms_forecast(self._h, n, rooms.ctypes.data, keys.ctypes.data, turns.ctypes.data, max_turns, bits,
+                                                     fkeys.ctypes.data, None if seat_arr is None else seat_arr.ctypes.data, n_rollouts,
+                                                     playout_max_turns, self._seed if seed is None else seed, played.ctypes.data,
+                                                     stopped.ctypes.data, events.ctypes.data, out.ctypes.data, out.nbytes,
+                                                     stats.ctypes.data, stats.nbytes), "ge_batch_run_rooms_forecast")
+        return played, stopped, events, out, stats
+
     def read_rooms_at(self, rooms) -> np.ndarray:
         """Canonical views of the listed rooms, out[k] = room rooms[k] (any order, repeats allowed)."""
         rooms = np.ascontiguousarray(rooms, dtype=np.uint64)

@@ -47,6 +47,7 @@ extern "C" {
  *      ge_batch_rollout_compare + ge_compare_stats (an entry against a baseline entry, playout by playout: the paired counts);
  *      ge_batch_run_rooms + GE_RUN_UNTIL_* (listed rooms played on until a person is needed: many turns per call, every turn traced);
  *      ge_batch_run_rooms_playout (the same with playout seats: the playouts of every turn enqueued without the host in between);
+ *      ge_batch_run_rooms_forecast (ge_batch_run_rooms with the ge_batch_rollout_seats forecast of every turn it played: a win-odds timeline);
  *      GE_PLAYOUT_HALVING (a new flag of both playout-seat calls, no new symbol: sequential halving of each decision's playout
  *      budget; a library from before it refuses the bit with GE_ERR_ARG) */
 #define GE_ABI_VERSION 5
@@ -503,6 +504,39 @@ int ge_batch_run_rooms_playout(ge_batch *b, uint64_t n, const uint64_t *rooms, c
                                uint32_t *decided /* n * max_turns, may be NULL */,
                                ge_turn_event *events /* n * max_turns, may be NULL */,
                                ge_room_view *views /* n * max_turns, may be NULL */, size_t views_cap_bytes);
+
+/* A run-on with a forecast of every turn: a win-odds timeline in one call (POLICY.md §3i).  ge_batch_run_rooms_forecast is
+ * ge_batch_run_rooms with the same (rooms, keys, turns, max_turns, until): played, stopped, events and views are ge_batch_run_rooms's
+ * word for word, and so are the stored records, the unlisted rooms, the batch's turn counter and the GE_FLAG_TRACE buffer.  In
+ * addition, for entry k and point p = 0 .. played[k], stats[k * (max_turns + 1) + p] is out[0] of the ge_batch_rollout_seats entry
+ * (room rooms[k] as it stood at point p, forecast_keys[k], turns[k] + p, seats[k], no actions; the call's n_rollouts,
+ * playout_max_turns and seed), word for word.  Point 0 is the room before the call, point p >= 1 the room after the call's turn
+ * p - 1 (views[k * max_turns + p - 1]).  Slots at p > played[k] are untouched.  seats NULL: the full view (seat 0) for every entry.
+ * The key is the same at every point, so replica r of two points draws the same stream at the same absolute turns (common random
+ * numbers: a swing between two points is the turn's effect, not resampling noise); point played[k] of one call equals point 0 of
+ * the next call on the room with turns[k] + played[k]; playouts play every seat by the policy without GE_FLAG_RESTART, so a point
+ * taken in a terminal phase is a finished game, even in a restart batch.
+ * All-or-nothing, nothing runs and nothing is touched on an error, in this order: with n > 0 ge_batch_run_rooms's checks in its
+ * order; then GE_ERR_ARG for forecast_keys or stats NULL, stats_cap_bytes < n * (max_turns + 1) * sizeof(ge_rollout_stats),
+ * n_rollouts == 0 or > 2^20, playout_max_turns > 4096, n * (max_turns + 1) > 2^16 (the accumulators are 640 B per point),
+ * n * (max_turns + 1) * n_rollouts > 2^26, or a seats[k] above the player count of room k's segment; then GE_ERR_RANGE for
+ * turns[k] + max_turns + playout_max_turns > 0xFFFFFFFF; then n == 0: GE_OK.
+ * The points are played from records the device already holds: point 0 from the batch records in front of the run, the others
+ * from the run's trace plane (64 B per room-turn) behind it on the same stream, with no host wait in between - a block of a turn
+ * its room did not play reads the run's turn count and leaves - and only the rows of the turns somebody played cross to the host.
+ * One launch per segment present for point 0, for the run and for the traced points.  With ge_batch_set_timing on,
+ * ge_batch_kernel_time includes the call's launches.  Ordered behind the previous step; synchronises.
+ * Not measured: tools/timeline_probe.py times the call against the composition it replaces (ge_batch_run_rooms, then per played
+ * turn a ge_batch_write_rooms_at into scratch rooms and a ge_batch_rollout_seats) but has not been run on an MI355X; the grid of
+ * the traced points is sized by max_turns, so a short run under a high limit pays for blocks that leave at their first test. */
+int ge_batch_run_rooms_forecast(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
+                                uint32_t max_turns, uint32_t until,
+                                const uint64_t *forecast_keys /* n */, const uint32_t *seats /* n, may be NULL: full view */,
+                                uint32_t n_rollouts, uint32_t playout_max_turns, uint64_t seed,
+                                uint32_t *played /* n */, uint32_t *stopped /* n, may be NULL */,
+                                ge_turn_event *events /* n * max_turns, may be NULL */,
+                                ge_room_view *views /* n * max_turns, may be NULL */, size_t views_cap_bytes,
+                                ge_rollout_stats *stats /* n * (max_turns + 1) */, size_t stats_cap_bytes);
 
 /* GE_FLAG_TRACE: events of the most recent ge_batch_step call, dst[(room - first) * *n_turns + t].
  * cap_bytes >= count * n_turns * sizeof(ge_turn_event).  Synchronises. */
