@@ -894,7 +894,7 @@ __device__ __forceinline__ void ww_prepare_deal(const WWR<NB> &s, const WwCtx &c
 // Lane = room leaves this step badly balanced, so the wavefront compacts all due (room, player) actions of its 64 rooms
 // into one queue in LDS (WaveLds), every lane takes one slot per round, results return by LDS atomic OR.
 // shadow1 / shadow2: work that does not depend on this turn's actions, placed behind the first slot read / the result
-// read (WwBuild::SHADOW), else run after the queue.
+// read (WwBuild::SHADOW; fused lone wavefront: both behind the first slot read, beside the first round), else run after the queue.
 struct WwActs { uint32_t newly, det_v, det_w; };   // who acted now; the Detective's new knowledge (villager / werewolf)
 
 template <int NB, bool LOWOCC, bool FUSED = false, typename S1, typename S2>
@@ -976,55 +976,102 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
     };
     uint4 c4 = fetch(lane);
     if (B::SHADOW) shadow1();
-    // at least one round (total == 0: every slot is stale and dropped): the loop is left BEFORE the next
-    // round's read is issued, so nothing of the queue is in flight behind it
-    for (uint32_t base = 0;; base += 64u) {
-        const uint32_t k = base + lane;
-        if (GE_STAMPS == 1 && stamps && base == 0u) { asm volatile("" :: "v"(c4.x)); stamps->mark(1); }   // [.. first slot in registers]
-        uint32_t L, i, know, lokw;
-        if (B::ORD) {
-            L = c4.y >> 26;
-            const uint32_t rank = (k - ((c4.y >> 16) & 0x3FFu)) & 7u;       // this slot = the rank-th due bot of room L
-            i = (c4.z >> (4u * rank)) & 7u;
-            know = c4.y & 0xFFu; lokw = (c4.y >> 8) & 0xFFu;
-        } else {
-            L = c4.z >> 26;
-            const uint32_t due = c4.z & 0xFFFFu, rank = (k - ((c4.z >> 16) & 0x3FFu)) & 15u;
-            i = (LOWOCC ? nth_set_bit<NB>(due | (1u << 31), rank) : nth_set_bit_lds<NB>(c.nth8, due, rank)) & 15u;
-            know = c4.y & 0xFFFFu; lokw = c4.y >> 16;
-        }
-        const uint32_t d = draw(c4.w, i);
-        const bool go = k < total && (d & 3u) != 0u;
-        if (LOWOCC) {
-            // the choice is computed for every slot and only the result is predicated: a
-            // conditional block would split the slot read in two dependent LDS round trips
+    // Fused lone wavefront: the first round stands outside the loop over rounds, with shadow2 in its block, where the scheduler
+    // interleaves the next turn's key and the deal's role words with the round's dependent chain (slot -> draw -> choice ->
+    // atomic).  Measured on C2 (profiles/ab_lone_shadow.txt, SQ counters): +2 % steps/s, wave cycles per wave-turn 2377 -> 2329,
+    // from 8.4 instructions fewer per wave-turn - the loop's control on the common one-round turn, two of them taken branches,
+    // which a lone wavefront pays with a fetch bubble each; the cycles it spends waiting (SQ_WAIT_ANY) did not change.
+    // Behind the result read, where shadow2 stood before, the scheduler had sunk it below the wait, and a fence that held it in
+    // front of the wait gained nothing (same file; tools/asm_shadow.py shows what stands where).
+    // Every other build keeps the loop below as it was, instruction for instruction
+    constexpr bool PEEL = LOWOCC && FUSED && B::SHADOW;
+    if (PEEL) {
+        auto round = [&](uint32_t base) {                  // the loop's body below, for a lone wavefront
+            const uint32_t k = base + lane;
+            if (GE_STAMPS == 1 && stamps && base == 0u) { asm volatile("" :: "v"(c4.x)); stamps->mark(1); }   // [.. first slot in registers]
+            uint32_t L, i, know, lokw;
+            if (B::ORD) {
+                L = c4.y >> 26;
+                const uint32_t rank = (k - ((c4.y >> 16) & 0x3FFu)) & 7u;
+                i = (c4.z >> (4u * rank)) & 7u;
+                know = c4.y & 0xFFu; lokw = (c4.y >> 8) & 0xFFu;
+            } else {
+                L = c4.z >> 26;
+                const uint32_t due = c4.z & 0xFFFFu, rank = (k - ((c4.z >> 16) & 0x3FFu)) & 15u;
+                i = nth_set_bit<NB>(due | (1u << 31), rank) & 15u;
+                know = c4.y & 0xFFFFu; lokw = c4.y >> 16;
+            }
+            const uint32_t d = draw(c4.w, i);
+            const bool go = k < total && (d & 3u) != 0u;
             uint32_t ch = B::ONEHOT ? ww_choose_onehot8(c4.x, i, d, know, lokw, know)
                                     : ww_choose<NB, false>(c4.x >> 28, i, d, c4.x & 0xFFFFu, (c4.x >> 16) & 0xFFFu, know, lokw, know, c.nth8);
-            if (B::PIN_CHOICE) asm volatile("" : "+v"(ch));   // stays outside the exec-masked block below
+            if (B::PIN_CHOICE) asm volatile("" : "+v"(ch));
             if (go) {
                 uint32_t *r = res_w + RW * L;
                 if (!B::ONE_ATOMIC) atomicOr(r, 1u << i);
                 atomicOr(r + 1 + (i >> 3), ch << (4u * (i & 7u)));
             }
-        } else if (go) {
-            const uint32_t ch = ww_choose<NB, true>(c4.x >> 28, i, d, c4.x & 0xFFFFu, (c4.x >> 16) & 0xFFFu, know, lokw, know, c.nth8);
-            uint32_t *r = res_w + RW * L;
-            if (NB <= 8 && GE_RES_PACKED && GE_RES_ATOMIC64) {
-                // both result words of the room in ONE 64-bit LDS atomic (the pair is 8-byte aligned): who acted | the choice nibble
-                atomicOr(reinterpret_cast<unsigned long long *>(r), (unsigned long long)(1u << i) | ((unsigned long long)(ch << (4u * i)) << 32));
-            } else {
-                atomicOr(r, 1u << i);
-                atomicOr(r + 1 + (i >> 3), ch << (4u * (i & 7u)));
-            }
+        };
+        shadow2();
+        round(0u);
+        for (uint32_t base = 64u; base < total; base += 64u) {   // wave-uniform; a round's read is issued only if it is needed
+            c4 = fetch(base + lane);
+            round(base);
         }
-        if (base + 64u >= total) break;                // wave-uniform
-        c4 = fetch(k + 64u);
+    } else {
+        // at least one round (total == 0: every slot is stale and dropped): the loop is left BEFORE the next
+        // round's read is issued, so nothing of the queue is in flight behind it.
+        // NOTE: `round` above is a copy of this body's LOWOCC half - a change to one belongs in the other.  The loop does not call
+        // the lambda itself because that alone changed the code of every other build (block layout and registers of the large-batch
+        // and single-turn kernels), which this way stay instruction-identical to what they were
+        for (uint32_t base = 0;; base += 64u) {
+            const uint32_t k = base + lane;
+            if (GE_STAMPS == 1 && stamps && base == 0u) { asm volatile("" :: "v"(c4.x)); stamps->mark(1); }   // [.. first slot in registers]
+            uint32_t L, i, know, lokw;
+            if (B::ORD) {
+                L = c4.y >> 26;
+                const uint32_t rank = (k - ((c4.y >> 16) & 0x3FFu)) & 7u;       // this slot = the rank-th due bot of room L
+                i = (c4.z >> (4u * rank)) & 7u;
+                know = c4.y & 0xFFu; lokw = (c4.y >> 8) & 0xFFu;
+            } else {
+                L = c4.z >> 26;
+                const uint32_t due = c4.z & 0xFFFFu, rank = (k - ((c4.z >> 16) & 0x3FFu)) & 15u;
+                i = (LOWOCC ? nth_set_bit<NB>(due | (1u << 31), rank) : nth_set_bit_lds<NB>(c.nth8, due, rank)) & 15u;
+                know = c4.y & 0xFFFFu; lokw = c4.y >> 16;
+            }
+            const uint32_t d = draw(c4.w, i);
+            const bool go = k < total && (d & 3u) != 0u;
+            if (LOWOCC) {
+                // the choice is computed for every slot and only the result is predicated: a
+                // conditional block would split the slot read in two dependent LDS round trips
+                uint32_t ch = B::ONEHOT ? ww_choose_onehot8(c4.x, i, d, know, lokw, know)
+                                        : ww_choose<NB, false>(c4.x >> 28, i, d, c4.x & 0xFFFFu, (c4.x >> 16) & 0xFFFu, know, lokw, know, c.nth8);
+                if (B::PIN_CHOICE) asm volatile("" : "+v"(ch));   // stays outside the exec-masked block below
+                if (go) {
+                    uint32_t *r = res_w + RW * L;
+                    if (!B::ONE_ATOMIC) atomicOr(r, 1u << i);
+                    atomicOr(r + 1 + (i >> 3), ch << (4u * (i & 7u)));
+                }
+            } else if (go) {
+                const uint32_t ch = ww_choose<NB, true>(c4.x >> 28, i, d, c4.x & 0xFFFFu, (c4.x >> 16) & 0xFFFu, know, lokw, know, c.nth8);
+                uint32_t *r = res_w + RW * L;
+                if (NB <= 8 && GE_RES_PACKED && GE_RES_ATOMIC64) {
+                    // both result words of the room in ONE 64-bit LDS atomic (the pair is 8-byte aligned): who acted | the choice nibble
+                    atomicOr(reinterpret_cast<unsigned long long *>(r), (unsigned long long)(1u << i) | ((unsigned long long)(ch << (4u * i)) << 32));
+                } else {
+                    atomicOr(r, 1u << i);
+                    atomicOr(r + 1 + (i >> 3), ch << (4u * (i & 7u)));
+                }
+            }
+            if (base + 64u >= total) break;                // wave-uniform
+            c4 = fetch(k + 64u);
+        }
     }
     wave_sync();
     const uint4 r = NB <= 8 ? make_uint4(reinterpret_cast<const uint2 *>(res_w + RW * lane)->x, reinterpret_cast<const uint2 *>(res_w + RW * lane)->y, 0u, 0u)
                             : lw->res[lane];
     if (B::SHADOW) {                                       // shadow of the result read
-        shadow2();
+        if (!PEEL) shadow2();
         // keeps the slot registers reserved up to here: reusing them for the work above would make the
         // compiler wait for the queue's LDS traffic first (a read into them may be in flight)
         asm volatile("" :: "v"(c4.x), "v"(c4.y), "v"(c4.z), "v"(c4.w));

@@ -1,0 +1,258 @@
+#!/usr/bin/env python3
+"""What the lone-wavefront turn loops run inside their LDS waits, read from the assembly that is shipped
+(game_engine_amd/csrc/ge_step.s, `make -C game_engine_amd/csrc asm`).
+
+A lone wavefront has no neighbour on its SIMD to hide an LDS round trip: the only thing that covers one is the wavefront's own
+instructions between the read and the `s_waitcnt lgkmcnt` that first waits for it.  The source places such work on purpose
+(ge_device.h: ww_queue_actions' shadow1 / shadow2, the pins of ww_turn), but where it ends up is the scheduler's decision -
+this tool reports it, and --check pins it.
+
+For every turn loop (outermost loop that holds the queue's LDS atomic) of the named kernels, and every LDS read in it: the
+`s_waitcnt` that first waits for that read, and the vector / scalar instructions issued between the two.  The path is the one a
+turn takes: exec-masked blocks are entered (their skip is not taken), unconditional branches are followed, and a forward
+wave-uniform branch (scc / vcc) in the turn loop's own blocks is taken - that is the skip of the deal block, which runs on
+every GE_DEAL_PERIOD-th turn only; inside the loop over queue rounds such a branch falls through (another round).  LDS and
+scalar-memory operations complete in issue order for this purpose: `lgkmcnt(n)` covers a read once at most n such
+operations were issued behind it.
+Reads are named by their place in the turn: `ord` (before the slot writes), `slot` (the first round's), `slot+` (a later
+round's, inside the queue loop), `result` (behind the atomics), `row` (everything after: the entered row, a recycled room).
+
+For the first round's slot read the walk goes on to the round's LDS atomic: `to atomic` = the vector instructions between that
+read and the atomic, i.e. the first round with whatever the scheduler interleaved with it - the placement that is adopted
+(shadow2 beside the first round) shows there and not in front of a wait.
+The floors are per kernel and read, the least over the kernel's turn loops (no loop ordinal in a key).
+
+    python tools/asm_shadow.py [file.s]        the table (no file: ge_step.s, rebuilt first if it is older than its sources)
+    python tools/asm_shadow.py --json          the same as JSON
+    python tools/asm_shadow.py --check         exit 1 if a count is below its floor in tools/asm_shadow_baseline.json
+    python tools/asm_shadow.py --write         record today's counts as the floors (those in front of a wait capped at 32)
+It reads instruction mnemonics only: LDS reads, LDS atomics and writes (to name the reads), waits, branches, and whether an
+instruction is a vector or a scalar one.
+
+Counts, vector + scalar instructions in front of the wait (Werewolf x 8 fused lone kernel, untraced tail-restart loop; the other
+loops and Werewolf x 12 alike):
+                                              ord        slot       result    slot read to atomic (x 8 / x 12)
+    before (shadow2 behind the result read)   15 + 0     9 + 2      0 + 4      67 / 119   the scheduler had sunk all of shadow2 below the wait
+    with a scheduling fence behind shadow2    15 + 0     9 + 2     20 + 7      67 / 119   measured level with `before` (profiles/ab_lone_shadow.txt)
+    first round peeled, shadow2 in its block  15 + 0     6 + 4      4 + 0      80 / 130   +2.0 %: what is adopted
+What the measurements say (profiles/ab_lone_shadow.txt): instructions in front of a wait are not the whole story.  Holding
+shadow2 in front of the result wait was level, and the counters of the adopted form show unchanged wait cycles - its gain is the
+loop control the peel removes.  The floors pin today's placement; a change that lowers one is to be measured, not assumed.
+"""
+import json
+import os
+import re
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ASM = os.path.join(ROOT, "game_engine_amd", "csrc", "ge_step.s")
+BASELINE = os.path.join(ROOT, "tools", "asm_shadow_baseline.json")
+# the fused lone-wavefront kernels whose turn goes through an LDS action queue
+KERNELS = {
+    "ge_step_kernelILi0ELb1ELi0ELb0ELi0E": "Werewolf x 8, lone-wavefront, fused",
+    "ge_step_kernelILi1ELb1ELi0ELb0ELi0E": "Werewolf x 12, lone-wavefront, fused",
+    "ge_step_kernelILi3ELb1ELi0ELb0ELi0E": "Two-Truths x 8, lone-wavefront, fused",
+    "ge_step_kernelILi4ELb1ELi0ELb0ELi0E": "Two-Truths x 12, lone-wavefront, fused",
+    "ge_step_kernel_mixedILb1ELi0ELb0E": "mixed batch, lone-wavefront, fused",
+}
+# floors are capped: 32 instructions of a lone wavefront are ~150 cycles, more than any LDS round trip of the turn - a wait with that
+# much in front of it is covered, and removing work from a long stretch must not fail the check
+CAP = 32
+LIMIT = 4000                                           # instructions walked from a read before giving up
+
+INSN = re.compile(r"^\t([a-z_0-9]+)\b(.*)")
+LABEL = re.compile(r"^(\.LBB\d+_\d+):")
+
+
+def kernel_bodies(lines):
+    """mangled-name fragment -> (first, last) line index of the kernel's code"""
+    out = {}
+    for i, ln in enumerate(lines):
+        m = re.match(r"^(_ZN\S*):", ln)
+        if not m:
+            continue
+        for frag in KERNELS:
+            if re.search(r"\d" + frag + "E+v", m.group(1)):
+                end = next(j for j in range(i, len(lines)) if lines[j].startswith(".Lfunc_end"))
+                out[frag] = (i, end)
+    return out
+
+
+def lgkm_wait(args):
+    """n of `lgkmcnt(n)` in a wait's operands; a bare immediate waits for everything; None: no LDS / scalar-memory wait"""
+    m = re.search(r"lgkmcnt\((\d+)\)", args)
+    if m:
+        return int(m.group(1))
+    return 0 if re.match(r"\s*(0x[0-9a-f]+|\d+)\s*$", args) else None
+
+
+def is_lgkm(op):
+    return op.startswith("ds_") or op.startswith("s_load") or op.startswith("s_buffer_load") or op in ("s_memtime", "s_memrealtime", "s_sendmsg")
+
+
+def loops_of(lines, lo, hi):
+    """turn loops of a kernel: [(header label, first line, last line)] of the Depth=1 loops"""
+    heads = [LABEL.match(lines[i]).group(1) for i in range(lo, hi) if "Loop Header: Depth=1" in lines[i] and LABEL.match(lines[i])]
+    out = []
+    for h in heads:
+        tag = re.compile(r"(Header=|Parent Loop )" + re.escape(h[2:]) + r"\b")
+        blocks = [i for i in range(lo, hi) if LABEL.match(lines[i]) and (lines[i].startswith(h + ":") or tag.search(lines[i]))]
+        blocks += [i + 1 for i in blocks if i + 1 < hi and tag.search(lines[i + 1])]     # (an inner header's second comment line)
+        first, last = min(blocks), max(blocks)
+        end = next((j for j in range(last + 1, hi) if LABEL.match(lines[j])), hi)
+        out.append((h, first, end))
+    return out
+
+
+ATOMIC = re.compile(r"ds_(or|add|and|max|min|xor)")
+
+
+def walk(lines, labels, start, first, end, to_atomic=False):
+    """from the LDS read at `start`: (wait line or None, vector, scalar, LDS) instructions issued up to its wait; to_atomic: the
+    walk goes on to the first LDS atomic, and a fifth value counts the vector instructions from the read to there"""
+    def in_queue_loop(i):                                   # the block of line i belongs to the loop over queue rounds
+        j = next(j for j in range(i, first - 1, -1) if LABEL.match(lines[j]))
+        return "Depth=2" in lines[j] or "Inner Loop Header" in lines[j + 1]
+    behind = v = s = d = 0
+    found = None                                            # (wait line, v, s, d) once the read's wait is passed
+    i, steps = start + 1, 0
+    while steps < LIMIT:
+        m = INSN.match(lines[i])
+        if not m:
+            i += 1
+            continue
+        op, args = m.group(1), m.group(2)
+        steps += 1
+        if op == "s_endpgm":
+            break
+        if found and ATOMIC.match(op):
+            return found + (v,)
+        if op == "s_waitcnt":
+            n = lgkm_wait(args)
+            if not found and n is not None and n <= behind:
+                found = (i, v, s, d)
+                if not to_atomic:
+                    return found
+            i += 1
+            continue
+        if op == "s_branch":
+            s += 1
+            i = labels[args.strip()]
+            continue
+        if op.startswith("s_cbranch_scc") or op.startswith("s_cbranch_vcc"):
+            s += 1
+            t = labels[args.strip()]
+            i = t if (i < t < end and not in_queue_loop(i)) else i + 1
+            continue
+        if is_lgkm(op):
+            behind += 1
+            d += op.startswith("ds_")
+        elif op.startswith("v_"):
+            v += 1
+        elif op.startswith("s_"):
+            s += 1
+        i += 1
+    return found + (None,) if found and to_atomic else found or (None, v, s, d)
+
+
+def fresh_asm():
+    """game_engine_amd/csrc/ge_step.s, rebuilt (`make asm`) if it is missing or older than a file it is made from"""
+    csrc = os.path.dirname(ASM)
+    srcs = [os.path.join(csrc, n) for n in os.listdir(csrc) if n.endswith((".hip", ".inl", ".h", ".sed")) or n == "Makefile"]
+    srcs.append(os.path.join(ROOT, "include", "ge_step.h"))
+    if not os.path.exists(ASM) or os.path.getmtime(ASM) < max(os.path.getmtime(p) for p in srcs):
+        p = subprocess.run(["make", "-C", csrc, "asm"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if p.returncode != 0:
+            sys.stderr.write(p.stdout)
+            raise SystemExit("make asm failed")
+    return ASM
+
+
+def collect(path):
+    with open(path) as f:
+        lines = f.read().split("\n")
+    rows = []
+    for frag, (lo, hi) in sorted(kernel_bodies(lines).items(), key=lambda kv: kv[1]):
+        labels = {LABEL.match(lines[i]).group(1): i for i in range(lo, hi) if LABEL.match(lines[i])}
+        n_loop = 0
+        for head, first, end in loops_of(lines, lo, hi):
+            ops = [(i, INSN.match(lines[i]).group(1)) for i in range(first, end) if INSN.match(lines[i])]
+            atomics = [i for i, op in ops if ATOMIC.match(op)]
+            writes = [i for i, op in ops if op.startswith("ds_write")]
+            if not atomics or not writes:                       # not a turn loop with an action queue
+                continue
+            def in_queue_loop(i):
+                j = next(j for j in range(i, first - 1, -1) if LABEL.match(lines[j]))
+                return "Depth=2" in lines[j] or "Inner Loop Header" in lines[j + 1]
+            seen = {}
+            for i, op in ops:
+                if not op.startswith("ds_read"):
+                    continue
+                if i < writes[0]:
+                    role = "ord"
+                elif in_queue_loop(i):
+                    role = "slot+"
+                elif i < atomics[0]:
+                    role = "slot"
+                elif "result" not in seen:
+                    role = "result"
+                else:
+                    role = "row"
+                seen[role] = seen.get(role, 0) + 1
+                wait, v, s, d, *rest = walk(lines, labels, i, first, end, to_atomic=(role == "slot"))
+                rows.append({"kernel": KERNELS[frag], "loop": n_loop, "read": f"{role}{seen[role] if seen[role] > 1 else ''}", "op": op,
+                             "wait": (INSN.match(lines[wait]).group(0).strip() if wait is not None else None),
+                             "vector": v, "scalar": s, "lds": d, "to_atomic": rest[0] if rest else None})
+            n_loop += 1
+    return rows
+
+
+def key(r):
+    return f"{r['kernel']} / loop {r['loop']} / {r['read']}"
+
+
+def least(rows):
+    """kernel / read -> the least counts over the kernel's turn loops (loops come and go with the source: the floors name none)"""
+    out = {}
+    for r in rows:
+        k = f"{r['kernel']} / {r['read']}"
+        o = out.setdefault(k, {"vector": r["vector"], "scalar": r["scalar"], "both": r["vector"] + r["scalar"]})
+        o["vector"], o["scalar"], o["both"] = min(o["vector"], r["vector"]), min(o["scalar"], r["scalar"]), min(o["both"], r["vector"] + r["scalar"])
+        if r["to_atomic"] is not None:
+            o["to_atomic"] = min(o.get("to_atomic", r["to_atomic"]), r["to_atomic"])
+    return out
+
+
+def main():
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    rows = collect(args[0] if args else fresh_asm())
+    if "--json" in sys.argv:
+        print(json.dumps(rows, indent=1))
+    else:
+        print(f"{'kernel / turn loop / read':64s} {'read':14s} {'vector':>6s} {'scalar':>6s} {'LDS':>4s} {'to atomic':>9s}  first wait")
+        for r in rows:
+            print(f"{key(r):64s} {r['op']:14s} {r['vector']:6d} {r['scalar']:6d} {r['lds']:4d} {r['to_atomic'] if r['to_atomic'] is not None else '':>9}  {r['wait']}")
+    got = least(rows)
+    if "--write" in sys.argv:
+        for o in got.values():
+            o["vector"], o["scalar"], o["both"] = min(o["vector"], CAP), min(o["scalar"], CAP), min(o["both"], CAP)
+        with open(BASELINE, "w") as f:
+            json.dump(got, f, indent=1, sort_keys=True)
+            f.write("\n")
+    if "--check" in sys.argv:
+        with open(BASELINE) as f:
+            floor = json.load(f)
+        bad = [f"{k}: missing from the assembly" for k in floor if k not in got]
+        for k, fl in floor.items():
+            g = got.get(k)
+            if g and (g["vector"] < fl["vector"] or g["both"] < fl["both"]):
+                bad.append(f"{k}: {g['vector']} vector, {g['both']} vector + scalar in front of the wait; floors {fl['vector']}, {fl['both']}")
+            if g and "to_atomic" in fl and g.get("to_atomic", 0) < fl["to_atomic"]:
+                bad.append(f"{k}: {g.get('to_atomic')} vector instructions from the slot read to the round's atomic, floor {fl['to_atomic']}")
+        if bad:
+            raise SystemExit("LDS shadow check failed:\n  " + "\n  ".join(bad))
+
+
+if __name__ == "__main__":
+    main()
