@@ -79,6 +79,18 @@ template <bool LOWOCC, bool SINGLE> constexpr bool single_global(int game_bit) {
 #ifndef GE_TALLY_BYTES
 #define GE_TALLY_BYTES 1
 #endif
+// Lone Werewolf x 8 turn, rare deal paths out of the loop's straight line (profiles/ab_lone_cold_deal.txt; the tail-recycling turn loops only).
+//   GE_COLD_FALLBACK: the on-the-spot deal of ww_apply_effect stands behind a wave-uniform vote marked unlikely, around the unchanged
+//   per-lane test: a turn in which no lane lacks its deal passes one scalar test instead of two exec-mask regions whose values met again
+//   in copies, and the ~125-instruction deal is laid out behind the loop.  C2 +4.1 % steps/s by the rule in two sessions: adopted.
+//   GE_COLD_DEAL_NOW: ww_prepare_deal's `deal_now` marked unlikely, so the block of every GE_DEAL_PERIOD-th turn is laid out behind the
+//   loop too (one taken branch less on 15 turns of 16): +1.5 % alone, which does not pass, and level on top of the other: not adopted
+#ifndef GE_COLD_FALLBACK
+#define GE_COLD_FALLBACK 1
+#endif
+#ifndef GE_COLD_DEAL_NOW
+#define GE_COLD_DEAL_NOW 0
+#endif
 #ifndef GE_ROWS_SPLIT
 #define GE_ROWS_SPLIT 1
 #endif
@@ -906,11 +918,12 @@ __device__ __forceinline__ void ww_phase_branch(const WWR<NB> &s, const DevRow &
 // ---- `deal_now` (wave-uniform, every GE_DEAL_PERIOD-th turn): lanes without a prepared deal compute their next one; then the
 // role-assignment values of the prepared deal (what an assignment writes) - except in the packed form, which only the
 // assigning lanes expand (ww_apply_effect)
-template <int NB, bool LOWOCC, bool SINGLE>
+// COLD (GE_COLD_DEAL_NOW, the tail-recycling turn loops; measured, off): `deal_now` is marked unlikely - the block leaves the turn's straight line
+template <int NB, bool LOWOCC, bool SINGLE, bool COLD = false>
 __device__ __forceinline__ void ww_prepare_deal(const WWR<NB> &s, const WwCtx &c, Deal &deal, bool deal_now, uint32_t ALL, WWR<NB> &dealt) {
     using B = WwBuild<NB, LOWOCC, SINGLE>;
     const uint32_t g = deal_next_game<NB>(s);
-    if (deal_now && deal.gv != (g | DEAL_VALID)) {             // no deal, or (single-turn Werewolf x 12: an entry of the side plane) one for another game
+    if ((COLD ? __builtin_expect(deal_now, false) : deal_now) && deal.gv != (g | DEAL_VALID)) {             // no deal, or (single-turn Werewolf x 12: an entry of the side plane) one for another game
         deal_roles<NB, B::TABLE, B::DEAL_FORM>(deal, deal_key(c.rkey, g), g, c.n, c.nw, c.nth8);
     }
     if (B::DEAL_FORM != DEAL_PACKED) deal_words<NB, B::DEAL_FORM>(deal, ALL, dealt);
@@ -1180,8 +1193,17 @@ __device__ __forceinline__ void ww_apply_effect(WWR<NB> &s, const DevRow &row, c
     };
     // role assignment: the deal of this game was normally prepared ahead (ww_prepare_deal, every GE_DEAL_PERIOD-th turn,
     // for all lanes of the wavefront at once); fall back to dealing here if it was not
+    // (TAILR, GE_COLD_FALLBACK: behind a wave-uniform vote first - almost no turn of a fused run has a lane without its deal)
     const bool is_assign = eff == EFF_ASSIGN_ROLES;
-    if (is_assign && deal.gv != (s.games | DEAL_VALID)) {
+    if (TAILR && GE_COLD_FALLBACK) {
+        const bool need_deal = is_assign && deal.gv != (s.games | DEAL_VALID);
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(need_deal) != 0u, 0)) {
+            if (need_deal) {
+                deal_roles<NB, B::TABLE, B::DEAL_FORM>(deal, deal_key(c.rkey, s.games), s.games, c.n, c.nw, c.nth8);
+                if (B::DEAL_FORM != DEAL_PACKED) deal_words<NB, B::DEAL_FORM>(deal, ALL, dealt);
+            }
+        }
+    } else if (is_assign && deal.gv != (s.games | DEAL_VALID)) {
         deal_roles<NB, B::TABLE, B::DEAL_FORM>(deal, deal_key(c.rkey, s.games), s.games, c.n, c.nw, c.nth8);
         if (B::DEAL_FORM != DEAL_PACKED) deal_words<NB, B::DEAL_FORM>(deal, ALL, dealt);
     }
@@ -1276,7 +1298,7 @@ __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c,
         },
         [&]() {
             if (!SINGLE) tk_next = turn_key(c.rkey, turn + 1u);
-            if (!B::DEAL_EARLY) ww_prepare_deal<NB, LOWOCC, SINGLE>(s, c, deal, deal_now, ALL, dealt);
+            if (!B::DEAL_EARLY) ww_prepare_deal<NB, LOWOCC, SINGLE, TAILR && GE_COLD_DEAL_NOW>(s, c, deal, deal_now, ALL, dealt);
             if (B::SHADOW) {
                 if (!SINGLE) asm volatile("" : "+v"(tk_next));
                 if (B::DEAL_FORM != DEAL_PACKED && !B::DEAL_EARLY) {

@@ -11,7 +11,8 @@ For every turn loop (outermost loop that holds the queue's LDS atomic) of the na
 `s_waitcnt` that first waits for that read, and the vector / scalar instructions issued between the two.  The path is the one a
 turn takes: exec-masked blocks are entered (their skip is not taken), unconditional branches are followed, and a forward
 wave-uniform branch (scc / vcc) in the turn loop's own blocks is taken - that is the skip of the deal block, which runs on
-every GE_DEAL_PERIOD-th turn only; inside the loop over queue rounds such a branch falls through (another round).  LDS and
+every GE_DEAL_PERIOD-th turn only; inside the loop over queue rounds such a branch falls through (another round).  A block
+of the loop that the compiler laid out behind the loop's back edge (a rare path: entered by a wave-uniform branch, it jumps back) is not entered.  LDS and
 scalar-memory operations complete in issue order for this purpose: `lgkmcnt(n)` covers a read once at most n such
 operations were issued behind it.
 Reads are named by their place in the turn: `ord` (before the slot writes), `slot` (the first round's), `slot+` (a later
@@ -25,6 +26,9 @@ The floors are per kernel and read, the least over the kernel's turn loops (no l
     python tools/asm_shadow.py [file.s]        the table (no file: ge_step.s, rebuilt first if it is older than its sources)
     python tools/asm_shadow.py --json          the same as JSON
     python tools/asm_shadow.py --check         exit 1 if a count is below its floor in tools/asm_shadow_baseline.json
+    python tools/asm_shadow.py --paths         per turn loop, as JSON: the common turn from the loop header to its back edge - instructions on it,
+                                               branches taken on it, role-deal blocks it runs through (tools/asm_shadow_paths.json pins the last
+                                               two for the Werewolf x 8 kernel: tests/test_asm_cold_deal.py)
     python tools/asm_shadow.py --write         record today's counts as the floors (those in front of a wait capped at 32)
 It reads instruction mnemonics only: LDS reads, LDS atomics and writes (to name the reads), waits, branches, and whether an
 instruction is a vector or a scalar one.
@@ -106,14 +110,56 @@ def loops_of(lines, lo, hi):
 
 
 ATOMIC = re.compile(r"ds_(or|add|and|max|min|xor)")
+PATHS = os.path.join(ROOT, "tools", "asm_shadow_paths.json")
+# the draw constants (17 .. 20) * GOLDEN of deal_roles' four picks (ge_device.h): only a role-deal block holds them
+DEAL_MARKS = tuple(hex((0x9E3779B9 * (17 + j)) & 0xFFFFFFFF) for j in range(4))
 
 
-def walk(lines, labels, start, first, end, to_atomic=False):
+def cold_from(lines, head, first, end):
+    """the line behind the turn loop's back edge (its first branch to the header): blocks of the loop that stand behind it are
+    rare paths the compiler laid out of line - they are entered by a wave-uniform branch and jump back.  No such branch: `end`"""
+    back = re.compile(r"^\ts_c?branch\w*\s+" + re.escape(head) + r"\s*$")
+    return next((i + 1 for i in range(first, end) if back.match(lines[i].split(";")[0].rstrip())), end)
+
+
+def turn_path(lines, labels, head, first, end):
+    """the common turn from the loop header to its back edge, by walk()'s rules (exec-masked blocks entered, the skip of an in-line
+    wave-uniform block taken, no branch into an out-of-line block, the loop over further queue rounds left at once): instructions on
+    it, branches taken on it (the back edge among them), and how many role-deal blocks it runs through"""
+    def in_queue_loop(i):
+        j = next(j for j in range(i, first - 1, -1) if LABEL.match(lines[j]))
+        return "Depth=2" in lines[j] or "Inner Loop Header" in lines[j + 1]
+    cold = cold_from(lines, head, first, end)
+    i, n, taken, marks = labels[head], 0, 0, 0
+    for _ in range(40 * LIMIT):
+        m = INSN.match(lines[i])
+        if not m:
+            i += 1
+            continue
+        op, args = m.group(1), m.group(2)
+        if op == "s_endpgm":
+            return None
+        n += 1
+        marks += any(c in lines[i] for c in DEAL_MARKS)
+        if op == "s_branch" or op.startswith("s_cbranch_scc") or op.startswith("s_cbranch_vcc"):
+            t = labels.get(args.strip())
+            if t is not None and t <= i and (op == "s_branch" or not in_queue_loop(i)):
+                return {"insns": n, "taken": taken + 1, "deal_blocks": (marks + 3) // 4}
+            if t is not None and t > i and (op == "s_branch" or (t < cold and not in_queue_loop(i))):
+                taken += 1
+                i = t
+                continue
+        i += 1
+    return None
+
+
+def walk(lines, labels, start, first, end, to_atomic=False, cold=None):
     """from the LDS read at `start`: (wait line or None, vector, scalar, LDS) instructions issued up to its wait; to_atomic: the
     walk goes on to the first LDS atomic, and a fifth value counts the vector instructions from the read to there"""
     def in_queue_loop(i):                                   # the block of line i belongs to the loop over queue rounds
         j = next(j for j in range(i, first - 1, -1) if LABEL.match(lines[j]))
         return "Depth=2" in lines[j] or "Inner Loop Header" in lines[j + 1]
+    cold = end if cold is None else cold                    # blocks from there on are out of line (cold_from): not the common turn
     behind = v = s = d = 0
     found = None                                            # (wait line, v, s, d) once the read's wait is passed
     i, steps = start + 1, 0
@@ -143,7 +189,7 @@ def walk(lines, labels, start, first, end, to_atomic=False):
         if op.startswith("s_cbranch_scc") or op.startswith("s_cbranch_vcc"):
             s += 1
             t = labels[args.strip()]
-            i = t if (i < t < end and not in_queue_loop(i)) else i + 1
+            i = t if (i < t < cold and not in_queue_loop(i)) else i + 1
             continue
         if is_lgkm(op):
             behind += 1
@@ -177,6 +223,7 @@ def collect(path):
         labels = {LABEL.match(lines[i]).group(1): i for i in range(lo, hi) if LABEL.match(lines[i])}
         n_loop = 0
         for head, first, end in loops_of(lines, lo, hi):
+            cold = cold_from(lines, head, first, end)
             ops = [(i, INSN.match(lines[i]).group(1)) for i in range(first, end) if INSN.match(lines[i])]
             atomics = [i for i, op in ops if ATOMIC.match(op)]
             writes = [i for i, op in ops if op.startswith("ds_write")]
@@ -200,12 +247,31 @@ def collect(path):
                 else:
                     role = "row"
                 seen[role] = seen.get(role, 0) + 1
-                wait, v, s, d, *rest = walk(lines, labels, i, first, end, to_atomic=(role == "slot"))
+                wait, v, s, d, *rest = walk(lines, labels, i, first, end, to_atomic=(role == "slot"), cold=cold)
                 rows.append({"kernel": KERNELS[frag], "loop": n_loop, "read": f"{role}{seen[role] if seen[role] > 1 else ''}", "op": op,
                              "wait": (INSN.match(lines[wait]).group(0).strip() if wait is not None else None),
                              "vector": v, "scalar": s, "lds": d, "to_atomic": rest[0] if rest else None})
             n_loop += 1
     return rows
+
+
+def paths(path):
+    """per turn loop (numbered as in collect): turn_path's figures and the loop's static size"""
+    with open(path) as f:
+        lines = f.read().split("\n")
+    out = {}
+    for frag, (lo, hi) in sorted(kernel_bodies(lines).items(), key=lambda kv: kv[1]):
+        labels = {LABEL.match(lines[i]).group(1): i for i in range(lo, hi) if LABEL.match(lines[i])}
+        n_loop = 0
+        for head, first, end in loops_of(lines, lo, hi):
+            ops = [INSN.match(lines[i]).group(1) for i in range(first, end) if INSN.match(lines[i])]
+            if not any(ATOMIC.match(op) for op in ops) or not any(op.startswith("ds_write") for op in ops):
+                continue
+            p = turn_path(lines, labels, head, first, end)
+            if p:
+                out[f"{KERNELS[frag]} / loop {n_loop}"] = dict(p, static=len(ops), out_of_line=cold_from(lines, head, first, end) < end)
+            n_loop += 1
+    return out
 
 
 def key(r):
@@ -226,19 +292,29 @@ def least(rows):
 
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
-    rows = collect(args[0] if args else fresh_asm())
-    if "--json" in sys.argv:
+    src = args[0] if args else fresh_asm()
+    rows = collect(src)
+    pth = paths(src)
+    if "--paths" in sys.argv:
+        print(json.dumps(pth, indent=1, sort_keys=True))
+    elif "--json" in sys.argv:
         print(json.dumps(rows, indent=1))
     else:
         print(f"{'kernel / turn loop / read':64s} {'read':14s} {'vector':>6s} {'scalar':>6s} {'LDS':>4s} {'to atomic':>9s}  first wait")
         for r in rows:
             print(f"{key(r):64s} {r['op']:14s} {r['vector']:6d} {r['scalar']:6d} {r['lds']:4d} {r['to_atomic'] if r['to_atomic'] is not None else '':>9}  {r['wait']}")
+        print(f"\n{'kernel / turn loop: the common turn, header to back edge':64s} {'instructions':>12s} {'taken branches':>14s} {'deal blocks':>11s} {'loop size':>9s}")
+        for k, p in pth.items():
+            print(f"{k:64s} {p['insns']:12d} {p['taken']:14d} {p['deal_blocks']:11d} {p['static']:9d}")
     got = least(rows)
     if "--write" in sys.argv:
         for o in got.values():
             o["vector"], o["scalar"], o["both"] = min(o["vector"], CAP), min(o["scalar"], CAP), min(o["both"], CAP)
         with open(BASELINE, "w") as f:
             json.dump(got, f, indent=1, sort_keys=True)
+            f.write("\n")
+        with open(PATHS, "w") as f:
+            json.dump({k: {"deal_blocks": p["deal_blocks"], "taken": p["taken"]} for k, p in pth.items() if "Werewolf x 8" in k}, f, indent=1, sort_keys=True)
             f.write("\n")
     if "--check" in sys.argv:
         with open(BASELINE) as f:
