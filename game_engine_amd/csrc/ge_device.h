@@ -91,6 +91,20 @@ template <bool LOWOCC, bool SINGLE> constexpr bool single_global(int game_bit) {
 #ifndef GE_COLD_DEAL_NOW
 #define GE_COLD_DEAL_NOW 0
 #endif
+// Lone Werewolf x 8 turn, once-per-game work out of the every-turn path (profiles/ab_lone_once_per_game.txt).
+//   GE_LONE_DEAL_WORDS: the fused lone-wavefront Werewolf x 8 builds keep a prepared deal as its three predicate words (DEAL_WORDS, the
+//   large-batch build's form: converted once per deal) instead of as four player masks that every turn of every lane turned into
+//   words again (DEAL_MASKS).  A lone wavefront pays an issue slot for each of those instructions wherever they stand.
+//   GE_TAIL_KNOWN_RESTART: whether a turn of the tail-recycling loops recycles is a compile-time fact of the turn (ww_turn's TAILR:
+//   TAIL_RECYCLE / TAIL_KEEP) - a recycling turn does not record `end_turn` (the fresh room's replaces it), a turn that does not
+//   recycle has no merge with the fresh room; a restart-on launch runs its last turn as a peeled TAIL_KEEP turn behind the loop and a
+//   restart-off launch goes to a kernel of its own (ge_step_kernel's LD = LD_NO_RECYCLE).  0 = the run-time form (rst->term_rs)
+#ifndef GE_LONE_DEAL_WORDS
+#define GE_LONE_DEAL_WORDS 1
+#endif
+#ifndef GE_TAIL_KNOWN_RESTART
+#define GE_TAIL_KNOWN_RESTART 1
+#endif
 #ifndef GE_ROWS_SPLIT
 #define GE_ROWS_SPLIT 1
 #endif
@@ -115,7 +129,9 @@ template <int NB, bool LOWOCC, bool SINGLE = false> struct WwBuild {
     static constexpr bool PIN_CHOICE = LOWOCC && NB > 8;    // the slot's choice computed outside its `acts this turn` region (r02_ab_sel_pin)
     static constexpr bool SEL_OPEN = LOWOCC;                // completion test without short-circuit evaluation (r02_ab_open_tpldeal)
     static constexpr bool TPL_TRACE = LOWOCC;               // the turn loop compiled once per trace setting (r02_ab_branch_diet)
-    static constexpr int DEAL_FORM = SINGLE ? 2 : LOWOCC ? 0 : NB <= 8 ? 1 : 2;   // DEAL_PACKED / DEAL_MASKS / DEAL_WORDS, see struct Deal
+    // DEAL_PACKED / DEAL_MASKS / DEAL_WORDS, see struct Deal.  Fused N <= 8: words, lone wavefront (GE_LONE_DEAL_WORDS) and large batch alike;
+    // Werewolf x 12 lone keeps the masks (its words are more registers, and that build was not counted)
+    static constexpr int DEAL_FORM = SINGLE ? 2 : NB <= 8 ? ((LOWOCC && !GE_LONE_DEAL_WORDS) ? 0 : 1) : LOWOCC ? 0 : 2;
     static constexpr bool DEAL_EARLY = GE_DEAL_EARLY && !LOWOCC && !SINGLE;   // the deal is prepared at the head of the turn, not in the queue's second LDS shadow (see ww_turn)
     static constexpr bool TABLE = !LOWOCC;                  // n-th-set-bit through the 2 KB LDS table instead of ~15 VALU instructions
     // the fused lone-wavefront turn of Werewolf x 8 may recycle a finished room where it enters its terminal row (ww_apply_effect,
@@ -480,10 +496,12 @@ __device__ __forceinline__ uint64_t nib_nonzero(uint64_t x) {
 // n-th-set-bit sampling of the players not yet dealt; the rest are Villagers.  Picks are keyed by (room, game index), not by
 // the turn that applies them, so a deal can be prepared ahead - in registers during a fused launch, and for N <= 8 across
 // launches in the record's spare half-word (ge_layout.h, WWLayout<8>).  Three in-register forms (WwBuild::DEAL_FORM):
-//   DEAL_MASKS   a / b / c / rem = werewolves / Doctor / Detective / Villagers as player masks - the lone-wavefront build,
-//                where turning them into predicate words sits in an LDS wait shadow and costs nothing;
-//   DEAL_WORDS   a / b / c = the three packed predicate words an assignment writes (N <= 8, large-batch fused build:
-//                the conversion is paid once per deal, not once per turn; profiles/r02_ab_onehot_swar_pk.txt);
+//   DEAL_MASKS   a / b / c / rem = werewolves / Doctor / Detective / Villagers as player masks - the lone-wavefront Werewolf x 12
+//                build; every turn turns them into predicate words in an LDS wait (ww_prepare_deal).  That was the lone N <= 8 form
+//                too, on the belief that work in a wait is free: a lone wavefront pays issue for it there as anywhere;
+//   DEAL_WORDS   a / b / c = the three packed predicate words an assignment writes (N <= 8, every fused build: the conversion is
+//                paid once per deal - deal_set, deal_from_cache - not once per turn; profiles/r02_ab_onehot_swar_pk.txt for the
+//                large batch, profiles/ab_lone_once_per_game.txt for the lone wavefront);
 //   DEAL_PACKED  a = DealPk, one register - Werewolf x 12 large-batch (register pressure: that build is held to 80 VGPRs)
 //                and every single-turn build; expanded only by the lanes that assign.
 // gv = game index | 1 << 31 while the deal is valid, else 0: "ready for this game" is one compare.
@@ -842,9 +860,14 @@ struct WwCtx {
 // move itself writes the fresh room - one bit-select per state word by a lane mask, and the fresh room's row through the
 // one LDS read the move issues anyway - and the turn loop's head has no restart block.  A room that is ALREADY terminal when
 // the launch loads it is recycled in front of the loop (run_ww); a table whose first phase is terminal keeps the head form.
+// Whether a turn recycles is a fact of the launch (restart on / off) and of the turn (a launch's last turn stores terminal rooms as they
+// are), so the turn is compiled per answer (GE_TAIL_KNOWN_RESTART): TAIL_RECYCLE - a lane that enters a terminal row leaves as the fresh
+// room, and nothing records `end_turn` (see ww_apply_effect); TAIL_KEEP - no lane is recycled: no merge with the fresh room at all.
+// TAIL_RUNTIME is the form that reads the answer from rst->term_rs on every turn (GE_TAIL_KNOWN_RESTART = 0).
+enum { TAIL_NONE = 0, TAIL_RUNTIME = 1, TAIL_RECYCLE = 2, TAIL_KEEP = 3 };
 template <int NB> struct WwRestart {
     const WWR<NB> *s0;         // the fresh room (wave-uniform: scalar registers)
-    uint32_t term_rs;          // in: the table's terminal-row mask if a room may be recycled at the end of this turn, else 0
+    uint32_t term_rs;          // in: the table's terminal-row mask if a room may be recycled at the end of this turn, else 0 (TAIL_KEEP: not read)
     uint32_t restarted;        // out: 1 = the lane was recycled at the end of this turn (the next turn's `restarted` trace bit)
     uint32_t q;                // out: the row the turn moved to (a recycled lane's terminal row: what the trace records)
 };
@@ -1172,8 +1195,12 @@ __device__ __forceinline__ uint32_t ww_decide(const WWR<NB> &s, uint32_t comp, u
 // more game (WwRestart; `qrow` is then already the fresh room's row).  That form runs for EVERY lane, not inside a divergent block
 // of the lanes that move: `moved` (0 / ~0) masks the entry effect and the few unconditional writes instead.  Some room of 64 moves
 // on every turn, so the block never skipped anything; it cost its exec-mask sequence, two branches, and a dozen register copies
-// per turn where the values it had and had not changed met again
-template <int NB, bool LOWOCC, bool SINGLE, bool TAILR = false>
+// per turn where the values it had and had not changed met again.
+// TAIL_RECYCLE leaves `end_turn` alone: a lane that enters a terminal row there is recycled (rmask), so `qrow` is the first phase's row -
+// not terminal, or the tail form would not run (run_ww) - and its end_turn becomes the fresh room's below; and no lane STAYS in a
+// terminal row inside a recycling loop (finished as loaded: recycled in front of the loop).  The test, the saturated turn number and the
+// select were 8 instructions of every turn for a value that was never kept.  TAIL_KEEP: rmask is 0, the merge folds away
+template <int NB, bool LOWOCC, bool SINGLE, int TAILR = TAIL_NONE>
 __device__ __forceinline__ void ww_apply_effect(WWR<NB> &s, const DevRow &row, const DevRow &qrow, const WwCtx &c, uint32_t qe, uint32_t alive, uint32_t ALL, uint32_t turn,
                                                 Deal &deal, WWR<NB> &dealt, uint32_t rmask = 0u, const WWR<NB> *s0 = nullptr, uint32_t moved = ~0u) {
     using R = WWR<NB>;
@@ -1251,10 +1278,12 @@ __device__ __forceinline__ void ww_apply_effect(WWR<NB> &s, const DevRow &row, c
         s.flags = bfi(moved, (s.flags & FLAG_PHASE0_DONE) | (p_eff << 1), s.flags);
         s.prev = bfi(moved, s.phase, s.prev);
         s.phase = q;                                           // (a lane that stays has q == s.phase)
-        const bool terminal = ((qrow.r0 >> 11) & 7u) == 0u;
-        s.end_turn = (terminal && moved != 0u && s.end_turn == END_NONE) ? (turn < 0xFFFEu ? turn : 0xFFFEu) : s.end_turn;
+        if (TAILR != TAIL_RECYCLE) {
+            const bool terminal = ((qrow.r0 >> 11) & 7u) == 0u;
+            s.end_turn = (terminal && moved != 0u && s.end_turn == END_NONE) ? (turn < 0xFFFEu ? turn : 0xFFFEu) : s.end_turn;
+        }
     }
-    if (TAILR) {
+    if (TAILR == TAIL_RUNTIME || TAILR == TAIL_RECYCLE) {
 #pragma unroll
         for (int k = 0; k < R::NW; k++) s.W[k] = bfi_uniform(rmask, s0->W[k], s.W[k]);
         s.acted |= rmask & s0->acted; s.choice |= (nib_t)rmask & s0->choice;      // (both were just cleared)
@@ -1271,8 +1300,9 @@ __device__ __forceinline__ void ww_apply_effect(WWR<NB> &s, const DevRow &row, c
 // build leaves it as it is: nobody reads it after the turn).
 // tk_io: in = turn_key(rkey, turn), out = the next turn's key (computed in an LDS wait shadow; not in a single-turn build).
 // ev_*: this turn's logged actions (who acted, what they chose) for the optional event trace.
-// TAILR: rooms that finish are recycled at the end of the turn (`rst`, WwRestart)
-template <int NB, bool LOWOCC, int GENERIC = false, bool SINGLE = false, bool TAILR = false>
+// TAILR: TAIL_NONE = the head form; else the tail form - rooms that finish are recycled at the end of the turn (`rst`, WwRestart):
+// on every turn (TAIL_RECYCLE), on none (TAIL_KEEP), or as rst->term_rs says (TAIL_RUNTIME)
+template <int NB, bool LOWOCC, int GENERIC = false, bool SINGLE = false, int TAILR = TAIL_NONE>
 __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c, uint32_t turn, uint32_t &tk_io, bool trace, Deal &deal, bool deal_now,
                                         uint32_t &ev_newly, uint64_t &ev_choice, Stamps *stamps = nullptr, WwRestart<NB> *rst = nullptr) {
     static_assert(!TAILR || (NB <= 8 && LOWOCC && !SINGLE), "tail recycling is the fused lone-wavefront Werewolf x 8 form");
@@ -1298,10 +1328,12 @@ __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c,
         },
         [&]() {
             if (!SINGLE) tk_next = turn_key(c.rkey, turn + 1u);
-            if (!B::DEAL_EARLY) ww_prepare_deal<NB, LOWOCC, SINGLE, TAILR && GE_COLD_DEAL_NOW>(s, c, deal, deal_now, ALL, dealt);
+            if (!B::DEAL_EARLY) ww_prepare_deal<NB, LOWOCC, SINGLE, TAILR != TAIL_NONE && GE_COLD_DEAL_NOW>(s, c, deal, deal_now, ALL, dealt);
             if (B::SHADOW) {
                 if (!SINGLE) asm volatile("" : "+v"(tk_next));
-                if (B::DEAL_FORM != DEAL_PACKED && !B::DEAL_EARLY) {
+                // (DEAL_MASKS: the pins keep the per-turn conversion in this block.  The lone DEAL_WORDS build has none: `dealt` is three
+                // plain copies of the deal's words there, and pinned they became three v_mov of every turn - 341 -> 338 on the common turn)
+                if (B::DEAL_FORM != DEAL_PACKED && !B::DEAL_EARLY && !(LOWOCC && B::DEAL_FORM == DEAL_WORDS)) {
 #pragma unroll
                     for (int k = 0; k < R::NW; k++) asm volatile("" : "+v"(dealt.W[k]));
                 }
@@ -1334,9 +1366,9 @@ __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c,
         const uint32_t moved = 0u - (uint32_t)(q != s.phase);
         // ~0: the lane enters a terminal row and is recycled.  (A lane that STAYS in a terminal row has term_rs == 0: it was loaded
         // terminal and recycled in front of the loop unless restart is off, and the first phase is not terminal - run_ww)
-        const uint32_t rmask = bit_mask(rst->term_rs, q);
-        const DevRow qrow = lds_row<false>(c.rows, bfi_uniform(rmask, c.phase0_idx, q));   // (the fresh room's row for those)
-        ww_apply_effect<NB, LOWOCC, false, true>(s, row, qrow, c, qe, alive, ALL, turn, deal, dealt, rmask, rst->s0, moved);
+        const uint32_t rmask = TAILR == TAIL_KEEP ? 0u : bit_mask(rst->term_rs, q);
+        const DevRow qrow = lds_row<false>(c.rows, TAILR == TAIL_KEEP ? q : bfi_uniform(rmask, c.phase0_idx, q));   // (the fresh room's row for those)
+        ww_apply_effect<NB, LOWOCC, false, TAILR>(s, row, qrow, c, qe, alive, ALL, turn, deal, dealt, rmask, rst->s0, moved);
         row = qrow;
         rst->q = q;
         rst->restarted = rmask & 1u;

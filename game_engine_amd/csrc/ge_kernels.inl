@@ -59,6 +59,9 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 // loads and drops the hint unless inline-asm statements keep them apart, and behind any such statement it fetches the launch's turn word
 // with a vector load instead of a scalar one - 4 % of the launch.)
 constexpr bool stream_loads(int ld, bool layout_default) { return ld == 0 ? layout_default : ld == 2; }
+// a further value of the step kernel's LD argument, for the fused lone-wavefront Werewolf x 8 kernel alone (GE_TAIL_KNOWN_RESTART, run_ww):
+// the launch has restart off, no turn of it recycles a room.  Record loads as the layout's default (plain: stream_loads above)
+constexpr int LD_NO_RECYCLE = 3;
 template <int WORDS, bool NT = false>
 __device__ __forceinline__ void load_words(const uint32_t *base, uint64_t rooms_padded, uint64_t room, uint32_t *w) {
     constexpr int NP = (WORDS + 3) / 4;
@@ -313,38 +316,76 @@ __device__ __forceinline__ void run_ww(const SegDev *__restrict__ sgp, const Ste
         // terminal row (ge_device.h WwRestart), not by a divergent block at the head of the next turn - that block was two dozen
         // register moves on four turns of five (some room of 64 finishes) and a branch on every turn.  Rooms that are terminal
         // as loaded are recycled once, in front of the loop
+        // GE_TAIL_KNOWN_RESTART: whether a turn of the tail form recycles is compiled in (ge_device.h TAIL_RECYCLE / TAIL_KEEP).  This kernel
+        // (LD = 0) is then launched with restart on only (ge_step.hip launch_kind): n_turns - 1 recycling turns in the loop, and the
+        // launch's last turn, which stores terminal rooms as they are, once behind it - straight-line code, not a second loop.  Restart
+        // off is the kernel LD = LD_NO_RECYCLE, whose loop is the form that never recycles.  (The head form, and with the switch at 0
+        // the tail form, read a.restart at run time: the loop below them.)
         auto turns = [&](auto trace_c, auto tail_c) {
             constexpr bool KNOWN = decltype(trace_c)::value != 2;
             constexpr bool TAILR = decltype(tail_c)::value;
             const bool trace = KNOWN ? decltype(trace_c)::value == 1 : a.trace != 0u;
             uint32_t restarted_in = 0;
             WwRestart<NB> rst = {&s0, 0u, 0u, 0u};
-            uint32_t term_r = a.restart ? term_mask : 0u;
-            if (TAILR) asm volatile("" : "+s"(term_r));          // one scalar across the loop, not the test of a.restart again on every turn
-            if (TAILR && a.restart && a.n_turns != 0u && ((row.r0 >> 11) & 7u) == 0u) {   // finished as loaded
-                const uint32_t g = s.games;
-                s = s0;
-                s.games = g < 0xFFFFu ? g + 1u : g;
-                row = row0;
-                restarted_in = 1;
-            }
-            for (uint32_t t = 0; t < a.n_turns; t++) {
-                uint32_t restarted = TAILR ? restarted_in : 0u;
-                if (!TAILR && a.restart && ((row.r0 >> 11) & 7u) == 0u) {      // recycle a finished room
-                    const uint32_t g = s.games;
-                    s = LOWOCC ? s0 : fresh_room();
-                    s.games = g < 0xFFFFu ? g + 1u : g;
-                    row = LOWOCC ? row0 : lds_row<!LOWOCC && !SINGLE>(rows, ctx.phase0_idx);
-                    restarted = 1;
+            if constexpr (TAILR && GE_TAIL_KNOWN_RESTART) {
+                constexpr bool RECYCLES = LD != LD_NO_RECYCLE;
+                if (a.n_turns == 0u) return;
+                if constexpr (RECYCLES) {
+                    uint32_t term_r = term_mask;
+                    asm volatile("" : "+s"(term_r));             // one scalar across the loop
+                    rst.term_rs = term_r;
                 }
-                const uint32_t p = s.phase;
-                uint32_t ev_newly = 0;
-                uint64_t ev_choice = 0;
-                const bool deal_now = ahead && ((deal_phase + t) & (deal_period<NB>() - 1u)) == 0u;    // wave-uniform
-                if (TAILR) rst.term_rs = t + 1u < a.n_turns ? term_r : 0u;           // (the launch's last turn stores terminal rooms as they are)
-                ww_turn<NB, LOWOCC, GENERIC, false, TAILR>(s, row, ctx, turn0 + t, tk, trace, deal, deal_now, ev_newly, ev_choice, (GE_STAMPS && a.stamps) ? &stamps : nullptr, &rst);
-                if (trace && valid) store_event(sg.trace, sg.rooms_padded, t, room, turn0 + t, p, TAILR ? rst.q : s.phase, restarted, ev_newly, ev_choice);
-                if (TAILR) restarted_in = rst.restarted;
+                if (RECYCLES && ((row.r0 >> 11) & 7u) == 0u) {   // finished as loaded
+                    const uint32_t g = s.games;
+                    s = s0;
+                    s.games = g < 0xFFFFu ? g + 1u : g;
+                    row = row0;
+                    restarted_in = 1;
+                }
+                auto one_turn = [&](auto form_c, uint32_t t) __attribute__((always_inline)) {
+                    const uint32_t restarted = restarted_in, p = s.phase;
+                    uint32_t ev_newly = 0;
+                    uint64_t ev_choice = 0;
+                    const bool deal_now = ahead && ((deal_phase + t) & (deal_period<NB>() - 1u)) == 0u;    // wave-uniform
+                    ww_turn<NB, LOWOCC, GENERIC, false, decltype(form_c)::value>(s, row, ctx, turn0 + t, tk, trace, deal, deal_now, ev_newly, ev_choice, (GE_STAMPS && a.stamps) ? &stamps : nullptr, &rst);
+                    if (trace && valid) store_event(sg.trace, sg.rooms_padded, t, room, turn0 + t, p, rst.q, restarted, ev_newly, ev_choice);
+                    restarted_in = rst.restarted;
+                };
+                if constexpr (RECYCLES) {
+                    const uint32_t last = a.n_turns - 1u;
+                    for (uint32_t t = 0; t < last; t++) one_turn(std::integral_constant<int, TAIL_RECYCLE>{}, t);
+                    one_turn(std::integral_constant<int, TAIL_KEEP>{}, last);        // (stores terminal rooms as they are)
+                } else {
+                    for (uint32_t t = 0; t < a.n_turns; t++) one_turn(std::integral_constant<int, TAIL_KEEP>{}, t);
+                }
+            } else {
+                uint32_t term_r = a.restart ? term_mask : 0u;
+                if (TAILR) asm volatile("" : "+s"(term_r));          // one scalar across the loop, not the test of a.restart again on every turn
+                if (TAILR && a.restart && a.n_turns != 0u && ((row.r0 >> 11) & 7u) == 0u) {   // finished as loaded
+                    const uint32_t g = s.games;
+                    s = s0;
+                    s.games = g < 0xFFFFu ? g + 1u : g;
+                    row = row0;
+                    restarted_in = 1;
+                }
+                for (uint32_t t = 0; t < a.n_turns; t++) {
+                    uint32_t restarted = TAILR ? restarted_in : 0u;
+                    if (!TAILR && a.restart && ((row.r0 >> 11) & 7u) == 0u) {      // recycle a finished room
+                        const uint32_t g = s.games;
+                        s = LOWOCC ? s0 : fresh_room();
+                        s.games = g < 0xFFFFu ? g + 1u : g;
+                        row = LOWOCC ? row0 : lds_row<!LOWOCC && !SINGLE>(rows, ctx.phase0_idx);
+                        restarted = 1;
+                    }
+                    const uint32_t p = s.phase;
+                    uint32_t ev_newly = 0;
+                    uint64_t ev_choice = 0;
+                    const bool deal_now = ahead && ((deal_phase + t) & (deal_period<NB>() - 1u)) == 0u;    // wave-uniform
+                    if (TAILR) rst.term_rs = t + 1u < a.n_turns ? term_r : 0u;           // (the launch's last turn stores terminal rooms as they are)
+                    ww_turn<NB, LOWOCC, GENERIC, false, TAILR ? TAIL_RUNTIME : TAIL_NONE>(s, row, ctx, turn0 + t, tk, trace, deal, deal_now, ev_newly, ev_choice, (GE_STAMPS && a.stamps) ? &stamps : nullptr, &rst);
+                    if (trace && valid) store_event(sg.trace, sg.rooms_padded, t, room, turn0 + t, p, TAILR ? rst.q : s.phase, restarted, ev_newly, ev_choice);
+                    if (TAILR) restarted_in = rst.restarted;
+                }
             }
         };
         if constexpr (B::LONE && !GENERIC && !MIXED) {             // (the generic and the mixed kernels hold their scalar registers to the limit already: the fresh room would spill)

@@ -123,7 +123,7 @@ def label(r):
     form = "single-turn" if r["single"] else "fused"
     occ = "lone-wavefront" if r["lowocc"] else "large-batch"
     shape = {0: "", 1: ", GENERIC", 2: ", GENERIC 1 x 1", 3: ", GENERIC 1 x 2"}[int(r["generic"])]
-    return f"{r['layout']}, {occ}, {form}{shape}" + {0: "", 1: ", plain record loads", 2: ", streaming record loads"}[r.get("ld", 0)]
+    return f"{r['layout']}, {occ}, {form}{shape}" + {0: "", 1: ", plain record loads", 2: ", streaming record loads", 3: ", restart off"}[r.get("ld", 0)]
 
 
 def markdown(rows):
