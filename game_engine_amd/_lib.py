@@ -68,12 +68,13 @@ class CompareStats(C.Structure):
 
 
 COMPARE_WORDS = C.sizeof(CompareStats) // 8      # 6
+BELIEF_SLOTS = 16                                # GE_BELIEF_SLOTS
 
 # every symbol include/ge_step.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = ["ge_table_compile_json", "ge_batch_create", "ge_batch_step", "ge_batch_reset", "ge_batch_set_turn", "ge_batch_inject_actions", "ge_batch_sync", "ge_batch_turn",
            "ge_batch_n_rooms", "ge_batch_read_rooms", "ge_batch_write_rooms", "ge_batch_read_events", "ge_batch_inject_action", "ge_batch_summary",
            "ge_batch_state", "ge_batch_set_timing", "ge_batch_kernel_time", "ge_batch_destroy", "ge_batch_step_rooms", "ge_batch_read_rooms_at",
-           "ge_batch_write_rooms_at", "ge_batch_rollout_rooms", "ge_batch_rollout_actions", "ge_batch_rollout_seats", "ge_batch_rollout_compare", "ge_batch_step_rooms_playout", "ge_batch_run_rooms", "ge_batch_run_rooms_playout", "ge_batch_run_rooms_forecast", "ge_group_partition", "ge_batch_create_shard", "ge_group_create", "ge_group_size", "ge_group_shard", "ge_group_step", "ge_group_sync", "ge_group_summary", "ge_group_destroy",
+           "ge_batch_write_rooms_at", "ge_batch_rollout_rooms", "ge_batch_rollout_actions", "ge_batch_rollout_seats", "ge_batch_rollout_compare", "ge_batch_rollout_beliefs", "ge_batch_step_rooms_playout", "ge_batch_run_rooms", "ge_batch_run_rooms_playout", "ge_batch_run_rooms_forecast", "ge_group_partition", "ge_batch_create_shard", "ge_group_create", "ge_group_size", "ge_group_shard", "ge_group_step", "ge_group_sync", "ge_group_summary", "ge_group_destroy",
            "ge_strerror", "ge_last_hip_error", "ge_last_rejected_room", "ge_last_comm_error", "ge_abi_version", "ge_device_count"]
 
 _lib = None
@@ -149,6 +150,8 @@ def load() -> C.CDLL:
         lib.ge_batch_rollout_seats.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u64, vp]
     if hasattr(lib, "ge_batch_rollout_compare") or not any_abi:
         lib.ge_batch_rollout_compare.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u64, vp, vp, vp, vp]
+    if hasattr(lib, "ge_batch_rollout_beliefs") or not any_abi:
+        lib.ge_batch_rollout_beliefs.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, u64, vp, vp, vp, vp]
     if hasattr(lib, "ge_batch_step_rooms_playout") or not any_abi:
         lib.ge_batch_step_rooms_playout.argtypes = [vp, u64, vp, vp, vp, vp, vp, u32, u32, u64, u32, vp, vp]
     if hasattr(lib, "ge_batch_run_rooms") or not any_abi:

@@ -1,7 +1,8 @@
 // ge_compare.inl — paired comparison of playout entries (ge_batch_rollout_compare, POLICY.md §3e): entry k against its baseline
 // entry, playout by playout (included at the end of ge_step.hip, behind ge_playout.inl: the existing kernels keep their
 // code-object offsets).  The call is rollout_call of ge_rollout.inl with act = 3: its checks, its chunk staging over ge_pool.inl's
-// PoolEntries and its launch by kind; what this file adds is the comparison kernel behind the playouts and the entry point.
+// PoolEntries and its launch by kind; what this file adds is the comparison kernel behind the playouts and the entry point
+// (and ge_batch_rollout_beliefs's, which is either call under POLICY.md §3j).
 //
 // The playouts are ge_batch_rollout_seats's, launched as form ACT = 3 of ge_rollout_kernel (ge_rollout.inl): the same turns and
 // the same reduction, and one byte more per lane - the outcome X of its replica for the entry's subject seat - stored into the
@@ -83,6 +84,19 @@ int ge_batch_rollout_compare(ge_batch *b, uint64_t n, const uint64_t *rooms, con
                              const uint32_t *subjects, ge_compare_stats *cmp) {
     RollRequest r = {n, rooms, keys, turns, seats, first_action, player_ids, choices, entry_status, n_rollouts, max_turns, seed, out, 3};
     r.baseline = baseline; r.subjects = subjects; r.cmp = cmp;
+    return rollout_call(b, r);
+}
+
+// ge_batch_rollout_seats (no comparison arrays) or ge_batch_rollout_compare under the entries' beliefs (POLICY.md §3j): forms
+// ACT = 6 / 7 of ge_rollout_kernel.  Some but not all of the comparison arrays: act 3, whose first check refuses the call
+int ge_batch_rollout_beliefs(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, const uint32_t *seats,
+                             const uint32_t *first_action, const uint32_t *player_ids, const uint32_t *choices, int32_t *entry_status,
+                             const uint8_t *beliefs, uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, ge_rollout_stats *out,
+                             const uint32_t *baseline, const uint32_t *subjects, ge_compare_stats *cmp) {
+    const bool comparing = baseline || subjects || cmp;
+    RollRequest r = {n, rooms, keys, turns, seats, first_action, player_ids, choices, entry_status, n_rollouts, max_turns, seed, out, comparing ? 3 : 2};
+    r.baseline = baseline; r.subjects = subjects; r.cmp = cmp;
+    r.weighted = true; r.beliefs = beliefs;
     return rollout_call(b, r);
 }
 

@@ -56,6 +56,15 @@
 // accumulator row is t * n_all + i (turn-major, as the trace plane).  A block whose t is not below the run's played[i] - read
 // from device memory, wave-uniform - returns before it loads or reduces anything.
 //
+// Playouts from a seat's view weighted by the caller's beliefs (ge_batch_rollout_beliefs, ACT = 6, and ACT = 7 with the outcome
+// plane of ACT = 3; POLICY.md §3j).  Everything ACT = 2 / ACT = 3 does, except that the two draws of the re-deal that decide
+// what the seat cannot see - which seats of Uq are wolves, which statement is the lie - are successive weighted draws by the
+// entry's 16 belief bytes.  The bytes are the same in every lane and are taken into four scalar registers; the pick is a
+// per-lane running sum over the statically indexed seats of the lane's shrinking `rem` mask (no array indexed by a seat: no
+// scratch), so only the draw and `rem` are per lane.  Cost against ACT = 2 on the same entries, measured
+// (profiles/beliefs_probe.txt): 65 536 playouts x 1 024 turns per layout 0.96 .. 1.02 x the unweighted call, within the run-to-run
+// spread; the single advise call (8 entries x 4 096) x 1.03 .. 1.04 (0.169 / 0.170 against 0.163 ms).
+//
 // Playouts that keep their outcome (ge_batch_rollout_compare, ACT = 3; ge_compare.inl).  Everything ACT = 2 does; then each lane
 // stores the outcome X of its replica for seat subjects[e] - Werewolf: the seat's team has won, Two-Truths: the seat's
 // total_score - as one byte of the entry's row of the outcome plane (waves * 64 bytes per row: a wavefront's lanes write 64
@@ -105,6 +114,17 @@ template <> struct RollArgs<5> : RollArgs<2> {
     const u32x2 *run_out;           // [n]: the run's (played, stop bits)
     uint32_t n_all, first;          // this launch's entries are the plane's entries first .. first + n - 1
 };
+
+// ACT = 6 / 7: ACT = 2 / 3 under the entry's beliefs (POLICY.md §3j): entry e's 16 bytes are beliefs[e], byte c = seat c + 1
+// (Werewolf) or statement c + 1 (Two-Truths)
+template <> struct RollArgs<6> : RollArgs<2> {
+    const u32x4 *beliefs;
+};
+template <> struct RollArgs<7> : RollArgs<3> {
+    const u32x4 *beliefs;
+};
+constexpr bool roll_weighted(int act) { return act == 6 || act == 7; }
+constexpr bool roll_keeps(int act) { return act == 3 || act == 7; }
 
 struct RollLane {
     RoomStats q;                // (zero on lanes past R)
@@ -215,10 +235,43 @@ __device__ __forceinline__ bool roll_act_tt(const SegDev &sg, const DevTable *__
 // ---- the view re-deal (POLICY.md §3c).  vk = the replica's view key.
 __device__ __forceinline__ uint32_t view_key(uint32_t rk, uint32_t turn0) { return mix32(rk ^ 0x56494557u ^ (turn0 * GOLDEN)); }
 
+// an entry's beliefs in scalar registers (the same in every lane); byte c of the 16
+struct Beliefs {
+    uint32_t w[4];
+    __device__ __forceinline__ uint32_t at(int c) const { return (w[c >> 2] >> (8 * (c & 3))) & 255u; }
+};
+__device__ __forceinline__ Beliefs roll_beliefs(const u32x4 *beliefs, uint32_t e) {
+    const u32x4 v = beliefs[e];
+    Beliefs b;
+    b.w[0] = (uint32_t)__builtin_amdgcn_readfirstlane(v.x); b.w[1] = (uint32_t)__builtin_amdgcn_readfirstlane(v.y);
+    b.w[2] = (uint32_t)__builtin_amdgcn_readfirstlane(v.z); b.w[3] = (uint32_t)__builtin_amdgcn_readfirstlane(v.w);
+    return b;
+}
+
+// the weighted pick of POLICY.md §3j over the first N slots of `rem` (bit c = slot c may be taken; cnt >= 1 of them,
+// wave-uniform): the bit of the first slot whose running sum of weights exceeds x = pick(d, W), W the sum over `rem`; W == 0:
+// every weight 1.  The running sum grows only at a slot of `rem` with a weight, so the lowest slot at which it exceeds x is
+// such a slot.
+template <int N> __device__ __forceinline__ uint32_t weighted_pick(const Beliefs &bw, uint32_t rem, uint32_t cnt, uint32_t d) {
+    uint32_t W = 0;
+#pragma unroll
+    for (int c = 0; c < N; c++) W += ((rem >> c) & 1u) ? bw.at(c) : 0u;
+    const bool flat = W == 0u;
+    const uint32_t x = pick(d, flat ? cnt : W);
+    uint32_t acc = 0, over = 0;
+#pragma unroll
+    for (int c = 0; c < N; c++) {
+        acc += ((rem >> c) & 1u) ? (flat ? 1u : bw.at(c)) : 0u;
+        over |= (acc > x ? 1u : 0u) << c;
+    }
+    return over & (0u - over);
+}
+
 // Werewolf: the hidden tuples of the seats seat s cannot rule out, dealt again over the seats they may sit on.  `u` holds the
 // record (wave-uniform on entry); priv = the phase's action log is private (WOLF_TARGET / DOCTOR_PROTECT / DETECTIVE).
-template <int NB>
-__device__ __forceinline__ void view_redeal_ww(WW<NB> &u, uint32_t seat, uint32_t n, bool priv, uint32_t vk) {
+// WT: step 1 places the wolves by the beliefs `bw` (POLICY.md §3j) instead of uniformly.
+template <int NB, bool WT = false>
+__device__ __forceinline__ void view_redeal_ww(WW<NB> &u, uint32_t seat, uint32_t n, bool priv, uint32_t vk, const Beliefs &bw = Beliefs{}) {
     constexpr int S = NB <= 8 ? 8 : 16;                      // bit-plane stride in a bundle
     constexpr uint64_t REP = NB <= 8 ? 0x0101010101010101ull : 0x0001000100010001ull;
     const uint32_t all = (1u << n) - 1u, me = 1u << (seat - 1u);
@@ -257,7 +310,9 @@ __device__ __forceinline__ void view_redeal_ww(WW<NB> &u, uint32_t seat, uint32_
     // step 1: the wolf seats.  Every count is uniform, so no lane needs a popcount
     uint32_t sw = Uw, rem = Uq;
     for (uint32_t j = 0; j < need; j++) {
-        const uint32_t bit = 1u << nth_set_bit<NB>(rem, pick(draw(vk, 32u + j), popc(Uq) - j));
+        uint32_t bit;
+        if constexpr (WT) bit = weighted_pick<NB>(bw, rem, popc(Uq) - j, draw(vk, 32u + j));
+        else bit = 1u << nth_set_bit<NB>(rem, pick(draw(vk, 32u + j), popc(Uq) - j));
         sw |= bit; rem &= ~bit;
     }
     uint32_t remW = sw, remV = U & ~sw;
@@ -314,19 +369,24 @@ __device__ __forceinline__ void view_redeal_ww(WW<NB> &u, uint32_t seat, uint32_
 }
 
 // Two-Truths: the speaker's lie, drawn again for a seat that is not the speaker, before the reveal (`s` wave-uniform)
-template <int NB> __device__ __forceinline__ void view_redeal_tt(TT<NB> &s, uint32_t seat, uint32_t vk) {
+// WT: the lie is drawn by the beliefs' first three bytes (POLICY.md §3j)
+template <int NB, bool WT = false>
+__device__ __forceinline__ void view_redeal_tt(TT<NB> &s, uint32_t seat, uint32_t vk, const Beliefs &bw = Beliefs{}) {
     const uint32_t spk = (uint32_t)__builtin_amdgcn_readfirstlane(s.speaker), lie = (uint32_t)__builtin_amdgcn_readfirstlane(s.lie);
     const uint32_t rev = (uint32_t)__builtin_amdgcn_readfirstlane(s.revealed);
     if (spk == 0u) return;
     const uint32_t sp = ctz(spk);                            // the lowest speaker
     if (sp == seat - 1u || ((rev >> sp) & 1u) || ((lie >> (2 * sp)) & 3u) == 0u) return;
-    s.lie = (lie & ~(3u << (2 * sp))) | (1u + pick(draw(vk, 80u), 3u)) << (2 * sp);
+    uint32_t fresh;
+    if constexpr (WT) fresh = 1u + ctz(weighted_pick<3>(bw, 7u, 3u, draw(vk, 80u)));
+    else fresh = 1u + pick(draw(vk, 80u), 3u);
+    s.lie = (lie & ~(3u << (2 * sp))) | fresh << (2 * sp);
 }
 
 // the ACT = 2 prologue of a Werewolf entry: the record words after the actions, re-dealt for the entry's seat in this lane
-template <int NB>
+template <int NB, bool WT = false>
 __device__ __forceinline__ void roll_view_ww(const SegDev &sg, const DevTable *__restrict__ tables, const RollArgs<2> &a, uint32_t e,
-                                             uint32_t rk, uint32_t turn0, uint32_t *w) {
+                                             uint32_t rk, uint32_t turn0, uint32_t *w, const u32x4 *beliefs = nullptr) {
     using L = WWLayout<NB>;
     const uint32_t seat = (uint32_t)__builtin_amdgcn_readfirstlane(a.seats[e]);
     if (seat == 0u) return;
@@ -335,7 +395,9 @@ __device__ __forceinline__ void roll_view_ww(const SegDev &sg, const DevTable *_
     WW<NB> u;
     L::unpack(w, u);
     const uint32_t act = (tables[sg.table_idx].rows[u.phase].r0 >> 2) & 7u;
-    view_redeal_ww<NB>(u, seat, sg.n_players, act == ACT_WOLF_TARGET || act == ACT_DOCTOR_PROTECT || act == ACT_DETECTIVE, view_key(rk, turn0));
+    const bool priv = act == ACT_WOLF_TARGET || act == ACT_DOCTOR_PROTECT || act == ACT_DETECTIVE;
+    if constexpr (WT) view_redeal_ww<NB, true>(u, seat, sg.n_players, priv, view_key(rk, turn0), roll_beliefs(beliefs, e));
+    else view_redeal_ww<NB>(u, seat, sg.n_players, priv, view_key(rk, turn0));
     L::pack(u, w);
 }
 
@@ -369,7 +431,8 @@ __device__ __forceinline__ void roll_ww(const SegDev &sg, const DevTable *__rest
         if (!roll_act_ww<NB>(sg, tables, a, e, r_in, w)) return;
     const uint64_t g = key + r;
     const uint32_t rk = room_key_from(a.seed_key, g);
-    if constexpr (ACT >= 2) roll_view_ww<NB>(sg, tables, a, e, rk, turn0, w);
+    if constexpr (roll_weighted(ACT)) roll_view_ww<NB, true>(sg, tables, a, e, rk, turn0, w, a.beliefs);
+    else if constexpr (ACT >= 2) roll_view_ww<NB>(sg, tables, a, e, rk, turn0, w);
     const uint32_t phase0 = __builtin_amdgcn_readfirstlane(sg.phase0_idx);
     const WwCtx ctx = lane_ww_ctx<GENERIC, false>(sg, tables, lw, rk, true);   // every seat played by the policy
     const DevRow *rows = ctx.rows;
@@ -393,7 +456,7 @@ __device__ __forceinline__ void roll_ww(const SegDev &sg, const DevTable *__rest
     uint32_t score[NB];
 #pragma unroll
     for (int i = 0; i < NB; i++) score[i] = 0u;
-    if constexpr (ACT == 3) {
+    if constexpr (roll_keeps(ACT)) {
         const uint32_t subj = (uint32_t)__builtin_amdgcn_readfirstlane(a.subjects[e]) - 1u;
         roll_keep(a, e, r_in, valid ? (l.win_mask >> subj) & 1u : 0u);
     }
@@ -439,7 +502,9 @@ __device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__rest
         if (!roll_act_tt<NB>(sg, tables, a, e, r_in, s)) return;
     if constexpr (ACT >= 2) {
         const uint32_t seat = (uint32_t)__builtin_amdgcn_readfirstlane(a.seats[e]);
-        if (seat != 0u) view_redeal_tt<NB>(s, seat, view_key(rk, turn0));
+        if constexpr (roll_weighted(ACT)) {
+            if (seat != 0u) view_redeal_tt<NB, true>(s, seat, view_key(rk, turn0), roll_beliefs(a.beliefs, e));
+        } else if (seat != 0u) view_redeal_tt<NB>(s, seat, view_key(rk, turn0));
     }
     uint32_t done = tt_done_mask<NB>(s.rounds, sg.rounds);
     for (uint32_t t = 0; t < a.max_turns; t++) {
@@ -467,7 +532,7 @@ __device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__rest
 #pragma unroll
         for (int i = 0; i < NB; i++) score[i] = 0u;
     }
-    if constexpr (ACT == 3) {
+    if constexpr (roll_keeps(ACT)) {
         const uint32_t subj = (uint32_t)__builtin_amdgcn_readfirstlane(a.subjects[e]) - 1u;
         uint32_t x = 0;
 #pragma unroll
@@ -509,7 +574,8 @@ uint32_t rollout_settle_mask(const Segment &sg) {
 
 // one call of the three entry points.  first_action null: every entry's slice is empty; seats null: the full view.  act is the
 // kernel form the call launches: 0 = ge_batch_rollout_rooms, 1 = ge_batch_rollout_actions, 2 = ge_batch_rollout_seats,
-// 3 = ge_batch_rollout_compare (ge_compare.inl; baseline / subjects / cmp are its own)
+// 3 = ge_batch_rollout_compare (ge_compare.inl; baseline / subjects / cmp are its own); `weighted` launches 2 as 6 and 3 as 7
+// (ge_batch_rollout_beliefs, ge_compare.inl)
 struct RollRequest {
     uint64_t n;
     const uint64_t *rooms, *keys;
@@ -521,16 +587,20 @@ struct RollRequest {
     int act;
     const uint32_t *baseline = nullptr, *subjects = nullptr;
     ge_compare_stats *cmp = nullptr;
+    bool weighted = false;                                    // ge_batch_rollout_beliefs: act 2 or 3 under `beliefs` (POLICY.md §3j)
+    const uint8_t *beliefs = nullptr;                         // n x GE_BELIEF_SLOTS
 };
 
 // one chunk's staging: the upload [rooms u64 x cn][keys u64 x cn][turns u32 x cn]; with actions [first u32 x (cn + 1)]
 // [players u32 x na][choices u32 x na], with seats [seats u32 x cn]; each array from a 16 B boundary.  Then the download:
 // [status i32 x cn] (with actions), the accumulators 8 B x ROLL_STRIDE x cn.  A comparing call (act 3) uploads [subjects u32 x cn]
 // [baseline u32 x cn] (sorted positions) behind the seats and downloads [ge_compare_stats x cn] behind the accumulators; its
-// outcome plane lies behind `total` on the device only (dev_total), so the pinned host buffer does not grow by it
+// outcome plane lies behind `total` on the device only (dev_total), so the pinned host buffer does not grow by it.  A weighted call
+// uploads [beliefs 16 B x cn] behind those, in front of the status words
 struct RollStage {
     size_t keys, turns, first, players, choices, seats, status, acc, total;
     size_t subjects, baseline, cmp, plane, dev_total;
+    size_t beliefs;
 };
 
 // ge_compare.inl: the paired sums of a comparing call's chunk staged at dev, behind its playouts on stream s
@@ -547,10 +617,11 @@ template <int ACT> RollArgs<ACT> rollout_form_args(const RolloutArgs &base, char
         a.status = reinterpret_cast<int32_t *>(dev + o.status) + lo;
     }
     if constexpr (ACT >= 2) a.seats = reinterpret_cast<const uint32_t *>(dev + o.seats) + lo;
-    if constexpr (ACT == 3) {
+    if constexpr (roll_keeps(ACT)) {
         a.subjects = reinterpret_cast<const uint32_t *>(dev + o.subjects) + lo;
         a.plane = reinterpret_cast<unsigned char *>(dev + o.plane) + (size_t)lo * ((size_t)base.waves * 64u);
     }
+    if constexpr (roll_weighted(ACT)) a.beliefs = reinterpret_cast<const u32x4 *>(dev + o.beliefs) + lo;
     return a;
 }
 
@@ -601,7 +672,8 @@ static int rollout_rooms_impl(ge_batch *b, const RollRequest &r) {
         o.choices = up16(o.players + 4 * (size_t)na); o.seats = up16(o.choices + 4 * (size_t)na);
         o.subjects = up16(o.seats + (view ? 4 * (size_t)cn : 0u));
         o.baseline = up16(o.subjects + (cmp ? 4 * (size_t)cn : 0u));
-        o.status = up16(o.baseline + (cmp ? 4 * (size_t)cn : 0u));
+        o.beliefs = up16(o.baseline + (cmp ? 4 * (size_t)cn : 0u));
+        o.status = up16(o.beliefs + (r.weighted ? (size_t)GE_BELIEF_SLOTS * cn : 0u));
         o.acc = act ? up16(o.status + 4 * (size_t)cn) : o.first;
         const size_t acc_bytes = 8 * (size_t)ROLL_STRIDE * cn;
         o.cmp = o.acc + acc_bytes;
@@ -633,6 +705,9 @@ static int rollout_rooms_impl(ge_batch *b, const RollRequest &r) {
                 for (uint32_t i = 0; i < cn; i++) pos[order[i]] = i;
                 for (uint32_t i = 0; i < cn; i++) { h_subj[i] = r.subjects[c0 + order[i]]; h_base[i] = pos[r.baseline[c0 + order[i]]]; }
             }
+            if (r.weighted)
+                for (uint32_t i = 0; i < cn; i++)
+                    memcpy(host + o.beliefs + (size_t)GE_BELIEF_SLOTS * i, r.beliefs + (size_t)GE_BELIEF_SLOTS * (c0 + order[i]), GE_BELIEF_SLOTS);
             memset(host + o.status, 0, 4 * (size_t)cn);         // GE_OK unless the device refuses the entry
         }
         char *dev = nullptr;
@@ -652,6 +727,7 @@ static int rollout_rooms_impl(ge_batch *b, const RollRequest &r) {
             a.n = cnt; a.seg = g; a.seed_key = seed_k; a.n_rollouts = r.n_rollouts; a.max_turns = r.max_turns; a.waves = waves;
             a.settle_mask = settle[g];
             HIP_TRY((r.act == 0 ? rollout_launch_form<0>(b, s, a, dev, o, lo)
+                     : r.weighted ? (cmp ? rollout_launch_form<7>(b, s, a, dev, o, lo) : rollout_launch_form<6>(b, s, a, dev, o, lo))
                      : cmp      ? rollout_launch_form<3>(b, s, a, dev, o, lo)
                      : view     ? rollout_launch_form<2>(b, s, a, dev, o, lo)
                                 : rollout_launch_form<1>(b, s, a, dev, o, lo)));
@@ -702,6 +778,15 @@ static int rollout_call(ge_batch *b, const RollRequest &r) {
     if (r.seats)
         for (uint64_t k = 0; k < n; k++)                      // (rooms[k] is in range: its segment is known)
             if (r.seats[k] > b->segs[pool_segment_of(b, r.rooms[k])].dev.n_players) return GE_ERR_ARG;
+    if (r.weighted) {                                         // ge_batch_rollout_beliefs's own, behind ge_batch_rollout_seats's
+        if (!r.beliefs) return GE_ERR_ARG;
+        for (uint64_t k = 0; k < n; k++) {                    // a byte past the room's slots is a wrong stride, not a belief
+            const SegDev &sd = b->segs[pool_segment_of(b, r.rooms[k])].dev;
+            const uint32_t slots = (sd.kind == K_WW8 || sd.kind == K_WW12) ? sd.n_players : 3u;
+            for (uint32_t c = slots; c < GE_BELIEF_SLOTS; c++)
+                if (r.beliefs[(size_t)GE_BELIEF_SLOTS * k + c]) return GE_ERR_ARG;
+        }
+    }
     if (r.act == 3) {                                         // ge_batch_rollout_compare's own, behind ge_batch_rollout_seats's
         if (!r.baseline || !r.subjects || !r.cmp || n > 65536u) return GE_ERR_ARG;   // one staging chunk: an entry and its baseline are resident together
         for (uint64_t k = 0; k < n; k++)

@@ -713,14 +713,16 @@ bool is_nullish(napi_env env, napi_value v) {
 // index.js's rolloutRooms / rolloutActions / rolloutSeats: ge_batch_rollout_seats with seats, else ge_batch_rollout_actions with
 // actions, else ge_batch_rollout_rooms.  A refused entry's words are 0 and its status < 0.  Two more arguments, baseline and
 // subjects (Uint32Array of rooms.length each, with seats): index.js's rolloutCompare, ge_batch_rollout_compare; the result gains
-// cmp: BigUint64Array of rooms.length x 6 (ge_compare_stats k at [6 k, 6 k + 6))
+// cmp: BigUint64Array of rooms.length x 6 (ge_compare_stats k at [6 k, 6 k + 6)).  One more, beliefs (Uint8Array of rooms.length x
+// GE_BELIEF_SLOTS, with seats): index.js's rolloutBeliefs, ge_batch_rollout_beliefs - with or without baseline and subjects
 napi_value Rollout(napi_env env, napi_callback_info info) {
-    size_t argc = 13;
-    napi_value argv[13];
+    size_t argc = 14;
+    napi_value argv[14];
     NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
     const bool seats = argc > 4 && !is_nullish(env, argv[4]), acts = argc > 5 && !is_nullish(env, argv[5]);
     const bool compare = argc > 12 && !is_nullish(env, argv[11]) && !is_nullish(env, argv[12]);
-    const char *what = compare ? "rolloutCompare" : seats ? "rolloutSeats" : acts ? "rolloutActions" : "rolloutRooms";
+    const bool weighted = argc > 13 && !is_nullish(env, argv[13]);
+    const char *what = weighted ? "rolloutBeliefs" : compare ? "rolloutCompare" : seats ? "rolloutSeats" : acts ? "rolloutActions" : "rolloutRooms";
     ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
     if (!b || argc < 11) return throw_status(env, GE_ERR_ARG, what);
     // rooms, keys, turns, then seats and firstAction, playerIds, choices where given
@@ -761,6 +763,20 @@ napi_value Rollout(napi_env env, napi_callback_info info) {
         base = static_cast<const uint32_t *>(cd[0]);
         subj = static_cast<const uint32_t *>(cd[1]);
     }
+    const uint8_t *beliefs = nullptr;
+    if (weighted) {
+        napi_typedarray_type bt;
+        size_t bl;
+        void *bd;
+        napi_value ab;
+        size_t off;
+        if (napi_get_typedarray_info(env, argv[13], &bt, &bl, &bd, &ab, &off) != napi_ok)
+            return throw_status(env, GE_ERR_ARG, what, "typed arrays expected");
+        const bool partial = argc > 12 && (is_nullish(env, argv[11]) != is_nullish(env, argv[12]));
+        if (!seats || partial || bt != napi_uint8_array || bl != len[0] * GE_BELIEF_SLOTS)
+            return throw_status(env, GE_ERR_ARG, what, "seats; beliefs: Uint8Array of 16 bytes per entry; baseline and subjects together or neither");
+        beliefs = static_cast<const uint8_t *>(bd);
+    }
     uint32_t n_rollouts = 0, max_turns = 0;
     uint64_t seed = 0;
     if (napi_get_value_uint32(env, argv[8], &n_rollouts) != napi_ok || napi_get_value_uint32(env, argv[9], &max_turns) != napi_ok ||
@@ -785,7 +801,9 @@ napi_value Rollout(napi_env env, napi_callback_info info) {
     const uint32_t *first = static_cast<const uint32_t *>(data[4]), *pl = static_cast<const uint32_t *>(data[5]);
     const uint32_t *ch = static_cast<const uint32_t *>(data[6]);
     ge_rollout_stats *o = static_cast<ge_rollout_stats *>(out);
-    const int st = compare ? ge_batch_rollout_compare(b, len[0], rooms, keys, turns, sv, first, pl, ch, status, n_rollouts, max_turns, seed, o,
+    const int st = weighted ? ge_batch_rollout_beliefs(b, len[0], rooms, keys, turns, sv, first, pl, ch, status, beliefs, n_rollouts, max_turns,
+                                                       seed, o, base, subj, static_cast<ge_compare_stats *>(cmp_data))
+                   : compare ? ge_batch_rollout_compare(b, len[0], rooms, keys, turns, sv, first, pl, ch, status, n_rollouts, max_turns, seed, o,
                                                       base, subj, static_cast<ge_compare_stats *>(cmp_data))
                    : seats ? ge_batch_rollout_seats(b, len[0], rooms, keys, turns, sv, first, pl, ch, status, n_rollouts, max_turns, seed, o)
                    : acts ? ge_batch_rollout_actions(b, len[0], rooms, keys, turns, first, pl, ch, status, n_rollouts, max_turns, seed, o)

@@ -118,6 +118,13 @@ export class RoomBatch {
   rolloutCompare(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, seats: ArrayLike<number>,
                  actions: ArrayLike<ArrayLike<[number, number]>> | null, baseline: ArrayLike<number>, subjects: ArrayLike<number>,
                  nRollouts?: number, maxTurns?: number, seed?: bigint | number): { words: BigUint64Array; status: Int32Array; cmp: BigUint64Array };
+  /** rolloutSeats - with baseline and subjects, rolloutCompare - under the caller's beliefs (POLICY.md §3j): 16 bytes per entry, byte c
+   *  how much the caller suspects seat c + 1 (Werewolf) or statement c + 1 (Two-Truths), as prior odds 0..255.  Equal weights are
+   *  rolloutSeats's entry word for word; nothing in the engine derives the weights.  The batch is only read. */
+  rolloutBeliefs(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, seats: ArrayLike<number>,
+                 actions: ArrayLike<ArrayLike<[number, number]>> | null, beliefs: Uint8Array | ArrayLike<ArrayLike<number>>,
+                 nRollouts?: number, maxTurns?: number, seed?: bigint | number, baseline?: ArrayLike<number> | null,
+                 subjects?: ArrayLike<number> | null): { words: BigUint64Array; status: Int32Array; cmp?: BigUint64Array };
   /** out[k] = room rooms[k] (any order, repeats allowed). */
   readRoomsAt(rooms: ArrayLike<number | bigint>): RoomState[];
   readRoomsAtRaw(rooms: ArrayLike<number | bigint>): ArrayBuffer;

@@ -154,6 +154,7 @@ const TT_INTS = { 2: 3, 5: 3, 7: 255, 8: 15 };
 const ACT_NIGHT = [1, 2, 3];                       // GE_ACT_WOLF_TARGET, GE_ACT_DOCTOR_PROTECT, GE_ACT_DETECTIVE
 const EFF_NIGHT_BEGIN = 2;
 const GE_MAX_PLAYERS = 12;
+const BELIEF_SLOTS = 16;                           // GE_BELIEF_SLOTS
 const isInt = (x) => typeof x === 'number' && Number.isInteger(x);
 const isDict = (x) => x !== null && typeof x === 'object' && !Array.isArray(x);
 const sameValue = (a, b) => JSON.stringify(a) === JSON.stringify(b);
@@ -720,9 +721,30 @@ class RoomBatch {
     return this._rollout(rooms, keys, turns, Uint32Array.from(seats), actions == null ? null : Array.from(actions), nRollouts, maxTurns, seed,
                          Uint32Array.from(baseline), Uint32Array.from(subjects));
   }
+  /** rolloutSeats - with baseline and subjects, rolloutCompare - under the caller's beliefs (twin of the Python
+   * RoomBatch.rollout_beliefs, POLICY.md §3j): beliefs is rooms.length x 16 bytes (a Uint8Array, or an array of 16-byte rows), byte c
+   * of entry k how much its caller suspects seat c + 1 of being a werewolf (Werewolf) or statement c + 1 of being the lie
+   * (Two-Truths), as prior odds 0 .. 255.  Equal weights give rolloutSeats's entry word for word; nothing in the engine derives
+   * the weights.  Returns { words, status }, with baseline and subjects { words, status, cmp }.  Throws only for a structural
+   * error (theirs, a non-zero byte at a slot the room does not have, baseline without subjects).  The batch is only read.  Synchronous. */
+  rolloutBeliefs(rooms, keys, turns, seats, actions, beliefs, nRollouts = 4096, maxTurns = 1024, seed, baseline = null, subjects = null) {
+    const n = Array.from(rooms).length;
+    let bel = beliefs;
+    if (!(bel instanceof Uint8Array)) {
+      const rows = Array.from(beliefs, (r) => Array.from(r));
+      if (rows.some((r) => r.length !== BELIEF_SLOTS || r.some((v) => !Number.isInteger(v) || v < 0 || v > 255))) {
+        throw new RangeError(`rolloutBeliefs: beliefs must be rows of ${BELIEF_SLOTS} bytes`);
+      }
+      bel = Uint8Array.from(rows.flat());
+    }
+    if (bel.length !== n * BELIEF_SLOTS) throw new RangeError(`rolloutBeliefs: beliefs must be ${BELIEF_SLOTS} bytes per entry`);
+    if ((baseline == null) !== (subjects == null)) throw new RangeError('rolloutBeliefs: baseline and subjects go together');
+    return this._rollout(rooms, keys, turns, Uint32Array.from(seats), actions == null ? null : Array.from(actions), nRollouts, maxTurns, seed,
+                         baseline == null ? null : Uint32Array.from(baseline), subjects == null ? null : Uint32Array.from(subjects), bel);
+  }
   /** The rollout* methods: one native call (ge_batch_rollout_seats with seats, else ge_batch_rollout_actions with actions -
    * [playerId, choice] pairs per entry, flattened to CSR - else ge_batch_rollout_rooms).  Returns { words, status }. */
-  _rollout(rooms, keys, turns, seats, actions, nRollouts, maxTurns, seed, baseline = null, subjects = null) {
+  _rollout(rooms, keys, turns, seats, actions, nRollouts, maxTurns, seed, baseline = null, subjects = null, beliefs = null) {
     let first = null, players = null, choices = null;
     if (actions) {
       const acts = actions.map((a) => Array.from(a));
@@ -734,7 +756,7 @@ class RoomBatch {
     }
     return addon.rollout(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r)), BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))),
                          Uint32Array.from(turns), seats, first, players, choices, nRollouts, maxTurns, seed === undefined ? this.seed : BigInt(seed),
-                         baseline, subjects);
+                         baseline, subjects, beliefs);
   }
   /** The listed rooms' states, out[k] = room rooms[k] (any order, repeats allowed). */
   readRoomsAt(rooms) {

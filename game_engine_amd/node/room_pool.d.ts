@@ -21,15 +21,17 @@ export class RoomPoolService {
   /** One tick for many threads (each at most once): per chunk touched one stepRooms and one readRoomsAt; outputs in input order. */
   handleMessages(msgs: [string, string, { id: string; type: string }[]?][]): Promise<MessageResult[]>;
   /** As RoomService.forecast (same keys, seed and output), from the thread's slot. */
-  forecast(threadId: string, nRollouts?: number, maxTurns?: number, seat?: number): Promise<Forecast>;
+  forecast(threadId: string, nRollouts?: number, maxTurns?: number, seat?: number, beliefs?: Record<number, number>): Promise<Forecast>;
   /** Forecasts of many threads in order: one rolloutRooms per chunk touched. */
-  forecasts(threadIds: string[], nRollouts?: number, maxTurns?: number, seats?: (number | undefined)[]): Promise<Forecast[]>;
+  forecasts(threadIds: string[], nRollouts?: number, maxTurns?: number, seats?: (number | undefined)[],
+            beliefs?: (Record<number, number> | undefined)[]): Promise<Forecast[]>;
   /** As RoomService.advise (same candidates, keys, seed and output), from the thread's slot. */
-  advise(threadId: string, playerId?: number, nRollouts?: number, maxTurns?: number, view?: 'full' | 'seat', compare?: boolean): Promise<Advice>;
+  advise(threadId: string, playerId?: number, nRollouts?: number, maxTurns?: number, view?: 'full' | 'seat', compare?: boolean,
+         beliefs?: Record<number, number>): Promise<Advice>;
   /** Advice for many threads in order (playerIds[j] absent: thread j's lowest human seat): one rolloutActions per chunk touched
    *  (with compare one rolloutCompare, and every option gains "versus"). */
   advises(threadIds: string[], playerIds?: (number | undefined)[], nRollouts?: number, maxTurns?: number,
-          view?: 'full' | 'seat', compare?: boolean): Promise<Advice[]>;
+          view?: 'full' | 'seat', compare?: boolean, beliefs?: (Record<number, number> | undefined)[]): Promise<Advice[]>;
   /** Forget a thread (its slot is reused); without an id, every thread and every chunk's device memory. */
   close(threadId?: string): Promise<boolean>;
 }

@@ -11,7 +11,7 @@
  */
 const { GameTable, RoomBatch, RoomLog, decodeRoom, turnToolCalls, uiToolCalls } = require('./index.js');
 const { roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, adviseCandidates, adviseSeat, runRollouts, adviseOutput,
-        seatForecastOutput, checkForecastSeat, checkView, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, forecastKey, forecastSeed, checkRunArgs, checkRunThread, runTurn, runOutput,
+        seatForecastOutput, beliefBytes, neutralBeliefs, checkForecastSeat, checkView, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, forecastKey, forecastSeed, checkRunArgs, checkRunThread, runTurn, runOutput,
         checkRunForecast, runForecastPerCall, runForecasts } = require('./room_service.js');
 const popcount = (m) => { let c = 0; for (let x = m; x; x &= x - 1) c++; return c; };
 const M = require('./messages.js');
@@ -256,18 +256,22 @@ class RoomPoolService {
       });
     });
   }
-  /** As RoomService.forecast (same keys, seed, seat view and output), from the thread's pool slot. */
-  forecast(threadId, nRollouts = 4096, maxTurns = 1024, seat) {
-    return this.forecasts([threadId], nRollouts, maxTurns, seat === undefined || seat === null ? undefined : [seat]).then((o) => o[0]);
+  /** As RoomService.forecast (same keys, seed, seat view, beliefs and output), from the thread's pool slot. */
+  forecast(threadId, nRollouts = 4096, maxTurns = 1024, seat, beliefs) {
+    return this.forecasts([threadId], nRollouts, maxTurns, seat === undefined || seat === null ? undefined : [seat],
+                          beliefs === undefined || beliefs === null ? undefined : [beliefs]).then((o) => o[0]);
   }
-  /** As RoomService.advise (same candidates, keys, seed, views, compare and output), from the thread's pool slot. */
-  advise(threadId, playerId, nRollouts = 4096, maxTurns = 1024, view = 'full', compare = false) {
-    return this.advises([threadId], [playerId], nRollouts, maxTurns, view, compare).then((o) => o[0]);
+  /** As RoomService.advise (same candidates, keys, seed, views, compare, beliefs and output), from the thread's pool slot. */
+  advise(threadId, playerId, nRollouts = 4096, maxTurns = 1024, view = 'full', compare = false, beliefs) {
+    return this.advises([threadId], [playerId], nRollouts, maxTurns, view, compare,
+                        beliefs === undefined || beliefs === null ? undefined : [beliefs]).then((o) => o[0]);
   }
   /** Advice for many threads, in order (playerIds[j] undefined / null or no playerIds: thread j's lowest human seat): one
    * rolloutActions call per chunk touched (rolloutSeats in the "seat" view; with compare one rolloutCompare, and every option
-   * gains "versus" as RoomService.advise's).  No thread changes. */
-  advises(threadIds, playerIds, nRollouts = 4096, maxTurns = 1024, view = 'full', compare = false) {
+   * gains "versus" as RoomService.advise's).  beliefs[j] (view "seat" only): thread j's advised seat's suspicions, as
+   * RoomService.advise's; a chunk any of whose threads has some gets one rolloutBeliefs call instead, its other threads under
+   * equal weights.  No thread changes. */
+  advises(threadIds, playerIds, nRollouts = 4096, maxTurns = 1024, view = 'full', compare = false, beliefs) {
     checkForecastArgs(nRollouts, maxTurns);
     const seatView = checkView(view);
     return this._serial(() => {
@@ -275,23 +279,29 @@ class RoomPoolService {
       const pids = playerIds || [];
       const seats = rooms.map((room, j) => adviseSeat(threadIds[j], room.humanSeats, pids[j]));
       const cands = rooms.map((room) => adviseCandidates(room.table, room.state));
-      const res = runRollouts(rooms.map((room, j) => ({ batch: room.chunk, slot: room.slot, key: room.key, turn: room.turn, seat: seats[j], cands: cands[j] })),
+      const bel = rooms.map((room, j) => beliefBytes(threadIds[j], room.table.info.pack, room.names.length, (beliefs || [])[j], seatView));
+      const res = runRollouts(rooms.map((room, j) => ({ batch: room.chunk, slot: room.slot, key: room.key, turn: room.turn, seat: seats[j], cands: cands[j],
+                                                        beliefs: bel[j], neutral: neutralBeliefs(room.table.info.pack, room.names.length) })),
                               seatView, nRollouts, maxTurns, this.seed, !!compare);
       return rooms.map((room, j) => adviseOutput(room.table, room.names, threadIds[j], room.turn, seats[j], room.state, cands[j], nRollouts, maxTurns,
-                                                 res[j], 0, seatView));
+                                                 res[j], 0, seatView, bel[j]));
     });
   }
   /** Forecasts of many threads, in order: one rolloutRooms per chunk touched; with seats (seats[j] 1 .. n: thread j from that
-   * seat's view, undefined / null: the full view), one rolloutSeats per chunk touched.  No thread changes. */
-  forecasts(threadIds, nRollouts = 4096, maxTurns = 1024, seats) {
+   * seat's view, undefined / null: the full view), one rolloutSeats per chunk touched.  beliefs[j] (for a thread with a seat): as
+   * RoomService.forecast's; a chunk any of whose threads has some gets one rolloutBeliefs call instead.  No thread changes. */
+  forecasts(threadIds, nRollouts = 4096, maxTurns = 1024, seats, beliefs) {
     checkForecastArgs(nRollouts, maxTurns);
     return this._serial(() => {
       const rooms = threadIds.map((t) => this._room(t));
       const sv = seats || [];
       rooms.forEach((room, j) => checkForecastSeat(threadIds[j], room.names.length, sv[j]));
-      const res = runRollouts(rooms.map((room, j) => ({ batch: room.chunk, slot: room.slot, key: room.key, turn: room.turn, seat: sv[j] })),
+      const bel = rooms.map((room, j) => beliefBytes(threadIds[j], room.table.info.pack, room.names.length, (beliefs || [])[j],
+                                                     sv[j] !== undefined && sv[j] !== null));
+      const res = runRollouts(rooms.map((room, j) => ({ batch: room.chunk, slot: room.slot, key: room.key, turn: room.turn, seat: sv[j],
+                                                        beliefs: bel[j], neutral: neutralBeliefs(room.table.info.pack, room.names.length) })),
                               !!seats, nRollouts, maxTurns, this.seed);
-      return rooms.map((room, j) => seatForecastOutput(room.table, room.names, threadIds[j], room.turn, nRollouts, maxTurns, sv[j], res[j].words));
+      return rooms.map((room, j) => seatForecastOutput(room.table, room.names, threadIds[j], room.turn, nRollouts, maxTurns, sv[j], res[j].words, 0, bel[j]));
     });
   }
   /** One turn of each room (distinct threads): one stepRooms and one readRoomsAt per chunk touched; a chunk holding a thread

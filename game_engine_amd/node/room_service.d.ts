@@ -83,13 +83,16 @@ export class RoomService {
   runRoom(threadId: string, maxTurns?: number, until?: RunUntil[], items?: { id: string; type: string }[], options?: RunOptions): Promise<RunResult>;
   /** nRollouts playouts (<= 65 536) of the thread's room, every seat played by the policy, keyed (threadKey << 16) + r under seed
    *  (service seed ^ 0x9E3779B97F4A7C15); the thread is not changed (INTEGRATION.md "Forecasting a thread").  seat: from what that
-   *  seat knows (hidden roles / the lie dealt again per replica); the JSON gains "seat". */
-  forecast(threadId: string, nRollouts?: number, maxTurns?: number, seat?: number): Promise<Forecast>;
+   *  seat knows (hidden roles / the lie dealt again per replica); the JSON gains "seat".  beliefs (with seat): what it suspects,
+   *  { seat or statement number: 0..255 }, unnamed ones 16 (INTEGRATION.md "Advising a seat from what it suspects"); the JSON gains "beliefs". */
+  forecast(threadId: string, nRollouts?: number, maxTurns?: number, seat?: number, beliefs?: Record<number, number>): Promise<Forecast>;
   /** For every choice playerId (default: the lowest human seat; RangeError if there is none) can make now, the forecast given
    *  that choice, under forecast's keys and seed; the thread is not changed (INTEGRATION.md "Advising a seat").  view "seat": from
    *  what that seat knows, the form to show a player (INTEGRATION.md "Advising a seat from what it knows"); the JSON gains "view".
-   *  compare: every option gains "versus" and the JSON "compare": true (INTEGRATION.md "Is this choice really better?"); the rest is unchanged. */
-  advise(threadId: string, playerId?: number, nRollouts?: number, maxTurns?: number, view?: 'full' | 'seat', compare?: boolean): Promise<Advice>;
+   *  compare: every option gains "versus" and the JSON "compare": true (INTEGRATION.md "Is this choice really better?"); the rest is unchanged.
+   *  beliefs (view "seat" only): as forecast's; the JSON gains "beliefs", the 16 bytes used. */
+  advise(threadId: string, playerId?: number, nRollouts?: number, maxTurns?: number, view?: 'full' | 'seat', compare?: boolean,
+         beliefs?: Record<number, number>): Promise<Advice>;
   /** Forget a thread and free its device memory; resolves false for an unknown thread. */
   close(threadId: string): Promise<boolean>;
   serve(port?: number): Promise<import('http').Server>;

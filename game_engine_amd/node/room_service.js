@@ -92,10 +92,38 @@ function forecastOutput(table, names, threadId, turn, nRollouts, maxTurns, w, of
   return out;
 }
 
-/** forecast's JSON; from a seat's view it gains "seat" (twin of room_service.py seat_forecast_output). */
-function seatForecastOutput(table, names, threadId, turn, nRollouts, maxTurns, seat, w, off = 0) {
+/** forecast's JSON; from a seat's view it gains "seat", under beliefs "beliefs" - the 16 bytes used (twin of room_service.py
+ * seat_forecast_output). */
+function seatForecastOutput(table, names, threadId, turn, nRollouts, maxTurns, seat, w, off = 0, beliefs = null) {
   const out = forecastOutput(table, names, threadId, turn, nRollouts, maxTurns, w, off);
   if (seat !== undefined && seat !== null) out.seat = Number(seat);
+  if (beliefs) out.beliefs = Array.from(beliefs);
+  return out;
+}
+const BELIEF_SLOTS = 16, BELIEF_NEUTRAL = 16;        // GE_BELIEF_SLOTS; an unnamed slot: a caller can go below neutral as well as above
+/** The slots a thread's beliefs can name: its seats (Werewolf, pack 1) or the three statements (Two-Truths). */
+const beliefSlots = (pack, nPlayers) => (pack === 1 ? nPlayers : 3);
+/** Equal weights: the unweighted deal exactly (a thread without beliefs in a call where another has some). */
+function neutralBeliefs(pack, nPlayers) {
+  const out = new Array(BELIEF_SLOTS).fill(0);
+  return out.fill(BELIEF_NEUTRAL, 0, beliefSlots(pack, nPlayers));
+}
+/** The 16 bytes of POLICY.md §3j from an object seat number (Werewolf) / statement number 1-3 (Two-Truths) -> integer 0..255; unnamed
+ * slots get 16, slots the thread does not have 0.  undefined / null stays null (today's path).  RangeError for a value out of range,
+ * a key that is no seat or statement of the thread, or beliefs without a seat view (twin of room_service.py belief_bytes). */
+function beliefBytes(threadId, pack, nPlayers, beliefs, seatView) {
+  if (beliefs === undefined || beliefs === null) return null;
+  if (!seatView) throw new RangeError(`thread ${threadId}: beliefs need a seat's view (forecast: seat, advise: view "seat")`);
+  if (typeof beliefs !== 'object' || Array.isArray(beliefs)) throw new RangeError(`thread ${threadId}: beliefs must map seat or statement numbers to 0..255`);
+  const slots = beliefSlots(pack, nPlayers);
+  const out = neutralBeliefs(pack, nPlayers);
+  const entries = beliefs instanceof Map ? Array.from(beliefs.entries()) : Object.entries(beliefs);
+  for (const [k, v] of entries) {
+    const key = typeof k === 'number' ? k : /^[0-9]+$/.test(String(k)) ? Number(k) : NaN;
+    if (!(Number.isInteger(key) && key >= 1 && key <= slots)) throw new RangeError(`thread ${threadId}: beliefs key ${k} is not 1 .. ${slots}`);
+    if (!(typeof v === 'number' && Number.isInteger(v) && v >= 0 && v <= 255)) throw new RangeError(`thread ${threadId}: beliefs[${k}] must be an integer 0 .. 255`);
+    out[key - 1] = v;
+  }
   return out;
 }
 function checkForecastSeat(threadId, n, seat) {
@@ -148,7 +176,9 @@ function adviseSeat(threadId, humanSeats, playerId) {
  * seat view (seat 0 for a thread without a seat: its full view).  Returns per request { words, status } (status null after
  * rolloutRooms), views into the call's results.  compare (an advise): the one call is rolloutCompare instead (seat 0 entries in
  * the full view) - every entry's baseline is its thread's policy entry, the subject the advised seat - and each result gains
- * cmp; a thread's entries stay in one call and a call at or below 65 536 entries. */
+ * cmp; a thread's entries stay in one call and a call at or below 65 536 entries.  A call any of whose requests carries beliefs
+ * (16 bytes, POLICY.md §3j) is rolloutBeliefs instead, with or without the comparison; its other requests get their `neutral`
+ * bytes - equal weights, the unweighted deal exactly.  Without beliefs nothing changes. */
 function runRollouts(reqs, seatView, nRollouts, maxTurns, seed, compare = false) {
   const byBatch = new Map();
   reqs.forEach((r, j) => {
@@ -172,14 +202,19 @@ function runRollouts(reqs, seatView, nRollouts, maxTurns, seed, compare = false)
   for (const part of parts) {
     const rooms = [], keys = [], turns = [], seats = [], base = [], subj = [];
     const acts = part.some((j) => reqs[j].cands) ? [] : null;
+    const weighted = part.some((j) => reqs[j].beliefs);
+    const bel = [];
     for (const j of part) {
       const r = reqs[j];
+      for (let i = 0; i < size[j]; i++) bel.push(r.beliefs || r.neutral || new Array(BELIEF_SLOTS).fill(0));
       for (let i = 0; i < size[j]; i++) { base.push(rooms.length + size[j] - 1); subj.push(r.seat); }
       for (let i = 0; i < size[j]; i++) { rooms.push(r.slot); keys.push(forecastKey(r.key)); turns.push(r.turn); seats.push(r.seat || 0); }
       if (acts) acts.push(...r.cands.map((c) => [[r.seat, c]]), []);
     }
     const batch = reqs[part[0]].batch;
-    const res = compare ? batch.rolloutCompare(rooms, keys, turns, seatView ? seats : seats.map(() => 0), acts, base, subj, nRollouts, maxTurns, fseed)
+    const res = weighted ? batch.rolloutBeliefs(rooms, keys, turns, seatView ? seats : seats.map(() => 0), acts, bel, nRollouts, maxTurns, fseed,
+                                                compare ? base : null, compare ? subj : null)
+      : compare ? batch.rolloutCompare(rooms, keys, turns, seatView ? seats : seats.map(() => 0), acts, base, subj, nRollouts, maxTurns, fseed)
       : seatView ? batch.rolloutSeats(rooms, keys, turns, seats, acts, nRollouts, maxTurns, fseed)
       : acts ? batch.rolloutActions(rooms, keys, turns, acts, nRollouts, maxTurns, fseed)
         : { words: batch.rolloutRooms(rooms, keys, turns, nRollouts, maxTurns, fseed), status: null };
@@ -193,7 +228,7 @@ function runRollouts(reqs, seatView, nRollouts, maxTurns, seed, compare = false)
   return out;
 }
 /** advise's JSON from the words and verdicts of an advise's entries (runRollouts) at entry offset `at`: the bytes the Python hosts print. */
-function adviseOutput(table, names, threadId, turn, seat, st, cands, nRollouts, maxTurns, res, at = 0, seatView = false) {
+function adviseOutput(table, names, threadId, turn, seat, st, cands, nRollouts, maxTurns, res, at = 0, seatView = false, beliefs = null) {
   const options = [];
   cands.forEach((c, j) => {
     if (res.status[at + j] !== 0) return;
@@ -208,6 +243,7 @@ function adviseOutput(table, names, threadId, turn, seat, st, cands, nRollouts, 
                 policy: forecastOutput(table, names, threadId, turn, nRollouts, maxTurns, res.words, 77 * (at + cands.length)), options };
   if (seatView) out.view = 'seat';
   if (res.cmp) out.compare = true;
+  if (beliefs) out.beliefs = Array.from(beliefs);
   return out;
 }
 
@@ -337,16 +373,20 @@ class RoomService {
    * at the same turn are identical and the thread is not changed.  Resolves with JSON integers: threadId, turn, rollouts, maxTurns,
    * finished, endTurnSum, ended, and per seat (Werewolf: sides {villagers, werewolves}, players {"1": {name, alive, wins}};
    * Two-Truths: players {"1": {name, scoreSum, topScore}}).  seat (1 .. n): the playouts start from what that seat knows
-   * (rolloutSeats, POLICY.md §3c) and the JSON gains "seat" - the form to show a player; the default is the full view. */
-  forecast(threadId, nRollouts = 4096, maxTurns = 1024, seat) {
+   * (rolloutSeats, POLICY.md §3c) and the JSON gains "seat" - the form to show a player; the default is the full view.  beliefs
+   * (with seat): what that seat suspects, { seat number (Werewolf) or statement number 1-3 (Two-Truths): 0..255 }, unnamed ones 16;
+   * the re-deal is weighted by it (rolloutBeliefs, POLICY.md §3j) and the JSON gains "beliefs", the 16 bytes used.  RangeError,
+   * before anything runs, for a value out of range, a key the thread does not have, or beliefs without a seat. */
+  forecast(threadId, nRollouts = 4096, maxTurns = 1024, seat, beliefs) {
     checkForecastArgs(nRollouts, maxTurns);
     const room = this.rooms.get(threadId);
     if (!room) return Promise.reject(new Error(`unknown thread ${threadId}`));
     checkForecastSeat(threadId, room.names.length, seat);
+    const bel = beliefBytes(threadId, room.table.info.pack, room.names.length, beliefs, seat !== undefined && seat !== null);
     return this._serial(room, () => {
-      const [res] = runRollouts([{ batch: room.batch, slot: 0, key: room.key, turn: room.turn, seat }], seat !== undefined && seat !== null,
+      const [res] = runRollouts([{ batch: room.batch, slot: 0, key: room.key, turn: room.turn, seat, beliefs: bel }], seat !== undefined && seat !== null,
                                 nRollouts, maxTurns, this.seed);
-      return seatForecastOutput(room.table, room.names, threadId, room.turn, nRollouts, maxTurns, seat, res.words);
+      return seatForecastOutput(room.table, room.names, threadId, room.turn, nRollouts, maxTurns, seat, res.words, 0, bel);
     });
   }
   /** What each choice the seat can make now leads to (twin of the Python RoomService.advise): for every candidate the forecast given
@@ -356,18 +396,21 @@ class RoomService {
    * candidates in ascending order.  The thread is not changed.  view "seat": every playout starts from what the advised seat knows
    * (rolloutSeats) - the form to show that player - and the JSON gains "view": "seat"; "full" (the default) is for spectators.
    * compare: the one call is rolloutCompare; the JSON gains "compare": true and per option "versus" { compared, better, worse, gain,
-   * loss, diffSq }: the option against the policy's entry, playout by playout, for the advised seat; the rest is the same bytes. */
-  advise(threadId, playerId, nRollouts = 4096, maxTurns = 1024, view = 'full', compare = false) {
+   * loss, diffSq }: the option against the policy's entry, playout by playout, for the advised seat; the rest is the same bytes.
+   * beliefs (view "seat" only): what the advised seat suspects, as forecast's; every entry of the call is dealt under it and the
+   * JSON gains "beliefs". */
+  advise(threadId, playerId, nRollouts = 4096, maxTurns = 1024, view = 'full', compare = false, beliefs) {
     checkForecastArgs(nRollouts, maxTurns);
     const seatView = checkView(view);
     const room = this.rooms.get(threadId);
     if (!room) return Promise.reject(new Error(`unknown thread ${threadId}`));
     const seat = adviseSeat(threadId, room.humanSeats, playerId);
+    const bel = beliefBytes(threadId, room.table.info.pack, room.names.length, beliefs, seatView);
     return this._serial(room, () => {
       const cands = adviseCandidates(room.table, room.state);
-      const [res] = runRollouts([{ batch: room.batch, slot: 0, key: room.key, turn: room.turn, seat, cands }], seatView, nRollouts, maxTurns,
+      const [res] = runRollouts([{ batch: room.batch, slot: 0, key: room.key, turn: room.turn, seat, cands, beliefs: bel }], seatView, nRollouts, maxTurns,
                                 this.seed, !!compare);
-      return adviseOutput(room.table, room.names, threadId, room.turn, seat, room.state, cands, nRollouts, maxTurns, res, 0, seatView);
+      return adviseOutput(room.table, room.names, threadId, room.turn, seat, room.state, cands, nRollouts, maxTurns, res, 0, seatView, bel);
     });
   }
   /** Forget a thread and free its device memory (after queued requests have finished). */
@@ -507,6 +550,8 @@ class RoomService {
           if (req.method === 'POST' && req.url === '/rooms') out = this.createRoom(msg);
           else if (req.method === 'POST' && req.url === '/continue') out = await this.continueRoom(msg.threadId, msg.items);
           else if (req.method === 'POST' && req.url === '/run') out = await this.runRoom(msg.threadId, msg.maxTurns, msg.until, msg.items, Object.assign({ playout: !!msg.playout }, msg.forecast && typeof msg.forecast === 'object' ? Object.assign({ forecast: true }, msg.forecast) : { forecast: !!msg.forecast }));
+          else if (req.method === 'POST' && req.url === '/forecast') out = await this.forecast(msg.threadId, msg.rollouts, msg.maxTurns, msg.seat, msg.beliefs);
+          else if (req.method === 'POST' && req.url === '/advise') out = await this.advise(msg.threadId, msg.playerId, msg.rollouts, msg.maxTurns, msg.view, msg.compare, msg.beliefs);
           else if (req.method === 'POST' && req.url === '/message') out = await this.handleMessage(msg.threadId, msg.text, msg.items);
           else if (req.method === 'POST' && req.url === '/action') out = await this.humanAction(msg.threadId, msg.playerId, msg.choice);
           else if (req.method === 'POST' && req.url === '/close') out = { closed: await this.close(msg.threadId) };
@@ -521,5 +566,5 @@ class RoomService {
 }
 
 module.exports = { RoomService, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput,
-                   adviseCandidates, adviseSeat, runRollouts, adviseOutput, seatForecastOutput, checkForecastSeat, checkView, checkRunArgs, checkRunThread, runTurn, runOutput,
+                   adviseCandidates, adviseSeat, runRollouts, adviseOutput, seatForecastOutput, beliefBytes, neutralBeliefs, checkForecastSeat, checkView, checkRunArgs, checkRunThread, runTurn, runOutput,
                    checkRunForecast, runForecastPerCall, runForecasts };

@@ -17,9 +17,9 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import messages as M
-from .room_service import (PLAYOUT_CAP, RolloutRequest, adopted_output, advise_candidates, advise_output, advise_seat,
+from .room_service import (PLAYOUT_CAP, RolloutRequest, adopted_output, advise_candidates, advise_output, advise_seat, belief_bytes,
                            check_forecast_args, check_forecast_seat, check_playout_options, check_run_args, check_run_forecast, check_run_thread, check_view,
-                           forecast_key, forecast_seed, playout_mask, playout_max_cands, prepare_adoption, room_index_of, run_forecast_per_call,
+                           forecast_key, forecast_seed, playout_mask, playout_max_cands, prepare_adoption, room_index_of, neutral_beliefs, run_forecast_per_call,
                            run_forecasts, run_output, run_rollouts, run_turn, seat_forecast_output)
 from .stepper import GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, load_dsl_by_gamename, slot_values
 from .toolcalls import WW_IS_ALIVE, RoomLog, turn_tool_calls
@@ -366,39 +366,51 @@ class RoomPoolService:
         room["panel"] = M.newest_panel(ui)
         return {"state": state, "toolCalls": calls, "uiCalls": ui}
 
-    def forecast(self, thread_id: str, n_rollouts: int = 4096, max_turns: int = 1024, seat: Optional[int] = None) -> Dict[str, Any]:
-        """As RoomService.forecast (same keys, seed, seat view and output), from the thread's pool slot."""
-        return self.forecasts([thread_id], n_rollouts, max_turns, None if seat is None else [seat])[0]
+    def forecast(self, thread_id: str, n_rollouts: int = 4096, max_turns: int = 1024, seat: Optional[int] = None,
+                 beliefs: Optional[Dict[Any, int]] = None) -> Dict[str, Any]:
+        """As RoomService.forecast (same keys, seed, seat view, beliefs and output), from the thread's pool slot."""
+        return self.forecasts([thread_id], n_rollouts, max_turns, None if seat is None else [seat], None if beliefs is None else [beliefs])[0]
 
     def forecasts(self, thread_ids: Sequence[str], n_rollouts: int = 4096, max_turns: int = 1024,
-                  seats: Optional[Sequence[Optional[int]]] = None) -> List[Dict[str, Any]]:
+                  seats: Optional[Sequence[Optional[int]]] = None,
+                  beliefs: Optional[Sequence[Optional[Dict[Any, int]]]] = None) -> List[Dict[str, Any]]:
         """Forecasts of many threads, in order: one rollout_rooms call per chunk touched (replica r of a thread is global room
         (thread_key << 16) + r under seed service seed ^ 0x9E3779B97F4A7C15, from the thread's own turn).  seats[j] (1 .. n):
         thread j's forecast from that seat's view, as RoomService.forecast(seat=...); with seats, one rollout_seats call per
-        chunk touched (seat 0 there for the threads without one: their full view).  No thread changes."""
+        chunk touched (seat 0 there for the threads without one: their full view).  beliefs[j] (None, or a mapping as
+        RoomService.forecast's, for a thread with a seat): a chunk any of whose threads has beliefs gets one rollout_beliefs
+        call instead, its other threads under equal weights - their unweighted deal exactly.  No thread changes."""
         check_forecast_args(n_rollouts, max_turns)
         rooms = [self._rooms[tid] for tid in thread_ids]          # KeyError for an unknown thread, before anything runs
         sv = list(seats) if seats is not None else [None] * len(rooms)
         if len(sv) != len(rooms):
             raise ValueError("forecasts: thread_ids and seats differ in length")
+        bv = list(beliefs) if beliefs is not None else [None] * len(rooms)
+        if len(bv) != len(rooms):
+            raise ValueError("forecasts: thread_ids and beliefs differ in length")
         for tid, room, st in zip(thread_ids, rooms, sv):
             check_forecast_seat(tid, len(room["names"]), st)
-        res = run_rollouts([RolloutRequest(room["chunk"], room["slot"], room["key"], room["turn"], st) for room, st in zip(rooms, sv)],
-                           seats is not None, n_rollouts, max_turns, self.seed)
-        return [seat_forecast_output(room["table"], room["names"], tid, room["turn"], n_rollouts, max_turns, sv[j], res[j][0][0])
+        bel = [belief_bytes(tid, room["table"], len(room["names"]), bm, st is not None) for tid, room, st, bm in zip(thread_ids, rooms, sv, bv)]
+        res = run_rollouts([RolloutRequest(room["chunk"], room["slot"], room["key"], room["turn"], st, None, bl,
+                                           neutral_beliefs(room["table"], len(room["names"])))
+                            for room, st, bl in zip(rooms, sv, bel)], seats is not None, n_rollouts, max_turns, self.seed)
+        return [seat_forecast_output(room["table"], room["names"], tid, room["turn"], n_rollouts, max_turns, sv[j], res[j][0][0], bel[j])
                 for j, (tid, room) in enumerate(zip(thread_ids, rooms))]
 
     def advise(self, thread_id: str, player_id: Optional[int] = None, n_rollouts: int = 4096, max_turns: int = 1024,
-               view: str = "full", compare: bool = False) -> Dict[str, Any]:
-        """As RoomService.advise (same candidates, keys, seed, views, compare and output), from the thread's pool slot."""
-        return self.advises([thread_id], None if player_id is None else [player_id], n_rollouts, max_turns, view, compare)[0]
+               view: str = "full", compare: bool = False, beliefs: Optional[Dict[Any, int]] = None) -> Dict[str, Any]:
+        """As RoomService.advise (same candidates, keys, seed, views, compare, beliefs and output), from the thread's pool slot."""
+        return self.advises([thread_id], None if player_id is None else [player_id], n_rollouts, max_turns, view, compare,
+                            None if beliefs is None else [beliefs])[0]
 
     def advises(self, thread_ids: Sequence[str], player_ids: Optional[Sequence[Optional[int]]] = None, n_rollouts: int = 4096,
-                max_turns: int = 1024, view: str = "full", compare: bool = False) -> List[Dict[str, Any]]:
+                max_turns: int = 1024, view: str = "full", compare: bool = False,
+                beliefs: Optional[Sequence[Optional[Dict[Any, int]]]] = None) -> List[Dict[str, Any]]:
         """Advice for many threads, in order (player_ids[j] None or absent: thread j's lowest human seat): one rollout_actions
         call per chunk touched - rollout_seats in the "seat" view, every thread from its advised seat's view - each thread's
         entries as RoomService.advise's.  compare: one rollout_compare call per chunk touched instead, and every option gains
-        "versus" as RoomService.advise's.  No thread changes."""
+        "versus" as RoomService.advise's.  beliefs[j] (view "seat" only): thread j's advised seat's suspicions, as
+        RoomService.advise's; a chunk any of whose threads has some gets one rollout_beliefs call instead.  No thread changes."""
         check_forecast_args(n_rollouts, max_turns)
         seat_view = check_view(view)
         rooms = [self._rooms[tid] for tid in thread_ids]          # KeyError for an unknown thread, before anything runs
@@ -407,10 +419,15 @@ class RoomPoolService:
             raise ValueError("advises: thread_ids and player_ids differ in length")
         seats = [advise_seat(tid, room["human_seats"], pid) for tid, room, pid in zip(thread_ids, rooms, pids)]
         cands = [advise_candidates(room["table"], room["view"]) for room in rooms]
-        res = run_rollouts([RolloutRequest(room["chunk"], room["slot"], room["key"], room["turn"], seat, c)
-                            for room, seat, c in zip(rooms, seats, cands)], seat_view, n_rollouts, max_turns, self.seed, compare)
+        bv = list(beliefs) if beliefs is not None else [None] * len(rooms)
+        if len(bv) != len(rooms):
+            raise ValueError("advises: thread_ids and beliefs differ in length")
+        bel = [belief_bytes(tid, room["table"], len(room["names"]), bm, seat_view) for tid, room, bm in zip(thread_ids, rooms, bv)]
+        res = run_rollouts([RolloutRequest(room["chunk"], room["slot"], room["key"], room["turn"], seat, c, bl,
+                                           neutral_beliefs(room["table"], len(room["names"])))
+                            for room, seat, c, bl in zip(rooms, seats, cands, bel)], seat_view, n_rollouts, max_turns, self.seed, compare)
         return [advise_output(room["table"], room["names"], tid, room["turn"], seats[j], room["view"], cands[j], n_rollouts, max_turns,
-                              res[j][0], res[j][1], seat_view, res[j][2] if compare else None)
+                              res[j][0], res[j][1], seat_view, res[j][2] if compare else None, bel[j])
                 for j, (tid, room) in enumerate(zip(thread_ids, rooms))]
 
     def close(self, thread_id: Optional[str] = None):

@@ -157,12 +157,52 @@ def check_forecast_seat(thread_id: str, n_players: int, seat: Optional[int]) -> 
         raise ValueError(f"thread {thread_id!r}: seat must be 1 .. {n_players}")
 
 
+BELIEF_SLOTS = 16                                           # GE_BELIEF_SLOTS
+BELIEF_NEUTRAL = 16                                         # an unnamed slot: a caller can go below neutral as well as above
+
+
+def belief_slots(table: GameTable, n_players: int) -> int:
+    """The slots a thread's beliefs can name: its seats (Werewolf) or the three statements (Two-Truths)."""
+    return int(n_players) if table.pack == PACK_WEREWOLF else 3
+
+
+def belief_bytes(thread_id: str, table: GameTable, n_players: int, beliefs, seat_view: bool) -> Optional[bytes]:
+    """The 16 bytes of POLICY.md §3j from a mapping seat number (Werewolf) / statement number 1-3 (Two-Truths) -> integer
+    0..255 (keys may be the decimal strings JSON makes of them); unnamed slots get 16, slots the thread does not have 0.
+    None stays None (today's path).  ValueError for a value out of range, a key that is no seat or statement of the thread,
+    or beliefs without a seat view - the same bytes as room_service.js's beliefBytes."""
+    if beliefs is None:
+        return None
+    if not seat_view:
+        raise ValueError(f"thread {thread_id!r}: beliefs need a seat's view (forecast: seat=..., advise: view=\"seat\")")
+    if not isinstance(beliefs, dict):
+        raise ValueError(f"thread {thread_id!r}: beliefs must map seat or statement numbers to 0..255")
+    slots = belief_slots(table, n_players)
+    out = [BELIEF_NEUTRAL] * slots + [0] * (BELIEF_SLOTS - slots)
+    for k, v in beliefs.items():
+        if isinstance(k, bool) or not (isinstance(k, int) or (isinstance(k, str) and k.isascii() and k.isdigit())) or not 1 <= int(k) <= slots:
+            raise ValueError(f"thread {thread_id!r}: beliefs key {k!r} is not 1 .. {slots}")
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 255:
+            raise ValueError(f"thread {thread_id!r}: beliefs[{k!r}] must be an integer 0 .. 255")
+        out[int(k) - 1] = v
+    return bytes(out)
+
+
+def neutral_beliefs(table: GameTable, n_players: int) -> bytes:
+    """Equal weights: the unweighted deal exactly (a thread without beliefs in a call where another has some)."""
+    slots = belief_slots(table, n_players)
+    return bytes([BELIEF_NEUTRAL] * slots + [0] * (BELIEF_SLOTS - slots))
+
+
 def seat_forecast_output(table: GameTable, names: List[str], thread_id: str, turn: int, n_rollouts: int, max_turns: int, seat: Optional[int],
-                         words) -> Dict[str, Any]:
-    """forecast's JSON; from a seat's view it gains "seat" (the default output is unchanged)."""
+                         words, beliefs: Optional[bytes] = None) -> Dict[str, Any]:
+    """forecast's JSON; from a seat's view it gains "seat", under beliefs "beliefs" - the 16 bytes used (the default output is
+    unchanged)."""
     out = forecast_output(table, names, thread_id, turn, n_rollouts, max_turns, words)
     if seat is not None:
         out["seat"] = int(seat)
+    if beliefs is not None:
+        out["beliefs"] = list(beliefs)
     return out
 
 
@@ -194,6 +234,8 @@ class RolloutRequest(NamedTuple):
     turn: int
     seat: Optional[int] = None
     cands: Optional[List[int]] = None
+    beliefs: Optional[bytes] = None                        # the 16 bytes of POLICY.md §3j, or the request has none
+    neutral: bytes = bytes(BELIEF_SLOTS)                   # what it gets in a call where another request has beliefs
 
 
 def run_rollouts(reqs: Sequence[RolloutRequest], seat_view: bool, n_rollouts: int, max_turns: int, seed: int,
@@ -204,7 +246,9 @@ def run_rollouts(reqs: Sequence[RolloutRequest], seat_view: bool, n_rollouts: in
     needs it: rollout_rooms for a forecast, rollout_actions for an advise, rollout_seats in the seat view (seat 0 for a thread
     without a seat: its full view).  compare (an advise): the one call is rollout_compare instead (seat 0 entries in the full
     view) - every entry's baseline is its thread's policy entry, the subject the advised seat - and each result is (words, status,
-    cmp); a thread's entries stay in one call and a call at or below 65 536 entries."""
+    cmp); a thread's entries stay in one call and a call at or below 65 536 entries.  A call any of whose requests carries
+    beliefs is rollout_beliefs instead (with or without the comparison); its other requests get their neutral bytes - equal
+    weights, the unweighted deal exactly.  Without beliefs nothing changes."""
     per_call = max(1, (1 << 26) // int(n_rollouts))
     if compare:
         per_call = min(per_call, 65536)
@@ -230,9 +274,12 @@ def run_rollouts(reqs: Sequence[RolloutRequest], seat_view: bool, n_rollouts: in
         acts: list = []
         base: list = []
         subj: list = []
+        bel: list = []
+        weighted = any(reqs[j].beliefs is not None for j in part)
         for j in part:
             r = reqs[j]
             k = 1 if r.cands is None else len(r.cands) + 1
+            bel += [list(r.neutral if r.beliefs is None else r.beliefs)] * k
             base += [len(rooms) + k - 1] * k
             subj += [r.seat] * k
             rooms += [r.slot] * k
@@ -243,7 +290,12 @@ def run_rollouts(reqs: Sequence[RolloutRequest], seat_view: bool, n_rollouts: in
                 acts += [[(r.seat, c)] for c in r.cands] + [[]]
         batch = reqs[part[0]].batch
         cmp = None
-        if compare:
+        if weighted:
+            res = batch.rollout_beliefs(rooms, keys, turns, seats if seat_view else [0] * len(rooms), acts or None, bel, n_rollouts,
+                                        max_turns, seed=seed, **({"baseline": base, "subjects": subj} if compare else {}))
+            words, status = res[0], res[1]
+            cmp = res[2] if compare else None
+        elif compare:
             words, status, cmp = batch.rollout_compare(rooms, keys, turns, seats if seat_view else [0] * len(rooms), acts, base, subj,
                                                        n_rollouts, max_turns, seed=seed)
         elif seat_view:
@@ -261,10 +313,11 @@ def run_rollouts(reqs: Sequence[RolloutRequest], seat_view: bool, n_rollouts: in
 
 
 def advise_output(table: GameTable, names: List[str], thread_id: str, turn: int, seat: int, view, cands: List[int], n_rollouts: int,
-                  max_turns: int, words, status, seat_view: bool = False, cmp=None) -> Dict[str, Any]:
+                  max_turns: int, words, status, seat_view: bool = False, cmp=None, beliefs: Optional[bytes] = None) -> Dict[str, Any]:
     """advise's JSON from the words and verdicts of an advise's entries (run_rollouts; the same bytes as room_service.js /
     room_pool.js); from the seat's view it gains "view": "seat"; with cmp (the entries' ge_compare_stats words) "compare": true
-    and per option "versus": the option against the policy's entry, playout by playout, for the advised seat."""
+    and per option "versus": the option against the policy's entry, playout by playout, for the advised seat; under beliefs
+    "beliefs": the 16 bytes used."""
     options = []
     for j, c in enumerate(cands):
         if int(status[j]) != 0:
@@ -277,7 +330,8 @@ def advise_output(table: GameTable, names: List[str], thread_id: str, turn: int,
     return {"threadId": thread_id, "turn": int(turn), "playerId": int(seat), "phaseId": int(view["phase_id"]),
             "rollouts": int(n_rollouts), "maxTurns": int(max_turns),
             "policy": forecast_output(table, names, thread_id, turn, n_rollouts, max_turns, words[len(cands)]), "options": options,
-            **({"view": "seat"} if seat_view else {}), **({"compare": True} if cmp is not None else {})}
+            **({"view": "seat"} if seat_view else {}), **({"compare": True} if cmp is not None else {}),
+            **({"beliefs": list(beliefs)} if beliefs is not None else {})}
 
 
 RUN_MAX_TURNS = 4096                                        # ge_batch_run_rooms's cap on max_turns
@@ -532,7 +586,8 @@ class RoomService:
         batch.set_turn(turn + int(played[0]))
         return run_output([run_turn(self._finish(room, views[0, t], events[0, t], items)) for t in range(int(played[0]))], int(stopped[0]))
 
-    def forecast(self, thread_id: str, n_rollouts: int = 4096, max_turns: int = 1024, seat: Optional[int] = None) -> Dict[str, Any]:
+    def forecast(self, thread_id: str, n_rollouts: int = 4096, max_turns: int = 1024, seat: Optional[int] = None,
+                 beliefs: Optional[Dict[Any, int]] = None) -> Dict[str, Any]:
         """How the thread ends from where it stands: n_rollouts playouts of its room (RoomBatch.rollout_rooms), each played for
         up to max_turns turns from the thread's next turn, every seat - human seats too - played by the policy.  Replica r is
         global room (thread_key << 16) + r, so n_rollouts <= 65 536 (ValueError above), under seed (service seed ^
@@ -541,17 +596,21 @@ class RoomService:
         (Werewolf: sides {villagers, werewolves}, players {"1": {name, alive, wins}}; Two-Truths: players {"1": {name,
         scoreSum, topScore}}); divide by rollouts for odds.  seat (1 .. n): the playouts start from what that seat knows
         (RoomBatch.rollout_seats, POLICY.md §3c: what it cannot see is dealt again in every replica), and the JSON gains
-        "seat" - the form to show a player; the default is the full view."""
+        "seat" - the form to show a player; the default is the full view.  beliefs (with seat): what that seat suspects, a
+        mapping seat number (Werewolf) or statement number 1-3 (Two-Truths) -> 0..255, unnamed ones 16; the re-deal is weighted
+        by it (RoomBatch.rollout_beliefs, POLICY.md §3j) and the JSON gains "beliefs", the 16 bytes used.  ValueError, before
+        anything runs, for a value out of range, a key the thread does not have, or beliefs without a seat."""
         check_forecast_args(n_rollouts, max_turns)
         room = self._rooms[thread_id]
         check_forecast_seat(thread_id, len(room["names"]), seat)
+        bel = belief_bytes(thread_id, room["table"], len(room["names"]), beliefs, seat is not None)
         turn = room["batch"].turn
-        (words, _), = run_rollouts([RolloutRequest(room["batch"], 0, room["key"], turn, seat)], seat is not None, n_rollouts, max_turns,
-                                   self.seed)
-        return seat_forecast_output(room["table"], room["names"], thread_id, turn, n_rollouts, max_turns, seat, words[0])
+        (words, _), = run_rollouts([RolloutRequest(room["batch"], 0, room["key"], turn, seat, None, bel)], seat is not None, n_rollouts,
+                                   max_turns, self.seed)
+        return seat_forecast_output(room["table"], room["names"], thread_id, turn, n_rollouts, max_turns, seat, words[0], bel)
 
     def advise(self, thread_id: str, player_id: Optional[int] = None, n_rollouts: int = 4096, max_turns: int = 1024,
-               view: str = "full", compare: bool = False) -> Dict[str, Any]:
+               view: str = "full", compare: bool = False, beliefs: Optional[Dict[Any, int]] = None) -> Dict[str, Any]:
         """What each choice the seat can make now leads to: for every candidate (advise_candidates) the forecast of the thread
         given that the seat logs it before the next turn, and the forecast with the policy's own choice ("policy", equal to
         forecast(thread_id)).  One rollout_actions call; every entry uses forecast's keys and seed, so replica r of every option
@@ -562,17 +621,20 @@ class RoomService:
         - the form to show that player - and the JSON gains "view": "seat"; "full" (the default) plays from the true record and
         is for spectators and debugging.  compare: the one call is rollout_compare; the JSON gains "compare": true and per option
         "versus" {compared, better, worse, gain, loss, diffSq}: the option against the policy's entry, playout by playout, for
-        the advised seat (INTEGRATION.md "Is this choice really better?"); everything else is byte for byte the same."""
+        the advised seat (INTEGRATION.md "Is this choice really better?"); everything else is byte for byte the same.
+        beliefs (view "seat" only): what the advised seat suspects, as forecast's; every entry of the call is dealt under it
+        (INTEGRATION.md "Advising a seat from what it suspects") and the JSON gains "beliefs"."""
         check_forecast_args(n_rollouts, max_turns)
         seat_view = check_view(view)
         room = self._rooms[thread_id]
         seat = advise_seat(thread_id, room["human_seats"], player_id)
+        bel = belief_bytes(thread_id, room["table"], len(room["names"]), beliefs, seat_view)
         rv, turn = room["view"], room["batch"].turn
         cands = advise_candidates(room["table"], rv)
-        res, = run_rollouts([RolloutRequest(room["batch"], 0, room["key"], turn, seat, cands)], seat_view, n_rollouts, max_turns,
+        res, = run_rollouts([RolloutRequest(room["batch"], 0, room["key"], turn, seat, cands, bel)], seat_view, n_rollouts, max_turns,
                             self.seed, compare)
         return advise_output(room["table"], room["names"], thread_id, turn, seat, rv, cands, n_rollouts, max_turns, res[0], res[1],
-                             seat_view, res[2] if compare else None)
+                             seat_view, res[2] if compare else None, bel)
 
     def close(self, thread_id: Optional[str] = None):
         for tid in ([thread_id] if thread_id else list(self._rooms)):

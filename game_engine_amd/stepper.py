@@ -505,19 +505,40 @@ class RoomBatch:
         extra = (np.ascontiguousarray(baseline, dtype=np.uint32), np.ascontiguousarray(subjects, dtype=np.uint32))
         return self._rollout("rollout_compare", rooms, keys, turns, seats, actions, n_rollouts, max_turns, seed, extra)
 
+    def rollout_beliefs(self, rooms, keys, turns, seats, actions, beliefs, n_rollouts: int = 4096, max_turns: int = 1024,
+                        seed: Optional[int] = None, baseline=None, subjects=None):
+        """rollout_seats - with baseline and subjects, rollout_compare - under the caller's beliefs (POLICY.md §3j): beliefs is
+        (n, 16) uint8, byte c of row k how much entry k's caller suspects seat c + 1 of being a werewolf (Werewolf) or statement
+        c + 1 of being the lie (Two-Truths), as prior odds 0 .. 255.  The wolf seats among the seats seats[k] cannot rule out,
+        and a redrawn lie, are drawn by these weights instead of uniformly; what the seat knows is never overridden.  Equal
+        weights give rollout_seats's entry word for word; nothing in the engine derives the weights.  Returns (words, status),
+        or with baseline and subjects (words, status, cmp), as those methods.  The batch is only read.  GeError only for a
+        structural error (theirs, a non-zero byte at a slot the room does not have, baseline without subjects or the reverse),
+        before anything runs."""
+        bel = np.ascontiguousarray(beliefs, dtype=np.uint8)
+        if bel.ndim != 2 or bel.shape[1] != _lib.BELIEF_SLOTS:
+            raise GeError(-1, f"rollout_beliefs: beliefs must be (n, {_lib.BELIEF_SLOTS}) bytes")
+        if (baseline is None) != (subjects is None):
+            raise GeError(-1, "rollout_beliefs: baseline and subjects go together")
+        extra = None
+        if baseline is not None:
+            extra = (np.ascontiguousarray(baseline, dtype=np.uint32), np.ascontiguousarray(subjects, dtype=np.uint32))
+        return self._rollout("rollout_beliefs", rooms, keys, turns, seats, actions, n_rollouts, max_turns, seed, extra, bel)
+
     def _rollout(self, method: str, rooms, keys, turns, seats, actions, n_rollouts: int, max_turns: int,
-                 seed: Optional[int], compare=None):
+                 seed: Optional[int], compare=None, beliefs=None):
         """The rollout_* methods: one call of ge_batch_<method> (seats and actions are read where the method has them;
         actions None: every entry's slice empty, passed as NULL).  Returns (words, status) - with compare, rollout_compare's
         (baseline, subjects), (words, status, cmp); GeError naming the method when the lengths differ, or naming the symbol when
         it fails without a verdict written."""
         rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
         args = [rooms, np.ascontiguousarray(keys, dtype=np.uint64), np.ascontiguousarray(turns, dtype=np.uint32)]
-        if method in ("rollout_seats", "rollout_compare"):
+        if method in ("rollout_seats", "rollout_compare", "rollout_beliefs"):
             args.append(np.ascontiguousarray(seats, dtype=np.uint32))
         if method == "rollout_actions" or actions is not None:
             actions = [list(a) for a in actions]
-        if len({len(x) for x in args + list(compare or ())} | ({len(rooms)} if actions is None else {len(actions)})) > 1:
+        if len({len(x) for x in args + list(compare or ()) + ([] if beliefs is None else [beliefs])}
+               | ({len(rooms)} if actions is None else {len(actions)})) > 1:
             raise GeError(-1, f"{method}: arrays differ in length")
         out = np.zeros((len(rooms), _lib.ROLLOUT_WORDS), dtype=np.uint64)
         status = None
@@ -531,11 +552,15 @@ class RoomBatch:
                 choices = np.ascontiguousarray([int(c) for _, c in flat], dtype=np.uint32)
             status = np.full(len(rooms), 1, dtype=np.int32)      # 1: untouched (no ge_status is positive)
             args += [first, players, choices, status]
+            if beliefs is not None:
+                args.append(beliefs)
         sym = "ge_batch_" + method
         tail = []
         if compare is not None:
             cmp = np.zeros((len(rooms), _lib.COMPARE_WORDS), dtype=np.uint64)
             tail = [compare[0].ctypes.data, compare[1].ctypes.data, cmp.ctypes.data]
+        elif beliefs is not None:
+            tail = [None, None, None]
         st = getattr(self._lib, sym)(self._h, len(rooms), *[x if x is None else x.ctypes.data for x in args], n_rollouts, max_turns,
                                      self._seed if seed is None else seed, out.ctypes.data, *tail)
         # a refused entry returns its status with every entry's verdict written; a structural error or a failure of the call

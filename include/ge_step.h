@@ -49,7 +49,8 @@ extern "C" {
  *      ge_batch_run_rooms_playout (the same with playout seats: the playouts of every turn enqueued without the host in between);
  *      ge_batch_run_rooms_forecast (ge_batch_run_rooms with the ge_batch_rollout_seats forecast of every turn it played: a win-odds timeline);
  *      GE_PLAYOUT_HALVING (a new flag of both playout-seat calls, no new symbol: sequential halving of each decision's playout
- *      budget; a library from before it refuses the bit with GE_ERR_ARG) */
+ *      budget; a library from before it refuses the bit with GE_ERR_ARG);
+ *      ge_batch_rollout_beliefs + GE_BELIEF_SLOTS (seat-view playouts and comparisons whose re-deal is weighted by the caller's suspicions) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -410,6 +411,32 @@ int ge_batch_rollout_compare(ge_batch *b, uint64_t n, const uint64_t *rooms, con
                              const uint32_t *player_ids, const uint32_t *choices, int32_t *entry_status /* may be NULL */,
                              uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, ge_rollout_stats *out,
                              const uint32_t *baseline /* n */, const uint32_t *subjects /* n, 1-based */, ge_compare_stats *cmp /* n */);
+
+/* Seat-view playouts weighted by the caller's beliefs (POLICY.md §3j).  Entry k carries GE_BELIEF_SLOTS bytes
+ * beliefs[16 k .. 16 k + 15]: byte c is how much the caller suspects seat c + 1 of being a werewolf (Werewolf) or statement c + 1
+ * of being the lie (Two-Truths), as prior odds 0 .. 255.  The re-deal of ge_batch_rollout_seats differs at two draws only: the
+ * wolf seats among the seats the viewing seat cannot rule out are taken by successive weighted draws without replacement
+ * (a pick whose remaining weights sum to 0 is uniform, so the call stays total), and a redrawn lie is one weighted draw over
+ * bytes 0 .. 2 (all zero: uniform).  What the seat knows - its partners, a Detective's results, revealed roles - is never
+ * overridden.  This is successive sampling by prior odds, not an exact posterior, and nothing in the library derives the
+ * weights.  Equal weights (any common value 1 .. 255) give ge_batch_rollout_seats's entry word for word; seats[k] = 0 means no
+ * re-deal and the entry's beliefs are not read by the device.
+ * baseline, subjects and cmp all NULL: the call is ge_batch_rollout_seats under these draws.  All three given: it is
+ * ge_batch_rollout_compare under them - out, entry_status and cmp exactly as there - and a comparison is on common random
+ * numbers only for equal keys, turns, seats and beliefs.  Structural errors, all before anything runs and with nothing
+ * touched, in this order: ge_batch_rollout_seats's own; GE_ERR_ARG for beliefs NULL with n > 0; GE_ERR_ARG for a non-zero byte
+ * at a slot >= the n_players of room rooms[k]'s segment (Werewolf) or >= 3 (Two-Truths) - a wrong stride; GE_ERR_ARG when some
+ * but not all of baseline / subjects / cmp are NULL; then, when comparing, ge_batch_rollout_compare's own.  Refusals per entry
+ * as ge_batch_rollout_seats.  The beliefs travel in the call's one upload, 16 B per entry.  Cost of the weighted draws against
+ * ge_batch_rollout_seats on the same entries, measured on an MI355X (profiles/beliefs_probe.txt): 65 536 playouts x 1 024 turns
+ * per layout 0.96 .. 1.02 x the unweighted call (within run-to-run spread), one advise call of 8 entries x 4 096 playouts
+ * x 1.03 .. 1.04.  The batch is only read.  Ordered behind the previous step; synchronises. */
+#define GE_BELIEF_SLOTS 16
+int ge_batch_rollout_beliefs(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
+                             const uint32_t *seats, const uint32_t *first_action, const uint32_t *player_ids, const uint32_t *choices,
+                             int32_t *entry_status, const uint8_t *beliefs /* n x GE_BELIEF_SLOTS */,
+                             uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, ge_rollout_stats *out,
+                             const uint32_t *baseline, const uint32_t *subjects, ge_compare_stats *cmp /* all three NULL: no comparison */);
 
 /* Playout seats (POLICY.md §3d): ge_batch_step_rooms with some bot seats choosing their action by playouts.  Room k is stepped
  * as ge_batch_step_rooms's entry (rooms[k], keys[k], turns[k]), except that every seat s of playout_masks[k] (bit i = seat

@@ -103,6 +103,9 @@ def label(r):
         return "ge_playout_halve (GE_PLAYOUT_HALVING: the cut between two rounds)"
     if r["kernel"] == "ge_rollout_kernel" and r.get("act") == 5:  # ge_batch_run_rooms_forecast: one launch per segment present, behind the run
         return f"{r['layout']}, playouts from a traced turn (ge_batch_run_rooms_forecast)" + (", GENERIC" if r["generic"] else "")
+    if r["kernel"] == "ge_rollout_kernel" and r.get("act") in (6, 7):   # ge_batch_rollout_beliefs: one launch per segment present
+        what = "weighted by beliefs" if r["act"] == 6 else "weighted by beliefs, outcome kept"
+        return f"{r['layout']}, playouts from a seat's view {what} (ge_batch_rollout_beliefs)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_rollout_kernel" and r.get("act") == 3:  # ge_batch_rollout_compare: one launch per segment present
         return f"{r['layout']}, playouts that keep their outcome (ge_batch_rollout_compare)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_rollout_kernel" and r.get("act") == 2:  # ge_batch_rollout_seats: one launch per segment present
