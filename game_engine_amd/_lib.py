@@ -71,7 +71,7 @@ COMPARE_WORDS = C.sizeof(CompareStats) // 8      # 6
 BELIEF_SLOTS = 16                                # GE_BELIEF_SLOTS
 
 # every symbol include/ge_step.h declares (tests/test_abi.py checks the library exports them all)
-SYMBOLS = ["ge_table_compile_json", "ge_batch_create", "ge_batch_step", "ge_batch_reset", "ge_batch_set_turn", "ge_batch_inject_actions", "ge_batch_sync", "ge_batch_turn",
+SYMBOLS = ["ge_table_compile_json", "ge_table_dev_row", "ge_batch_create", "ge_batch_step", "ge_batch_reset", "ge_batch_set_turn", "ge_batch_inject_actions", "ge_batch_sync", "ge_batch_turn",
            "ge_batch_n_rooms", "ge_batch_read_rooms", "ge_batch_write_rooms", "ge_batch_read_events", "ge_batch_inject_action", "ge_batch_summary",
            "ge_batch_state", "ge_batch_set_timing", "ge_batch_kernel_time", "ge_batch_destroy", "ge_batch_step_rooms", "ge_batch_read_rooms_at",
            "ge_batch_write_rooms_at", "ge_batch_rollout_rooms", "ge_batch_rollout_actions", "ge_batch_rollout_seats", "ge_batch_rollout_compare", "ge_batch_rollout_beliefs", "ge_batch_step_rooms_playout", "ge_batch_run_rooms", "ge_batch_run_rooms_playout", "ge_batch_run_rooms_forecast", "ge_group_partition", "ge_batch_create_shard", "ge_group_create", "ge_group_size", "ge_group_shard", "ge_group_step", "ge_group_sync", "ge_group_summary", "ge_group_destroy",
@@ -111,6 +111,8 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH)
     vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
     lib.ge_table_compile_json.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(Table), C.c_char_p, C.c_size_t]
+    if hasattr(lib, "ge_table_dev_row"):
+        lib.ge_table_dev_row.argtypes = [C.POINTER(Table), u32, u32, C.POINTER(u32)]
     lib.ge_batch_create.argtypes = [C.POINTER(BatchDesc), C.POINTER(vp)]
     lib.ge_batch_step.argtypes = [vp, u32, vp]
     lib.ge_batch_sync.argtypes = [vp]

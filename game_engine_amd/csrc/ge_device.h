@@ -105,6 +105,33 @@ template <bool LOWOCC, bool SINGLE> constexpr bool single_global(int game_bit) {
 #ifndef GE_TAIL_KNOWN_RESTART
 #define GE_TAIL_KNOWN_RESTART 1
 #endif
+// Lone Werewolf x 8 turn, row-constant and launch-constant work out of the every-turn path (profiles/ab_lone_row_const.txt).
+//   Each applies to the fused lone-wavefront Werewolf x 8 builds without generic rows (WwBuild::LONE, GENERIC = 0) and to nothing else;
+//   GE_SKIP_MASK to their tail-recycling turn loops (TAIL_RECYCLE / TAIL_KEEP: the loops run_ww hands the mask to).
+//   GE_ROW_DERIVED: the turn takes what is a constant of the table row from the row's derived word (DevRow r6, ge_layout.h: the
+//   all-players-or-0 byte of the completion test, the night flag, the flags byte a room leaves the row with, the one-hot action kind)
+//   instead of working it out of r0 on every turn of every lane.  The word arrives in the row read the loop issues anyway.
+//   GE_CTX_PERM: alive | team_w << 16 of a queue slot's context word is one v_perm_b32 of the packed predicate words W1:W0.
+//   GE_SKIP_MASK: `valid` and the segment's human mask are one per-lane mask made in front of the turn loop: all ones for
+//   a lane past the segment's end (run_ww hands it to ww_turn), so todo = T & ~acted & ~skip has no select.
+//   GE_RES_UNMASKED: the peeled first queue round returns its result from every lane - a slot that does not act ORs a zero into its
+//   (possibly stale, always in-range: the room index is 6 bits) room's word - instead of inside an exec-masked block.
+//   Measured on C2, five alternating runs each, steps/s against the parent: GE_ROW_DERIVED alone +3.4 .. +3.8 % (passes the rule in both
+//   sessions; common turn 338 -> 331): adopted.  The other three alone: GE_CTX_PERM +0.0 % (339: the shifts it replaces fold into
+//   neighbours), GE_SKIP_MASK +1.0 % (337), GE_RES_UNMASKED -0.5 % (336); on top of the others none adds anything by the rule
+//   (all four 327 instructions, +3.4 %; without GE_RES_UNMASKED +4.2 %): they stay switches, off.
+#ifndef GE_ROW_DERIVED
+#define GE_ROW_DERIVED 1
+#endif
+#ifndef GE_CTX_PERM
+#define GE_CTX_PERM 0
+#endif
+#ifndef GE_SKIP_MASK
+#define GE_SKIP_MASK 0
+#endif
+#ifndef GE_RES_UNMASKED
+#define GE_RES_UNMASKED 0
+#endif
 #ifndef GE_ROWS_SPLIT
 #define GE_ROWS_SPLIT 1
 #endif
@@ -876,7 +903,8 @@ template <int NB> struct WwRestart {
 // The 12 base predicates live packed in s.W; the row carries byte-permute selectors that pull each term's mask out of
 // the word pairs (0xFF where the term is elsewhere / absent), so the condition is 2-3 v_perm + AND, XOR with the
 // negation mask, and a fold of the term bytes (ge_layout.h DevRow).
-template <int NB, bool LOWOCC, int GENERIC>
+// DER (GE_ROW_DERIVED): the low byte of the row's derived word is ALL for an `action` row and 0 otherwise (alive has no higher bits)
+template <int NB, bool LOWOCC, int GENERIC, bool DER = false>
 __device__ __forceinline__ uint32_t ww_targets(const WWR<NB> &s, const DevRow &row, const WwCtx &c, uint32_t alive, uint32_t ALL) {
     using R = WWR<NB>;
     const uint32_t comp = row.r0 & 3u, nterms = (row.r0 >> 8) & 7u;
@@ -906,7 +934,7 @@ __device__ __forceinline__ uint32_t ww_targets(const WWR<NB> &s, const DevRow &r
                 X &= term(2) & term(3);
             }
         }
-        T = X & alive & (comp == COMP_ACTION ? ALL : 0u);
+        T = DER ? X & alive & row.r6 : X & alive & (comp == COMP_ACTION ? ALL : 0u);
     }
     if (generic_row && comp == COMP_ACTION)                    // or / in [..] / numeric comparisons: the clause form
         T = ww_cond_generic<NB>(s, c.cc, row.r0, ALL) & alive;
@@ -959,13 +987,19 @@ __device__ __forceinline__ void ww_prepare_deal(const WWR<NB> &s, const WwCtx &c
 // read (WwBuild::SHADOW; fused lone wavefront: both behind the first slot read, beside the first round), else run after the queue.
 struct WwActs { uint32_t newly, det_v, det_w; };   // who acted now; the Detective's new knowledge (villager / werewolf)
 
-template <int NB, bool LOWOCC, bool FUSED = false, typename S1, typename S2>
+// LONE8: the fused lone-wavefront Werewolf x 8 turn without generic rows - `rowd` is the row's derived word and `nmask` its night flag
+// as 0 / ~0 (GE_ROW_DERIVED: `act` and `night` are then not read), `skip` is the launch's per-lane mask (GE_SKIP_MASK: c.human for a valid
+// lane, all ones for a lane past the segment's end - made once in front of the turn loop, ge_kernels.inl run_ww), SKIP_GIVEN: the caller has it
+template <int NB, bool LOWOCC, bool FUSED = false, bool LONE8 = false, bool SKIP_GIVEN = false, typename S1, typename S2>
 __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uint32_t T, uint32_t act, bool night, uint32_t alive, uint32_t team_w,
-                                                 uint32_t r_det, uint32_t tk, WwActs &out, S1 &&shadow1, S2 &&shadow2, Stamps *stamps) {
+                                                 uint32_t r_det, uint32_t tk, WwActs &out, S1 &&shadow1, S2 &&shadow2, Stamps *stamps,
+                                                 uint32_t rowd = 0u, uint32_t nmask = 0u, uint32_t skip = 0u) {
     using nib_t = typename WWR<NB>::nib_t;
     using B = WwBuild<NB, LOWOCC>;
+    constexpr bool DER = LONE8 && GE_ROW_DERIVED, PERM = LONE8 && GE_CTX_PERM && NB <= 8, UNMASKED = LONE8 && GE_RES_UNMASKED && B::ONE_ATOMIC;
+    constexpr bool SKIPM = GE_SKIP_MASK && SKIP_GIVEN;
     auto *lw = static_cast<typename WaveLdsOf<LOWOCC>::type *>(c.wave_lds);
-    const uint32_t todo = c.valid ? (T & ~s.acted & ~c.human) : 0u;
+    const uint32_t todo = SKIPM ? (T & ~s.acted & ~skip) : c.valid ? (T & ~s.acted & ~c.human) : 0u;
     const uint32_t known = s.det_v | s.det_w;
     const uint32_t kw_alive = s.det_w & alive;
     const uint32_t lo_kw = kw_alive & (0u - kw_alive);       // lowest known living werewolf
@@ -991,9 +1025,13 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
     }
     // per-room context of an action; `ky`: what the acting role knows (the Detective's memory
     // at night, who the Detective is by day - ww_choose reads only one of the two per kind)
-    const uint32_t ky = night ? known : (B::ONEHOT ? (lo_kw != 0u ? r_det : 0u) : r_det);
+    const uint32_t ky = DER ? bfi(nmask, known, lo_kw != 0u ? r_det : 0u) : night ? known : (B::ONEHOT ? (lo_kw != 0u ? r_det : 0u) : r_det);
     const uint32_t kind = B::ONEHOT ? ((1u << act) >> 1) : act;          // one-hot: ACT_WOLF_TARGET = 1 -> bit 0 ...
-    const uint4 ctx = B::ORD ? make_uint4(alive | (team_w << 16) | (kind << 28), ky | (lo_kw << 8) | (off << 16) | (lane << 26), ord, tk)
+    // GE_CTX_PERM: alive (byte 0 of W0) and team_w (byte 3 of W1) into bytes 0 and 2, zero bytes between (selector 0x0C), by one permute
+    static_assert(F_ALIVE == 0 && F_TEAM_W == 7, "the selector below is made for this layout");
+    const uint32_t at = PERM ? __builtin_amdgcn_perm(s.W[1], s.W[0], 0x0C070C00u) : alive | (team_w << 16);
+    const uint32_t x0 = DER ? at | (rowd & (0xFu << ROWD_KIND_SHIFT)) : at | (kind << 28);
+    const uint4 ctx = B::ORD ? make_uint4(x0, ky | (lo_kw << 8) | (off << 16) | (lane << 26), ord, tk)
                              : make_uint4(alive | (team_w << 16) | (act << 28), ky | (lo_kw << 16), todo | (off << 16) | (lane << 26), tk);
     // N <= 8: only x, y come back - the results sit 8 bytes apart (GE_RES_PACKED; 16 bytes apart, a 64-bit access of 16 consecutive
     // lanes hits every bank twice: /opt/skills/guides/MI355X_MICROARCH.md "LDS", ds_write_b64 / ds_read_b64 banking)
@@ -1048,7 +1086,7 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
     // Every other build keeps the loop below as it was, instruction for instruction
     constexpr bool PEEL = LOWOCC && FUSED && B::SHADOW;
     if (PEEL) {
-        auto round = [&](uint32_t base) {                  // the loop's body below, for a lone wavefront
+        auto round = [&](uint32_t base, auto first_c) {    // the loop's body below, for a lone wavefront
             const uint32_t k = base + lane;
             if (GE_STAMPS == 1 && stamps && base == 0u) { asm volatile("" :: "v"(c4.x)); stamps->mark(1); }   // [.. first slot in registers]
             uint32_t L, i, know, lokw;
@@ -1068,17 +1106,20 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
             uint32_t ch = B::ONEHOT ? ww_choose_onehot8(c4.x, i, d, know, lokw, know)
                                     : ww_choose<NB, false>(c4.x >> 28, i, d, c4.x & 0xFFFFu, (c4.x >> 16) & 0xFFFu, know, lokw, know, c.nth8);
             if (B::PIN_CHOICE) asm volatile("" : "+v"(ch));
-            if (go) {
+            if (UNMASKED && decltype(first_c)::value) {
+                // every lane: no exec-mask region (a scalar pair and a branch).  L is 6 bits of whatever the slot holds: in range
+                atomicOr(res_w + RW * L + 1, go ? ch << (4u * i) : 0u);
+            } else if (go) {
                 uint32_t *r = res_w + RW * L;
                 if (!B::ONE_ATOMIC) atomicOr(r, 1u << i);
                 atomicOr(r + 1 + (i >> 3), ch << (4u * (i & 7u)));
             }
         };
         shadow2();
-        round(0u);
+        round(0u, std::true_type{});
         for (uint32_t base = 64u; base < total; base += 64u) {   // wave-uniform; a round's read is issued only if it is needed
             c4 = fetch(base + lane);
-            round(base);
+            round(base, std::false_type{});
         }
     } else {
         // at least one round (total == 0: every slot is stale and dropped): the loop is left BEFORE the next
@@ -1159,13 +1200,13 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
     }
     s.choice = (s.choice & ~m15) | got;
     // RefereeNode (A): record the action (bt:204-225 update_player_state)
-    s.sel = night ? ((s.sel & ~m15) | got) : s.sel;
+    s.sel = DER ? (nib_t)bfi(nmask, (uint32_t)((s.sel & ~m15) | got), (uint32_t)s.sel) : night ? ((s.sel & ~m15) | got) : s.sel;
     if (B::ONEHOT && FUSED) {
         // the lowest non-zero choice nibble is the first new actor's (a choice is >= 1); no actor: nibble 7 = 0, and (1 << 0) >> 1 = 0.
         // `act == ACT_DETECTIVE` is bit 2 of the one-hot kind: a mask, no compare
         const uint32_t g = (uint32_t)got;
         const uint32_t ch = (g >> ((uint32_t)__builtin_ctz(g | 0x80000000u) & 28u)) & 15u;
-        const uint32_t tb = ((1u << ch) >> 1) & bit_mask(kind, 2u);
+        const uint32_t tb = ((1u << ch) >> 1) & (DER ? bit_mask(rowd, ROWD_KIND_SHIFT + 2u) : bit_mask(kind, 2u));
         out.det_w = tb & team_w;
         out.det_v = tb & ~team_w;
     } else {
@@ -1179,8 +1220,10 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
 }
 
 // ---- PhaseNode: completion (every target player has acted in this visit) and the chosen branch
-template <int NB, bool LOWOCC>
+// T_MASKED (GE_ROW_DERIVED): T is 0 in a row whose completion is not `action` (ww_targets), so the test of `comp` says nothing more
+template <int NB, bool LOWOCC, bool T_MASKED = false>
 __device__ __forceinline__ uint32_t ww_decide(const WWR<NB> &s, uint32_t comp, uint32_t T, const WwBranch &b) {
+    if (T_MASKED) return sel32(b.open & ((T & ~s.acted) == 0u), b.qe, s.phase);
     if (WwBuild<NB, LOWOCC>::SEL_OPEN) {
         // no short-circuit evaluation: && / || became three nested exec-mask regions here (see ww_choose)
         const uint32_t open = (uint32_t)b.open & ((uint32_t)(comp != COMP_ACTION) | (uint32_t)((T & ~s.acted) == 0u));
@@ -1275,7 +1318,8 @@ __device__ __forceinline__ void ww_apply_effect(WWR<NB> &s, const DevRow &row, c
         s.end_turn = (terminal && s.end_turn == END_NONE) ? (turn < 0xFFFEu ? turn : 0xFFFEu) : s.end_turn;
     } else {
         s.acted &= ~moved; s.choice &= (nib_t)~moved;
-        s.flags = bfi(moved, (s.flags & FLAG_PHASE0_DONE) | (p_eff << 1), s.flags);
+        // (GE_ROW_DERIVED: FLAG_PHASE0_DONE is set on every turn before the move - ww_turn - so the new flags are a byte of the row)
+        s.flags = bfi(moved, GE_ROW_DERIVED ? (row.r6 >> ROWD_FLAGS_SHIFT) & 0xFFu : (s.flags & FLAG_PHASE0_DONE) | (p_eff << 1), s.flags);
         s.prev = bfi(moved, s.phase, s.prev);
         s.phase = q;                                           // (a lane that stays has q == s.phase)
         if (TAILR != TAIL_RECYCLE) {
@@ -1304,7 +1348,7 @@ __device__ __forceinline__ void ww_apply_effect(WWR<NB> &s, const DevRow &row, c
 // on every turn (TAIL_RECYCLE), on none (TAIL_KEEP), or as rst->term_rs says (TAIL_RUNTIME)
 template <int NB, bool LOWOCC, int GENERIC = false, bool SINGLE = false, int TAILR = TAIL_NONE>
 __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c, uint32_t turn, uint32_t &tk_io, bool trace, Deal &deal, bool deal_now,
-                                        uint32_t &ev_newly, uint64_t &ev_choice, Stamps *stamps = nullptr, WwRestart<NB> *rst = nullptr) {
+                                        uint32_t &ev_newly, uint64_t &ev_choice, Stamps *stamps = nullptr, WwRestart<NB> *rst = nullptr, uint32_t skip = 0u) {
     static_assert(!TAILR || (NB <= 8 && LOWOCC && !SINGLE), "tail recycling is the fused lone-wavefront Werewolf x 8 form");
     using R = WWR<NB>;
     using B = WwBuild<NB, LOWOCC, SINGLE>;
@@ -1313,7 +1357,11 @@ __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c,
     const uint32_t alive = s.template get<F_ALIVE>(), team_w = s.template get<F_TEAM_W>(), r_det = s.template get<F_DET>();
     const bool night = act >= ACT_WOLF_TARGET && act <= ACT_DETECTIVE;
 
-    const uint32_t T = ww_targets<NB, LOWOCC, GENERIC>(s, row, c, alive, ALL);
+    // the fused lone-wavefront Werewolf x 8 turn without generic rows: what the GE_ROW_DERIVED .. GE_RES_UNMASKED switches apply to
+    constexpr bool LONE8 = B::LONE && GENERIC == 0, DER = LONE8 && GE_ROW_DERIVED;
+    const uint32_t rowd = row.r6, nmask = DER ? bit_mask(rowd, ROWD_NIGHT_BIT) : 0u;
+
+    const uint32_t T = ww_targets<NB, LOWOCC, GENERIC, DER>(s, row, c, alive, ALL);
     if (GE_STAMPS == 1 && stamps) { asm volatile("" :: "v"(T)); stamps->mark(0); }        // [end of previous turn .. row in registers]
 
     WwBranch br;
@@ -1321,7 +1369,7 @@ __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c,
     if (B::DEAL_EARLY) ww_prepare_deal<NB, LOWOCC, SINGLE>(s, c, deal, deal_now, ALL, dealt);
     uint32_t tk_next = 0;
     WwActs acts;
-    ww_queue_actions<NB, LOWOCC, !SINGLE>(s, c, T, act, night, alive, team_w, r_det, tk_io, acts,
+    ww_queue_actions<NB, LOWOCC, !SINGLE, LONE8, TAILR == TAIL_RECYCLE || TAILR == TAIL_KEEP>(s, c, T, act, night, alive, team_w, r_det, tk_io, acts,
         [&]() {
             ww_phase_branch<NB>(s, row, c.phase0_idx, alive, team_w, br);
             if (B::SHADOW) asm volatile("" : "+v"(br.qe));     // stays in the shadow: not sunk below the queue loop
@@ -1338,9 +1386,9 @@ __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c,
                     for (int k = 0; k < R::NW; k++) asm volatile("" : "+v"(dealt.W[k]));
                 }
             }
-        }, stamps);
+        }, stamps, rowd, nmask, skip);
     s.acted |= acts.newly;
-    s.template set<F_SUB>(night ? acts.newly : 0u);            // night_action_submitted
+    s.template set<F_SUB>(DER ? acts.newly & nmask : night ? acts.newly : 0u);   // night_action_submitted
     ev_newly = acts.newly;
     if (trace) {                                              // wave-uniform
         uint64_t m = 0;                                       // nibble mask of the new actors
@@ -1351,7 +1399,7 @@ __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c,
 
     tk_io = tk_next;
     s.flags |= FLAG_PHASE0_DONE;                               // set by the guard turn; already set afterwards
-    const uint32_t qe = ww_decide<NB, LOWOCC>(s, comp, T, br);
+    const uint32_t qe = ww_decide<NB, LOWOCC, DER>(s, comp, T, br);
     {   // investigated_alignments[c] = team(c): an assignment, so a stale entry is replaced
         // (the guard turn has no actions: both masks are 0)
         const uint32_t seen = acts.det_v | acts.det_w;

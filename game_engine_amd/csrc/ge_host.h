@@ -34,7 +34,17 @@ inline void term_selectors(uint32_t kind, int n, const uint8_t *bases, const uin
     }
 }
 
-inline DevRow to_dev_row(const ge_game_table &tb, const ge_phase_row &r, uint32_t kind) {
+// Werewolf N <= 8: what the fused lone-wavefront turn would otherwise derive from r0 on every turn of every lane (ge_layout.h ROWD_*)
+inline uint32_t ww8_row_derived(const ge_phase_row &r, uint32_t n_players) {
+    const uint32_t all = n_players >= 8u ? 0xFFu : (1u << n_players) - 1u;
+    const uint32_t act = r.act & 7u;
+    const bool night = act >= GE_ACT_WOLF_TARGET && act <= GE_ACT_DETECTIVE;
+    return ((r.completion & 3u) == GE_COMP_ACTION ? all : 0u) | (night ? 1u << ROWD_NIGHT_BIT : 0u) |
+           (((uint32_t)FLAG_PHASE0_DONE | ((r.effect & 7u) << 1)) << ROWD_FLAGS_SHIFT) | (((1u << act) >> 1) << ROWD_KIND_SHIFT);
+}
+
+// n_players: the segment's player count (the derived word of a Werewolf N <= 8 row holds the all-players mask)
+inline DevRow to_dev_row(const ge_game_table &tb, const ge_phase_row &r, uint32_t kind, uint32_t n_players = 8) {
     // predicate masks per 32-bit word (ge_device.h): 4 bytes (werewolf N<=8) or 2 half-words (all others)
     const bool bytes4 = kind == K_WW8;
     const int fpw = bytes4 ? 4 : 2;
@@ -64,6 +74,7 @@ inline DevRow to_dev_row(const ge_game_table &tb, const ge_phase_row &r, uint32_
         term_selectors(kind, std::min(n_terms, bytes4 ? 4 : 2), r.term_base, r.term_neg, sel, nm);
         d.r4 = sel[0]; d.r5 = sel[1]; d.r6 = sel[2]; d.r7 = nm;
     }
+    if (kind == K_WW8) d.r6 = ww8_row_derived(r, n_players);     // (no pair (W5:W4) there: the third selector was never read)
     return d;
 }
 

@@ -342,12 +342,21 @@ __device__ __forceinline__ void run_ww(const SegDev *__restrict__ sgp, const Ste
                     row = row0;
                     restarted_in = 1;
                 }
+#if GE_SKIP_MASK
+                // who these turns never act for, a constant of the lane for the whole launch (ge_device.h GE_SKIP_MASK; under the
+                // preprocessor, not a constant condition: a value named here at all reorders operands in other kernels' code)
+                const uint32_t skip = valid ? ctx.human : ~0u;
+#endif
                 auto one_turn = [&](auto form_c, uint32_t t) __attribute__((always_inline)) {
                     const uint32_t restarted = restarted_in, p = s.phase;
                     uint32_t ev_newly = 0;
                     uint64_t ev_choice = 0;
                     const bool deal_now = ahead && ((deal_phase + t) & (deal_period<NB>() - 1u)) == 0u;    // wave-uniform
+#if GE_SKIP_MASK
+                    ww_turn<NB, LOWOCC, GENERIC, false, decltype(form_c)::value>(s, row, ctx, turn0 + t, tk, trace, deal, deal_now, ev_newly, ev_choice, (GE_STAMPS && a.stamps) ? &stamps : nullptr, &rst, skip);
+#else
                     ww_turn<NB, LOWOCC, GENERIC, false, decltype(form_c)::value>(s, row, ctx, turn0 + t, tk, trace, deal, deal_now, ev_newly, ev_choice, (GE_STAMPS && a.stamps) ? &stamps : nullptr, &rst);
+#endif
                     if (trace && valid) store_event(sg.trace, sg.rooms_padded, t, room, turn0 + t, p, rst.q, restarted, ev_newly, ev_choice);
                     restarted_in = rst.restarted;
                 };

@@ -322,11 +322,17 @@ template <> struct TTLayout<12> {
 //       word pairs (W1:W0), (W3:W2), (W5:W4) - a term's bytes in the pair that holds its predicate,
 //       0xFF bytes (selector 0x0D) in the others, so the AND of the three permutes is the term.
 //       N<=8: 4 terms x 1 byte, pair (W2:W2) in r5;  N<=12: terms 0..1 x 2 bytes.
+//   r6, werewolf N<=8 (which has no third pair): the row's DERIVED word - constants of the row that the fused lone-wavefront
+//       turn would otherwise work out of r0 on every turn (ge_device.h GE_ROW_DERIVED; filled by ge_host.h ww8_row_derived):
+//       bits 0..7 the all-players mask if completion is `action`, else 0; bit 8 the row's action is a night action;
+//       bits 16..23 the flags byte a room has after it leaves the row (FLAG_PHASE0_DONE | effect << 1);
+//       bits 28..31 the action kind one-hot, (1 << act) >> 1, as a queue slot's context word carries it
 //   r7: XOR mask of the negated terms (same byte positions)
 //   r0 bit 21: the target condition is generic (or / in [..] / numeric): the row's DevCond describes it, r1/r4..r7 do not;
 //   r0 bits 22..26: its slot in the table's literal image (DevTable::cond_img)
 struct DevRow { uint32_t r0, r1, r2, r3, r4, r5, r6, r7; };
 constexpr uint32_t ROW_GENERIC = 1u << 21;
+constexpr uint32_t ROWD_NIGHT_BIT = 8, ROWD_FLAGS_SHIFT = 16, ROWD_KIND_SHIFT = 28;   // DevRow r6, werewolf N<=8
 
 // A target condition in clause form (include/ge_step.h ge_literal), for the rows whose condition is not a plain
 // conjunction of base predicates.  lit[c][l]: bits 0..15 = base-predicate bit set, or lo | hi << 8 of a numeric

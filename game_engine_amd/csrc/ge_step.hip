@@ -144,6 +144,24 @@ int ge_abi_version(void) { return GE_ABI_VERSION; }
 int ge_last_hip_error(void) { return g_last_hip; }
 uint64_t ge_last_rejected_room(void) { return g_last_rejected_room; }
 
+// the device image's row as create_impl builds it below (ge_host.h to_dev_row): host arithmetic only
+int ge_table_dev_row(const ge_game_table *tb, uint32_t n_players, uint32_t row, uint32_t *out8) {
+    if (!tb || !out8 || tb->n_phases <= 0 || tb->n_phases > GE_MAX_PHASES || row >= (uint32_t)tb->n_phases || n_players > GE_MAX_PLAYERS) return GE_ERR_ARG;
+    uint32_t kind;
+    if (tb->pack == GE_PACK_WEREWOLF) {
+        if (n_players < 4) return GE_ERR_ARG;
+        kind = n_players <= 8 ? K_WW8 : K_WW12;
+    } else if (tb->pack == GE_PACK_TWO_TRUTHS) {
+        if (n_players < 2) return GE_ERR_ARG;
+        kind = n_players <= 4 ? K_TT4 : (n_players <= 8 ? K_TT8 : K_TT12);
+    } else {
+        return GE_ERR_ARG;
+    }
+    const DevRow d = to_dev_row(*tb, tb->rows[row], kind, n_players);
+    memcpy(out8, &d, sizeof d);
+    return GE_OK;
+}
+
 int ge_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -275,7 +293,7 @@ static int create_impl(const ge_batch_desc *desc, ge_batch **out, const uint64_t
                 DevTable &dt = host_tables[k];
                 memset(&dt, 0, sizeof dt);
                 for (int r = 0; r < s.table.n_phases; r++) {
-                    dt.rows[r] = to_dev_row(s.table, s.table.rows[r], s.dev.kind);
+                    dt.rows[r] = to_dev_row(s.table, s.table.rows[r], s.dev.kind, s.dev.n_players);
                     dt.conds[r] = to_dev_cond(s.table.rows[r]);
                     if (s.table.rows[r].generic) b->generic = true;
                 }

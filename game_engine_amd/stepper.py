@@ -164,6 +164,12 @@ class GameTable:
                         "branches": [(r.br_res[j], r.br_target[j]) for j in range(r.n_branches)]})
         return out
 
+    def dev_row(self, n_players: int, row: int) -> List[int]:
+        """The 8 words of row `row` in the device phase table of a segment of `n_players` players (csrc/ge_layout.h DevRow)."""
+        out = (C.c_uint32 * 8)()
+        _check(_lib.load().ge_table_dev_row(C.byref(self.c), n_players, row, out), "ge_table_dev_row")
+        return list(out)
+
     def phase_name(self, phase_id: int) -> str:
         for i in range(self.c.n_phases):
             if self.c.rows[i].phase_id == phase_id:

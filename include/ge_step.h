@@ -169,6 +169,10 @@ typedef struct ge_game_table {
 int ge_table_compile_json(const char *dsl_json, size_t len, int rounds, ge_game_table *out,
                           char *err, size_t err_cap);
 
+/* Row `row` of the device phase table (8 words, csrc/ge_layout.h DevRow) as a batch segment of `n_players` players of this
+ * table gets it.  Host arithmetic only, no GPU: for inspection and tests of the image the kernels read. */
+int ge_table_dev_row(const ge_game_table *tb, uint32_t n_players, uint32_t row, uint32_t *out8);
+
 /* Canonical, layout-independent view of one room: the integer projection of the reference's
  * AgentState (v2:97-117): current_phase_id, phase history tail, player_states fields.
  * players[i] = player id i+1; field order per pack:
