@@ -795,6 +795,10 @@ static int rollout_call(ge_batch *b, const RollRequest &r) {
             if (r.rooms[r.baseline[k]] != r.rooms[k]) return GE_ERR_ARG;
         for (uint64_t k = 0; k < n; k++)
             if (r.subjects[k] == 0u || r.subjects[k] > b->segs[pool_segment_of(b, r.rooms[k])].dev.n_players) return GE_ERR_ARG;
+        // a row of the outcome plane holds one byte per replica, the outcome for the row's own subject: an entry is compared with
+        // its baseline's row, so both must name the same seat (until this check the sums of such an entry mixed two seats' outcomes)
+        for (uint64_t k = 0; k < n; k++)
+            if (r.subjects[r.baseline[k]] != r.subjects[k]) return GE_ERR_ARG;
     }
     return guarded([&] { return rollout_rooms_impl(b, r); });
 }

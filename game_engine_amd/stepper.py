@@ -507,7 +507,7 @@ class RoomBatch:
         gain, loss, diff_sq) of ge_compare_stats, all zero when entry k or its baseline was refused.  Only equal keys, turns
         and seats of an entry and its baseline make it a comparison on common random numbers.  At most 65 536 entries.  The
         batch is only read.  GeError only for a structural error (rollout_seats's, a baseline outside the call or of another
-        room, a subject outside 1 .. n_players), before anything runs."""
+        room, a subject outside 1 .. n_players or other than its baseline's), before anything runs."""
         extra = (np.ascontiguousarray(baseline, dtype=np.uint32), np.ascontiguousarray(subjects, dtype=np.uint32))
         return self._rollout("rollout_compare", rooms, keys, turns, seats, actions, n_rollouts, max_turns, seed, extra)
 

@@ -407,7 +407,8 @@ typedef struct ge_compare_stats {         /* 6 x u64 = 48 B; all zero when entry
  * two differ only by what their actions change.  Structural errors, all before anything runs and with nothing touched, in this
  * order: ge_batch_rollout_seats's own; then GE_ERR_ARG for baseline, subjects or cmp NULL with n > 0, n > 65 536 (an entry and
  * its baseline are staged together), a baseline[k] >= n, rooms[baseline[k]] != rooms[k] (the same room, hence the same seat
- * numbering), subjects[k] == 0 or above the n_players of room rooms[k]'s segment.  Refusals per entry as
+ * numbering), subjects[k] == 0 or above the n_players of room rooms[k]'s segment, subjects[baseline[k]] != subjects[k] (a
+ * playout keeps its outcome for one seat: an entry and its baseline are compared for the same one).  Refusals per entry as
  * ge_batch_rollout_seats; cmp[k] is all zero when entry k or its baseline was refused.  Each playout's outcome takes one byte
  * of device memory and none crosses to the host.  The batch is only read.  Ordered behind the previous step; synchronises. */
 int ge_batch_rollout_compare(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,

@@ -16,10 +16,11 @@ import zlib
 import numpy as np
 import pytest
 
+from abi_model import Model as _Model
 from conftest import load_dsl
 from game_engine_amd import GameTable, GeError, RoomBatch
 from oracle.oracle import Oracle
-from parity_util import assert_views_equal, oracle_events, oracle_rooms_as_views, views_as_oracle_rooms
+from parity_util import assert_views_equal, oracle_rooms_as_views
 
 pytestmark = pytest.mark.gpu
 
@@ -78,81 +79,6 @@ def test_read_inject_step_read_one_seat(dsl_ww, R):
                 orc.run(rooms, seed, first, t, 1, threads=0, human_mask=mask)
             assert_views_equal(b.read_rooms(), oracle_rooms_as_views(orc, rooms), f"R={R} seed {seed} at the end")
     assert injected >= R
-
-
-class _Model:
-    """The oracle side of a batch: one room array per segment + the turn counter."""
-
-    def __init__(self, segs, seed, first, restart):
-        self.segs, self.seed, self.first, self.restart = segs, seed, first, restart
-        self.orcs = [Oracle(load_dsl(g), n) for g, n, _, _ in segs]
-        self.lo = np.cumsum([0] + [r for _, _, r, _ in segs]).tolist()
-        self.total = self.lo[-1]
-        self.reset()
-
-    def reset(self):
-        self.rooms = [o.init_rooms(r) for o, (_, _, r, _) in zip(self.orcs, self.segs)]
-        self.turn = 0
-        self.last_events = None
-
-    def seg_of(self, room):
-        k = int(np.searchsorted(self.lo, room, side="right")) - 1
-        return k, room - self.lo[k]
-
-    def views(self, lo=0, hi=None):
-        hi = self.total if hi is None else hi
-        parts = []
-        for k, o in enumerate(self.orcs):
-            a, z = max(lo, self.lo[k]), min(hi, self.lo[k + 1])
-            if a < z:
-                parts.append(oracle_rooms_as_views(o, self.rooms[k][a - self.lo[k]: z - self.lo[k]]))
-        return np.concatenate(parts)
-
-    def step(self, k):
-        ev = []
-        for t in range(k):                                          # turn by turn: the event trace is per turn
-            row = []
-            for s, o in enumerate(self.orcs):
-                o.run(self.rooms[s], self.seed, self.first + self.lo[s], self.turn, 1, threads=0, restart=self.restart,
-                      human_mask=self.segs[s][3])
-                row.append(oracle_events(o, self.rooms[s], self.turn))
-            ev.append(np.concatenate(row))
-            self.turn += 1
-        self.last_events = np.stack(ev, axis=1)                     # [room, turn]
-
-    def inject(self, room, player, choice):
-        if room >= self.total:
-            return -6
-        k, r = self.seg_of(room)
-        return 0 if self.orcs[k].inject(self.rooms[k], r, player, choice) else -1
-
-    def write(self, lo, views):
-        for k, o in enumerate(self.orcs):
-            a, z = max(lo, self.lo[k]), min(lo + len(views), self.lo[k + 1])
-            if a < z:
-                self.rooms[k][a - self.lo[k]: z - self.lo[k]] = views_as_oracle_rooms(o, views[a - lo: z - lo])
-
-    def summary(self):
-        s = {"rooms": self.total, "turn": self.turn, "finished": 0, "village_wins": 0, "wolf_wins": 0, "alive_players": 0,
-             "sum_end_turn": 0, "end_turn_hist": np.zeros(16, dtype=np.int64), "score_hist": np.zeros(16, dtype=np.int64),
-             "games_recycled": 0}
-        for o, rooms, (_, n, _, _) in zip(self.orcs, self.rooms, self.segs):
-            fin = rooms["end_turn"] >= 0
-            s["finished"] += int(fin.sum())
-            s["sum_end_turn"] += int(rooms["end_turn"][fin].sum())
-            s["end_turn_hist"] += np.bincount(np.minimum(rooms["end_turn"][fin] // 8, 15), minlength=16)
-            s["games_recycled"] += int(rooms["games"].sum())
-            if o.table.pack == 1:
-                alive = rooms["p"][:, :n, 2]
-                wolves = ((rooms["p"][:, :n, 1] == 2) & (alive == 1)).sum(axis=1)
-                s["alive_players"] += int(alive.sum())
-                s["village_wins"] += int((fin & (wolves == 0)).sum())
-                s["wolf_wins"] += int((fin & (wolves > 0)).sum())
-            else:
-                s["alive_players"] += n * len(rooms)                 # nobody is eliminated in Two-Truths
-                s["score_hist"] += np.bincount(np.minimum(rooms["p"][:, :n, 7].ravel(), 15), minlength=16)
-        s["end_turn_hist"], s["score_hist"] = s["end_turn_hist"].tolist(), s["score_hist"].tolist()
-        return s
 
 
 # rooms per segment straddle the 4 KB stack / pinned threshold of rooms_io: 32-B records 128 | 129, 24-B 170 | 171, 40-B 102 | 103
