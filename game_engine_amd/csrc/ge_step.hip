@@ -1049,3 +1049,4 @@ void ge_batch_destroy(ge_batch *b) {
 #include "ge_run.inl"           // behind ge_compare.inl: listed rooms played on until a person is needed (ge_batch_run_rooms)
 #include "ge_run_playout.inl"   // behind ge_run.inl: the same with playout seats (ge_batch_run_rooms_playout)
 #include "ge_timeline.inl"      // behind ge_run_playout.inl: a run-on with a forecast of every turn (ge_batch_run_rooms_forecast)
+#include "ge_find.inl"          // behind ge_timeline.inl: the rooms of a range that need attention (ge_batch_find_rooms)

@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 
 #include <string>
 #include <vector>
@@ -574,6 +575,53 @@ napi_value RunRooms(napi_env env, napi_callback_info info) {
     return out;
 }
 
+// findRooms(batch, first, count, want: GE_FIND_* bits, masks: Uint32Array (one word per segment) | null, cap): { hits: ArrayBuffer of
+// nHits ge_room_hit (16 B each), nHits, matched } - the rooms of a range that need attention (ge_batch_find_rooms, POLICY.md §3k).
+// Synchronous; GE_BUSY from batch_arg.
+napi_value FindRooms(napi_env env, napi_callback_info info) {
+    size_t argc = 6;
+    napi_value argv[6];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
+    if (!b || argc < 6) return throw_status(env, GE_ERR_ARG, "findRooms");
+    int64_t first = 0, count = 0, cap = 0;
+    uint32_t want = 0;
+    if (napi_get_value_int64(env, argv[1], &first) != napi_ok || napi_get_value_int64(env, argv[2], &count) != napi_ok ||
+        napi_get_value_uint32(env, argv[3], &want) != napi_ok || napi_get_value_int64(env, argv[5], &cap) != napi_ok || first < 0 || count < 0 || cap < 0)
+        return throw_status(env, GE_ERR_ARG, "findRooms", "first, count, want, cap (non-negative numbers) expected");
+    const uint32_t *masks = nullptr;
+    napi_valuetype vt;
+    NAPI_OK(napi_typeof(env, argv[4], &vt));
+    if (vt != napi_null && vt != napi_undefined) {
+        napi_typedarray_type tt;
+        size_t len, off;
+        void *data;
+        napi_value ab;
+        if (napi_get_typedarray_info(env, argv[4], &tt, &len, &data, &ab, &off) != napi_ok || tt != napi_uint32_array || len < GE_MAX_SEGMENTS)
+            return throw_status(env, GE_ERR_ARG, "findRooms", "masks: a Uint32Array of GE_MAX_SEGMENTS words, or null");
+        masks = static_cast<const uint32_t *>(data);
+    }
+    uint64_t n_total = 0;
+    (void)ge_batch_n_rooms(b, &n_total);
+    // no buffer for a range the library refuses; otherwise min(cap, count) slots, cut to the hits there are
+    const uint64_t slots = (uint64_t)first + (uint64_t)count <= n_total ? std::min<uint64_t>((uint64_t)cap, (uint64_t)count) : 0;
+    std::vector<ge_room_hit> hits((size_t)slots);
+    uint64_t n_hits = 0, n_match = 0;
+    const int st = ge_batch_find_rooms(b, (uint64_t)first, (uint64_t)count, want, masks, slots ? hits.data() : nullptr, slots, &n_hits, &n_match);
+    if (st != GE_OK) return throw_status(env, st, "findRooms");
+    void *dst = nullptr;
+    napi_value buf, out, v;
+    NAPI_OK(napi_create_arraybuffer(env, (size_t)n_hits * sizeof(ge_room_hit), &dst, &buf));
+    if (n_hits) memcpy(dst, hits.data(), (size_t)n_hits * sizeof(ge_room_hit));
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_set_named_property(env, out, "hits", buf));
+    NAPI_OK(napi_create_double(env, (double)n_hits, &v));
+    NAPI_OK(napi_set_named_property(env, out, "nHits", v));
+    NAPI_OK(napi_create_double(env, (double)n_match, &v));
+    NAPI_OK(napi_set_named_property(env, out, "matched", v));
+    return out;
+}
+
 // runRoomsPlayout(batch, rooms: BigUint64Array, keys: BigUint64Array, turns: Uint32Array, masks: Uint32Array, playoutKeys:
 // BigUint64Array, nRollouts, playoutMaxTurns, seed: BigInt, flags, maxTurns, until: GE_RUN_UNTIL_* bits, views: boolean): runRooms's
 // result plus decided: Uint32Array of rooms.length x maxTurns - runRooms with playout seats (ge_batch_run_rooms_playout, POLICY.md
@@ -1101,6 +1149,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"runRooms", nullptr, RunRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"runRoomsPlayout", nullptr, RunRoomsPlayout, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"runRoomsForecast", nullptr, RunRoomsForecast, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"findRooms", nullptr, FindRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"readRoomsAt", nullptr, ReadRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"rollout", nullptr, Rollout, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"writeRoomsAt", nullptr, WriteRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},

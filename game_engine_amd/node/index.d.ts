@@ -35,6 +35,11 @@ export interface TurnEvent {
 export type RunUntil = 'person' | 'end' | 'phase';
 export function runUntilBits(until: RunUntil[] | RunUntil | number): number;
 export function runUntilNames(bits: number): RunUntil[];
+export type FindWant = 'person' | 'end' | 'phase';
+export function findWantBits(want: FindWant[] | FindWant | number): number;
+export function findWantNames(bits: number): FindWant[];
+/** A room findRooms matched: why = the conditions of `want` that hold, pending = the host-driven seats that could act now. */
+export interface RoomHit { room: number; why: FindWant[]; pending: number[]; phaseId: number; segment: number; }
 export interface ToolCall { name: 'update_player_actions' | 'set_next_phase' | 'update_player_state' | 'add_game_note'; args: Record<string, unknown>; }
 export interface PhaseInfo { id: number; name: string; completion: number; act: number; effect: number; nBranches: number; }
 
@@ -82,6 +87,11 @@ export class RoomBatch {
   runRooms(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, maxTurns?: number,
            until?: RunUntil[] | RunUntil | number, views?: boolean):
     { played: Uint32Array; stopped: Uint32Array; events: TurnEvent[][]; views: RoomState[][] | null };
+  /** The rooms of a range that need attention, as they stand (POLICY.md §3k; the batch is only read): "person" = runRooms's test,
+   *  "end" = a terminal phase, "phase" = the room's phase id is in `phases` (ids for every segment, or segment -> ids).  hits: the
+   *  first min(matched, cap) matches in ascending room order; cap 0 counts only.  Synchronous; GE_BUSY while an async step() is in flight. */
+  findRooms(options?: { want?: FindWant[] | FindWant | number; phases?: number[] | Record<number, number[]> | null; first?: number;
+                        count?: number; cap?: number }): { hits: RoomHit[]; matched: number };
   /** runRooms with playout seats (POLICY.md §3g): stepRoomsPlayout's entries (rooms[k], keys[k], turns[k] + t, masks[k], playoutKeys[k])
    *  turn after turn, stopped as runRooms stops them, without a host wait between the turns.  decided[k][t]: turn t's decided mask.
    *  Synchronous; GE_BUSY while an async step() is in flight. */

@@ -502,17 +502,25 @@ class RoomLog {
 
 // include/ge_step.h GE_RUN_UNTIL_*
 const RUN_UNTIL = { person: 1, end: 2, phase: 4 };
-/** `until` of runRooms / runRoom as the ABI's bit set: an array of "person" / "end" / "phase", one of them, or the bits. */
-function runUntilBits(until) {
-  if (typeof until === 'number') return until;
+// an array of names of `names`, one of them, or the bits themselves, as the ABI's bit set
+function namedBits(value, names, what) {
+  if (typeof value === 'number') return value;
   let bits = 0;
-  for (const name of typeof until === 'string' ? [until] : until) {
-    if (!Object.prototype.hasOwnProperty.call(RUN_UNTIL, name)) throw new RangeError(`until: unknown stop condition ${JSON.stringify(name)}`);
-    bits |= RUN_UNTIL[name];
+  for (const name of typeof value === 'string' ? [value] : value) {
+    if (!Object.prototype.hasOwnProperty.call(names, name)) throw new RangeError(`${what} ${JSON.stringify(name)}`);
+    bits |= names[name];
   }
   return bits;
 }
+/** `until` of runRooms / runRoom as the ABI's bit set: an array of "person" / "end" / "phase", one of them, or the bits. */
+function runUntilBits(until) { return namedBits(until, RUN_UNTIL, 'until: unknown stop condition'); }
 function runUntilNames(bits) { return Object.keys(RUN_UNTIL).filter((name) => bits & RUN_UNTIL[name]); }
+
+// include/ge_step.h GE_FIND_*
+const FIND_WANT = { person: 1, end: 2, phase: 4 };
+/** `want` of findRooms as the ABI's bit set: an array of "person" / "end" / "phase", one of them, or the bits. */
+function findWantBits(want) { return namedBits(want, FIND_WANT, 'want: unknown condition'); }
+function findWantNames(bits) { return Object.keys(FIND_WANT).filter((name) => bits & FIND_WANT[name]); }
 
 function decodeEvent(buffer, off) {
   const dv = new DataView(buffer, off, EVENT_SIZE);
@@ -636,6 +644,38 @@ class RoomBatch {
       if (views) states.push(vw);
     }
     return { played: r.played, stopped: r.stopped, events, views: states };
+  }
+  /** The rooms of first .. first + count - 1 that need attention, as they stand (twin of the Python RoomBatch.find_rooms, POLICY.md
+   * §3k; the batch is only read).  want: an array of "person" (a host-driven seat of the room's segment is a pending target:
+   * runRooms's test), "end" (a terminal phase) and "phase" (the room's phase id is in `phases`), or the ABI's bit set.  phases: an
+   * array of phase ids for every segment, or an object segment -> array; it requires "phase" in want.  Returns { hits, matched }:
+   * hits are the first min(matched, cap) matches in ascending room order, each { room, why: [names], pending: [seats that could act
+   * now], phaseId, segment }; matched counts every match of the range.  count undefined: to the end of the batch; cap undefined:
+   * count; cap 0 counts only.  A truncated scan goes on from first = last hit's room + 1.  Synchronous; GE_BUSY while an async
+   * step() is in flight. */
+  findRooms({ want = ['person', 'end'], phases = null, first = 0, count, cap } = {}) {
+    const bits = findWantBits(want);
+    let masks = null;
+    if (phases !== null && phases !== undefined) {
+      if (!(bits & FIND_WANT.phase)) throw new RangeError('findRooms: phases requires "phase" in want');
+      masks = new Uint32Array(4);                              // GE_MAX_SEGMENTS
+      for (let g = 0; g < this.segments.length; g++) {
+        for (const pid of Array.isArray(phases) ? phases : (phases[g] || [])) {
+          if (!Number.isInteger(pid) || pid < 0 || pid >= 32) throw new RangeError(`findRooms: phase id ${pid}`);
+          masks[g] = (masks[g] | (1 << pid)) >>> 0;
+        }
+      }
+    }
+    const n = count === undefined ? this.nRooms - first : count;
+    const r = addon.findRooms(this.handle, first, n, bits, masks, cap === undefined ? n : cap);
+    const dv = new DataView(r.hits), hits = [];
+    for (let k = 0; k < r.nHits; k++) {
+      const pending = dv.getUint16(16 * k + 12, true), seats = [];
+      for (let i = 0; i < 12; i++) if ((pending >> i) & 1) seats.push(i + 1);
+      hits.push({ room: Number(dv.getBigUint64(16 * k, true)), why: findWantNames(dv.getUint32(16 * k + 8, true)), pending: seats,
+                  phaseId: dv.getUint8(16 * k + 14), segment: dv.getUint8(16 * k + 15) });
+    }
+    return { hits, matched: r.matched };
   }
   /** runRooms with playout seats (twin of the Python RoomBatch.run_rooms_playout, POLICY.md §3g): room k takes stepRoomsPlayout's
    * entries (rooms[k], keys[k], turns[k] + t, masks[k], playoutKeys[k]; nRollouts, playoutMaxTurns, seed, fullView), t = 0, 1, ...,
@@ -918,5 +958,5 @@ class DeviceGroup {
 
 const { compileCriteria, audienceGroups, uiToolCalls } = require('./ui_script.js');
 
-module.exports = { GameTable, RoomBatch, runUntilBits, runUntilNames, decodeRoom, agentStateToView, ShardedBatch, DeviceGroup, locateInShards, RoomLog, formatNote, loadDslByGamename, findGameFile, initializePlayers, turnToolCalls, compileCriteria, audienceGroups, uiToolCalls,
+module.exports = { GameTable, RoomBatch, runUntilBits, runUntilNames, findWantBits, findWantNames, decodeRoom, agentStateToView, ShardedBatch, DeviceGroup, locateInShards, RoomLog, formatNote, loadDslByGamename, findGameFile, initializePlayers, turnToolCalls, compileCriteria, audienceGroups, uiToolCalls,
                    deviceCount: addon.deviceCount, addon };

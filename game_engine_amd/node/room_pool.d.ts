@@ -13,6 +13,10 @@ export class RoomPoolService {
   continueRoom(threadId: string, items?: { id: string; type: string }[]): Promise<TurnResult>;
   /** As RoomService.runRoom, from the thread's pool slot. */
   runRoom(threadId: string, maxTurns?: number, until?: RunUntil[], items?: { id: string; type: string }[], options?: RunOptions): Promise<RunResult>;
+  /** The threads that wait for a person, and the seats that could act now in each: one findRooms per chunk (POLICY.md §3k). */
+  waiting(): Promise<Record<string, number[]>>;
+  /** The threads whose game stands in a terminal phase. */
+  finished(): Promise<string[]>;
   /** runRoom for many threads, in order: one runRooms call per chunk touched; a thread may be named once.  items[j]: thread j's items.
    *  options.forecast: one runRoomsForecast call per chunk touched instead, and every result gains forecasts (options.seats[j]: thread j's seat). */
   runRooms(threadIds: string[], maxTurns?: number, until?: RunUntil[], items?: ({ id: string; type: string }[] | undefined)[],

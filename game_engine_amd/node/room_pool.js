@@ -359,6 +359,25 @@ class RoomPoolService {
     room.panel = M.newestPanel(uiCalls);
     return { state, toolCalls, uiCalls };
   }
+  // one findRooms per chunk that holds a thread; [threadId, hit] of the slots a thread owns (a free slot holds a template room or
+  // what its last thread left: never reported)
+  _scan(want) {
+    const owner = new Map();                                   // chunk -> Map(slot -> threadId)
+    for (const [threadId, room] of this.rooms) {
+      if (!owner.has(room.chunk)) owner.set(room.chunk, new Map());
+      owner.get(room.chunk).set(room.slot, threadId);
+    }
+    const out = [];
+    for (const [chunk, slots] of owner) {
+      for (const h of chunk.findRooms({ want }).hits) if (slots.has(h.room)) out.push([slots.get(h.room), h]);
+    }
+    return out;
+  }
+  /** The threads that wait for a person, and for whom: { threadId: [seats that could act now] } (twin of the Python
+   * RoomPoolService.waiting) - one findRooms per chunk instead of a walk over the threads' states. */
+  waiting() { return this._serial(() => Object.fromEntries(this._scan(['person']).map(([t, h]) => [t, h.pending]))); }
+  /** The threads whose game stands in a terminal phase: [threadId] (twin of the Python RoomPoolService.finished). */
+  finished() { return this._serial(() => this._scan(['end']).map(([t]) => t)); }
   _release(threadId) {
     const room = this.rooms.get(threadId);
     if (!room) return false;

@@ -21,7 +21,7 @@ from .room_service import (PLAYOUT_CAP, RolloutRequest, adopted_output, advise_c
                            check_forecast_args, check_forecast_seat, check_playout_options, check_run_args, check_run_forecast, check_run_thread, check_view,
                            forecast_key, forecast_seed, playout_mask, playout_max_cands, prepare_adoption, room_index_of, neutral_beliefs, run_forecast_per_call,
                            run_forecasts, run_output, run_rollouts, run_turn, seat_forecast_output)
-from .stepper import GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, load_dsl_by_gamename, slot_values
+from .stepper import GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, load_dsl_by_gamename, pending_seats, slot_values
 from .toolcalls import WW_IS_ALIVE, RoomLog, turn_tool_calls
 from .ui_script import ui_tool_calls
 
@@ -429,6 +429,27 @@ class RoomPoolService:
         return [advise_output(room["table"], room["names"], tid, room["turn"], seats[j], room["view"], cands[j], n_rollouts, max_turns,
                               res[j][0], res[j][1], seat_view, res[j][2] if compare else None, bel[j])
                 for j, (tid, room) in enumerate(zip(thread_ids, rooms))]
+
+    def _scan(self, want) -> List[Tuple[str, Any]]:
+        """One find_rooms per chunk that holds a thread; (thread_id, hit) of the slots a thread owns - a free slot holds a template
+        room or what its last thread left, and is never reported."""
+        owner: Dict[int, Tuple[Any, Dict[int, str]]] = {}
+        for tid, room in self._rooms.items():
+            owner.setdefault(id(room["chunk"]), (room["chunk"], {}))[1][room["slot"]] = tid
+        out = []
+        for chunk, slots in owner.values():
+            hits, _ = chunk.find_rooms(want)
+            out.extend((slots[int(h["room"])], h) for h in hits if int(h["room"]) in slots)
+        return out
+
+    def waiting(self) -> Dict[str, List[int]]:
+        """The threads that wait for a person, and for whom: {thread_id: [seats that could act now]} - from one find_rooms per
+        chunk (POLICY.md §3k) instead of a walk over the threads' states."""
+        return {tid: pending_seats(h["pending"]) for tid, h in self._scan(("person",))}
+
+    def finished(self) -> List[str]:
+        """The threads whose game stands in a terminal phase."""
+        return [tid for tid, _ in self._scan(("end",))]
 
     def close(self, thread_id: Optional[str] = None):
         """Close one thread (its slot goes back to the pool's free list) or, without an id, every thread and every chunk."""

@@ -43,22 +43,46 @@ GE_MAX_PLAYERS = 12                       # include/ge_step.h
 RUN_UNTIL = {"person": 1, "end": 2, "phase": 4}   # include/ge_step.h GE_RUN_UNTIL_*
 
 
+def _named_bits(value, names: Dict[str, int], what: str) -> int:
+    """A sequence of names of `names`, one of them, or the bits themselves, as the ABI's bit set."""
+    if isinstance(value, (int, np.integer)):
+        return int(value)
+    if isinstance(value, str):
+        value = (value,)
+    bits = 0
+    for name in value:
+        if name not in names:
+            raise ValueError(f"{what} {name!r}")
+        bits |= names[name]
+    return bits
+
+
 def run_until_bits(until) -> int:
     """`until` of run_rooms / run_room as the ABI's bit set: a sequence of "person" / "end" / "phase", or the bits themselves."""
-    if isinstance(until, (int, np.integer)):
-        return int(until)
-    if isinstance(until, str):
-        until = (until,)
-    bits = 0
-    for name in until:
-        if name not in RUN_UNTIL:
-            raise ValueError(f"until: unknown stop condition {name!r}")
-        bits |= RUN_UNTIL[name]
-    return bits
+    return _named_bits(until, RUN_UNTIL, "until: unknown stop condition")
 
 
 def run_until_names(bits: int) -> List[str]:
     return [name for name, bit in RUN_UNTIL.items() if bits & bit]
+
+
+FIND_WANT = {"person": 1, "end": 2, "phase": 4}   # include/ge_step.h GE_FIND_*
+# include/ge_step.h ge_room_hit
+ROOM_HIT_DTYPE = np.dtype([("room", "<u8"), ("why", "<u4"), ("pending", "<u2"), ("phase_id", "u1"), ("segment", "u1")])
+
+
+def find_want_bits(want) -> int:
+    """`want` of find_rooms as the ABI's bit set: a sequence of "person" / "end" / "phase", or the bits themselves."""
+    return _named_bits(want, FIND_WANT, "want: unknown condition")
+
+
+def find_want_names(bits: int) -> List[str]:
+    return [name for name, bit in FIND_WANT.items() if bits & bit]
+
+
+def pending_seats(pending: int) -> List[int]:
+    """the seats (1-based) of a hit's `pending` mask"""
+    return [i + 1 for i in range(GE_MAX_PLAYERS) if (int(pending) >> i) & 1]
 
 
 class GeError(RuntimeError):
@@ -444,6 +468,38 @@ class RoomBatch:
                                                      stopped.ctypes.data, events.ctypes.data, out.ctypes.data, out.nbytes,
                                                      stats.ctypes.data, stats.nbytes), "ge_batch_run_rooms_forecast")
         return played, stopped, events, out, stats
+
+    def find_rooms(self, want=("person", "end"), phases=None, first: int = 0, count: Optional[int] = None,
+                   cap: Optional[int] = None) -> Tuple[np.ndarray, int]:
+        """The rooms of first .. first + count - 1 that need attention, as they stand (POLICY.md §3k; the batch is only read).
+        `want` is a sequence of "person" (a host-driven seat of the room's segment is a pending target: run_rooms's test), "end"
+        (a terminal phase) and "phase" (the room's phase id is in `phases`), or the ABI's bit set.  phases: a list of phase ids
+        for every segment, or a dict segment -> list; it requires "phase" in `want`.  Returns (hits, n_match): hits
+        (ROOM_HIT_DTYPE: room, why, pending, phase_id, segment) are the first min(n_match, cap) matches in ascending room order,
+        `why` the FIND_WANT bits that hold, `pending` bit i = host-driven seat i+1 could act now (pending_seats); n_match counts
+        every match of the range.  count None: to the end of the batch; cap None: count; cap 0 counts only.  A truncated scan
+        goes on from first = hits[-1]["room"] + 1."""
+        bits = find_want_bits(want)
+        masks = None
+        if phases is not None:
+            if not bits & FIND_WANT["phase"]:
+                raise ValueError('find_rooms: phases requires "phase" in want')
+            masks = np.zeros(len(self.segments), dtype=np.uint32)
+            for g in range(len(self.segments)):
+                for pid in (phases.get(g, ()) if isinstance(phases, dict) else phases):
+                    if not 0 <= int(pid) < 32:
+                        raise GeError(GE_ERR_ARG, "find_rooms: phase id")
+                    masks[g] |= np.uint32(1 << int(pid))
+        count = self.n_rooms - first if count is None else count
+        cap = count if cap is None else cap
+        if min(int(first), int(count), int(cap)) < 0:
+            raise GeError(GE_ERR_ARG, "find_rooms: first / count / cap")
+        hits = np.zeros(max(0, min(int(cap), int(count))), dtype=ROOM_HIT_DTYPE)
+        n_hits, n_match = C.c_uint64(), C.c_uint64()
+        _check(self._lib.ge_batch_find_rooms(self._h, first, count, bits, masks.ctypes.data if masks is not None else None,
+                                             hits.ctypes.data if len(hits) else None, len(hits), C.byref(n_hits), C.byref(n_match)),
+               "ge_batch_find_rooms")
+        return hits[: n_hits.value], int(n_match.value)
 
     def read_rooms_at(self, rooms) -> np.ndarray:
         """Canonical views of the listed rooms, out[k] = room rooms[k] (any order, repeats allowed)."""

@@ -50,7 +50,8 @@ extern "C" {
  *      ge_batch_run_rooms_forecast (ge_batch_run_rooms with the ge_batch_rollout_seats forecast of every turn it played: a win-odds timeline);
  *      GE_PLAYOUT_HALVING (a new flag of both playout-seat calls, no new symbol: sequential halving of each decision's playout
  *      budget; a library from before it refuses the bit with GE_ERR_ARG);
- *      ge_batch_rollout_beliefs + GE_BELIEF_SLOTS (seat-view playouts and comparisons whose re-deal is weighted by the caller's suspicions) */
+ *      ge_batch_rollout_beliefs + GE_BELIEF_SLOTS (seat-view playouts and comparisons whose re-deal is weighted by the caller's suspicions);
+ *      ge_batch_find_rooms + ge_room_hit + GE_FIND_* (a device scan of a range: the rooms that wait for a person, have ended or stand in given phases) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -569,6 +570,46 @@ int ge_batch_run_rooms_forecast(ge_batch *b, uint64_t n, const uint64_t *rooms, 
                                 ge_turn_event *events /* n * max_turns, may be NULL */,
                                 ge_room_view *views /* n * max_turns, may be NULL */, size_t views_cap_bytes,
                                 ge_rollout_stats *stats /* n * (max_turns + 1) */, size_t stats_cap_bytes);
+
+/* The rooms of a range that need attention: a device scan of a resident batch (POLICY.md §3k).  Over the rooms first .. first +
+ * count - 1 as they stand (local indices, as ge_batch_read_rooms counts), a room matches when some condition named in `want` holds:
+ *   GE_FIND_PERSON  some seat of the segment's human_mask is a pending target - word for word the PERSON test of ge_batch_run_rooms.
+ *                   `pending` says which: bit i is set exactly when seat i+1 is in the segment's human_mask and
+ *                   ge_batch_inject_action(room, i+1, c) would be accepted for at least one c (0 without GE_FIND_PERSON in `want`)
+ *   GE_FIND_END     the room's phase is terminal, with or without GE_FLAG_RESTART: the record is judged as stored
+ *   GE_FIND_PHASE   bit phase_id of phase_masks[segment of the room] is set (n_segments words, read only with this bit)
+ * `why` holds the bits of `want` that hold for the room (never 0).  *n_match = the matches in the range; *n_hits = min(n_match,
+ * cap); hits[0 .. n_hits) are the first matches in ascending room order, slots from n_hits on are untouched.  cap == 0 counts only
+ * (hits may be NULL).  A truncated scan is resumed with first = hits[n_hits - 1].room + 1.
+ * The batch is only read: records, prepared deals (in the record and in the Werewolf x 12 side plane), the turn counter and the
+ * GE_FLAG_TRACE buffer stay as they are.  All errors before anything runs, every output untouched, in this order: GE_ERR_ARG for
+ * want == 0 or unknown bits; for n_hits or n_match NULL; for hits NULL with cap > 0; for GE_FIND_PHASE with phase_masks NULL; for a
+ * mask bit at or above the phase count of its segment's table (a wrong stride); GE_ERR_RANGE for first + count beyond the batch;
+ * then count == 0: GE_OK, both counters 0.
+ * One test launch per segment of the range (lane = room, records loaded as the step kernels load them: one result word per room,
+ * one match count per wavefront), one launch that scans the wavefront counts, one that re-reads the result words and stores the
+ * hits at their wavefronts' offsets: no block waits for another, and the order of the output does not depend on scheduling.  Only
+ * n_hits * 16 bytes and two counters cross to the host.  With ge_batch_set_timing on, ge_batch_kernel_time includes the call's
+ * launches.  Ordered behind the previous step; synchronises.
+ * Measured on an MI355X (tools/find_probe.py, profiles/find_probe.txt: Werewolf x 8, human_mask = 1, 40 turns stepped and nobody
+ * answering, so that 99 % of the rooms match and every hit is copied back - the call's worst case; medians of 20 calls): against
+ * ge_batch_read_rooms of the range into a reused array plus the host's END test, the call is 21 x faster at 65 536 rooms (124 us
+ * against 2.66 ms) and 8.8 x at 1 048 576 (1.50 ms against 13.2 ms); its three launches take 11 us and 40 us of that, the rest is
+ * the copy of the hits (16 B each) and their conversion.
+ * A phase id of 32 or more has no bit in a mask word (the shipped tables' terminal phases, 98 and 99): GE_FIND_END finds those. */
+#define GE_FIND_PERSON 1u   /* == GE_RUN_UNTIL_PERSON: some seat of the segment's human_mask is a pending target */
+#define GE_FIND_END    2u   /* == GE_RUN_UNTIL_END: the room's phase is terminal */
+#define GE_FIND_PHASE  4u   /* bit phase_id of phase_masks[segment of the room] is set */
+typedef struct ge_room_hit {          /* 16 B */
+    uint64_t room;                    /* local index, as ge_batch_read_rooms counts */
+    uint32_t why;                     /* the bits of `want` that hold for the room (never 0) */
+    uint16_t pending;                 /* want & GE_FIND_PERSON: bit i = host-driven seat i+1 could act now; else 0 */
+    uint8_t  phase_id;
+    uint8_t  segment;
+} ge_room_hit;
+int ge_batch_find_rooms(ge_batch *b, uint64_t first, uint64_t count, uint32_t want,
+                        const uint32_t *phase_masks /* n_segments words; read only with GE_FIND_PHASE */,
+                        ge_room_hit *hits, uint64_t cap, uint64_t *n_hits, uint64_t *n_match);
 
 /* GE_FLAG_TRACE: events of the most recent ge_batch_step call, dst[(room - first) * *n_turns + t].
  * cap_bytes >= count * n_turns * sizeof(ge_turn_event).  Synchronises. */

@@ -39,6 +39,9 @@ def describe(mangled: str) -> dict:
     m = re.search(r"ge_run_kernelILi(\d)ELi(\d)E", mangled)
     if m:
         return {"kernel": "ge_run_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True}
+    m = re.search(r"ge_find_kernelILi(\d)ELi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_find_kernel", "layout": KINDS[int(m.group(1))], "lowocc": False, "generic": int(m.group(2)), "single": True}
     m = re.search(r"ge_rollout_kernelILi(\d)ELi(\d)E(?:Li(\d)E)?", mangled)
     if m:
         return {"kernel": "ge_rollout_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True,
@@ -91,6 +94,11 @@ def label(r):
         return f"{r['layout']}, indexed single-turn (ge_batch_step_rooms)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_run_kernel":                           # ge_batch_run_rooms: one launch per segment present
         return f"{r['layout']}, indexed turn loop (ge_batch_run_rooms)" + (", GENERIC" if r["generic"] else "")
+    if r["kernel"] == "ge_find_kernel":                          # ge_batch_find_rooms: one launch per segment of the range
+        return f"{r['layout']}, test of a range of rooms (ge_batch_find_rooms)" + (", GENERIC" if r["generic"] else "")
+    if r["kernel"] in ("ge_find_scan", "ge_find_emit"):          # ge_batch_find_rooms: behind the test launches
+        what = {"ge_find_scan": "the scan of the wavefront counts", "ge_find_emit": "the ordered store of the hits"}[r["kernel"]]
+        return f"{r['kernel']} (ge_batch_find_rooms: {what})"
     if r["kernel"] == "ge_rollout_kernel" and r.get("act") == 4:  # GE_PLAYOUT_HALVING: one launch per unit and round
         return f"{r['layout']}, playouts over a replica range (GE_PLAYOUT_HALVING)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_playout_plan_ranged":
