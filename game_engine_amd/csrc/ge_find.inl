@@ -15,7 +15,8 @@
 //
 // The PERSON test is ge_run.inl's, reused: Werewolf - lane_ww_ctx, the row of the room's phase, ww_targets less who has acted,
 // within the human mask; Two-Truths - inject_tt on a copy of the record per seat of the human mask, choice 1.  `pending` is that
-// mask seat by seat.  A segment without host-driven seats skips the test wave-uniformly.
+// mask seat by seat.  The mask is the room's own where the batch has a seat plane (ge_pool.inl lane_seat_mask), so the test is per
+// lane; a wavefront whose rooms have no host-driven seat still skips it wave-uniformly.
 
 namespace {
 
@@ -25,6 +26,7 @@ constexpr uint32_t FIND_SCAN_WAVES = 1024u;     // wavefront counts one pass of 
 struct FindArgs {
     uint32_t *res;             // this part's result words (padded to whole wavefronts)
     uint32_t *counts;          // this part's wavefront counts
+    const uint16_t *seats;     // the batch's seat plane, or null (ge_pool.inl lane_seat_mask)
     uint64_t r0, nr;           // the part: segment-local rooms r0 .. r0 + nr - 1
     uint32_t seg, want, row_mask, pad;
 };
@@ -48,14 +50,15 @@ __device__ __forceinline__ uint32_t find_ww(const SegDev &sg, const DevTable *__
     using L = WWLayout<NB>;
     uint32_t w[L::WORDS];
     load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
-    const WwCtx ctx = lane_ww_ctx<GENERIC, true>(sg, tables, nullptr, 0u, true);
-    const uint32_t human = __builtin_amdgcn_readfirstlane(sg.human_mask);
+    const uint32_t human = lane_seat_mask(sg, a.seats, room);
+    const WwCtx ctx = lane_ww_ctx<GENERIC>(sg, tables, nullptr, 0u, true, human);
+    const bool any = a.seats ? __ballot(human != 0u) != 0ull : __builtin_amdgcn_readfirstlane(human) != 0u;
     const uint32_t ALL = (1u << sg.n_players) - 1u;
     WWR<NB> s;
     uint32_t cache;                                           // the record's prepared deal: no part of the test
     ww_load_regs<NB>(w, s, cache);
     uint32_t pending = 0;
-    if ((a.want & GE_FIND_PERSON) && human != 0u) {           // (wave-uniform)
+    if ((a.want & GE_FIND_PERSON) && any) {                   // (wave-uniform)
         const DevRow row = lds_row<false>(ctx.rows, s.phase);
         const uint32_t T = ww_targets<NB, true, GENERIC>(s, row, ctx, s.template get<F_ALIVE>(), ALL);
         pending = T & ~s.acted & human;
@@ -69,16 +72,18 @@ __device__ __forceinline__ uint32_t find_tt(const SegDev &sg, const DevTable *__
     uint32_t w[L::WORDS];
     load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
     const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
-    const uint32_t human = __builtin_amdgcn_readfirstlane(sg.human_mask) & ((1u << sg.n_players) - 1u);
+    // the seats probed are the wavefront's: with a seat plane the union of its rooms' masks, each lane counting only its own bits
+    const uint32_t human = lane_seat_mask(sg, a.seats, room) & ((1u << sg.n_players) - 1u);
+    const uint32_t probe = a.seats ? wave_seat_union(human, NB) : (uint32_t)__builtin_amdgcn_readfirstlane(human);
     TT<NB> s;
     L::unpack(w, s);
     uint32_t pending = 0;
-    if ((a.want & GE_FIND_PERSON) && human != 0u) {           // (wave-uniform)
+    if ((a.want & GE_FIND_PERSON) && probe != 0u) {           // (wave-uniform)
         const DevRow &row = tables[sg.table_idx].rows[s.phase];
         const DevCond &cond = tables[sg.table_idx].conds[s.phase];   // read in place, as inject_group_tt
-        for (uint32_t m = human; m; m &= m - 1u) {
+        for (uint32_t m = probe; m; m &= m - 1u) {
             TT<NB> c = s;                                     // a pending target exactly when an injected action would be accepted
-            pending |= inject_tt<NB>(c, row, cond, sg.n_players, ctz(m) + 1u, 1u) == GE_OK ? m & (0u - m) : 0u;
+            pending |= inject_tt<NB>(c, row, cond, sg.n_players, ctz(m) + 1u, 1u) == GE_OK ? m & (0u - m) & human : 0u;
         }
     }
     return find_word(a.want, pending, s.phase, term_mask, a.row_mask);
@@ -215,6 +220,7 @@ static int find_rooms_impl(ge_batch *b, uint64_t first, uint64_t count, uint32_t
         FindArgs a;
         a.res = reinterpret_cast<uint32_t *>(dev) + p.res_off;
         a.counts = reinterpret_cast<uint32_t *>(dev + off_cnt) + p.res_off / 64u;
+        a.seats = b->seats;
         a.r0 = p.r0; a.nr = p.nr; a.seg = p.seg; a.want = want; a.row_mask = row_mask[p.seg]; a.pad = 0;
         const dim3 grid((uint32_t)((p.nr + FIND_BLOCK - 1u) / FIND_BLOCK));
         HIP_TRY(b->generic ? find_launch<1>(b->segs[p.seg].dev.kind, grid, s, b, a) : find_launch<0>(b->segs[p.seg].dev.kind, grid, s, b, a));

@@ -491,7 +491,8 @@ static int playout_check(const ge_batch *b, uint64_t n, const uint64_t *rooms, c
     for (uint64_t k = 0; k < n; k++) {
         const SegDev &sg = b->segs[pool_segment_of(b, rooms[k])].dev;
         const uint32_t m = playout_masks[k];
-        if ((m >> sg.n_players) != 0u || (m & sg.human_mask) != 0u) return GE_ERR_ARG;
+        const uint32_t human = b->seats_host.empty() ? sg.human_mask : (uint32_t)b->seats_host[(size_t)rooms[k]];   // the room's own seats (ge_seats.inl): the mirror decides
+        if ((m >> sg.n_players) != 0u || (m & human) != 0u) return GE_ERR_ARG;
         cost += (uint64_t)__builtin_popcount(m) * playout_max_cands(sg) * n_rollouts;
         if (cost > (1ull << 26)) return GE_ERR_ARG;
     }

@@ -57,14 +57,27 @@ template <int GENERIC> __device__ __forceinline__ CondCtx lane_cond_ctx(const Se
                    GENERIC ? pool_cond_shape(tables[sg.table_idx]) : CondShape{0u, 0u, 0u, 0u, 0u}};
 }
 
-// Werewolf: what the lane's turns keep constant.  PEOPLE: the segment's human seats are left to people (else the policy plays every
-// seat: the playouts); valid: the lane holds a real entry (else it shadows one and never acts)
-template <int GENERIC, bool PEOPLE> __device__ __forceinline__ WwCtx lane_ww_ctx(const SegDev &sg, const DevTable *__restrict__ tables, void *lw, uint32_t rk, bool valid) {
+// the lane's mask of host-driven seats: the room's own once the batch has a seat plane (ge_seats.inl; `seats` is a kernel argument,
+// so the test is wave-uniform), else its segment's.  room: segment-local
+__device__ __forceinline__ uint32_t lane_seat_mask(const SegDev &sg, const uint16_t *__restrict__ seats, uint64_t room) {
+    return seats ? (uint32_t)seats[sg.local_first + room] : sg.human_mask;
+}
+
+// the seats that are host-driven in some lane of the wavefront (bits below nb)
+__device__ __forceinline__ uint32_t wave_seat_union(uint32_t mask, int nb) {
+    uint32_t any = 0;
+    for (int i = 0; i < nb; i++) any |= __ballot((mask >> i) & 1u) != 0ull ? 1u << i : 0u;
+    return any;
+}
+
+// Werewolf: what the lane's turns keep constant.  human: the seats left to people - the lane's own mask (lane_seat_mask), or 0 where
+// the policy plays every seat (the playouts); valid: the lane holds a real entry (else it shadows one and never acts)
+template <int GENERIC> __device__ __forceinline__ WwCtx lane_ww_ctx(const SegDev &sg, const DevTable *__restrict__ tables, void *lw, uint32_t rk, bool valid, uint32_t human) {
     const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
     const CondCtx cc = lane_cond_ctx<GENERIC>(sg, tables);
     const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
     return WwCtx{reinterpret_cast<const DevRow *>(img), cc, lw, img + IMG_NTH8, reinterpret_cast<const uint32_t *>(img + IMG_ORD8), valid, sg.n_players, sg.nw,
-                 sg.phase0_idx, rk, PEOPLE ? sg.human_mask : 0u, term_mask};
+                 sg.phase0_idx, rk, human, term_mask};
 }
 
 // a finished room of a restarting batch becomes the init template with one more game, saturating (Two-Truths: the caller reloads
@@ -93,15 +106,15 @@ template <int NB, int GENERIC> __device__ __forceinline__ LaneTurn lane_ww_turn(
     return t;
 }
 
-template <int NB, int GENERIC, bool PEOPLE>
+template <int NB, int GENERIC>
 __device__ __forceinline__ LaneTurn lane_tt_turn(TT<NB> &s, uint32_t &done, const SegDev &sg, const DevTable *__restrict__ tables, const CondCtx &cc, void *lw,
-                                                 bool valid, uint32_t rk, uint32_t turn, bool log, uint32_t term_mask) {
+                                                 bool valid, uint32_t rk, uint32_t turn, bool log, uint32_t human, uint32_t term_mask) {
     const unsigned char *img = reinterpret_cast<const unsigned char *>(tables + sg.table_idx);
     const DevRow *rows = reinterpret_cast<const DevRow *>(img);
     DevRow row = lds_row<false>(rows, s.phase);
     LaneTurn t = {s.phase, 0u, 0ull};
     tt_turn<NB, tt_uses_queue(NB, true), false, GENERIC, true>(s, done, row, rows, cc, lw, img + IMG_NTH8, valid, sg.n_players, sg.rounds, sg.phase0_idx, rk,
-                                                             turn, log, PEOPLE ? sg.human_mask : 0u, term_mask, t.newly, t.choice);
+                                                             turn, log, human, term_mask, t.newly, t.choice);
     return t;
 }
 
@@ -120,6 +133,7 @@ struct PoolArgs {
     const uint64_t *keys;      // global room index its RNG stream is keyed by
     const uint32_t *turns;     // its turn number
     uint32_t *events;          // [n] x 4 words: lane_event
+    const uint16_t *seats;     // the batch's seat plane, or null (lane_seat_mask)
     uint32_t n, seg, seed_key, restart;
 };
 
@@ -134,7 +148,7 @@ __device__ __forceinline__ void pool_ww(const SegDev &sg, const DevTable *__rest
     load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
     const uint32_t rk = room_key_from(a.seed_key, a.keys[k]);
     const uint32_t turn = a.turns[k];
-    const WwCtx ctx = lane_ww_ctx<GENERIC, true>(sg, tables, lw, rk, valid);
+    const WwCtx ctx = lane_ww_ctx<GENERIC>(sg, tables, lw, rk, valid, lane_seat_mask(sg, a.seats, room));
     WWR<NB> s;
     uint32_t cache;                                           // the record's prepared deal: not of this key, never used
     ww_load_regs<NB>(w, s, cache);
@@ -163,7 +177,7 @@ __device__ __forceinline__ void pool_tt(const SegDev &sg, const DevTable *__rest
     uint32_t done = tt_done_mask<NB>(s.rounds, sg.rounds);
     const uint32_t restarted = lane_recycle(sg, s, a.restart, term_mask);
     if (restarted) done = __builtin_amdgcn_readfirstlane(sg.done0);
-    const LaneTurn t = lane_tt_turn<NB, GENERIC, true>(s, done, sg, tables, cc, lw, valid, rk, turn, true, term_mask);
+    const LaneTurn t = lane_tt_turn<NB, GENERIC>(s, done, sg, tables, cc, lw, valid, rk, turn, true, lane_seat_mask(sg, a.seats, room), term_mask);
     if (!valid) return;
     reinterpret_cast<u32x4 *>(a.events)[k] = lane_event(turn, t, s.phase, restarted);
     L::pack(s, w);
@@ -345,6 +359,7 @@ static int launch_pool_turn(ge_batch *b, hipStream_t s, const PoolEntries &en, c
         a.keys = reinterpret_cast<const uint64_t *>(dev + off_keys) + lo;
         a.turns = reinterpret_cast<const uint32_t *>(dev + off_turns) + lo;
         a.events = reinterpret_cast<uint32_t *>(dev + off_ev) + 4u * (size_t)lo;
+        a.seats = b->seats;
         a.n = cnt; a.seg = g; a.seed_key = seed_k;
         a.restart = (b->flags & GE_FLAG_RESTART) ? 1u : 0u;
         const dim3 grid((cnt + 63u) / 64u);

@@ -434,7 +434,7 @@ __device__ __forceinline__ void roll_ww(const SegDev &sg, const DevTable *__rest
     if constexpr (roll_weighted(ACT)) roll_view_ww<NB, true>(sg, tables, a, e, rk, turn0, w, a.beliefs);
     else if constexpr (ACT >= 2) roll_view_ww<NB>(sg, tables, a, e, rk, turn0, w);
     const uint32_t phase0 = __builtin_amdgcn_readfirstlane(sg.phase0_idx);
-    const WwCtx ctx = lane_ww_ctx<GENERIC, false>(sg, tables, lw, rk, true);   // every seat played by the policy
+    const WwCtx ctx = lane_ww_ctx<GENERIC>(sg, tables, lw, rk, true, 0u);   // every seat played by the policy
     const DevRow *rows = ctx.rows;
     WWR<NB> s;
     uint32_t cache;                                           // the record's prepared deal: not of these keys, never used
@@ -508,7 +508,7 @@ __device__ __forceinline__ void roll_tt(const SegDev &sg, const DevTable *__rest
     }
     uint32_t done = tt_done_mask<NB>(s.rounds, sg.rounds);
     for (uint32_t t = 0; t < a.max_turns; t++) {
-        lane_tt_turn<NB, GENERIC, false>(s, done, sg, tables, cc, lw, true, rk, turn0 + t, false, term_mask);
+        lane_tt_turn<NB, GENERIC>(s, done, sg, tables, cc, lw, true, rk, turn0 + t, false, 0u, term_mask);
         const bool settled = ((a.settle_mask >> s.phase) & 1u) && (s.phase != phase0 || (s.flags & FLAG_PHASE0_DONE));
         if (__ballot(!settled) == 0ull) break;
     }

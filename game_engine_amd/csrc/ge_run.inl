@@ -34,6 +34,7 @@ struct RunArgs {
     const uint32_t *turns;     // its first turn
     u32x4 *trace;              // the call's trace plane; this launch's entries start at slot `first`
     u32x2 *out;                // [n]: turns played, stop bits
+    const uint16_t *seats;     // the batch's seat plane, or null (ge_pool.inl lane_seat_mask)
     uint32_t n, seg, seed_key, restart;
     uint32_t max_turns, until, n_all, first;
 };
@@ -63,7 +64,8 @@ __device__ __forceinline__ void run_ww(const SegDev &sg, const DevTable *__restr
     load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
     const uint32_t rk = room_key_from(a.seed_key, a.keys[k]);
     const uint32_t turn0 = a.turns[k];
-    WwCtx ctx = lane_ww_ctx<GENERIC, true>(sg, tables, lw, rk, live);
+    const uint32_t human = lane_seat_mask(sg, a.seats, room);   // the room's own seats: per lane
+    WwCtx ctx = lane_ww_ctx<GENERIC>(sg, tables, lw, rk, live, human);
     const DevRow *rows = ctx.rows;
     const uint32_t term_mask = ctx.term_mask;
     const uint32_t ALL = (1u << sg.n_players) - 1u;
@@ -84,7 +86,7 @@ __device__ __forceinline__ void run_ww(const SegDev &sg, const DevTable *__restr
             if (a.until & GE_RUN_UNTIL_PERSON) {
                 const DevRow nrow = lds_row<false>(rows, s.phase);
                 const uint32_t T = ww_targets<NB, true, GENERIC>(s, nrow, ctx, s.template get<F_ALIVE>(), ALL);
-                why |= (T & ~s.acted & sg.human_mask) ? GE_RUN_UNTIL_PERSON : 0u;
+                why |= (T & ~s.acted & human) ? GE_RUN_UNTIL_PERSON : 0u;
             }
             why |= ((term_mask >> s.phase) & 1u) ? (a.until & GE_RUN_UNTIL_END) : 0u;
             why |= s.phase != p ? (a.until & GE_RUN_UNTIL_PHASE) : 0u;
@@ -111,7 +113,9 @@ __device__ __forceinline__ void run_tt(const SegDev &sg, const DevTable *__restr
     const uint32_t turn0 = a.turns[k];
     const CondCtx cc = lane_cond_ctx<GENERIC>(sg, tables);
     const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
-    const uint32_t human = __builtin_amdgcn_readfirstlane(sg.human_mask) & ((1u << sg.n_players) - 1u);
+    // the seats probed are the wavefront's: with a seat plane the union of its rooms' masks, each lane counting only its own bits
+    const uint32_t human = lane_seat_mask(sg, a.seats, room) & ((1u << sg.n_players) - 1u);
+    const uint32_t probe = a.seats ? wave_seat_union(human, NB) : (uint32_t)__builtin_amdgcn_readfirstlane(human);
     TT<NB> s;
     L::unpack(w, s);
     uint32_t done = tt_done_mask<NB>(s.rounds, sg.rounds);
@@ -119,19 +123,20 @@ __device__ __forceinline__ void run_tt(const SegDev &sg, const DevTable *__restr
         const uint32_t turn = turn0 + t;
         const uint32_t restarted = lane_recycle(sg, s, a.restart, term_mask);   // every turn
         if (restarted) done = __builtin_amdgcn_readfirstlane(sg.done0);
-        const LaneTurn ev = lane_tt_turn<NB, GENERIC, true>(s, done, sg, tables, cc, lw, live, rk, turn, true, term_mask);
+        const LaneTurn ev = lane_tt_turn<NB, GENERIC>(s, done, sg, tables, cc, lw, live, rk, turn, true, human, term_mask);
         const uint32_t p = ev.p;
         t++;
         if (live) {
             L::pack(s, w);
             run_trace<L::WORDS>(a, t - 1u, k, lane_event(turn, ev, s.phase, restarted), w);
             uint32_t why = 0;
-            if ((a.until & GE_RUN_UNTIL_PERSON) && human != 0u) {   // (wave-uniform)
+            if ((a.until & GE_RUN_UNTIL_PERSON) && probe != 0u) {   // (wave-uniform)
                 const DevRow &nrow = tables[sg.table_idx].rows[s.phase];
                 const DevCond &cond = tables[sg.table_idx].conds[s.phase];   // read in place, as inject_group_tt
-                for (uint32_t m = human; m; m &= m - 1u) {
+                for (uint32_t m = probe; m; m &= m - 1u) {
                     TT<NB> c = s;                             // a pending target exactly when an injected action would be accepted
-                    why |= inject_tt<NB>(c, nrow, cond, sg.n_players, ctz(m) + 1u, 1u) == GE_OK ? GE_RUN_UNTIL_PERSON : 0u;
+                    const bool ok = inject_tt<NB>(c, nrow, cond, sg.n_players, ctz(m) + 1u, 1u) == GE_OK;
+                    why |= (ok && (human & m & (0u - m)) != 0u) ? GE_RUN_UNTIL_PERSON : 0u;
                 }
             }
             why |= ((term_mask >> s.phase) & 1u) ? (a.until & GE_RUN_UNTIL_END) : 0u;
@@ -262,6 +267,7 @@ static int run_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const 
         a.turns = reinterpret_cast<const uint32_t *>(dev + off_turns) + lo;
         a.trace = reinterpret_cast<u32x4 *>(dev + off_trace);
         a.out = reinterpret_cast<u32x2 *>(dev + off_out) + lo;
+        a.seats = b->seats;
         a.n = cnt; a.seg = g; a.seed_key = seed_k;
         a.restart = (b->flags & GE_FLAG_RESTART) ? 1u : 0u;
         a.max_turns = max_turns; a.until = until; a.n_all = (uint32_t)n; a.first = lo;

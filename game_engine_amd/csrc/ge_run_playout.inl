@@ -318,6 +318,7 @@ static int run_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, cons
                 a.turns = d_cur + lo;
                 a.trace = reinterpret_cast<u32x4 *>(dev + o_trace) + 4u * N * t;
                 a.out = reinterpret_cast<u32x2 *>(dev + o_one) + lo;
+                a.seats = b->seats;
                 a.n = cnt; a.seg = g; a.seed_key = seed_b; a.restart = restart;
                 a.max_turns = 1u; a.until = until; a.n_all = (uint32_t)n; a.first = lo;
                 RunpRooms x;

@@ -55,6 +55,8 @@ struct ge_batch {
     void *trace = nullptr;            // GE_FLAG_TRACE: per segment [max_fuse][rooms_padded] x 16 B
     void *deal_side = nullptr;        // Werewolf x 12 segments: prepared role deals of the single-turn launches, [rooms_padded] x 8 B each (ge_kernels.inl run_ww); allocated by the first single-turn launch (ensure_deal_side)
     bool deal_side_failed = false;    // ... or never (no Werewolf x 12 segment / no memory for a cache)
+    uint16_t *seats = nullptr;        // the seat plane (ge_seats.inl): each room's mask of host-driven seats, [n_rooms] x 2 B in batch-local room order; null until the first ge_batch_set_seats
+    std::vector<uint16_t> seats_host; // ... and its host mirror (empty without a plane)
     uint32_t last_step_turns = 0;     // turns of the most recent ge_batch_step (what the trace holds)
     size_t state_bytes = 0;
     bool stream_loads = false;  // a single-game batch's large single-turn launches load the record with streaming loads (create_impl)
@@ -601,10 +603,13 @@ static int timing_begin(ge_batch *b, hipStream_t st, hipEvent_t *e1) {
     return GE_OK;
 }
 
+static int seat_step_impl(ge_batch *b, uint32_t n_turns, hipStream_t st);   // ge_seats.inl
+
 static int step_impl(ge_batch *b, uint32_t n_turns, void *hip_stream) {
     if (b->turn + n_turns > 0xFFFFFFFFull) return GE_ERR_RANGE;
     if ((b->flags & GE_FLAG_TRACE) && n_turns > b->max_fuse) return GE_ERR_RANGE;   // the trace holds one launch
     GE_ON_DEVICE(b);
+    if (b->seats) return seat_step_impl(b, n_turns, static_cast<hipStream_t>(hip_stream));   // rooms with seats of their own: plain launches of ge_seat_step_kernel, no prepared deals, no graph
     if (n_turns % b->max_fuse == 1u || b->max_fuse == 1u) {   // a single-turn launch is due: its Werewolf x 12 segments take deals from the side plane
         int ds = ensure_deal_side(b);
         if (ds != GE_OK) return ds;
@@ -1032,6 +1037,7 @@ void ge_batch_destroy(ge_batch *b) {
         if (b->state) (void)hipFree(b->state);
         if (b->trace) (void)hipFree(b->trace);
         if (b->deal_side) (void)hipFree(b->deal_side);
+        if (b->seats) (void)hipFree(b->seats);
         if (b->tables) (void)hipFree(b->tables);
         if (b->segs_dev) (void)hipFree(b->segs_dev);
         if (b->sum_dev) (void)hipFree(b->sum_dev);
@@ -1050,3 +1056,4 @@ void ge_batch_destroy(ge_batch *b) {
 #include "ge_run_playout.inl"   // behind ge_run.inl: the same with playout seats (ge_batch_run_rooms_playout)
 #include "ge_timeline.inl"      // behind ge_run_playout.inl: a run-on with a forecast of every turn (ge_batch_run_rooms_forecast)
 #include "ge_find.inl"          // behind ge_timeline.inl: the rooms of a range that need attention (ge_batch_find_rooms)
+#include "ge_seats.inl"         // behind ge_find.inl: each room's own host-driven seats (ge_batch_set_seats) and the whole-batch step under them

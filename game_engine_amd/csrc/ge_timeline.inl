@@ -105,6 +105,7 @@ static int run_forecast_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
         a.turns = reinterpret_cast<const uint32_t *>(dev + o_turns) + lo;
         a.trace = reinterpret_cast<u32x4 *>(dev + o_trace);
         a.out = reinterpret_cast<u32x2 *>(dev + o_out) + lo;
+        a.seats = b->seats;
         a.n = cnt; a.seg = g; a.seed_key = seed_b;
         a.restart = (b->flags & GE_FLAG_RESTART) ? 1u : 0u;
         a.max_turns = max_turns; a.until = until; a.n_all = (uint32_t)n; a.first = lo;

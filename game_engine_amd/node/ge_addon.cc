@@ -622,6 +622,69 @@ napi_value FindRooms(napi_env env, napi_callback_info info) {
     return out;
 }
 
+// setSeats(batch, rooms: BigUint64Array, masks: Uint32Array): undefined - masks[k] becomes the seat mask of room rooms[k]
+// (ge_batch_set_seats, POLICY.md §3l).  Synchronous; GE_BUSY from batch_arg.
+napi_value SetSeats(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
+    if (!b || argc < 3) return throw_status(env, GE_ERR_ARG, "setSeats");
+    napi_typedarray_type tt[2];
+    size_t len[2];
+    void *data[2];
+    for (int k = 0; k < 2; k++) {
+        napi_value ab;
+        size_t off;
+        if (napi_get_typedarray_info(env, argv[1 + k], &tt[k], &len[k], &data[k], &ab, &off) != napi_ok)
+            return throw_status(env, GE_ERR_ARG, "setSeats", "typed arrays expected");
+    }
+    if (tt[0] != napi_biguint64_array || tt[1] != napi_uint32_array || len[0] != len[1])
+        return throw_status(env, GE_ERR_ARG, "setSeats", "BigUint64Array, Uint32Array of equal length");
+    const int st = ge_batch_set_seats(b, len[0], static_cast<const uint64_t *>(data[0]), static_cast<const uint32_t *>(data[1]));
+    if (st != GE_OK) return throw_status(env, st, "setSeats");
+    napi_value undef;
+    NAPI_OK(napi_get_undefined(env, &undef));
+    return undef;
+}
+
+// seats(batch, first, count): Uint32Array - the seat masks of rooms first .. first + count - 1 (ge_batch_get_seats).  Synchronous;
+// GE_BUSY from batch_arg.
+napi_value Seats(napi_env env, napi_callback_info info) {
+    size_t argc = 3;
+    napi_value argv[3];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
+    if (!b || argc < 3) return throw_status(env, GE_ERR_ARG, "seats");
+    int64_t first = 0, count = 0;
+    if (napi_get_value_int64(env, argv[1], &first) != napi_ok || napi_get_value_int64(env, argv[2], &count) != napi_ok || first < 0 || count < 0)
+        return throw_status(env, GE_ERR_ARG, "seats", "first, count (non-negative numbers) expected");
+    uint64_t n_total = 0;
+    (void)ge_batch_n_rooms(b, &n_total);
+    if ((uint64_t)first + (uint64_t)count > n_total) return throw_status(env, GE_ERR_RANGE, "seats");   // no buffer for a range the library refuses
+    void *dst = nullptr;
+    napi_value buf, arr;
+    NAPI_OK(napi_create_arraybuffer(env, (size_t)count * sizeof(uint32_t), &dst, &buf));
+    const int st = ge_batch_get_seats(b, (uint64_t)first, (uint64_t)count, count ? static_cast<uint32_t *>(dst) : nullptr);
+    if (st != GE_OK) return throw_status(env, st, "seats");
+    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, (size_t)count, buf, 0, &arr));
+    return arr;
+}
+
+// clearSeats(batch): undefined - every room back to its segment's human_mask (ge_batch_clear_seats).  Synchronous; GE_BUSY from batch_arg.
+napi_value ClearSeats(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
+    if (!b) return throw_status(env, GE_ERR_ARG, "clearSeats");
+    const int st = ge_batch_clear_seats(b);
+    if (st != GE_OK) return throw_status(env, st, "clearSeats");
+    napi_value undef;
+    NAPI_OK(napi_get_undefined(env, &undef));
+    return undef;
+}
+
 // runRoomsPlayout(batch, rooms: BigUint64Array, keys: BigUint64Array, turns: Uint32Array, masks: Uint32Array, playoutKeys:
 // BigUint64Array, nRollouts, playoutMaxTurns, seed: BigInt, flags, maxTurns, until: GE_RUN_UNTIL_* bits, views: boolean): runRooms's
 // result plus decided: Uint32Array of rooms.length x maxTurns - runRooms with playout seats (ge_batch_run_rooms_playout, POLICY.md
@@ -1150,6 +1213,9 @@ napi_value Init(napi_env env, napi_value exports) {
         {"runRoomsPlayout", nullptr, RunRoomsPlayout, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"runRoomsForecast", nullptr, RunRoomsForecast, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"findRooms", nullptr, FindRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"setSeats", nullptr, SetSeats, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"seats", nullptr, Seats, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"clearSeats", nullptr, ClearSeats, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"readRoomsAt", nullptr, ReadRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"rollout", nullptr, Rollout, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"writeRoomsAt", nullptr, WriteRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -92,6 +92,15 @@ export class RoomBatch {
    *  first min(matched, cap) matches in ascending room order; cap 0 counts only.  Synchronous; GE_BUSY while an async step() is in flight. */
   findRooms(options?: { want?: FindWant[] | FindWant | number; phases?: number[] | Record<number, number[]> | null; first?: number;
                         count?: number; cap?: number }): { hits: RoomHit[]; matched: number };
+  /** Per-room host-driven seats (POLICY.md §3l): masks[k] (bit i = seat i + 1 is host-driven) becomes the seat mask of room rooms[k];
+   *  step, stepRooms, the run-ons, findRooms and the playout-seat check then honour the room's own mask.  All-or-nothing.
+   *  Synchronous; GE_BUSY while an async step() is in flight. */
+  setSeats(rooms: ArrayLike<number | bigint>, masks: ArrayLike<number>): void;
+  /** The seat masks of rooms first .. first + count - 1 (the segment's mask where none was ever set).  Synchronous; GE_BUSY while an
+   *  async step() is in flight. */
+  seats(first?: number, count?: number): Uint32Array;
+  /** Every room back to its segment's mask.  Synchronous; GE_BUSY while an async step() is in flight. */
+  clearSeats(): void;
   /** runRooms with playout seats (POLICY.md §3g): stepRoomsPlayout's entries (rooms[k], keys[k], turns[k] + t, masks[k], playoutKeys[k])
    *  turn after turn, stopped as runRooms stops them, without a host wait between the turns.  decided[k][t]: turn t's decided mask.
    *  Synchronous; GE_BUSY while an async step() is in flight. */

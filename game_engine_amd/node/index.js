@@ -677,6 +677,25 @@ class RoomBatch {
     }
     return { hits, matched: r.matched };
   }
+  /** Per-room host-driven seats (twin of the Python RoomBatch.set_seats, POLICY.md §3l): masks[k] (bit i = seat i + 1 is host-driven)
+   * becomes the seat mask of room rooms[k] (local indices, pairwise distinct).  From then on step, stepRooms, the run-ons, findRooms
+   * and the playout-seat check honour the room's own mask instead of its segment's.  All-or-nothing: a room outside the batch, a
+   * repeated room or a mask bit at or above the room's player count throws and changes nothing.  The mask is configuration: reset,
+   * record writes and restarts leave it; a change takes effect with the next turn played.  Synchronous; GE_BUSY while an async
+   * step() is in flight. */
+  setSeats(rooms, masks) {
+    if (rooms.length !== masks.length) throw new RangeError('setSeats: rooms and masks differ in length');
+    addon.setSeats(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r)), Uint32Array.from(masks));
+  }
+  /** The seat masks of rooms first .. first + count - 1 as a Uint32Array (the segment's mask where none was ever set); count
+   * undefined: to the end of the batch.  Synchronous; GE_BUSY while an async step() is in flight. */
+  seats(first = 0, count) {
+    return addon.seats(this.handle, first, count === undefined ? this.nRooms - first : count);
+  }
+  /** Every room back to its segment's mask; the seat plane is freed.  Synchronous; GE_BUSY while an async step() is in flight. */
+  clearSeats() {
+    addon.clearSeats(this.handle);
+  }
   /** runRooms with playout seats (twin of the Python RoomBatch.run_rooms_playout, POLICY.md §3g): room k takes stepRoomsPlayout's
    * entries (rooms[k], keys[k], turns[k] + t, masks[k], playoutKeys[k]; nRollouts, playoutMaxTurns, seed, fullView), t = 0, 1, ...,
    * and stops as runRooms stops it; between the turns of the call the host does not wait for the device.  Returns { played, stopped,

@@ -10,6 +10,9 @@ export class RoomPoolService {
   /** As RoomService.adoptRoom for many threads: every state is converted before a slot is taken, then one writeRoomsAt per chunk. */
   adoptRooms(entries: AdoptOptions[]): Promise<TurnResult[]>;
   humanAction(threadId: string, playerId: number, choice: number): Promise<AgentStateView>;
+  /** A seat changes hands mid-game (POLICY.md §3l): from the next turn on exactly `seats` (player ids) are played by people.  Rejects
+   *  for an unknown thread or a seat outside 1..n, before anything changes; resolves with the seats. */
+  setHumanSeats(threadId: string, seats: number[]): Promise<number[]>;
   continueRoom(threadId: string, items?: { id: string; type: string }[]): Promise<TurnResult>;
   /** As RoomService.runRoom, from the thread's pool slot. */
   runRoom(threadId: string, maxTurns?: number, until?: RunUntil[], items?: { id: string; type: string }[], options?: RunOptions): Promise<RunResult>;

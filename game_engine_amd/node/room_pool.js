@@ -11,7 +11,7 @@
  */
 const { GameTable, RoomBatch, RoomLog, decodeRoom, turnToolCalls, uiToolCalls } = require('./index.js');
 const { roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, adviseCandidates, adviseSeat, runRollouts, adviseOutput,
-        seatForecastOutput, beliefBytes, neutralBeliefs, checkForecastSeat, checkView, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, forecastKey, forecastSeed, checkRunArgs, checkRunThread, runTurn, runOutput,
+        seatForecastOutput, beliefBytes, neutralBeliefs, checkForecastSeat, checkView, seatsMask, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, forecastKey, forecastSeed, checkRunArgs, checkRunThread, runTurn, runOutput,
         checkRunForecast, runForecastPerCall, runForecasts } = require('./room_service.js');
 const popcount = (m) => { let c = 0; for (let x = m; x; x &= x - 1) c++; return c; };
 const M = require('./messages.js');
@@ -28,7 +28,7 @@ class RoomPoolService {
     if (!(chunkRooms >= 1)) throw new RangeError('chunkRooms must be >= 1');
     this.gamesDir = gamesDir; this.seed = BigInt(seed); this.device = device; this.chunkRooms = chunkRooms;
     this.tables = new Map();       // gameName -> GameTable
-    this.pools = new Map();        // `${gameName}/${nPlayers}/${humanMask}` -> { table, nPlayers, humanMask, chunks, free, used, templateRaw }
+    this.pools = new Map();        // `${gameName}/${nPlayers}/${humanMask}` -> { table, nPlayers, humanMask, chunks, free, used, seated, templateRaw }
     this.rooms = new Map();        // threadId -> { pool, chunk, ci, slot, key, turn, table, gameName, names, humanSeats, panel, state, log }
     this.queue = Promise.resolve();
   }
@@ -54,6 +54,10 @@ class RoomPoolService {
     const chunk = pool.chunks[ci];
     const id = `${ci}/${slot}`;
     if (template && pool.used.has(id)) chunk.writeRoomsRaw(slot, pool.templateRaw);   // a reused slot starts from the template (no prepared deal)
+    if (pool.seated.has(id)) {     // ... and with the pool's own seating (setHumanSeats changed the slot's mask)
+      chunk.setSeats([slot], [pool.humanMask]);
+      pool.seated.delete(id);
+    }
     pool.used.add(id);
     return { chunk, ci, slot };
   }
@@ -64,7 +68,7 @@ class RoomPoolService {
     const playoutMask = playoutMaskOf(players.length, humanMask, playoutSeats);
     if (this.rooms.has(threadId)) this._release(threadId);
     const pk = `${gameName}/${players.length}/${humanMask}`;
-    if (!this.pools.has(pk)) this.pools.set(pk, { table, nPlayers: players.length, humanMask, chunks: [], free: [], used: new Set(), templateRaw: null });
+    if (!this.pools.has(pk)) this.pools.set(pk, { table, nPlayers: players.length, humanMask, chunks: [], free: [], used: new Set(), seated: new Set(), templateRaw: null });
     const pool = this.pools.get(pk);
     const { chunk, ci, slot } = this._acquire(pool);
     const names = players.map((p, i) => p.name || `Player ${i + 1}`);
@@ -94,7 +98,7 @@ class RoomPoolService {
       try {
         for (const p of prep) {
           const pk = `${p.e.gameName}/${p.n}/${p.humanMask}`;
-          if (!this.pools.has(pk)) this.pools.set(pk, { table: p.table, nPlayers: p.n, humanMask: p.humanMask, chunks: [], free: [], used: new Set(), templateRaw: null });
+          if (!this.pools.has(pk)) this.pools.set(pk, { table: p.table, nPlayers: p.n, humanMask: p.humanMask, chunks: [], free: [], used: new Set(), seated: new Set(), templateRaw: null });
           const pool = this.pools.get(pk);
           taken.push(Object.assign({ pool }, this._acquire(pool, false)));
         }
@@ -135,6 +139,20 @@ class RoomPoolService {
       if (st[0] !== 0) { const e = new Error(`injectAction: status ${st[0]}`); e.code = `GE${st[0]}`; throw e; }
       room.state = room.chunk.readRoomsAt([room.slot])[0];
       return this.agentState(room);
+    });
+  }
+  /** As RoomService.setHumanSeats (POLICY.md §3l): from the next turn on exactly `seats` (player ids) of the thread are played by
+   * people.  The thread stays in its slot and its pool; the slot's seat mask goes back to the pool's when the slot is reused.
+   * Rejects for an unknown thread or a seat outside 1..n, before anything changes; resolves with the seats. */
+  setHumanSeats(threadId, seats) {
+    return this._serial(() => {
+      const room = this._room(threadId);
+      const mask = seatsMask(threadId, room.pool.nPlayers, seats);
+      room.chunk.setSeats([room.slot], [mask]);
+      room.pool.seated.add(`${room.ci}/${room.slot}`);
+      room.humanSeats = room.names.map((_, i) => i + 1).filter((i) => (mask >> (i - 1)) & 1);
+      room.playoutMask &= ~mask;
+      return room.humanSeats.slice();
     });
   }
   continueRoom(threadId, items) {

@@ -72,6 +72,9 @@ export class RoomService {
   adoptRoom(opts: AdoptOptions): TurnResult;
   /** Requests of one thread are served strictly one after the other. */
   humanAction(threadId: string, playerId: number, choice: number): Promise<AgentStateView>;
+  /** A seat changes hands mid-game (POLICY.md §3l): from the next turn on exactly `seats` (player ids) are played by people.  Rejects
+   *  for an unknown thread or a seat outside 1..n, before anything changes; resolves with the seats. */
+  setHumanSeats(threadId: string, seats: number[]): Promise<number[]>;
   /** One message of the browser, as the reference's graph reads it (page.tsx:272-275, 302-305, 341-349, 2774, 2843, 2962;
    *  POLICY.md 3b): chat plays no turn; anything else plays one, after a game message was logged under Player 1 and - where it
    *  is a valid action of a host-driven seat - applied. */

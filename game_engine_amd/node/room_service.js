@@ -163,6 +163,16 @@ function adviseCandidates(table, st) {
   const phase = table.info.phases.find((x) => x.id === st.current_phase_id);
   return phase && phase.act === 5 ? [1] : [1, 2, 3];             // 5: GE_ACT_TT_STATEMENTS
 }
+/** setHumanSeats: the seats (player ids 1..n) as the room's seat mask (POLICY.md §3l); RangeError for an id outside 1..n */
+function seatsMask(threadId, n, seats) {
+  let mask = 0;
+  for (const seat of seats || []) {
+    if (!Number.isInteger(seat) || seat < 1 || seat > n) throw new RangeError(`thread ${threadId}: seat ${seat} is not a player 1..${n}`);
+    mask |= 1 << (seat - 1);
+  }
+  return mask;
+}
+
 function adviseSeat(threadId, humanSeats, playerId) {
   if (playerId !== undefined && playerId !== null) return Number(playerId);
   if (!humanSeats.length) throw new RangeError(`thread ${threadId} has no human seat: name the player to advise`);
@@ -359,6 +369,22 @@ class RoomService {
     return adoptedOutput(room, a.turn);
   }
   agentState(room) { return room.log.agentState(room.state); }
+  /** A seat changes hands mid-game (twin of the Python RoomService.set_human_seats, POLICY.md §3l): from the next turn on exactly
+   * `seats` (player ids) are played by people, every other seat by the policy.  The thread's humanSeats (what handleMessage
+   * resolves against and advise defaults to) follow, and a seat given to a person leaves the thread's playout seats.  Rejects for an
+   * unknown thread or a seat outside 1..n, before anything changes; resolves with the seats. */
+  setHumanSeats(threadId, seats) {
+    const room = this.rooms.get(threadId);
+    if (!room) return Promise.reject(new Error(`unknown thread ${threadId}`));
+    let mask;
+    try { mask = seatsMask(threadId, room.names.length, seats); } catch (e) { return Promise.reject(e); }
+    return this._serial(room, () => {
+      room.batch.setSeats([0], [mask]);
+      room.humanSeats = room.names.map((_, i) => i + 1).filter((i) => (mask >> (i - 1)) & 1);
+      room.playoutMask &= ~mask;
+      return room.humanSeats.slice();
+    });
+  }
   /** Requests of one thread run strictly one after the other (the reference's LangGraph server queues
    * runs per thread the same way): overlapping /continue and /action calls neither race on the batch
    * handle nor see a half-updated log. */
@@ -565,6 +591,6 @@ class RoomService {
   }
 }
 
-module.exports = { RoomService, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput,
+module.exports = { RoomService, seatsMask, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput,
                    adviseCandidates, adviseSeat, runRollouts, adviseOutput, seatForecastOutput, beliefBytes, neutralBeliefs, checkForecastSeat, checkView, checkRunArgs, checkRunThread, runTurn, runOutput,
                    checkRunForecast, runForecastPerCall, runForecasts };

@@ -20,7 +20,7 @@ from . import messages as M
 from .room_service import (PLAYOUT_CAP, RolloutRequest, adopted_output, advise_candidates, advise_output, advise_seat, belief_bytes,
                            check_forecast_args, check_forecast_seat, check_playout_options, check_run_args, check_run_forecast, check_run_thread, check_view,
                            forecast_key, forecast_seed, playout_mask, playout_max_cands, prepare_adoption, room_index_of, neutral_beliefs, run_forecast_per_call,
-                           run_forecasts, run_output, run_rollouts, run_turn, seat_forecast_output)
+                           run_forecasts, run_output, run_rollouts, run_turn, seat_forecast_output, seats_mask)
 from .stepper import GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, load_dsl_by_gamename, pending_seats, slot_values
 from .toolcalls import WW_IS_ALIVE, RoomLog, turn_tool_calls
 from .ui_script import ui_tool_calls
@@ -34,6 +34,7 @@ class _Pool:
         self.chunks: List[Any] = []
         self.free: List[Tuple[int, int]] = []      # (chunk, slot), popped from the end
         self.used: set = set()                     # slots a thread has held: written back to the template when reused
+        self.seated: set = set()                   # slots whose seat mask set_human_seats changed: set back to human_mask when reused
         self.template = None                       # the initial room view (player_states_template, phase 0)
 
 
@@ -74,6 +75,9 @@ class RoomPoolService:
         chunk = pool.chunks[ci]
         if template and (ci, slot) in pool.used:  # a reused slot starts from the template (which also drops any prepared deal)
             chunk.write_rooms(slot, np.array([pool.template], dtype=pool.template.dtype))
+        if (ci, slot) in pool.seated:             # ... and with the pool's own seating (set_human_seats changed the slot's mask)
+            chunk.set_seats([slot], [pool.human_mask])
+            pool.seated.discard((ci, slot))
         pool.used.add((ci, slot))
         return chunk, ci, slot
 
@@ -165,6 +169,22 @@ class RoomPoolService:
             raise GeError(int(st[0]), "ge_batch_inject_actions")
         room["view"] = room["chunk"].read_rooms_at([room["slot"]])[0]
         return self._agent_state(room)
+
+    def set_human_seats(self, thread_id: str, seats) -> List[int]:
+        """As RoomService.set_human_seats: from the next turn on exactly `seats` (player ids) of the thread are played by people
+        (POLICY.md §3l).  The thread stays in its slot and its pool (pools stay keyed by the seating threads are created with); the
+        slot's seat mask goes back to the pool's when the slot is reused.  ValueError for an unknown thread or a seat outside
+        1..n, before anything changes."""
+        room = self._rooms.get(thread_id)
+        if room is None:
+            raise ValueError(f"unknown thread {thread_id!r}")
+        pool = room["pool"]
+        mask = seats_mask(thread_id, pool.n_players, seats)
+        room["chunk"].set_seats([room["slot"]], [mask])
+        pool.seated.add((room["ci"], room["slot"]))
+        room["human_seats"] = [i + 1 for i in range(pool.n_players) if (mask >> i) & 1]
+        room["playout_mask"] &= ~mask
+        return list(room["human_seats"])
 
     def continue_room(self, thread_id: str, items: Optional[List[Dict[str, Any]]] = None) -> Dict[str, Any]:
         """One turn of one thread: {"state", "toolCalls", "uiCalls"}, as RoomService.continue_room."""

@@ -106,6 +106,16 @@ def playout_mask(n_players: int, human_mask: int, playout_seats) -> int:
     return mask
 
 
+def seats_mask(thread_id: str, n_players: int, seats) -> int:
+    """set_human_seats: the seats (player ids 1..n) as the room's seat mask (POLICY.md §3l); ValueError for an id outside 1..n."""
+    mask = 0
+    for seat in seats or ():
+        if isinstance(seat, bool) or int(seat) != seat or not 1 <= int(seat) <= n_players:
+            raise ValueError(f"thread {thread_id!r}: seat {seat!r} is not a player 1..{n_players}")
+        mask |= 1 << (int(seat) - 1)
+    return mask
+
+
 def check_playout_options(n_rollouts: int, max_turns: int, view: str, halving: bool = False) -> bool:
     """The services' playout-bot options; returns True for the full view."""
     check_forecast_args(n_rollouts, max_turns)
@@ -479,6 +489,20 @@ class RoomService:
         room["batch"].inject_action(0, player_id, choice)
         room["view"] = room["batch"].read_rooms(0, 1)[0]
         return self._agent_state(room)
+
+    def set_human_seats(self, thread_id: str, seats) -> List[int]:
+        """A seat changes hands mid-game (POLICY.md §3l): from the next turn on exactly `seats` (player ids) are played by people,
+        every other seat by the policy - a person who leaves, a person who takes over a bot's seat.  The thread's human_seats
+        (what handle_message resolves against and advise defaults to) follow, and a seat given to a person leaves the thread's
+        playout seats.  ValueError for an unknown thread or a seat outside 1..n, before anything changes.  Returns the seats."""
+        room = self._rooms.get(thread_id)
+        if room is None:
+            raise ValueError(f"unknown thread {thread_id!r}")
+        mask = seats_mask(thread_id, int(room["view"]["n_players"]), seats)
+        room["batch"].set_seats([0], [mask])
+        room["human_seats"] = [i + 1 for i in range(int(room["view"]["n_players"])) if (mask >> i) & 1]
+        room["playout_mask"] &= ~mask
+        return list(room["human_seats"])
 
     def continue_room(self, thread_id: str, items: Optional[List[Dict[str, Any]]] = None) -> Dict[str, Any]:
         """One turn (one graph run): {"state": AgentState, "toolCalls": [...], "uiCalls": [...]}.

@@ -501,6 +501,32 @@ class RoomBatch:
                "ge_batch_find_rooms")
         return hits[: n_hits.value], int(n_match.value)
 
+    def set_seats(self, rooms, masks):
+        """Per-room host-driven seats (POLICY.md §3l): masks[k] (bit i = seat i+1 is host-driven) becomes the seat mask of room
+        rooms[k] (local indices, pairwise distinct).  From then on every call that honours the segment's human_mask - step,
+        step_rooms, the run-ons, find_rooms, the playout-seat check - honours the room's own mask instead.  All-or-nothing: a room
+        outside the batch, a repeated room or a mask bit at or above the room's player count raises and changes nothing.  The mask
+        is configuration: reset, set_turn, record writes and restarts leave it; a change takes effect with the next turn played."""
+        rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
+        masks = np.ascontiguousarray(masks, dtype=np.uint32)
+        if len(rooms) != len(masks):
+            raise GeError(-1, "set_seats: rooms and masks differ in length")
+        _check(self._lib.ge_batch_set_seats(self._h, len(rooms), rooms.ctypes.data, masks.ctypes.data), "ge_batch_set_seats")
+
+    def seats(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The seat masks of rooms first .. first + count - 1 (uint32; the segment's human_mask where none was ever set), from the
+        library's host mirror: no device synchronisation.  count None: to the end of the batch."""
+        count = self.n_rooms - first if count is None else count
+        if min(int(first), int(count)) < 0:
+            raise GeError(GE_ERR_ARG, "seats: first / count")
+        out = np.zeros(int(count), dtype=np.uint32)
+        _check(self._lib.ge_batch_get_seats(self._h, first, count, out.ctypes.data if len(out) else None), "ge_batch_get_seats")
+        return out
+
+    def clear_seats(self):
+        """Every room back to its segment's human_mask; the seat plane is freed."""
+        _check(self._lib.ge_batch_clear_seats(self._h), "ge_batch_clear_seats")
+
     def read_rooms_at(self, rooms) -> np.ndarray:
         """Canonical views of the listed rooms, out[k] = room rooms[k] (any order, repeats allowed)."""
         rooms = np.ascontiguousarray(rooms, dtype=np.uint64)

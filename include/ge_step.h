@@ -611,6 +611,55 @@ int ge_batch_find_rooms(ge_batch *b, uint64_t first, uint64_t count, uint32_t wa
                         const uint32_t *phase_masks /* n_segments words; read only with GE_FIND_PHASE */,
                         ge_room_hit *hits, uint64_t cap, uint64_t *n_hits, uint64_t *n_match);
 
+/* Per-room host-driven seats: a seat plane beside the records (POLICY.md §3l).  Every room has a seat mask (bit i = seat i + 1 is
+ * host-driven).  Until the first ge_batch_set_seats a room's seat mask is its segment's human_mask and no memory is spent; a batch
+ * that never sets a seat behaves exactly as before.
+ *   ge_batch_set_seats    rooms[] are local indices, pairwise distinct; masks[k] becomes room rooms[k]'s seat mask.  All-or-nothing,
+ *                         every entry checked before anything changes, in this order: GE_ERR_ARG for b NULL, or rooms / masks NULL
+ *                         with n > 0; GE_ERR_RANGE for a room outside the batch; GE_ERR_ARG for a repeated room; GE_ERR_ARG for a
+ *                         mask bit at or above the n_players of the room's segment.  n == 0: GE_OK, nothing allocated.  The first
+ *                         successful call allocates the plane - 2 B per room on the device plus a host mirror, filled with the
+ *                         segments' masks; a failed allocation returns GE_ERR_NOMEM and leaves the batch without a plane, usable
+ *                         as before.  Ordered behind the previous step; synchronises.
+ *   ge_batch_get_seats    dst[i] = seat mask of room first + i (the segment's human_mask where none was ever set), served from the
+ *                         host mirror: no device synchronisation.  GE_ERR_ARG for dst NULL with count > 0, GE_ERR_RANGE for a range
+ *                         beyond the batch.
+ *   ge_batch_clear_seats  every room back to its segment's human_mask; the plane is freed (without a plane: GE_OK).  Synchronises.
+ * Once a plane exists, "the segment's human_mask" reads "the room's seat mask" in every definition above, and nothing else about
+ * those calls changes: the turn itself (the policy acts for no seat of the mask: ge_batch_step, ge_batch_step_rooms,
+ * ge_batch_step_rooms_playout and the three run-ons), the PERSON test of ge_batch_run_rooms / _playout / _forecast, GE_FIND_PERSON
+ * and `pending` of ge_batch_find_rooms, and the refusal of a playout-mask bit on a host-driven seat in ge_batch_step_rooms_playout and
+ * ge_batch_run_rooms_playout (the host mirror decides it: a seat of the segment's mask that the room has handed back to the policy
+ * is accepted).  Unchanged: the rollouts (human mask 0 by definition: the same result word for word with or without a plane),
+ * ge_batch_inject_action(s) (never consulted the mask), ge_batch_summary and its checksum, ge_batch_state, ge_room_view,
+ * ge_batch_read_rooms(_at) and ge_batch_write_rooms(_at).
+ * The mask is configuration, not game state: it survives ge_batch_reset, ge_batch_set_turn, every write of records and a
+ * GE_FLAG_RESTART recycle; a checkpoint is (records, turn, seats).  A change takes effect with the next turn played: a seat handed to
+ * the policy acts on the next turn if it is a pending target that has not acted this visit, with the ordinary draw of (room, turn,
+ * player); a seat handed to a person that has already acted this visit stays acted.  ge_group_shard lends the shard's batch, so the
+ * three calls work per shard; there is no group-level call.
+ * ge_batch_step on a batch with a plane: room r takes, for t = 0 .. n_turns - 1, exactly ge_batch_step_rooms's entry (r, global
+ * index of r, turn + t) under its seat mask.  The turn counter advances by n_turns, the same range checks apply, and under
+ * GE_FLAG_TRACE the buffer holds these turns' events as ge_batch_read_events defines them.  Records are stored without a prepared
+ * deal and the Werewolf x 12 deal side plane is neither read nor written; so with all seat masks equal to the segment's mask the
+ * records (as views), events, summary and checksum equal those of the same batch without a plane.  It keeps the stream-ordered
+ * contract of ge_batch_step, uses plain launches (one per segment and per max_fuse turns) and never a captured graph; the graphs
+ * cached for the no-plane path stay valid and are used again after ge_batch_clear_seats.  With ge_batch_set_timing on its launches
+ * count in ge_batch_kernel_time.
+ * Measured on an MI355X (tools/seats_probe.py, profiles/seats_probe.txt; wall time, medians of 20 calls).  (a) A batch without a
+ * plane, this library against the one before the change, whose indexed kernels had no plane pointer to test: ge_batch_step_rooms of
+ * 1 024 entries x 0.998, ge_batch_run_rooms of 1 024 entries x 16 turns x 0.997, ge_batch_find_rooms over 65 536 / 1 048 576
+ * Werewolf x 8 rooms x 1.017 / x 1.008 - each inside the spread of the older library against itself in the same run (5 - 18 %), so
+ * "has a plane" stays a run-time test of a kernel argument.  (b) ge_batch_step with a plane against the same batch with the equal
+ * segment mask and no plane (the flagship kernels), time per turn, single-turn launches / fused launches of 64 turns: Werewolf x 8
+ * at 65 536 rooms x 1.00 / x 1.06, at 1 048 576 rooms x 1.26 / x 3.37; Werewolf x 12 at 2 097 152 rooms x 1.44 / x 4.52; Two-Truths
+ * x 4 at 1 048 576 rooms x 0.92 / x 1.19.  The step with a plane is the lone-wavefront single-turn lane (tables read from global
+ * memory, deals on the spot), a form DESIGN.md §4 measured slower than the large-batch builds: where seating is uniform over many
+ * rooms, a batch per seating steps faster. */
+int ge_batch_set_seats(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint32_t *masks);
+int ge_batch_get_seats(ge_batch *b, uint64_t first, uint64_t count, uint32_t *dst);
+int ge_batch_clear_seats(ge_batch *b);
+
 /* GE_FLAG_TRACE: events of the most recent ge_batch_step call, dst[(room - first) * *n_turns + t].
  * cap_bytes >= count * n_turns * sizeof(ge_turn_event).  Synchronises. */
 int ge_batch_read_events(ge_batch *b, uint64_t first, uint64_t count, uint32_t *n_turns,

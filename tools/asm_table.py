@@ -42,6 +42,9 @@ def describe(mangled: str) -> dict:
     m = re.search(r"ge_find_kernelILi(\d)ELi(\d)E", mangled)
     if m:
         return {"kernel": "ge_find_kernel", "layout": KINDS[int(m.group(1))], "lowocc": False, "generic": int(m.group(2)), "single": True}
+    m = re.search(r"ge_seat_step_kernelILi(\d)ELi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_seat_step_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": False}
     m = re.search(r"ge_rollout_kernelILi(\d)ELi(\d)E(?:Li(\d)E)?", mangled)
     if m:
         return {"kernel": "ge_rollout_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True,
@@ -99,6 +102,11 @@ def label(r):
     if r["kernel"] in ("ge_find_scan", "ge_find_emit"):          # ge_batch_find_rooms: behind the test launches
         what = {"ge_find_scan": "the scan of the wavefront counts", "ge_find_emit": "the ordered store of the hits"}[r["kernel"]]
         return f"{r['kernel']} (ge_batch_find_rooms: {what})"
+    if r["kernel"] == "ge_seat_step_kernel":                     # ge_batch_step of a batch with a seat plane: one launch per segment and per max_fuse turns
+        return f"{r['layout']}, whole-batch step under per-room seats (ge_batch_step after ge_batch_set_seats)" + (", GENERIC" if r["generic"] else "")
+    if r["kernel"] in ("ge_seats_fill", "ge_seats_scatter"):     # ge_batch_set_seats
+        what = {"ge_seats_fill": "a segment's mask for its rooms", "ge_seats_scatter": "the listed rooms' masks"}[r["kernel"]]
+        return f"{r['kernel']} (ge_batch_set_seats: {what})"
     if r["kernel"] == "ge_rollout_kernel" and r.get("act") == 4:  # GE_PLAYOUT_HALVING: one launch per unit and round
         return f"{r['layout']}, playouts over a replica range (GE_PLAYOUT_HALVING)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_playout_plan_ranged":
