@@ -1057,3 +1057,4 @@ void ge_batch_destroy(ge_batch *b) {
 #include "ge_timeline.inl"      // behind ge_run_playout.inl: a run-on with a forecast of every turn (ge_batch_run_rooms_forecast)
 #include "ge_find.inl"          // behind ge_timeline.inl: the rooms of a range that need attention (ge_batch_find_rooms)
 #include "ge_seats.inl"         // behind ge_find.inl: each room's own host-driven seats (ge_batch_set_seats) and the whole-batch step under them
+#include "ge_advise.inl"        // behind ge_seats.inl: listed seats advised on the device (ge_batch_advise_seats)

@@ -622,6 +622,45 @@ napi_value FindRooms(napi_env env, napi_callback_info info) {
     return out;
 }
 
+// adviseSeats(batch, rooms: BigUint64Array, keys: BigUint64Array, turns: Uint32Array, seats: Uint32Array, nRollouts, maxTurns,
+// seed: BigInt, flags: GE_ADVISE_* bits): ArrayBuffer of n ge_advice (224 B each) - the listed seats' legal choices found, played and
+// ranked on the device (ge_batch_advise_seats, POLICY.md §3m).  Synchronous; GE_BUSY from batch_arg.
+napi_value AdviseSeats(napi_env env, napi_callback_info info) {
+    size_t argc = 9;
+    napi_value argv[9];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    ge_batch *b = argc >= 1 ? batch_arg(env, argv[0]) : nullptr;
+    if (!b || argc < 9) return throw_status(env, GE_ERR_ARG, "adviseSeats");
+    napi_typedarray_type tt[4];
+    size_t len[4];
+    void *data[4];
+    for (int k = 0; k < 4; k++) {
+        napi_value ab;
+        size_t off;
+        if (napi_get_typedarray_info(env, argv[1 + k], &tt[k], &len[k], &data[k], &ab, &off) != napi_ok)
+            return throw_status(env, GE_ERR_ARG, "adviseSeats", "typed arrays expected");
+    }
+    if (tt[0] != napi_biguint64_array || tt[1] != napi_biguint64_array || tt[2] != napi_uint32_array || tt[3] != napi_uint32_array ||
+        len[1] != len[0] || len[2] != len[0] || len[3] != len[0])
+        return throw_status(env, GE_ERR_ARG, "adviseSeats", "BigUint64Array, BigUint64Array, Uint32Array, Uint32Array of equal length");
+    uint32_t n_rollouts = 0, max_turns = 0, flags = 0;
+    uint64_t seed = 0;
+    bool lossless = true;
+    if (napi_get_value_uint32(env, argv[5], &n_rollouts) != napi_ok || napi_get_value_uint32(env, argv[6], &max_turns) != napi_ok ||
+        napi_get_value_bigint_uint64(env, argv[7], &seed, &lossless) != napi_ok || napi_get_value_uint32(env, argv[8], &flags) != napi_ok)
+        return throw_status(env, GE_ERR_ARG, "adviseSeats", "nRollouts, maxTurns (numbers), seed (BigInt), flags expected");
+    const size_t n = len[0];
+    void *dst = nullptr;
+    napi_value buf;
+    NAPI_OK(napi_create_arraybuffer(env, n * sizeof(ge_advice), &dst, &buf));
+    if (n) memset(dst, 0, n * sizeof(ge_advice));
+    const int st = ge_batch_advise_seats(b, n, static_cast<const uint64_t *>(data[0]), static_cast<const uint64_t *>(data[1]),
+                                         static_cast<const uint32_t *>(data[2]), static_cast<const uint32_t *>(data[3]), n_rollouts, max_turns, seed,
+                                         flags, static_cast<ge_advice *>(dst));
+    if (st != GE_OK) return throw_status(env, st, "adviseSeats");
+    return buf;
+}
+
 // setSeats(batch, rooms: BigUint64Array, masks: Uint32Array): undefined - masks[k] becomes the seat mask of room rooms[k]
 // (ge_batch_set_seats, POLICY.md §3l).  Synchronous; GE_BUSY from batch_arg.
 napi_value SetSeats(napi_env env, napi_callback_info info) {
@@ -1214,6 +1253,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"runRoomsForecast", nullptr, RunRoomsForecast, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"findRooms", nullptr, FindRooms, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"setSeats", nullptr, SetSeats, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"adviseSeats", nullptr, AdviseSeats, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"seats", nullptr, Seats, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"clearSeats", nullptr, ClearSeats, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"readRoomsAt", nullptr, ReadRoomsAt, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -40,6 +40,10 @@ export function findWantBits(want: FindWant[] | FindWant | number): number;
 export function findWantNames(bits: number): FindWant[];
 /** A room findRooms matched: why = the conditions of `want` that hold, pending = the host-driven seats that could act now. */
 export interface RoomHit { room: number; why: FindWant[]; pending: number[]; phaseId: number; segment: number; }
+/** What adviseSeats says of one choice (or of the policy playing the seat): finished playouts, those the seat's side won, the seat's summed score. */
+export interface AdviceOption { finished: number; wins: number; score: number; }
+/** adviseSeats's answer for one (room, seat): status 0, or -1 when no choice of the seat would be accepted now (then no options). */
+export interface SeatAdvice { status: number; legal: number[]; best: number; phaseId: number; policy: AdviceOption; options: (AdviceOption & { choice: number })[]; }
 export interface ToolCall { name: 'update_player_actions' | 'set_next_phase' | 'update_player_state' | 'add_game_note'; args: Record<string, unknown>; }
 export interface PhaseInfo { id: number; name: string; completion: number; act: number; effect: number; nBranches: number; }
 
@@ -92,6 +96,12 @@ export class RoomBatch {
    *  first min(matched, cap) matches in ascending room order; cap 0 counts only.  Synchronous; GE_BUSY while an async step() is in flight. */
   findRooms(options?: { want?: FindWant[] | FindWant | number; phases?: number[] | Record<number, number[]> | null; first?: number;
                         count?: number; cap?: number }): { hits: RoomHit[]; matched: number };
+  /** Advice for listed seats on the device (POLICY.md §3m): per (rooms[k], seats[k]) the choices injectAction would accept now, each
+   *  played as rolloutSeats's entry (keys[k], turns[k], the seat's view or the full view, that one action), and the best of them.
+   *  Throws only for a structural error; a seat that cannot act now answers with status -1.  The batch is only read.  Synchronous;
+   *  GE_BUSY while an async step() is in flight. */
+  adviseSeats(rooms: ArrayLike<number | bigint>, keys: ArrayLike<number | bigint>, turns: ArrayLike<number>, seats: ArrayLike<number>,
+              nRollouts: number, maxTurns?: number, seed?: number | bigint, fullView?: boolean): SeatAdvice[];
   /** Per-room host-driven seats (POLICY.md §3l): masks[k] (bit i = seat i + 1 is host-driven) becomes the seat mask of room rooms[k];
    *  step, stepRooms, the run-ons, findRooms and the playout-seat check then honour the room's own mask.  All-or-nothing.
    *  Synchronous; GE_BUSY while an async step() is in flight. */

@@ -518,6 +518,22 @@ function runUntilNames(bits) { return Object.keys(RUN_UNTIL).filter((name) => bi
 
 // include/ge_step.h GE_FIND_*
 const FIND_WANT = { person: 1, end: 2, phase: 4 };
+const ADVICE_SIZE = 224;                                     // sizeof(ge_advice): 16 B header, policy, option[12] (16 B each)
+/** n ge_advice records as adviseSeats returns them. */
+function decodeAdvice(buf) {
+  const dv = new DataView(buf), out = [];
+  const option = (at) => ({ finished: dv.getUint32(at, true), wins: dv.getUint32(at + 4, true), score: Number(dv.getBigUint64(at + 8, true)) });
+  for (let k = 0; k * ADVICE_SIZE < buf.byteLength; k++) {
+    const at = k * ADVICE_SIZE, bits = dv.getUint32(at + 4, true), legal = [], options = [];
+    for (let c = 1; c <= 12; c++) {
+      if (!((bits >>> (c - 1)) & 1)) continue;
+      legal.push(c);
+      options.push({ choice: c, ...option(at + 32 + 16 * (c - 1)) });
+    }
+    out.push({ status: dv.getInt32(at, true), legal, best: dv.getUint32(at + 8, true), phaseId: dv.getUint32(at + 12, true), policy: option(at + 16), options });
+  }
+  return out;
+}
 /** `want` of findRooms as the ABI's bit set: an array of "person" / "end" / "phase", one of them, or the bits. */
 function findWantBits(want) { return namedBits(want, FIND_WANT, 'want: unknown condition'); }
 function findWantNames(bits) { return Object.keys(FIND_WANT).filter((name) => bits & FIND_WANT[name]); }
@@ -676,6 +692,22 @@ class RoomBatch {
                   phaseId: dv.getUint8(16 * k + 14), segment: dv.getUint8(16 * k + 15) });
     }
     return { hits, matched: r.matched };
+  }
+  /** Advice for listed seats, found, played and ranked on the device (twin of the Python RoomBatch.advise_seats, POLICY.md §3m).
+   * Entry k is seat seats[k] (1-based, any seat: no human mask is consulted) of room rooms[k].  Returns one object per entry:
+   * { status, legal: [choices injectAction would accept now], best, phaseId, policy: { finished, wins, score }, options: [{ choice,
+   * finished, wins, score }] } - an option's three numbers are summary.finished, seat_wins[seat-1] and seat_score[seat-1] of
+   * rolloutSeats's entry (rooms[k], keys[k], turns[k], the seat or 0 with fullView, [[seat, choice]]; nRollouts, maxTurns, seed),
+   * policy the same of that entry without actions, best the legal choice with the most wins (Werewolf) or the highest score
+   * (Two-Truths), the lowest on a tie.  A seat that could not act now has status -1 (GE_ERR_ARG), no options and zeros: an answer,
+   * not an error.  Throws only for a structural error, before anything runs.  The batch is only read.  Synchronous; GE_BUSY while
+   * an async step() is in flight. */
+  adviseSeats(rooms, keys, turns, seats, nRollouts, maxTurns = 1024, seed, fullView = false) {
+    if (rooms.length !== keys.length || rooms.length !== turns.length || rooms.length !== seats.length) throw new RangeError('adviseSeats: arrays differ in length');
+    const buf = addon.adviseSeats(this.handle, BigUint64Array.from(rooms, (r) => BigInt(r)), BigUint64Array.from(keys, (k) => BigInt.asUintN(64, BigInt(k))),
+                                  Uint32Array.from(turns), Uint32Array.from(seats), nRollouts, maxTurns,
+                                  seed === undefined ? this.seed : BigInt.asUintN(64, BigInt(seed)), fullView ? 1 : 0);
+    return decodeAdvice(buf);
   }
   /** Per-room host-driven seats (twin of the Python RoomBatch.set_seats, POLICY.md §3l): masks[k] (bit i = seat i + 1 is host-driven)
    * becomes the seat mask of room rooms[k] (local indices, pairwise distinct).  From then on step, stepRooms, the run-ons, findRooms
@@ -977,5 +1009,5 @@ class DeviceGroup {
 
 const { compileCriteria, audienceGroups, uiToolCalls } = require('./ui_script.js');
 
-module.exports = { GameTable, RoomBatch, runUntilBits, runUntilNames, findWantBits, findWantNames, decodeRoom, agentStateToView, ShardedBatch, DeviceGroup, locateInShards, RoomLog, formatNote, loadDslByGamename, findGameFile, initializePlayers, turnToolCalls, compileCriteria, audienceGroups, uiToolCalls,
+module.exports = { GameTable, RoomBatch, decodeAdvice, runUntilBits, runUntilNames, findWantBits, findWantNames, decodeRoom, agentStateToView, ShardedBatch, DeviceGroup, locateInShards, RoomLog, formatNote, loadDslByGamename, findGameFile, initializePlayers, turnToolCalls, compileCriteria, audienceGroups, uiToolCalls,
                    deviceCount: addon.deviceCount, addon };

@@ -1,5 +1,5 @@
 // Types for room_pool.js — many game threads hosted in a few resident batches.
-import { AdoptOptions, Advice, AgentStateView, Forecast, PlayoutOptions, RoomPlayer, RunOptions, RunResult, RunUntil, TurnResult } from './room_service';
+import { AdoptOptions, Advice, AgentStateView, Forecast, Hint, PlayoutOptions, RoomPlayer, RunOptions, RunResult, RunUntil, TurnResult } from './room_service';
 
 export type MessageResult = TurnResult & { played: boolean; kind: 'chat' | 'control' | 'action' };
 export class RoomPoolService {
@@ -39,6 +39,10 @@ export class RoomPoolService {
    *  (with compare one rolloutCompare, and every option gains "versus"). */
   advises(threadIds: string[], playerIds?: (number | undefined)[], nRollouts?: number, maxTurns?: number,
           view?: 'full' | 'seat', compare?: boolean, beliefs?: (Record<number, number> | undefined)[]): Promise<Advice[]>;
+  /** Hints for many (thread, seat) pairs: one adviseSeats per chunk touched.  Without threadIds: every thread waiting() reports, each
+   *  of its pending seats; with them, playerIds[j] (absent: thread j's lowest human seat). */
+  hints(threadIds?: string[] | null, playerIds?: (number | undefined)[] | null, nRollouts?: number, maxTurns?: number,
+        view?: 'full' | 'seat'): Promise<Hint[]>;
   /** Forget a thread (its slot is reused); without an id, every thread and every chunk's device memory. */
   close(threadId?: string): Promise<boolean>;
 }

@@ -10,7 +10,7 @@
  * stepRooms and one readRoomsAt.  The chunks are shared, so every call of the service runs strictly one after the other.
  */
 const { GameTable, RoomBatch, RoomLog, decodeRoom, turnToolCalls, uiToolCalls } = require('./index.js');
-const { roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, adviseCandidates, adviseSeat, runRollouts, adviseOutput,
+const { roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, adviseCandidates, adviseSeat, runRollouts, adviseOutput, runHints, hintOutput,
         seatForecastOutput, beliefBytes, neutralBeliefs, checkForecastSeat, checkView, seatsMask, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, forecastKey, forecastSeed, checkRunArgs, checkRunThread, runTurn, runOutput,
         checkRunForecast, runForecastPerCall, runForecasts } = require('./room_service.js');
 const popcount = (m) => { let c = 0; for (let x = m; x; x &= x - 1) c++; return c; };
@@ -303,6 +303,31 @@ class RoomPoolService {
                               seatView, nRollouts, maxTurns, this.seed, !!compare);
       return rooms.map((room, j) => adviseOutput(room.table, room.names, threadIds[j], room.turn, seats[j], room.state, cands[j], nRollouts, maxTurns,
                                                  res[j], 0, seatView, bel[j]));
+    });
+  }
+  /** Hints for many (thread, seat) pairs, each as RoomService.hint's (twin of the Python RoomPoolService.hints): one adviseSeats
+   * call per chunk touched (POLICY.md §3m).  threadIds undefined / null: every thread waiting() reports, in the order the threads
+   * were created, and each of its pending seats ascending.  With threadIds: playerIds[j] (undefined / null or no playerIds: thread
+   * j's lowest human seat).  No thread changes. */
+  hints(threadIds, playerIds, nRollouts = 4096, maxTurns = 1024, view = 'seat') {
+    checkForecastArgs(nRollouts, maxTurns);
+    const seatView = checkView(view);
+    return this._serial(() => {
+      let pairs;
+      if (threadIds === undefined || threadIds === null) {
+        if (playerIds !== undefined && playerIds !== null) throw new RangeError('hints: playerIds need threadIds');
+        const wait = new Map(this._scan(['person']).map(([t, h]) => [t, h.pending]));
+        pairs = [];
+        for (const t of this.rooms.keys()) for (const seat of wait.get(t) || []) pairs.push([t, seat]);
+      } else {
+        const pids = playerIds || [];
+        pairs = threadIds.map((t, j) => [t, adviseSeat(t, this._room(t).humanSeats, pids[j])]);
+      }
+      const rooms = pairs.map(([t]) => this._room(t));
+      const advs = runHints(rooms.map((room, j) => ({ batch: room.chunk, slot: room.slot, key: room.key, turn: room.turn, seat: pairs[j][1],
+                                                      cost: playoutMaxCands(room.table.info.pack, room.names.length) + 1 })),
+                            seatView, nRollouts, maxTurns, this.seed);
+      return rooms.map((room, j) => hintOutput(room.table, room.names, pairs[j][0], room.turn, pairs[j][1], room.state, nRollouts, maxTurns, advs[j], seatView));
     });
   }
   /** Forecasts of many threads, in order: one rolloutRooms per chunk touched; with seats (seats[j] 1 .. n: thread j from that

@@ -63,6 +63,17 @@ export interface Advice {
   /** true when the options carry "versus" */
   compare?: true;
 }
+/** advise in a few numbers per choice, ranked on the device (INTEGRATION.md "Hints for everyone who waits"). */
+export interface Hint {
+  threadId: string; turn: number; playerId: number; phaseId: number; rollouts: number; maxTurns: number;
+  /** the choice with the most wins (Two-Truths: the highest score), the lowest on a tie; null when the seat has nothing to do now */
+  best: number | null;
+  /** the policy plays the seat; null when the seat has nothing to do now */
+  policy: { finished: number; wins: number; score: number } | null;
+  /** the choices the seat can make now, ascending: the advised seat's own wins / topScore, scoreSum and the finished playouts of advise's option forecast */
+  options: { choice: number; label: string; wins: number; score: number; finished: number }[];
+  view?: 'seat';
+}
 export class RoomService {
   constructor(opts?: { gamesDir?: string; seed?: bigint | number; device?: number } & PlayoutOptions);
   createRoom(opts: { threadId: string; gameName: string; players: RoomPlayer[]; dsl?: object; /** global room index the RNG is keyed by (default: hash of the thread id) */ roomIndex?: number | bigint;
@@ -96,6 +107,9 @@ export class RoomService {
    *  beliefs (view "seat" only): as forecast's; the JSON gains "beliefs", the 16 bytes used. */
   advise(threadId: string, playerId?: number, nRollouts?: number, maxTurns?: number, view?: 'full' | 'seat', compare?: boolean,
          beliefs?: Record<number, number>): Promise<Advice>;
+  /** advise's numbers for playerId (default: the lowest human seat) without the per-option forecasts: the legal choices found, played
+   *  and ranked on the device (RoomBatch.adviseSeats) under advise's keys and seed.  view defaults to "seat".  The thread is not changed. */
+  hint(threadId: string, playerId?: number, nRollouts?: number, maxTurns?: number, view?: 'full' | 'seat'): Promise<Hint>;
   /** Forget a thread and free its device memory; resolves false for an unknown thread. */
   close(threadId: string): Promise<boolean>;
   serve(port?: number): Promise<import('http').Server>;

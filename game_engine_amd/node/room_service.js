@@ -257,6 +257,46 @@ function adviseOutput(table, names, threadId, turn, seat, st, cands, nRollouts, 
   return out;
 }
 
+const ADVISE_CAP = 2 ** 26;                         // ge_batch_advise_seats: sum of (maxCands + 1) x nRollouts per call
+/** The advice records of a hint call, one per request (twin of room_service.py run_hints): reqs [{ batch, slot, key, turn, seat, cost }]
+ * - cost: the entries the library reserves for it (playoutMaxCands + 1).  RoomBatch.adviseSeats (POLICY.md §3m) under the thread's
+ * forecast key and the forecast seed - advise's keys and seed.  One call per batch, in the order the batches first appear, split
+ * only where the library's cap on reserved playouts needs it. */
+function runHints(reqs, seatView, nRollouts, maxTurns, seed) {
+  const byBatch = new Map();
+  reqs.forEach((r, j) => {
+    if (!byBatch.has(r.batch)) byBatch.set(r.batch, []);
+    byBatch.get(r.batch).push(j);
+  });
+  const parts = [];
+  for (const js of byBatch.values()) {
+    let cost = 0;
+    parts.push([]);
+    for (const j of js) {
+      if (parts[parts.length - 1].length && (cost + reqs[j].cost) * nRollouts > ADVISE_CAP) { parts.push([]); cost = 0; }
+      parts[parts.length - 1].push(j);
+      cost += reqs[j].cost;
+    }
+  }
+  const out = new Array(reqs.length);
+  for (const part of parts) {
+    const adv = reqs[part[0]].batch.adviseSeats(part.map((j) => reqs[j].slot), part.map((j) => forecastKey(reqs[j].key)), part.map((j) => reqs[j].turn),
+                                                part.map((j) => reqs[j].seat), nRollouts, maxTurns, forecastSeed(seed), !seatView);
+    part.forEach((j, k) => { out[j] = adv[k]; });
+  }
+  return out;
+}
+/** hint's JSON from one advice record of RoomBatch.adviseSeats: the bytes the Python hosts print. */
+function hintOutput(table, names, threadId, turn, seat, st, nRollouts, maxTurns, adv, seatView = true) {
+  const ok = adv.status === 0;
+  const options = ok ? adv.options.map((o) => ({ choice: o.choice, label: st.pack === 1 ? names[o.choice - 1] : String(o.choice), wins: o.wins,
+                                                 score: o.score, finished: o.finished })) : [];
+  const out = { threadId, turn: Number(turn), playerId: seat, phaseId: st.current_phase_id, rollouts: nRollouts, maxTurns, best: ok ? adv.best : null,
+                policy: ok ? { finished: adv.policy.finished, wins: adv.policy.wins, score: adv.policy.score } : null, options };
+  if (seatView) out.view = 'seat';
+  return out;
+}
+
 const RUN_MAX_TURNS = 4096;                         // ge_batch_run_rooms's cap on maxTurns
 /** runRoom's maxTurns and until, before anything runs; returns `until` as ge_batch_run_rooms's bit set. */
 function checkRunArgs(maxTurns, until) {
@@ -439,6 +479,24 @@ class RoomService {
       return adviseOutput(room.table, room.names, threadId, room.turn, seat, room.state, cands, nRollouts, maxTurns, res, 0, seatView, bel);
     });
   }
+  /** advise in 224 bytes (twin of the Python RoomService.hint): which choices the seat can make now, what each leads to for that
+   * seat, and the best of them - found, played and ranked on the device (RoomBatch.adviseSeats, POLICY.md §3m) under advise's keys
+   * and seed, so every number is the advised seat's own inside advise's option forecasts.  playerId defaults to the lowest human
+   * seat.  Resolves with { threadId, turn, playerId, phaseId, rollouts, maxTurns, best, policy: { finished, wins, score }, options:
+   * [{ choice, label, wins, score, finished }], view: "seat" } (no `view` key for view "full"); best and policy are null and options
+   * [] when the seat has nothing to do now.  The thread is not changed. */
+  hint(threadId, playerId, nRollouts = 4096, maxTurns = 1024, view = 'seat') {
+    checkForecastArgs(nRollouts, maxTurns);
+    const seatView = checkView(view);
+    const room = this.rooms.get(threadId);
+    if (!room) return Promise.reject(new Error(`unknown thread ${threadId}`));
+    const seat = adviseSeat(threadId, room.humanSeats, playerId);
+    return this._serial(room, () => {
+      const cost = playoutMaxCands(room.table.info.pack, room.names.length) + 1;
+      const [adv] = runHints([{ batch: room.batch, slot: 0, key: room.key, turn: room.turn, seat, cost }], seatView, nRollouts, maxTurns, this.seed);
+      return hintOutput(room.table, room.names, threadId, room.turn, seat, room.state, nRollouts, maxTurns, adv, seatView);
+    });
+  }
   /** Forget a thread and free its device memory (after queued requests have finished). */
   close(threadId) {
     const room = this.rooms.get(threadId);
@@ -592,5 +650,5 @@ class RoomService {
 }
 
 module.exports = { RoomService, seatsMask, playoutMaskOf, checkPlayoutOptions, PLAYOUT_CAP, playoutMaxCands, roomIndexOf, prepareAdoption, adoptedOutput, checkForecastArgs, forecastKey, forecastSeed, forecastOutput,
-                   adviseCandidates, adviseSeat, runRollouts, adviseOutput, seatForecastOutput, beliefBytes, neutralBeliefs, checkForecastSeat, checkView, checkRunArgs, checkRunThread, runTurn, runOutput,
+                   adviseCandidates, adviseSeat, runRollouts, adviseOutput, runHints, hintOutput, seatForecastOutput, beliefBytes, neutralBeliefs, checkForecastSeat, checkView, checkRunArgs, checkRunThread, runTurn, runOutput,
                    checkRunForecast, runForecastPerCall, runForecasts };

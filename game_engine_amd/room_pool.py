@@ -17,10 +17,10 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import messages as M
-from .room_service import (PLAYOUT_CAP, RolloutRequest, adopted_output, advise_candidates, advise_output, advise_seat, belief_bytes,
+from .room_service import (PLAYOUT_CAP, HintRequest, RolloutRequest, adopted_output, advise_candidates, advise_output, advise_seat, belief_bytes,
                            check_forecast_args, check_forecast_seat, check_playout_options, check_run_args, check_run_forecast, check_run_thread, check_view,
-                           forecast_key, forecast_seed, playout_mask, playout_max_cands, prepare_adoption, room_index_of, neutral_beliefs, run_forecast_per_call,
-                           run_forecasts, run_output, run_rollouts, run_turn, seat_forecast_output, seats_mask)
+                           forecast_key, forecast_seed, hint_output, playout_mask, playout_max_cands, prepare_adoption, room_index_of, neutral_beliefs, run_forecast_per_call,
+                           run_forecasts, run_hints, run_output, run_rollouts, run_turn, seat_forecast_output, seats_mask)
 from .stepper import GE_ERR_ARG, PACK_WEREWOLF, GeError, GameTable, RoomBatch, load_dsl_by_gamename, pending_seats, slot_values
 from .toolcalls import WW_IS_ALIVE, RoomLog, turn_tool_calls
 from .ui_script import ui_tool_calls
@@ -449,6 +449,31 @@ class RoomPoolService:
         return [advise_output(room["table"], room["names"], tid, room["turn"], seats[j], room["view"], cands[j], n_rollouts, max_turns,
                               res[j][0], res[j][1], seat_view, res[j][2] if compare else None, bel[j])
                 for j, (tid, room) in enumerate(zip(thread_ids, rooms))]
+
+    def hints(self, thread_ids: Optional[Sequence[str]] = None, player_ids: Optional[Sequence[Optional[int]]] = None,
+              n_rollouts: int = 4096, max_turns: int = 1024, view: str = "seat") -> List[Dict[str, Any]]:
+        """Hints for many (thread, seat) pairs, each as RoomService.hint's: one advise_seats call per chunk touched (POLICY.md §3m).
+        thread_ids None: every thread waiting() reports, in the order the threads were created, and each of its pending seats
+        ascending - the tick "find who waits, tell each what their choices lead to" in two device calls per chunk.  With
+        thread_ids: player_ids[j] (None or absent: thread j's lowest human seat).  No thread changes."""
+        check_forecast_args(n_rollouts, max_turns)
+        seat_view = check_view(view)
+        if thread_ids is None:
+            if player_ids is not None:
+                raise ValueError("hints: player_ids need thread_ids")
+            wait = self.waiting()
+            pairs = [(tid, seat) for tid in self._rooms if tid in wait for seat in wait[tid]]
+        else:
+            pids = list(player_ids) if player_ids is not None else [None] * len(thread_ids)
+            if len(pids) != len(thread_ids):
+                raise ValueError("hints: thread_ids and player_ids differ in length")
+            pairs = [(tid, advise_seat(tid, self._rooms[tid]["human_seats"], pid)) for tid, pid in zip(thread_ids, pids)]
+        rooms = [self._rooms[tid] for tid, _ in pairs]
+        advs = run_hints([HintRequest(room["chunk"], room["slot"], room["key"], room["turn"], seat,
+                                      playout_max_cands(room["table"].pack, len(room["names"])) + 1)
+                          for room, (_, seat) in zip(rooms, pairs)], seat_view, n_rollouts, max_turns, self.seed)
+        return [hint_output(room["table"], room["names"], tid, room["turn"], seat, room["view"], n_rollouts, max_turns, adv, seat_view)
+                for room, (tid, seat), adv in zip(rooms, pairs, advs)]
 
     def _scan(self, want) -> List[Tuple[str, Any]]:
         """One find_rooms per chunk that holds a thread; (thread_id, hit) of the slots a thread owns - a free slot holds a template

@@ -344,6 +344,63 @@ def advise_output(table: GameTable, names: List[str], thread_id: str, turn: int,
             **({"beliefs": list(beliefs)} if beliefs is not None else {})}
 
 
+ADVISE_CAP = 1 << 26                        # ge_batch_advise_seats: sum of (max_cands + 1) x n_rollouts per call
+
+
+class HintRequest(NamedTuple):
+    """One (thread, seat) of a hint call: its batch, slot, thread key and turn, the advised seat, and the entries the library
+    reserves for it (playout_max_cands + 1)."""
+    batch: Any
+    slot: int
+    key: int
+    turn: int
+    seat: int
+    cost: int
+
+
+def run_hints(reqs: Sequence[HintRequest], seat_view: bool, n_rollouts: int, max_turns: int, seed: int) -> List[Any]:
+    """The advice records of a hint call, one per request: RoomBatch.advise_seats (POLICY.md §3m) under the thread's forecast key
+    and the forecast seed - advise's keys and seed, so a hint's numbers are those inside advise's option forecasts.  One call per
+    batch, in the order the batches first appear, split only where the library's cap on reserved playouts needs it."""
+    calls: Dict[int, List[List[int]]] = {}
+    cost: Dict[int, int] = {}
+    for j, r in enumerate(reqs):
+        b = id(r.batch)
+        if b not in calls:
+            calls[b], cost[b] = [[]], 0
+        elif (cost[b] + r.cost) * int(n_rollouts) > ADVISE_CAP:
+            calls[b].append([])
+            cost[b] = 0
+        calls[b][-1].append(j)
+        cost[b] += r.cost
+    out: List[Any] = [None] * len(reqs)
+    for part in (part for parts in calls.values() for part in parts):
+        adv = reqs[part[0]].batch.advise_seats([reqs[j].slot for j in part], [forecast_key(reqs[j].key) for j in part],
+                                               [reqs[j].turn for j in part], [reqs[j].seat for j in part], n_rollouts, max_turns,
+                                               seed=forecast_seed(seed), full_view=not seat_view)
+        for k, j in enumerate(part):
+            out[j] = adv[k]
+    return out
+
+
+def hint_output(table: GameTable, names: List[str], thread_id: str, turn: int, seat: int, view, n_rollouts: int, max_turns: int, adv,
+                seat_view: bool = True) -> Dict[str, Any]:
+    """hint's JSON from one advice record (ADVICE_DTYPE; the same bytes as room_service.js / room_pool.js): integers, names and
+    labels only.  `best` and `policy` are None when the seat has nothing to do now (then options is [])."""
+    ok = int(adv["status"]) == 0
+    options = []
+    for c in range(1, 13):
+        if ok and (int(adv["legal"]) >> (c - 1)) & 1:
+            o = adv["option"][c - 1]
+            options.append({"choice": c, "label": names[c - 1] if table.pack == PACK_WEREWOLF else str(c), "wins": int(o["wins"]),
+                            "score": int(o["score"]), "finished": int(o["finished"])})
+    p = adv["policy"]
+    return {"threadId": thread_id, "turn": int(turn), "playerId": int(seat), "phaseId": int(view["phase_id"]),
+            "rollouts": int(n_rollouts), "maxTurns": int(max_turns), "best": int(adv["best"]) if ok else None,
+            "policy": {"finished": int(p["finished"]), "wins": int(p["wins"]), "score": int(p["score"])} if ok else None,
+            "options": options, **({"view": "seat"} if seat_view else {})}
+
+
 RUN_MAX_TURNS = 4096                                        # ge_batch_run_rooms's cap on max_turns
 
 
@@ -659,6 +716,26 @@ class RoomService:
                             self.seed, compare)
         return advise_output(room["table"], room["names"], thread_id, turn, seat, rv, cands, n_rollouts, max_turns, res[0], res[1],
                              seat_view, res[2] if compare else None, bel)
+
+    def hint(self, thread_id: str, player_id: Optional[int] = None, n_rollouts: int = 4096, max_turns: int = 1024,
+             view: str = "seat") -> Dict[str, Any]:
+        """advise in 224 bytes: which choices the seat can make now, what each leads to for that seat, and the best of them - found,
+        played and ranked on the device (RoomBatch.advise_seats, POLICY.md §3m), under advise's keys and seed, so every number is
+        the advised seat's own inside advise(..., view=...)'s option forecasts (wins = players[seat].wins or topScore, score =
+        scoreSum, finished).  player_id defaults to the lowest human seat.  Returns JSON integers and labels: threadId, turn,
+        playerId, phaseId, rollouts, maxTurns, best (the choice with the most wins - Two-Truths: the highest score -, the lowest
+        on a tie), policy {finished, wins, score} (the policy plays the seat), options [{choice, label, wins, score, finished}]
+        ascending, and "view": "seat" in the default view ("full" plays from the true record: spectators and debugging).  best
+        and policy are None and options [] when the seat has nothing to do now.  The thread is not changed.  advise stays the
+        call for the full per-option forecast."""
+        check_forecast_args(n_rollouts, max_turns)
+        seat_view = check_view(view)
+        room = self._rooms[thread_id]
+        seat = advise_seat(thread_id, room["human_seats"], player_id)
+        turn = room["batch"].turn
+        cost = playout_max_cands(room["table"].pack, len(room["names"])) + 1
+        adv, = run_hints([HintRequest(room["batch"], 0, room["key"], turn, seat, cost)], seat_view, n_rollouts, max_turns, self.seed)
+        return hint_output(room["table"], room["names"], thread_id, turn, seat, room["view"], n_rollouts, max_turns, adv, seat_view)
 
     def close(self, thread_id: Optional[str] = None):
         for tid in ([thread_id] if thread_id else list(self._rooms)):

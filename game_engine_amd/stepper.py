@@ -69,6 +69,10 @@ def run_until_names(bits: int) -> List[str]:
 FIND_WANT = {"person": 1, "end": 2, "phase": 4}   # include/ge_step.h GE_FIND_*
 # include/ge_step.h ge_room_hit
 ROOM_HIT_DTYPE = np.dtype([("room", "<u8"), ("why", "<u4"), ("pending", "<u2"), ("phase_id", "u1"), ("segment", "u1")])
+# ge_advice (224 B) and its ge_advice_option (16 B)
+ADVICE_OPTION_DTYPE = np.dtype([("finished", "<u4"), ("wins", "<u4"), ("score", "<u8")])
+ADVICE_DTYPE = np.dtype([("status", "<i4"), ("legal", "<u4"), ("best", "<u4"), ("phase_id", "<u4"), ("policy", ADVICE_OPTION_DTYPE),
+                         ("option", ADVICE_OPTION_DTYPE, (12,))])
 
 
 def find_want_bits(want) -> int:
@@ -612,6 +616,30 @@ class RoomBatch:
         if baseline is not None:
             extra = (np.ascontiguousarray(baseline, dtype=np.uint32), np.ascontiguousarray(subjects, dtype=np.uint32))
         return self._rollout("rollout_beliefs", rooms, keys, turns, seats, actions, n_rollouts, max_turns, seed, extra, bel)
+
+    def advise_seats(self, rooms, keys, turns, seats, n_rollouts: int, max_turns: int = 1024, seed: Optional[int] = None,
+                     full_view: bool = False) -> np.ndarray:
+        """Advice for listed seats, found, played and ranked on the device (POLICY.md §3m).  Entry k is seat seats[k] (1-based,
+        any seat: no human mask is consulted) of room rooms[k].  Returns an ADVICE_DTYPE array: `legal` bit c-1 is set exactly
+        when inject_action(rooms[k], seats[k], c) would be accepted now; for each such c, option[c-1] = (finished, wins, score)
+        are summary.finished, seat_wins[seat-1] and seat_score[seat-1] of rollout_seats's entry (rooms[k], keys[k], turns[k],
+        seats[k] - 0 with full_view -, [(seats[k], c)]; n_rollouts, max_turns, seed); `policy` the same of that entry without
+        actions; `best` the legal choice with the most wins (Werewolf) or the highest score (Two-Truths), the lowest on a tie;
+        `phase_id` the room's phase.  A seat that could not act now gets status GE_ERR_ARG and zeros: that is an answer, not an
+        error.  The batch is only read.  GeError only for a structural error (NULL-free here: n_rollouts outside 1 .. 2^20,
+        max_turns > 4096, a room outside the batch, a seat outside 1 .. its room's player count, turns[k] + max_turns beyond
+        0xFFFFFFFF, more than 2^26 playouts reserved), before anything runs."""
+        rooms = np.ascontiguousarray(rooms, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        turns = np.ascontiguousarray(turns, dtype=np.uint32)
+        seats = np.ascontiguousarray(seats, dtype=np.uint32)
+        if not len(rooms) == len(keys) == len(turns) == len(seats):
+            raise GeError(-1, "advise_seats: arrays differ in length")
+        out = np.zeros(len(rooms), dtype=ADVICE_DTYPE)
+        _check(self._lib.ge_batch_advise_seats(self._h, len(rooms), rooms.ctypes.data, keys.ctypes.data, turns.ctypes.data,
+                                               seats.ctypes.data, n_rollouts, max_turns, self._seed if seed is None else seed,
+                                               _lib.ADVISE_FULL_VIEW if full_view else 0, out.ctypes.data), "ge_batch_advise_seats")
+        return out
 
     def _rollout(self, method: str, rooms, keys, turns, seats, actions, n_rollouts: int, max_turns: int,
                  seed: Optional[int], compare=None, beliefs=None):

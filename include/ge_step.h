@@ -51,7 +51,8 @@ extern "C" {
  *      GE_PLAYOUT_HALVING (a new flag of both playout-seat calls, no new symbol: sequential halving of each decision's playout
  *      budget; a library from before it refuses the bit with GE_ERR_ARG);
  *      ge_batch_rollout_beliefs + GE_BELIEF_SLOTS (seat-view playouts and comparisons whose re-deal is weighted by the caller's suspicions);
- *      ge_batch_find_rooms + ge_room_hit + GE_FIND_* (a device scan of a range: the rooms that wait for a person, have ended or stand in given phases) */
+ *      ge_batch_find_rooms + ge_room_hit + GE_FIND_* (a device scan of a range: the rooms that wait for a person, have ended or stand in given phases);
+ *      ge_batch_advise_seats + ge_advice + GE_ADVISE_FULL_VIEW (listed seats advised on the device: their legal choices found, played and ranked) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -659,6 +660,51 @@ int ge_batch_find_rooms(ge_batch *b, uint64_t first, uint64_t count, uint32_t wa
 int ge_batch_set_seats(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint32_t *masks);
 int ge_batch_get_seats(ge_batch *b, uint64_t first, uint64_t count, uint32_t *dst);
 int ge_batch_clear_seats(ge_batch *b);
+
+/* Advice for listed seats, on the device (POLICY.md §3m): which choices seat seats[k] (1-based) of batch room rooms[k] can make
+ * now, what ge_batch_rollout_seats says about each of them, and which is best.  Definition, by composition: the choices are
+ * c = 1 .. C, C = the n_players of the room's segment (Werewolf) or 3 (Two-Truths).  Bit c-1 of `legal` is set exactly when
+ * ge_batch_inject_action(room, seats[k], c) on a copy of the room returns GE_OK - the human mask and the seat plane play no part:
+ * any seat may be advised.  For every legal c, option[c-1] = (summary.finished, seat_wins[s-1], seat_score[s-1]) of
+ * ge_batch_rollout_seats's entry (rooms[k], keys[k], turns[k], seat s = seats[k] - seat 0 under GE_ADVISE_FULL_VIEW -, actions
+ * [(s, c)], n_rollouts, max_turns, seed); `policy` is the same three words of that entry without actions (the policy plays the
+ * seat).  `best` is the legal choice with the highest value, the lowest such choice on a tie; the value is `wins` in Werewolf and
+ * `score` in Two-Truths - the outcome ge_batch_rollout_compare compares.  A Two-Truths statements phase has the single legal
+ * choice 1 and is played like any other.  legal == 0 (the seat is no pending target: the phase takes no action, the seat is dead,
+ * has acted, or the game is over): status = GE_ERR_ARG, nothing is played and every other word of the record is 0.
+ * A structurally valid call returns GE_OK whatever the per-entry statuses are - unlike ge_batch_rollout_actions, which returns
+ * the first refused entry's status: a seat that is not pending is an expected answer to a host that lists seats it has not
+ * tested, not a failed call.  Read out[k].status.
+ * All checks run before anything runs, and on a failure *out is untouched: GE_ERR_ARG for a NULL array with n > 0, unknown flag
+ * bits, n_rollouts == 0 or > 2^20, max_turns > 4096; GE_ERR_RANGE for a room outside the batch or turns[k] + max_turns >
+ * 0xFFFFFFFF; then GE_ERR_ARG for seats[k] == 0 or above the n_players of room k's segment, or sum_k (c_k + 1) * n_rollouts >
+ * 2^26, c_k = the most candidates a seat of room k can have (Werewolf: n_players, Two-Truths: max(n_players, 3): an upper bound
+ * of what is played, as in ge_batch_step_rooms_playout).  n == 0: GE_OK.  Repeated rooms and repeated (room, seat) pairs are
+ * allowed.  The batch is only read: records, prepared deals, the seat plane, the turn counter and the GE_FLAG_TRACE buffer stay
+ * as they are.  Ordered behind the previous step; synchronises.
+ * On the device: a plan kernel (lane = listed entry) finds `legal` with the code of ge_batch_inject_action on copies of the
+ * record and writes popcount(legal) + 1 entries of ge_batch_rollout_seats; that call's playout kernel plays them where they
+ * lie; a reduce kernel stores the 224 bytes.  Only the entry list goes up, and the advice records and 8 bytes per launch unit
+ * come back (a pass of the call holds at most 65 536 playout entries).
+ * Measured on an MI355X (tools/advise_seats_probe.py, profiles/advise_seats_probe.txt: Werewolf x 8, human_mask = 1, 40 turns stepped,
+ * seat 1 of every waiting room advised at 64 playouts per choice; medians of 9 ticks, the call against itself in the same run x 1.02):
+ * ge_batch_find_rooms + this call against ge_batch_find_rooms + ge_batch_read_rooms_at + the host listing every seat id +
+ * ge_batch_rollout_seats + the host's maximum (the same playouts, the same `best` in every room): 1.10 ms against 3.35 ms at 4 096
+ * rooms (3 556 waiting), 15.4 ms against 77.5 ms at 65 536 (56 688 waiting); 13.6 MB come back instead of 330 MB.  No other shape
+ * has been measured. */
+typedef struct ge_advice_option { uint32_t finished, wins; uint64_t score; } ge_advice_option;   /* 16 B */
+typedef struct ge_advice {                 /* 224 B */
+    int32_t  status;     /* GE_OK, or GE_ERR_ARG: no choice of this seat would be accepted now; everything below is then 0 */
+    uint32_t legal;      /* bit c-1: choice c is accepted by ge_batch_inject_action for this seat now, and was played */
+    uint32_t best;       /* the legal choice with the highest value, the lowest such choice on a tie */
+    uint32_t phase_id;   /* the room's current phase id (DSL id, as ge_room_hit.phase_id) */
+    ge_advice_option policy;       /* the entry without an action: the policy plays the seat */
+    ge_advice_option option[12];   /* option[c-1], zero where bit c-1 of legal is clear */
+} ge_advice;
+#define GE_ADVISE_FULL_VIEW 1u   /* play from the true record (seat 0) instead of the seat's view */
+int ge_batch_advise_seats(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
+                          const uint32_t *seats /* n, 1-based */, uint32_t n_rollouts, uint32_t max_turns, uint64_t seed,
+                          uint32_t flags, ge_advice *out /* n */);
 
 /* GE_FLAG_TRACE: events of the most recent ge_batch_step call, dst[(room - first) * *n_turns + t].
  * cap_bytes >= count * n_turns * sizeof(ge_turn_event).  Synchronises. */

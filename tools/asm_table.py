@@ -49,6 +49,9 @@ def describe(mangled: str) -> dict:
     if m:
         return {"kernel": "ge_rollout_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True,
                 "act": int(m.group(3) or 0)}
+    m = re.search(r"ge_advise_planILi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_advise_plan", "layout": KINDS[int(m.group(1))], "lowocc": False, "generic": False, "single": True}
     m = re.search(r"ge_playout_plan_rangedILi(\d)E", mangled)
     if m:
         return {"kernel": "ge_playout_plan_ranged", "layout": KINDS[int(m.group(1))], "lowocc": False, "generic": False, "single": True}
@@ -107,6 +110,10 @@ def label(r):
     if r["kernel"] in ("ge_seats_fill", "ge_seats_scatter"):     # ge_batch_set_seats
         what = {"ge_seats_fill": "a segment's mask for its rooms", "ge_seats_scatter": "the listed rooms' masks"}[r["kernel"]]
         return f"{r['kernel']} (ge_batch_set_seats: {what})"
+    if r["kernel"] == "ge_advise_plan":                          # ge_batch_advise_seats: one launch per unit of listed entries
+        return f"{r['layout']}, advised seats, plan (ge_batch_advise_seats)"
+    if r["kernel"] == "ge_advise_reduce":                        # ge_batch_advise_seats: behind the playouts of a unit
+        return "ge_advise_reduce (ge_batch_advise_seats: the advice records from the accumulators)"
     if r["kernel"] == "ge_rollout_kernel" and r.get("act") == 4:  # GE_PLAYOUT_HALVING: one launch per unit and round
         return f"{r['layout']}, playouts over a replica range (GE_PLAYOUT_HALVING)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_playout_plan_ranged":
