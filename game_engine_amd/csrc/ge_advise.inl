@@ -2,7 +2,8 @@
 // seat could make now are found, each is played by ge_batch_rollout_seats's own kernel, and the ranking comes back in 224 bytes
 // (included at the end of ge_step.hip, behind ge_seats.inl: the existing kernels keep their code-object offsets).  The grouping
 // and staging of the listed entries are ge_pool.inl's (PoolEntries, io_stage, pool_scratch), the units and passes follow
-// ge_playout.inl's, the playouts are ge_rollout.inl's.  What this file adds is the plan and reduce kernels.
+// ge_playout.inl's, which also owns the pass's entry block and a unit's playout arguments (PassEntries, bind_entries,
+// unit_rollout_args); the playouts are ge_rollout.inl's.  What this file adds is the plan and reduce kernels.
 //
 // Per listed entry, on the device, with no room record and no ge_rollout_stats crossing to the host:
 //   1. ge_advise_plan: one lane per listed entry.  It unpacks the record and tests every choice c = 1 .. C of the seat with
@@ -177,22 +178,12 @@ static int advise_seats_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
     advise_units(b, en, units, n_pass, max_cap);
     const uint32_t n_units = (uint32_t)units.size();
     // one scratch layout, each array from a 16 B boundary.  Upload: [rooms u64][keys u64][turns u32][seats u32][unit counters
-    // u64, zeroed].  Then [plan 16 B][advice 224 B] per listed entry and the pass's entries: [rooms u64][keys u64][turns u32]
-    // [seats u32][first u32 (+1)][players u32][choices u32][status i32][acc]
-    const size_t N = (size_t)n, C = max_cap;
+    // u64, zeroed].  Then [plan 16 B][advice 224 B] per listed entry and the pass's entries
+    const size_t N = (size_t)n;
     const size_t o_keys = 8 * N, o_turns = 16 * N, o_seats = up16(o_turns + 4 * N), o_ctr = up16(o_seats + 4 * N);
     const size_t o_up_end = up16(o_ctr + 8 * (size_t)n_units);
     const size_t o_plan = o_up_end, o_adv = o_plan + 16 * N;
-    RollStage o;
-    const size_t o_erooms = o_adv + sizeof(ge_advice) * N, o_ekeys = o_erooms + 8 * C, o_eturns = o_ekeys + 8 * C;
-    o.keys = o.turns = 0;
-    o.seats = up16(o_eturns + 4 * C);
-    o.first = up16(o.seats + 4 * C);
-    o.players = up16(o.first + 4 * (C + 1u));
-    o.choices = up16(o.players + 4 * C);
-    o.status = up16(o.choices + 4 * C);
-    o.acc = up16(o.status + 4 * C);
-    o.total = o.acc + 8 * (size_t)ROLL_STRIDE * C;
+    const PassEntries pe(o_adv + sizeof(ge_advice) * N, max_cap, false);
     // the pinned buffer holds the upload, then the advice records on their way back
     uint32_t *host32 = nullptr;
     if ((st = io_stage(b, std::max(o_up_end, sizeof(ge_advice) * N), &host32)) != GE_OK) return st;
@@ -202,12 +193,11 @@ static int advise_seats_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
     for (size_t i = 0; i < N; i++) h_seats[i] = seats[order[i]];
     memset(host + o_ctr, 0, o_up_end - o_ctr);
     char *dev = nullptr;
-    if ((st = pool_scratch(b, o.total, &dev)) != GE_OK) return st;
+    if ((st = pool_scratch(b, pe.o.total, &dev)) != GE_OK) return st;
     hipStream_t s = b->last_stream;
     if ((st = order_after_previous(b, s)) != GE_OK) return st;
     HIP_TRY(hipMemcpyAsync(dev, host, o_up_end, hipMemcpyHostToDevice, s));
     const uint64_t *h_ctr = reinterpret_cast<const uint64_t *>(host + o_ctr);
-    const uint32_t waves = (n_rollouts + 63u) / 64u;
     for (uint32_t p = 0; p < n_pass; p++) {
         // 1. plan every unit of the pass
         for (const PlayoutUnit &u : units) {
@@ -219,10 +209,7 @@ static int advise_seats_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
             a.seats = reinterpret_cast<const uint32_t *>(dev + o_seats) + u.lo;
             a.plan = reinterpret_cast<u32x4 *>(dev + o_plan) + u.lo;
             a.counter = reinterpret_cast<unsigned long long *>(dev + o_ctr) + (&u - units.data());
-            a.e_rooms = reinterpret_cast<uint64_t *>(dev + o_erooms); a.e_keys = reinterpret_cast<uint64_t *>(dev + o_ekeys);
-            a.e_turns = reinterpret_cast<uint32_t *>(dev + o_eturns); a.e_seats = reinterpret_cast<uint32_t *>(dev + o.seats);
-            a.e_first = reinterpret_cast<uint32_t *>(dev + o.first); a.e_players = reinterpret_cast<uint32_t *>(dev + o.players);
-            a.e_choices = reinterpret_cast<uint32_t *>(dev + o.choices); a.e_status = reinterpret_cast<int32_t *>(dev + o.status);
+            bind_entries(a, dev, pe);
             a.n = u.cnt; a.seg = u.seg; a.full_view = (flags & GE_ADVISE_FULL_VIEW) ? 1u : 0u; a.e_base = u.e_base;
             HIP_TRY(advise_launch(b->segs[u.seg].dev.kind, dim3((u.cnt + 63u) / 64u), s, b, a));
         }
@@ -233,16 +220,8 @@ static int advise_seats_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
         for (const PlayoutUnit &u : units) {
             const uint32_t cnt = (uint32_t)(h_ctr[&u - units.data()] >> 32);
             if (u.pass != p || !cnt) continue;                // (cnt < e_cap: a listed entry reserves its most)
-            HIP_TRY(hipMemsetAsync(dev + o.acc + 8 * (size_t)ROLL_STRIDE * u.e_base, 0, 8 * (size_t)ROLL_STRIDE * cnt, s));
-            RolloutArgs a;
-            a.rooms = reinterpret_cast<const uint64_t *>(dev + o_erooms) + u.e_base;
-            a.keys = reinterpret_cast<const uint64_t *>(dev + o_ekeys) + u.e_base;
-            a.turns = reinterpret_cast<const uint32_t *>(dev + o_eturns) + u.e_base;
-            a.acc = reinterpret_cast<unsigned long long *>(dev + o.acc) + (size_t)ROLL_STRIDE * u.e_base;
-            a.n = cnt; a.seg = u.seg; a.seed_key = seed_key((uint32_t)seed, (uint32_t)(seed >> 32));
-            a.n_rollouts = n_rollouts; a.max_turns = max_turns; a.waves = waves;
-            a.settle_mask = rollout_settle_mask(b->segs[u.seg]);
-            HIP_TRY(rollout_launch_form<2>(b, s, a, dev, o, u.e_base));
+            HIP_TRY(hipMemsetAsync(dev + pe.o.acc + 8 * (size_t)ROLL_STRIDE * u.e_base, 0, 8 * (size_t)ROLL_STRIDE * cnt, s));
+            HIP_TRY(rollout_launch_form<2>(b, s, unit_rollout_args(b, dev, pe, u, cnt, seed, n_rollouts, max_turns), dev, pe.o, u.e_base));
         }
         // 3. the advice records (a unit without a run still stores its refusals)
         for (const PlayoutUnit &u : units) {
@@ -251,7 +230,7 @@ static int advise_seats_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
             AdviseReduceArgs a;
             a.plan = reinterpret_cast<const u32x4 *>(dev + o_plan) + u.lo;
             a.seats = reinterpret_cast<const uint32_t *>(dev + o_seats) + u.lo;
-            a.acc = reinterpret_cast<const unsigned long long *>(dev + o.acc);
+            a.acc = reinterpret_cast<const unsigned long long *>(dev + pe.o.acc);
             a.out = reinterpret_cast<u32x4 *>(dev + o_adv) + (size_t)ADVISE_VEC * u.lo;
             a.n = u.cnt; a.by_score = (kind == K_WW8 || kind == K_WW12) ? 0u : 1u;
             HIP_TRY(advise_launch(dim3((u.cnt + 63u) / 64u), s, a));

@@ -2,7 +2,9 @@
 // their action by their own seat-view playouts (included at the end of ge_step.hip, behind ge_rollout.inl: the existing kernels
 // keep their code-object offsets).  The entry checks, the grouping and staging of the listed rooms, the turn launch (step 4) and
 // the event decoding are ge_pool.inl's (pool_check_entries, PoolEntries, launch_pool_turn, pool_decode_event); the playouts are
-// ge_rollout.inl's.  What this file adds is the plan and decide kernels - one body each over PlayoutGame - and the passes.
+// ge_rollout.inl's.  What this file adds is the plan and decide kernels - one body each over PlayoutGame - and the playout pass:
+// the units and passes, the pass's entry block, the arguments of its kernels and the playing of a unit (PassEntries .. play_unit),
+// which ge_run_playout.inl uses as they are and ge_advise.inl in part.
 //
 // Per listed room, on the device, with no room record crossing to the host:
 //   1. ge_playout_plan: one lane per room.  It unpacks the record and finds the seats of its playout mask that decide in this
@@ -328,6 +330,131 @@ static void playout_units(const ge_batch *b, const PoolEntries &en, const uint32
     }
 }
 
+// ---- the playout pass: what ge_batch_step_rooms_playout, ge_batch_run_rooms_playout (ge_run_playout.inl) and
+// ge_batch_advise_seats (ge_advise.inl) share.  Each call lays out its own upload and download arrays; these are the same bytes
+// and the same launches in all of them.
+
+// The entries of a pass, device only: C entries from byte `at` of the call's scratch, each array from a 16 B boundary -
+// [rooms u64][keys u64][turns u32][seats u32][first u32 (+1)][players u32][choices u32][status i32][acc 8 B x ROLL_STRIDE] and,
+// `ranged` (GE_PLAYOUT_HALVING), [replica range 8 B].  o: the arrays rollout_form_args reads (a unit's rooms, keys and turns go
+// through its RolloutArgs, so o.keys and o.turns are not used); o.total: the end of the block, the scratch the call needs
+struct PassEntries {
+    size_t rooms, keys, turns, range;
+    RollStage o;
+    PassEntries(size_t at, size_t C, bool ranged) : rooms(at), keys(rooms + 8 * C), turns(keys + 8 * C) {
+        o.keys = o.turns = 0;
+        o.seats = up16(turns + 4 * C);
+        o.first = up16(o.seats + 4 * C);
+        o.players = up16(o.first + 4 * (C + 1u));
+        o.choices = up16(o.players + 4 * C);
+        o.status = up16(o.choices + 4 * C);
+        o.acc = up16(o.status + 4 * C);
+        range = o.acc + 8 * (size_t)ROLL_STRIDE * C;
+        o.total = range + (ranged ? 8 * C : 0u);
+    }
+};
+
+// the e_* members of a plan's arguments (PlanArgs, AdvisePlanArgs): the pass's entries in the block at dev
+template <class A> static void bind_entries(A &a, char *dev, const PassEntries &e) {
+    a.e_rooms = reinterpret_cast<uint64_t *>(dev + e.rooms); a.e_keys = reinterpret_cast<uint64_t *>(dev + e.keys);
+    a.e_turns = reinterpret_cast<uint32_t *>(dev + e.turns); a.e_seats = reinterpret_cast<uint32_t *>(dev + e.o.seats);
+    a.e_first = reinterpret_cast<uint32_t *>(dev + e.o.first); a.e_players = reinterpret_cast<uint32_t *>(dev + e.o.players);
+    a.e_choices = reinterpret_cast<uint32_t *>(dev + e.o.choices); a.e_status = reinterpret_cast<int32_t *>(dev + e.o.status);
+}
+
+// the playouts of unit u's first n entries: `seed` the playouts' own, one wavefront per 64 playouts (a round of §3h sets its own)
+static RolloutArgs unit_rollout_args(const ge_batch *b, char *dev, const PassEntries &e, const PlayoutUnit &u, uint32_t n, uint64_t seed,
+                                     uint32_t n_rollouts, uint32_t max_turns) {
+    RolloutArgs a;
+    a.rooms = reinterpret_cast<const uint64_t *>(dev + e.rooms) + u.e_base;
+    a.keys = reinterpret_cast<const uint64_t *>(dev + e.keys) + u.e_base;
+    a.turns = reinterpret_cast<const uint32_t *>(dev + e.turns) + u.e_base;
+    a.acc = reinterpret_cast<unsigned long long *>(dev + e.o.acc) + (size_t)ROLL_STRIDE * u.e_base;
+    a.n = n; a.seg = u.seg; a.seed_key = seed_key((uint32_t)seed, (uint32_t)(seed >> 32));
+    a.n_rollouts = n_rollouts; a.max_turns = max_turns; a.waves = (n_rollouts + 63u) / 64u;
+    a.settle_mask = rollout_settle_mask(b->segs[u.seg]);
+    return a;
+}
+
+// the listed rooms of a playout-seat call on the device, over the sorted positions (a unit's are these + u.lo), and the scalars
+// every unit shares; the offsets are the call's own layout (rooms at 0)
+struct PassRooms {
+    const uint64_t *rooms, *keys, *pkeys;
+    const uint32_t *turns, *masks;
+    uint32_t *room_first, *room_cnt;        // per listed room: its entries [first, first + cnt) of the pass
+    uint32_t seed_key, restart, full_view;
+};
+static PassRooms pass_rooms(const ge_batch *b, char *dev, size_t o_keys, size_t o_pkeys, size_t o_turns, size_t o_masks, size_t o_rfirst, size_t o_rcnt,
+                            uint32_t flags) {
+    PassRooms r;
+    r.rooms = reinterpret_cast<const uint64_t *>(dev);
+    r.keys = reinterpret_cast<const uint64_t *>(dev + o_keys);
+    r.pkeys = reinterpret_cast<const uint64_t *>(dev + o_pkeys);
+    r.turns = reinterpret_cast<const uint32_t *>(dev + o_turns);
+    r.masks = reinterpret_cast<const uint32_t *>(dev + o_masks);
+    r.room_first = reinterpret_cast<uint32_t *>(dev + o_rfirst);
+    r.room_cnt = reinterpret_cast<uint32_t *>(dev + o_rcnt);
+    r.seed_key = seed_key((uint32_t)b->seed, (uint32_t)(b->seed >> 32));
+    r.restart = (b->flags & GE_FLAG_RESTART) ? 1u : 0u;
+    r.full_view = (flags & GE_PLAYOUT_FULL_VIEW) ? 1u : 0u;
+    return r;
+}
+
+static PlanArgs plan_args(const PassRooms &r, const PlayoutUnit &u, uint32_t *counter, char *dev, const PassEntries &e) {
+    PlanArgs a;
+    a.rooms = r.rooms + u.lo; a.keys = r.keys + u.lo; a.pkeys = r.pkeys + u.lo;
+    a.turns = r.turns + u.lo; a.masks = r.masks + u.lo;
+    a.room_first = r.room_first + u.lo; a.room_cnt = r.room_cnt + u.lo;
+    a.counter = counter;
+    bind_entries(a, dev, e);
+    a.n = u.cnt; a.seg = u.seg; a.seed_key = r.seed_key; a.restart = r.restart; a.full_view = r.full_view; a.e_base = u.e_base;
+    return a;
+}
+
+// out: the unit's first room's 16 bytes (decided mask, choice nibbles)
+static DecideArgs decide_args(const PassRooms &r, const PlayoutUnit &u, u32x4 *out, char *dev, const PassEntries &e) {
+    DecideArgs a;
+    a.rooms = r.rooms + u.lo; a.keys = r.keys + u.lo; a.turns = r.turns + u.lo;
+    a.room_first = r.room_first + u.lo; a.room_cnt = r.room_cnt + u.lo;
+    a.e_players = reinterpret_cast<const uint32_t *>(dev + e.o.players);
+    a.e_choices = reinterpret_cast<const uint32_t *>(dev + e.o.choices);
+    a.acc = reinterpret_cast<const unsigned long long *>(dev + e.o.acc);
+    a.out = out;
+    a.n = u.cnt; a.seg = u.seg; a.seed_key = r.seed_key;
+    return a;
+}
+
+// Step 2 for one unit: its entries (a = unit_rollout_args) played as form 2 in one launch or, `halving`, in the rounds of §3h -
+// form 4 over the entries' replica ranges, the accumulators adding up, ge_playout_halve between two rounds and no cut behind the
+// last.  launch(RollArgs<2 | 4>) is the caller's: it knows whether the host has the entry count (rollout_launch_counted) or the
+// device reads it (ge_run_playout.inl)
+template <class LAUNCH>
+static hipError_t play_unit(const ge_batch *b, hipStream_t s, char *dev, const PassEntries &e, const PassRooms &r, const PlayoutUnit &u, RolloutArgs a,
+                            bool halving, LAUNCH &&launch) {
+    if (!halving) return launch(rollout_form_args<2>(a, dev, e.o, u.e_base));
+    const SegDev &sd = b->segs[u.seg].dev;
+    const uint32_t r_max = halving_max_rounds(sd);
+    HalveArgs h;
+    h.room_first = r.room_first + u.lo; h.room_cnt = r.room_cnt + u.lo;
+    h.e_players = reinterpret_cast<const uint32_t *>(dev + e.o.players);
+    h.acc = reinterpret_cast<const unsigned long long *>(dev + e.o.acc);
+    h.e_range = reinterpret_cast<u32x2 *>(dev + e.range);
+    h.n = u.cnt; h.n_rollouts = a.n_rollouts;
+    for (uint32_t j = 0; j < r_max; j++) {
+        hipError_t err = hipSuccess;
+        a.waves = halving_waves(a.n_rollouts, playout_max_cands(sd), j);
+        if (a.waves) {                                        // (no round is longer than n_rollouts: the grid is within the plain form's)
+            RollArgs<4> ra = rollout_form_args<4>(a, dev, e.o, u.e_base);
+            ra.range = h.e_range + u.e_base;
+            if ((err = launch(ra)) != hipSuccess) return err;
+        }
+        if (j + 1u == r_max) break;
+        h.round = j;
+        if ((err = playout_launch(dim3((u.cnt + 63u) / 64u), s, h)) != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+
 static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, const uint32_t *masks,
                              const uint64_t *pkeys, uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, uint32_t flags, ge_turn_event *events,
                              uint32_t *decided) {
@@ -341,26 +468,16 @@ static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
     playout_units(b, en, masks, units, n_pass, max_cap);
     const uint32_t n_units = (uint32_t)units.size();
     // one scratch layout, each array from a 16 B boundary.  Upload: [rooms u64][keys u64][pkeys u64][turns u32][masks u32]
-    // [unit counters u32][per-room outputs 16 B, zeroed].  Then [room_first u32][room_cnt u32][events 16 B] and the pass's
-    // entries: [rooms u64][keys u64][turns u32][seats u32][first u32 (+1)][players u32][choices u32][status i32][acc]
-    const size_t N = (size_t)n, C = max_cap;
+    // [unit counters u32][per-room outputs 16 B, zeroed].  Then [room_first u32][room_cnt u32][events 16 B]: the pinned buffer ends
+    // here.  Behind it, on the device only, the pass's entries
+    const size_t N = (size_t)n;
     const size_t o_keys = 8 * N, o_pkeys = 16 * N, o_turns = 24 * N, o_masks = up16(o_turns + 4 * N), o_ctr = up16(o_masks + 4 * N);
     const size_t o_out = up16(o_ctr + 4 * (size_t)n_units), o_up_end = o_out + 16 * N;
-    const size_t o_rfirst = o_up_end, o_rcnt = up16(o_rfirst + 4 * N), o_ev = up16(o_rcnt + 4 * N);
-    RollStage o;
-    const size_t o_erooms = o_ev + 16 * N, o_ekeys = o_erooms + 8 * C, o_eturns = o_ekeys + 8 * C;
-    o.keys = o.turns = 0;
-    o.seats = up16(o_eturns + 4 * C);
-    o.first = up16(o.seats + 4 * C);
-    o.players = up16(o.first + 4 * (C + 1u));
-    o.choices = up16(o.players + 4 * C);
-    o.status = up16(o.choices + 4 * C);
-    o.acc = up16(o.status + 4 * C);
+    const size_t o_rfirst = o_up_end, o_rcnt = up16(o_rfirst + 4 * N), o_ev = up16(o_rcnt + 4 * N), host_total = o_ev + 16 * N;
     const bool halving = (flags & GE_PLAYOUT_HALVING) != 0u;
-    const size_t o_range = o.acc + 8 * (size_t)ROLL_STRIDE * C;   // (halving only) the entries' replica ranges, 8 B each
-    o.total = o_range + (halving ? 8 * C : 0u);
+    const PassEntries pe(host_total, max_cap, halving);
     uint32_t *host32 = nullptr;
-    if ((st = io_stage(b, o.total, &host32)) != GE_OK) return st;
+    if ((st = io_stage(b, host_total, &host32)) != GE_OK) return st;
     unsigned char *host = reinterpret_cast<unsigned char *>(host32);
     en.stage(b, rooms, keys, turns, host, o_keys, o_turns);
     uint64_t *h_pkeys = reinterpret_cast<uint64_t *>(host + o_pkeys);
@@ -368,93 +485,36 @@ static int step_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
     for (size_t i = 0; i < N; i++) { h_pkeys[i] = pkeys[order[i]]; h_masks[i] = masks[order[i]]; }
     memset(host + o_ctr, 0, o_up_end - o_ctr);
     char *dev = nullptr;
-    if ((st = pool_scratch(b, o.total, &dev)) != GE_OK) return st;
+    if ((st = pool_scratch(b, pe.o.total, &dev)) != GE_OK) return st;
     hipStream_t s = b->last_stream;
     if ((st = order_after_previous(b, s)) != GE_OK) return st;
     HIP_TRY(hipMemcpyAsync(dev, host, o_up_end, hipMemcpyHostToDevice, s));
-    const uint32_t seed_b = seed_key((uint32_t)b->seed, (uint32_t)(b->seed >> 32));
-    const uint32_t restart = (b->flags & GE_FLAG_RESTART) ? 1u : 0u;
+    const PassRooms pr = pass_rooms(b, dev, o_keys, o_pkeys, o_turns, o_masks, o_rfirst, o_rcnt, flags);
     const uint32_t *h_ctr = reinterpret_cast<const uint32_t *>(host + o_ctr);
     for (uint32_t p = 0; p < n_pass; p++) {
         // 1. plan every unit of the pass
         for (const PlayoutUnit &u : units) {
             if (u.pass != p) continue;
-            PlanArgs a;
-            a.rooms = reinterpret_cast<const uint64_t *>(dev) + u.lo;
-            a.keys = reinterpret_cast<const uint64_t *>(dev + o_keys) + u.lo;
-            a.pkeys = reinterpret_cast<const uint64_t *>(dev + o_pkeys) + u.lo;
-            a.turns = reinterpret_cast<const uint32_t *>(dev + o_turns) + u.lo;
-            a.masks = reinterpret_cast<const uint32_t *>(dev + o_masks) + u.lo;
-            a.room_first = reinterpret_cast<uint32_t *>(dev + o_rfirst) + u.lo;
-            a.room_cnt = reinterpret_cast<uint32_t *>(dev + o_rcnt) + u.lo;
-            a.counter = reinterpret_cast<uint32_t *>(dev + o_ctr) + (&u - units.data());
-            a.e_rooms = reinterpret_cast<uint64_t *>(dev + o_erooms); a.e_keys = reinterpret_cast<uint64_t *>(dev + o_ekeys);
-            a.e_turns = reinterpret_cast<uint32_t *>(dev + o_eturns); a.e_seats = reinterpret_cast<uint32_t *>(dev + o.seats);
-            a.e_first = reinterpret_cast<uint32_t *>(dev + o.first); a.e_players = reinterpret_cast<uint32_t *>(dev + o.players);
-            a.e_choices = reinterpret_cast<uint32_t *>(dev + o.choices); a.e_status = reinterpret_cast<int32_t *>(dev + o.status);
-            a.n = u.cnt; a.seg = u.seg; a.seed_key = seed_b; a.restart = restart;
-            a.full_view = (flags & GE_PLAYOUT_FULL_VIEW) ? 1u : 0u; a.e_base = u.e_base;
+            const PlanArgs a = plan_args(pr, u, reinterpret_cast<uint32_t *>(dev + o_ctr) + (&u - units.data()), dev, pe);
             const dim3 grid((u.cnt + 63u) / 64u);
-            HIP_TRY(halving ? playout_launch(b->segs[u.seg].dev.kind, grid, s, b, a, reinterpret_cast<u32x2 *>(dev + o_range), n_rollouts)
+            HIP_TRY(halving ? playout_launch(b->segs[u.seg].dev.kind, grid, s, b, a, reinterpret_cast<u32x2 *>(dev + pe.range), n_rollouts)
                             : playout_launch(b->segs[u.seg].dev.kind, grid, s, b, a));
         }
         // 2. the entry counts (the one host round trip), then the playouts of each unit
         HIP_TRY(hipMemcpyAsync(host + o_ctr, dev + o_ctr, 4 * (size_t)n_units, hipMemcpyDeviceToHost, s));
         if ((st = sync_impl(b)) != GE_OK) return st;
         if ((st = order_after_previous(b, s)) != GE_OK) return st;
-        const uint32_t waves = (n_rollouts + 63u) / 64u;
         for (const PlayoutUnit &u : units) {
             const uint32_t cnt = h_ctr[&u - units.data()];
             if (u.pass != p || !cnt) continue;
-            HIP_TRY(hipMemsetAsync(dev + o.acc + 8 * (size_t)ROLL_STRIDE * u.e_base, 0, 8 * (size_t)ROLL_STRIDE * cnt, s));
-            RolloutArgs a;
-            a.rooms = reinterpret_cast<const uint64_t *>(dev + o_erooms) + u.e_base;
-            a.keys = reinterpret_cast<const uint64_t *>(dev + o_ekeys) + u.e_base;
-            a.turns = reinterpret_cast<const uint32_t *>(dev + o_eturns) + u.e_base;
-            a.acc = reinterpret_cast<unsigned long long *>(dev + o.acc) + (size_t)ROLL_STRIDE * u.e_base;
-            a.n = cnt; a.seg = u.seg; a.seed_key = seed_key((uint32_t)seed, (uint32_t)(seed >> 32));
-            a.n_rollouts = n_rollouts; a.max_turns = max_turns; a.waves = waves;
-            a.settle_mask = rollout_settle_mask(b->segs[u.seg]);
-            if (!halving) {
-                HIP_TRY(rollout_launch_form<2>(b, s, a, dev, o, u.e_base));
-                continue;
-            }
-            // §3h: the rounds of this unit's segment, the accumulators adding up; no cut behind the last round
-            const SegDev &sd = b->segs[u.seg].dev;
-            const uint32_t kind = sd.kind, r_max = halving_max_rounds(sd);
-            for (uint32_t j = 0; j < r_max; j++) {
-                a.waves = halving_waves(n_rollouts, playout_max_cands(sd), j);
-                if (a.waves) {
-                    RollArgs<4> ra = rollout_form_args<4>(a, dev, o, u.e_base);
-                    ra.range = reinterpret_cast<const u32x2 *>(dev + o_range) + u.e_base;
-                    const dim3 grid(cnt * a.waves);           // <= 2^26 blocks: no round is longer than n_rollouts
-                    HIP_TRY((b->generic ? rollout_launch<1, 4>(kind, grid, s, b, ra) : rollout_launch<0, 4>(kind, grid, s, b, ra)));
-                }
-                if (j + 1u == r_max) break;
-                HalveArgs h;
-                h.room_first = reinterpret_cast<const uint32_t *>(dev + o_rfirst) + u.lo;
-                h.room_cnt = reinterpret_cast<const uint32_t *>(dev + o_rcnt) + u.lo;
-                h.e_players = reinterpret_cast<const uint32_t *>(dev + o.players);
-                h.acc = reinterpret_cast<const unsigned long long *>(dev + o.acc);
-                h.e_range = reinterpret_cast<u32x2 *>(dev + o_range);
-                h.n = u.cnt; h.n_rollouts = n_rollouts; h.round = j;
-                HIP_TRY(playout_launch(dim3((u.cnt + 63u) / 64u), s, h));
-            }
+            HIP_TRY(hipMemsetAsync(dev + pe.o.acc + 8 * (size_t)ROLL_STRIDE * u.e_base, 0, 8 * (size_t)ROLL_STRIDE * cnt, s));
+            HIP_TRY(play_unit(b, s, dev, pe, pr, u, unit_rollout_args(b, dev, pe, u, cnt, seed, n_rollouts, max_turns), halving,
+                              [&](const auto &ra) { return rollout_launch_counted(b, s, ra); }));
         }
         // 3. decide and log
         for (const PlayoutUnit &u : units) {
             if (u.pass != p || !h_ctr[&u - units.data()]) continue;
-            DecideArgs a;
-            a.rooms = reinterpret_cast<const uint64_t *>(dev) + u.lo;
-            a.keys = reinterpret_cast<const uint64_t *>(dev + o_keys) + u.lo;
-            a.turns = reinterpret_cast<const uint32_t *>(dev + o_turns) + u.lo;
-            a.room_first = reinterpret_cast<const uint32_t *>(dev + o_rfirst) + u.lo;
-            a.room_cnt = reinterpret_cast<const uint32_t *>(dev + o_rcnt) + u.lo;
-            a.e_players = reinterpret_cast<const uint32_t *>(dev + o.players);
-            a.e_choices = reinterpret_cast<const uint32_t *>(dev + o.choices);
-            a.acc = reinterpret_cast<const unsigned long long *>(dev + o.acc);
-            a.out = reinterpret_cast<u32x4 *>(dev + o_out) + u.lo;
-            a.n = u.cnt; a.seg = u.seg; a.seed_key = seed_b;
+            const DecideArgs a = decide_args(pr, u, reinterpret_cast<u32x4 *>(dev + o_out) + u.lo, dev, pe);
             HIP_TRY(playout_launch(b->segs[u.seg].dev.kind, dim3((u.cnt + 63u) / 64u), s, b, a));
         }
     }

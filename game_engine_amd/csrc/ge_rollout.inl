@@ -625,13 +625,17 @@ template <int ACT> RollArgs<ACT> rollout_form_args(const RolloutArgs &base, char
     return a;
 }
 
+// a.n entries the host has counted, one block per (entry, 64 replicas)
+template <int ACT> hipError_t rollout_launch_counted(const ge_batch *b, hipStream_t s, const RollArgs<ACT> &a) {
+    const dim3 grid(a.n * a.waves);                         // <= 2^26 blocks (n * R <= 2^26)
+    const uint32_t kind = b->segs[a.seg].dev.kind;
+    return b->generic ? rollout_launch<1, ACT>(kind, grid, s, b, a) : rollout_launch<0, ACT>(kind, grid, s, b, a);
+}
+
 // segment g's entries [lo, lo + cnt) of the chunk staged at dev, as form ACT
 template <int ACT>
 hipError_t rollout_launch_form(const ge_batch *b, hipStream_t s, const RolloutArgs &base, char *dev, const RollStage &o, uint32_t lo) {
-    const RollArgs<ACT> a = rollout_form_args<ACT>(base, dev, o, lo);
-    const dim3 grid(base.n * base.waves);                   // <= 2^26 blocks (n * R <= 2^26)
-    const uint32_t kind = b->segs[base.seg].dev.kind;
-    return b->generic ? rollout_launch<1, ACT>(kind, grid, s, b, a) : rollout_launch<0, ACT>(kind, grid, s, b, a);
+    return rollout_launch_counted(b, s, rollout_form_args<ACT>(base, dev, o, lo));
 }
 
 // an entry's accumulator words as its ge_rollout_stats; turn_end = its first turn + max_turns

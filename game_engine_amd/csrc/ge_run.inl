@@ -234,6 +234,23 @@ static void run_decode(const ge_batch *b, const PoolEntries &en, uint32_t max_tu
     });
 }
 
+// segment g's entries of a run staged at dev (rooms at 0, keys, turns): the trace plane from off_trace, (played, stop bits) at off_out
+static RunArgs run_args(const ge_batch *b, const PoolEntries &en, uint32_t g, char *dev, size_t off_keys, size_t off_turns, size_t off_trace,
+                        size_t off_out, uint32_t max_turns, uint32_t until) {
+    const uint32_t lo = en.begin[g];
+    RunArgs a;
+    a.rooms = reinterpret_cast<const uint64_t *>(dev) + lo;
+    a.keys = reinterpret_cast<const uint64_t *>(dev + off_keys) + lo;
+    a.turns = reinterpret_cast<const uint32_t *>(dev + off_turns) + lo;
+    a.trace = reinterpret_cast<u32x4 *>(dev + off_trace);
+    a.out = reinterpret_cast<u32x2 *>(dev + off_out) + lo;
+    a.seats = b->seats;
+    a.n = en.begin[g + 1u] - lo; a.seg = g; a.seed_key = seed_key((uint32_t)b->seed, (uint32_t)(b->seed >> 32));
+    a.restart = (b->flags & GE_FLAG_RESTART) ? 1u : 0u;
+    a.max_turns = max_turns; a.until = until; a.n_all = (uint32_t)en.size(); a.first = lo;
+    return a;
+}
+
 static int run_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns, uint32_t max_turns,
                           uint32_t until, uint32_t *played, uint32_t *stopped, ge_turn_event *events, ge_room_view *views, size_t views_cap_bytes) {
     if (n == 0) return GE_OK;
@@ -257,21 +274,10 @@ static int run_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const 
     HIP_TRY(hipMemcpyAsync(dev, host, off_out, hipMemcpyHostToDevice, s));
     hipEvent_t e1 = nullptr;                                      // ge_batch_kernel_time counts the launches of this call as one interval
     if ((st = timing_begin(b, s, &e1)) != GE_OK) return st;
-    const uint32_t seed_k = seed_key((uint32_t)b->seed, (uint32_t)(b->seed >> 32));
     for (uint32_t g = 0; g < (uint32_t)b->segs.size(); g++) {
-        const uint32_t lo = en.begin[g], cnt = en.begin[g + 1u] - lo;
-        if (!cnt) continue;
-        RunArgs a;
-        a.rooms = reinterpret_cast<const uint64_t *>(dev) + lo;
-        a.keys = reinterpret_cast<const uint64_t *>(dev + off_keys) + lo;
-        a.turns = reinterpret_cast<const uint32_t *>(dev + off_turns) + lo;
-        a.trace = reinterpret_cast<u32x4 *>(dev + off_trace);
-        a.out = reinterpret_cast<u32x2 *>(dev + off_out) + lo;
-        a.seats = b->seats;
-        a.n = cnt; a.seg = g; a.seed_key = seed_k;
-        a.restart = (b->flags & GE_FLAG_RESTART) ? 1u : 0u;
-        a.max_turns = max_turns; a.until = until; a.n_all = (uint32_t)n; a.first = lo;
-        const dim3 grid((cnt + 63u) / 64u);
+        if (en.begin[g + 1u] == en.begin[g]) continue;
+        const RunArgs a = run_args(b, en, g, dev, off_keys, off_turns, off_trace, off_out, max_turns, until);
+        const dim3 grid((a.n + 63u) / 64u);
         HIP_TRY(b->generic ? run_launch<1>(b->segs[g].dev.kind, grid, s, b, a) : run_launch<0>(b->segs[g].dev.kind, grid, s, b, a));
     }
     if (e1) HIP_TRY(hipEventRecord(e1, s));

@@ -2,9 +2,10 @@
 // §3g): ge_batch_step_rooms_playout turn after turn without the host in between (included at the end of ge_step.hip, behind
 // ge_run.inl: the existing kernels keep their code-object offsets).  Everything a turn does is other files' code: the checks, the
 // grouping and the staging are ge_pool.inl's and ge_run.inl's (pool_check_entries, PoolEntries, run_check), the units and passes,
-// the plan of a room and the decision are ge_playout.inl's (playout_units, playout_plan_room, ge_playout_decide), the playout is
-// ge_rollout.inl's (roll_ww / roll_tt, ACT = 2), the turn with its trace store and its stop tests is ge_run.inl's (run_ww / run_tt
-// with one turn to play), and so is the decoding of the trace plane (run_counts, run_decode).  What this file adds is the form in
+// the plan of a room, the decision and the host side of a pass - its entry block, the kernels' arguments, the rounds of §3h - are
+// ge_playout.inl's (playout_units, playout_plan_room, ge_playout_decide, PassEntries .. play_unit), the playout is ge_rollout.inl's
+// (roll_ww / roll_tt, ACT = 2), the turn with its trace store and its stop tests is ge_run.inl's (run_ww / run_tt with one turn to
+// play, run_args), and so is the decoding of the trace plane (run_counts, run_decode).  What this file adds is the form in
 // which they follow each other on the stream: three thin kernels that take what the host used to know from device memory.
 //
 // Per listed room, in device memory between the launches: its next turn (`cur`, the uploaded turns, counted up), a live flag, and
@@ -184,25 +185,15 @@ static int run_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, cons
     // one layout, each array from a 16 B boundary.  Upload: [rooms u64][keys u64][pkeys u64][cur u32][masks u32][live u32 = 1]
     // [fin 8 B = 0][entry counters u32 x units x max_turns = 0][live counts u32 x max_turns = 0].  Behind it what comes back - the
     // trace plane (64 B per room-turn) and the decision plane (16 B per room-turn) - and then what stays on the device: [one-turn
-    // out 8 B][room_first u32][room_cnt u32] and a pass's entries, as ge_batch_step_rooms_playout lays them out
-    const size_t N = (size_t)n, C = max_cap, T = max_turns;
+    // out 8 B][room_first u32][room_cnt u32] and a pass's entries
+    const size_t N = (size_t)n, T = max_turns;
     const size_t o_keys = 8 * N, o_pkeys = 16 * N, o_cur = 24 * N, o_masks = up16(o_cur + 4 * N), o_live = up16(o_masks + 4 * N);
     const size_t o_fin = up16(o_live + 4 * N), o_ctr = up16(o_fin + 8 * N), o_lcnt = up16(o_ctr + 4 * (size_t)n_units * T);
     const size_t o_up_end = up16(o_lcnt + 4 * T);
     const size_t o_trace = o_up_end, o_dec = o_trace + 64 * N * T, host_total = o_dec + 16 * N * T;
     const size_t o_one = host_total, o_rfirst = up16(o_one + 8 * N), o_rcnt = up16(o_rfirst + 4 * N);
-    RollStage o;
-    const size_t o_erooms = up16(o_rcnt + 4 * N), o_ekeys = o_erooms + 8 * C, o_eturns = o_ekeys + 8 * C;
-    o.keys = o.turns = 0;
-    o.seats = up16(o_eturns + 4 * C);
-    o.first = up16(o.seats + 4 * C);
-    o.players = up16(o.first + 4 * (C + 1u));
-    o.choices = up16(o.players + 4 * C);
-    o.status = up16(o.choices + 4 * C);
-    o.acc = up16(o.status + 4 * C);
     const bool halving = (flags & GE_PLAYOUT_HALVING) != 0u;
-    const size_t o_range = o.acc + 8 * (size_t)ROLL_STRIDE * C;   // (halving only) the entries' replica ranges, 8 B each
-    o.total = o_range + (halving ? 8 * C : 0u);
+    const PassEntries pe(up16(o_rcnt + 4 * N), max_cap, halving);
     uint32_t *host32 = nullptr;
     if ((st = io_stage(b, host_total, &host32)) != GE_OK) return st;
     unsigned char *host = reinterpret_cast<unsigned char *>(host32);
@@ -212,15 +203,13 @@ static int run_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, cons
     for (size_t i = 0; i < N; i++) { h_pkeys[i] = pkeys[order[i]]; h_masks[i] = masks[order[i]]; h_live[i] = 1u; }
     memset(host + o_fin, 0, o_up_end - o_fin);
     char *dev = nullptr;
-    if ((st = pool_scratch(b, o.total, &dev)) != GE_OK) return st;
+    if ((st = pool_scratch(b, pe.o.total, &dev)) != GE_OK) return st;
     hipStream_t s = b->last_stream;
     if ((st = order_after_previous(b, s)) != GE_OK) return st;
     HIP_TRY(hipMemcpyAsync(dev, host, o_up_end, hipMemcpyHostToDevice, s));
     hipEvent_t e1 = nullptr;                                      // ge_batch_kernel_time counts the launches of this call as one interval
     if ((st = timing_begin(b, s, &e1)) != GE_OK) return st;
-    const uint32_t seed_b = seed_key((uint32_t)b->seed, (uint32_t)(b->seed >> 32));
-    const uint32_t restart = (b->flags & GE_FLAG_RESTART) ? 1u : 0u;
-    const uint32_t waves = (n_rollouts + 63u) / 64u;
+    const PassRooms pr = pass_rooms(b, dev, o_keys, o_pkeys, o_cur, o_masks, o_rfirst, o_rcnt, flags);   // a room's turn: its `cur`
     uint32_t *d_live = reinterpret_cast<uint32_t *>(dev + o_live), *d_cur = reinterpret_cast<uint32_t *>(dev + o_cur);
     const uint32_t G = runp_group();
     uint32_t t_end = 0;                                           // turns enqueued
@@ -231,102 +220,39 @@ static int run_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, cons
             for (uint32_t p = 0; p < n_pass; p++) {
                 for (const PlayoutUnit &u : units) {              // 1. plan
                     if (u.pass != p) continue;
-                    PlanArgs a;
-                    a.rooms = reinterpret_cast<const uint64_t *>(dev) + u.lo;
-                    a.keys = reinterpret_cast<const uint64_t *>(dev + o_keys) + u.lo;
-                    a.pkeys = reinterpret_cast<const uint64_t *>(dev + o_pkeys) + u.lo;
-                    a.turns = d_cur + u.lo;
-                    a.masks = reinterpret_cast<const uint32_t *>(dev + o_masks) + u.lo;
-                    a.room_first = reinterpret_cast<uint32_t *>(dev + o_rfirst) + u.lo;
-                    a.room_cnt = reinterpret_cast<uint32_t *>(dev + o_rcnt) + u.lo;
-                    a.counter = reinterpret_cast<uint32_t *>(dev + o_ctr) + (size_t)(&u - units.data()) * T + t;
-                    a.e_rooms = reinterpret_cast<uint64_t *>(dev + o_erooms); a.e_keys = reinterpret_cast<uint64_t *>(dev + o_ekeys);
-                    a.e_turns = reinterpret_cast<uint32_t *>(dev + o_eturns); a.e_seats = reinterpret_cast<uint32_t *>(dev + o.seats);
-                    a.e_first = reinterpret_cast<uint32_t *>(dev + o.first); a.e_players = reinterpret_cast<uint32_t *>(dev + o.players);
-                    a.e_choices = reinterpret_cast<uint32_t *>(dev + o.choices); a.e_status = reinterpret_cast<int32_t *>(dev + o.status);
-                    a.n = u.cnt; a.seg = u.seg; a.seed_key = seed_b; a.restart = restart;
-                    a.full_view = (flags & GE_PLAYOUT_FULL_VIEW) ? 1u : 0u; a.e_base = u.e_base;
+                    const PlanArgs a = plan_args(pr, u, reinterpret_cast<uint32_t *>(dev + o_ctr) + (size_t)(&u - units.data()) * T + t, dev, pe);
                     const dim3 grid((u.cnt + 63u) / 64u);
-                    u32x4 *acc = reinterpret_cast<u32x4 *>(dev + o.acc);
-                    HIP_TRY(halving ? runp_launch(b->segs[u.seg].dev.kind, grid, s, b, a, d_live + u.lo, acc, reinterpret_cast<u32x2 *>(dev + o_range), n_rollouts)
+                    u32x4 *acc = reinterpret_cast<u32x4 *>(dev + pe.o.acc);
+                    HIP_TRY(halving ? runp_launch(b->segs[u.seg].dev.kind, grid, s, b, a, d_live + u.lo, acc, reinterpret_cast<u32x2 *>(dev + pe.range), n_rollouts)
                                     : runp_launch(b->segs[u.seg].dev.kind, grid, s, b, a, d_live + u.lo, acc));
                 }
                 for (const PlayoutUnit &u : units) {              // 2. the playouts, their number read on the device
                     if (u.pass != p) continue;
-                    RolloutArgs a;
-                    a.rooms = reinterpret_cast<const uint64_t *>(dev + o_erooms) + u.e_base;
-                    a.keys = reinterpret_cast<const uint64_t *>(dev + o_ekeys) + u.e_base;
-                    a.turns = reinterpret_cast<const uint32_t *>(dev + o_eturns) + u.e_base;
-                    a.acc = reinterpret_cast<unsigned long long *>(dev + o.acc) + (size_t)ROLL_STRIDE * u.e_base;
-                    a.n = u.e_cap; a.seg = u.seg; a.seed_key = seed_key((uint32_t)seed, (uint32_t)(seed >> 32));
-                    a.n_rollouts = n_rollouts; a.max_turns = pmax; a.waves = waves;
-                    a.settle_mask = rollout_settle_mask(b->segs[u.seg]);
                     const uint32_t *cnt = reinterpret_cast<const uint32_t *>(dev + o_ctr) + (size_t)(&u - units.data()) * T + t;
                     const uint32_t kind = b->segs[u.seg].dev.kind;
-                    if (!halving) {
-                        const RollArgs<2> ra = rollout_form_args<2>(a, dev, o, u.e_base);
-                        const uint64_t cap_pairs = (uint64_t)u.e_cap * waves;   // <= 2^26: the cost cap
+                    const auto launch = [&](const auto &ra) {     // the unit's capacity in pairs is <= 2^26: the cost cap
+                        const uint64_t cap_pairs = (uint64_t)ra.n * ra.waves;
                         const dim3 grid((uint32_t)(runp_capacity_grid() ? cap_pairs : std::min<uint64_t>(cap_pairs, RUNP_GRID_BLOCKS)));
-                        HIP_TRY(b->generic ? runp_launch<1>(kind, grid, s, b, ra, cnt) : runp_launch<0>(kind, grid, s, b, ra, cnt));
-                        continue;
-                    }
-                    // §3h: the rounds of this unit's segment, each in the same two grid shapes; no cut behind the last round
-                    const SegDev &sd = b->segs[u.seg].dev;
-                    const uint32_t r_max = halving_max_rounds(sd);
-                    for (uint32_t j = 0; j < r_max; j++) {
-                        a.waves = halving_waves(n_rollouts, playout_max_cands(sd), j);
-                        if (a.waves) {
-                            RollArgs<4> ra = rollout_form_args<4>(a, dev, o, u.e_base);
-                            ra.range = reinterpret_cast<const u32x2 *>(dev + o_range) + u.e_base;
-                            const uint64_t cap_pairs = (uint64_t)u.e_cap * a.waves;   // <= 2^26: no round is longer than n_rollouts
-                            const dim3 grid((uint32_t)(runp_capacity_grid() ? cap_pairs : std::min<uint64_t>(cap_pairs, RUNP_GRID_BLOCKS)));
-                            HIP_TRY(b->generic ? runp_launch<1>(kind, grid, s, b, ra, cnt) : runp_launch<0>(kind, grid, s, b, ra, cnt));
-                        }
-                        if (j + 1u == r_max) break;
-                        HalveArgs h;
-                        h.room_first = reinterpret_cast<const uint32_t *>(dev + o_rfirst) + u.lo;
-                        h.room_cnt = reinterpret_cast<const uint32_t *>(dev + o_rcnt) + u.lo;
-                        h.e_players = reinterpret_cast<const uint32_t *>(dev + o.players);
-                        h.acc = reinterpret_cast<const unsigned long long *>(dev + o.acc);
-                        h.e_range = reinterpret_cast<u32x2 *>(dev + o_range);
-                        h.n = u.cnt; h.n_rollouts = n_rollouts; h.round = j;
-                        HIP_TRY(playout_launch(dim3((u.cnt + 63u) / 64u), s, h));
-                    }
+                        return b->generic ? runp_launch<1>(kind, grid, s, b, ra, cnt) : runp_launch<0>(kind, grid, s, b, ra, cnt);
+                    };
+                    HIP_TRY(play_unit(b, s, dev, pe, pr, u, unit_rollout_args(b, dev, pe, u, u.e_cap, seed, n_rollouts, pmax), halving, launch));
                 }
                 for (const PlayoutUnit &u : units) {              // 3. decide and log
                     if (u.pass != p) continue;
-                    DecideArgs a;
-                    a.rooms = reinterpret_cast<const uint64_t *>(dev) + u.lo;
-                    a.keys = reinterpret_cast<const uint64_t *>(dev + o_keys) + u.lo;
-                    a.turns = d_cur + u.lo;
-                    a.room_first = reinterpret_cast<const uint32_t *>(dev + o_rfirst) + u.lo;
-                    a.room_cnt = reinterpret_cast<const uint32_t *>(dev + o_rcnt) + u.lo;
-                    a.e_players = reinterpret_cast<const uint32_t *>(dev + o.players);
-                    a.e_choices = reinterpret_cast<const uint32_t *>(dev + o.choices);
-                    a.acc = reinterpret_cast<const unsigned long long *>(dev + o.acc);
-                    a.out = reinterpret_cast<u32x4 *>(dev + o_dec) + N * t + u.lo;
-                    a.n = u.cnt; a.seg = u.seg; a.seed_key = seed_b;
+                    const DecideArgs a = decide_args(pr, u, reinterpret_cast<u32x4 *>(dev + o_dec) + N * t + u.lo, dev, pe);
                     HIP_TRY(playout_launch(b->segs[u.seg].dev.kind, dim3((u.cnt + 63u) / 64u), s, b, a));
                 }
             }
             for (uint32_t g = 0; g < (uint32_t)b->segs.size(); g++) {   // 4. the turn, its trace row and the rooms' state
-                const uint32_t lo = en.begin[g], cnt = en.begin[g + 1u] - lo;
-                if (!cnt) continue;
-                RunArgs a;
-                a.rooms = reinterpret_cast<const uint64_t *>(dev) + lo;
-                a.keys = reinterpret_cast<const uint64_t *>(dev + o_keys) + lo;
-                a.turns = d_cur + lo;
-                a.trace = reinterpret_cast<u32x4 *>(dev + o_trace) + 4u * N * t;
-                a.out = reinterpret_cast<u32x2 *>(dev + o_one) + lo;
-                a.seats = b->seats;
-                a.n = cnt; a.seg = g; a.seed_key = seed_b; a.restart = restart;
-                a.max_turns = 1u; a.until = until; a.n_all = (uint32_t)n; a.first = lo;
+                if (en.begin[g + 1u] == en.begin[g]) continue;
+                const RunArgs a = run_args(b, en, g, dev, o_keys, o_cur, o_trace + 64 * N * t, o_one, 1u, until);
+                const uint32_t lo = a.first;
                 RunpRooms x;
                 x.live = d_live + lo; x.cur = d_cur + lo;
                 x.fin = reinterpret_cast<u32x2 *>(dev + o_fin) + lo;
                 x.live_cnt = reinterpret_cast<uint32_t *>(dev + o_lcnt);
                 x.t = t; x.max_turns = max_turns;
-                const dim3 grid((cnt + 63u) / 64u);
+                const dim3 grid((a.n + 63u) / 64u);
                 const uint32_t kind = b->segs[g].dev.kind;
                 HIP_TRY(b->generic ? runp_launch<1>(kind, grid, s, b, a, x) : runp_launch<0>(kind, grid, s, b, a, x));
             }

@@ -72,7 +72,7 @@ static int run_forecast_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
     hipEvent_t e1 = nullptr;                                      // ge_batch_kernel_time counts the launches of this call as one interval
     if ((st = timing_begin(b, s, &e1)) != GE_OK) return st;
     const uint32_t n_seg = (uint32_t)b->segs.size();
-    const uint32_t seed_b = seed_key((uint32_t)b->seed, (uint32_t)(b->seed >> 32)), seed_f = seed_key((uint32_t)seed, (uint32_t)(seed >> 32));
+    const uint32_t seed_f = seed_key((uint32_t)seed, (uint32_t)(seed >> 32));
     const uint32_t waves = (n_rollouts + 63u) / 64u;
     // the playout arguments of segment g's entries [lo, lo + cnt): forecast keys, first turns, seats; no actions
     auto roll_args = [&](uint32_t g, uint32_t lo, uint32_t cnt, auto &a) {
@@ -97,19 +97,9 @@ static int run_forecast_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
         HIP_TRY((b->generic ? rollout_launch<1, 2>(kind, grid, s, b, a) : rollout_launch<0, 2>(kind, grid, s, b, a)));
     }
     for (uint32_t g = 0; g < n_seg; g++) {                        // 2. the run
-        const uint32_t lo = en.begin[g], cnt = en.begin[g + 1u] - lo;
-        if (!cnt) continue;
-        RunArgs a;
-        a.rooms = reinterpret_cast<const uint64_t *>(dev) + lo;
-        a.keys = reinterpret_cast<const uint64_t *>(dev + o_keys) + lo;
-        a.turns = reinterpret_cast<const uint32_t *>(dev + o_turns) + lo;
-        a.trace = reinterpret_cast<u32x4 *>(dev + o_trace);
-        a.out = reinterpret_cast<u32x2 *>(dev + o_out) + lo;
-        a.seats = b->seats;
-        a.n = cnt; a.seg = g; a.seed_key = seed_b;
-        a.restart = (b->flags & GE_FLAG_RESTART) ? 1u : 0u;
-        a.max_turns = max_turns; a.until = until; a.n_all = (uint32_t)n; a.first = lo;
-        const dim3 grid((cnt + 63u) / 64u);
+        if (en.begin[g + 1u] == en.begin[g]) continue;
+        const RunArgs a = run_args(b, en, g, dev, o_keys, o_turns, o_trace, o_out, max_turns, until);
+        const dim3 grid((a.n + 63u) / 64u);
         HIP_TRY(b->generic ? run_launch<1>(b->segs[g].dev.kind, grid, s, b, a) : run_launch<0>(b->segs[g].dev.kind, grid, s, b, a));
     }
     for (uint32_t g = 0; g < n_seg; g++) {                        // 3. points 1 .. max_turns, from the trace plane

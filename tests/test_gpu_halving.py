@@ -2,7 +2,8 @@
 word against tests/halving_ref.py (the rule restated on the oracle; its room sets hold the decisions that matter - proved on the
 CPU by tests/test_halving_host.py) and against the composition of public calls on the GPU (per round one ge_batch_rollout_seats
 call over key + o_j, the cut and the pick in numpy, inject_actions, step_rooms); the invariants of §3h; the run-on call against
-the loop of flagged steps; the refusals; Python and Node giving the same bytes; both services playing a thread alike."""
+the loop of flagged steps; a two-segment list (two units in one pass) against the per-segment calls, step and run-on; the
+refusals; Python and Node giving the same bytes; both services playing a thread alike."""
 import copy
 import json
 import os
@@ -20,6 +21,7 @@ from oracle.rng import pick
 from parity_util import assert_views_equal, oracle_rooms_as_views, views_as_oracle_rooms
 from playout_ref import SEAT_WINS, candidates, due_seats, seat_draw
 from run_ref import END, PERSON, PHASE, person_pending
+from test_gpu_playout import _all_bots, _twins
 
 pytestmark = pytest.mark.gpu
 
@@ -252,6 +254,77 @@ def test_flagged_run_is_the_loop_of_flagged_steps(until, max_turns):
         assert d.any()
         if max_turns == 9 and until == PHASE:
             assert int(p.max()) == 9 or int(p.min()) < int(p.max())
+
+
+# ---- two units in one pass: a two-segment list, the second segment's entries behind the first's (e_base != 0)
+TWO_SEGMENTS = [("ww", 6, 0), ("tt", 4, 0b10)]
+
+
+def _two_segment_list():
+    """Twin batches of both segments and a list of all their rooms, the segments interleaved, every bot seat a playout seat."""
+    b1, b2, parts, R_src = _twins(TWO_SEGMENTS, seed=19, R=16)
+    rng = np.random.default_rng(19)
+    rooms = rng.permutation(2 * R_src).astype(np.uint64)
+    keys = rng.choice(1 << 40, size=len(rooms), replace=False).astype(np.uint64)
+    turns = rng.integers(0, 50000, len(rooms)).astype(np.uint32)
+    masks = np.array(_all_bots(parts, R_src, rooms), dtype=np.uint32)
+    pkeys = rng.integers(0, 1 << 63, len(rooms)).astype(np.uint64)
+    per_segment = [np.nonzero(rooms // R_src == g)[0] for g in range(2)]
+    return b1, b2, (rooms, keys, turns, masks, pkeys), per_segment
+
+
+@pytest.mark.parametrize("halving", [True, False], ids=["halving", "plain"])
+@pytest.mark.parametrize("n", [5, 200])
+def test_two_segment_step_is_the_per_segment_steps(n, halving):
+    """A listed room's result depends only on its own record, keys and turn: the whole list in one call (two units sharing one
+    pass's arrays) equals one call per segment on a twin, byte for byte.  n = 5 and n = 200: the two replica-range regimes of
+    test_flagged_step_is_the_composition_of_public_calls."""
+    b1, b2, cols, per_segment = _two_segment_list()
+    with b1, b2:
+        ev, dec = b1.step_rooms_playout(*cols, n, 48, seed=H.PSEED, halving=halving)
+        for idx in per_segment:
+            ev_g, dec_g = b2.step_rooms_playout(*(c[idx] for c in cols), n, 48, seed=H.PSEED, halving=halving)
+            assert ev[idx].tobytes() == ev_g.tobytes() and dec[idx].tolist() == dec_g.tolist()
+            assert dec_g.any(), "a segment without a decision"
+        assert b1.read_rooms().tobytes() == b2.read_rooms().tobytes()
+
+
+def _filled_run(b, cols, n_rollouts, max_turns, until):
+    """ge_batch_run_rooms_playout under the flag into outputs that hold a pattern: (played, stopped, events, views, decided)"""
+    rooms, keys, turns, masks, pkeys = (np.ascontiguousarray(c) for c in cols)
+    n = len(rooms)
+    played, stopped = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    events = np.full((n, max_turns, EVENT_DTYPE.itemsize), 0xA5, np.uint8)
+    views = np.full((n, max_turns, ROOM_VIEW_DTYPE.itemsize), 0x5A, np.uint8)
+    decided = np.full((n, max_turns), 0xC3C3C3C3, np.uint32)
+    st = b._lib.ge_batch_run_rooms_playout(b._h, n, rooms.ctypes.data, keys.ctypes.data, turns.ctypes.data, masks.ctypes.data, pkeys.ctypes.data,
+                                           n_rollouts, 48, H.PSEED, 4, max_turns, until, played.ctypes.data, stopped.ctypes.data,
+                                           decided.ctypes.data, events.ctypes.data, views.ctypes.data, views.nbytes)
+    assert st == 0, st
+    return played, stopped, events, views, decided
+
+
+def test_two_segment_flagged_run_is_the_per_segment_runs():
+    """The same list through the run-on call under the flag, against one call per segment on a twin: turn counts, stop bits,
+    everything below `played`, the records; the slots behind `played` keep their pattern."""
+    b1, b2, cols, per_segment = _two_segment_list()
+    max_turns = 9
+    with b1, b2:
+        played, stopped, events, views, decided = _filled_run(b1, cols, 24, max_turns, PERSON | END)
+        for idx in per_segment:
+            p_g, s_g, e_g, v_g, d_g = _filled_run(b2, [c[idx] for c in cols], 24, max_turns, PERSON | END)
+            assert played[idx].tolist() == p_g.tolist() and stopped[idx].tolist() == s_g.tolist()
+            for x, k in enumerate(idx):
+                q = int(played[k])
+                assert events[k, :q].tobytes() == e_g[x, :q].tobytes() and views[k, :q].tobytes() == v_g[x, :q].tobytes(), k
+                assert decided[k, :q].tolist() == d_g[x, :q].tolist(), k
+            assert any(d_g[x, :int(p_g[x])].any() for x in range(len(idx))), "a segment without a decision"
+        for k in range(len(played)):
+            q = int(played[k])
+            assert 1 <= q <= max_turns
+            assert (events[k, q:] == 0xA5).all() and (views[k, q:] == 0x5A).all() and (decided[k, q:] == 0xC3C3C3C3).all(), k
+        assert (played < max_turns).any(), "no room stopped before the last turn: no slot behind `played`"
+        assert b1.read_rooms().tobytes() == b2.read_rooms().tobytes()
 
 
 def test_flag_values_refused_and_accepted(dsl_ww):

@@ -16,6 +16,8 @@ from parity_util import assert_views_equal, oracle_events, oracle_rooms_as_views
 from playout_ref import SEAT_WINS, candidates, due_seats, reference_step_playout, seat_draw
 from test_gpu_rollout import _dsl, _views, _words
 from test_gpu_rollout_seats import _swapped
+from test_gpu_run_playout import _all_bot_ww8
+from test_gpu_run_rooms import _batch as _run_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -285,6 +287,21 @@ def test_every_choice_is_the_argmax_of_rollout_seats(game, n, full_view):
         assert sum(bin(int(d)).count("1") for d in dec) == len(best)
     assert checked > 0
     b1.close(); b2.close()
+
+
+@pytest.mark.parametrize("halving", [False, True], ids=["plain", "halving"])
+def test_step_rooms_playout_across_the_pass_boundary(halving):
+    """1 025 rooms x 8 playout seats x 8 candidates: a capacity of 65 600 entries, two passes.  A listed room's result depends only
+    on its own record, keys and turn, so the one call equals the list given in two calls that stay inside one pass each."""
+    segs, listed, keys, turns, masks, pkeys, _ = _all_bot_ww8(1100, 1025, 5)
+    with _run_batch(segs, True) as b, _run_batch(segs, True) as twin:
+        ev, dec = b.step_rooms_playout(listed, keys, turns, masks, pkeys, 4, 8, seed=11, halving=halving)
+        halves = [twin.step_rooms_playout(listed[s], keys[s], turns[s], masks[s], pkeys[s], 4, 8, seed=11, halving=halving)
+                  for s in (slice(0, 512), slice(512, 1025))]
+        assert ev.tobytes() == np.concatenate([h[0] for h in halves]).tobytes()
+        assert dec.tolist() == np.concatenate([h[1] for h in halves]).tolist()
+        assert b.read_rooms().tobytes() == twin.read_rooms().tobytes()
+    assert dec[-64:].any(), "the second pass decided nothing"
 
 
 def test_unlisted_rooms_turn_counter_and_trace_untouched_and_determinism():
