@@ -2,7 +2,15 @@
 per ABI call - the indexed calls composed from the references restated on the oracle (run_ref, playout_ref, halving_ref,
 run_playout_ref, timeline_ref, rollout_*_ref, compare_ref), no rule logic of its own - and draw_ops, the seeded operation stream
 tests/test_gpu_abi_indexed_sequences.py replays on the GPU and tests/test_abi_model_host.py measures on the model alone: every
-operation is applied to the model when it is drawn and carries what the library must return for it."""
+operation is applied to the model when it is drawn and carries what the library must return for it.
+
+The seat plane is part of the model: Model.masks is None or one mask per batch room, mask_of(room) what every indexed reference
+plays a room under, and with a plane Model.step is the header's definition - room r takes ge_batch_step_rooms's entry (r, first
++ r, turn + t) under its own mask.  set_seats / get_seats / clear_seats, find_rooms (find_ref.find_ref over seats_ref.pending_of
+under each room's own mask) and advise_seats (advise_ref.reference_advice on a copy of the room) are composed like the other
+calls.  Their operation kinds (SEAT_OPS, SEAT_REFUSALS, the serving loop served_rounds and the switch of step paths around a
+cached graph, seat_graph_sequence) are drawn only in SEAT_SCENARIOS; the streams of SCENARIOS are what they were before these
+kinds existed."""
 import zlib
 from collections import Counter
 
@@ -19,7 +27,7 @@ GE_ERR_ARG, GE_ERR_RANGE = -1, -6
 PERSON, END, PHASE = 1, 2, 4
 M64 = (1 << 64) - 1
 EV_FIELDS = ("turn", "from_phase_id", "to_phase_id", "acted_now", "restarted", "choice")
-NONE, BY_STEP, BY_INDEXED = 0, 1, 2                              # what last changed a room (Model.last_mut)
+NONE, BY_STEP, BY_INDEXED, BY_SEAT = 0, 1, 2, 3                  # what last changed a room (Model.last_mut); BY_SEAT: a whole-batch step with a plane
 
 
 def dsl_for(game):
@@ -37,12 +45,17 @@ class Model:
         self.orcs = [Oracle(dsl_for(g), n) for g, n, _, _ in segs]
         self.lo = np.cumsum([0] + [r for _, _, r, _ in segs]).tolist()
         self.total = self.lo[-1]
+        self.masks = None                                           # the seat plane: None, or one uint32 mask per batch room
         self.reset()
 
-    def reset(self):
+    def reset(self):                                                # (the masks are configuration: a reset leaves them)
         self.rooms = [o.init_rooms(r) for o, (_, _, r, _) in zip(self.orcs, self.segs)]
         self.turn = 0
         self.last_events = None
+
+    def mask_of(self, room):
+        """The host-driven seats of a batch room: its own mask once a plane exists, else its segment's."""
+        return int(self.masks[int(room)]) if self.masks is not None else self.segs[self.seg_of(int(room))[0]][3]
 
     def seg_of(self, room):
         k = int(np.searchsorted(self.lo, room, side="right")) - 1
@@ -62,8 +75,13 @@ class Model:
         for t in range(k):                                          # turn by turn: the event trace is per turn
             row = []
             for s, o in enumerate(self.orcs):
-                o.run(self.rooms[s], self.seed, self.first + self.lo[s], self.turn, 1, threads=0, restart=self.restart,
-                      human_mask=self.segs[s][3])
+                if self.masks is None:
+                    o.run(self.rooms[s], self.seed, self.first + self.lo[s], self.turn, 1, threads=0, restart=self.restart,
+                          human_mask=self.segs[s][3])
+                else:                                               # with a plane: room r takes step_rooms's entry (r, first + r, turn) under its own mask
+                    for i in range(len(self.rooms[s])):
+                        o.run(self.rooms[s][i:i + 1], self.seed, self.first + self.lo[s] + i, self.turn, 1, threads=1, restart=self.restart,
+                              human_mask=int(self.masks[self.lo[s] + i]))
                 row.append(oracle_events(o, self.rooms[s], self.turn))
             ev.append(np.concatenate(row))
             self.turn += 1
@@ -115,7 +133,7 @@ class Model:
         for r, key, turn in zip(listed, keys, turns):
             s, i = self.seg_of(int(r))
             o, one = self.orcs[s], self.rooms[s][i:i + 1]
-            o.run(one, self.seed, int(key), int(turn), 1, threads=1, restart=self.restart, human_mask=self.segs[s][3])
+            o.run(one, self.seed, int(key), int(turn), 1, threads=1, restart=self.restart, human_mask=self.mask_of(r))
             out.append(oracle_events(o, one, int(turn))[0])
         return out
 
@@ -133,7 +151,7 @@ class Model:
         for r, key, turn in zip(listed, keys, turns):
             s, i = self.seg_of(int(r))
             p, why, ev, vw = run_ref(self.orcs[s], self.rooms[s], i, self.seed, int(key), int(turn), max_turns, until, self.restart,
-                                     self.segs[s][3])
+                                     self.mask_of(r))
             played.append(p); stopped.append(why); events.append(ev); views.append(vw)
         return np.array(played, dtype=np.uint32), np.array(stopped, dtype=np.uint32), events, views
 
@@ -146,7 +164,7 @@ class Model:
             s, i = self.seg_of(int(r))
             o = self.orcs[s]
             d = step(o, self.rooms[s], i, self.seed, int(key), int(turn), int(mask), int(pkey), pseed, R, M, full_view, self.restart,
-                     self.segs[s][3])
+                     self.mask_of(r))
             events.append(oracle_events(o, self.rooms[s][i:i + 1], int(turn))[0])
             decided.append(d)
         return events, np.array(decided, dtype=np.uint32)
@@ -157,7 +175,7 @@ class Model:
         for r, key, turn, mask, pkey in zip(listed, keys, turns, masks, pkeys):
             s, i = self.seg_of(int(r))
             p, why, ev, vw, dec = run_playout_ref(self.orcs[s], self.rooms[s], i, self.seed, int(key), int(turn), int(mask), int(pkey), pseed,
-                                                  R, M, full_view, max_turns, until, self.restart, self.segs[s][3])
+                                                  R, M, full_view, max_turns, until, self.restart, self.mask_of(r))
             played.append(p); stopped.append(why); events.append(ev); views.append(vw); decided.append(dec)
         return np.array(played, dtype=np.uint32), np.array(stopped, dtype=np.uint32), events, views, decided
 
@@ -196,6 +214,54 @@ class Model:
         from compare_ref import reference_compare
         return reference_compare(self.orc_of, listed, keys, turns, seats, actions, baseline, subjects, R, M, pseed)
 
+    # ---- the seat plane (ge_step.h, "Per-room host-driven seats"): configuration, which reset, write, write_rooms_at and the turn
+    # counter leave alone
+
+    def set_seats(self, rooms, masks):
+        """ge_batch_set_seats: the status; a refused call changes nothing, the first accepted one of n > 0 allocates the plane."""
+        rooms = [int(r) for r in rooms]
+        if not rooms:
+            return 0
+        if any(r >= self.total for r in rooms):
+            return GE_ERR_RANGE
+        if len(set(rooms)) != len(rooms):
+            return GE_ERR_ARG
+        if any(int(k) >> self.segs[self.seg_of(r)[0]][1] for r, k in zip(rooms, masks)):
+            return GE_ERR_ARG
+        if self.masks is None:
+            self.masks = np.concatenate([np.full(r, mask, dtype=np.uint32) for _, _, r, mask in self.segs])
+        self.masks[rooms] = np.asarray(masks, dtype=np.uint32)
+        return 0
+
+    def get_seats(self, first=0, count=None):
+        count = self.total - first if count is None else count
+        return np.array([self.mask_of(r) for r in range(first, first + count)], dtype=np.uint32)
+
+    def clear_seats(self):
+        self.masks = None
+
+    def find_rooms(self, first, count, want, phase_masks, cap):
+        """ge_batch_find_rooms: (the first cap hits as (room, why, pending, phase_id, segment), n_match) - find_ref.find_ref over
+        each room's facts, `pending` by seats_ref.pending_of under the room's own mask."""
+        from find_ref import find_ref
+        from run_ref import is_terminal
+        from seats_ref import pending_of
+        hits = []
+        for r in range(first, first + count):
+            s, i = self.seg_of(r)
+            o, one = self.orcs[s], self.rooms[s][i:i + 1]
+            fact = (pending_of(o, one, self.mask_of(r)) if want & PERSON else 0, bool(is_terminal(o, one)), int(o.ids[int(one["phase"][0])]))
+            why, pending, pid = find_ref([fact], want, int(phase_masks[s]) if phase_masks is not None else 0)[0]
+            if why:
+                hits.append((r, why, pending, pid, s))
+        return hits[:cap], len(hits)
+
+    def advise_seats(self, listed, keys, turns, seats, R, M, aseed, full_view):
+        """ge_batch_advise_seats: advise_ref.reference_advice of each entry on a copy of its room."""
+        from advise_ref import ADVICE_REF_DTYPE, reference_advice
+        return np.array([reference_advice(self.orc_of(r)[0], self.orc_of(r)[1].copy(), aseed, int(k), int(t), int(s), R, M, full_view)
+                         for r, k, t, s in zip(listed, keys, turns, seats)], dtype=ADVICE_REF_DTYPE)
+
 
 class TrackedModel(Model):
     """Model + what the operation stream needs to know about its own past (tests/test_abi_model_host.py reads cov): which kind
@@ -207,11 +273,15 @@ class TrackedModel(Model):
         orcs = [Oracle(dsl_for(g), n) for g, n, _, _ in segs]
         self.assign_ids = [{o.ids[i] for i, ph in enumerate(o.table.phases) if ph.effect == EFF_ASSIGN_ROLES} for o in orcs]
         self.cov = Counter()
+        self.fuse, self.had_plane_now = 1, False                    # (fuse: the batch's max_fuse, set by the generator)
         super().__init__(segs, seed, first, restart)
 
     def reset(self):
         super().reset()
         self.last_mut = np.zeros(self.total, dtype=np.uint8)
+        # rooms whose game ended and was recycled under a seat step and has not been dealt since: their next deal is the first that
+        # the other step path makes for them
+        self.seat_restarted = np.zeros(self.total, dtype=bool)
         # rooms in which a single indexed turn (ge_pool_kernel) dealt the roles over a record a whole-batch step wrote: were that
         # record's prepared deal - of the game just dealt - stored back, the next game's whole-batch deal would take it
         self.kept_deal = np.zeros(self.total, dtype=bool)
@@ -224,27 +294,55 @@ class TrackedModel(Model):
 
     def step(self, k):
         turns = []
-        for _ in range(k):
+        for t in range(k):
             super().step(1)
             e = self.last_events[:, 0]
             hit = np.concatenate([self._assigned(s, e[self.lo[s]: self.lo[s + 1]]) for s in range(len(self.orcs))])
+            if self.masks is not None:
+                # a seat step (ge_seat_step_kernel): the record's prepared deal is ignored, roles are dealt on the spot, the record is
+                # stored without a deal and the Werewolf x 12 side plane is not touched
+                self.cov["seat_step_assigns_after_step"] += int((hit & (self.last_mut == BY_STEP)).sum())
+                self.seat_restarted = (self.seat_restarted | (e["restarted"] != 0)) & ~hit
+                self.kept_deal[:] = False
+                self.last_mut[:] = BY_SEAT
+                turns.append(e)
+                continue
             self.cov["step_assigns_after_indexed"] += int((hit & (self.last_mut == BY_INDEXED)).sum())
+            self.cov["plain_step_assigns_after_seat_step"] += int((hit & (self.last_mut == BY_SEAT)).sum())
             self.cov["step_assigns_game_after_indexed_deal"] += int((hit & self.kept_deal).sum())
+            if self.fuse == 1 or (t == k - 1 and k % self.fuse == 1):   # a single-turn launch: Werewolf x 12 deals come from the side plane
+                for s, (_, n, _, _) in enumerate(self.segs):
+                    if n == 12 and self.assign_ids[s]:
+                        self.cov["restart_under_seat_step_then_plain_single_turn_deal"] += int((hit & self.seat_restarted)[self.lo[s]: self.lo[s + 1]].sum())
+            self.seat_restarted &= ~hit
             self.kept_deal &= ~hit
             self.last_mut[:] = BY_STEP
             turns.append(e)
         self.last_events = np.stack(turns, axis=1)
 
+    def set_seats(self, rooms, masks):
+        st = super().set_seats(rooms, masks)
+        self.cov["set_seats_allocates"] += int(st == 0 and len(rooms) > 0 and not self.had_plane_now)
+        self.had_plane_now = self.masks is not None
+        return st
+
+    def clear_seats(self):
+        self.cov["clear_with_plane" if self.masks is not None else "clear_without_plane"] += 1
+        super().clear_seats()
+        self.had_plane_now = False
+
     def write(self, lo, views):
         super().write(lo, views)
         self.last_mut[lo: lo + len(views)] = NONE
         self.kept_deal[lo: lo + len(views)] = False
+        self.seat_restarted[lo: lo + len(views)] = False
 
     def write_rooms_at(self, listed, views):
         super().write_rooms_at(listed, views)
         idx = np.asarray(listed, dtype=np.int64)
         self.last_mut[idx] = BY_INDEXED
         self.kept_deal[idx] = False
+        self.seat_restarted[idx] = False
 
     def _note(self, room, events, call):
         """The turns indexed call `call` played on a room.  indexed_assigns_after_step counts a step_rooms entry or a run whose
@@ -254,7 +352,7 @@ class TrackedModel(Model):
         room = int(room)
         s, _ = self.seg_of(room)
         ev = np.array(events).reshape(-1)
-        single = call in ("step_rooms", "hosted_threads", "step_rooms_playout")
+        single = call in ("step_rooms", "hosted_threads", "step_rooms_playout", "served_rounds")
         first = bool(self._assigned(s, ev[:1])[0])
         if self.last_mut[room] == BY_STEP and first:
             self.cov["indexed_assigns_after_step"] += int(call in ("step_rooms", "run_rooms", "run_rooms_playout"))
@@ -262,9 +360,19 @@ class TrackedModel(Model):
         if not single:
             self.kept_deal[room] = False
         self.cov["indexed_restarted"] += int(ev["restarted"].sum())
+        if self._assigned(s, ev).any():
+            self.seat_restarted[room] = False
         self.last_mut[room] = BY_INDEXED
 
     def step_rooms(self, listed, keys, turns, call="step_rooms"):
+        if self.masks is not None:                                  # masks_matter: the same turn under the segment's mask gives another record
+            for r, key, turn in zip(listed, keys, turns):
+                s, i = self.seg_of(int(r))
+                if self.mask_of(r) != self.segs[s][3]:
+                    own, seg = self.rooms[s][i:i + 1].copy(), self.rooms[s][i:i + 1].copy()
+                    self.orcs[s].run(own, self.seed, int(key), int(turn), 1, threads=1, restart=self.restart, human_mask=self.mask_of(r))
+                    self.orcs[s].run(seg, self.seed, int(key), int(turn), 1, threads=1, restart=self.restart, human_mask=self.segs[s][3])
+                    self.cov["masks_matter"] += int(own.tobytes() != seg.tobytes())
         out = super().step_rooms(listed, keys, turns)
         for r, e in zip(listed, out):
             self._note(r, [e], call)
@@ -320,6 +428,23 @@ SCENARIOS = [
 ]
 SCENARIO_NAMES = [s[0] for s in SCENARIOS]
 
+# ---- the scenarios of the seat plane, ge_batch_find_rooms and ge_batch_advise_seats: the operation kinds of SEAT_OPS and
+# SEAT_REFUSALS are drawn only here, next to every kind above.  400 rooms: a partial last wavefront, set_seats lists on both sides
+# of 341 | 342 entries and a find_rooms range of 192 | 193 rooms inside one segment
+MIXED_SEGS = [(WW, 12, 102, 0b1), (TT, 4, 170, 0b11), (WW, 8, 128, 0b10), (TT, 7, 150, 0)]
+SEAT_SCENARIOS = [
+    ("seats-ww8-400-traced", [([(WW, 8, 400, 0b1)], 1, True, True)]),
+    ("seats-ww12-400-fused", [([(WW, 12, 400, 0b1)], 4, True, False)]),       # graphs and the deal side plane on the other step path
+    ("seats-tt4-400", [([(TT, 4, 400, 0b10)], 3, True, True)]),
+    ("seats-tt7-400", [([(TT, 7, 400, 0b1000000)], 8, True, False)]),         # the queue form: a wavefront probes the union of its lanes' masks
+    ("seats-mixed-4seg", [(MIXED_SEGS, 2, True, False)]),
+    ("seats-ww8-generic-400", [([(WW_GENERIC, 8, 400, 0b10)], 2, True, False)]),   # the GENERIC seat-step, find and advise kernels
+    # the first batch gets a plane; the second, alive beside it, never does and behaves as before
+    ("seats-two-batches", [([(WW, 8, 400, 0b1)], 4, True, False), ([(TT, 4, 120, 0b10), (WW, 12, 90, 0b1)], 1, True, True)]),
+]
+SEAT_SCENARIO_NAMES = [s[0] for s in SEAT_SCENARIOS]
+ALL_SCENARIOS = SCENARIOS + SEAT_SCENARIOS
+
 OLD_OPS = {"step": 6, "read": 2, "read_part": 2, "write": 3, "inject": 2, "inject_many": 3, "reset": 2, "set_turn": 2, "summary": 2,
            "events": 2}
 INDEXED_OPS = ["step_rooms", "read_rooms_at", "write_rooms_at", "run_rooms", "run_rooms_playout", "run_rooms_forecast",
@@ -327,6 +452,15 @@ INDEXED_OPS = ["step_rooms", "read_rooms_at", "write_rooms_at", "run_rooms", "ru
                "rollout_beliefs", "rollout_compare", "hosted_threads"]
 REFUSALS = ["refuse_repeat", "refuse_range", "refuse_turn", "refuse_view"]
 TIMING_OPS = {"set_timing": 3, "kernel_time": 2, "timed_steps": 3}
+SEAT_OLD_OPS = {"step": 5, "read": 1, "read_part": 1, "write": 2, "inject": 1, "inject_many": 2, "reset": 1, "set_turn": 1, "summary": 1,
+                "events": 1}
+SEAT_TIMING_OPS = {"set_timing": 2, "kernel_time": 1, "timed_steps": 2}
+SEAT_OPS = {"set_seats": 4, "get_seats": 2, "clear_seats": 2, "find_rooms": 5, "advise_seats": 3, "served_rounds": 2}
+# the new refusals, one call of each kind a case; which of its forms a case draws goes round with the case
+SEAT_REFUSALS = {"refuse_set_seats": ("range", "repeat", "mask_bit"),
+                 "refuse_find_rooms": ("want_zero", "unknown_bit", "beyond", "phase_bit"),
+                 "refuse_advise_seats": ("seat_zero", "seat_above", "turn_overflow"),
+                 "refuse_playout_seat": ("step_rooms_playout", "run_rooms_playout")}
 MUTATING_INDEXED = {"hosted_threads", "step_rooms", "write_rooms_at", "run_rooms", "run_rooms_playout", "run_rooms_forecast", "step_rooms_playout",
                     "step_rooms_playout_halving"}
 
@@ -343,6 +477,23 @@ def deck():
     d += REFUSALS
     for k, c in TIMING_OPS.items():
         d += [k] * c
+    return d
+
+
+def seat_deck(rng, fuzz_seed):
+    """The operations of a seat-plane case before the shuffle: every kind of deck() (the whole-batch kinds and the indexed calls
+    fewer times: they have their own scenarios), the kinds of SEAT_OPS, one of each new refusal and one seat_graph_sequence
+    (draw_ops).  Shuffled here, then the set_seats and clear_seats put in an order in which the first of
+    them allocates the plane, a clear_seats meets a plane and the last set_seats allocates a plane again."""
+    d = []
+    for k, c in list(SEAT_OLD_OPS.items()) + list(SEAT_TIMING_OPS.items()) + list(SEAT_OPS.items()):
+        d += [k] * c
+    d += INDEXED_OPS + REFUSALS[fuzz_seed % 2::2] + list(SEAT_REFUSALS) + ["seat_graph_sequence"]
+    rng.shuffle(d)
+    at = [i for i, k in enumerate(d) if k in ("set_seats", "clear_seats")]
+    order = ["set_seats"] + [str(k) for k in rng.permutation(["set_seats", "set_seats", "clear_seats"])] + ["clear_seats", "set_seats"]
+    for i, k in zip(at, order):
+        d[i] = k
     return d
 
 
@@ -377,6 +528,9 @@ class _Draw:
     def __init__(self, spec, seed, first, fuzz_seed):
         self.segs, self.fuse, self.restart, self.trace = spec
         self.m = TrackedModel(self.segs, seed, first, self.restart)
+        self.m.fuse = self.fuse
+        self.seatable, self.had_plane = True, False                 # may get a seat plane; has or had one
+        self.graphs, self.seat_moved, self.prev_big = [], False, False   # the n_turns replayed as graphs; seat steps since the last replay
         self.snapshots = []
         self.nmax = max(n for _, n, _, _ in self.segs)
         self.timing = False
@@ -397,7 +551,11 @@ def _ends_soon(rng, m, turns):
     for s, o in enumerate(m.orcs):
         idx = rng.permutation(len(m.rooms[s]))[:1024]
         trial = m.rooms[s][idx].copy()
-        o.run(trial, m.seed, 0, 0, turns, threads=0, restart=False, human_mask=m.segs[s][3])
+        if m.masks is None:
+            o.run(trial, m.seed, 0, 0, turns, threads=0, restart=False, human_mask=m.segs[s][3])
+        else:                                                       # each room without its own people
+            for j, i in enumerate(idx):
+                o.run(trial[j:j + 1], m.seed, j, 0, turns, threads=1, restart=False, human_mask=m.mask_of(m.lo[s] + int(i)))
         done = np.array([not ph.branches for ph in o.table.phases])[trial["phase"]]
         out.append(m.lo[s] + idx[done & ~_terminal(m)[m.lo[s] + idx]])
     return np.concatenate(out)
@@ -441,8 +599,7 @@ def _entries(rng, m, n, distinct=True, last_fit=None, far=True, ends_within=0):
 
 
 def _bots(m, room):
-    s, _ = m.seg_of(int(room))
-    _, n, _, mask = m.segs[s]
+    n, mask = m.segs[m.seg_of(int(room))[0]][1], m.mask_of(room)    # (the room's own people once the batch has a seat plane)
     return [c for c in range(n) if not (mask >> c) & 1]
 
 
@@ -453,6 +610,8 @@ def _masks(rng, m, listed, whole=(), none_every=4):
     for k, r in enumerate(listed):
         if k % none_every != none_every - 1 or k in whole:
             bots = _bots(m, r)
+            if not bots:                                            # (a room whose every seat is a person's: no playout seat)
+                continue
             for c in rng.choice(bots, size=len(bots) if k % 2 or k in whole else min(len(bots), int(rng.integers(1, 3))), replace=False):
                 out[k] |= np.uint32(1 << int(c))
     return out
@@ -468,7 +627,7 @@ def _prefer_deciders(rng, d, listed, keys, turns):
     for k in range(0, len(listed), 1 if len(listed) <= 5 else 2):
         for r in rng.integers(0, m.total, 16):
             o, rec = m.orc_of(r)
-            due = [] if int(r) in used else due_seats(o, rec, m.seed, int(keys[k]), int(turns[k]), d.restart, m.segs[m.seg_of(int(r))[0]][3])
+            due = [] if int(r) in used else due_seats(o, rec, m.seed, int(keys[k]), int(turns[k]), d.restart, m.mask_of(r))
             if any(len(candidates(o, rec, seat)) >= 2 for seat in due):
                 used.add(int(r))
                 found.add(k)
@@ -505,7 +664,7 @@ def _hosted_threads(rng, d, n=12, max_rounds=70):
         inj = ([], [], [])
         for r in rooms[idx]:
             s, i = m.seg_of(int(r))
-            o, mask = m.orcs[s], m.segs[s][3]
+            o, mask = m.orcs[s], m.mask_of(r)
             for seat in [c + 1 for c in range(o.n) if (mask >> c) & 1]:
                 for choice in rng.permutation(max(o.n, 3)) + 1:
                     if o.inject(m.rooms[s][i:i + 1].copy(), 0, seat, int(choice)):
@@ -562,11 +721,30 @@ def _pairs(rng, choices, budget, n_of=lambda n: n):
 def draw_ops(name, fuzz_seed):
     """The operations of case (scenario, fuzz seed), in order, each already applied to the model of its batch.  Yields
     (op, draws): draws[op.bi].m is that model as the operation left it."""
-    specs = dict(SCENARIOS)[name]
+    for op, draws in _draw_stream(name, fuzz_seed):
+        d = draws[op.bi]
+        # a set_seats directly behind a multi-launch step that nothing has waited for
+        d.m.cov["set_seats_behind_graph_step"] += int(op.kind == "set_seats" and d.prev_big)
+        d.prev_big = op.kind == "step" and op.a["launches"][-1] >= 4
+        d.had_plane |= d.m.masks is not None
+        yield op, draws
+
+
+def _draw_stream(name, fuzz_seed):
+    specs = dict(ALL_SCENARIOS)[name]
+    seat = name in SEAT_SCENARIO_NAMES
     rng = np.random.default_rng(zlib.crc32(name.encode()) + fuzz_seed)
     draws = [_Draw(spec, 777 + fuzz_seed + 1000 * j, (1 << 30) + 3 + (j << 33), fuzz_seed) for j, spec in enumerate(specs)]
-    kinds = deck()
-    rng.shuffle(kinds)
+    if seat:
+        kinds = seat_deck(rng, fuzz_seed)
+        for d in draws[1:]:
+            d.seatable = False                                      # seats-two-batches: the second batch never has a plane
+        case = 2 * SEAT_SCENARIO_NAMES.index(name) + fuzz_seed
+        for d in draws:
+            d.case = case
+    else:
+        kinds = deck()
+        rng.shuffle(kinds)
     untraced = [j for j, d in enumerate(draws) if not d.trace]
     if untraced:
         # twice a case: indexed call -> step of four launches or more (the graph replay, not waited for) -> indexed call, all
@@ -586,7 +764,48 @@ def draw_ops(name, fuzz_seed):
         elif not hold:
             bi = int(rng.integers(len(draws)))
         hold = max(0, hold - 1)
+        if (kind in SEAT_OPS or kind in SEAT_REFUSALS or kind == "seat_graph_sequence") and not draws[bi].seatable:
+            bi = 0
         d = draws[bi]
+        if kind == "seat_graph_sequence":
+            # the switch of step paths around a cached graph: a step of K turns (four launches or more, timing off, no plane: a graph
+            # replay) -> set_seats directly behind it -> steps with the plane, which move the turn counter and not the graphs'
+            # device turn word -> clear_seats -> single turns (a Werewolf x 12 deal then comes from the side plane) -> K turns again
+            if d.m.masks is not None:
+                yield _draw_seat(rng, "clear_seats", bi, d), draws
+            if d.timing:
+                yield _draw_one(rng, name, "set_timing", bi, d), draws
+            K = max(4, 3 * d.fuse + 1)
+            parts = ([K], "set_seats", [d.fuse + 1, int(rng.integers(1, d.fuse + 1))], "clear_seats", [1, 1, 1], [K])
+            if d.trace:
+                # a traced batch (a step holds one launch, no graphs): games all over their course, a turn without a plane, turns
+                # with one - roles dealt over records the other path stored -, and turns without one again
+                parts = ("adopt", [d.fuse], "set_seats", [d.fuse] * -(-6 // d.fuse), "clear_seats", [d.fuse] * -(-6 // d.fuse))
+            for part in parts:
+                if part == "adopt":
+                    yield _adopt_played(rng, bi, d), draws
+                elif isinstance(part, str):
+                    yield _draw_seat(rng, part, bi, d), draws
+                else:
+                    op = Op("step", bi)
+                    _apply_steps(op, d, part)
+                    d.pure = False
+                    yield op, draws
+            continue
+        if kind == "served_rounds" and d.m.masks is None:          # the serving loop runs on a batch with a plane
+            yield _draw_seat(rng, "set_seats", bi, d), draws
+        if seat and kind in INDEXED_OPS and d.seatable and d.m.masks is None and rng.random() < .6:
+            yield _draw_seat(rng, "set_seats", bi, d), draws        # the indexed calls of these scenarios mostly meet a plane
+        if kind == "find_rooms" and _terminal(d.m).sum() < 3:      # GE_FIND_END has something to find
+            yield _write_ended(rng, bi, d), draws
+        if kind in SEAT_OPS or kind in SEAT_REFUSALS:
+            op = _draw_seat(rng, kind, bi, d)
+            yield op, draws
+            if kind == "clear_seats" and op.a["plane"]:             # ... and once more, now without a plane: nothing to do
+                yield _draw_seat(rng, "clear_seats", bi, d), draws
+            if kind in ("set_seats", "clear_seats"):                # the step path just switched: a few turns on the other one
+                yield _advance(rng, name, bi, d, int(rng.integers(2, 6))), draws
+            continue
         if kind == "graph_step":
             late = name == "ww12-300-late-plane" and not d.plane_ready
             op = Op("step", bi)
@@ -624,6 +843,25 @@ def _played_views(rng, d):
     return np.concatenate(parts)
 
 
+def _write_ended(rng, bi, d):
+    """A write_rooms_at of a few rooms with their own games played to the end on the oracle (every seat by the policy, nothing
+    recycled): finished games that wait for the next turn of a restarting batch."""
+    m = d.m
+    rooms, views = [], []
+    for r in rng.permutation(m.total)[:8]:
+        o, rec = m.orc_of(r)
+        one = np.array([rec])
+        o.run(one, m.seed, int(rng.integers(0, 1 << 40)), int(rng.integers(0, 300)), 600, threads=1, restart=False, human_mask=0)
+        if not o.table.phases[int(one["phase"][0])].branches:
+            rooms.append(int(r))
+            views.append(oracle_rooms_as_views(o, one)[0])
+    assert rooms
+    op = Op("write_rooms_at", bi, rooms=np.array(rooms, dtype=np.uint64), views=np.ascontiguousarray(np.array(views, dtype=views[0].dtype)))
+    m.write_rooms_at(op.a["rooms"], op.a["views"])
+    op.listed = op.a["rooms"]
+    return op
+
+
 def _adopt_played(rng, bi, d):
     """A write_rooms of the whole batch with _played_views."""
     op = Op("write", bi, lo=0, views=_played_views(rng, d))
@@ -648,9 +886,19 @@ def _advance(rng, name, bi, d, turns):
 def _apply_steps(op, d, ks):
     op.a["ks"] = ks
     op.a["launches"] = [-(-k // d.fuse) for k in ks]
+    # with a seat plane a step launches once per segment and per max_fuse turns (ge_step.h), plainly; without one, a call of four
+    # launches or more replays a graph cached by its n_turns (eight of them, the oldest evicted) unless timing is on
+    op.a["per_launch"] = len(d.segs) if d.m.masks is not None else 1
     for k in ks:
+        if d.m.masks is not None:
+            d.seat_moved = True
+        elif -(-k // d.fuse) >= 4 and not d.timing:
+            d.m.cov["graph_replay_after_seat_steps"] += int(d.seat_moved and k in d.graphs)
+            if k not in d.graphs:
+                d.graphs = (d.graphs + [k])[-8:]
+            d.seat_moved = False
         d.m.step(k)
-    d.launches += sum(op.a["launches"])
+    d.launches += sum(op.a["launches"]) * op.a["per_launch"]
 
 
 def _draw_one(rng, name, kind, bi, d):
@@ -876,3 +1124,223 @@ def _views_for(rng, d, listed):
         s, _ = m.seg_of(int(min(int(r), m.total - 1)))
         out.append(srcs[int(rng.choice(4, p=[.35, .25, .2, .2]))][int(rng.integers(m.lo[s], m.lo[s + 1]))])
     return np.ascontiguousarray(np.array(out, dtype=srcs[0].dtype))
+
+
+# ---- the kinds of the seat-plane scenarios
+
+# ge_batch_set_seats stages 12 n bytes (8 n of rooms, 4 n of masks): 341: 4 092 | 342: 4 104, either side of the scratch's first size.
+# ge_batch_find_rooms over one segment's range with cap >= count, by the layout in find_rooms_impl (result words and wavefront
+# counts padded to whole wavefronts, offsets, a total, 16 B a hit): 192 rooms: 768 + 12 -> 784, + 24 = 808, + 8 -> 816, + 3 072 =
+# 3 888 | 193 rooms: 1 024 + 16 = 1 040, + 32 = 1 072, + 8 -> 1 088, + 3 088 = 4 176
+SET_SEATS_SIDES, FIND_SIDES = (341, 342), (192, 193)
+ADVISE_TURNS = (0, 5, 24)
+ROLLOUT_BUDGET = 520                                               # the oracle's playouts a call, as the rollout_* kinds
+
+
+def _seat_masks_for(rng, m, rooms):
+    """seats_ref.seat_masks over each segment (the six forms from lane to lane, rotated by a drawn offset), read at the rooms."""
+    from seats_ref import seat_masks
+    whole = np.concatenate([np.roll(seat_masks(n, r, rng), int(rng.integers(0, 6))) for _, n, r, _ in m.segs])
+    return whole[np.asarray(rooms, dtype=np.int64)].astype(np.uint32)
+
+
+def _phase_masks(rng, m):
+    """A mask word per segment: about half of the phase ids its rooms stand in and one id of the table that no room is in (ids
+    a mask word may name: below 32 and below the table's phase count)."""
+    out = []
+    for o, rooms in zip(m.orcs, m.rooms):
+        ok = [int(p) for p in o.ids if p < min(32, len(o.table.phases))]
+        here = sorted({int(o.ids[int(r)]) for r in np.unique(rooms["phase"])} & set(ok))
+        absent = [p for p in ok if p not in here]
+        pick = [int(p) for p in rng.permutation(here)[: max(1, len(here) // 2)]] + [int(p) for p in rng.permutation(absent)[:1]]
+        out.append(sum(1 << p for p in pick))
+    return np.array(out, dtype=np.uint32)
+
+
+def _find_range(rng, m, shape, side):
+    """(first, count): 0 the whole batch; 1 inside one segment, 192 | 193 rooms in turn (where none is that large: as 2); 2 across a
+    segment boundary (one segment: as 3); 3 a random range."""
+    if shape == 0:
+        return 0, m.total
+    big = [s for s in range(len(m.segs)) if m.segs[s][2] >= FIND_SIDES[1]]
+    if shape == 1 and big:
+        s, n = int(rng.choice(big)), FIND_SIDES[side % 2]
+        return m.lo[s] + int(rng.integers(0, m.segs[s][2] - n + 1)), n
+    if shape in (1, 2) and len(m.segs) > 1:
+        s = int(rng.integers(1, len(m.segs)))
+        first = m.lo[s] - int(rng.integers(1, min(70, m.segs[s - 1][2]) + 1))
+        return first, int(rng.integers(m.lo[s] - first + 1, min(m.total - first, 200) + 1))
+    first = int(rng.integers(0, m.total - 1))
+    return first, int(rng.integers(1, m.total - first + 1))
+
+
+def _advise_entries(rng, m, n):
+    """n (room, seat) pairs, repeats allowed: at least half of them seats that can act now (advise_ref.legal_mask on the model, as
+    _prefer_deciders looks for deciders), those with a choice to make first; the others drawn blindly (most are refused)."""
+    from advise_ref import legal_mask
+    some, many = [], []
+    for r in rng.permutation(m.total)[:48]:
+        o, rec = m.orc_of(r)
+        for seat in range(1, o.n + 1):
+            legal = legal_mask(o, rec, seat)
+            if legal:
+                (many if bin(legal).count("1") >= 2 else some).append((int(r), seat))
+    found = [many[int(i)] for i in rng.permutation(len(many))] + [some[int(i)] for i in rng.permutation(len(some))]
+    pairs = found[: -(-n // 2)]
+    while len(pairs) < n:
+        r = int(rng.integers(0, m.total))
+        pairs.append(pairs[0] if pairs and rng.random() < .2 else (r, int(rng.integers(1, m.orc_of(r)[0].n + 1))))
+    return [pairs[int(i)] for i in rng.permutation(len(pairs))]
+
+
+def _n_choices(m, room):
+    o = m.orc_of(room)[0]
+    return o.n if o.table.pack == 1 else 3
+
+
+def _draw_seat(rng, kind, bi, d):
+    m = d.m
+    op = Op(kind, bi)
+    a = op.a
+    call = d.calls[kind]
+    d.calls[kind] += 1
+    d.pure = False
+    if kind == "set_seats":
+        # the case's calls go round: the whole batch in shuffled order, the two sides of the threshold, one entry or a few
+        n = [m.total, SET_SEATS_SIDES[0], SET_SEATS_SIDES[1], int(rng.choice([1, int(rng.integers(2, 40))]))][(2 * d.fuzz_seed + call) % 4]
+        rooms = rng.permutation(m.total)[: min(n, m.total)].astype(np.uint64)
+        a.update(rooms=rooms, masks=_seat_masks_for(rng, m, rooms), allocates=m.masks is None)
+        assert m.set_seats(rooms, a["masks"]) == 0
+        op.listed = rooms
+    elif kind == "get_seats":
+        first = int(rng.integers(0, m.total))
+        count = [int(rng.integers(1, m.total - first + 1)), 0, m.total - first][(d.fuzz_seed + call) % 3]
+        a.update(first=first, count=count)
+        op.want = m.get_seats(first, count)
+        op.listed = np.zeros(0, dtype=np.uint64)
+    elif kind == "clear_seats":
+        a["plane"] = m.masks is not None
+        m.clear_seats()
+    elif kind == "find_rooms":
+        a["calls"] = []
+        rooms = []
+        for j in range(2):
+            q = 2 * call + j + d.fuzz_seed
+            want = (3 * q + d.fuzz_seed) % 7 + 1                    # all seven combinations within seven calls
+            shape = q % 4
+            first, count = _find_range(rng, m, shape, q // 4 + d.fuzz_seed)
+            masks = _phase_masks(rng, m) if want & PHASE else None
+            hits, n_match = m.find_rooms(first, count, want, masks, count)
+            # cap: at least count (always so for the 192 | 193 ranges), above n_match, below it (the scan is resumed), 0
+            mode = 0 if shape == 1 else 1 + (q // 4 + q) % 3
+            cap = [count + int(rng.integers(0, 3)), n_match + int(rng.integers(1, 4)), max(1, -(-n_match // 3)) if n_match >= 2 else 0, 0][mode]
+            a["calls"].append(dict(first=first, count=count, want=want, masks=masks, cap=cap, hits=hits, n_match=n_match))
+            rooms += [h[0] for h in hits[:16]]
+        op.listed = np.array(rooms, dtype=np.uint64)
+    elif kind == "advise_seats":
+        M = int(ADVISE_TURNS[(d.fuzz_seed + call) % 3])
+        full = bool((d.fuzz_seed + call) % 2)
+        cmax = max(n if g != TT else 3 for g, n, _, _ in m.segs) + 1   # the most entries of work one listed entry can cost
+        R = int(rng.choice([r for r in N_ROLLOUTS if cmax * r <= ROLLOUT_BUDGET]))
+        n = int(rng.integers(1, min(40, ROLLOUT_BUDGET // (cmax * R)) + 1))
+        pairs = _advise_entries(rng, m, n)
+        rooms = np.array([r for r, _ in pairs], dtype=np.uint64)
+        seats = np.array([s for _, s in pairs], dtype=np.uint32)
+        keys = rng.integers(0, 1 << 40, n).astype(np.uint64)
+        keys[int(rng.integers(n))] = np.uint64(M64 - int(rng.integers(0, 40)))
+        turns = rng.integers(0, 300, n).astype(np.uint32)
+        turns[0] = 0xFFFFFFFF - M                                    # the last turn that fits
+        aseed = int(rng.integers(0, 1 << 40))
+        a.update(rooms=rooms, keys=keys, turns=turns, seats=seats, R=R, M=M, seed=aseed, full_view=full)
+        op.want = m.advise_seats(rooms, keys, turns, seats, R, M, aseed, full)
+        op.listed = rooms
+    elif kind == "served_rounds":
+        # find who waits, advise them, inject the advice, step them: each served room under a key and a clock of its own
+        a.update(R=1, M=int(rng.choice([5, 24])), seed=int(rng.integers(0, 1 << 40)), rounds=[])
+        keys, clocks, served = {}, {}, []
+        for _ in range(3):
+            hits, n_match = m.find_rooms(0, m.total, PERSON, None, m.total)
+            pick = sorted(int(i) for i in rng.permutation(len(hits))[:8])
+            rooms = np.array([hits[i][0] for i in pick], dtype=np.uint64)
+            seats = np.array([(hits[i][2] & -hits[i][2]).bit_length() for i in pick], dtype=np.uint32)   # the lowest pending seat
+            for r in rooms:
+                keys.setdefault(int(r), int(rng.integers(0, 1 << 40)))
+                clocks.setdefault(int(r), int(rng.integers(0, 300)))
+            k = np.array([keys[int(r)] for r in rooms], dtype=np.uint64)
+            t = np.array([clocks[int(r)] for r in rooms], dtype=np.uint32)
+            advice = m.advise_seats(rooms, k, t, seats, a["R"], a["M"], a["seed"], False)
+            for r, seat, adv in zip(rooms, seats, advice):
+                assert adv["status"] == 0 and m.inject(int(r), int(seat), int(adv["best"])) == 0, (int(r), int(seat), adv)
+                clocks[int(r)] += 1
+            events = m.step_rooms(rooms, k, t, call="served_rounds")
+            a["rounds"].append(dict(hits=hits, rooms=rooms, keys=k, turns=t, seats=seats, advice=advice, events=events))
+            served += rooms.tolist()
+        op.listed = np.array(sorted(set(served)), dtype=np.uint64)
+    else:
+        how = SEAT_REFUSALS[kind][d.case % len(SEAT_REFUSALS[kind])]
+        a["how"] = how
+        op.status = GE_ERR_ARG
+        op.listed = np.zeros(0, dtype=np.uint64)
+        if kind == "refuse_set_seats":
+            rooms = rng.permutation(m.total)[: int(rng.integers(3, 9))].astype(np.uint64)
+            masks = _seat_masks_for(rng, m, rooms)
+            j = int(rng.integers(len(rooms)))
+            if how == "range":
+                rooms[j] = m.total
+                op.status = GE_ERR_RANGE
+            elif how == "repeat":
+                rooms[j] = rooms[(j + 1) % len(rooms)]
+            else:
+                masks[j] |= np.uint32(1 << m.segs[m.seg_of(int(rooms[j]))[0]][1])
+            a.update(rooms=rooms, masks=masks)
+            assert m.set_seats(rooms, masks) == op.status
+            op.listed = rooms[rooms < m.total]
+        elif kind == "refuse_find_rooms":
+            a.update(first=int(rng.integers(0, m.total - 8)), count=8, want=PERSON | END, masks=None)
+            if how == "want_zero":
+                a["want"] = 0
+            elif how == "unknown_bit":
+                a["want"] = 8 | int(rng.integers(0, 8))
+            elif how == "beyond":
+                a.update(first=m.total - 7)
+                op.status = GE_ERR_RANGE
+            else:
+                masks = _phase_masks(rng, m)
+                s = int(rng.integers(len(m.segs)))
+                assert len(m.orcs[s].table.phases) < 32
+                masks[s] |= np.uint32(1 << len(m.orcs[s].table.phases))
+                a.update(want=PHASE | END, masks=masks)
+        elif kind == "refuse_advise_seats":
+            pairs = _advise_entries(rng, m, int(rng.integers(2, 6)))
+            rooms = np.array([r for r, _ in pairs], dtype=np.uint64)
+            seats = np.array([s for _, s in pairs], dtype=np.uint32)
+            turns = rng.integers(0, 300, len(rooms)).astype(np.uint32)
+            j = int(rng.integers(len(rooms)))
+            if how == "seat_zero":
+                seats[j] = 0
+            elif how == "seat_above":
+                seats[j] = m.orc_of(rooms[j])[0].n + 1
+            else:
+                turns[j] = 0xFFFFFFFF - 5 + 1
+                op.status = GE_ERR_RANGE
+            a.update(rooms=rooms, keys=rng.integers(0, 1 << 40, len(rooms)).astype(np.uint64), turns=turns, seats=seats, R=4, M=5)
+            op.listed = rooms
+        else:
+            # room y: a seat handed to a person -> a playout bit on it is refused; room x: a seat of the segment's mask handed back to
+            # the policy -> a playout bit on it is accepted (the host mirror of the room's own mask decides, not the segment's)
+            segs = [s for s in range(len(m.segs)) if m.segs[s][3]]
+            s = int(rng.choice(segs))
+            x = m.lo[s] + int(rng.integers(0, m.segs[s][2]))
+            y = int(rng.choice([r for r in rng.integers(0, m.total, 8) if int(r) != x]))
+            seat_y = int(rng.integers(0, m.segs[m.seg_of(y)[0]][1]))
+            bit_x = m.segs[s][3] & -m.segs[s][3]
+            a["set"] = (np.array([x, y], dtype=np.uint64), np.array([0, m.mask_of(y) | (1 << seat_y)], dtype=np.uint32))
+            assert m.set_seats(*a["set"]) == 0
+            keys, turns = rng.integers(0, 1 << 40, 1).astype(np.uint64), rng.integers(0, 300, 1).astype(np.uint32)
+            pkeys, pseed = rng.integers(0, 1 << 62, 1).astype(np.uint64), int(rng.integers(0, 1 << 40))
+            a.update(refused=dict(rooms=np.array([y], dtype=np.uint64), masks=np.array([1 << seat_y], dtype=np.uint32)),
+                     rooms=np.array([x], dtype=np.uint64), keys=keys, turns=turns, masks=np.array([bit_x], dtype=np.uint32), pkeys=pkeys,
+                     R=4, M=4, seed=pseed)
+            op.want = m.step_rooms_playout(a["rooms"], keys, turns, a["masks"], pkeys, 4, 4, pseed, False, False)
+            op.listed = np.array([x, y], dtype=np.uint64)
+    return op

@@ -14,7 +14,20 @@ sample of the others, and on traced batches the last step's events; at the end t
 records of every segment (no bit outside the view depends on which kernels wrote the record).  set_timing and kernel_time are
 toggled along the way: timing turns graph replay off, so the same sequence must give the same rooms; three times a case the
 launch count is read exactly over whole-batch steps alone (timed_steps), with timing on and off.  Hosted game threads
-(inject_actions then step_rooms, round after round, each room on its own key and clock) run in slots the batch has recycled."""
+(inject_actions then step_rooms, round after round, each room on its own key and clock) run in slots the batch has recycled.
+
+The seats-* scenarios put the seat plane, ge_batch_find_rooms and ge_batch_advise_seats into the same orders: set_seats (lists of
+1, a few, 341 | 342 entries and the whole batch: 12 n staged bytes on either side of 4 096), get_seats, clear_seats with and
+without a plane and a plane allocated again afterwards; find_rooms under all seven `want` sets, per-segment phase masks, ranges
+across segments and of 192 | 193 rooms (3 888 | 4 176 B of scratch), cap 0, above and below n_match (the scan is resumed and the
+concatenation compared), the slots from n_hits on pre-filled and untouched; advise_seats of seats that can act and seats that
+cannot, both views; the serving loop (find who waits, advise, inject the advice, step_rooms) on a batch with a plane; the new
+refusals with their statuses, and the playout bit a room's own mask allows where its segment's would not.  Every other kind runs
+on batches with a plane as well: ge_batch_step then launches ge_seat_step_kernel plainly (one launch per segment and per max_fuse
+turns, counted exactly), stores records without a prepared deal and leaves the Werewolf x 12 deal side plane and the graphs'
+device turn word alone, and after clear_seats the cached graphs, the side plane and the flagship kernels take over again.  After
+every operation on a batch that has or had a plane a sample of seats() is compared with the model, at the end all of it."""
+import ctypes as C
 import math
 import os
 
@@ -22,7 +35,8 @@ import numpy as np
 import pytest
 
 import abi_model as A
-from game_engine_amd import GameTable, GeError, RoomBatch
+from find_ref import hits_as_tuples
+from game_engine_amd import ROOM_HIT_DTYPE, GameTable, GeError, RoomBatch
 from parity_util import assert_records_canonical, assert_views_equal
 
 pytestmark = pytest.mark.gpu
@@ -64,6 +78,68 @@ def _refused(b, op):
         b.read_rooms_at(a["rooms"])
     else:
         b.write_rooms_at(a["rooms"], a["views"])
+
+
+_U64P = C.POINTER(C.c_uint64)
+
+
+def _find_equal(b, c, what):
+    """One drawn ge_batch_find_rooms call through the C ABI, the hit buffer pre-filled: hit for hit the model's, the slots from
+    n_hits on untouched; a call that cap truncates is resumed behind its last hit until the scan is done."""
+    got, first, left = [], c["first"], c["count"]
+    while True:
+        cap = c["cap"]
+        buf = np.full(cap + 3, 0xA5, dtype=np.uint8).repeat(16).view(ROOM_HIT_DTYPE)
+        n_hits, n_match = np.full(1, 77, dtype=np.uint64), np.full(1, 77, dtype=np.uint64)
+        st = b._lib.ge_batch_find_rooms(b._h, first, left, c["want"], c["masks"].ctypes.data if c["masks"] is not None else None,
+                                        buf.ctypes.data if cap else None, cap, n_hits.ctypes.data_as(_U64P), n_match.ctypes.data_as(_U64P))
+        k = int(n_hits[0])
+        assert st == 0 and int(n_match[0]) == c["n_match"] - len(got) and k == min(int(n_match[0]), cap, left), (what, st, n_hits, n_match, len(got))
+        assert set(buf[k:].tobytes()) == {0xA5}, f"{what}: slots from n_hits on were written"
+        got += hits_as_tuples(buf[:k])
+        if cap == 0 or k == int(n_match[0]):
+            break
+        nxt = got[-1][0] + 1                                        # resume: first = hits[n_hits - 1].room + 1
+        first, left = nxt, c["first"] + c["count"] - nxt
+    assert got == (c["hits"] if c["cap"] else []), (what, got[:4], c["hits"][:4])
+
+
+def _advice_equal(got, want, what):
+    for f in ("status", "legal", "best", "phase_id"):
+        assert got[f].tolist() == want[f].tolist(), (what, f, got[f].tolist(), want[f].tolist())
+    for f in ("finished", "wins", "score"):
+        assert got["policy"][f].tolist() == want["policy"][f].tolist(), (what, "policy", f)
+        assert got["option"][f].tolist() == want["option"][f].tolist(), (what, "option", f)
+
+
+def _seat_refusal(b, op, what):
+    """A new refusal with its documented status (the after-call checks of apply show that nothing moved); refuse_playout_seat:
+    and the accepted counterpart."""
+    a, kind = op.a, op.kind
+    if kind == "refuse_playout_seat":
+        b.set_seats(*a["set"])
+        r = a["refused"]
+    with pytest.raises(GeError) as e:
+        if kind == "refuse_set_seats":
+            b.set_seats(a["rooms"], a["masks"])
+        elif kind == "refuse_find_rooms":
+            n_hits, n_match = C.c_uint64(77), C.c_uint64(78)
+            buf = np.full(8, 0xA5, dtype=np.uint8).repeat(16).view(ROOM_HIT_DTYPE)
+            st = b._lib.ge_batch_find_rooms(b._h, a["first"], a["count"], a["want"], a["masks"].ctypes.data if a["masks"] is not None else None,
+                                            buf.ctypes.data, 8, C.byref(n_hits), C.byref(n_match))
+            assert set(buf.tobytes()) == {0xA5} and (n_hits.value, n_match.value) == (77, 78), (what, "an output was written")
+            raise GeError(st, "ge_batch_find_rooms") if st else AssertionError(what + ": accepted")
+        elif kind == "refuse_advise_seats":
+            b.advise_seats(a["rooms"], a["keys"], a["turns"], a["seats"], a["R"], a["M"])
+        elif a["how"] == "step_rooms_playout":
+            b.step_rooms_playout(r["rooms"], a["keys"], a["turns"], r["masks"], a["pkeys"], a["R"], a["M"])
+        else:
+            b.run_rooms_playout(r["rooms"], a["keys"], a["turns"], r["masks"], a["pkeys"], a["R"], a["M"], max_turns=2)
+    assert e.value.status == op.status, (what, a["how"], e.value.status)
+    if kind == "refuse_playout_seat":       # a seat of the segment's mask that the room has handed back to the policy plays out
+        ev, decided = b.step_rooms_playout(a["rooms"], a["keys"], a["turns"], a["masks"], a["pkeys"], a["R"], a["M"], seed=a["seed"])
+        assert decided.tolist() == op.want[1].tolist(), (what, "decided")
+        _events_equal(ev, op.want[0], what)
 
 
 def apply(b, op, d, what, check):
@@ -121,7 +197,8 @@ def apply(b, op, d, what, check):
         for k in a["ks"]:
             b.step(k)
         ms, launches = b.kernel_time(reset=a["reset"])
-        assert launches == a["total"] == sum(-(-k // d.fuse) for k in a["ks"]), (what, a["ks"], launches, a["total"])
+        # (with a seat plane: one launch per segment and per max_fuse turns)
+        assert launches == a["total"] == a["per_launch"] * sum(-(-k // d.fuse) for k in a["ks"]), (what, a["ks"], launches, a["total"])
         assert math.isfinite(ms) and ms >= 0 and (ms > 0 or not a["on"]), (what, ms)
     elif kind == "step_rooms":
         _events_equal(b.step_rooms(a["rooms"], a["keys"], a["turns"]), op.want, what)
@@ -168,6 +245,31 @@ def apply(b, op, d, what, check):
         _words_equal(got[0], op.want[0], what)
         if len(got) == 3:
             _words_equal(got[2], op.want[2], what + " cmp")
+    elif kind == "set_seats":
+        b.set_seats(a["rooms"], a["masks"])
+    elif kind == "get_seats":
+        got = b.seats(a["first"], a["count"])
+        assert got.dtype == np.uint32 and np.array_equal(got, op.want), what
+    elif kind == "clear_seats":
+        b.clear_seats()
+    elif kind == "find_rooms":
+        for j, c in enumerate(a["calls"]):
+            _find_equal(b, c, f"{what} call {j}")
+    elif kind == "advise_seats":
+        _advice_equal(b.advise_seats(a["rooms"], a["keys"], a["turns"], a["seats"], a["R"], a["M"], seed=a["seed"], full_view=a["full_view"]),
+                      op.want, what)
+    elif kind == "served_rounds":
+        for t, r in enumerate(a["rounds"]):
+            hits, n_match = b.find_rooms("person")
+            assert n_match == len(r["hits"]) and hits_as_tuples(hits) == r["hits"], f"{what} round {t}: who waits"
+            if not len(r["rooms"]):                                 # nobody waits
+                continue
+            advice = b.advise_seats(r["rooms"], r["keys"], r["turns"], r["seats"], a["R"], a["M"], seed=a["seed"])
+            _advice_equal(advice, r["advice"], f"{what} round {t}")
+            assert not b.inject_actions(r["rooms"], r["seats"], advice["best"]).any(), (what, t, "an advised action was refused")
+            _events_equal(b.step_rooms(r["rooms"], r["keys"], r["turns"]), r["events"], f"{what} round {t}")
+    elif kind in A.SEAT_REFUSALS:
+        _seat_refusal(b, op, what)
     elif kind in A.REFUSALS:
         with pytest.raises(GeError) as e:
             _refused(b, op)
@@ -176,6 +278,10 @@ def apply(b, op, d, what, check):
             assert str(a["rejected"]) in str(e.value), (what, str(e.value))
     else:
         raise AssertionError(kind)
+    if d.had_plane:                                                 # the masks are configuration: only set_seats and clear_seats move them
+        lo = int(check.integers(0, m.total))
+        cnt = int(check.integers(0, min(96, m.total - lo) + 1))
+        assert np.array_equal(b.seats(lo, cnt), m.get_seats(lo, cnt)), (what, "seats", lo, cnt)
     if op.listed is None:
         return
     # what an indexed call (and a refused one) must leave alone, and what it must have stored
@@ -217,10 +323,10 @@ def test_compare_refuses_a_subject_other_than_its_baselines():
         assert_views_equal(b.read_rooms(), m.views(), "the batch is only read")
 
 
-@pytest.mark.parametrize("name", A.SCENARIO_NAMES)
+@pytest.mark.parametrize("name", A.SCENARIO_NAMES + A.SEAT_SCENARIO_NAMES)
 @pytest.mark.parametrize("fuzz_seed", range(int(os.environ.get("GE_SEQ_FUZZ_SEEDS", "2"))))     # (a soak run sets more)
 def test_abi_indexed_state_machine_fuzz(name, fuzz_seed):
-    specs = dict(A.SCENARIOS)[name]
+    specs = dict(A.ALL_SCENARIOS)[name]
     tables = {g: GameTable(A.dsl_for(g)) for segs, _, _, _ in specs for g, _, _, _ in segs}
     check = np.random.default_rng(fuzz_seed)
     batches, draws = [], None
@@ -239,6 +345,7 @@ def test_abi_indexed_state_machine_fuzz(name, fuzz_seed):
                 assert got[key] == v, (what, key)
             for s, (o, rooms) in enumerate(zip(d.m.orcs, d.m.rooms)):
                 assert_records_canonical(b, s, o, rooms, f"{what} segment {s}")
+            assert np.array_equal(b.seats(), d.m.get_seats()), what + ": final seats"
     finally:
         for b in batches:
             b.close()
