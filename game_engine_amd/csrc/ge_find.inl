@@ -13,10 +13,11 @@
 //                    the wavefront's hits (mbcnt), dropping what lies at or beyond cap.  So the order of the output is the order
 //                    of the rooms, whatever the order the blocks ran in.
 //
-// The PERSON test is ge_run.inl's, reused: Werewolf - lane_ww_ctx, the row of the room's phase, ww_targets less who has acted,
-// within the human mask; Two-Truths - inject_tt on a copy of the record per seat of the human mask, choice 1.  `pending` is that
-// mask seat by seat.  The mask is the room's own where the batch has a seat plane (ge_pool.inl lane_seat_mask), so the test is per
-// lane; a wavefront whose rooms have no host-driven seat still skips it wave-uniformly.
+// The PERSON test is ge_batch_run_rooms's, as ge_pool.inl's lane type has it (Lane::pending; ge_run.inl's turn loop keeps its own
+// inline copy per game, see ge_pool.inl's header): Werewolf - the row of the room's phase, ww_targets less who has acted, within
+// the human mask; Two-Truths - inject_tt on a copy of the record per seat of the human mask, choice 1.  `pending` is that mask
+// seat by seat.  The mask is the room's own where the batch has a seat plane (ge_pool.inl lane_seat_mask), so the test is per
+// lane; a wavefront whose rooms have no host-driven seat still skips it wave-uniformly (Lane::probe).
 
 namespace {
 
@@ -45,48 +46,18 @@ __device__ __forceinline__ uint32_t find_word(uint32_t want, uint32_t pending, u
     return why ? why | (pending << 8) | (phase << 24) : 0u;
 }
 
-template <int NB, int GENERIC>
-__device__ __forceinline__ uint32_t find_ww(const SegDev &sg, const DevTable *__restrict__ tables, const FindArgs &a, uint64_t room) {
-    using L = WWLayout<NB>;
+template <int NB, bool WWP, int GENERIC>
+__device__ __forceinline__ uint32_t find_lane(const SegDev &sg, const DevTable *__restrict__ tables, const FindArgs &a, uint64_t room) {
+    using Ln = Lane<NB, WWP, GENERIC>;
+    using L = typename Ln::L;
     uint32_t w[L::WORDS];
     load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
     const uint32_t human = lane_seat_mask(sg, a.seats, room);
-    const WwCtx ctx = lane_ww_ctx<GENERIC>(sg, tables, nullptr, 0u, true, human);
-    const bool any = a.seats ? __ballot(human != 0u) != 0ull : __builtin_amdgcn_readfirstlane(human) != 0u;
-    const uint32_t ALL = (1u << sg.n_players) - 1u;
-    WWR<NB> s;
-    uint32_t cache;                                           // the record's prepared deal: no part of the test
-    ww_load_regs<NB>(w, s, cache);
-    uint32_t pending = 0;
-    if ((a.want & GE_FIND_PERSON) && any) {                   // (wave-uniform)
-        const DevRow row = lds_row<false>(ctx.rows, s.phase);
-        const uint32_t T = ww_targets<NB, true, GENERIC>(s, row, ctx, s.template get<F_ALIVE>(), ALL);
-        pending = T & ~s.acted & human;
-    }
-    return find_word(a.want, pending, s.phase, ctx.term_mask, a.row_mask);
-}
-
-template <int NB, int GENERIC>
-__device__ __forceinline__ uint32_t find_tt(const SegDev &sg, const DevTable *__restrict__ tables, const FindArgs &a, uint64_t room) {
-    using L = TTLayout<NB>;
-    uint32_t w[L::WORDS];
-    load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
-    const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
-    // the seats probed are the wavefront's: with a seat plane the union of its rooms' masks, each lane counting only its own bits
-    const uint32_t human = lane_seat_mask(sg, a.seats, room) & ((1u << sg.n_players) - 1u);
-    const uint32_t probe = a.seats ? wave_seat_union(human, NB) : (uint32_t)__builtin_amdgcn_readfirstlane(human);
-    TT<NB> s;
-    L::unpack(w, s);
-    uint32_t pending = 0;
-    if ((a.want & GE_FIND_PERSON) && probe != 0u) {           // (wave-uniform)
-        const DevRow &row = tables[sg.table_idx].rows[s.phase];
-        const DevCond &cond = tables[sg.table_idx].conds[s.phase];   // read in place, as inject_group_tt
-        for (uint32_t m = probe; m; m &= m - 1u) {
-            TT<NB> c = s;                                     // a pending target exactly when an injected action would be accepted
-            pending |= inject_tt<NB>(c, row, cond, sg.n_players, ctz(m) + 1u, 1u) == GE_OK ? m & (0u - m) & human : 0u;
-        }
-    }
-    return find_word(a.want, pending, s.phase, term_mask, a.row_mask);
+    const uint32_t probe = Ln::probe(sg, a.seats, human);
+    Ln lane;                                                  // no turn is played: no queue, no key
+    lane.open(sg, tables, nullptr, w, 0u, true, human);
+    const uint32_t pending = (a.want & GE_FIND_PERSON) && probe != 0u ? lane.pending(human, probe) : 0u;   // (wave-uniform)
+    return find_word(a.want, pending, lane.phase(), lane.term_mask(), a.row_mask);
 }
 
 template <int KIND, int GENERIC>
@@ -95,9 +66,7 @@ __global__ void __launch_bounds__(FIND_BLOCK) ge_find_kernel(const SegDev *__res
     const uint64_t k = (uint64_t)blockIdx.x * FIND_BLOCK + threadIdx.x;
     const bool valid = k < a.nr;
     const uint64_t room = a.r0 + (valid ? k : 0u);            // lanes past the part test its first room and report nothing
-    uint32_t r;
-    if constexpr (KindOf<KIND>::WW) r = find_ww<KindOf<KIND>::NB, GENERIC>(sg, tables, a, room);
-    else r = find_tt<KindOf<KIND>::NB, GENERIC>(sg, tables, a, room);
+    uint32_t r = find_lane<KindOf<KIND>::NB, KindOf<KIND>::WW, GENERIC>(sg, tables, a, room);
     r = valid ? r : 0u;
     const uint64_t hits = __ballot(r != 0u);
     const uint64_t padded = (a.nr + 63u) & ~(uint64_t)63u;

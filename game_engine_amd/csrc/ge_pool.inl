@@ -33,7 +33,12 @@
 // KIND as players' bound and game), by_kind + lane_lds (the launch of a segment's kind and its LDS size), up16, the entry checks
 // (pool_check_rooms / pool_check_entries: their order and their errors are ABI behaviour), PoolEntries (the listed rooms grouped by
 // segment and their staging as [rooms][keys][turns]), launch_pool_turn and pool_decode_event.  On the device: the indexed lane's
-// context (lane_cond_ctx, lane_ww_ctx), recycle rule (lane_recycle), turn call (lane_ww_turn, lane_tt_turn) and event words (lane_event).
+// context (lane_cond_ctx, lane_ww_ctx), recycle rule (lane_recycle), turn call (lane_ww_turn, lane_tt_turn) and event words
+// (lane_event), and Lane<NB, WWP, GENERIC>, which wraps them per game - record, constants, recycle, turn, pack, PERSON test - so
+// that a kernel body is written once for both games: pool_lane here, seat_lane (ge_seats.inl), find_lane (ge_find.inl).  The turn
+// loop of ge_run.inl and the playouts of ge_rollout.inl keep a body per game (run_ww / run_tt, roll_ww / roll_tt) on the functions
+// the type wraps: over the type their builds spill more scalar registers than tools/asm_baseline.json allows
+// (profiles/indexed_lane_asm.txt).
 
 namespace {
 
@@ -126,6 +131,90 @@ __device__ __forceinline__ u32x4 lane_event(uint32_t turn, const LaneTurn &t, ui
     return v;
 }
 
+// ---- Lane<NB, WWP, GENERIC>: what the two games' indexed lanes differ in - the record and its state, what the lane's turns keep
+// constant, the call that plays a turn and how the PERSON test finds a pending seat
+template <int NB, bool WWP, int GENERIC> struct Lane;
+
+template <int NB, int GENERIC> struct Lane<NB, true, GENERIC> {
+    using L = WWLayout<NB>;
+    WwCtx ctx;
+    WWR<NB> s;
+    // the lane's constants and the record w into its state (human, valid: lane_ww_ctx)
+    __device__ __forceinline__ void open(const SegDev &sg, const DevTable *__restrict__ tables, void *lw, const uint32_t *w, uint32_t rk, bool valid, uint32_t human) {
+        ctx = lane_ww_ctx<GENERIC>(sg, tables, lw, rk, valid, human);
+        uint32_t cache;                                       // the record's prepared deal: not of this key, never used
+        ww_load_regs<NB>(w, s, cache);
+    }
+    __device__ __forceinline__ uint32_t recycle(const SegDev &sg, uint32_t restart) { return lane_recycle(sg, s, restart, ctx.term_mask); }
+    __device__ __forceinline__ LaneTurn turn(uint32_t turn, bool log) { return lane_ww_turn<NB, GENERIC>(s, ctx, turn, log); }
+    // the canonical record: stored without a prepared deal
+    __device__ __forceinline__ void pack(uint32_t *w) const { ww_store_regs<NB>(s, 0u, w); }
+    __device__ __forceinline__ uint32_t phase() const { return s.phase; }
+    __device__ __forceinline__ uint32_t term_mask() const { return ctx.term_mask; }
+    // wave-uniform, 0: no lane of the wavefront has a host-driven seat, so the PERSON test finds nothing.  The scan skips the test
+    // then; the run-on's loop does not branch on it (the branch costs its Werewolf builds scalar registers: profiles/indexed_lane_asm.txt)
+    static __device__ __forceinline__ uint32_t probe(const SegDev &, const uint16_t *__restrict__ seats, uint32_t human) {
+        return (seats ? __ballot(human != 0u) != 0ull : __builtin_amdgcn_readfirstlane(human) != 0u) ? 1u : 0u;
+    }
+    // the PERSON test: the seats of `human` that are pending targets of the record as it stands - the turn's own ww_targets on the
+    // row of its phase, less who has acted
+    __device__ __forceinline__ uint32_t pending(uint32_t human, uint32_t) const {
+        const DevRow row = lds_row<false>(ctx.rows, s.phase);
+        const uint32_t T = ww_targets<NB, true, GENERIC>(s, row, ctx, s.template get<F_ALIVE>(), (1u << ctx.n) - 1u);
+        return T & ~s.acted & human;
+    }
+};
+
+template <int NB, int GENERIC> struct Lane<NB, false, GENERIC> {
+    using L = TTLayout<NB>;
+    TT<NB> s;
+    uint32_t done;                                            // tt_done_mask of s.rounds, maintained by the turn
+    const SegDev *sg;
+    const DevTable *tables;
+    CondCtx cc;
+    void *lw;
+    bool valid;
+    uint32_t rk, human, tmask;
+    __device__ __forceinline__ void open(const SegDev &sg_, const DevTable *__restrict__ tables_, void *lw_, const uint32_t *w, uint32_t rk_, bool valid_, uint32_t human_) {
+        sg = &sg_; tables = tables_; lw = lw_; rk = rk_; valid = valid_; human = human_;
+        cc = lane_cond_ctx<GENERIC>(sg_, tables_);
+        tmask = __builtin_amdgcn_readfirstlane(sg_.term_mask);
+        L::unpack(w, s);
+        done = tt_done_mask<NB>(s.rounds, sg_.rounds);
+    }
+    __device__ __forceinline__ uint32_t recycle(const SegDev &sg_, uint32_t restart) {
+        const uint32_t restarted = lane_recycle(sg_, s, restart, tmask);
+        if (restarted) done = __builtin_amdgcn_readfirstlane(sg_.done0);
+        return restarted;
+    }
+    __device__ __forceinline__ LaneTurn turn(uint32_t turn, bool log) {
+        return lane_tt_turn<NB, GENERIC>(s, done, *sg, tables, cc, lw, valid, rk, turn, log, human, tmask);
+    }
+    __device__ __forceinline__ void pack(uint32_t *w) const { L::pack(s, w); }
+    __device__ __forceinline__ uint32_t phase() const { return s.phase; }
+    __device__ __forceinline__ uint32_t term_mask() const { return tmask; }
+    // wave-uniform: the seats the PERSON test tries are the wavefront's - with a seat plane the union of its rooms' masks, each
+    // lane counting only its own bits; 0: the test finds nothing
+    static __device__ __forceinline__ uint32_t probe(const SegDev &sg_, const uint16_t *__restrict__ seats, uint32_t mask) {
+        const uint32_t h = mask & ((1u << sg_.n_players) - 1u);
+        return seats ? wave_seat_union(h, NB) : (uint32_t)__builtin_amdgcn_readfirstlane(h);
+    }
+    // the PERSON test (the turn has its target set inline): the seats of `mask` for which inject_tt on a copy of the record, choice
+    // 1, is accepted - the test ge_batch_inject_actions itself makes, as ge_playout_plan uses it
+    __device__ __forceinline__ uint32_t pending(uint32_t mask, uint32_t probe) const {
+        uint32_t pend = 0;
+        if (probe != 0u) {                                    // (wave-uniform)
+            const DevRow &row = tables[sg->table_idx].rows[s.phase];
+            const DevCond &cond = tables[sg->table_idx].conds[s.phase];   // read in place, as inject_group_tt
+            for (uint32_t m = probe; m; m &= m - 1u) {
+                TT<NB> c = s;                                 // a pending target exactly when an injected action would be accepted
+                pend |= inject_tt<NB>(c, row, cond, sg->n_players, ctz(m) + 1u, 1u) == GE_OK ? m & (0u - m) & mask : 0u;
+            }
+        }
+        return pend;
+    }
+};
+
 // ---- ge_pool_kernel: one turn of each listed room
 
 struct PoolArgs {
@@ -137,9 +226,10 @@ struct PoolArgs {
     uint32_t n, seg, seed_key, restart;
 };
 
-template <int NB, int GENERIC>
-__device__ __forceinline__ void pool_ww(const SegDev &sg, const DevTable *__restrict__ tables, const PoolArgs &a, void *lw, uint32_t k_in) {
-    using L = WWLayout<NB>;
+template <int NB, bool WWP, int GENERIC>
+__device__ __forceinline__ void pool_lane(const SegDev &sg, const DevTable *__restrict__ tables, const PoolArgs &a, void *lw, uint32_t k_in) {
+    using Ln = Lane<NB, WWP, GENERIC>;
+    using L = typename Ln::L;
     // lanes past the list stay in the wavefront (the action queue is a wave-wide collective): they shadow entry 0 and store nothing
     const bool valid = k_in < a.n;
     const uint32_t k = valid ? k_in : 0u;
@@ -148,39 +238,13 @@ __device__ __forceinline__ void pool_ww(const SegDev &sg, const DevTable *__rest
     load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
     const uint32_t rk = room_key_from(a.seed_key, a.keys[k]);
     const uint32_t turn = a.turns[k];
-    const WwCtx ctx = lane_ww_ctx<GENERIC>(sg, tables, lw, rk, valid, lane_seat_mask(sg, a.seats, room));
-    WWR<NB> s;
-    uint32_t cache;                                           // the record's prepared deal: not of this key, never used
-    ww_load_regs<NB>(w, s, cache);
-    const uint32_t restarted = lane_recycle(sg, s, a.restart, ctx.term_mask);
-    const LaneTurn t = lane_ww_turn<NB, GENERIC>(s, ctx, turn, true);
+    Ln lane;
+    lane.open(sg, tables, lw, w, rk, valid, lane_seat_mask(sg, a.seats, room));
+    const uint32_t restarted = lane.recycle(sg, a.restart);
+    const LaneTurn t = lane.turn(turn, true);
     if (!valid) return;
-    reinterpret_cast<u32x4 *>(a.events)[k] = lane_event(turn, t, s.phase, restarted);
-    ww_store_regs<NB>(s, 0u, w);                              // stored without a prepared deal
-    store_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
-}
-
-template <int NB, int GENERIC>
-__device__ __forceinline__ void pool_tt(const SegDev &sg, const DevTable *__restrict__ tables, const PoolArgs &a, void *lw, uint32_t k_in) {
-    using L = TTLayout<NB>;
-    const bool valid = k_in < a.n;
-    const uint32_t k = valid ? k_in : 0u;
-    const uint64_t room = a.rooms[k];
-    uint32_t w[L::WORDS];
-    load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
-    const uint32_t rk = room_key_from(a.seed_key, a.keys[k]);
-    const uint32_t turn = a.turns[k];
-    const CondCtx cc = lane_cond_ctx<GENERIC>(sg, tables);
-    const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
-    TT<NB> s;
-    L::unpack(w, s);
-    uint32_t done = tt_done_mask<NB>(s.rounds, sg.rounds);
-    const uint32_t restarted = lane_recycle(sg, s, a.restart, term_mask);
-    if (restarted) done = __builtin_amdgcn_readfirstlane(sg.done0);
-    const LaneTurn t = lane_tt_turn<NB, GENERIC>(s, done, sg, tables, cc, lw, valid, rk, turn, true, lane_seat_mask(sg, a.seats, room), term_mask);
-    if (!valid) return;
-    reinterpret_cast<u32x4 *>(a.events)[k] = lane_event(turn, t, s.phase, restarted);
-    L::pack(s, w);
+    reinterpret_cast<u32x4 *>(a.events)[k] = lane_event(turn, t, lane.phase(), restarted);
+    lane.pack(w);
     store_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
 }
 
@@ -190,8 +254,7 @@ __global__ void __launch_bounds__(64) ge_pool_kernel(const SegDev *__restrict__ 
     const SegDev &sg = segs[a.seg];
     const uint32_t k = blockIdx.x * 64u + threadIdx.x;
     void *lw = ge_lds;
-    if constexpr (KindOf<KIND>::WW) pool_ww<KindOf<KIND>::NB, GENERIC>(sg, tables, a, lw, k);
-    else pool_tt<KindOf<KIND>::NB, GENERIC>(sg, tables, a, lw, k);
+    pool_lane<KindOf<KIND>::NB, KindOf<KIND>::WW, GENERIC>(sg, tables, a, lw, k);
 }
 
 // ge_batch_read_rooms_at: the packed record of batch room rooms[k] -> out[k * 12 ..] (its segment's words; the rest untouched)

@@ -12,7 +12,8 @@
 // ge_run_kernel / ge_runp_turn and ge_find_kernel) and ge_seat_step_kernel below.  The flagship step kernels (ge_kernels.inl) never
 // see it: a batch with a plane does not launch them.
 //
-// ge_seat_step_kernel<KIND, GENERIC>: ge_batch_step on a batch with a plane.  ge_run_kernel's turn loop in ranged form - lane =
+// ge_seat_step_kernel<KIND, GENERIC>: ge_batch_step on a batch with a plane, one body for both games over ge_pool.inl's Lane
+// (seat_lane).  ge_run_kernel's turn loop in ranged form - lane =
 // room of the segment, key = the room's global index, turns turn0 .. turn0 + k - 1, no stop tests, no trace plane; the event of each
 // turn goes into the segment's GE_FLAG_TRACE buffer (store_event) when the batch traces.  So room r takes exactly
 // ge_batch_step_rooms's entry (r, its global index, turn) turn after turn under its own mask: the record's prepared deal is
@@ -42,55 +43,27 @@ struct SeatStepArgs {
     uint32_t turn0, n_turns;
 };
 
-template <int NB, int GENERIC>
-__device__ __forceinline__ void seat_ww(const SegDev &sg, const DevTable *__restrict__ tables, const SeatStepArgs &a, void *lw, uint64_t room_in) {
-    using L = WWLayout<NB>;
+template <int NB, bool WWP, int GENERIC>
+__device__ __forceinline__ void seat_lane(const SegDev &sg, const DevTable *__restrict__ tables, const SeatStepArgs &a, void *lw, uint64_t room_in) {
+    using Ln = Lane<NB, WWP, GENERIC>;
+    using L = typename Ln::L;
     // lanes past the segment stay in the wavefront (the action queue is a wave-wide collective): they shadow room 0 and store nothing
     const bool valid = room_in < sg.rooms;
     const uint64_t room = valid ? room_in : 0u;
     uint32_t w[L::WORDS];
     load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
     const uint32_t rk = room_key_from(a.seed_key, sg.first_global + room);
-    const WwCtx ctx = lane_ww_ctx<GENERIC>(sg, tables, lw, rk, valid, lane_seat_mask(sg, a.seats, room));
-    WWR<NB> s;
-    uint32_t cache;                                           // the record's prepared deal: never used (as an indexed step)
-    ww_load_regs<NB>(w, s, cache);
+    Ln lane;                                                  // the record's prepared deal is never used (as an indexed step)
+    lane.open(sg, tables, lw, w, rk, valid, lane_seat_mask(sg, a.seats, room));
     const bool trace = a.trace != 0u;
     for (uint32_t t = 0; t < a.n_turns; t++) {
         const uint32_t turn = a.turn0 + t;
-        const uint32_t restarted = lane_recycle(sg, s, a.restart, ctx.term_mask);   // every turn
-        const LaneTurn ev = lane_ww_turn<NB, GENERIC>(s, ctx, turn, trace);
-        if (trace && valid) store_event(sg.trace, sg.rooms_padded, t, room, turn, ev.p, s.phase, restarted, ev.newly, ev.choice);
+        const uint32_t restarted = lane.recycle(sg, a.restart);   // every turn
+        const LaneTurn ev = lane.turn(turn, trace);
+        if (trace && valid) store_event(sg.trace, sg.rooms_padded, t, room, turn, ev.p, lane.phase(), restarted, ev.newly, ev.choice);
     }
     if (!valid) return;
-    ww_store_regs<NB>(s, 0u, w);                              // stored without a prepared deal
-    store_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
-}
-
-template <int NB, int GENERIC>
-__device__ __forceinline__ void seat_tt(const SegDev &sg, const DevTable *__restrict__ tables, const SeatStepArgs &a, void *lw, uint64_t room_in) {
-    using L = TTLayout<NB>;
-    const bool valid = room_in < sg.rooms;
-    const uint64_t room = valid ? room_in : 0u;
-    uint32_t w[L::WORDS];
-    load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
-    const uint32_t rk = room_key_from(a.seed_key, sg.first_global + room);
-    const CondCtx cc = lane_cond_ctx<GENERIC>(sg, tables);
-    const uint32_t term_mask = __builtin_amdgcn_readfirstlane(sg.term_mask);
-    const uint32_t human = lane_seat_mask(sg, a.seats, room);
-    TT<NB> s;
-    L::unpack(w, s);
-    uint32_t done = tt_done_mask<NB>(s.rounds, sg.rounds);
-    const bool trace = a.trace != 0u;
-    for (uint32_t t = 0; t < a.n_turns; t++) {
-        const uint32_t turn = a.turn0 + t;
-        const uint32_t restarted = lane_recycle(sg, s, a.restart, term_mask);       // every turn
-        if (restarted) done = __builtin_amdgcn_readfirstlane(sg.done0);
-        const LaneTurn ev = lane_tt_turn<NB, GENERIC>(s, done, sg, tables, cc, lw, valid, rk, turn, trace, human, term_mask);
-        if (trace && valid) store_event(sg.trace, sg.rooms_padded, t, room, turn, ev.p, s.phase, restarted, ev.newly, ev.choice);
-    }
-    if (!valid) return;
-    L::pack(s, w);
+    lane.pack(w);                                             // stored without a prepared deal
     store_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
 }
 
@@ -100,8 +73,7 @@ __global__ void __launch_bounds__(64) ge_seat_step_kernel(const SegDev *__restri
     const SegDev &sg = segs[a.seg];
     const uint64_t room = (uint64_t)blockIdx.x * 64u + threadIdx.x;
     void *lw = ge_lds;
-    if constexpr (KindOf<KIND>::WW) seat_ww<KindOf<KIND>::NB, GENERIC>(sg, tables, a, lw, room);
-    else seat_tt<KindOf<KIND>::NB, GENERIC>(sg, tables, a, lw, room);
+    seat_lane<KindOf<KIND>::NB, KindOf<KIND>::WW, GENERIC>(sg, tables, a, lw, room);
 }
 
 template <int GEN> hipError_t seat_step_launch(uint32_t kind, dim3 grid, hipStream_t st, const ge_batch *b, const SeatStepArgs &a) {

@@ -216,6 +216,17 @@ def _summary_ref(segs, rooms, turn):
 @pytest.mark.parametrize("max_fuse,n_turns", [(1, 1), (1, 5), (1, 64), (1, 70), (64, 1), (64, 5), (64, 64), (64, 70)])
 @pytest.mark.parametrize("name", ["ww8", "tt8", "mixed"])
 def test_step_with_a_plane_is_the_per_room_oracle(name, max_fuse, n_turns, restart):
+    assert _check_step_with_a_plane(name, max_fuse, n_turns, restart) > 0
+
+
+# the builds of the stepping kernel no case above launches - Two-Truths x 12 and every GENERIC one: 65 rooms, the turns of one launch, traced
+@pytest.mark.parametrize("name", ["tt12", "ww8_generic_h1", "ww12_generic_h2", "tt4_generic_h1", "tt8_generic_h1", "tt12_generic"])
+def test_step_with_a_plane_on_the_other_layouts_and_generic_tables(name):
+    _check_step_with_a_plane(name, 64, 5, True)
+
+
+def _check_step_with_a_plane(name, max_fuse, n_turns, restart):
+    """Returns the number of scripted answers that were injected."""
     per = 65
     trace = n_turns <= max_fuse
     segs, _, _, _, masks = seat_case(name, per, restart)
@@ -237,7 +248,7 @@ def test_step_with_a_plane_is_the_per_room_oracle(name, max_fuse, n_turns, resta
                     _assert_events(got[:, t], events[t], (what, t))
             assert_summary_equal(b.summary_words(), _summary_ref(segs, rooms, b.turn), what)
             answered += _answer(b, segs, rooms, masks)
-    assert answered > 0
+    return answered
 
 
 @pytest.mark.parametrize("max_fuse", [1, 64])

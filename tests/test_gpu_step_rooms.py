@@ -61,12 +61,26 @@ CASES = [[("ww", 4, 0)], [("ww", 8, 0)], [("ww", 12, 0)], [("tt", 3, 0)], [("tt"
          [("ww", 6, 0), ("tt", 4, 0b10), ("ww", 10, 0), ("tt", 7, 0)]]
 
 
+def _case_id(g):
+    return "+".join(f"{n}x{k}" + (f"h{m:x}" if m else "") for n, k, m in g)
+
+
 @pytest.mark.parametrize("restart", [False, True])
-@pytest.mark.parametrize("games", CASES, ids=lambda g: "+".join(f"{n}x{k}" + (f"h{m:x}" if m else "") for n, k, m in g))
+@pytest.mark.parametrize("games", CASES, ids=_case_id)
 def test_step_rooms_matches_the_oracle_under_each_key_and_turn(games, restart):
-    seed = 0xB0B0 + len(games)
     rng = np.random.default_rng(sum(k * 7 + m for _, k, m in games) + restart)
     sizes = [int(rng.integers(300, 700)) for _ in games]
+    _check_step_rooms(games, restart, rng, sizes, sum(sizes) // 3)
+
+
+# the GENERIC builds of the twelve-seat layouts, which no case above launches: 65 entries - a full wavefront and one live lane
+@pytest.mark.parametrize("games", [[("ww_generic", 12, 0b100000000100)], [("tt_generic", 9, 0b100000001)]], ids=_case_id)
+def test_step_rooms_generic_tables_of_twelve_seats(games):
+    _check_step_rooms(games, True, np.random.default_rng(12), [97], 65)
+
+
+def _check_step_rooms(games, restart, rng, sizes, n_listed):
+    seed = 0xB0B0 + len(games)
     parts, segs = [], []
     for (game, n, mask), R in zip(games, sizes):
         dsl = _dsl(game)
@@ -84,7 +98,7 @@ def test_step_rooms_matches_the_oracle_under_each_key_and_turn(games, restart):
         turn_before = b.turn
         for rnd in range(3):
             before = _raw(b, parts)
-            chosen = rng.choice(total, size=total // 3, replace=False)          # a random subset, in shuffled order
+            chosen = rng.choice(total, size=n_listed, replace=False)            # a random subset, in shuffled order
             keys = rng.choice(1 << 40, size=len(chosen), replace=False).astype(np.uint64)
             keys[: len(keys) // 2] = rng.integers(0, 1 << 20, len(keys) // 2)   # keys below and above 2^32
             keys[0], keys[1] = (1 << 32) - 1, (1 << 47) + 3
