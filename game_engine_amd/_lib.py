@@ -83,6 +83,16 @@ class Advice(C.Structure):                       # ge_advice: 224 B
                 ("policy", AdviceOption), ("option", AdviceOption * 12)]
 
 
+class SeatObs(C.Structure):                      # ge_seat_obs: 192 B
+    _fields_ = [("seat", C.c_uint8), ("n_players", C.c_uint8), ("pack", C.c_uint8), ("act", C.c_uint8),
+                ("phase_row", C.c_uint8), ("done", C.c_uint8), ("won", C.c_uint8), ("pad0", C.c_uint8),
+                ("legal", C.c_uint16), ("unknown", C.c_uint16),
+                ("phase_id", C.c_int32), ("prev_phase_id", C.c_int32), ("end_turn", C.c_int32), ("games", C.c_int32), ("pad1", C.c_uint32),
+                ("players", (C.c_uint8 * 12) * 12), ("det", C.c_uint8 * 12), ("pad2", C.c_uint8 * 4)]
+
+
+SEAT_OBS_BYTES = C.sizeof(SeatObs)               # 192
+
 ADVISE_FULL_VIEW = 1                             # GE_ADVISE_FULL_VIEW
 BELIEF_SLOTS = 16                                # GE_BELIEF_SLOTS
 
@@ -90,7 +100,7 @@ BELIEF_SLOTS = 16                                # GE_BELIEF_SLOTS
 SYMBOLS = ["ge_table_compile_json", "ge_table_dev_row", "ge_batch_create", "ge_batch_step", "ge_batch_reset", "ge_batch_set_turn", "ge_batch_inject_actions", "ge_batch_sync", "ge_batch_turn",
            "ge_batch_n_rooms", "ge_batch_read_rooms", "ge_batch_write_rooms", "ge_batch_read_events", "ge_batch_inject_action", "ge_batch_summary",
            "ge_batch_state", "ge_batch_set_timing", "ge_batch_kernel_time", "ge_batch_destroy", "ge_batch_step_rooms", "ge_batch_read_rooms_at",
-           "ge_batch_write_rooms_at", "ge_batch_rollout_rooms", "ge_batch_rollout_actions", "ge_batch_rollout_seats", "ge_batch_rollout_compare", "ge_batch_rollout_beliefs", "ge_batch_step_rooms_playout", "ge_batch_run_rooms", "ge_batch_run_rooms_playout", "ge_batch_run_rooms_forecast", "ge_batch_find_rooms", "ge_batch_set_seats", "ge_batch_get_seats", "ge_batch_clear_seats", "ge_batch_advise_seats", "ge_group_partition", "ge_batch_create_shard", "ge_group_create", "ge_group_size", "ge_group_shard", "ge_group_step", "ge_group_sync", "ge_group_summary", "ge_group_destroy",
+           "ge_batch_write_rooms_at", "ge_batch_rollout_rooms", "ge_batch_rollout_actions", "ge_batch_rollout_seats", "ge_batch_rollout_compare", "ge_batch_rollout_beliefs", "ge_batch_step_rooms_playout", "ge_batch_run_rooms", "ge_batch_run_rooms_playout", "ge_batch_run_rooms_forecast", "ge_batch_find_rooms", "ge_batch_set_seats", "ge_batch_get_seats", "ge_batch_clear_seats", "ge_batch_advise_seats", "ge_batch_observe_seats", "ge_batch_act_seats", "ge_group_partition", "ge_batch_create_shard", "ge_group_create", "ge_group_size", "ge_group_shard", "ge_group_step", "ge_group_sync", "ge_group_summary", "ge_group_destroy",
            "ge_strerror", "ge_last_hip_error", "ge_last_rejected_room", "ge_last_comm_error", "ge_abi_version", "ge_device_count"]
 
 _lib = None
@@ -186,6 +196,9 @@ def load() -> C.CDLL:
         lib.ge_batch_clear_seats.argtypes = [vp]
     if hasattr(lib, "ge_batch_advise_seats") or not any_abi:
         lib.ge_batch_advise_seats.argtypes = [vp, u64, vp, vp, vp, vp, u32, u32, u64, u32, vp]
+    if hasattr(lib, "ge_batch_observe_seats") or not any_abi:
+        lib.ge_batch_observe_seats.argtypes = [vp, u64, u64, u32, vp, vp, C.c_size_t, vp]
+        lib.ge_batch_act_seats.argtypes = [vp, u64, u64, u32, vp, vp, vp, vp]
     if hasattr(lib, "ge_group_create") or not any_abi:
         lib.ge_group_create.argtypes = [C.POINTER(BatchDesc), C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
         lib.ge_group_size.argtypes = [vp]

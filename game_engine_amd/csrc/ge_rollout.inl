@@ -267,6 +267,27 @@ template <int N> __device__ __forceinline__ uint32_t weighted_pick(const Beliefs
     return over & (0u - over);
 }
 
+// Werewolf: what seat `seat` (1-based) of the n players of record `u` knows of the others (POLICY.md §3c), declared in the scope
+// that names it: U the seats whose hidden tuple it cannot see, Uw / Uv those of them it knows to be werewolves / not to be - both
+// empty where a Detective's memory does not fit the record -, nA / nB the werewolves / the others among U, team_w the record's,
+// s_wolf / s_det the seat's own side and role class.  The re-deal below and the seat observation (ge_env.inl, §3n) both take their
+// sets from here.  A macro, not a function: through an inlined call the same statements moved the register allocation of the
+// playout kernels beyond what tools/asm_baseline.json allows (Werewolf x 12 over a replica range: 64 spilled scalar registers
+// for 37); expanded in place, the re-deal compiles to the code it had before the statements had a second user.
+#define GE_VIEW_SETS_WW(u, seat, n)                                                                                       \
+    const uint32_t all = (1u << (n)) - 1u, me = 1u << ((seat) - 1u);                                                      \
+    const uint32_t U = all & ~(u).revealed & ~me;                                                                         \
+    const uint32_t team_w = (u).team_w;                                                                                   \
+    const bool s_wolf = (team_w & me) != 0u;                                                                              \
+    const bool s_det = ((u).rb2 & me) && !((u).rb1 & me) && !((u).rb0 & me);                                              \
+    uint32_t Uw = s_wolf ? (U & team_w) : s_det ? (U & (u).det_w) : 0u;                                                   \
+    uint32_t Uv = s_wolf ? (U & ~team_w) : s_det ? (U & (u).det_v) : 0u;                                                  \
+    const uint32_t nA = popc(U & team_w), nB = popc(U & ~team_w);                                                         \
+    {                                                                                                                     \
+        const int need = (int)nA - (int)popc(Uw);                                                                         \
+        if (need < 0 || need > (int)popc(U & ~Uw & ~Uv)) { Uw = 0u; Uv = 0u; }   /* the Detective's knowledge does not fit */ \
+    }
+
 // Werewolf: the hidden tuples of the seats seat s cannot rule out, dealt again over the seats they may sit on.  `u` holds the
 // record (wave-uniform on entry); priv = the phase's action log is private (WOLF_TARGET / DOCTOR_PROTECT / DETECTIVE).
 // WT: step 1 places the wolves by the beliefs `bw` (POLICY.md §3j) instead of uniformly.
@@ -274,18 +295,7 @@ template <int NB, bool WT = false>
 __device__ __forceinline__ void view_redeal_ww(WW<NB> &u, uint32_t seat, uint32_t n, bool priv, uint32_t vk, const Beliefs &bw = Beliefs{}) {
     constexpr int S = NB <= 8 ? 8 : 16;                      // bit-plane stride in a bundle
     constexpr uint64_t REP = NB <= 8 ? 0x0101010101010101ull : 0x0001000100010001ull;
-    const uint32_t all = (1u << n) - 1u, me = 1u << (seat - 1u);
-    const uint32_t U = all & ~u.revealed & ~me;
-    const uint32_t team_w = u.team_w;
-    const bool s_wolf = (team_w & me) != 0u;
-    const bool s_det = (u.rb2 & me) && !(u.rb1 & me) && !(u.rb0 & me);
-    uint32_t Uw = s_wolf ? (U & team_w) : s_det ? (U & u.det_w) : 0u;
-    uint32_t Uv = s_wolf ? (U & ~team_w) : s_det ? (U & u.det_v) : 0u;
-    const uint32_t nA = popc(U & team_w), nB = popc(U & ~team_w);
-    {
-        const int need = (int)nA - (int)popc(Uw);
-        if (need < 0 || need > (int)popc(U & ~Uw & ~Uv)) { Uw = 0u; Uv = 0u; }   // the Detective's knowledge does not fit
-    }
+    GE_VIEW_SETS_WW(u, seat, n)
     const uint32_t Uq = U & ~Uw & ~Uv, need = nA - popc(Uw);
     // the hidden tuples as sort keys: (team is werewolves, role, team, secret, elig, sub, sel[, acted, choice], seat), so the
     // sorted list is B ascending, then A ascending; seats outside U sort last
@@ -368,6 +378,10 @@ __device__ __forceinline__ void view_redeal_ww(WW<NB> &u, uint32_t seat, uint32_
     }
 }
 
+// Two-Truths: the lie of speaker `sp` (0-based: the lowest speaker) is no secret to seat `seat` - its own, or revealed (§3c; a
+// macro for the reason GE_VIEW_SETS_WW is one)
+#define GE_VIEW_SHOWN_TT(sp, revealed, seat) ((sp) == (seat) - 1u || (((revealed) >> (sp)) & 1u))
+
 // Two-Truths: the speaker's lie, drawn again for a seat that is not the speaker, before the reveal (`s` wave-uniform)
 // WT: the lie is drawn by the beliefs' first three bytes (POLICY.md §3j)
 template <int NB, bool WT = false>
@@ -376,7 +390,7 @@ __device__ __forceinline__ void view_redeal_tt(TT<NB> &s, uint32_t seat, uint32_
     const uint32_t rev = (uint32_t)__builtin_amdgcn_readfirstlane(s.revealed);
     if (spk == 0u) return;
     const uint32_t sp = ctz(spk);                            // the lowest speaker
-    if (sp == seat - 1u || ((rev >> sp) & 1u) || ((lie >> (2 * sp)) & 3u) == 0u) return;
+    if (GE_VIEW_SHOWN_TT(sp, rev, seat) || ((lie >> (2 * sp)) & 3u) == 0u) return;
     uint32_t fresh;
     if constexpr (WT) fresh = 1u + ctz(weighted_pick<3>(bw, 7u, 3u, draw(vk, 80u)));
     else fresh = 1u + pick(draw(vk, 80u), 3u);

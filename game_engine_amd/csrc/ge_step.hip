@@ -61,6 +61,7 @@ struct ge_batch {
     size_t state_bytes = 0;
     bool stream_loads = false;  // a single-game batch's large single-turn launches load the record with streaming loads (create_impl)
     DevTable *tables = nullptr;
+    int32_t *phase_ids = nullptr;     // per segment GE_MAX_PHASES words: the DSL phase id of each dense row (ge_env.inl: an observation names its phases by id)
     SegDev *segs_dev = nullptr;
     unsigned long long *sum_dev = nullptr;
     hipStream_t last_stream = nullptr;
@@ -328,6 +329,11 @@ static int create_impl(const ge_batch_desc *desc, ge_batch **out, const uint64_t
                     if (s.table.rows[r].n_branches == 0) s.dev.term_mask |= 1u << r;
             }
             if (hipMemcpy(b->tables, host_tables.data(), sizeof(DevTable) * host_tables.size(), hipMemcpyHostToDevice) != hipSuccess) { st = GE_ERR_HIP; break; }
+            std::vector<int32_t> ids(b->segs.size() * GE_MAX_PHASES, 0);
+            for (size_t k = 0; k < b->segs.size(); k++)
+                for (int r = 0; r < b->segs[k].table.n_phases; r++) ids[k * GE_MAX_PHASES + r] = b->segs[k].table.rows[r].phase_id;
+            if (hipMalloc(reinterpret_cast<void **>(&b->phase_ids), sizeof(int32_t) * ids.size()) != hipSuccess ||
+                hipMemcpy(b->phase_ids, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice) != hipSuccess) { st = GE_ERR_HIP; break; }
             SegDev host[GE_MAX_SEGMENTS];
             memset(host, 0, sizeof host);
             for (size_t k = 0; k < b->segs.size(); k++) host[k] = b->segs[k].dev;
@@ -1039,6 +1045,7 @@ void ge_batch_destroy(ge_batch *b) {
         if (b->deal_side) (void)hipFree(b->deal_side);
         if (b->seats) (void)hipFree(b->seats);
         if (b->tables) (void)hipFree(b->tables);
+        if (b->phase_ids) (void)hipFree(b->phase_ids);
         if (b->segs_dev) (void)hipFree(b->segs_dev);
         if (b->sum_dev) (void)hipFree(b->sum_dev);
     }
@@ -1058,3 +1065,4 @@ void ge_batch_destroy(ge_batch *b) {
 #include "ge_find.inl"          // behind ge_timeline.inl: the rooms of a range that need attention (ge_batch_find_rooms)
 #include "ge_seats.inl"         // behind ge_find.inl: each room's own host-driven seats (ge_batch_set_seats) and the whole-batch step under them
 #include "ge_advise.inl"        // behind ge_seats.inl: listed seats advised on the device (ge_batch_advise_seats)
+#include "ge_env.inl"           // behind ge_advise.inl: seat observations and actions in device memory (ge_batch_observe_seats, ge_batch_act_seats)

@@ -1,0 +1,100 @@
+"""SeatEnv - a resident RoomBatch as an environment for a decision maker that lives on the GPU and sits in a seat of every room
+(POLICY.md §3n): observations and actions are torch tensors on the batch's device, every call goes on torch's current stream, and
+no byte crosses to the host.  torch is imported when a SeatEnv is made; the rest of the package imports without it.  A process
+that uses SeatEnv imports torch before it creates its first GameTable or RoomBatch: torch ships a HIP runtime of its own, and
+the library binds to the runtime that is loaded first.
+
+    env = SeatEnv(batch, seats=[1])
+    obs = env.observe()
+    for _ in range(steps):
+        actions = SeatEnv.random_legal(obs)              # or a policy network's choice among fields(obs)["legal"]
+        obs, done, won = env.step(actions)
+
+A room that has ended shows done = 1 once; under restart=True the next step recycles it (the turn that starts from a terminal
+phase re-initialises the room), so the observation after that step is of the new game."""
+from typing import Dict, Sequence
+
+from .stepper import RoomBatch
+from ._lib import SEAT_OBS_BYTES
+
+# byte offsets inside a ge_seat_obs (include/ge_step.h)
+_BYTE_FIELDS = {"seat": 0, "n_players": 1, "pack": 2, "act": 3, "phase_row": 4}
+_INT_FIELDS = {"phase_id": 0, "prev_phase_id": 1, "end_turn": 2, "games": 3}      # the four int32 from byte 12 on
+
+
+class SeatEnv:
+    """Owns `obs` (uint8 [R, S, 192]: one ge_seat_obs per room and listed seat), `actions` and `status` (int32 [R, S]) on the
+    batch's device; R = batch.n_rooms, S = len(seats).  The human mask and the seat plane play no part: to keep the policy from
+    playing a listed seat as well, make it host-driven in the batch (human_mask / set_seats)."""
+
+    def __init__(self, batch: RoomBatch, seats: Sequence[int]):
+        import torch
+        if not torch.cuda.is_available():
+            # torch ships a HIP runtime of its own; one process can drive the GPU through one runtime only, and the library
+            # binds to whichever is loaded first
+            raise RuntimeError("SeatEnv: torch sees no GPU.  Import torch before the first GameTable / RoomBatch of the process, "
+                               "so that libge_step.so and torch share one HIP runtime")
+        self.batch, self.seats = batch, [int(s) for s in seats]
+        self._torch = torch
+        dev = torch.device("cuda", batch.device)
+        shape = (batch.n_rooms, len(self.seats))
+        self.obs = torch.zeros(shape + (SEAT_OBS_BYTES,), dtype=torch.uint8, device=dev)
+        self.actions = torch.zeros(shape, dtype=torch.int32, device=dev)
+        self.status = torch.zeros(shape, dtype=torch.int32, device=dev)
+
+    def _stream(self) -> int:
+        return int(self._torch.cuda.current_stream(self.obs.device).cuda_stream)
+
+    def observe(self):
+        """The observation tensor, filled for the batch as it stands."""
+        self.batch.observe_seats(self.seats, self.obs, stream=self._stream())
+        return self.obs
+
+    def step(self, actions, n_turns: int = 1):
+        """act_seats(actions), batch.step(n_turns), observe_seats - all on torch's current stream.  actions: [R, S] choices, 0 = no
+        action (any integer dtype or device; an int32 tensor on the batch's device is read where it lies); `status` holds each
+        entry's verdict afterwards.  Returns (obs, done, won): done and won are bool views [R, S] of the observation.  With
+        n_turns > 1 the turns are fused: a room that waits for a listed seat idles, and a finished room stays finished unless
+        the batch restarts, so step(actions, 16) is "play on until my seats are needed", within 16 turns."""
+        torch = self._torch
+        a = actions
+        if not (a.dtype == torch.int32 and a.device == self.obs.device and a.is_contiguous() and a.shape == self.actions.shape):
+            self.actions.copy_(a.reshape(self.actions.shape))
+            a = self.actions
+        st = self._stream()
+        self.batch.act_seats(self.seats, a, self.status, stream=st)
+        self.batch.step(n_turns, stream=st)
+        self.batch.observe_seats(self.seats, self.obs, stream=st)
+        f = self.fields(self.obs)
+        return self.obs, f["done"], f["won"]
+
+    @staticmethod
+    def fields(obs) -> Dict[str, "object"]:
+        """The fields of an observation tensor [..., 192] as tensor views (no copies): seat, n_players, pack, act, phase_row (uint8);
+        done, won (bool); legal_bits, unknown (int16 bit masks: bit c-1 = choice c / bit i = seat i+1); phase_id, prev_phase_id,
+        end_turn, games (int32); players [..., 12, 12] and det [..., 12] (uint8).  `legal` is the one derived tensor: legal_bits
+        expanded to bool [..., 12], legal[..., c-1] = choice c would be accepted now."""
+        import torch
+        out = {name: obs[..., at] for name, at in _BYTE_FIELDS.items()}
+        out["done"] = obs[..., 5].view(torch.bool)
+        out["won"] = obs[..., 6].view(torch.bool)
+        masks = obs[..., 8:12].view(torch.int16)
+        out["legal_bits"], out["unknown"] = masks[..., 0], masks[..., 1]
+        ints = obs[..., 12:28].view(torch.int32)
+        for name, at in _INT_FIELDS.items():
+            out[name] = ints[..., at]
+        out["players"] = obs[..., 32:176].unflatten(-1, (12, 12))
+        out["det"] = obs[..., 176:188]
+        bit = torch.arange(12, device=obs.device, dtype=torch.int32)
+        out["legal"] = ((out["legal_bits"].to(torch.int32).unsqueeze(-1) >> bit) & 1).bool()
+        return out
+
+    @staticmethod
+    def random_legal(obs, generator=None):
+        """A uniform legal choice per entry (int32, the shape of obs without its last axis), 0 where nothing is legal; computed on
+        the device: the largest of twelve uniform draws among the legal choices."""
+        import torch
+        legal = SeatEnv.fields(obs)["legal"]
+        draws = torch.rand(legal.shape, device=obs.device, generator=generator)
+        pick = torch.where(legal, draws, torch.full_like(draws, -1.0)).argmax(dim=-1).to(torch.int32) + 1
+        return torch.where(legal.any(dim=-1), pick, torch.zeros_like(pick))

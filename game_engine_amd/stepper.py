@@ -73,6 +73,18 @@ ROOM_HIT_DTYPE = np.dtype([("room", "<u8"), ("why", "<u4"), ("pending", "<u2"), 
 ADVICE_OPTION_DTYPE = np.dtype([("finished", "<u4"), ("wins", "<u4"), ("score", "<u8")])
 ADVICE_DTYPE = np.dtype([("status", "<i4"), ("legal", "<u4"), ("best", "<u4"), ("phase_id", "<u4"), ("policy", ADVICE_OPTION_DTYPE),
                          ("option", ADVICE_OPTION_DTYPE, (12,))])
+# ge_seat_obs (192 B): what ge_batch_observe_seats stores per (room, seat)
+SEAT_OBS_DTYPE = np.dtype([("seat", "u1"), ("n_players", "u1"), ("pack", "u1"), ("act", "u1"), ("phase_row", "u1"), ("done", "u1"), ("won", "u1"),
+                           ("pad0", "u1"), ("legal", "<u2"), ("unknown", "<u2"), ("phase_id", "<i4"), ("prev_phase_id", "<i4"), ("end_turn", "<i4"),
+                           ("games", "<i4"), ("pad1", "<u4"), ("players", "u1", (12, 12)), ("det", "u1", (12,)), ("pad2", "u1", (4,))])
+
+
+def _device_buffer(obj) -> Tuple[int, int]:
+    """(device pointer, bytes) of a torch tensor or of any object with data_ptr() and a byte size"""
+    ptr = int(obj.data_ptr())
+    if hasattr(obj, "nbytes"):
+        return ptr, int(obj.nbytes)
+    return ptr, int(obj.numel()) * int(obj.element_size())
 
 
 def find_want_bits(want) -> int:
@@ -234,6 +246,7 @@ class RoomBatch:
         self._h = h
         self._lib = lib
         self._seed, self._first_room, self._max_fuse, self._restart, self._trace = seed, first_room, max_fuse, restart, trace
+        self.device = device
         self.n_rooms = sum(s[2] for s in segments)
 
     def close(self):
@@ -640,6 +653,33 @@ class RoomBatch:
                                                seats.ctypes.data, n_rollouts, max_turns, self._seed if seed is None else seed,
                                                _lib.ADVISE_FULL_VIEW if full_view else 0, out.ctypes.data), "ge_batch_advise_seats")
         return out
+
+    def observe_seats(self, seats, out, first: int = 0, count: Optional[int] = None, stream: int = 0):
+        """What each listed seat (1-based, pairwise distinct) is shown of rooms first .. first + count - 1, into DEVICE memory the
+        caller owns (POLICY.md §3n): `out` is a torch tensor, or any object with data_ptr() and a byte size (nbytes, or numel()
+        and element_size()), of at least count * len(seats) * 192 bytes; record (r - first) * len(seats) + j is room r as seat
+        seats[j] sees it (SEAT_OBS_DTYPE).  Launched on `stream` (a hipStream_t handle; torch: current_stream().cuda_stream),
+        asynchronous, ordered behind the batch's earlier work as step() is; nothing crosses to the host.  The batch is only read."""
+        seats = np.ascontiguousarray(seats, dtype=np.uint32)
+        count = self.n_rooms - first if count is None else count
+        ptr, nbytes = _device_buffer(out)
+        _check(self._lib.ge_batch_observe_seats(self._h, first, count, len(seats), seats.ctypes.data if len(seats) else None, ptr, nbytes,
+                                                C.c_void_p(stream or None)), "ge_batch_observe_seats")
+
+    def act_seats(self, seats, choices, status=None, first: int = 0, count: Optional[int] = None, stream: int = 0):
+        """inject_actions over a range of rooms with the choices read from DEVICE memory: `choices` (int32, count * len(seats)
+        entries, same kinds of object as observe_seats's `out`) holds at (r - first) * len(seats) + j the choice of seat seats[j]
+        in room r, 0 = no action.  `status` (int32, same shape, optional) gets 0 for a zero or an applied choice and GE_ERR_ARG
+        for a refused one, which changes nothing.  Launched on `stream`, asynchronous, ordered as step() is."""
+        seats = np.ascontiguousarray(seats, dtype=np.uint32)
+        count = self.n_rooms - first if count is None else count
+        need = 4 * int(count) * len(seats)
+        ptr, nbytes = _device_buffer(choices)
+        st_ptr, st_bytes = _device_buffer(status) if status is not None else (None, need)
+        if nbytes < need or st_bytes < need:
+            raise GeError(GE_ERR_ARG, "act_seats: choices / status hold fewer than count * len(seats) int32 entries")
+        _check(self._lib.ge_batch_act_seats(self._h, first, count, len(seats), seats.ctypes.data if len(seats) else None, ptr, st_ptr,
+                                            C.c_void_p(stream or None)), "ge_batch_act_seats")
 
     def _rollout(self, method: str, rooms, keys, turns, seats, actions, n_rollouts: int, max_turns: int,
                  seed: Optional[int], compare=None, beliefs=None):

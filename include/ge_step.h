@@ -52,7 +52,8 @@ extern "C" {
  *      budget; a library from before it refuses the bit with GE_ERR_ARG);
  *      ge_batch_rollout_beliefs + GE_BELIEF_SLOTS (seat-view playouts and comparisons whose re-deal is weighted by the caller's suspicions);
  *      ge_batch_find_rooms + ge_room_hit + GE_FIND_* (a device scan of a range: the rooms that wait for a person, have ended or stand in given phases);
- *      ge_batch_advise_seats + ge_advice + GE_ADVISE_FULL_VIEW (listed seats advised on the device: their legal choices found, played and ranked) */
+ *      ge_batch_advise_seats + ge_advice + GE_ADVISE_FULL_VIEW (listed seats advised on the device: their legal choices found, played and ranked);
+ *      ge_batch_observe_seats + ge_batch_act_seats + ge_seat_obs (a seat of every room observed into, and played from, device memory the caller owns) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -705,6 +706,63 @@ typedef struct ge_advice {                 /* 224 B */
 int ge_batch_advise_seats(ge_batch *b, uint64_t n, const uint64_t *rooms, const uint64_t *keys, const uint32_t *turns,
                           const uint32_t *seats /* n, 1-based */, uint32_t n_rollouts, uint32_t max_turns, uint64_t seed,
                           uint32_t flags, ge_advice *out /* n */);
+
+/* Seat observations and actions in device memory: a decision maker that lives on the GPU and sits in a seat of every room
+ * (POLICY.md §3n).  Both calls take a range of rooms (local indices, as ge_batch_read_rooms counts) and a short list of seats
+ * (host memory, 1-based, pairwise distinct, at most 12), and device memory the caller owns, with count * n_seats entries:
+ * entry (r - first) * n_seats + j belongs to batch room r and seat seats[j].
+ *   ge_batch_observe_seats  obs_dev[entry] = what seat seats[j] is shown of room r, 192 bytes: the canonical view's columns with
+ *                           every field hidden that ge_batch_rollout_seats's re-deal from that seat may change (§3n restates the
+ *                           rule field by field; `unknown` is the mask of the seats it hides), the seat's legal choices
+ *                           (`legal` = ge_advice.legal: bit c-1 is set exactly when ge_batch_inject_action(r, seat, c) on a copy
+ *                           of the room returns GE_OK), and two outcome words that are not part of the observation proper: `done`
+ *                           (the stored phase is terminal, judged as GE_FIND_END judges it, with or without GE_FLAG_RESTART) and
+ *                           `won` (done, and the seat counts in ge_rollout_stats.seat_wins's rule for this finished room: its
+ *                           true team won / its total_score is the highest, ties count; 0 until done).  The batch is only read.
+ *   ge_batch_act_seats      by composition: ge_batch_inject_actions over the entries (r, seats[j], choices_dev[entry]) with a
+ *                           non-zero choice, in ascending (r, j) order.  status_dev[entry] (may be NULL) = GE_OK for a zero or an
+ *                           applied choice, GE_ERR_ARG for a refused one - a choice below 0 or above 15 is refused -, and a
+ *                           refused action changes nothing.  Records are written as ge_batch_inject_actions writes them; a room
+ *                           whose choices are all zero is not written.
+ * Neither the segment's human mask nor the seat plane plays a part, as for ge_batch_inject_action and ge_batch_advise_seats.
+ * The stream contract is ge_batch_step's, not the indexed calls': the launches go on hip_stream, ordered behind the batch's
+ * earlier work; every later call on the batch is ordered behind them; no byte crosses to the host and the host waits for
+ * nothing.  With ge_batch_set_timing on, the launches count in ge_batch_kernel_time.
+ * All checks run before anything is launched, in this order: GE_ERR_ARG for b NULL; for seats, obs_dev or choices_dev NULL with
+ * count * n_seats > 0; for n_seats > 12; for a repeated seat; GE_ERR_RANGE for a range beyond the batch; GE_ERR_ARG for a seat
+ * of 0 or above the n_players of a segment the range touches; for cap_bytes < count * n_seats * sizeof(ge_seat_obs); for a
+ * device pointer whose first or last byte hipPointerGetAttributes does not report as memory of the batch's device, managed
+ * memory or pinned host memory (memory of a peer device is refused) - the library launches on no pointer it has not vetted;
+ * then count == 0 or n_seats == 0: GE_OK.
+ * On the device: lane = room, the record loaded as ge_batch_find_rooms loads it, one launch per segment of the range, the seat
+ * list in the launch's arguments.  The knowledge sets are computed by the code the re-deal uses and `legal` by the loop of
+ * ge_batch_advise_seats's plan kernel; the bitboards are unpacked into the byte columns in registers; a wavefront's records go
+ * through LDS so that every 16-byte store instruction writes 1 KiB of consecutive bytes.  ge_batch_act_seats is the injection
+ * kernel's body with its inputs read from choices_dev.
+ * Measured on an MI355X (tools/env_probe.py, profiles/env_probe.txt: Werewolf x 8, human_mask = 1, restart on, 40 turns stepped
+ * first, seat 1 played by a uniform legal choice computed in torch on the device; medians of 15).  (a) The loop act_seats, step,
+ * observe_seats and the choice against the way there was before - ge_batch_read_rooms, a host-side choice in numpy (cheaper than
+ * the legality and redaction a real host must restate: a lower bound), ge_batch_inject_actions, ge_batch_step: 0.218 ms against
+ * 8.41 ms per turn at 65 536 rooms (x 39), 0.434 ms against 104 ms at 1 048 576 (x 240).  (b) ge_batch_observe_seats alone, launch
+ * interval: 11.9 us at 65 536 rooms x 1 seat, 60.3 us at 1 048 576 x 1 seat (235 MB of records read and observations written:
+ * 3.90 TB/s, 49 % of 8 TB/s), 266.8 us x 4 seats (839 MB, 3.14 TB/s); the layouts measured beside the LDS round trip and dropped:
+ * each lane storing its own record 13.7, 83.9 and 340.4 us, the same with streaming stores 452.6 us at 1 048 576 x 1.  No other
+ * shape has been measured. */
+typedef struct ge_seat_obs {            /* 192 B = 12 x 16 B */
+    uint8_t  seat, n_players, pack, act;          /* act: GE_ACT_* of the current phase's row */
+    uint8_t  phase_row, done, won, pad0;          /* phase_row: dense row in the segment's table (an embedding index) */
+    uint16_t legal, unknown;
+    int32_t  phase_id, prev_phase_id, end_turn, games;   /* as ge_room_view */
+    uint32_t pad1;                                 /* 0 */
+    uint8_t  players[12][12];                      /* redacted view columns; rows >= n_players are 0 */
+    uint8_t  det[12];
+    uint8_t  pad2[4];                              /* 0 */
+} ge_seat_obs;
+int ge_batch_observe_seats(ge_batch *b, uint64_t first, uint64_t count, uint32_t n_seats, const uint32_t *seats /* host, 1-based */,
+                           ge_seat_obs *obs_dev /* DEVICE: count * n_seats */, size_t cap_bytes, void *hip_stream);
+int ge_batch_act_seats(ge_batch *b, uint64_t first, uint64_t count, uint32_t n_seats, const uint32_t *seats /* host */,
+                       const int32_t *choices_dev /* DEVICE: count * n_seats, 0 = no action */,
+                       int32_t *status_dev /* DEVICE, may be NULL */, void *hip_stream);
 
 /* GE_FLAG_TRACE: events of the most recent ge_batch_step call, dst[(room - first) * *n_turns + t].
  * cap_bytes >= count * n_turns * sizeof(ge_turn_event).  Synchronises. */

@@ -52,6 +52,12 @@ def describe(mangled: str) -> dict:
     m = re.search(r"ge_advise_planILi(\d)E", mangled)
     if m:
         return {"kernel": "ge_advise_plan", "layout": KINDS[int(m.group(1))], "lowocc": False, "generic": False, "single": True}
+    m = re.search(r"ge_observe_kernelILi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_observe_kernel", "layout": KINDS[int(m.group(1))], "lowocc": False, "generic": False, "single": True}
+    m = re.search(r"ge_act_kernelILi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_act_kernel", "layout": KINDS[int(m.group(1))], "lowocc": False, "generic": False, "single": True}
     m = re.search(r"ge_playout_plan_rangedILi(\d)E", mangled)
     if m:
         return {"kernel": "ge_playout_plan_ranged", "layout": KINDS[int(m.group(1))], "lowocc": False, "generic": False, "single": True}
@@ -114,6 +120,10 @@ def label(r):
         return f"{r['layout']}, advised seats, plan (ge_batch_advise_seats)"
     if r["kernel"] == "ge_advise_reduce":                        # ge_batch_advise_seats: behind the playouts of a unit
         return "ge_advise_reduce (ge_batch_advise_seats: the advice records from the accumulators)"
+    if r["kernel"] == "ge_observe_kernel":                       # ge_batch_observe_seats: one launch per segment of the range
+        return f"{r['layout']}, seat observations (ge_batch_observe_seats)"
+    if r["kernel"] == "ge_act_kernel":                           # ge_batch_act_seats: one launch per segment of the range
+        return f"{r['layout']}, seat actions from device memory (ge_batch_act_seats)"
     if r["kernel"] == "ge_rollout_kernel" and r.get("act") == 4:  # GE_PLAYOUT_HALVING: one launch per unit and round
         return f"{r['layout']}, playouts over a replica range (GE_PLAYOUT_HALVING)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_playout_plan_ranged":
