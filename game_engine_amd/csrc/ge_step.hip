@@ -1066,3 +1066,4 @@ void ge_batch_destroy(ge_batch *b) {
 #include "ge_seats.inl"         // behind ge_find.inl: each room's own host-driven seats (ge_batch_set_seats) and the whole-batch step under them
 #include "ge_advise.inl"        // behind ge_seats.inl: listed seats advised on the device (ge_batch_advise_seats)
 #include "ge_env.inl"           // behind ge_advise.inl: seat observations and actions in device memory (ge_batch_observe_seats, ge_batch_act_seats)
+#include "ge_teach.inl"         // behind ge_env.inl: a seat of every room advised into device memory (ge_batch_teach_seats)

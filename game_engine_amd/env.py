@@ -10,22 +10,28 @@ the library binds to the runtime that is loaded first.
         actions = SeatEnv.random_legal(obs)              # or a policy network's choice among fields(obs)["legal"]
         obs, done, won = env.step(actions)
 
+A teacher for the loop (POLICY.md §3o): env.teach(64) fills `advice` with the playout advice of every listed seat - the win odds of
+each choice it can make now - without leaving the device, and advice_fields(advice)["best"] is an action tensor for step().
+
 A room that has ended shows done = 1 once; under restart=True the next step recycles it (the turn that starts from a terminal
 phase re-initialises the room), so the observation after that step is of the new game."""
 from typing import Dict, Sequence
 
-from .stepper import RoomBatch
+from .stepper import RoomBatch, ADVICE_BYTES
 from ._lib import SEAT_OBS_BYTES
 
 # byte offsets inside a ge_seat_obs (include/ge_step.h)
 _BYTE_FIELDS = {"seat": 0, "n_players": 1, "pack": 2, "act": 3, "phase_row": 4}
 _INT_FIELDS = {"phase_id": 0, "prev_phase_id": 1, "end_turn": 2, "games": 3}      # the four int32 from byte 12 on
+# the four int32 a ge_advice begins with; behind them 13 ge_advice_option of 16 bytes: the policy's, then option[12]
+_ADVICE_HEAD = {"status": 0, "legal_bits": 1, "best": 2, "phase_id": 3}
 
 
 class SeatEnv:
     """Owns `obs` (uint8 [R, S, 192]: one ge_seat_obs per room and listed seat), `actions` and `status` (int32 [R, S]) on the
-    batch's device; R = batch.n_rooms, S = len(seats).  The human mask and the seat plane play no part: to keep the policy from
-    playing a listed seat as well, make it host-driven in the batch (human_mask / set_seats)."""
+    batch's device, and `advice` (uint8 [R, S, 224]: one ge_advice each) from the first teach() on; R = batch.n_rooms,
+    S = len(seats).  The human mask and the seat plane play no part: to keep the policy from playing a listed seat as well, make
+    it host-driven in the batch (human_mask / set_seats)."""
 
     def __init__(self, batch: RoomBatch, seats: Sequence[int]):
         import torch
@@ -41,6 +47,7 @@ class SeatEnv:
         self.obs = torch.zeros(shape + (SEAT_OBS_BYTES,), dtype=torch.uint8, device=dev)
         self.actions = torch.zeros(shape, dtype=torch.int32, device=dev)
         self.status = torch.zeros(shape, dtype=torch.int32, device=dev)
+        self.advice = None                                   # uint8 [R, S, 224], made by the first teach()
 
     def _stream(self) -> int:
         return int(self._torch.cuda.current_stream(self.obs.device).cuda_stream)
@@ -67,6 +74,33 @@ class SeatEnv:
         self.batch.observe_seats(self.seats, self.obs, stream=st)
         f = self.fields(self.obs)
         return self.obs, f["done"], f["won"]
+
+    def teach(self, n_rollouts: int, max_turns: int = 1024, key0: int = 0, full_view: bool = False):
+        """The playout advice of every listed seat for the batch as it stands (RoomBatch.teach_seats, POLICY.md §3o), on torch's
+        current stream: `advice`, uint8 [R, S, 224], one ge_advice per room and listed seat, allocated on first use.  Room r is
+        played under the key key0 + (r << 20), the batch's turn and the batch's seed.  advice_fields(advice)["best"] is an action
+        tensor for step(): 0 exactly where nothing is legal."""
+        if self.advice is None:
+            self.advice = self._torch.zeros(self.actions.shape + (ADVICE_BYTES,), dtype=self._torch.uint8, device=self.obs.device)
+        self.batch.teach_seats(self.seats, self.advice, n_rollouts, max_turns, key0=key0, full_view=full_view, stream=self._stream())
+        return self.advice
+
+    @staticmethod
+    def advice_fields(advice) -> Dict[str, "object"]:
+        """The fields of an advice tensor [..., 224] as tensor views (no copies): status, legal_bits, best, phase_id (int32);
+        policy_finished, policy_wins (int32) and policy_score (int64), the entry without an action; finished, wins (int32) and
+        score (int64) as [..., 12], index c-1 = choice c, zero where bit c-1 of legal_bits is clear."""
+        import torch
+        head = advice[..., 0:16].view(torch.int32)
+        out = {name: head[..., at] for name, at in _ADVICE_HEAD.items()}
+        out["policy_finished"] = advice[..., 16:20].view(torch.int32)[..., 0]
+        out["policy_wins"] = advice[..., 20:24].view(torch.int32)[..., 0]
+        out["policy_score"] = advice[..., 24:32].view(torch.int64)[..., 0]
+        opt = advice[..., 32:224].unflatten(-1, (12, 16))
+        out["finished"] = opt[..., 0:4].view(torch.int32)[..., 0]
+        out["wins"] = opt[..., 4:8].view(torch.int32)[..., 0]
+        out["score"] = opt[..., 8:16].view(torch.int64)[..., 0]
+        return out
 
     @staticmethod
     def fields(obs) -> Dict[str, "object"]:

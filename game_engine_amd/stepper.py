@@ -73,6 +73,7 @@ ROOM_HIT_DTYPE = np.dtype([("room", "<u8"), ("why", "<u4"), ("pending", "<u2"), 
 ADVICE_OPTION_DTYPE = np.dtype([("finished", "<u4"), ("wins", "<u4"), ("score", "<u8")])
 ADVICE_DTYPE = np.dtype([("status", "<i4"), ("legal", "<u4"), ("best", "<u4"), ("phase_id", "<u4"), ("policy", ADVICE_OPTION_DTYPE),
                          ("option", ADVICE_OPTION_DTYPE, (12,))])
+ADVICE_BYTES = ADVICE_DTYPE.itemsize              # 224
 # ge_seat_obs (192 B): what ge_batch_observe_seats stores per (room, seat)
 SEAT_OBS_DTYPE = np.dtype([("seat", "u1"), ("n_players", "u1"), ("pack", "u1"), ("act", "u1"), ("phase_row", "u1"), ("done", "u1"), ("won", "u1"),
                            ("pad0", "u1"), ("legal", "<u2"), ("unknown", "<u2"), ("phase_id", "<i4"), ("prev_phase_id", "<i4"), ("end_turn", "<i4"),
@@ -680,6 +681,29 @@ class RoomBatch:
             raise GeError(GE_ERR_ARG, "act_seats: choices / status hold fewer than count * len(seats) int32 entries")
         _check(self._lib.ge_batch_act_seats(self._h, first, count, len(seats), seats.ctypes.data if len(seats) else None, ptr, st_ptr,
                                             C.c_void_p(stream or None)), "ge_batch_act_seats")
+
+    def teach_seats(self, seats, out, n_rollouts: int, max_turns: int = 1024, *, first: int = 0, count: Optional[int] = None, keys=None,
+                    key0: int = 0, turn: Optional[int] = None, seed: Optional[int] = None, full_view: bool = False, stream: int = 0):
+        """advise_seats for each listed seat (1-based, pairwise distinct) of rooms first .. first + count - 1, into DEVICE memory the
+        caller owns (POLICY.md §3o): `out` (the kinds of object observe_seats takes, at least count * len(seats) * 224 bytes) gets
+        at (r - first) * len(seats) + j, byte for byte, the ADVICE_DTYPE record advise_seats returns for (room r, key(r), turn,
+        seats[j]) under the same n_rollouts, max_turns, seed and full_view.  key(r) = keys[r - first] where `keys` (uint64 on the
+        device, count entries) is given, else key0 + (r << 20) mod 2^64.  turn None: the batch's turn; seed None: the batch's seed.
+        Launched on `stream`, asynchronous, ordered behind the batch's earlier work as step() is; nothing crosses to the host (a
+        call of a larger shape than any before it grows the batch's scratch, which may wait for the device).  The batch is only
+        read."""
+        seats = np.ascontiguousarray(seats, dtype=np.uint32)
+        count = self.n_rooms - first if count is None else count
+        ptr, nbytes = _device_buffer(out)
+        k_ptr = None
+        if keys is not None:
+            k_ptr, k_bytes = _device_buffer(keys)
+            if k_bytes < 8 * int(count):
+                raise GeError(GE_ERR_ARG, "teach_seats: keys hold fewer than count uint64 entries")
+        _check(self._lib.ge_batch_teach_seats(self._h, first, count, len(seats), seats.ctypes.data if len(seats) else None, k_ptr,
+                                              int(key0) & 0xFFFFFFFFFFFFFFFF, self.turn if turn is None else turn, n_rollouts, max_turns,
+                                              self._seed if seed is None else seed, _lib.ADVISE_FULL_VIEW if full_view else 0, ptr, nbytes,
+                                              C.c_void_p(stream or None)), "ge_batch_teach_seats")
 
     def _rollout(self, method: str, rooms, keys, turns, seats, actions, n_rollouts: int, max_turns: int,
                  seed: Optional[int], compare=None, beliefs=None):

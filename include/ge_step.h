@@ -53,7 +53,8 @@ extern "C" {
  *      ge_batch_rollout_beliefs + GE_BELIEF_SLOTS (seat-view playouts and comparisons whose re-deal is weighted by the caller's suspicions);
  *      ge_batch_find_rooms + ge_room_hit + GE_FIND_* (a device scan of a range: the rooms that wait for a person, have ended or stand in given phases);
  *      ge_batch_advise_seats + ge_advice + GE_ADVISE_FULL_VIEW (listed seats advised on the device: their legal choices found, played and ranked);
- *      ge_batch_observe_seats + ge_batch_act_seats + ge_seat_obs (a seat of every room observed into, and played from, device memory the caller owns) */
+ *      ge_batch_observe_seats + ge_batch_act_seats + ge_seat_obs (a seat of every room observed into, and played from, device memory the caller owns);
+ *      ge_batch_teach_seats (ge_batch_advise_seats for a seat list of every room of a range, into device memory the caller owns) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -763,6 +764,48 @@ int ge_batch_observe_seats(ge_batch *b, uint64_t first, uint64_t count, uint32_t
 int ge_batch_act_seats(ge_batch *b, uint64_t first, uint64_t count, uint32_t n_seats, const uint32_t *seats /* host */,
                        const int32_t *choices_dev /* DEVICE: count * n_seats, 0 = no action */,
                        int32_t *status_dev /* DEVICE, may be NULL */, void *hip_stream);
+
+/* A teacher beside the two calls above: the seat-view playout advice of ge_batch_advise_seats for a seat list of every room of a
+ * range, into device memory the caller owns (POLICY.md §3o).  Result, by composition: entry (r - first) * n_seats + j of out_dev
+ * is, byte for byte, the ge_advice that ge_batch_advise_seats returns for the listed entry (rooms = r, keys = key(r), turns = turn,
+ * seats = seats[j]) under the same n_rollouts, max_turns, seed and flags - `legal`, the refusal record (status = GE_ERR_ARG, every
+ * other word 0), `policy`, option[] and `best` exactly as there, phase_id the phase's id.  key(r) = keys_dev[r - first] where
+ * keys_dev is given, else key0 + (r << 20) mod 2^64, r the batch room index as ge_batch_read_rooms counts it: n_rollouts <= 2^20,
+ * so the replica key ranges of two rooms never overlap; all listed seats of a room share the room's key.  The batch is only read;
+ * neither the human mask nor the seat plane plays a part.  GE_PLAYOUT_HALVING and beliefs are not offered.
+ * The stream contract is ge_batch_observe_seats's: every launch and memset goes on hip_stream, ordered behind the batch's earlier
+ * work; later calls on the batch are ordered behind it; no byte crosses to the host and the host waits for nothing - with one
+ * exception: a call that needs more scratch than the batch holds grows it, and hipFree / hipMalloc may wait for the device; a later
+ * call of no larger shape allocates nothing and waits for nothing.  With ge_batch_set_timing on, the call counts as one interval in
+ * ge_batch_kernel_time.
+ * All checks run before anything is launched, and a failure leaves out_dev untouched, in this order: GE_ERR_ARG for b NULL; for a
+ * flag bit other than GE_ADVISE_FULL_VIEW; for n_rollouts 0 or above 2^20, or max_turns above 4096; then the checks of
+ * ge_batch_observe_seats in their order - GE_ERR_ARG for seats or out_dev NULL with count * n_seats > 0, for n_seats > 12, for a
+ * repeated seat; GE_ERR_RANGE for a range beyond the batch; GE_ERR_ARG for a seat of 0 or above the n_players of a segment the
+ * range touches, for cap_bytes < count * n_seats * sizeof(ge_advice), for an out_dev the batch's device does not reach, a non-NULL
+ * keys_dev (count x 8 bytes) vetted the same way -; GE_ERR_RANGE for turn + max_turns > 0xFFFFFFFF; GE_ERR_ARG when the sum over
+ * the touched segments of pairs x (c + 1) x n_rollouts exceeds 2^26, c as in ge_batch_advise_seats, whose cap and reservation this
+ * is; then count == 0 or n_seats == 0: GE_OK.
+ * On the device: no counter comes back, so the entry layout is fixed by shape - a pair (room, seat) owns c + 1 consecutive entry
+ * slots of ge_batch_rollout_seats, slot k - 1 for choice k and the last for the entry without an action.  A plan kernel (lane =
+ * pair, `legal` as ge_batch_observe_seats finds it) gives a live slot the replica range [0, n_rollouts) and a dead one - an illegal
+ * choice, any slot of a pair with legal == 0 - an empty range; the playout kernel is the replica-range form of the playout-seat
+ * calls, unchanged, launched on the grid of every slot: the wavefronts of a dead slot return before they load anything.  A reduce
+ * kernel (lane = pair) stores the 224 bytes.  Slots are played in passes of at most 65 536, enqueued back to back.
+ * Measured on an MI355X (tools/teach_probe.py, profiles/teach_probe.txt: Werewolf x 8, human_mask = 1, restart on, 40 turns stepped
+ * first, seat 1 of every room at 64 playouts per choice played to the end; medians of 15).  (a) The advice of every room as a device
+ * tensor, end to end with a final synchronise, against the way there was before - ge_batch_observe_seats, `legal` copied to the
+ * host, the due pairs listed in numpy, ge_batch_advise_seats, the records uploaded; the same bytes: 1.04 ms against 1.99 ms at
+ * 4 096 rooms (3 863 due), 15.6 ms against 29.2 ms at 65 536 (62 147 due).  (b) Of the call's kernel time the playouts are 97.4 % and
+ * 98.3 %, the plan 1.1 % and 0.6 %, the memset 0.8 % and 0.7 %, the reduce 0.7 % and 0.4 %.  (c) The dead slots - the same call
+ * where no pair is due: plan, memset, the grid of every slot with each wavefront leaving at its first test, reduce - cost 0.037 ms
+ * and 0.302 ms, 3.5 % and 1.9 % of (a): what a device-side count of the live slots could save at most.  (d) The reduce with its
+ * records staged through LDS 6.6 and 7.5 us per launch, with each lane storing its own record 7.6 and 8.4 us.  No other shape has
+ * been measured. */
+int ge_batch_teach_seats(ge_batch *b, uint64_t first, uint64_t count, uint32_t n_seats, const uint32_t *seats /* host, 1-based */,
+                         const uint64_t *keys_dev /* DEVICE: count, or NULL */, uint64_t key0, uint32_t turn,
+                         uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, uint32_t flags /* GE_ADVISE_FULL_VIEW */,
+                         ge_advice *out_dev /* DEVICE: count * n_seats */, size_t cap_bytes, void *hip_stream);
 
 /* GE_FLAG_TRACE: events of the most recent ge_batch_step call, dst[(room - first) * *n_turns + t].
  * cap_bytes >= count * n_turns * sizeof(ge_turn_event).  Synchronises. */

@@ -58,6 +58,9 @@ def describe(mangled: str) -> dict:
     m = re.search(r"ge_act_kernelILi(\d)E", mangled)
     if m:
         return {"kernel": "ge_act_kernel", "layout": KINDS[int(m.group(1))], "lowocc": False, "generic": False, "single": True}
+    m = re.search(r"ge_teach_planILi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_teach_plan", "layout": KINDS[int(m.group(1))], "lowocc": False, "generic": False, "single": True}
     m = re.search(r"ge_playout_plan_rangedILi(\d)E", mangled)
     if m:
         return {"kernel": "ge_playout_plan_ranged", "layout": KINDS[int(m.group(1))], "lowocc": False, "generic": False, "single": True}
@@ -124,6 +127,10 @@ def label(r):
         return f"{r['layout']}, seat observations (ge_batch_observe_seats)"
     if r["kernel"] == "ge_act_kernel":                           # ge_batch_act_seats: one launch per segment of the range
         return f"{r['layout']}, seat actions from device memory (ge_batch_act_seats)"
+    if r["kernel"] == "ge_teach_plan":                           # ge_batch_teach_seats: one launch per part of a pass
+        return f"{r['layout']}, taught seats, plan (ge_batch_teach_seats)"
+    if r["kernel"] == "ge_teach_reduce":                         # ge_batch_teach_seats: behind the playouts of a pass
+        return "ge_teach_reduce (ge_batch_teach_seats: the advice records from the accumulators)"
     if r["kernel"] == "ge_rollout_kernel" and r.get("act") == 4:  # GE_PLAYOUT_HALVING: one launch per unit and round
         return f"{r['layout']}, playouts over a replica range (GE_PLAYOUT_HALVING)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_playout_plan_ranged":
