@@ -132,6 +132,24 @@ template <bool LOWOCC, bool SINGLE> constexpr bool single_global(int game_bit) {
 #ifndef GE_RES_UNMASKED
 #define GE_RES_UNMASKED 0
 #endif
+// Lone Werewolf x 8 turn, the action queue's store transfer (profiles/ab_lone_pull_queue.txt).  Same scope as GE_ROW_DERIVED:
+//   the fused lone-wavefront Werewolf x 8 builds without generic rows.  A store moves its address and data registers to the LDS at a price
+//   per wave-instruction that nothing hides (a 16-byte store about three times a 4-byte one), whatever the exec mask; the slot form
+//   (WaveLdsLow) pays it for eight 16-byte stores per turn in front of the first slot read, although a room has about one due bot.
+//   0 = the slot form: an owner writes its context into every slot it might own.
+//   1 = the pull form (WaveLdsPull): an owner writes its context ONCE, at its rank among the rooms with a due bot, and a wave-uniform
+//       stamp (the absolute turn + 1) into the head word of its first slot; a slot reads its head word, counts the heads up to
+//       itself (ballot + mbcnt, earlier rounds' heads in a scalar) and reads that owner's context: one 16-byte + one 4-byte store,
+//       and a second, dependent read.
+//   2 = the byte form, the large-batch builds' queue (WaveLds) for this turn: one context store by lane + eight byte stores of the
+//       lane id, a slot reads its byte and then the context.
+//   Measured on C2, five alternating runs each, against the parent (= the slot form): the pull form +3.8 % steps/s, -3.9 % per launch,
+//   the byte form +3.1 % / -3.0 %; both pass the rule, the two do not differ by it: the pull form is the default.  Per wave-turn the pull
+//   form issues 16.5 instructions MORE (common turn 331 -> 338, and every further round pays the head read again), 4.6 LDS
+//   instructions fewer, and takes 84 cycles less (2061 -> 1976) with SQ_WAIT_ANY 26 cycles higher: what fell is neither issue nor counted wait.
+#ifndef GE_PULL_QUEUE
+#define GE_PULL_QUEUE 1
+#endif
 #ifndef GE_ROWS_SPLIT
 #define GE_ROWS_SPLIT 1
 #endif
@@ -393,6 +411,19 @@ struct WaveLdsLow {
     uint4 slot[64 * 13 + 80];  // + scratch for rooms without a due bot (lane .. lane + 12)
     uint4 res[64];
 };
+// GE_PULL_QUEUE 1 / 2 (the fused lone-wavefront Werewolf x 8 turn): contexts stored once, slots find their owner.
+//   1: cctx[r] = the context of the r-th room that has a due bot, cctx[64 + lane] = scratch of a room without one; head[k] = the stamp
+//      of the turn in which slot k was last some room's first slot.  head[] is zeroed once per wavefront (run_ww) and never cleared: a
+//      stamp is the absolute turn + 1, never 0 and a new value on every turn of a batch's 32-bit clock - which is why it is a word and not a byte:
+//      a byte would come round again after 256 turns of a launch of 1 024, in a word that no turn in between rewrote (the high slots are
+//      written on the first turn of a vote only), and a stale head would have to be cleared every turn; the store costs the same either way.
+//   2: cctx[lane] = the room's context, the head[] words hold the byte queue (slot -> lane, + scratch behind 64 * 13 as in WaveLdsLow)
+struct WaveLdsPull {
+    uint4 cctx[128];
+    uint4 res[64];
+    uint32_t head[64 * 13];
+};
+static_assert(sizeof(WaveLdsPull) <= sizeof(WaveLdsLow) && sizeof(WaveLdsPull) % 16 == 0, "the pull form lives in a lone wavefront's queue memory");
 template <bool LOWOCC> struct WaveLdsOf { using type = WaveLds; };
 template <> struct WaveLdsOf<true> { using type = WaveLdsLow; };
 
@@ -993,9 +1024,11 @@ struct WwActs { uint32_t newly, det_v, det_w; };   // who acted now; the Detecti
 template <int NB, bool LOWOCC, bool FUSED = false, bool LONE8 = false, bool SKIP_GIVEN = false, typename S1, typename S2>
 __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uint32_t T, uint32_t act, bool night, uint32_t alive, uint32_t team_w,
                                                  uint32_t r_det, uint32_t tk, WwActs &out, S1 &&shadow1, S2 &&shadow2, Stamps *stamps,
-                                                 uint32_t rowd = 0u, uint32_t nmask = 0u, uint32_t skip = 0u) {
+                                                 uint32_t rowd = 0u, uint32_t nmask = 0u, uint32_t skip = 0u, uint32_t qstamp = 0u) {
     using nib_t = typename WWR<NB>::nib_t;
     using B = WwBuild<NB, LOWOCC>;
+    constexpr int PULL = LONE8 ? GE_PULL_QUEUE : 0;          // (LONE8: LOWOCC, FUSED and NB <= 8)
+    auto *pq = static_cast<WaveLdsPull *>(c.wave_lds);
     constexpr bool DER = LONE8 && GE_ROW_DERIVED, PERM = LONE8 && GE_CTX_PERM && NB <= 8, UNMASKED = LONE8 && GE_RES_UNMASKED && B::ONE_ATOMIC;
     constexpr bool SKIPM = GE_SKIP_MASK && SKIP_GIVEN;
     auto *lw = static_cast<typename WaveLdsOf<LOWOCC>::type *>(c.wave_lds);
@@ -1036,7 +1069,7 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
     // N <= 8: only x, y come back - the results sit 8 bytes apart (GE_RES_PACKED; 16 bytes apart, a 64-bit access of 16 consecutive
     // lanes hits every bank twice: /opt/skills/guides/MI355X_MICROARCH.md "LDS", ds_write_b64 / ds_read_b64 banking)
     constexpr uint32_t RW = (NB <= 8 && GE_RES_PACKED) ? 2u : 4u;      // words per room in `res`
-    uint32_t *const res_w = reinterpret_cast<uint32_t *>(lw->res);
+    uint32_t *const res_w = PULL ? reinterpret_cast<uint32_t *>(pq->res) : reinterpret_cast<uint32_t *>(lw->res);
     if (NB <= 8) *reinterpret_cast<uint2 *>(res_w + RW * lane) = make_uint2(0u, 0u);
     else lw->res[lane] = make_uint4(0u, 0u, 0u, 0u);
     // Queue slot -> owning room.  A room with cnt due bots owns slots [off, off + cnt); it writes
@@ -1045,7 +1078,23 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
     // overwritten by their owners: an owner's write to its r-th slot is issued at step r,
     // any intruder's at a step > r, i.e. earlier.  Rooms without a due bot do not write
     // (they would tie with the next owner inside one instruction).
-    if (LOWOCC) {
+    if (PULL == 1) {
+        // the context once, at the room's rank among the owners (a room without a due bot: into the scratch behind them), and the turn's
+        // stamp into the head word of the room's first slot.  No predicate on that one either: a room without a due bot has the `off` of the
+        // next owner and writes the same word there, the trailing ones write head[total], which no slot below `total` reads
+        const uint64_t nz = __builtin_amdgcn_ballot_w64(cnt != 0u);
+        const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(nz >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nz, 0u));
+        pq->cctx[cnt != 0u ? r : 64u + lane] = ctx;
+        pq->head[off] = qstamp;
+    } else if (PULL == 2) {
+        pq->cctx[lane] = ctx;
+        uint8_t *qp = reinterpret_cast<uint8_t *>(pq->head) + (cnt != 0u ? off : 64u * 13u + lane);
+#pragma unroll
+        for (int j = NB - 1; j >= 0; j--) {
+            qp[j] = (uint8_t)lane;
+            asm volatile("" ::: "memory");             // the stores must issue in this order
+        }
+    } else if (LOWOCC) {
         auto *lo = reinterpret_cast<WaveLdsLow *>(lw);
         // no predicate here either: a room without a due bot writes to a scratch range behind the queue
         uint4 *qp = lo->slot + (cnt != 0u ? off : 64u * 13u + lane);
@@ -1069,12 +1118,25 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
     wave_sync();
     // slot k -> the owning room's context (slots past `total` hold stale entries: computed like the
     // others, result dropped).  The first round's read is issued BEFORE the shadow work below.
-    auto fetch = [&](uint32_t k) -> uint4 {
+    uint32_t heads_before = 0;                             // PULL == 1: head slots in the rounds before this one (wave-uniform)
+    auto fetch = [&](uint32_t k, bool first = false) -> uint4 {
+        if (PULL == 1) {
+            // the slot's owner is the last head at or before it: its rank is the heads of the earlier rounds (a segment that straddles a
+            // round boundary finds the last head before `base`) + those of this round up to and including the lane - 1.  Counted as the
+            // heads ABOVE the round's first slot up to the lane (the ballot shifted down by one: what mbcnt counts below a lane) on top of
+            // a scalar; the first round's first slot is always a head (lane 0 has off == 0) and nothing stands before it: the scalar is 0
+            const bool is_head = pq->head[k] == qstamp;
+            const uint64_t hb = __builtin_amdgcn_ballot_w64(is_head), above = hb >> 1;
+            const uint32_t at0 = first ? 0u : heads_before + ((uint32_t)hb & 1u) - 1u;
+            heads_before += (uint32_t)__builtin_popcountll(hb);
+            return pq->cctx[__builtin_amdgcn_mbcnt_hi((uint32_t)(above >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)above, at0))];
+        }
+        if (PULL == 2) return pq->cctx[reinterpret_cast<const uint8_t *>(pq->head)[k] & 63u];
         if (LOWOCC) return reinterpret_cast<WaveLdsLow *>(lw)->slot[k];
         auto *hi = reinterpret_cast<WaveLds *>(lw);
         return hi->ctx[hi->queue[k] & 63u];
     };
-    uint4 c4 = fetch(lane);
+    uint4 c4 = fetch(lane, true);
     if (B::SHADOW) shadow1();
     // Fused lone wavefront: the first round stands outside the loop over rounds, with shadow2 in its block, where the scheduler
     // interleaves the next turn's key and the deal's role words with the round's dependent chain (slot -> draw -> choice ->
@@ -1386,7 +1448,11 @@ __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c,
                     for (int k = 0; k < R::NW; k++) asm volatile("" : "+v"(dealt.W[k]));
                 }
             }
+#if GE_PULL_QUEUE == 1
+        }, stamps, rowd, nmask, skip, turn + 1u);             // (the head stamp; under the preprocessor for the reason GE_SKIP_MASK's mask is, ge_kernels.inl)
+#else
         }, stamps, rowd, nmask, skip);
+#endif
     s.acted |= acts.newly;
     s.template set<F_SUB>(DER ? acts.newly & nmask : night ? acts.newly : 0u);   // night_action_submitted
     ev_newly = acts.newly;

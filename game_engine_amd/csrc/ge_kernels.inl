@@ -306,6 +306,12 @@ __device__ __forceinline__ void run_ww(const SegDev *__restrict__ sgp, const Ste
         }
         if (trace && valid) store_event(sg.trace, sg.rooms_padded, 0u, room, turn0, p, s.phase, restarted, ev_newly, ev_choice);
     } else {
+        if constexpr (B::LONE && GENERIC == 0 && GE_PULL_QUEUE == 1) {
+            // the pull queue's head words start at 0, which no turn's stamp is; nothing clears them afterwards (ge_device.h WaveLdsPull)
+            uint32_t *head = static_cast<WaveLdsPull *>(lw)->head;
+#pragma unroll
+            for (uint32_t j = 0; j < 13u; j++) head[64u * j + __lane_id()] = 0u;
+        }
         DevRow row = lds_row<!LOWOCC && !SINGLE>(rows_t, s.phase);
         WWR<NB> s0;
         DevRow row0 = row;
@@ -555,9 +561,13 @@ static_assert(offsetof(DevTable, ord8) == IMG_ORD8 && offsetof(DevTable, nth8) =
               offsetof(DevTable, tally64) == IMG_TALLY && offsetof(DevTable, n_phases) == IMG_END, "DevTable leads with the LDS image");
 static_assert(sizeof(WaveLds) % 16 == 0 && sizeof(WaveLdsLow) % 16 == 0 && LDS_ROWS % 16 == 0 && LDS_ORD8 % 16 == 0, "LDS sections stay 16-byte aligned");
 
-inline uint32_t step_lds_bytes(bool queue, bool lowocc, uint32_t block_threads) {
+// the single-game kernels whose every wavefront runs the fused lone Werewolf x 8 turn in its pull or byte form (GE_PULL_QUEUE): their
+// queue memory is a WaveLdsPull per wavefront.  (The mixed lone kernel keeps WaveLdsLow: its other kinds' queues live there too)
+constexpr bool pull_queue_kernel(int kind, bool lowocc, int generic, bool single) { return GE_PULL_QUEUE != 0 && kind == K_WW8 && lowocc && generic == 0 && !single; }
+
+inline uint32_t step_lds_bytes(bool queue, bool lowocc, uint32_t block_threads, bool pull = false) {
     if (!queue) return LDS_ROWS;                              // Two-Truths N <= 4: phase rows only
-    return LDS_ROWS + LDS_ORD8 + (lowocc ? 0u : LDS_NTH8 + LDS_S0) + (uint32_t)(lowocc ? sizeof(WaveLdsLow) : sizeof(WaveLds)) * (block_threads / 64u);
+    return LDS_ROWS + LDS_ORD8 + (lowocc ? 0u : LDS_NTH8 + LDS_S0) + (uint32_t)(pull ? sizeof(WaveLdsPull) : lowocc ? sizeof(WaveLdsLow) : sizeof(WaveLds)) * (block_threads / 64u);
 }
 // (GENERIC builds: the literal image of the table's generic rows follows at StepArgs::cond_off = this size, cond_bytes more)
 
@@ -586,7 +596,8 @@ __device__ __forceinline__ void step_body(const SegDev *__restrict__ segs, const
     constexpr bool WWK = KIND == K_WW8 || KIND == K_WW12 || tt_uses_queue(KIND == K_TT4 ? 4 : KIND == K_TT8 ? 8 : 12, LOWOCC);   // uses the action queue
     DevRow *rows = reinterpret_cast<DevRow *>(ge_lds);
     uint8_t *nth8 = ge_lds + LDS_ROWS + LDS_ORD8;
-    auto *wl = reinterpret_cast<typename WaveLdsOf<LOWOCC>::type *>(ge_lds + LDS_ROWS + LDS_ORD8 + (LOWOCC ? 0u : LDS_NTH8 + LDS_S0));
+    using wave_lds_t = std::conditional_t<pull_queue_kernel(KIND, LOWOCC, GENERIC, SINGLE), WaveLdsPull, typename WaveLdsOf<LOWOCC>::type>;
+    auto *wl = reinterpret_cast<wave_lds_t *>(ge_lds + LDS_ROWS + LDS_ORD8 + (LOWOCC ? 0u : LDS_NTH8 + LDS_S0));
     // (a lane past rooms_per_block holds no room: it shadows room 0 like a lane past the end of the segment)
     const uint64_t room = (!LOWOCC || threadIdx.x < a.rooms_per_block) ? (uint64_t)blockIdx.x * (LOWOCC ? a.rooms_per_block : blockDim.x) + threadIdx.x : ~0ull;
     run_kind<KIND, LOWOCC, GENERIC, SINGLE, LD>(segs, a, rows, WWK ? &wl[threadIdx.x >> 6] : nullptr, nth8, tables, room);

@@ -380,9 +380,9 @@ static int reset_impl(ge_batch *b) {
 namespace {
 struct LaunchShape { dim3 grid, block; hipStream_t st; const ge_batch *b; StepArgs a; };
 
-template <class K> inline void launch_one(K kernel, const LaunchShape &L, bool queue, bool lds_low) {
+template <class K> inline void launch_one(K kernel, const LaunchShape &L, bool queue, bool lds_low, bool lds_pull = false) {
     StepArgs a = L.a;
-    const uint32_t base = step_lds_bytes(queue, lds_low, L.block.x);
+    const uint32_t base = step_lds_bytes(queue, lds_low, L.block.x, lds_pull);
     a.cond_off = base;                                        // GENERIC builds: the literal image follows everything else in LDS
     hipLaunchKernelGGL(kernel, L.grid, L.block, base + (L.b->generic ? L.b->cond_bytes : 0u), L.st, L.b->segs_dev, L.b->tables, a);
 }
@@ -398,8 +398,8 @@ template <bool LOW, int GEN, bool SINGLE> inline void launch_kind(uint32_t kind,
         // (the fused lone-wavefront kernel compiles in whether its turns recycle finished rooms - GE_TAIL_KNOWN_RESTART, ge_kernels.inl run_ww:
         // LD = 0 is the restart-on kernel, LD_NO_RECYCLE the restart-off one)
         if (alt) launch_one(ge_step_kernel<K_WW8, LOW, GEN, SINGLE, HAS_ALT ? 2 : 0>, L, true, LOW);
-        else if (NO_RECYCLE && !L.a.restart) launch_one(ge_step_kernel<K_WW8, LOW, GEN, SINGLE, NO_RECYCLE ? LD_NO_RECYCLE : 0>, L, true, LOW);
-        else launch_one(ge_step_kernel<K_WW8, LOW, GEN, SINGLE>, L, true, LOW);
+        else if (NO_RECYCLE && !L.a.restart) launch_one(ge_step_kernel<K_WW8, LOW, GEN, SINGLE, NO_RECYCLE ? LD_NO_RECYCLE : 0>, L, true, LOW, pull_queue_kernel(K_WW8, LOW, GEN, SINGLE));
+        else launch_one(ge_step_kernel<K_WW8, LOW, GEN, SINGLE>, L, true, LOW, pull_queue_kernel(K_WW8, LOW, GEN, SINGLE));
         break;
     case K_WW12:
         if (alt) launch_one(ge_step_kernel<K_WW12, LOW, GEN, SINGLE, HAS_ALT ? 1 : 0>, L, true, LOW);

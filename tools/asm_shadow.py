@@ -16,7 +16,7 @@ of the loop that the compiler laid out behind the loop's back edge (a rare path:
 scalar-memory operations complete in issue order for this purpose: `lgkmcnt(n)` covers a read once at most n such
 operations were issued behind it.
 Reads are named by their place in the turn: `ord` (before the slot writes), `slot` (the first round's), `slot+` (a later
-round's, inside the queue loop), `result` (behind the atomics), `row` (everything after: the entered row, a recycled room).
+round's, inside the queue loop), `head` / `head+` (the pull queue's head word, read in front of the context that `slot` / `slot+` then is), `result` (behind the atomics), `row` (everything after: the entered row, a recycled room).
 
 For the first round's slot read the walk goes on to the round's LDS atomic: `to atomic` = the vector instructions between that
 read and the atomic, i.e. the first round with whatever the scheduler interleaved with it - the placement that is adopted
@@ -233,15 +233,17 @@ def collect(path):
                 j = next(j for j in range(i, first - 1, -1) if LABEL.match(lines[j]))
                 return "Depth=2" in lines[j] or "Inner Loop Header" in lines[j + 1]
             seen = {}
-            for i, op in ops:
-                if not op.startswith("ds_read"):
-                    continue
+            reads = [(i, op) for i, op in ops if op.startswith("ds_read")]
+            for n, (i, op) in enumerate(reads):
+                # the pull queue (ge_device.h GE_PULL_QUEUE): a slot reads its head word, then the owner's 16-byte context
+                heads_ctx = op == "ds_read_b32" and n + 1 < len(reads) and reads[n + 1][1] == "ds_read_b128" and i >= writes[0] and \
+                    (in_queue_loop(i) and in_queue_loop(reads[n + 1][0]) or reads[n + 1][0] < atomics[0])
                 if i < writes[0]:
                     role = "ord"
                 elif in_queue_loop(i):
-                    role = "slot+"
+                    role = "head+" if heads_ctx else "slot+"
                 elif i < atomics[0]:
-                    role = "slot"
+                    role = "head" if heads_ctx else "slot"
                 elif "result" not in seen:
                     role = "result"
                 else:
