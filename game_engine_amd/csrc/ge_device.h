@@ -150,6 +150,27 @@ template <bool LOWOCC, bool SINGLE> constexpr bool single_global(int game_bit) {
 #ifndef GE_PULL_QUEUE
 #define GE_PULL_QUEUE 1
 #endif
+// Lone Werewolf x 8 turn, the turn that needs a second queue round (profiles/ab_lone_round2.txt).  Same scope as GE_PULL_QUEUE, and
+//   only its pull form (GE_PULL_QUEUE == 1).  A wavefront of 64 rooms has more than 64 due actions on about 0.44 of its turns; in the pull form
+//   every further round runs the loop over rounds with two dependent LDS reads (head word, then the owner's context) that nothing covers,
+//   and the one-round turn jumps over that loop with a taken branch.
+//   0 = the loop over rounds behind the peeled first round, as it was.
+//   1 = `total > 64` is decided once, straight behind the scan, and the two-round turn is a straight-line block of its own laid out
+//       behind the turn loop (stores, first fetch, both shadows, round 0, fetch of round 1, round 1); the loop over rounds runs from slot
+//       128 on for a third and later round.
+//   2 = 1, and the two-round block reads head[64 + lane] beside head[lane] and issues the second round's context read straight behind
+//       the first's, into slot registers of its own: round 0's dependent chain stands in front of both waits of round 1.
+//   3 = one path up to and including round 0; behind it `total > 64` marked unlikely, so the second round and the loop from slot 128 on
+//       are a block behind the turn loop's back edge and the one-round turn falls through (one taken branch less, nothing issued early).
+//   4 = 3, and on every turn the head words of both rounds come in ONE two-address read (ds_read2st64_b32 in place of ds_read_b32): the
+//       second round starts at its rank, one exposed round trip instead of two, and the one-round turn is no instruction longer.
+//   Measured on C2, five alternating runs each, steps/s against the parent: 1 -4.7 %, 2 -4.0 % (the two arms meet in register copies
+//   and 0 / 1 conditions: common turn 338 -> 354 instructions; 2 against 1 is what its covered waits buy, +0.8 .. +1.0 %), 3 +1.1 .. +1.7 %
+//   (passes the rule in one series of three), 4 +2.9 .. +3.3 %, passing in every series: adopted.  Per wave-turn 4 takes 60 cycles less
+//   (1976 -> 1917), 45 of them SQ_WAIT_ANY; 3 takes 25 less, 10 of them waits.
+#ifndef GE_QUEUE_ROUND2
+#define GE_QUEUE_ROUND2 4
+#endif
 #ifndef GE_ROWS_SPLIT
 #define GE_ROWS_SPLIT 1
 #endif
@@ -1028,6 +1049,8 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
     using nib_t = typename WWR<NB>::nib_t;
     using B = WwBuild<NB, LOWOCC>;
     constexpr int PULL = LONE8 ? GE_PULL_QUEUE : 0;          // (LONE8: LOWOCC, FUSED and NB <= 8)
+    constexpr int R2 = PULL == 1 ? GE_QUEUE_ROUND2 : 0;      // the two-round turn as a block of its own (below)
+    constexpr bool R2_ARMS = R2 == 1 || R2 == 2;             // .. from the stores on; 3 / 4: from the first fetch on
     auto *pq = static_cast<WaveLdsPull *>(c.wave_lds);
     constexpr bool DER = LONE8 && GE_ROW_DERIVED, PERM = LONE8 && GE_CTX_PERM && NB <= 8, UNMASKED = LONE8 && GE_RES_UNMASKED && B::ONE_ATOMIC;
     constexpr bool SKIPM = GE_SKIP_MASK && SKIP_GIVEN;
@@ -1078,7 +1101,9 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
     // overwritten by their owners: an owner's write to its r-th slot is issued at step r,
     // any intruder's at a step > r, i.e. earlier.  Rooms without a due bot do not write
     // (they would tie with the next owner inside one instruction).
-    if (PULL == 1) {
+    if (PULL == 1 && R2_ARMS) {
+        // (behind the decision between the one-round and the two-round turn, below: a copy of these four lines in either arm)
+    } else if (PULL == 1) {
         // the context once, at the room's rank among the owners (a room without a due bot: into the scratch behind them), and the turn's
         // stamp into the head word of the room's first slot.  No predicate on that one either: a room without a due bot has the `off` of the
         // next owner and writes the same word there, the trailing ones write head[total], which no slot below `total` reads
@@ -1115,7 +1140,7 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
             }
         }
     }
-    wave_sync();
+    if (!R2_ARMS) wave_sync();
     // slot k -> the owning room's context (slots past `total` hold stale entries: computed like the
     // others, result dropped).  The first round's read is issued BEFORE the shadow work below.
     uint32_t heads_before = 0;                             // PULL == 1: head slots in the rounds before this one (wave-uniform)
@@ -1136,8 +1161,11 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
         auto *hi = reinterpret_cast<WaveLds *>(lw);
         return hi->ctx[hi->queue[k] & 63u];
     };
-    uint4 c4 = fetch(lane, true);
-    if (B::SHADOW) shadow1();
+    uint4 c4;
+    if (!R2) {
+        c4 = fetch(lane, true);
+        if (B::SHADOW) shadow1();
+    }
     // Fused lone wavefront: the first round stands outside the loop over rounds, with shadow2 in its block, where the scheduler
     // interleaves the next turn's key and the deal's role words with the round's dependent chain (slot -> draw -> choice ->
     // atomic).  Measured on C2 (profiles/ab_lone_shadow.txt, SQ counters): +2 % steps/s, wave cycles per wave-turn 2377 -> 2329,
@@ -1147,6 +1175,7 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
     // front of the wait gained nothing (same file; tools/asm_shadow.py shows what stands where).
     // Every other build keeps the loop below as it was, instruction for instruction
     constexpr bool PEEL = LOWOCC && FUSED && B::SHADOW;
+    static_assert(!R2 || PEEL, "the two-round block is a form of the peeled first round");
     if (PEEL) {
         auto round = [&](uint32_t base, auto first_c) {    // the loop's body below, for a lone wavefront
             const uint32_t k = base + lane;
@@ -1177,11 +1206,98 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
                 atomicOr(r + 1 + (i >> 3), ch << (4u * (i & 7u)));
             }
         };
-        shadow2();
-        round(0u, std::true_type{});
-        for (uint32_t base = 64u; base < total; base += 64u) {   // wave-uniform; a round's read is issued only if it is needed
-            c4 = fetch(base + lane);
-            round(base, std::false_type{});
+        if (R2 >= 3) {
+            // GE_QUEUE_ROUND2 3 / 4: the stores, both shadows and round 0 once, for either turn - the two arms of 1 / 2 meet again in
+            // register copies and in conditions that cross the branch as 0 / 1 values, which the one-round turn pays too (+16 instructions).
+            // Only the second round and the loop behind it are out of line: marked unlikely for where the block is laid out, behind the
+            // turn loop's back edge as GE_COLD_FALLBACK's deal is, so that the one-round turn falls through its test of `total`
+            uint32_t h1w = 0;
+            if (R2 == 4) {
+                // on every turn head[64 + lane] comes with head[lane]: one two-address read in place of a one-address read, no instruction
+                // more.  The second round then starts at its rank (`fetch`: the heads of the round before + whether its first slot is one
+                // - 1, so a segment that straddles 63 | 64 finds the last head before 64) and has one exposed LDS round trip, not two
+                const uint32_t h0w = pq->head[lane];
+                h1w = pq->head[64u + lane];
+                const uint64_t b0 = __builtin_amdgcn_ballot_w64(h0w == qstamp), a0 = b0 >> 1;
+                heads_before = (uint32_t)__builtin_popcountll(b0);
+                c4 = pq->cctx[__builtin_amdgcn_mbcnt_hi((uint32_t)(a0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)a0, 0u))];
+            } else {
+                c4 = fetch(lane, true);
+            }
+            shadow1();
+            shadow2();
+            round(0u, std::true_type{});
+            if (__builtin_expect(total > 64u, 0)) {
+                if (R2 == 4) {
+                    const uint64_t b1 = __builtin_amdgcn_ballot_w64(h1w == qstamp), a1 = b1 >> 1;
+                    c4 = pq->cctx[__builtin_amdgcn_mbcnt_hi((uint32_t)(a1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)a1, heads_before + ((uint32_t)b1 & 1u) - 1u))];
+                    heads_before += (uint32_t)__builtin_popcountll(b1);
+                } else {
+                    c4 = fetch(64u + lane);
+                }
+                round(64u, std::false_type{});
+                for (uint32_t base = 128u; base < total; base += 64u) {   // a third and later round: rare (the first day vote after a reset takes eight)
+                    c4 = fetch(base + lane);
+                    round(base, std::false_type{});
+                }
+            }
+        } else if (R2) {
+            // GE_QUEUE_ROUND2: one wave-uniform decision as soon as the scan has `total`; each arm is a straight line from the stores on.
+            // The two-round turn (0.44 of a 64-room wavefront's turns) is marked unlikely only for where it is laid out: behind the turn
+            // loop's back edge, as GE_COLD_FALLBACK's deal is, so that the one-round turn falls through and never tests `total` again
+            if (__builtin_expect(total > 64u, 0)) {
+                {   // the owner's stores, as above
+                    const uint64_t nz = __builtin_amdgcn_ballot_w64(cnt != 0u);
+                    const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(nz >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nz, 0u));
+                    pq->cctx[cnt != 0u ? r : 64u + lane] = ctx;
+                    pq->head[off] = qstamp;
+                }
+                wave_sync();
+                uint4 c4b;                                 // R2 == 2: the second round's slot, in registers of its own
+                if (R2 == 2) {
+                    // both head words behind the same wave_sync; the second round's rank from the first's heads (`fetch`: the heads of
+                    // the earlier rounds + whether this round's first slot is one - 1, so a segment that straddles 63 | 64 finds the last
+                    // head before 64), and its context read issued straight behind the first's, in front of both shadows and round 0
+                    const bool h0 = pq->head[lane] == qstamp, h1 = pq->head[64u + lane] == qstamp;
+                    const uint64_t b0 = __builtin_amdgcn_ballot_w64(h0), b1 = __builtin_amdgcn_ballot_w64(h1), a0 = b0 >> 1, a1 = b1 >> 1;
+                    const uint32_t n0 = (uint32_t)__builtin_popcountll(b0), at1 = n0 + ((uint32_t)b1 & 1u) - 1u;
+                    c4 = pq->cctx[__builtin_amdgcn_mbcnt_hi((uint32_t)(a0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)a0, 0u))];
+                    c4b = pq->cctx[__builtin_amdgcn_mbcnt_hi((uint32_t)(a1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)a1, at1))];
+                    heads_before = n0 + (uint32_t)__builtin_popcountll(b1);
+                } else {
+                    c4 = fetch(lane, true);
+                }
+                shadow1();
+                shadow2();
+                round(0u, std::true_type{});
+                if (R2 == 2) c4 = c4b; else c4 = fetch(64u + lane);
+                round(64u, std::false_type{});
+                // (as c4 below: the second set stays reserved while the queue's traffic may be in flight)
+                if (R2 == 2) asm volatile("" :: "v"(c4b.x), "v"(c4b.y), "v"(c4b.z), "v"(c4b.w));
+                for (uint32_t base = 128u; base < total; base += 64u) {   // a third and later round: rare (the first day vote after a reset takes eight)
+                    c4 = fetch(base + lane);
+                    round(base, std::false_type{});
+                }
+            } else {
+                {   // the owner's stores, as above
+                    const uint64_t nz = __builtin_amdgcn_ballot_w64(cnt != 0u);
+                    const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(nz >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nz, 0u));
+                    pq->cctx[cnt != 0u ? r : 64u + lane] = ctx;
+                    pq->head[off] = qstamp;
+                }
+                wave_sync();
+                c4 = fetch(lane, true);
+                shadow1();
+                shadow2();
+                round(0u, std::true_type{});
+            }
+        } else {
+            shadow2();
+            round(0u, std::true_type{});
+            for (uint32_t base = 64u; base < total; base += 64u) {   // wave-uniform; a round's read is issued only if it is needed
+                c4 = fetch(base + lane);
+                round(base, std::false_type{});
+            }
         }
     } else {
         // at least one round (total == 0: every slot is stale and dropped): the loop is left BEFORE the next

@@ -11,7 +11,8 @@ VARIANTS=("deal8:-DGE_DEAL_PERIOD=8" "deal32:-DGE_DEAL_PERIOD=32" "ttq13:-DGE_TT
           "lone_deal_masks:-DGE_LONE_DEAL_WORDS=0" "tail_restart_runtime:-DGE_TAIL_KNOWN_RESTART=0"
           "row_from_r0:-DGE_ROW_DERIVED=0" "ctx_perm:-DGE_CTX_PERM=1" "skip_mask:-DGE_SKIP_MASK=1" "res_unmasked:-DGE_RES_UNMASKED=1"
           "row_const_all:-DGE_CTX_PERM=1 -DGE_SKIP_MASK=1 -DGE_RES_UNMASKED=1"
-          "queue_slots:-DGE_PULL_QUEUE=0" "queue_bytes:-DGE_PULL_QUEUE=2")
+          "queue_slots:-DGE_PULL_QUEUE=0" "queue_bytes:-DGE_PULL_QUEUE=2"
+          "round2_loop:-DGE_QUEUE_ROUND2=0" "round2_arms:-DGE_QUEUE_ROUND2=1" "round2_arms_early:-DGE_QUEUE_ROUND2=2" "round2_tail:-DGE_QUEUE_ROUND2=3")
 cd "$(dirname "$0")/.."
 case "${1:-}" in
 build)

@@ -17,6 +17,9 @@ scalar-memory operations complete in issue order for this purpose: `lgkmcnt(n)` 
 operations were issued behind it.
 Reads are named by their place in the turn: `ord` (before the slot writes), `slot` (the first round's), `slot+` (a later
 round's, inside the queue loop), `head` / `head+` (the pull queue's head word, read in front of the context that `slot` / `slot+` then is), `result` (behind the atomics), `row` (everything after: the entered row, a recycled room).
+GE_QUEUE_ROUND2 (ge_device.h) lays the second round out of line - a block of its own outside the loop over rounds, behind the turn loop's back edge in the tail-recycling loops: its
+reads are `head2` (the head word, where the round reads one of its own) and `slot2` (the context, the read whose next LDS operation is
+the round's atomic).  With the head words of both rounds read at once the first read is a two-address one and still `head`.
 
 For the first round's slot read the walk goes on to the round's LDS atomic: `to atomic` = the vector instructions between that
 read and the atomic, i.e. the first round with whatever the scheduler interleaved with it - the placement that is adopted
@@ -28,7 +31,8 @@ The floors are per kernel and read, the least over the kernel's turn loops (no l
     python tools/asm_shadow.py --check         exit 1 if a count is below its floor in tools/asm_shadow_baseline.json
     python tools/asm_shadow.py --paths         per turn loop, as JSON: the common turn from the loop header to its back edge - instructions on it,
                                                branches taken on it, role-deal blocks it runs through (tools/asm_shadow_paths.json pins the last
-                                               two for the Werewolf x 8 kernel: tests/test_asm_cold_deal.py)
+                                               two for the Werewolf x 8 kernel: tests/test_asm_cold_deal.py); `two_round`: the same walk through
+                                               the out-of-line second round (instructions, taken branches), where the loop has one
     python tools/asm_shadow.py --write         record today's counts as the floors (those in front of a wait capped at 32)
 It reads instruction mnemonics only: LDS reads, LDS atomics and writes (to name the reads), waits, branches, and whether an
 instruction is a vector or a scalar one.
@@ -122,14 +126,44 @@ def cold_from(lines, head, first, end):
     return next((i + 1 for i in range(first, end) if back.match(lines[i].split(";")[0].rstrip())), end)
 
 
-def turn_path(lines, labels, head, first, end):
+def second_round_blocks(lines, labels, first, end):
+    """GE_QUEUE_ROUND2: the second queue round as a block of its own, entered by a forward wave-uniform branch and left by an
+    unconditional one - wherever the compiler laid it (behind the back edge in the tail-recycling loops, in front of it in the
+    others).  What tells it from a deal block and from the first round's: a context read (ds_read_b128) and then an LDS atomic stand in it before any
+    wave-uniform branch.  [(first line, last line)]"""
+    out = []
+    for i in range(first, end):
+        m = INSN.match(lines[i])
+        if not m or not m.group(1).startswith(("s_cbranch_scc", "s_cbranch_vcc")):
+            continue
+        t = labels.get(m.group(2).strip())
+        if t is None or t <= i or any(a <= t <= b for a, b in out):
+            continue
+        read = False
+        for j in range(t, end):
+            mj = INSN.match(lines[j])
+            if mj and (mj.group(1) == "s_branch" or mj.group(1).startswith(("s_cbranch_scc", "s_cbranch_vcc"))) or "Loop Header" in lines[j]:
+                break
+            read |= bool(mj) and mj.group(1) == "ds_read_b128"
+            if mj and ATOMIC.match(mj.group(1)) and read:
+                stop = next((k for k in range(j, end) if INSN.match(lines[k]) and INSN.match(lines[k]).group(1) == "s_branch"), end - 1)
+                out.append((t, stop))
+                break
+    return out
+
+
+def turn_path(lines, labels, head, first, end, two=False):
     """the common turn from the loop header to its back edge, by walk()'s rules (exec-masked blocks entered, the skip of an in-line
     wave-uniform block taken, no branch into an out-of-line block, the loop over further queue rounds left at once): instructions on
-    it, branches taken on it (the back edge among them), and how many role-deal blocks it runs through"""
+    it, branches taken on it (the back edge among them), and how many role-deal blocks it runs through.
+    two: the turn that needs a second queue round where that round is a block behind the back edge (GE_QUEUE_ROUND2) - the branch into
+    that block is taken and its branch back followed; None if the loop has no such block"""
     def in_queue_loop(i):
         j = next(j for j in range(i, first - 1, -1) if LABEL.match(lines[j]))
         return "Depth=2" in lines[j] or "Inner Loop Header" in lines[j + 1]
     cold = cold_from(lines, head, first, end)
+    second = second_round_blocks(lines, labels, first, end)
+    entered = False
     i, n, taken, marks = labels[head], 0, 0, 0
     for _ in range(40 * LIMIT):
         m = INSN.match(lines[i])
@@ -143,7 +177,18 @@ def turn_path(lines, labels, head, first, end):
         marks += any(c in lines[i] for c in DEAL_MARKS)
         if op == "s_branch" or op.startswith("s_cbranch_scc") or op.startswith("s_cbranch_vcc"):
             t = labels.get(args.strip())
+            if t is not None and op != "s_branch" and any(a == t for a, _ in second) and not any(a <= i <= b for a, b in second):
+                if two:
+                    entered, taken, i = True, taken + 1, t
+                else:
+                    i += 1                                  # the one-round turn falls through
+                continue
+            if t is not None and t <= i and op != "s_branch" and any(a <= i <= b for a, b in second):
+                taken, i = taken + 1, t                     # back from the second round to where the turn goes on (no third round)
+                continue
             if t is not None and t <= i and (op == "s_branch" or not in_queue_loop(i)):
+                if two and not entered:
+                    return None
                 return {"insns": n, "taken": taken + 1, "deal_blocks": (marks + 3) // 4}
             if t is not None and t > i and (op == "s_branch" or (t < cold and not in_queue_loop(i))):
                 taken += 1
@@ -153,7 +198,7 @@ def turn_path(lines, labels, head, first, end):
     return None
 
 
-def walk(lines, labels, start, first, end, to_atomic=False, cold=None):
+def walk(lines, labels, start, first, end, to_atomic=False, cold=None, second=()):
     """from the LDS read at `start`: (wait line or None, vector, scalar, LDS) instructions issued up to its wait; to_atomic: the
     walk goes on to the first LDS atomic, and a fifth value counts the vector instructions from the read to there"""
     def in_queue_loop(i):                                   # the block of line i belongs to the loop over queue rounds
@@ -189,7 +234,8 @@ def walk(lines, labels, start, first, end, to_atomic=False, cold=None):
         if op.startswith("s_cbranch_scc") or op.startswith("s_cbranch_vcc"):
             s += 1
             t = labels[args.strip()]
-            i = t if (i < t < cold and not in_queue_loop(i)) else i + 1
+            into_second = any(a == t for a, _ in second) and not any(a <= i <= b for a, b in second)
+            i = t if (i < t < cold and not in_queue_loop(i) and not into_second) else i + 1
             continue
         if is_lgkm(op):
             behind += 1
@@ -224,6 +270,7 @@ def collect(path):
         n_loop = 0
         for head, first, end in loops_of(lines, lo, hi):
             cold = cold_from(lines, head, first, end)
+            second = second_round_blocks(lines, labels, first, end)
             ops = [(i, INSN.match(lines[i]).group(1)) for i in range(first, end) if INSN.match(lines[i])]
             atomics = [i for i, op in ops if ATOMIC.match(op)]
             writes = [i for i, op in ops if op.startswith("ds_write")]
@@ -232,14 +279,19 @@ def collect(path):
             def in_queue_loop(i):
                 j = next(j for j in range(i, first - 1, -1) if LABEL.match(lines[j]))
                 return "Depth=2" in lines[j] or "Inner Loop Header" in lines[j + 1]
+            def in_second(i):
+                return any(a <= i <= b for a, b in second)
             seen = {}
             reads = [(i, op) for i, op in ops if op.startswith("ds_read")]
             for n, (i, op) in enumerate(reads):
                 # the pull queue (ge_device.h GE_PULL_QUEUE): a slot reads its head word, then the owner's 16-byte context
-                heads_ctx = op == "ds_read_b32" and n + 1 < len(reads) and reads[n + 1][1] == "ds_read_b128" and i >= writes[0] and \
-                    (in_queue_loop(i) and in_queue_loop(reads[n + 1][0]) or reads[n + 1][0] < atomics[0])
+                heads_ctx = op in ("ds_read_b32", "ds_read2st64_b32") and n + 1 < len(reads) and reads[n + 1][1] == "ds_read_b128" and i >= writes[0] and \
+                    (in_queue_loop(i) and in_queue_loop(reads[n + 1][0]) or reads[n + 1][0] < atomics[0] or in_second(i) and not in_queue_loop(reads[n + 1][0]))
+                next_lds = next((o for j, o in ops if j > i and o.startswith("ds_")), "")
                 if i < writes[0]:
                     role = "ord"
+                elif in_second(i) and not in_queue_loop(i) and (heads_ctx or op == "ds_read_b128" and ATOMIC.match(next_lds)):
+                    role = "head2" if heads_ctx else "slot2"     # the second round out of line (GE_QUEUE_ROUND2)
                 elif in_queue_loop(i):
                     role = "head+" if heads_ctx else "slot+"
                 elif i < atomics[0]:
@@ -249,7 +301,7 @@ def collect(path):
                 else:
                     role = "row"
                 seen[role] = seen.get(role, 0) + 1
-                wait, v, s, d, *rest = walk(lines, labels, i, first, end, to_atomic=(role == "slot"), cold=cold)
+                wait, v, s, d, *rest = walk(lines, labels, i, first, end, to_atomic=(role == "slot"), cold=cold, second=second)
                 rows.append({"kernel": KERNELS[frag], "loop": n_loop, "read": f"{role}{seen[role] if seen[role] > 1 else ''}", "op": op,
                              "wait": (INSN.match(lines[wait]).group(0).strip() if wait is not None else None),
                              "vector": v, "scalar": s, "lds": d, "to_atomic": rest[0] if rest else None})
@@ -272,6 +324,9 @@ def paths(path):
             p = turn_path(lines, labels, head, first, end)
             if p:
                 out[f"{KERNELS[frag]} / loop {n_loop}"] = dict(p, static=len(ops), out_of_line=cold_from(lines, head, first, end) < end)
+                p2 = turn_path(lines, labels, head, first, end, two=True)
+                if p2:
+                    out[f"{KERNELS[frag]} / loop {n_loop}"]["two_round"] = {"insns": p2["insns"], "taken": p2["taken"]}
             n_loop += 1
     return out
 
