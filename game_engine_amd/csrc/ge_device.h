@@ -26,7 +26,8 @@ constexpr uint32_t GOLDEN = 0x9E3779B9u;
 
 // Compile-time switches.  Every one selects between shipped builds or is a tuning constant; tools/ab_switches.sh builds
 // the non-default value of each and runs the parity subset on it.  (What used to be A/B switches for measured-and-rejected
-// variants is gone from the source: the numbers live in profiles/r02_ab_*.txt and in git history.)
+// variants is gone from the source: the numbers live in profiles/r02_ab_*.txt, for the lone Werewolf x 8 turn in profiles/ab_lone_*.txt
+// and DESIGN.md 10, and in git history.)
 // GE_STAMPS=1: diagnostic build (tools/stamps.py) - s_memtime stamps at points of the werewolf turn where no LDS operation
 //   is outstanding anyway, accumulated per wavefront; never in the product build.  GE_STAMPS=2: only the two clocks at a
 //   wavefront's start and end - s_memtime (shader cycles) against s_memrealtime (constant 100 MHz): the shader clock the
@@ -73,104 +74,6 @@ template <bool LOWOCC, bool SINGLE> constexpr bool single_global(int game_bit) {
 #ifndef GE_RESOLVE_PRIO
 #define GE_RESOLVE_PRIO 2
 #endif
-// Lone Werewolf x 8 turn, instruction count (profiles/ab_lone_tally.txt).  GE_TALLY_BYTES: the computed plurality<N <= 8> expands the masked
-//   votes to bytes of 4 * nibble once, and a voter's counter increment is ONE shift whose amount is a byte select (shl_by_byte) instead of
-//   extract + mask + shift: 28 -> 16 vector instructions per resolution, C2 +1.8 .. +2.0 % steps/s
-#ifndef GE_TALLY_BYTES
-#define GE_TALLY_BYTES 1
-#endif
-// Lone Werewolf x 8 turn, rare deal paths out of the loop's straight line (profiles/ab_lone_cold_deal.txt; the tail-recycling turn loops only).
-//   GE_COLD_FALLBACK: the on-the-spot deal of ww_apply_effect stands behind a wave-uniform vote marked unlikely, around the unchanged
-//   per-lane test: a turn in which no lane lacks its deal passes one scalar test instead of two exec-mask regions whose values met again
-//   in copies, and the ~125-instruction deal is laid out behind the loop.  C2 +4.1 % steps/s by the rule in two sessions: adopted.
-//   GE_COLD_DEAL_NOW: ww_prepare_deal's `deal_now` marked unlikely, so the block of every GE_DEAL_PERIOD-th turn is laid out behind the
-//   loop too (one taken branch less on 15 turns of 16): +1.5 % alone, which does not pass, and level on top of the other: not adopted
-#ifndef GE_COLD_FALLBACK
-#define GE_COLD_FALLBACK 1
-#endif
-#ifndef GE_COLD_DEAL_NOW
-#define GE_COLD_DEAL_NOW 0
-#endif
-// Lone Werewolf x 8 turn, once-per-game work out of the every-turn path (profiles/ab_lone_once_per_game.txt).
-//   GE_LONE_DEAL_WORDS: the fused lone-wavefront Werewolf x 8 builds keep a prepared deal as its three predicate words (DEAL_WORDS, the
-//   large-batch build's form: converted once per deal) instead of as four player masks that every turn of every lane turned into
-//   words again (DEAL_MASKS).  A lone wavefront pays an issue slot for each of those instructions wherever they stand.
-//   GE_TAIL_KNOWN_RESTART: whether a turn of the tail-recycling loops recycles is a compile-time fact of the turn (ww_turn's TAILR:
-//   TAIL_RECYCLE / TAIL_KEEP) - a recycling turn does not record `end_turn` (the fresh room's replaces it), a turn that does not
-//   recycle has no merge with the fresh room; a restart-on launch runs its last turn as a peeled TAIL_KEEP turn behind the loop and a
-//   restart-off launch goes to a kernel of its own (ge_step_kernel's LD = LD_NO_RECYCLE).  0 = the run-time form (rst->term_rs)
-#ifndef GE_LONE_DEAL_WORDS
-#define GE_LONE_DEAL_WORDS 1
-#endif
-#ifndef GE_TAIL_KNOWN_RESTART
-#define GE_TAIL_KNOWN_RESTART 1
-#endif
-// Lone Werewolf x 8 turn, row-constant and launch-constant work out of the every-turn path (profiles/ab_lone_row_const.txt).
-//   Each applies to the fused lone-wavefront Werewolf x 8 builds without generic rows (WwBuild::LONE, GENERIC = 0) and to nothing else;
-//   GE_SKIP_MASK to their tail-recycling turn loops (TAIL_RECYCLE / TAIL_KEEP: the loops run_ww hands the mask to).
-//   GE_ROW_DERIVED: the turn takes what is a constant of the table row from the row's derived word (DevRow r6, ge_layout.h: the
-//   all-players-or-0 byte of the completion test, the night flag, the flags byte a room leaves the row with, the one-hot action kind)
-//   instead of working it out of r0 on every turn of every lane.  The word arrives in the row read the loop issues anyway.
-//   GE_CTX_PERM: alive | team_w << 16 of a queue slot's context word is one v_perm_b32 of the packed predicate words W1:W0.
-//   GE_SKIP_MASK: `valid` and the segment's human mask are one per-lane mask made in front of the turn loop: all ones for
-//   a lane past the segment's end (run_ww hands it to ww_turn), so todo = T & ~acted & ~skip has no select.
-//   GE_RES_UNMASKED: the peeled first queue round returns its result from every lane - a slot that does not act ORs a zero into its
-//   (possibly stale, always in-range: the room index is 6 bits) room's word - instead of inside an exec-masked block.
-//   Measured on C2, five alternating runs each, steps/s against the parent: GE_ROW_DERIVED alone +3.4 .. +3.8 % (passes the rule in both
-//   sessions; common turn 338 -> 331): adopted.  The other three alone: GE_CTX_PERM +0.0 % (339: the shifts it replaces fold into
-//   neighbours), GE_SKIP_MASK +1.0 % (337), GE_RES_UNMASKED -0.5 % (336); on top of the others none adds anything by the rule
-//   (all four 327 instructions, +3.4 %; without GE_RES_UNMASKED +4.2 %): they stay switches, off.
-#ifndef GE_ROW_DERIVED
-#define GE_ROW_DERIVED 1
-#endif
-#ifndef GE_CTX_PERM
-#define GE_CTX_PERM 0
-#endif
-#ifndef GE_SKIP_MASK
-#define GE_SKIP_MASK 0
-#endif
-#ifndef GE_RES_UNMASKED
-#define GE_RES_UNMASKED 0
-#endif
-// Lone Werewolf x 8 turn, the action queue's store transfer (profiles/ab_lone_pull_queue.txt).  Same scope as GE_ROW_DERIVED:
-//   the fused lone-wavefront Werewolf x 8 builds without generic rows.  A store moves its address and data registers to the LDS at a price
-//   per wave-instruction that nothing hides (a 16-byte store about three times a 4-byte one), whatever the exec mask; the slot form
-//   (WaveLdsLow) pays it for eight 16-byte stores per turn in front of the first slot read, although a room has about one due bot.
-//   0 = the slot form: an owner writes its context into every slot it might own.
-//   1 = the pull form (WaveLdsPull): an owner writes its context ONCE, at its rank among the rooms with a due bot, and a wave-uniform
-//       stamp (the absolute turn + 1) into the head word of its first slot; a slot reads its head word, counts the heads up to
-//       itself (ballot + mbcnt, earlier rounds' heads in a scalar) and reads that owner's context: one 16-byte + one 4-byte store,
-//       and a second, dependent read.
-//   2 = the byte form, the large-batch builds' queue (WaveLds) for this turn: one context store by lane + eight byte stores of the
-//       lane id, a slot reads its byte and then the context.
-//   Measured on C2, five alternating runs each, against the parent (= the slot form): the pull form +3.8 % steps/s, -3.9 % per launch,
-//   the byte form +3.1 % / -3.0 %; both pass the rule, the two do not differ by it: the pull form is the default.  Per wave-turn the pull
-//   form issues 16.5 instructions MORE (common turn 331 -> 338, and every further round pays the head read again), 4.6 LDS
-//   instructions fewer, and takes 84 cycles less (2061 -> 1976) with SQ_WAIT_ANY 26 cycles higher: what fell is neither issue nor counted wait.
-#ifndef GE_PULL_QUEUE
-#define GE_PULL_QUEUE 1
-#endif
-// Lone Werewolf x 8 turn, the turn that needs a second queue round (profiles/ab_lone_round2.txt).  Same scope as GE_PULL_QUEUE, and
-//   only its pull form (GE_PULL_QUEUE == 1).  A wavefront of 64 rooms has more than 64 due actions on about 0.44 of its turns; in the pull form
-//   every further round runs the loop over rounds with two dependent LDS reads (head word, then the owner's context) that nothing covers,
-//   and the one-round turn jumps over that loop with a taken branch.
-//   0 = the loop over rounds behind the peeled first round, as it was.
-//   1 = `total > 64` is decided once, straight behind the scan, and the two-round turn is a straight-line block of its own laid out
-//       behind the turn loop (stores, first fetch, both shadows, round 0, fetch of round 1, round 1); the loop over rounds runs from slot
-//       128 on for a third and later round.
-//   2 = 1, and the two-round block reads head[64 + lane] beside head[lane] and issues the second round's context read straight behind
-//       the first's, into slot registers of its own: round 0's dependent chain stands in front of both waits of round 1.
-//   3 = one path up to and including round 0; behind it `total > 64` marked unlikely, so the second round and the loop from slot 128 on
-//       are a block behind the turn loop's back edge and the one-round turn falls through (one taken branch less, nothing issued early).
-//   4 = 3, and on every turn the head words of both rounds come in ONE two-address read (ds_read2st64_b32 in place of ds_read_b32): the
-//       second round starts at its rank, one exposed round trip instead of two, and the one-round turn is no instruction longer.
-//   Measured on C2, five alternating runs each, steps/s against the parent: 1 -4.7 %, 2 -4.0 % (the two arms meet in register copies
-//   and 0 / 1 conditions: common turn 338 -> 354 instructions; 2 against 1 is what its covered waits buy, +0.8 .. +1.0 %), 3 +1.1 .. +1.7 %
-//   (passes the rule in one series of three), 4 +2.9 .. +3.3 %, passing in every series: adopted.  Per wave-turn 4 takes 60 cycles less
-//   (1976 -> 1917), 45 of them SQ_WAIT_ANY; 3 takes 25 less, 10 of them waits.
-#ifndef GE_QUEUE_ROUND2
-#define GE_QUEUE_ROUND2 4
-#endif
 #ifndef GE_ROWS_SPLIT
 #define GE_ROWS_SPLIT 1
 #endif
@@ -195,9 +98,9 @@ template <int NB, bool LOWOCC, bool SINGLE = false> struct WwBuild {
     static constexpr bool PIN_CHOICE = LOWOCC && NB > 8;    // the slot's choice computed outside its `acts this turn` region (r02_ab_sel_pin)
     static constexpr bool SEL_OPEN = LOWOCC;                // completion test without short-circuit evaluation (r02_ab_open_tpldeal)
     static constexpr bool TPL_TRACE = LOWOCC;               // the turn loop compiled once per trace setting (r02_ab_branch_diet)
-    // DEAL_PACKED / DEAL_MASKS / DEAL_WORDS, see struct Deal.  Fused N <= 8: words, lone wavefront (GE_LONE_DEAL_WORDS) and large batch alike;
-    // Werewolf x 12 lone keeps the masks (its words are more registers, and that build was not counted)
-    static constexpr int DEAL_FORM = SINGLE ? 2 : NB <= 8 ? ((LOWOCC && !GE_LONE_DEAL_WORDS) ? 0 : 1) : LOWOCC ? 0 : 2;
+    // DEAL_PACKED / DEAL_MASKS / DEAL_WORDS, see struct Deal.  Fused N <= 8: words, lone wavefront (converted once per deal, not on every
+    // turn: profiles/ab_lone_once_per_game.txt) and large batch alike; Werewolf x 12 lone keeps the masks (its words are more registers)
+    static constexpr int DEAL_FORM = SINGLE ? 2 : NB <= 8 ? 1 : LOWOCC ? 0 : 2;
     static constexpr bool DEAL_EARLY = GE_DEAL_EARLY && !LOWOCC && !SINGLE;   // the deal is prepared at the head of the turn, not in the queue's second LDS shadow (see ww_turn)
     static constexpr bool TABLE = !LOWOCC;                  // n-th-set-bit through the 2 KB LDS table instead of ~15 VALU instructions
     // the fused lone-wavefront turn of Werewolf x 8 may recycle a finished room where it enters its terminal row (ww_apply_effect,
@@ -374,17 +277,11 @@ __device__ __forceinline__ uint32_t plurality(nib_t votes, uint32_t voters, cons
         // 32-bit counters: a vote for player 8 would be nibble 8; its shift (32) wraps to nibble 0,
         // which nobody reads, and player 8 is counted from bit 3 of the vote nibbles instead
         const uint32_t v32 = (uint32_t)v;
-        uint32_t tally = 0;
-        if (GE_TALLY_BYTES) {
-            // the votes as bytes of 4 * nibble (even players in one register, odd ones in the other); nibbles of players >= NB are
-            // masked out above and add 1 << 0 each, to the nibble nobody reads
-            const uint32_t ev = (v32 << 2) & 0x3C3C3C3Cu, od = (v32 >> 2) & 0x3C3C3C3Cu, one = 1u;
-            tally = (shl_by_byte<0>(one, ev) + shl_by_byte<0>(one, od) + shl_by_byte<1>(one, ev)) + (shl_by_byte<1>(one, od) + shl_by_byte<2>(one, ev))
-                  + (shl_by_byte<2>(one, od) + shl_by_byte<3>(one, ev)) + shl_by_byte<3>(one, od);
-        } else {
-#pragma unroll
-            for (int i = 0; i < NB; i++) tally += 1u << ((4u * ((v32 >> (4 * i)) & 15u)) & 31u);
-        }
+        // the votes as bytes of 4 * nibble (even players in one register, odd ones in the other), so that a voter's increment is one shift
+        // by a byte select (profiles/ab_lone_tally.txt); nibbles of players >= NB are masked out above and add 1 << 0 each, to the nibble nobody reads
+        const uint32_t ev = (v32 << 2) & 0x3C3C3C3Cu, od = (v32 >> 2) & 0x3C3C3C3Cu, one = 1u;
+        const uint32_t tally = (shl_by_byte<0>(one, ev) + shl_by_byte<0>(one, od) + shl_by_byte<1>(one, ev)) + (shl_by_byte<1>(one, od) + shl_by_byte<2>(one, ev))
+                             + (shl_by_byte<2>(one, od) + shl_by_byte<3>(one, ev)) + shl_by_byte<3>(one, od);
         {
             // two keys per register, 16 bits each: counters 1 / 5 sit at bits 4..7 of the two halves already (count << 4),
             // 2 / 6, 3 / 7 and 4 after a shift; player 8's count comes from bit 3 of the vote nibbles
@@ -432,13 +329,10 @@ struct WaveLdsLow {
     uint4 slot[64 * 13 + 80];  // + scratch for rooms without a due bot (lane .. lane + 12)
     uint4 res[64];
 };
-// GE_PULL_QUEUE 1 / 2 (the fused lone-wavefront Werewolf x 8 turn): contexts stored once, slots find their owner.
-//   1: cctx[r] = the context of the r-th room that has a due bot, cctx[64 + lane] = scratch of a room without one; head[k] = the stamp
-//      of the turn in which slot k was last some room's first slot.  head[] is zeroed once per wavefront (run_ww) and never cleared: a
-//      stamp is the absolute turn + 1, never 0 and a new value on every turn of a batch's 32-bit clock - which is why it is a word and not a byte:
-//      a byte would come round again after 256 turns of a launch of 1 024, in a word that no turn in between rewrote (the high slots are
-//      written on the first turn of a vote only), and a stale head would have to be cleared every turn; the store costs the same either way.
-//   2: cctx[lane] = the room's context, the head[] words hold the byte queue (slot -> lane, + scratch behind 64 * 13 as in WaveLdsLow)
+// The pull form of the queue (the fused lone-wavefront Werewolf x 8 turn; profiles/ab_lone_pull_queue.txt): contexts stored once, slots find
+// their owner.  cctx[r] = the context of the r-th room that has a due bot, cctx[64 + lane] = scratch of a room without one; head[k] = the
+// stamp of the turn in which slot k was last some room's first slot.  head[] is zeroed once per wavefront (run_ww) and never cleared: a
+// stamp is the absolute turn + 1, never 0 and a new value on every turn of a batch's 32-bit clock (why a word and not a byte: DESIGN.md 10).
 struct WaveLdsPull {
     uint4 cctx[128];
     uint4 res[64];
@@ -467,6 +361,11 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// base + the number of lanes below this one whose bit is set in `mask` (a ballot; shifted down by one: the lanes up to and including this one, less lane 0)
+__device__ __forceinline__ uint32_t lanes_below(uint64_t mask, uint32_t base) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, base));
 }
 
 // exclusive prefix sum of a small per-lane count over the wavefront, and the wave total (uniform)
@@ -940,13 +839,12 @@ struct WwCtx {
 // one LDS read the move issues anyway - and the turn loop's head has no restart block.  A room that is ALREADY terminal when
 // the launch loads it is recycled in front of the loop (run_ww); a table whose first phase is terminal keeps the head form.
 // Whether a turn recycles is a fact of the launch (restart on / off) and of the turn (a launch's last turn stores terminal rooms as they
-// are), so the turn is compiled per answer (GE_TAIL_KNOWN_RESTART): TAIL_RECYCLE - a lane that enters a terminal row leaves as the fresh
-// room, and nothing records `end_turn` (see ww_apply_effect); TAIL_KEEP - no lane is recycled: no merge with the fresh room at all.
-// TAIL_RUNTIME is the form that reads the answer from rst->term_rs on every turn (GE_TAIL_KNOWN_RESTART = 0).
-enum { TAIL_NONE = 0, TAIL_RUNTIME = 1, TAIL_RECYCLE = 2, TAIL_KEEP = 3 };
+// are), so the turn is compiled per answer (profiles/ab_lone_once_per_game.txt): TAIL_RECYCLE - a lane that enters a terminal row leaves as
+// the fresh room, and nothing records `end_turn` (see ww_apply_effect); TAIL_KEEP - no lane is recycled: no merge with the fresh room at all.
+enum { TAIL_NONE = 0, TAIL_RECYCLE = 2, TAIL_KEEP = 3 };
 template <int NB> struct WwRestart {
     const WWR<NB> *s0;         // the fresh room (wave-uniform: scalar registers)
-    uint32_t term_rs;          // in: the table's terminal-row mask if a room may be recycled at the end of this turn, else 0 (TAIL_KEEP: not read)
+    uint32_t term_rs;          // in: the table's terminal-row mask (TAIL_RECYCLE; TAIL_KEEP: not read)
     uint32_t restarted;        // out: 1 = the lane was recycled at the end of this turn (the next turn's `restarted` trace bit)
     uint32_t q;                // out: the row the turn moved to (a recycled lane's terminal row: what the trace records)
 };
@@ -955,7 +853,7 @@ template <int NB> struct WwRestart {
 // The 12 base predicates live packed in s.W; the row carries byte-permute selectors that pull each term's mask out of
 // the word pairs (0xFF where the term is elsewhere / absent), so the condition is 2-3 v_perm + AND, XOR with the
 // negation mask, and a fold of the term bytes (ge_layout.h DevRow).
-// DER (GE_ROW_DERIVED): the low byte of the row's derived word is ALL for an `action` row and 0 otherwise (alive has no higher bits)
+// DER (the fused lone Werewolf x 8 turn; profiles/ab_lone_row_const.txt): the low byte of the row's derived word (DevRow r6) is ALL for an `action` row and 0 otherwise (alive has no higher bits)
 template <int NB, bool LOWOCC, int GENERIC, bool DER = false>
 __device__ __forceinline__ uint32_t ww_targets(const WWR<NB> &s, const DevRow &row, const WwCtx &c, uint32_t alive, uint32_t ALL) {
     using R = WWR<NB>;
@@ -1021,12 +919,11 @@ __device__ __forceinline__ void ww_phase_branch(const WWR<NB> &s, const DevRow &
 // ---- `deal_now` (wave-uniform, every GE_DEAL_PERIOD-th turn): lanes without a prepared deal compute their next one; then the
 // role-assignment values of the prepared deal (what an assignment writes) - except in the packed form, which only the
 // assigning lanes expand (ww_apply_effect)
-// COLD (GE_COLD_DEAL_NOW, the tail-recycling turn loops; measured, off): `deal_now` is marked unlikely - the block leaves the turn's straight line
-template <int NB, bool LOWOCC, bool SINGLE, bool COLD = false>
+template <int NB, bool LOWOCC, bool SINGLE>
 __device__ __forceinline__ void ww_prepare_deal(const WWR<NB> &s, const WwCtx &c, Deal &deal, bool deal_now, uint32_t ALL, WWR<NB> &dealt) {
     using B = WwBuild<NB, LOWOCC, SINGLE>;
     const uint32_t g = deal_next_game<NB>(s);
-    if ((COLD ? __builtin_expect(deal_now, false) : deal_now) && deal.gv != (g | DEAL_VALID)) {             // no deal, or (single-turn Werewolf x 12: an entry of the side plane) one for another game
+    if (deal_now && deal.gv != (g | DEAL_VALID)) {             // no deal, or (single-turn Werewolf x 12: an entry of the side plane) one for another game
         deal_roles<NB, B::TABLE, B::DEAL_FORM>(deal, deal_key(c.rkey, g), g, c.n, c.nw, c.nth8);
     }
     if (B::DEAL_FORM != DEAL_PACKED) deal_words<NB, B::DEAL_FORM>(deal, ALL, dealt);
@@ -1040,22 +937,17 @@ __device__ __forceinline__ void ww_prepare_deal(const WWR<NB> &s, const WwCtx &c
 struct WwActs { uint32_t newly, det_v, det_w; };   // who acted now; the Detective's new knowledge (villager / werewolf)
 
 // LONE8: the fused lone-wavefront Werewolf x 8 turn without generic rows - `rowd` is the row's derived word and `nmask` its night flag
-// as 0 / ~0 (GE_ROW_DERIVED: `act` and `night` are then not read), `skip` is the launch's per-lane mask (GE_SKIP_MASK: c.human for a valid
-// lane, all ones for a lane past the segment's end - made once in front of the turn loop, ge_kernels.inl run_ww), SKIP_GIVEN: the caller has it
-template <int NB, bool LOWOCC, bool FUSED = false, bool LONE8 = false, bool SKIP_GIVEN = false, typename S1, typename S2>
+// as 0 / ~0 (`act` and `night` are then not read: profiles/ab_lone_row_const.txt), `qstamp` the turn's head stamp.  That turn's queue is the
+// pull form (WaveLdsPull) and its second round stands out of line (below)
+template <int NB, bool LOWOCC, bool FUSED = false, bool LONE8 = false, typename S1, typename S2>
 __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uint32_t T, uint32_t act, bool night, uint32_t alive, uint32_t team_w,
                                                  uint32_t r_det, uint32_t tk, WwActs &out, S1 &&shadow1, S2 &&shadow2, Stamps *stamps,
-                                                 uint32_t rowd = 0u, uint32_t nmask = 0u, uint32_t skip = 0u, uint32_t qstamp = 0u) {
+                                                 uint32_t rowd = 0u, uint32_t nmask = 0u, uint32_t qstamp = 0u) {
     using nib_t = typename WWR<NB>::nib_t;
     using B = WwBuild<NB, LOWOCC>;
-    constexpr int PULL = LONE8 ? GE_PULL_QUEUE : 0;          // (LONE8: LOWOCC, FUSED and NB <= 8)
-    constexpr int R2 = PULL == 1 ? GE_QUEUE_ROUND2 : 0;      // the two-round turn as a block of its own (below)
-    constexpr bool R2_ARMS = R2 == 1 || R2 == 2;             // .. from the stores on; 3 / 4: from the first fetch on
-    auto *pq = static_cast<WaveLdsPull *>(c.wave_lds);
-    constexpr bool DER = LONE8 && GE_ROW_DERIVED, PERM = LONE8 && GE_CTX_PERM && NB <= 8, UNMASKED = LONE8 && GE_RES_UNMASKED && B::ONE_ATOMIC;
-    constexpr bool SKIPM = GE_SKIP_MASK && SKIP_GIVEN;
+    auto *pq = static_cast<WaveLdsPull *>(c.wave_lds);       // (LONE8: LOWOCC, FUSED and NB <= 8)
     auto *lw = static_cast<typename WaveLdsOf<LOWOCC>::type *>(c.wave_lds);
-    const uint32_t todo = SKIPM ? (T & ~s.acted & ~skip) : c.valid ? (T & ~s.acted & ~c.human) : 0u;
+    const uint32_t todo = c.valid ? (T & ~s.acted & ~c.human) : 0u;
     const uint32_t known = s.det_v | s.det_w;
     const uint32_t kw_alive = s.det_w & alive;
     const uint32_t lo_kw = kw_alive & (0u - kw_alive);       // lowest known living werewolf
@@ -1081,18 +973,16 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
     }
     // per-room context of an action; `ky`: what the acting role knows (the Detective's memory
     // at night, who the Detective is by day - ww_choose reads only one of the two per kind)
-    const uint32_t ky = DER ? bfi(nmask, known, lo_kw != 0u ? r_det : 0u) : night ? known : (B::ONEHOT ? (lo_kw != 0u ? r_det : 0u) : r_det);
+    const uint32_t ky = LONE8 ? bfi(nmask, known, lo_kw != 0u ? r_det : 0u) : night ? known : (B::ONEHOT ? (lo_kw != 0u ? r_det : 0u) : r_det);
     const uint32_t kind = B::ONEHOT ? ((1u << act) >> 1) : act;          // one-hot: ACT_WOLF_TARGET = 1 -> bit 0 ...
-    // GE_CTX_PERM: alive (byte 0 of W0) and team_w (byte 3 of W1) into bytes 0 and 2, zero bytes between (selector 0x0C), by one permute
-    static_assert(F_ALIVE == 0 && F_TEAM_W == 7, "the selector below is made for this layout");
-    const uint32_t at = PERM ? __builtin_amdgcn_perm(s.W[1], s.W[0], 0x0C070C00u) : alive | (team_w << 16);
-    const uint32_t x0 = DER ? at | (rowd & (0xFu << ROWD_KIND_SHIFT)) : at | (kind << 28);
+    const uint32_t at = alive | (team_w << 16);
+    const uint32_t x0 = LONE8 ? at | (rowd & (0xFu << ROWD_KIND_SHIFT)) : at | (kind << 28);
     const uint4 ctx = B::ORD ? make_uint4(x0, ky | (lo_kw << 8) | (off << 16) | (lane << 26), ord, tk)
                              : make_uint4(alive | (team_w << 16) | (act << 28), ky | (lo_kw << 16), todo | (off << 16) | (lane << 26), tk);
     // N <= 8: only x, y come back - the results sit 8 bytes apart (GE_RES_PACKED; 16 bytes apart, a 64-bit access of 16 consecutive
     // lanes hits every bank twice: /opt/skills/guides/MI355X_MICROARCH.md "LDS", ds_write_b64 / ds_read_b64 banking)
     constexpr uint32_t RW = (NB <= 8 && GE_RES_PACKED) ? 2u : 4u;      // words per room in `res`
-    uint32_t *const res_w = PULL ? reinterpret_cast<uint32_t *>(pq->res) : reinterpret_cast<uint32_t *>(lw->res);
+    uint32_t *const res_w = LONE8 ? reinterpret_cast<uint32_t *>(pq->res) : reinterpret_cast<uint32_t *>(lw->res);
     if (NB <= 8) *reinterpret_cast<uint2 *>(res_w + RW * lane) = make_uint2(0u, 0u);
     else lw->res[lane] = make_uint4(0u, 0u, 0u, 0u);
     // Queue slot -> owning room.  A room with cnt due bots owns slots [off, off + cnt); it writes
@@ -1101,24 +991,14 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
     // overwritten by their owners: an owner's write to its r-th slot is issued at step r,
     // any intruder's at a step > r, i.e. earlier.  Rooms without a due bot do not write
     // (they would tie with the next owner inside one instruction).
-    if (PULL == 1 && R2_ARMS) {
-        // (behind the decision between the one-round and the two-round turn, below: a copy of these four lines in either arm)
-    } else if (PULL == 1) {
-        // the context once, at the room's rank among the owners (a room without a due bot: into the scratch behind them), and the turn's
-        // stamp into the head word of the room's first slot.  No predicate on that one either: a room without a due bot has the `off` of the
-        // next owner and writes the same word there, the trailing ones write head[total], which no slot below `total` reads
-        const uint64_t nz = __builtin_amdgcn_ballot_w64(cnt != 0u);
-        const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(nz >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nz, 0u));
+    if (LONE8) {
+        // the pull form (profiles/ab_lone_pull_queue.txt): the context once, at the room's rank among the owners (a room without a due bot: into
+        // the scratch behind them), and the turn's stamp into the head word of the room's first slot.  No predicate on that one either: a room
+        // without a due bot has the `off` of the next owner and writes the same word there, the trailing ones write head[total], which no slot
+        // below `total` reads
+        const uint32_t r = lanes_below(__builtin_amdgcn_ballot_w64(cnt != 0u), 0u);
         pq->cctx[cnt != 0u ? r : 64u + lane] = ctx;
         pq->head[off] = qstamp;
-    } else if (PULL == 2) {
-        pq->cctx[lane] = ctx;
-        uint8_t *qp = reinterpret_cast<uint8_t *>(pq->head) + (cnt != 0u ? off : 64u * 13u + lane);
-#pragma unroll
-        for (int j = NB - 1; j >= 0; j--) {
-            qp[j] = (uint8_t)lane;
-            asm volatile("" ::: "memory");             // the stores must issue in this order
-        }
     } else if (LOWOCC) {
         auto *lo = reinterpret_cast<WaveLdsLow *>(lw);
         // no predicate here either: a room without a due bot writes to a scratch range behind the queue
@@ -1140,30 +1020,27 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
             }
         }
     }
-    if (!R2_ARMS) wave_sync();
+    wave_sync();
     // slot k -> the owning room's context (slots past `total` hold stale entries: computed like the
     // others, result dropped).  The first round's read is issued BEFORE the shadow work below.
-    uint32_t heads_before = 0;                             // PULL == 1: head slots in the rounds before this one (wave-uniform)
-    auto fetch = [&](uint32_t k, bool first = false) -> uint4 {
-        if (PULL == 1) {
-            // the slot's owner is the last head at or before it: its rank is the heads of the earlier rounds (a segment that straddles a
-            // round boundary finds the last head before `base`) + those of this round up to and including the lane - 1.  Counted as the
-            // heads ABOVE the round's first slot up to the lane (the ballot shifted down by one: what mbcnt counts below a lane) on top of
-            // a scalar; the first round's first slot is always a head (lane 0 has off == 0) and nothing stands before it: the scalar is 0
-            const bool is_head = pq->head[k] == qstamp;
-            const uint64_t hb = __builtin_amdgcn_ballot_w64(is_head), above = hb >> 1;
-            const uint32_t at0 = first ? 0u : heads_before + ((uint32_t)hb & 1u) - 1u;
+    uint32_t heads_before = 0;                             // LONE8: head slots in the rounds before this one (wave-uniform)
+    auto fetch = [&](uint32_t k) -> uint4 {
+        if (LONE8) {
+            // a round behind the first.  The slot's owner is the last head at or before it: its rank is the heads of the earlier rounds (a
+            // segment that straddles a round boundary finds the last head before `base`) + those of this round up to and including the
+            // lane - 1.  Counted as the heads ABOVE the round's first slot up to the lane (the ballot shifted down by one) on top of a scalar
+            const uint64_t hb = __builtin_amdgcn_ballot_w64(pq->head[k] == qstamp);
+            const uint32_t at0 = heads_before + ((uint32_t)hb & 1u) - 1u;
             heads_before += (uint32_t)__builtin_popcountll(hb);
-            return pq->cctx[__builtin_amdgcn_mbcnt_hi((uint32_t)(above >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)above, at0))];
+            return pq->cctx[lanes_below(hb >> 1, at0)];
         }
-        if (PULL == 2) return pq->cctx[reinterpret_cast<const uint8_t *>(pq->head)[k] & 63u];
         if (LOWOCC) return reinterpret_cast<WaveLdsLow *>(lw)->slot[k];
         auto *hi = reinterpret_cast<WaveLds *>(lw);
         return hi->ctx[hi->queue[k] & 63u];
     };
     uint4 c4;
-    if (!R2) {
-        c4 = fetch(lane, true);
+    if (!LONE8) {
+        c4 = fetch(lane);
         if (B::SHADOW) shadow1();
     }
     // Fused lone wavefront: the first round stands outside the loop over rounds, with shadow2 in its block, where the scheduler
@@ -1175,9 +1052,9 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
     // front of the wait gained nothing (same file; tools/asm_shadow.py shows what stands where).
     // Every other build keeps the loop below as it was, instruction for instruction
     constexpr bool PEEL = LOWOCC && FUSED && B::SHADOW;
-    static_assert(!R2 || PEEL, "the two-round block is a form of the peeled first round");
+    static_assert(!LONE8 || PEEL, "the pull form's out-of-line second round is a form of the peeled first round");
     if (PEEL) {
-        auto round = [&](uint32_t base, auto first_c) {    // the loop's body below, for a lone wavefront
+        auto round = [&](uint32_t base) {                  // the loop's body below, for a lone wavefront
             const uint32_t k = base + lane;
             if (GE_STAMPS == 1 && stamps && base == 0u) { asm volatile("" :: "v"(c4.x)); stamps->mark(1); }   // [.. first slot in registers]
             uint32_t L, i, know, lokw;
@@ -1197,106 +1074,41 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
             uint32_t ch = B::ONEHOT ? ww_choose_onehot8(c4.x, i, d, know, lokw, know)
                                     : ww_choose<NB, false>(c4.x >> 28, i, d, c4.x & 0xFFFFu, (c4.x >> 16) & 0xFFFu, know, lokw, know, c.nth8);
             if (B::PIN_CHOICE) asm volatile("" : "+v"(ch));
-            if (UNMASKED && decltype(first_c)::value) {
-                // every lane: no exec-mask region (a scalar pair and a branch).  L is 6 bits of whatever the slot holds: in range
-                atomicOr(res_w + RW * L + 1, go ? ch << (4u * i) : 0u);
-            } else if (go) {
+            if (go) {
                 uint32_t *r = res_w + RW * L;
                 if (!B::ONE_ATOMIC) atomicOr(r, 1u << i);
                 atomicOr(r + 1 + (i >> 3), ch << (4u * (i & 7u)));
             }
         };
-        if (R2 >= 3) {
-            // GE_QUEUE_ROUND2 3 / 4: the stores, both shadows and round 0 once, for either turn - the two arms of 1 / 2 meet again in
-            // register copies and in conditions that cross the branch as 0 / 1 values, which the one-round turn pays too (+16 instructions).
-            // Only the second round and the loop behind it are out of line: marked unlikely for where the block is laid out, behind the
-            // turn loop's back edge as GE_COLD_FALLBACK's deal is, so that the one-round turn falls through its test of `total`
-            uint32_t h1w = 0;
-            if (R2 == 4) {
-                // on every turn head[64 + lane] comes with head[lane]: one two-address read in place of a one-address read, no instruction
-                // more.  The second round then starts at its rank (`fetch`: the heads of the round before + whether its first slot is one
-                // - 1, so a segment that straddles 63 | 64 finds the last head before 64) and has one exposed LDS round trip, not two
-                const uint32_t h0w = pq->head[lane];
-                h1w = pq->head[64u + lane];
-                const uint64_t b0 = __builtin_amdgcn_ballot_w64(h0w == qstamp), a0 = b0 >> 1;
-                heads_before = (uint32_t)__builtin_popcountll(b0);
-                c4 = pq->cctx[__builtin_amdgcn_mbcnt_hi((uint32_t)(a0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)a0, 0u))];
-            } else {
-                c4 = fetch(lane, true);
-            }
+        if (LONE8) {
+            // The head words of both rounds come in ONE two-address read on every turn (no instruction more than a one-address read).  The
+            // first round's first slot is always a head (lane 0 has off == 0) and nothing stands before it; the second round then starts at
+            // its rank (as in `fetch`) with one exposed LDS round trip, not two (profiles/ab_lone_round2.txt)
+            const uint32_t h0w = pq->head[lane], h1w = pq->head[64u + lane];
+            const uint64_t b0 = __builtin_amdgcn_ballot_w64(h0w == qstamp);
+            heads_before = (uint32_t)__builtin_popcountll(b0);
+            c4 = pq->cctx[lanes_below(b0 >> 1, 0u)];
             shadow1();
             shadow2();
-            round(0u, std::true_type{});
+            round(0u);
+            // a wavefront has more than 64 due actions on about 0.44 of its turns; marked unlikely only for where the block is laid out: behind
+            // the turn loop's back edge, as ww_apply_effect's fallback deal is, so that the one-round turn falls through its test of `total`
             if (__builtin_expect(total > 64u, 0)) {
-                if (R2 == 4) {
-                    const uint64_t b1 = __builtin_amdgcn_ballot_w64(h1w == qstamp), a1 = b1 >> 1;
-                    c4 = pq->cctx[__builtin_amdgcn_mbcnt_hi((uint32_t)(a1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)a1, heads_before + ((uint32_t)b1 & 1u) - 1u))];
-                    heads_before += (uint32_t)__builtin_popcountll(b1);
-                } else {
-                    c4 = fetch(64u + lane);
-                }
-                round(64u, std::false_type{});
+                const uint64_t b1 = __builtin_amdgcn_ballot_w64(h1w == qstamp);
+                c4 = pq->cctx[lanes_below(b1 >> 1, heads_before + ((uint32_t)b1 & 1u) - 1u)];
+                heads_before += (uint32_t)__builtin_popcountll(b1);
+                round(64u);
                 for (uint32_t base = 128u; base < total; base += 64u) {   // a third and later round: rare (the first day vote after a reset takes eight)
                     c4 = fetch(base + lane);
-                    round(base, std::false_type{});
+                    round(base);
                 }
-            }
-        } else if (R2) {
-            // GE_QUEUE_ROUND2: one wave-uniform decision as soon as the scan has `total`; each arm is a straight line from the stores on.
-            // The two-round turn (0.44 of a 64-room wavefront's turns) is marked unlikely only for where it is laid out: behind the turn
-            // loop's back edge, as GE_COLD_FALLBACK's deal is, so that the one-round turn falls through and never tests `total` again
-            if (__builtin_expect(total > 64u, 0)) {
-                {   // the owner's stores, as above
-                    const uint64_t nz = __builtin_amdgcn_ballot_w64(cnt != 0u);
-                    const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(nz >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nz, 0u));
-                    pq->cctx[cnt != 0u ? r : 64u + lane] = ctx;
-                    pq->head[off] = qstamp;
-                }
-                wave_sync();
-                uint4 c4b;                                 // R2 == 2: the second round's slot, in registers of its own
-                if (R2 == 2) {
-                    // both head words behind the same wave_sync; the second round's rank from the first's heads (`fetch`: the heads of
-                    // the earlier rounds + whether this round's first slot is one - 1, so a segment that straddles 63 | 64 finds the last
-                    // head before 64), and its context read issued straight behind the first's, in front of both shadows and round 0
-                    const bool h0 = pq->head[lane] == qstamp, h1 = pq->head[64u + lane] == qstamp;
-                    const uint64_t b0 = __builtin_amdgcn_ballot_w64(h0), b1 = __builtin_amdgcn_ballot_w64(h1), a0 = b0 >> 1, a1 = b1 >> 1;
-                    const uint32_t n0 = (uint32_t)__builtin_popcountll(b0), at1 = n0 + ((uint32_t)b1 & 1u) - 1u;
-                    c4 = pq->cctx[__builtin_amdgcn_mbcnt_hi((uint32_t)(a0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)a0, 0u))];
-                    c4b = pq->cctx[__builtin_amdgcn_mbcnt_hi((uint32_t)(a1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)a1, at1))];
-                    heads_before = n0 + (uint32_t)__builtin_popcountll(b1);
-                } else {
-                    c4 = fetch(lane, true);
-                }
-                shadow1();
-                shadow2();
-                round(0u, std::true_type{});
-                if (R2 == 2) c4 = c4b; else c4 = fetch(64u + lane);
-                round(64u, std::false_type{});
-                // (as c4 below: the second set stays reserved while the queue's traffic may be in flight)
-                if (R2 == 2) asm volatile("" :: "v"(c4b.x), "v"(c4b.y), "v"(c4b.z), "v"(c4b.w));
-                for (uint32_t base = 128u; base < total; base += 64u) {   // a third and later round: rare (the first day vote after a reset takes eight)
-                    c4 = fetch(base + lane);
-                    round(base, std::false_type{});
-                }
-            } else {
-                {   // the owner's stores, as above
-                    const uint64_t nz = __builtin_amdgcn_ballot_w64(cnt != 0u);
-                    const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(nz >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nz, 0u));
-                    pq->cctx[cnt != 0u ? r : 64u + lane] = ctx;
-                    pq->head[off] = qstamp;
-                }
-                wave_sync();
-                c4 = fetch(lane, true);
-                shadow1();
-                shadow2();
-                round(0u, std::true_type{});
             }
         } else {
             shadow2();
-            round(0u, std::true_type{});
+            round(0u);
             for (uint32_t base = 64u; base < total; base += 64u) {   // wave-uniform; a round's read is issued only if it is needed
                 c4 = fetch(base + lane);
-                round(base, std::false_type{});
+                round(base);
             }
         }
     } else {
@@ -1378,13 +1190,13 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
     }
     s.choice = (s.choice & ~m15) | got;
     // RefereeNode (A): record the action (bt:204-225 update_player_state)
-    s.sel = DER ? (nib_t)bfi(nmask, (uint32_t)((s.sel & ~m15) | got), (uint32_t)s.sel) : night ? ((s.sel & ~m15) | got) : s.sel;
+    s.sel = LONE8 ? (nib_t)bfi(nmask, (uint32_t)((s.sel & ~m15) | got), (uint32_t)s.sel) : night ? ((s.sel & ~m15) | got) : s.sel;
     if (B::ONEHOT && FUSED) {
         // the lowest non-zero choice nibble is the first new actor's (a choice is >= 1); no actor: nibble 7 = 0, and (1 << 0) >> 1 = 0.
         // `act == ACT_DETECTIVE` is bit 2 of the one-hot kind: a mask, no compare
         const uint32_t g = (uint32_t)got;
         const uint32_t ch = (g >> ((uint32_t)__builtin_ctz(g | 0x80000000u) & 28u)) & 15u;
-        const uint32_t tb = ((1u << ch) >> 1) & (DER ? bit_mask(rowd, ROWD_KIND_SHIFT + 2u) : bit_mask(kind, 2u));
+        const uint32_t tb = ((1u << ch) >> 1) & (LONE8 ? bit_mask(rowd, ROWD_KIND_SHIFT + 2u) : bit_mask(kind, 2u));
         out.det_w = tb & team_w;
         out.det_v = tb & ~team_w;
     } else {
@@ -1398,7 +1210,7 @@ __device__ __forceinline__ void ww_queue_actions(WWR<NB> &s, const WwCtx &c, uin
 }
 
 // ---- PhaseNode: completion (every target player has acted in this visit) and the chosen branch
-// T_MASKED (GE_ROW_DERIVED): T is 0 in a row whose completion is not `action` (ww_targets), so the test of `comp` says nothing more
+// T_MASKED (the fused lone Werewolf x 8 turn): T is 0 in a row whose completion is not `action` (ww_targets), so the test of `comp` says nothing more
 template <int NB, bool LOWOCC, bool T_MASKED = false>
 __device__ __forceinline__ uint32_t ww_decide(const WWR<NB> &s, uint32_t comp, uint32_t T, const WwBranch &b) {
     if (T_MASKED) return sel32(b.open & ((T & ~s.acted) == 0u), b.qe, s.phase);
@@ -1441,9 +1253,10 @@ __device__ __forceinline__ void ww_apply_effect(WWR<NB> &s, const DevRow &row, c
     };
     // role assignment: the deal of this game was normally prepared ahead (ww_prepare_deal, every GE_DEAL_PERIOD-th turn,
     // for all lanes of the wavefront at once); fall back to dealing here if it was not
-    // (TAILR, GE_COLD_FALLBACK: behind a wave-uniform vote first - almost no turn of a fused run has a lane without its deal)
+    // (TAILR: behind a wave-uniform vote marked unlikely, so that the deal is laid out behind the turn loop - almost no turn of a fused run
+    // has a lane without its deal: profiles/ab_lone_cold_deal.txt)
     const bool is_assign = eff == EFF_ASSIGN_ROLES;
-    if (TAILR && GE_COLD_FALLBACK) {
+    if (TAILR) {
         const bool need_deal = is_assign && deal.gv != (s.games | DEAL_VALID);
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(need_deal) != 0u, 0)) {
             if (need_deal) {
@@ -1496,8 +1309,8 @@ __device__ __forceinline__ void ww_apply_effect(WWR<NB> &s, const DevRow &row, c
         s.end_turn = (terminal && s.end_turn == END_NONE) ? (turn < 0xFFFEu ? turn : 0xFFFEu) : s.end_turn;
     } else {
         s.acted &= ~moved; s.choice &= (nib_t)~moved;
-        // (GE_ROW_DERIVED: FLAG_PHASE0_DONE is set on every turn before the move - ww_turn - so the new flags are a byte of the row)
-        s.flags = bfi(moved, GE_ROW_DERIVED ? (row.r6 >> ROWD_FLAGS_SHIFT) & 0xFFu : (s.flags & FLAG_PHASE0_DONE) | (p_eff << 1), s.flags);
+        // (FLAG_PHASE0_DONE is set on every turn before the move - ww_turn - so the new flags are a byte of the row's derived word)
+        s.flags = bfi(moved, (row.r6 >> ROWD_FLAGS_SHIFT) & 0xFFu, s.flags);
         s.prev = bfi(moved, s.phase, s.prev);
         s.phase = q;                                           // (a lane that stays has q == s.phase)
         if (TAILR != TAIL_RECYCLE) {
@@ -1505,7 +1318,7 @@ __device__ __forceinline__ void ww_apply_effect(WWR<NB> &s, const DevRow &row, c
             s.end_turn = (terminal && moved != 0u && s.end_turn == END_NONE) ? (turn < 0xFFFEu ? turn : 0xFFFEu) : s.end_turn;
         }
     }
-    if (TAILR == TAIL_RUNTIME || TAILR == TAIL_RECYCLE) {
+    if (TAILR == TAIL_RECYCLE) {
 #pragma unroll
         for (int k = 0; k < R::NW; k++) s.W[k] = bfi_uniform(rmask, s0->W[k], s.W[k]);
         s.acted |= rmask & s0->acted; s.choice |= (nib_t)rmask & s0->choice;      // (both were just cleared)
@@ -1523,10 +1336,10 @@ __device__ __forceinline__ void ww_apply_effect(WWR<NB> &s, const DevRow &row, c
 // tk_io: in = turn_key(rkey, turn), out = the next turn's key (computed in an LDS wait shadow; not in a single-turn build).
 // ev_*: this turn's logged actions (who acted, what they chose) for the optional event trace.
 // TAILR: TAIL_NONE = the head form; else the tail form - rooms that finish are recycled at the end of the turn (`rst`, WwRestart):
-// on every turn (TAIL_RECYCLE), on none (TAIL_KEEP), or as rst->term_rs says (TAIL_RUNTIME)
+// on every turn (TAIL_RECYCLE) or on none (TAIL_KEEP)
 template <int NB, bool LOWOCC, int GENERIC = false, bool SINGLE = false, int TAILR = TAIL_NONE>
 __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c, uint32_t turn, uint32_t &tk_io, bool trace, Deal &deal, bool deal_now,
-                                        uint32_t &ev_newly, uint64_t &ev_choice, Stamps *stamps = nullptr, WwRestart<NB> *rst = nullptr, uint32_t skip = 0u) {
+                                        uint32_t &ev_newly, uint64_t &ev_choice, Stamps *stamps = nullptr, WwRestart<NB> *rst = nullptr) {
     static_assert(!TAILR || (NB <= 8 && LOWOCC && !SINGLE), "tail recycling is the fused lone-wavefront Werewolf x 8 form");
     using R = WWR<NB>;
     using B = WwBuild<NB, LOWOCC, SINGLE>;
@@ -1535,11 +1348,12 @@ __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c,
     const uint32_t alive = s.template get<F_ALIVE>(), team_w = s.template get<F_TEAM_W>(), r_det = s.template get<F_DET>();
     const bool night = act >= ACT_WOLF_TARGET && act <= ACT_DETECTIVE;
 
-    // the fused lone-wavefront Werewolf x 8 turn without generic rows: what the GE_ROW_DERIVED .. GE_RES_UNMASKED switches apply to
-    constexpr bool LONE8 = B::LONE && GENERIC == 0, DER = LONE8 && GE_ROW_DERIVED;
-    const uint32_t rowd = row.r6, nmask = DER ? bit_mask(rowd, ROWD_NIGHT_BIT) : 0u;
+    // the fused lone-wavefront Werewolf x 8 turn without generic rows takes what is a constant of the table row from the row's derived word
+    // (DevRow r6, ge_layout.h; profiles/ab_lone_row_const.txt)
+    constexpr bool LONE8 = B::LONE && GENERIC == 0;
+    const uint32_t rowd = row.r6, nmask = LONE8 ? bit_mask(rowd, ROWD_NIGHT_BIT) : 0u;
 
-    const uint32_t T = ww_targets<NB, LOWOCC, GENERIC, DER>(s, row, c, alive, ALL);
+    const uint32_t T = ww_targets<NB, LOWOCC, GENERIC, LONE8>(s, row, c, alive, ALL);
     if (GE_STAMPS == 1 && stamps) { asm volatile("" :: "v"(T)); stamps->mark(0); }        // [end of previous turn .. row in registers]
 
     WwBranch br;
@@ -1547,14 +1361,14 @@ __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c,
     if (B::DEAL_EARLY) ww_prepare_deal<NB, LOWOCC, SINGLE>(s, c, deal, deal_now, ALL, dealt);
     uint32_t tk_next = 0;
     WwActs acts;
-    ww_queue_actions<NB, LOWOCC, !SINGLE, LONE8, TAILR == TAIL_RECYCLE || TAILR == TAIL_KEEP>(s, c, T, act, night, alive, team_w, r_det, tk_io, acts,
+    ww_queue_actions<NB, LOWOCC, !SINGLE, LONE8>(s, c, T, act, night, alive, team_w, r_det, tk_io, acts,
         [&]() {
             ww_phase_branch<NB>(s, row, c.phase0_idx, alive, team_w, br);
             if (B::SHADOW) asm volatile("" : "+v"(br.qe));     // stays in the shadow: not sunk below the queue loop
         },
         [&]() {
             if (!SINGLE) tk_next = turn_key(c.rkey, turn + 1u);
-            if (!B::DEAL_EARLY) ww_prepare_deal<NB, LOWOCC, SINGLE, TAILR != TAIL_NONE && GE_COLD_DEAL_NOW>(s, c, deal, deal_now, ALL, dealt);
+            if (!B::DEAL_EARLY) ww_prepare_deal<NB, LOWOCC, SINGLE>(s, c, deal, deal_now, ALL, dealt);
             if (B::SHADOW) {
                 if (!SINGLE) asm volatile("" : "+v"(tk_next));
                 // (DEAL_MASKS: the pins keep the per-turn conversion in this block.  The lone DEAL_WORDS build has none: `dealt` is three
@@ -1564,13 +1378,9 @@ __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c,
                     for (int k = 0; k < R::NW; k++) asm volatile("" : "+v"(dealt.W[k]));
                 }
             }
-#if GE_PULL_QUEUE == 1
-        }, stamps, rowd, nmask, skip, turn + 1u);             // (the head stamp; under the preprocessor for the reason GE_SKIP_MASK's mask is, ge_kernels.inl)
-#else
-        }, stamps, rowd, nmask, skip);
-#endif
+        }, stamps, rowd, nmask, turn + 1u);                   // (the pull queue's head stamp)
     s.acted |= acts.newly;
-    s.template set<F_SUB>(DER ? acts.newly & nmask : night ? acts.newly : 0u);   // night_action_submitted
+    s.template set<F_SUB>(LONE8 ? acts.newly & nmask : night ? acts.newly : 0u);   // night_action_submitted
     ev_newly = acts.newly;
     if (trace) {                                              // wave-uniform
         uint64_t m = 0;                                       // nibble mask of the new actors
@@ -1581,7 +1391,7 @@ __device__ __forceinline__ void ww_turn(WWR<NB> &s, DevRow &row, const WwCtx &c,
 
     tk_io = tk_next;
     s.flags |= FLAG_PHASE0_DONE;                               // set by the guard turn; already set afterwards
-    const uint32_t qe = ww_decide<NB, LOWOCC, DER>(s, comp, T, br);
+    const uint32_t qe = ww_decide<NB, LOWOCC, LONE8>(s, comp, T, br);
     {   // investigated_alignments[c] = team(c): an assignment, so a stale entry is replaced
         // (the guard turn has no actions: both masks are 0)
         const uint32_t seen = acts.det_v | acts.det_w;

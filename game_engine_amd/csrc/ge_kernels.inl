@@ -59,7 +59,7 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 // loads and drops the hint unless inline-asm statements keep them apart, and behind any such statement it fetches the launch's turn word
 // with a vector load instead of a scalar one - 4 % of the launch.)
 constexpr bool stream_loads(int ld, bool layout_default) { return ld == 0 ? layout_default : ld == 2; }
-// a further value of the step kernel's LD argument, for the fused lone-wavefront Werewolf x 8 kernel alone (GE_TAIL_KNOWN_RESTART, run_ww):
+// a further value of the step kernel's LD argument, for the fused lone-wavefront Werewolf x 8 kernel alone (run_ww):
 // the launch has restart off, no turn of it recycles a room.  Record loads as the layout's default (plain: stream_loads above)
 constexpr int LD_NO_RECYCLE = 3;
 template <int WORDS, bool NT = false>
@@ -306,7 +306,7 @@ __device__ __forceinline__ void run_ww(const SegDev *__restrict__ sgp, const Ste
         }
         if (trace && valid) store_event(sg.trace, sg.rooms_padded, 0u, room, turn0, p, s.phase, restarted, ev_newly, ev_choice);
     } else {
-        if constexpr (B::LONE && GENERIC == 0 && GE_PULL_QUEUE == 1) {
+        if constexpr (B::LONE && GENERIC == 0) {
             // the pull queue's head words start at 0, which no turn's stamp is; nothing clears them afterwards (ge_device.h WaveLdsPull)
             uint32_t *head = static_cast<WaveLdsPull *>(lw)->head;
 #pragma unroll
@@ -322,18 +322,17 @@ __device__ __forceinline__ void run_ww(const SegDev *__restrict__ sgp, const Ste
         // terminal row (ge_device.h WwRestart), not by a divergent block at the head of the next turn - that block was two dozen
         // register moves on four turns of five (some room of 64 finishes) and a branch on every turn.  Rooms that are terminal
         // as loaded are recycled once, in front of the loop
-        // GE_TAIL_KNOWN_RESTART: whether a turn of the tail form recycles is compiled in (ge_device.h TAIL_RECYCLE / TAIL_KEEP).  This kernel
-        // (LD = 0) is then launched with restart on only (ge_step.hip launch_kind): n_turns - 1 recycling turns in the loop, and the
-        // launch's last turn, which stores terminal rooms as they are, once behind it - straight-line code, not a second loop.  Restart
-        // off is the kernel LD = LD_NO_RECYCLE, whose loop is the form that never recycles.  (The head form, and with the switch at 0
-        // the tail form, read a.restart at run time: the loop below them.)
+        // Whether a turn of the tail form recycles is compiled in (ge_device.h TAIL_RECYCLE / TAIL_KEEP).  This kernel (LD = 0) is
+        // launched with restart on only (ge_step.hip launch_kind): n_turns - 1 recycling turns in the loop, and the launch's last
+        // turn, which stores terminal rooms as they are, once behind it - straight-line code, not a second loop.  Restart off is the
+        // kernel LD = LD_NO_RECYCLE, whose loop is the form that never recycles.  (The head form reads a.restart at run time.)
         auto turns = [&](auto trace_c, auto tail_c) {
             constexpr bool KNOWN = decltype(trace_c)::value != 2;
             constexpr bool TAILR = decltype(tail_c)::value;
             const bool trace = KNOWN ? decltype(trace_c)::value == 1 : a.trace != 0u;
-            uint32_t restarted_in = 0;
-            WwRestart<NB> rst = {&s0, 0u, 0u, 0u};
-            if constexpr (TAILR && GE_TAIL_KNOWN_RESTART) {
+            if constexpr (TAILR) {
+                uint32_t restarted_in = 0;
+                WwRestart<NB> rst = {&s0, 0u, 0u, 0u};
                 constexpr bool RECYCLES = LD != LD_NO_RECYCLE;
                 if (a.n_turns == 0u) return;
                 if constexpr (RECYCLES) {
@@ -348,21 +347,12 @@ __device__ __forceinline__ void run_ww(const SegDev *__restrict__ sgp, const Ste
                     row = row0;
                     restarted_in = 1;
                 }
-#if GE_SKIP_MASK
-                // who these turns never act for, a constant of the lane for the whole launch (ge_device.h GE_SKIP_MASK; under the
-                // preprocessor, not a constant condition: a value named here at all reorders operands in other kernels' code)
-                const uint32_t skip = valid ? ctx.human : ~0u;
-#endif
                 auto one_turn = [&](auto form_c, uint32_t t) __attribute__((always_inline)) {
                     const uint32_t restarted = restarted_in, p = s.phase;
                     uint32_t ev_newly = 0;
                     uint64_t ev_choice = 0;
                     const bool deal_now = ahead && ((deal_phase + t) & (deal_period<NB>() - 1u)) == 0u;    // wave-uniform
-#if GE_SKIP_MASK
-                    ww_turn<NB, LOWOCC, GENERIC, false, decltype(form_c)::value>(s, row, ctx, turn0 + t, tk, trace, deal, deal_now, ev_newly, ev_choice, (GE_STAMPS && a.stamps) ? &stamps : nullptr, &rst, skip);
-#else
                     ww_turn<NB, LOWOCC, GENERIC, false, decltype(form_c)::value>(s, row, ctx, turn0 + t, tk, trace, deal, deal_now, ev_newly, ev_choice, (GE_STAMPS && a.stamps) ? &stamps : nullptr, &rst);
-#endif
                     if (trace && valid) store_event(sg.trace, sg.rooms_padded, t, room, turn0 + t, p, rst.q, restarted, ev_newly, ev_choice);
                     restarted_in = rst.restarted;
                 };
@@ -374,18 +364,13 @@ __device__ __forceinline__ void run_ww(const SegDev *__restrict__ sgp, const Ste
                     for (uint32_t t = 0; t < a.n_turns; t++) one_turn(std::integral_constant<int, TAIL_KEEP>{}, t);
                 }
             } else {
+                // (the next two lines are what is left of the tail form's run-time variant and nothing reads them: without them one
+                // commutative operand pair of the restart-off kernel <0,true,0,false,3> swaps - through what is not established)
                 uint32_t term_r = a.restart ? term_mask : 0u;
-                if (TAILR) asm volatile("" : "+s"(term_r));          // one scalar across the loop, not the test of a.restart again on every turn
-                if (TAILR && a.restart && a.n_turns != 0u && ((row.r0 >> 11) & 7u) == 0u) {   // finished as loaded
-                    const uint32_t g = s.games;
-                    s = s0;
-                    s.games = g < 0xFFFFu ? g + 1u : g;
-                    row = row0;
-                    restarted_in = 1;
-                }
-                for (uint32_t t = 0; t < a.n_turns; t++) {
-                    uint32_t restarted = TAILR ? restarted_in : 0u;
-                    if (!TAILR && a.restart && ((row.r0 >> 11) & 7u) == 0u) {      // recycle a finished room
+                if (TAILR) asm volatile("" : "+s"(term_r));
+                for (uint32_t t = 0; t < a.n_turns; t++) {               // the head form
+                    uint32_t restarted = 0u;
+                    if (a.restart && ((row.r0 >> 11) & 7u) == 0u) {      // recycle a finished room
                         const uint32_t g = s.games;
                         s = LOWOCC ? s0 : fresh_room();
                         s.games = g < 0xFFFFu ? g + 1u : g;
@@ -396,10 +381,8 @@ __device__ __forceinline__ void run_ww(const SegDev *__restrict__ sgp, const Ste
                     uint32_t ev_newly = 0;
                     uint64_t ev_choice = 0;
                     const bool deal_now = ahead && ((deal_phase + t) & (deal_period<NB>() - 1u)) == 0u;    // wave-uniform
-                    if (TAILR) rst.term_rs = t + 1u < a.n_turns ? term_r : 0u;           // (the launch's last turn stores terminal rooms as they are)
-                    ww_turn<NB, LOWOCC, GENERIC, false, TAILR ? TAIL_RUNTIME : TAIL_NONE>(s, row, ctx, turn0 + t, tk, trace, deal, deal_now, ev_newly, ev_choice, (GE_STAMPS && a.stamps) ? &stamps : nullptr, &rst);
-                    if (trace && valid) store_event(sg.trace, sg.rooms_padded, t, room, turn0 + t, p, TAILR ? rst.q : s.phase, restarted, ev_newly, ev_choice);
-                    if (TAILR) restarted_in = rst.restarted;
+                    ww_turn<NB, LOWOCC, GENERIC, false>(s, row, ctx, turn0 + t, tk, trace, deal, deal_now, ev_newly, ev_choice, (GE_STAMPS && a.stamps) ? &stamps : nullptr);
+                    if (trace && valid) store_event(sg.trace, sg.rooms_padded, t, room, turn0 + t, p, s.phase, restarted, ev_newly, ev_choice);
                 }
             }
         };
@@ -561,9 +544,9 @@ static_assert(offsetof(DevTable, ord8) == IMG_ORD8 && offsetof(DevTable, nth8) =
               offsetof(DevTable, tally64) == IMG_TALLY && offsetof(DevTable, n_phases) == IMG_END, "DevTable leads with the LDS image");
 static_assert(sizeof(WaveLds) % 16 == 0 && sizeof(WaveLdsLow) % 16 == 0 && LDS_ROWS % 16 == 0 && LDS_ORD8 % 16 == 0, "LDS sections stay 16-byte aligned");
 
-// the single-game kernels whose every wavefront runs the fused lone Werewolf x 8 turn in its pull or byte form (GE_PULL_QUEUE): their
+// the single-game kernels whose every wavefront runs the fused lone Werewolf x 8 turn, whose queue is the pull form: their
 // queue memory is a WaveLdsPull per wavefront.  (The mixed lone kernel keeps WaveLdsLow: its other kinds' queues live there too)
-constexpr bool pull_queue_kernel(int kind, bool lowocc, int generic, bool single) { return GE_PULL_QUEUE != 0 && kind == K_WW8 && lowocc && generic == 0 && !single; }
+constexpr bool pull_queue_kernel(int kind, bool lowocc, int generic, bool single) { return kind == K_WW8 && lowocc && generic == 0 && !single; }
 
 inline uint32_t step_lds_bytes(bool queue, bool lowocc, uint32_t block_threads, bool pull = false) {
     if (!queue) return LDS_ROWS;                              // Two-Truths N <= 4: phase rows only

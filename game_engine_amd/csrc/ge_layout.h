@@ -323,7 +323,7 @@ template <> struct TTLayout<12> {
 //       0xFF bytes (selector 0x0D) in the others, so the AND of the three permutes is the term.
 //       N<=8: 4 terms x 1 byte, pair (W2:W2) in r5;  N<=12: terms 0..1 x 2 bytes.
 //   r6, werewolf N<=8 (which has no third pair): the row's DERIVED word - constants of the row that the fused lone-wavefront
-//       turn would otherwise work out of r0 on every turn (ge_device.h GE_ROW_DERIVED; filled by ge_host.h ww8_row_derived):
+//       turn would otherwise work out of r0 on every turn (ge_device.h ww_turn; filled by ge_host.h ww8_row_derived):
 //       bits 0..7 the all-players mask if completion is `action`, else 0; bit 8 the row's action is a night action;
 //       bits 16..23 the flags byte a room has after it leaves the row (FLAG_PHASE0_DONE | effect << 1);
 //       bits 28..31 the action kind one-hot, (1 << act) >> 1, as a queue slot's context word carries it

@@ -389,13 +389,13 @@ template <class K> inline void launch_one(K kernel, const LaunchShape &L, bool q
 
 template <bool LOW, int GEN, bool SINGLE> inline void launch_kind(uint32_t kind, const LaunchShape &L) {
     constexpr bool HAS_ALT = SINGLE && !LOW && GEN == 0;
-    constexpr bool NO_RECYCLE = GE_TAIL_KNOWN_RESTART && LOW && !SINGLE && GEN == 0;
+    constexpr bool NO_RECYCLE = LOW && !SINGLE && GEN == 0;
     const bool alt = HAS_ALT && L.b->stream_loads != (kind != K_WW8);      // the layouts' default: Werewolf x 8 plain, the others streaming
     switch (kind) {
     // (the large-batch single-turn kernels of the shipped games exist with plain and with streaming record loads: ALT = the form that is not the
     // layout's default, launched when the batch's stream_loads (create_impl: record_loads) differs from that default)
     case K_WW8:
-        // (the fused lone-wavefront kernel compiles in whether its turns recycle finished rooms - GE_TAIL_KNOWN_RESTART, ge_kernels.inl run_ww:
+        // (the fused lone-wavefront kernel compiles in whether its turns recycle finished rooms - ge_kernels.inl run_ww:
         // LD = 0 is the restart-on kernel, LD_NO_RECYCLE the restart-off one)
         if (alt) launch_one(ge_step_kernel<K_WW8, LOW, GEN, SINGLE, HAS_ALT ? 2 : 0>, L, true, LOW);
         else if (NO_RECYCLE && !L.a.restart) launch_one(ge_step_kernel<K_WW8, LOW, GEN, SINGLE, NO_RECYCLE ? LD_NO_RECYCLE : 0>, L, true, LOW, pull_queue_kernel(K_WW8, LOW, GEN, SINGLE));

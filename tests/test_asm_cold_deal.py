@@ -2,7 +2,7 @@
 (CPU: hipcc -S needs no GPU).  `tools/asm_shadow.py --paths` walks the common turn of every turn loop from the loop header to its
 back edge; tools/asm_shadow_paths.json pins, per loop of the Werewolf x 8 fused lone kernel, how many role-deal blocks that
 path runs through and how many branches are taken on it (the figures of the adopted build, profiles/ab_lone_cold_deal.txt).  In
-the tail-recycling loops (GE_COLD_FALLBACK, GE_COLD_DEAL_NOW in ge_device.h) the path holds neither the on-the-spot deal of
+the tail-recycling loops (ge_device.h ww_apply_effect, TAILR) the path holds neither the on-the-spot deal of
 ww_apply_effect nor the `deal_now` block of ww_prepare_deal; the head-restart loops keep the parent's form and figures."""
 import json
 import os

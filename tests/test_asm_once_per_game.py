@@ -1,7 +1,8 @@
 """The once-per-game work of the lone-wavefront Werewolf x 8 turn is out of its tail-recycling turn loops, from the assembly that is
 shipped (CPU: hipcc -S needs no GPU).  `tools/asm_shadow.py --paths` counts the instructions of the common turn of every turn loop,
 from the loop header to its back edge; tools/asm_once_per_game.json holds those counts for the two tail-recycling loops (untraced,
-traced) on the parent commit and with GE_LONE_DEAL_WORDS and GE_TAIL_KNOWN_RESTART (ge_device.h): the role words of a prepared deal
+traced) on the parent commit and with the deal kept as words and the restart known at compile time (ge_device.h DEAL_WORDS,
+TAIL_RECYCLE / TAIL_KEEP; the keys of the file's `parts` are the names the two had as switches): the role words of a prepared deal
 are no longer rebuilt on every turn, and a recycling turn no longer records an `end_turn` that recycling overwrites.  Instruction
 counts only; what they are worth in time is profiles/ab_lone_once_per_game.txt."""
 import json

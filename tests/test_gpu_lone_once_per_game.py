@@ -1,5 +1,5 @@
 """GPU parity (-m gpu) of the lone-wavefront Werewolf x 8 turn around the two things it does once per game and no longer once
-per turn (ge_device.h GE_LONE_DEAL_WORDS, GE_TAIL_KNOWN_RESTART): a prepared deal kept as the words a role assignment writes
+per turn (ge_device.h DEAL_WORDS, TAIL_RECYCLE / TAIL_KEEP): a prepared deal kept as the words a role assignment writes
 (converted when it is dealt, when the record's 16-bit cache is loaded and when it is stored), and a fused launch whose turns know
 at compile time whether they recycle finished rooms - a restart-on launch runs its last turn, which stores terminal rooms as they
 are, as one peeled turn behind the recycling loop; a restart-off launch is a kernel of its own.  The tests pin behaviour, not a

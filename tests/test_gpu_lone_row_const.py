@@ -1,8 +1,8 @@
 """GPU parity (-m gpu) of the fused lone-wavefront Werewolf x 8 turn around what it no longer works out on every turn
-(ge_device.h GE_ROW_DERIVED, GE_CTX_PERM, GE_SKIP_MASK, GE_RES_UNMASKED): constants of the table row taken from the row's derived
-word, the slot context built by a byte permute, the lanes past a segment's end and the host-driven players folded into one mask
-made in front of the turn loop, and the first queue round's result returned from every lane.  The tests pin results, not a
-build: they pass on the kernels before that as well.
+(ge_device.h ww_turn): constants of the table row taken from the row's derived word - and, measured beside it and not adopted
+(profiles/ab_lone_row_const.txt), the slot context built by a byte permute, the lanes past a segment's end and the host-driven
+players folded into one mask made in front of the turn loop, and the first queue round's result returned from every lane.  The
+tests pin results, not a build: they pass on the kernels before that as well.
 
   rooms      64 (one full wavefront), 65 (a second wavefront with 63 lanes past the segment's end), 130 (three, the last with 2 rooms)
   launches   of 1 turn (x 3: the single-turn kernel beside the fused ones), of 17 (x 2: a deal preparation, every 16th turn, inside a

@@ -1,4 +1,4 @@
-"""GPU parity (-m gpu) of the fused lone-wavefront Werewolf x 8 turn around its action queue (ge_device.h GE_PULL_QUEUE): in the pull
+"""GPU parity (-m gpu) of the fused lone-wavefront Werewolf x 8 turn around its action queue (ge_device.h WaveLdsPull): in the pull
 form an owner stores its context once and a stamp into the head word of its first slot, and a slot finds its owner by counting
 the heads up to itself - across the rounds of a long queue too.  The tests pin results, not a build: they pass on the slot form
 as well.

@@ -1,5 +1,5 @@
 """GPU parity (-m gpu) of the fused lone-wavefront Werewolf x 8 turn where a wavefront's due actions cross one and two rounds of its
-action queue (ge_device.h GE_QUEUE_ROUND2): the turn that needs a second round is a path of its own there, a third and later round
+action queue (ge_device.h ww_queue_actions): the turn that needs a second round is a path of its own there, a third and later round
 runs the loop over rounds behind it, and the one-round turn no longer looks at the total.  The tests pin results, not a build: they
 pass on the loop form as well.
 

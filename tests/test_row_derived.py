@@ -1,7 +1,7 @@
 """The derived word of a device table row (CPU; csrc/ge_layout.h DevRow r6, filled by csrc/ge_host.h ww8_row_derived).
 
 A Werewolf row of a segment of at most 8 players carries, in the word that was the unused third permute selector, the constants
-of the row that the fused lone-wavefront turn used to work out of r0 on every turn (ge_device.h GE_ROW_DERIVED):
+of the row that the fused lone-wavefront turn used to work out of r0 on every turn (ge_device.h ww_turn):
   bits 0..7    the all-players mask if the row completes by actions, else 0
   bit 8        the row's action is a night action (wolf target, Doctor, Detective)
   bits 16..23  the flags byte of a room that has left the row: phase-0-done | the row's effect << 1

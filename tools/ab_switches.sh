@@ -1,18 +1,13 @@
 #!/bin/bash
 # Every compile-time switch that is left in the kernels (ge_device.h, ge_kernels.inl) is built once with a non-default value
-# and run through the parity subset, so that no switch value rots untested.
+# and run through the parity subset, so that no switch value rots untested.  (The lone Werewolf x 8 turn's settled A/B variants, tally_shift ..
+# round2_tail, are retired: numbers in profiles/ab_lone_*.txt, source in commit aad3851.)
 #   tools/ab_switches.sh build        in the container: game_engine_amd/ab/sw_*.so (they travel with the gpurun snapshot)
 #   tools/ab_switches.sh test <tag>   on the GPU box: parity subset + timing probe per variant -> gpurun_out/<tag>/switches.txt
 set -u
 VARIANTS=("deal8:-DGE_DEAL_PERIOD=8" "deal32:-DGE_DEAL_PERIOD=32" "ttq13:-DGE_TT_LOW_QUEUE_MIN=13" "ttq4:-DGE_TT_LOW_QUEUE_MIN=4"
           "ww12w5:-DGE_WW12_WAVES=5" "ww8w8:-DGE_WW8_WAVES=8" "genw7:-DGE_GENERIC_WAVES=7" "stamps:-DGE_STAMPS=1" "clock:-DGE_STAMPS=2"
-          "lds_old:-DGE_RES_PACKED=0 -DGE_ROWS_SPLIT=0 -DGE_RES_ATOMIC64=0" "noprio:-DGE_QUEUE_PRIO=0 -DGE_RESOLVE_PRIO=0 -DGE_STORE_PRIO=0" "deal_in_shadow:-DGE_DEAL_EARLY=0" "tally_shift:-DGE_TALLY_BYTES=0"
-          "deal_fallback_inline:-DGE_COLD_FALLBACK=0" "deal_now_cold:-DGE_COLD_DEAL_NOW=1"
-          "lone_deal_masks:-DGE_LONE_DEAL_WORDS=0" "tail_restart_runtime:-DGE_TAIL_KNOWN_RESTART=0"
-          "row_from_r0:-DGE_ROW_DERIVED=0" "ctx_perm:-DGE_CTX_PERM=1" "skip_mask:-DGE_SKIP_MASK=1" "res_unmasked:-DGE_RES_UNMASKED=1"
-          "row_const_all:-DGE_CTX_PERM=1 -DGE_SKIP_MASK=1 -DGE_RES_UNMASKED=1"
-          "queue_slots:-DGE_PULL_QUEUE=0" "queue_bytes:-DGE_PULL_QUEUE=2"
-          "round2_loop:-DGE_QUEUE_ROUND2=0" "round2_arms:-DGE_QUEUE_ROUND2=1" "round2_arms_early:-DGE_QUEUE_ROUND2=2" "round2_tail:-DGE_QUEUE_ROUND2=3")
+          "lds_old:-DGE_RES_PACKED=0 -DGE_ROWS_SPLIT=0 -DGE_RES_ATOMIC64=0" "noprio:-DGE_QUEUE_PRIO=0 -DGE_RESOLVE_PRIO=0 -DGE_STORE_PRIO=0" "deal_in_shadow:-DGE_DEAL_EARLY=0")
 cd "$(dirname "$0")/.."
 case "${1:-}" in
 build)

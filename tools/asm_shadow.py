@@ -17,7 +17,7 @@ scalar-memory operations complete in issue order for this purpose: `lgkmcnt(n)` 
 operations were issued behind it.
 Reads are named by their place in the turn: `ord` (before the slot writes), `slot` (the first round's), `slot+` (a later
 round's, inside the queue loop), `head` / `head+` (the pull queue's head word, read in front of the context that `slot` / `slot+` then is), `result` (behind the atomics), `row` (everything after: the entered row, a recycled room).
-GE_QUEUE_ROUND2 (ge_device.h) lays the second round out of line - a block of its own outside the loop over rounds, behind the turn loop's back edge in the tail-recycling loops: its
+The fused lone Werewolf x 8 turn (ge_device.h ww_queue_actions) lays the second round out of line - a block of its own outside the loop over rounds, behind the turn loop's back edge in the tail-recycling loops: its
 reads are `head2` (the head word, where the round reads one of its own) and `slot2` (the context, the read whose next LDS operation is
 the round's atomic).  With the head words of both rounds read at once the first read is a two-address one and still `head`.
 
@@ -127,7 +127,7 @@ def cold_from(lines, head, first, end):
 
 
 def second_round_blocks(lines, labels, first, end):
-    """GE_QUEUE_ROUND2: the second queue round as a block of its own, entered by a forward wave-uniform branch and left by an
+    """The second queue round as a block of its own, entered by a forward wave-uniform branch and left by an
     unconditional one - wherever the compiler laid it (behind the back edge in the tail-recycling loops, in front of it in the
     others).  What tells it from a deal block and from the first round's: a context read (ds_read_b128) and then an LDS atomic stand in it before any
     wave-uniform branch.  [(first line, last line)]"""
@@ -156,7 +156,7 @@ def turn_path(lines, labels, head, first, end, two=False):
     """the common turn from the loop header to its back edge, by walk()'s rules (exec-masked blocks entered, the skip of an in-line
     wave-uniform block taken, no branch into an out-of-line block, the loop over further queue rounds left at once): instructions on
     it, branches taken on it (the back edge among them), and how many role-deal blocks it runs through.
-    two: the turn that needs a second queue round where that round is a block behind the back edge (GE_QUEUE_ROUND2) - the branch into
+    two: the turn that needs a second queue round where that round is a block behind the back edge - the branch into
     that block is taken and its branch back followed; None if the loop has no such block"""
     def in_queue_loop(i):
         j = next(j for j in range(i, first - 1, -1) if LABEL.match(lines[j]))
@@ -284,14 +284,14 @@ def collect(path):
             seen = {}
             reads = [(i, op) for i, op in ops if op.startswith("ds_read")]
             for n, (i, op) in enumerate(reads):
-                # the pull queue (ge_device.h GE_PULL_QUEUE): a slot reads its head word, then the owner's 16-byte context
+                # the pull queue (ge_device.h WaveLdsPull): a slot reads its head word, then the owner's 16-byte context
                 heads_ctx = op in ("ds_read_b32", "ds_read2st64_b32") and n + 1 < len(reads) and reads[n + 1][1] == "ds_read_b128" and i >= writes[0] and \
                     (in_queue_loop(i) and in_queue_loop(reads[n + 1][0]) or reads[n + 1][0] < atomics[0] or in_second(i) and not in_queue_loop(reads[n + 1][0]))
                 next_lds = next((o for j, o in ops if j > i and o.startswith("ds_")), "")
                 if i < writes[0]:
                     role = "ord"
                 elif in_second(i) and not in_queue_loop(i) and (heads_ctx or op == "ds_read_b128" and ATOMIC.match(next_lds)):
-                    role = "head2" if heads_ctx else "slot2"     # the second round out of line (GE_QUEUE_ROUND2)
+                    role = "head2" if heads_ctx else "slot2"     # the second round out of line
                 elif in_queue_loop(i):
                     role = "head+" if heads_ctx else "slot+"
                 elif i < atomics[0]:
