@@ -192,7 +192,7 @@ static int find_rooms_impl(ge_batch *b, uint64_t first, uint64_t count, uint32_t
         a.seats = b->seats;
         a.r0 = p.r0; a.nr = p.nr; a.seg = p.seg; a.want = want; a.row_mask = row_mask[p.seg]; a.pad = 0;
         const dim3 grid((uint32_t)((p.nr + FIND_BLOCK - 1u) / FIND_BLOCK));
-        HIP_TRY(b->generic ? find_launch<1>(b->segs[p.seg].dev.kind, grid, s, b, a) : find_launch<0>(b->segs[p.seg].dev.kind, grid, s, b, a));
+        HIP_TRY(b->plan.generic ? find_launch<1>(b->segs[p.seg].dev.kind, grid, s, b, a) : find_launch<0>(b->segs[p.seg].dev.kind, grid, s, b, a));
     }
     uint64_t *d_pre = reinterpret_cast<uint64_t *>(dev + off_pre), *d_tot = reinterpret_cast<uint64_t *>(dev + off_tot);
     hipLaunchKernelGGL(ge_find_scan, dim3(1), dim3(FIND_SCAN_WAVES), 0, s, reinterpret_cast<const uint32_t *>(dev + off_cnt), n_waves, d_pre, d_tot);

@@ -1,7 +1,8 @@
 // ge_host.h - the host-only half of libge_step.so that needs no HIP: compiled DSL rows -> the kernels' table rows and literal
 // image, the restart template, and the canonical room view <-> packed record conversion of ge_batch_read_rooms / write_rooms.
 // Plain C++17 (ge_layout.h is host / device neutral), so this file and ge_table.cpp also build with g++ under
-// AddressSanitizer + UBSan (tests/test_host_sanitizers.py) - sanitizers are CPU-only on this pool.
+// AddressSanitizer + UBSan (tests/test_host_sanitizers.py) - sanitizers are CPU-only on this pool.  Its sibling ge_plan.h (what a
+// step launches: knobs, block sizes, grids, kernel forms) is HIP-free in the same way (tests/test_launch_plan.py).
 #pragma once
 #include <stdint.h>
 #include <string.h>

@@ -426,7 +426,7 @@ static int launch_pool_turn(ge_batch *b, hipStream_t s, const PoolEntries &en, c
         a.n = cnt; a.seg = g; a.seed_key = seed_k;
         a.restart = (b->flags & GE_FLAG_RESTART) ? 1u : 0u;
         const dim3 grid((cnt + 63u) / 64u);
-        HIP_TRY(b->generic ? pool_launch<1>(b->segs[g].dev.kind, grid, s, b, a) : pool_launch<0>(b->segs[g].dev.kind, grid, s, b, a));
+        HIP_TRY(b->plan.generic ? pool_launch<1>(b->segs[g].dev.kind, grid, s, b, a) : pool_launch<0>(b->segs[g].dev.kind, grid, s, b, a));
     }
     return GE_OK;
 }

@@ -643,7 +643,7 @@ template <int ACT> RollArgs<ACT> rollout_form_args(const RolloutArgs &base, char
 template <int ACT> hipError_t rollout_launch_counted(const ge_batch *b, hipStream_t s, const RollArgs<ACT> &a) {
     const dim3 grid(a.n * a.waves);                         // <= 2^26 blocks (n * R <= 2^26)
     const uint32_t kind = b->segs[a.seg].dev.kind;
-    return b->generic ? rollout_launch<1, ACT>(kind, grid, s, b, a) : rollout_launch<0, ACT>(kind, grid, s, b, a);
+    return b->plan.generic ? rollout_launch<1, ACT>(kind, grid, s, b, a) : rollout_launch<0, ACT>(kind, grid, s, b, a);
 }
 
 // segment g's entries [lo, lo + cnt) of the chunk staged at dev, as form ACT

@@ -278,7 +278,7 @@ static int run_rooms_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, const 
         if (en.begin[g + 1u] == en.begin[g]) continue;
         const RunArgs a = run_args(b, en, g, dev, off_keys, off_turns, off_trace, off_out, max_turns, until);
         const dim3 grid((a.n + 63u) / 64u);
-        HIP_TRY(b->generic ? run_launch<1>(b->segs[g].dev.kind, grid, s, b, a) : run_launch<0>(b->segs[g].dev.kind, grid, s, b, a));
+        HIP_TRY(b->plan.generic ? run_launch<1>(b->segs[g].dev.kind, grid, s, b, a) : run_launch<0>(b->segs[g].dev.kind, grid, s, b, a));
     }
     if (e1) HIP_TRY(hipEventRecord(e1, s));
     // the turn counts first: only the rows of turns somebody played are copied - unless the whole plane is small

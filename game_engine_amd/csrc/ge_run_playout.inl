@@ -233,7 +233,7 @@ static int run_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, cons
                     const auto launch = [&](const auto &ra) {     // the unit's capacity in pairs is <= 2^26: the cost cap
                         const uint64_t cap_pairs = (uint64_t)ra.n * ra.waves;
                         const dim3 grid((uint32_t)(runp_capacity_grid() ? cap_pairs : std::min<uint64_t>(cap_pairs, RUNP_GRID_BLOCKS)));
-                        return b->generic ? runp_launch<1>(kind, grid, s, b, ra, cnt) : runp_launch<0>(kind, grid, s, b, ra, cnt);
+                        return b->plan.generic ? runp_launch<1>(kind, grid, s, b, ra, cnt) : runp_launch<0>(kind, grid, s, b, ra, cnt);
                     };
                     HIP_TRY(play_unit(b, s, dev, pe, pr, u, unit_rollout_args(b, dev, pe, u, u.e_cap, seed, n_rollouts, pmax), halving, launch));
                 }
@@ -254,7 +254,7 @@ static int run_playout_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, cons
                 x.t = t; x.max_turns = max_turns;
                 const dim3 grid((a.n + 63u) / 64u);
                 const uint32_t kind = b->segs[g].dev.kind;
-                HIP_TRY(b->generic ? runp_launch<1>(kind, grid, s, b, a, x) : runp_launch<0>(kind, grid, s, b, a, x));
+                HIP_TRY(b->plan.generic ? runp_launch<1>(kind, grid, s, b, a, x) : runp_launch<0>(kind, grid, s, b, a, x));
             }
         }
         t_end = g_end;

@@ -103,7 +103,7 @@ static int seat_step_impl(ge_batch *b, uint32_t n_turns, hipStream_t st) {
             a.trace = (b->flags & GE_FLAG_TRACE) ? 1u : 0u;
             a.turn0 = (uint32_t)b->turn; a.n_turns = k;
             const dim3 grid((uint32_t)((d.rooms + 63u) / 64u));
-            HIP_TRY(b->generic ? seat_step_launch<1>(d.kind, grid, st, b, a) : seat_step_launch<0>(d.kind, grid, st, b, a));
+            HIP_TRY(b->plan.generic ? seat_step_launch<1>(d.kind, grid, st, b, a) : seat_step_launch<0>(d.kind, grid, st, b, a));
             b->launches++;
         }
         if (e1) HIP_TRY(hipEventRecord(e1, st));

@@ -22,6 +22,7 @@
 #include "ge_device.h"
 #include "ge_layout.h"
 #include "ge_host.h"
+#include "ge_plan.h"
 
 using namespace ge;
 
@@ -49,7 +50,8 @@ struct Segment {
 struct ge_batch {
     int device = 0;
     uint64_t seed = 0, first_room = 0, turn = 0, n_rooms = 0;
-    uint32_t max_fuse = 64, block_threads = 256, n_blocks = 0, flags = 0;
+    uint32_t max_fuse = 64, flags = 0;
+    BatchPlan plan;                   // what the step launches follow from (ge_plan.h batch_plan)
     std::vector<Segment> segs;
     void *state = nullptr;            // one allocation, segments back to back
     void *trace = nullptr;            // GE_FLAG_TRACE: per segment [max_fuse][rooms_padded] x 16 B
@@ -59,15 +61,11 @@ struct ge_batch {
     std::vector<uint16_t> seats_host; // ... and its host mirror (empty without a plane)
     uint32_t last_step_turns = 0;     // turns of the most recent ge_batch_step (what the trace holds)
     size_t state_bytes = 0;
-    bool stream_loads = false;  // a single-game batch's large single-turn launches load the record with streaming loads (create_impl)
     DevTable *tables = nullptr;
     int32_t *phase_ids = nullptr;     // per segment GE_MAX_PHASES words: the DSL phase id of each dense row (ge_env.inl: an observation names its phases by id)
     SegDev *segs_dev = nullptr;
     unsigned long long *sum_dev = nullptr;
     hipStream_t last_stream = nullptr;
-    bool generic = false;             // some phase has a generic target condition: the GENERIC kernel builds are launched
-    uint32_t gshape = 0;              // ... a single Two-Truths table whose conditions all fit 1 x 1 / 1 x 2 literal slots: 2 / 3 = the shape-specialised fused builds
-    uint32_t cond_bytes = 0;          // ... and their blocks keep this much of literal image in LDS (the largest table's)
     bool pending = false;             // work was queued on last_stream since the last synchronisation
     hipEvent_t order_ev = nullptr;    // orders a step on a new stream behind the previous stream's work
     unsigned long long *stamps_dev = nullptr;   // GE_STAMPS diagnostic build only
@@ -94,18 +92,8 @@ static int fill_args(const ge_batch *b, StepArgs &a, uint32_t turn0, uint32_t n_
     for (uint32_t k = 0; k < a.n_seg; k++) a.block_begin[k] = b->segs[k].dev.block_begin;
     a.turn0 = turn0; a.n_turns = n_turns;
     a.seed_key = seed_key((uint32_t)b->seed, (uint32_t)(b->seed >> 32));
-    a.block_threads = b->block_threads;
     a.restart = (b->flags & GE_FLAG_RESTART) ? 1u : 0u;
     a.trace = (b->flags & GE_FLAG_TRACE) ? 1u : 0u;
-    // up to one wavefront per SIMD (1 024 SIMDs x 64 rooms) -> the branch-lean lone-wavefront build (ge_device.h LOWOCC):
-    // 65 536 rooms 1.283 vs 1.372 us/turn; from the first SIMD with two wavefronts on the large-batch build is as fast or
-    // faster (69 632 rooms 1.680 vs 1.668, 131 072: 1.791 vs 1.738; tools/threshold_probe.sh, profiles/r02_threshold.txt).
-    // GE_LOWOCC_ROOMS overrides the threshold (tuning / A-B runs)
-    static const uint64_t low_rooms = [] {
-        const char *e = getenv("GE_LOWOCC_ROOMS");
-        return e ? strtoull(e, nullptr, 10) : (uint64_t)(1024u * 64u + 1u);
-    }();
-    a.lowocc = b->n_rooms < low_rooms ? 1u : 0u;
     a.stamps = b->stamps_dev;
     return GE_OK;
 }
@@ -200,24 +188,9 @@ static int create_impl(const ge_batch_desc *desc, ge_batch **out, const uint64_t
     b->device = desc->device; b->seed = desc->seed; b->first_room = desc->first_room;
     b->max_fuse = desc->max_fuse ? desc->max_fuse : 64u;
     b->flags = desc->flags;
-    uint64_t total = 0;
-    for (uint32_t k = 0; k < desc->n_segments; k++) total += desc->seg[k].n_rooms;
-    // Rooms per block.  Up to four wavefronts per SIMD (262 144 rooms) 64-room blocks are as fast as any and balance best; beyond, a block's
-    // LDS (the 7 KB table image + its wavefronts' queues) caps a CU at 5 wavefronts per SIMD when every wavefront brings its own image, and
-    // the launch takes a second round: fused us per turn at 393 216 / 524 000 rooms, 64- against 256-room blocks: Werewolf x 8 3.50 / 4.66 ->
-    // 2.54 / 3.52, Two-Truths x 4 at 524 000 3.31 -> 2.35, Werewolf x 12 6.46 -> 4.87 (-24 .. -28 %; level at 262 144 and below;
-    // profiles/r05_fused_midsize.txt).  (Until round 5 the switch was at 524 288 rooms.)
-    b->block_threads = total > (1u << 18) ? 256u : 64u;
-    // a batch that only ever runs single-turn launches (max_fuse = 1) on the large-batch kernels: 256-room blocks at once (launch_geometry does
-    // the same per launch for a single-game batch; a mixed batch's block size is fixed here, its segments are padded to it)
-    if (b->max_fuse == 1u && total > 65536u) b->block_threads = 256u;
-    if (const char *e = getenv("GE_BLOCK_THREADS")) {          // tuning / A-B runs: 64, 128 or 256
-        const unsigned long v = strtoul(e, nullptr, 10);
-        if (v == 64 || v == 128 || v == 256) b->block_threads = (uint32_t)v;
-    }
     uint64_t local = 0, global = desc->first_room;
     size_t bytes = 0;
-    uint32_t blocks = 0;
+    PlanSeg pseg[GE_MAX_SEGMENTS];
     for (uint32_t k = 0; k < desc->n_segments; k++) {
         const ge_segment_desc &sd = desc->seg[k];
         if (!sd.table || sd.n_rooms == 0 || sd.table->abi_version != GE_ABI_VERSION ||
@@ -247,28 +220,15 @@ static int create_impl(const ge_batch_desc *desc, ge_batch **out, const uint64_t
         for (int r = 0; r < s.table.n_phases; r++)
             if (s.table.rows[r].phase_id == 0) d.phase0_idx = (uint32_t)r;
         if (d.phase0_idx == 255) { delete b; return GE_ERR_ARG; }   // AgentState starts at phase id 0 (v2:103)
-        d.block_begin = blocks; d.table_idx = k;
-        blocks += (uint32_t)((sd.n_rooms + b->block_threads - 1) / b->block_threads);
+        d.table_idx = k;
+        pseg[k] = {d.kind, d.words, d.rooms};
         s.local_first = local;
         d.base = reinterpret_cast<uint32_t *>(bytes);     // offset for now, rebased after hipMalloc
         bytes += (size_t)planes_of((int)d.words) * 16u * d.rooms_padded;
         local += sd.n_rooms; global += sd.n_rooms;
         b->segs.push_back(s);
     }
-    b->n_rooms = local; b->n_blocks = blocks; b->state_bytes = bytes;
-    // record_loads - the record loads of a single-game batch's large single-turn launches, plain or streaming (non-temporal), by layout and by where the state
-    // lives (ge_kernels.inl load_words; profiles/r05_ab_ww8_nt_loads.txt, r05_ab_nt_others.txt): beyond the 256 MiB Infinity Cache of MI355X
-    // every layout streams; while the cache holds the state plain loads are served from it (+4 ... +18 % at 100 - 250 MiB), except that the
-    // smallest states measured - Two-Truths at 24 MiB, Werewolf x 12 at 80 MiB - are level or 2 % better streaming.  GE_NT_LOADS=0 / 1 forces
-    // plain / streaming (A/B, knob runs)
-    {
-        static const int nt_env = [] { const char *e = getenv("GE_NT_LOADS"); return e ? atoi(e) : -1; }();
-        const uint32_t kind0 = b->segs[0].dev.kind;
-        const size_t mib = (size_t)1 << 20, small = kind0 == K_WW8 ? 0 : kind0 == K_WW12 ? 96 * mib : 48 * mib;
-        size_t touched = 0;                                     // what a launch reads: the records' own words (a layout's last plane is allocated 16 bytes wide)
-        for (const Segment &sg : b->segs) touched += (size_t)sg.dev.words * 4u * sg.dev.rooms_padded;
-        b->stream_loads = nt_env >= 0 ? nt_env != 0 : (touched > 288 * mib || touched <= small);
-    }
+    b->n_rooms = local; b->state_bytes = bytes;
     int st = GE_OK;
     {
         DeviceGuard dg(b->device);
@@ -290,6 +250,8 @@ static int create_impl(const ge_batch_desc *desc, ge_batch **out, const uint64_t
                 }
             }
             std::vector<DevTable> host_tables(b->segs.size());
+            bool generic = false;
+            uint32_t cond_bytes = 0;
             for (size_t k = 0; k < b->segs.size(); k++) {
                 Segment &s = b->segs[k];
                 s.dev.base = reinterpret_cast<uint32_t *>(static_cast<char *>(b->state) + reinterpret_cast<size_t>(s.dev.base));
@@ -298,15 +260,10 @@ static int create_impl(const ge_batch_desc *desc, ge_batch **out, const uint64_t
                 for (int r = 0; r < s.table.n_phases; r++) {
                     dt.rows[r] = to_dev_row(s.table, s.table.rows[r], s.dev.kind, s.dev.n_players);
                     dt.conds[r] = to_dev_cond(s.table.rows[r]);
-                    if (s.table.rows[r].generic) b->generic = true;
+                    if (s.table.rows[r].generic) generic = true;
                 }
                 build_cond_image(s.table, s.dev.kind, dt);
-                b->cond_bytes = std::max<uint32_t>(b->cond_bytes, dt.cond_n16 * 16u);
-                if (b->segs.size() == 1 && s.table.pack == GE_PACK_TWO_TRUTHS && dt.cond_n16) {
-                    static const bool no_shapes = getenv("GE_NO_GENERIC_SHAPES") != nullptr;       // A/B runs: the rolled walk for every table
-                    const uint32_t ncl = dt.cond_shape & 7u, len = (dt.cond_shape >> 4) & 7u;
-                    b->gshape = no_shapes ? 0u : (ncl == 1u && len == 1u) ? 2u : (ncl == 1u && len == 2u) ? 3u : 0u;
-                }
+                cond_bytes = std::max<uint32_t>(cond_bytes, dt.cond_n16 * 16u);
                 dt.n_phases = s.table.n_phases; dt.rounds = s.table.rounds; dt.n_players = (int32_t)s.dev.n_players;
                 fill_nth8_host(dt.nth8);
                 fill_ord8_host(dt.ord8);
@@ -329,6 +286,8 @@ static int create_impl(const ge_batch_desc *desc, ge_batch **out, const uint64_t
                     if (s.table.rows[r].n_branches == 0) s.dev.term_mask |= 1u << r;
             }
             if (hipMemcpy(b->tables, host_tables.data(), sizeof(DevTable) * host_tables.size(), hipMemcpyHostToDevice) != hipSuccess) { st = GE_ERR_HIP; break; }
+            b->plan = batch_plan(launch_knobs(), pseg, (uint32_t)b->segs.size(), b->max_fuse, generic, host_tables[0].cond_n16 ? host_tables[0].cond_shape : 0u, cond_bytes, GE_TT_LOW_QUEUE_MIN);
+            for (size_t k = 0; k < b->segs.size(); k++) b->segs[k].dev.block_begin = b->plan.block_begin[k];
             std::vector<int32_t> ids(b->segs.size() * GE_MAX_PHASES, 0);
             for (size_t k = 0; k < b->segs.size(); k++)
                 for (int r = 0; r < b->segs[k].table.n_phases; r++) ids[k * GE_MAX_PHASES + r] = b->segs[k].table.rows[r].phase_id;
@@ -344,7 +303,7 @@ static int create_impl(const ge_batch_desc *desc, ge_batch **out, const uint64_t
 #if GE_STAMPS
     if (getenv("GE_STAMPS_OUT")) {
         DeviceGuard dg(b->device);
-        const size_t sb = 64 + (GE_STAMPS == 2 ? 32 * (size_t)((b->n_rooms + 63) / 64 + 64) : 0);    // GE_STAMPS = 2: + a {start, end, where, cycles} record per wavefront
+        const size_t sb = 64 + (GE_STAMPS == 2 ? 32 * (size_t)b->plan.stamp_records : 0);    // GE_STAMPS = 2: + a {start, end, where, cycles} record per wavefront
         if (hipMalloc(reinterpret_cast<void **>(&b->stamps_dev), sb) == hipSuccess) (void)hipMemset(b->stamps_dev, 0, sb);
     }
 #endif
@@ -374,48 +333,55 @@ static int reset_impl(ge_batch *b) {
     return sync_impl(b);
 }
 
-// ---- one launch of the step kernel.  What is launched is chosen from four facts, each a template argument of the kernels so that
-// every build gets its own register allocation (ge_kernels.inl): the record layout (or "mixed": several segments), LOWOCC (up to
-// one wavefront per SIMD), GENERIC (some table has a generic target condition) and SINGLE (the launch is exactly one turn).
+// ---- one launch of the step kernel: ge_plan.h launch_plan decides what is launched; here a plan is mapped to the kernel build
+// that has its facts as template arguments (ge_kernels.inl) and launched with the LDS the build needs.
 namespace {
-struct LaunchShape { dim3 grid, block; hipStream_t st; const ge_batch *b; StepArgs a; };
+struct LaunchShape { hipStream_t st; const ge_batch *b; StepArgs a; LaunchPlan p; };
 
-template <class K> inline void launch_one(K kernel, const LaunchShape &L, bool queue, bool lds_low, bool lds_pull = false) {
+// the plan's queue facts are the kernels' (the plan is HIP-free and cannot see ge_kernels.inl: create_impl passes it GE_TT_LOW_QUEUE_MIN)
+constexpr bool queue_facts_agree() {
+    for (int kind = 0; kind < K_COUNT; kind++)
+        for (int low = 0; low < 2; low++) {
+            if (kind >= K_TT4 && plan_uses_queue(kind, low, GE_TT_LOW_QUEUE_MIN) != tt_uses_queue(kind == K_TT4 ? 4 : kind == K_TT8 ? 8 : 12, low)) return false;
+            for (int gs = 0; gs < 8; gs++)
+                if (plan_pull_queue(kind, low, gs >> 1, gs & 1) != pull_queue_kernel(kind, low, gs >> 1, gs & 1)) return false;
+        }
+    return true;
+}
+static_assert(queue_facts_agree(), "ge_plan.h and ge_kernels.inl disagree on which builds have a queue");
+
+template <class K> inline void launch_one(K kernel, const LaunchShape &L) {
     StepArgs a = L.a;
-    const uint32_t base = step_lds_bytes(queue, lds_low, L.block.x, lds_pull);
+    const uint32_t base = step_lds_bytes(L.p.queue, L.p.low, L.p.bt, L.p.pull);
     a.cond_off = base;                                        // GENERIC builds: the literal image follows everything else in LDS
-    hipLaunchKernelGGL(kernel, L.grid, L.block, base + (L.b->generic ? L.b->cond_bytes : 0u), L.st, L.b->segs_dev, L.b->tables, a);
+    hipLaunchKernelGGL(kernel, dim3(L.p.blocks), dim3(L.p.bt), base + (L.b->plan.generic ? L.b->plan.cond_bytes : 0u), L.st, L.b->segs_dev, L.b->tables, a);
 }
 
 template <bool LOW, int GEN, bool SINGLE> inline void launch_kind(uint32_t kind, const LaunchShape &L) {
     constexpr bool HAS_ALT = SINGLE && !LOW && GEN == 0;
     constexpr bool NO_RECYCLE = LOW && !SINGLE && GEN == 0;
-    const bool alt = HAS_ALT && L.b->stream_loads != (kind != K_WW8);      // the layouts' default: Werewolf x 8 plain, the others streaming
+    const bool alt = HAS_ALT && L.p.load == LOAD_ALT;
     switch (kind) {
-    // (the large-batch single-turn kernels of the shipped games exist with plain and with streaming record loads: ALT = the form that is not the
-    // layout's default, launched when the batch's stream_loads (create_impl: record_loads) differs from that default)
     case K_WW8:
-        // (the fused lone-wavefront kernel compiles in whether its turns recycle finished rooms - ge_kernels.inl run_ww:
-        // LD = 0 is the restart-on kernel, LD_NO_RECYCLE the restart-off one)
-        if (alt) launch_one(ge_step_kernel<K_WW8, LOW, GEN, SINGLE, HAS_ALT ? 2 : 0>, L, true, LOW);
-        else if (NO_RECYCLE && !L.a.restart) launch_one(ge_step_kernel<K_WW8, LOW, GEN, SINGLE, NO_RECYCLE ? LD_NO_RECYCLE : 0>, L, true, LOW, pull_queue_kernel(K_WW8, LOW, GEN, SINGLE));
-        else launch_one(ge_step_kernel<K_WW8, LOW, GEN, SINGLE>, L, true, LOW, pull_queue_kernel(K_WW8, LOW, GEN, SINGLE));
+        if (alt) launch_one(ge_step_kernel<K_WW8, LOW, GEN, SINGLE, HAS_ALT ? 2 : 0>, L);
+        else if (NO_RECYCLE && L.p.load == LOAD_NO_RECYCLE) launch_one(ge_step_kernel<K_WW8, LOW, GEN, SINGLE, NO_RECYCLE ? LD_NO_RECYCLE : 0>, L);
+        else launch_one(ge_step_kernel<K_WW8, LOW, GEN, SINGLE>, L);
         break;
     case K_WW12:
-        if (alt) launch_one(ge_step_kernel<K_WW12, LOW, GEN, SINGLE, HAS_ALT ? 1 : 0>, L, true, LOW);
-        else launch_one(ge_step_kernel<K_WW12, LOW, GEN, SINGLE>, L, true, LOW);
+        if (alt) launch_one(ge_step_kernel<K_WW12, LOW, GEN, SINGLE, HAS_ALT ? 1 : 0>, L);
+        else launch_one(ge_step_kernel<K_WW12, LOW, GEN, SINGLE>, L);
         break;
     case K_TT4:
-        if (alt) launch_one(ge_step_kernel<K_TT4, LOW, GEN, SINGLE, HAS_ALT ? 1 : 0>, L, tt_uses_queue(4, LOW), LOW);
-        else launch_one(ge_step_kernel<K_TT4, LOW, GEN, SINGLE>, L, tt_uses_queue(4, LOW), LOW);
+        if (alt) launch_one(ge_step_kernel<K_TT4, LOW, GEN, SINGLE, HAS_ALT ? 1 : 0>, L);
+        else launch_one(ge_step_kernel<K_TT4, LOW, GEN, SINGLE>, L);
         break;
     case K_TT8:
-        if (alt) launch_one(ge_step_kernel<K_TT8, LOW, GEN, SINGLE, HAS_ALT ? 1 : 0>, L, tt_uses_queue(8, LOW), LOW);
-        else launch_one(ge_step_kernel<K_TT8, LOW, GEN, SINGLE>, L, tt_uses_queue(8, LOW), LOW);
+        if (alt) launch_one(ge_step_kernel<K_TT8, LOW, GEN, SINGLE, HAS_ALT ? 1 : 0>, L);
+        else launch_one(ge_step_kernel<K_TT8, LOW, GEN, SINGLE>, L);
         break;
     default:
-        if (alt) launch_one(ge_step_kernel<K_TT12, LOW, GEN, SINGLE, HAS_ALT ? 1 : 0>, L, tt_uses_queue(12, LOW), LOW);
-        else launch_one(ge_step_kernel<K_TT12, LOW, GEN, SINGLE>, L, tt_uses_queue(12, LOW), LOW);
+        if (alt) launch_one(ge_step_kernel<K_TT12, LOW, GEN, SINGLE, HAS_ALT ? 1 : 0>, L);
+        else launch_one(ge_step_kernel<K_TT12, LOW, GEN, SINGLE>, L);
         break;
     }
 }
@@ -425,93 +391,36 @@ template <bool LOW, int GEN> inline void launch_kind(uint32_t kind, bool single,
 // Two-Truths fused launches on a table whose generic conditions all have one of the common shapes: the shape-specialised builds
 template <bool LOW, int GEN> inline void launch_tt_shaped(uint32_t kind, const LaunchShape &L) {
     switch (kind) {
-    case K_TT4: launch_one(ge_step_kernel<K_TT4, LOW, GEN, false>, L, tt_uses_queue(4, LOW), LOW); break;
-    case K_TT8: launch_one(ge_step_kernel<K_TT8, LOW, GEN, false>, L, tt_uses_queue(8, LOW), LOW); break;
-    default: launch_one(ge_step_kernel<K_TT12, LOW, GEN, false>, L, tt_uses_queue(12, LOW), LOW); break;
+    case K_TT4: launch_one(ge_step_kernel<K_TT4, LOW, GEN, false>, L); break;
+    case K_TT8: launch_one(ge_step_kernel<K_TT8, LOW, GEN, false>, L); break;
+    default: launch_one(ge_step_kernel<K_TT12, LOW, GEN, false>, L); break;
     }
 }
 template <bool LOW> inline void launch_tt_shaped(uint32_t gshape, uint32_t kind, const LaunchShape &L) {
     if (gshape == 2u) launch_tt_shaped<LOW, 2>(kind, L); else launch_tt_shaped<LOW, 3>(kind, L);
 }
 template <bool LOW, int GEN> inline void launch_mixed(bool single, const LaunchShape &L) {
-    if (single) launch_one(ge_step_kernel_mixed<LOW, GEN, true>, L, true, LOW); else launch_one(ge_step_kernel_mixed<LOW, GEN, false>, L, true, LOW);
+    if (single) launch_one(ge_step_kernel_mixed<LOW, GEN, true>, L); else launch_one(ge_step_kernel_mixed<LOW, GEN, false>, L);
 }
 }  // namespace
 
-// rooms per block and number of blocks of a launch of n_turns turns
-static void launch_geometry(const ge_batch *b, bool low, bool single, uint32_t &bt, uint32_t &blocks, uint32_t &rpb) {
-    bt = b->block_threads; blocks = b->n_blocks;
-    rpb = bt;                                                   // rooms per block
-    // One turn per launch (max_fuse = 1, or the tail of a step): a block's first act is to fill its 7 KB of LDS tables behind a
-    // barrier - the fewer blocks, the less of that per launch - so a large single-game Werewolf x 8 batch runs these launches in
-    // blocks of 512 rooms (GE_SINGLE_BLOCK = 256 / 512 / 1024 overrides, for A/B runs); a single game's rooms start at block 0,
-    // so the grid is just the rooms over the block size
-    // (profiles/r04_ab_single_block.txt, sustained us per launch at 256 / 512 / 1 024 rooms per block: Werewolf x 8 14.23 / 14.01 /
-    // 14.22 at 1 M rooms and 386 / 373 / 377 at 33 M; Werewolf x 12 34.4 / 34.6 / 37.9 at 2 M; Two-Truths x 4 10.2 / 10.2 / 10.4)
-    static const uint32_t single_block_env = [] {
-        const char *e = getenv("GE_SINGLE_BLOCK");
-        const unsigned long v = e ? strtoul(e, nullptr, 10) : 0ul;
-        return (v == 256 || v == 512 || v == 1024) ? (uint32_t)v : 0u;
-    }();
-    if (single && b->segs.size() == 1 && !b->generic && !low && bt == 256u) {
-        // (not below 393 216 rooms: 300 000 rooms are 586 blocks of 512 - 2.3 per CU - and take 6.69 us against 6.10 in 256-room blocks)
-        bt = single_block_env ? single_block_env : (b->segs[0].dev.kind == K_WW8 && b->segs[0].dev.rooms >= 393216u ? 512u : 256u);
-        blocks = (uint32_t)((b->segs[0].dev.rooms + bt - 1u) / bt);
-        rpb = bt;
-    }
-    // A single-game batch of up to 262 144 rooms is cut into 64-room blocks (create_impl: more, shorter blocks balance a fused launch
-    // better).  Its single-turn launches on the large-batch kernels run 256-room blocks all the same - a quarter of the table fills:
-    // sustained us per launch, 64- against 256-room blocks (profiles/r05_k1_midsize.txt): Werewolf x 8 at 131 072 / 262 144 rooms
-    // 4.96 / 6.35 -> 4.21 / 5.40, Two-Truths x 4 at 262 144 5.14 -> 4.58, Werewolf x 12 at 131 072 / 262 144 5.80 / 7.53 -> 5.10 / 6.90
-    // (-8 .. -15 %; -29 % at 524 000 rooms, which create_impl now cuts into 256-room blocks anyway; the lone-wavefront kernels, which fill
-    // nothing, are level at 131 072 rooms and slower beyond).  A mixed batch's segments are padded to its block size, so it keeps it.
-    if (single && b->segs.size() == 1 && !low && bt < 256u && single_block_env == 0u) {
-        bt = 256u;
-        blocks = (uint32_t)((b->segs[0].dev.rooms + bt - 1u) / bt);
-        rpb = bt;
-    }
-    // Half-filled lone wavefronts: a fused launch over a single-game batch of at most 32 768 rooms runs 32 rooms per wavefront (still
-    // at most one wavefront per SIMD).  A lone wavefront's time is its instruction stream, whatever its lanes hold, and a wavefront of
-    // 32 rooms almost never needs the second round of its action queue that 43 % (Werewolf x 8) to 86 % (x 12) of the 64-room
-    // wave-turns take: at 32 768 rooms Werewolf x 8 1.09 -> 0.97 us per turn (-11 %), x 12 -16 %, Two-Truths x 4 / 8 / 12 -9 / -16 /
-    // -19 % (profiles/r05_ab_half_waves.txt).  Not beyond 32 768: two such wavefronts on a SIMD take 1.39 us against 1.06 for one
-    // full one - at this occupancy a SIMD issues about one instruction per 4 cycles in all.  Not for single-turn launches (twice the
-    // blocks to fill tables for: up to +9 %).  GE_HALF_WAVES=0 / 1 forces it off / on (A/B, and a knob run of the test suite)
-    static const int half_env = [] { const char *e = getenv("GE_HALF_WAVES"); return e ? atoi(e) : -1; }();
-    const bool half_fits = b->segs.size() == 1 && low && bt == 64u && (!single || half_env == 1);
-    if (half_fits && (half_env == 1 || (half_env != 0 && b->segs[0].dev.rooms <= 32768u))) {
-        rpb = 32u;
-        blocks = (uint32_t)((b->segs[0].dev.rooms + 31u) / 32u);
-    } else if (half_fits && half_env != 0 && b->segs[0].dev.rooms < 65536u) {
-        // between 32 768 and 65 536 rooms: as few rooms per wavefront as still give every SIMD at most one (49 152 rooms = 1 024 wavefronts of 48):
-        // us per turn against 64 rooms per wavefront (profiles/r05_rooms_per_wavefront.txt) Werewolf x 8 at 40 000 / 49 152 / 57 000 rooms
-        // 1.08 / 1.06 / 1.05 -> 0.98 / 0.96 / 1.02, x 12 1.51 / 1.49 / 1.49 -> 1.29 / 1.35 / 1.43, Two-Truths x 7 1.15 -> 1.01 / 1.01 / 1.09, x 4 -4 %
-        rpb = (uint32_t)((b->segs[0].dev.rooms + 1023u) / 1024u);
-        blocks = (uint32_t)((b->segs[0].dev.rooms + rpb - 1u) / rpb);
-    }
-}
-
-static bool launch_low(const ge_batch *b, const StepArgs &a) {
-    return a.lowocc != 0u && !(b->generic && b->segs.size() > 1);   // mixed batches with generic tables: the large-batch build serves every size
-}
-
 static hipError_t launch_step(const ge_batch *b, const StepArgs &a_in, hipStream_t st) {
-    const bool single = a_in.n_turns == 1u, mixed = b->segs.size() > 1, low = launch_low(b, a_in);
-    uint32_t bt, blocks, rpb;
-    launch_geometry(b, low, single, bt, blocks, rpb);
-    LaunchShape L{dim3(blocks), dim3(bt), st, b, a_in};
-    L.a.block_threads = bt;
-    L.a.rooms_per_block = rpb;
-    const uint32_t kind = b->segs[0].dev.kind;
-    if (mixed) {
-        if (b->generic) launch_mixed<false, 1>(single, L);
-        else if (low) launch_mixed<true, 0>(single, L);
-        else launch_mixed<false, 0>(single, L);
-    } else if (b->generic) {
-        if (b->gshape && !single) { if (low) launch_tt_shaped<true>(b->gshape, kind, L); else launch_tt_shaped<false>(b->gshape, kind, L); }
-        else if (low) launch_kind<true, 1>(kind, single, L); else launch_kind<false, 1>(kind, single, L);
+    const LaunchPlan p = launch_plan(b->plan, a_in.n_turns, a_in.restart != 0u);
+    LaunchShape L{st, b, a_in, p};
+    L.a.block_threads = p.bt;
+    L.a.rooms_per_block = p.rpb;
+    L.a.lowocc = p.low ? 1u : 0u;
+    const uint32_t kind = b->plan.kind0;
+    if (p.mixed) {
+        if (p.gen) launch_mixed<false, 1>(p.single, L);
+        else if (p.low) launch_mixed<true, 0>(p.single, L);
+        else launch_mixed<false, 0>(p.single, L);
+    } else if (p.gen > 1u) {
+        if (p.low) launch_tt_shaped<true>(p.gen, kind, L); else launch_tt_shaped<false>(p.gen, kind, L);
+    } else if (p.gen) {
+        if (p.low) launch_kind<true, 1>(kind, p.single, L); else launch_kind<false, 1>(kind, p.single, L);
     } else {
-        if (low) launch_kind<true, 0>(kind, single, L); else launch_kind<false, 0>(kind, single, L);
+        if (p.low) launch_kind<true, 0>(kind, p.single, L); else launch_kind<false, 0>(kind, p.single, L);
     }
     return hipGetLastError();
 }
@@ -547,11 +456,8 @@ static int ensure_deal_side(ge_batch *b) {
     return GE_OK;
 }
 
-// A ge_batch_step call that needs many launches (small max_fuse: interactive or traced stepping) is
-// launch-bound for small batches; the sequence is captured once per n_turns into a hipGraph whose
-// launches take their first turn relative to a device word, and replayed.
-constexpr uint32_t GRAPH_MIN_LAUNCHES = 4;
-
+// A ge_batch_step call that needs many launches (ge_plan.h LaunchSeq::worth_graph) is launch-bound for small batches; the
+// sequence is captured once per n_turns into a hipGraph whose launches take their first turn relative to a device word, and replayed.
 static hipGraphExec_t graph_for(ge_batch *b, uint32_t n_turns) {
     for (auto &g : b->graphs)
         if (g.first == n_turns) return g.second;
@@ -562,13 +468,12 @@ static hipGraphExec_t graph_for(ge_batch *b, uint32_t n_turns) {
     // (Round 5 also captured the launches as S independent chains over block ranges - parallel graph branches, rooms never
     // interact - to overlap one range's drain with another's steady state: the chains' launches ran on separate hardware queues
     // but never together, and every shorter launch paid its own ramp and drain; 0-65 % slower.  profiles/r05_ab_launch_chains.txt)
-    for (uint32_t done = 0; done < n_turns && ok; ) {
-        const uint32_t k = (n_turns - done) < b->max_fuse ? (n_turns - done) : b->max_fuse;
+    const LaunchSeq seq = launch_sequence(n_turns, b->max_fuse);
+    for (uint32_t i = 0, done = 0; i < seq.n_launch && ok; done += seq.turns(i), i++) {
         StepArgs a;
-        fill_args(b, a, done, k);
+        fill_args(b, a, done, seq.turns(i));
         a.turn_dev = b->turn_dev;
         ok = launch_step(b, a, b->cap_stream) == hipSuccess;
-        done += k;
     }
     if (ok) {
         hipLaunchKernelGGL(ge_turn_bump, dim3(1), dim3(1), 0, b->cap_stream, b->turn_dev, n_turns);
@@ -616,16 +521,15 @@ static int step_impl(ge_batch *b, uint32_t n_turns, void *hip_stream) {
     if ((b->flags & GE_FLAG_TRACE) && n_turns > b->max_fuse) return GE_ERR_RANGE;   // the trace holds one launch
     GE_ON_DEVICE(b);
     if (b->seats) return seat_step_impl(b, n_turns, static_cast<hipStream_t>(hip_stream));   // rooms with seats of their own: plain launches of ge_seat_step_kernel, no prepared deals, no graph
-    if (n_turns % b->max_fuse == 1u || b->max_fuse == 1u) {   // a single-turn launch is due: its Werewolf x 12 segments take deals from the side plane
+    const LaunchSeq seq = launch_sequence(n_turns, b->max_fuse);
+    if (seq.has_single()) {                                   // a single-turn launch is due: its Werewolf x 12 segments take deals from the side plane
         int ds = ensure_deal_side(b);
         if (ds != GE_OK) return ds;
     }
     b->last_step_turns = n_turns;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const uint32_t n_launch = (n_turns + b->max_fuse - 1) / b->max_fuse;
-    static const bool no_graph = getenv("GE_NO_GRAPH") != nullptr;           // A/B runs
     hipGraphExec_t exec = nullptr;
-    if (n_launch >= GRAPH_MIN_LAUNCHES && !b->timing && b->graphs_ok && !no_graph) {
+    if (seq.worth_graph(launch_knobs()) && !b->timing && b->graphs_ok) {
         exec = graph_for(b, n_turns);                       // may synchronise the previous stream (eviction)
         if (!exec) { b->graphs_ok = false; (void)hipGetLastError(); }   // capture unsupported here: plain launches from now on
     }
@@ -637,12 +541,11 @@ static int step_impl(ge_batch *b, uint32_t n_turns, void *hip_stream) {
         HIP_TRY(hipGraphLaunch(exec, st));
         b->turn += n_turns;
         b->turn_dev_value = b->turn;
-        b->launches += n_launch;
+        b->launches += seq.n_launch;
         return GE_OK;
     }
-    uint32_t left = n_turns;
-    while (left) {
-        const uint32_t k = left < b->max_fuse ? left : b->max_fuse;
+    for (uint32_t i = 0; i < seq.n_launch; i++) {
+        const uint32_t k = seq.turns(i);
         StepArgs a;
         fill_args(b, a, (uint32_t)b->turn, k);
         hipEvent_t e1 = nullptr;
@@ -652,7 +555,6 @@ static int step_impl(ge_batch *b, uint32_t n_turns, void *hip_stream) {
         if (e1) HIP_TRY(hipEventRecord(e1, st));
         b->launches++;
         b->turn += k;
-        left -= k;
     }
     return GE_OK;
 }
@@ -1023,7 +925,7 @@ void ge_batch_destroy(ge_batch *b) {
             }
 #if GE_STAMPS == 2
             if (b->segs.size() == 1) {                                       // the last long launch's timeline, one record per wavefront
-                const size_t nw = (size_t)((b->n_rooms + 63) / 64);
+                const size_t nw = b->plan.stamp_records;
                 std::vector<unsigned long long> log(4 * nw);
                 (void)hipMemcpy(log.data(), b->stamps_dev + 8, 32 * nw, hipMemcpyDeviceToHost);
                 std::string path = std::string(getenv("GE_STAMPS_OUT")) + ".waves.bin";

@@ -94,13 +94,13 @@ static int run_forecast_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
         a.acc = reinterpret_cast<unsigned long long *>(dev + o_acc) + (size_t)ROLL_STRIDE * lo;
         const dim3 grid(cnt * waves);
         const uint32_t kind = b->segs[g].dev.kind;
-        HIP_TRY((b->generic ? rollout_launch<1, 2>(kind, grid, s, b, a) : rollout_launch<0, 2>(kind, grid, s, b, a)));
+        HIP_TRY((b->plan.generic ? rollout_launch<1, 2>(kind, grid, s, b, a) : rollout_launch<0, 2>(kind, grid, s, b, a)));
     }
     for (uint32_t g = 0; g < n_seg; g++) {                        // 2. the run
         if (en.begin[g + 1u] == en.begin[g]) continue;
         const RunArgs a = run_args(b, en, g, dev, o_keys, o_turns, o_trace, o_out, max_turns, until);
         const dim3 grid((a.n + 63u) / 64u);
-        HIP_TRY(b->generic ? run_launch<1>(b->segs[g].dev.kind, grid, s, b, a) : run_launch<0>(b->segs[g].dev.kind, grid, s, b, a));
+        HIP_TRY(b->plan.generic ? run_launch<1>(b->segs[g].dev.kind, grid, s, b, a) : run_launch<0>(b->segs[g].dev.kind, grid, s, b, a));
     }
     for (uint32_t g = 0; g < n_seg; g++) {                        // 3. points 1 .. max_turns, from the trace plane
         const uint32_t lo = en.begin[g], cnt = en.begin[g + 1u] - lo;
@@ -114,7 +114,7 @@ static int run_forecast_impl(ge_batch *b, uint64_t n, const uint64_t *rooms, con
         a.n_all = (uint32_t)n; a.first = lo;
         const dim3 grid(cnt * max_turns * waves);                // <= 2^26 / 64 + 2^16 blocks (the caps on the points)
         const uint32_t kind = b->segs[g].dev.kind;
-        HIP_TRY((b->generic ? rollout_launch<1, 5>(kind, grid, s, b, a) : rollout_launch<0, 5>(kind, grid, s, b, a)));
+        HIP_TRY((b->plan.generic ? rollout_launch<1, 5>(kind, grid, s, b, a) : rollout_launch<0, 5>(kind, grid, s, b, a)));
     }
     if (e1) HIP_TRY(hipEventRecord(e1, s));
     // the turn counts first: only the rows of the turns somebody played are copied - unless both planes are small

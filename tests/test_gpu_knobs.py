@@ -1,6 +1,6 @@
 """Every kernel build over every batch size (-m gpu).  Which build a launch gets - the lone-wavefront one or the
-large-batch one, 64- or 256-room blocks - is normally chosen from the batch size (ge_step.hip fill_args / create_impl); the
-knobs GE_LOWOCC_ROOMS / GE_BLOCK_THREADS / GE_NT_LOADS force the choice.  They are read once per process, so every case runs its scenario
+large-batch one, 64- or 256-room blocks - is normally chosen from the batch size (csrc/ge_plan.h batch_plan / launch_plan; on the CPU: tests/test_launch_plan.py); the
+knobs GE_LOWOCC_ROOMS / GE_BLOCK_THREADS / GE_NT_LOADS (ge_plan.h parse_knobs) force the choice.  They are read once per process, so every case runs its scenario
 (tests/knob_worker.py: event trace, host-driven seats + batched injection, mixed batch in steady state - each against the
 oracle, with single-turn and fused launches) in a fresh child process.  Without these the large-batch build's trace path
 and the lone-wavefront mixed kernel with restart would only be covered at the sizes that pick them by default."""

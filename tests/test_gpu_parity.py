@@ -48,7 +48,7 @@ def test_golden_trajectories_fused(name):
 @pytest.mark.parametrize("game,n,n_rooms,turns,rounds", [
     ("werewolf-(mafia)", 8, 65536, 64, 1),          # BASELINE config C2
     ("werewolf-(mafia)", 12, 20000, 80, 1),
-    ("werewolf-(mafia)", 12, 40000, 70, 1),         # 32 769 .. 65 535 rooms: lone wavefronts of 33 .. 63 rooms (ge_step.hip launch_geometry)
+    ("werewolf-(mafia)", 12, 40000, 70, 1),         # 32 769 .. 65 535 rooms: lone wavefronts of 33 .. 63 rooms (csrc/ge_plan.h launch_plan)
     ("werewolf-(mafia)", 8, 57001, 70, 1),
     ("two-truths-and-a-lie", 7, 49152, 70, 1),
     ("werewolf-(mafia)", 4, 5000, 40, 1),
@@ -534,7 +534,7 @@ def test_mixed_batch_with_werewolf_12_single_turn_launches(dsl_ww, dsl_tt, n_roo
 
 @pytest.mark.parametrize("game,n", [("werewolf-(mafia)", 8), ("werewolf-(mafia)", 12), ("two-truths-and-a-lie", 4), ("two-truths-and-a-lie", 9)])
 def test_half_filled_lone_wavefronts_around_their_threshold(game, n):
-    """A fused launch over at most 32 768 rooms runs 32 rooms per wavefront (csrc/ge_step.hip launch_geometry), one more room and it
+    """A fused launch over at most 32 768 rooms runs 32 rooms per wavefront (csrc/ge_plan.h launch_plan), one more room and it
     is 64 again; ragged sizes leave a last wavefront with a handful of rooms in either form.  Every room against the oracle, steady
     state, and the same batch stepped in single-turn launches (always 64 rooms per wavefront) ends in the same bytes."""
     dsl = load_dsl(game)
