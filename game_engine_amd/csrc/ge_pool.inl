@@ -35,7 +35,8 @@
 // segment and their staging as [rooms][keys][turns]), launch_pool_turn and pool_decode_event.  On the device: the indexed lane's
 // context (lane_cond_ctx, lane_ww_ctx), recycle rule (lane_recycle), turn call (lane_ww_turn, lane_tt_turn) and event words
 // (lane_event), and Lane<NB, WWP, GENERIC>, which wraps them per game - record, constants, recycle, turn, pack, PERSON test - so
-// that a kernel body is written once for both games: pool_lane here, seat_lane (ge_seats.inl), find_lane (ge_find.inl).  The turn
+// that a kernel body is written once for both games: pool_lane here, seat_lane (ge_seats.inl), find_lane (ge_find.inl),
+// seat_run_lane (ge_run_seats.inl: a turn loop with stop tests over the type, within the baseline it was given).  The turn
 // loop of ge_run.inl and the playouts of ge_rollout.inl keep a body per game (run_ww / run_tt, roll_ww / roll_tt) on the functions
 // the type wraps: over the type their builds spill more scalar registers than tools/asm_baseline.json allows
 // (profiles/indexed_lane_asm.txt).
@@ -146,6 +147,8 @@ template <int NB, int GENERIC> struct Lane<NB, true, GENERIC> {
         ww_load_regs<NB>(w, s, cache);
     }
     __device__ __forceinline__ uint32_t recycle(const SegDev &sg, uint32_t restart) { return lane_recycle(sg, s, restart, ctx.term_mask); }
+    // on: from here on the lane shadows its room and never acts (a room of a turn loop that has stopped)
+    __device__ __forceinline__ void shadow(bool on) { ctx.valid = !on; }
     __device__ __forceinline__ LaneTurn turn(uint32_t turn, bool log) { return lane_ww_turn<NB, GENERIC>(s, ctx, turn, log); }
     // the canonical record: stored without a prepared deal
     __device__ __forceinline__ void pack(uint32_t *w) const { ww_store_regs<NB>(s, 0u, w); }
@@ -187,6 +190,7 @@ template <int NB, int GENERIC> struct Lane<NB, false, GENERIC> {
         if (restarted) done = __builtin_amdgcn_readfirstlane(sg_.done0);
         return restarted;
     }
+    __device__ __forceinline__ void shadow(bool on) { valid = !on; }
     __device__ __forceinline__ LaneTurn turn(uint32_t turn, bool log) {
         return lane_tt_turn<NB, GENERIC>(s, done, *sg, tables, cc, lw, valid, rk, turn, log, human, tmask);
     }

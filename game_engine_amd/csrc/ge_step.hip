@@ -969,3 +969,4 @@ void ge_batch_destroy(ge_batch *b) {
 #include "ge_advise.inl"        // behind ge_seats.inl: listed seats advised on the device (ge_batch_advise_seats)
 #include "ge_env.inl"           // behind ge_advise.inl: seat observations and actions in device memory (ge_batch_observe_seats, ge_batch_act_seats)
 #include "ge_teach.inl"         // behind ge_env.inl: a seat of every room advised into device memory (ge_batch_teach_seats)
+#include "ge_run_seats.inl"     // behind ge_teach.inl: every room of a range played on until a listed seat must act (ge_batch_run_seats)

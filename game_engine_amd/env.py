@@ -13,8 +13,13 @@ the library binds to the runtime that is loaded first.
 A teacher for the loop (POLICY.md §3o): env.teach(64) fills `advice` with the playout advice of every listed seat - the win odds of
 each choice it can make now - without leaving the device, and advice_fields(advice)["best"] is an action tensor for step().
 
-A room that has ended shows done = 1 once; under restart=True the next step recycles it (the turn that starts from a terminal
-phase re-initialises the room), so the observation after that step is of the new game."""
+A room that has ended shows done = 1 once at one turn per step; under restart=True the next step recycles it (the turn that starts
+from a terminal phase re-initialises the room), so the observation after that step is of the new game.  step(actions, n) with
+n > 1 fuses its turns: under restart=True a game that ends inside the call is recycled inside it as well, and its done and won are
+never observed.  step_until is the call that shows every end (POLICY.md §3p): each room plays on until a listed seat must act, its
+game has ended or the turn limit, so every observation is a decision point, a finished game or the limit -
+
+        obs, done, won = env.step_until(actions)         # env.played: the turns each room took, env.stopped: why it stopped"""
 from typing import Dict, Sequence
 
 from .stepper import RoomBatch, ADVICE_BYTES
@@ -48,9 +53,18 @@ class SeatEnv:
         self.actions = torch.zeros(shape, dtype=torch.int32, device=dev)
         self.status = torch.zeros(shape, dtype=torch.int32, device=dev)
         self.advice = None                                   # uint8 [R, S, 224], made by the first teach()
+        self.played = self.stopped = None                    # int32 [R], made by the first step_until()
 
     def _stream(self) -> int:
         return int(self._torch.cuda.current_stream(self.obs.device).cuda_stream)
+
+    def _act(self, actions, st: int):
+        torch = self._torch
+        a = actions
+        if not (a.dtype == torch.int32 and a.device == self.obs.device and a.is_contiguous() and a.shape == self.actions.shape):
+            self.actions.copy_(a.reshape(self.actions.shape))
+            a = self.actions
+        self.batch.act_seats(self.seats, a, self.status, stream=st)
 
     def observe(self):
         """The observation tensor, filled for the batch as it stands."""
@@ -62,15 +76,29 @@ class SeatEnv:
         action (any integer dtype or device; an int32 tensor on the batch's device is read where it lies); `status` holds each
         entry's verdict afterwards.  Returns (obs, done, won): done and won are bool views [R, S] of the observation.  With
         n_turns > 1 the turns are fused: a room that waits for a listed seat idles, and a finished room stays finished unless
-        the batch restarts, so step(actions, 16) is "play on until my seats are needed", within 16 turns."""
-        torch = self._torch
-        a = actions
-        if not (a.dtype == torch.int32 and a.device == self.obs.device and a.is_contiguous() and a.shape == self.actions.shape):
-            self.actions.copy_(a.reshape(self.actions.shape))
-            a = self.actions
+        the batch restarts, so step(actions, 16) is "play on until my seats are needed", within 16 turns - without restart
+        only: a restarting batch recycles a game that ends inside the call, and step_until is the call to use."""
         st = self._stream()
-        self.batch.act_seats(self.seats, a, self.status, stream=st)
+        self._act(actions, st)
         self.batch.step(n_turns, stream=st)
+        self.batch.observe_seats(self.seats, self.obs, stream=st)
+        f = self.fields(self.obs)
+        return self.obs, f["done"], f["won"]
+
+    def step_until(self, actions, max_turns: int = 16, until=("seat", "end")):
+        """act_seats(actions), batch.run_seats(max_turns, until), observe_seats - all on torch's current stream (POLICY.md §3p).
+        Every room plays on until a listed seat is a pending target ("seat"), its game has ended ("end") or max_turns turns are
+        played, so no end is lost under restart=True: a finished room is observed with done = 1 and recycled by the next call's
+        first turn.  `until` as RoomBatch.run_seats takes it.  Returns (obs, done, won) as step(); `played` and `stopped` (int32
+        [R], allocated on first use) hold the turns each room took and the RUN_SEATS_UNTIL bits that stopped it (0: the limit).
+        The batch's turn advances by max_turns per call."""
+        if self.played is None:
+            torch = self._torch
+            self.played = torch.zeros(self.batch.n_rooms, dtype=torch.int32, device=self.obs.device)
+            self.stopped = torch.zeros(self.batch.n_rooms, dtype=torch.int32, device=self.obs.device)
+        st = self._stream()
+        self._act(actions, st)
+        self.batch.run_seats(self.seats, self.played, self.stopped, max_turns, until, stream=st)
         self.batch.observe_seats(self.seats, self.obs, stream=st)
         f = self.fields(self.obs)
         return self.obs, f["done"], f["won"]

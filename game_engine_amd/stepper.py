@@ -66,6 +66,9 @@ def run_until_names(bits: int) -> List[str]:
     return [name for name, bit in RUN_UNTIL.items() if bits & bit]
 
 
+RUN_SEATS_UNTIL = dict(RUN_UNTIL, seat=8)         # include/ge_step.h GE_RUN_UNTIL_SEAT: run_seats alone takes it
+
+
 FIND_WANT = {"person": 1, "end": 2, "phase": 4}   # include/ge_step.h GE_FIND_*
 # include/ge_step.h ge_room_hit
 ROOM_HIT_DTYPE = np.dtype([("room", "<u8"), ("why", "<u4"), ("pending", "<u2"), ("phase_id", "u1"), ("segment", "u1")])
@@ -681,6 +684,30 @@ class RoomBatch:
             raise GeError(GE_ERR_ARG, "act_seats: choices / status hold fewer than count * len(seats) int32 entries")
         _check(self._lib.ge_batch_act_seats(self._h, first, count, len(seats), seats.ctypes.data if len(seats) else None, ptr, st_ptr,
                                             C.c_void_p(stream or None)), "ge_batch_act_seats")
+
+    def run_seats(self, seats, played, stopped=None, max_turns: int = 16, until=("seat", "end"), first: int = 0, count: Optional[int] = None,
+                  stream: int = 0):
+        """Play every room of first .. first + count - 1 on until a listed seat (1-based, pairwise distinct) must act, with the
+        results in DEVICE memory the caller owns (POLICY.md §3p): room r takes run_rooms's entry (r, its global index, the batch's
+        turn) under max_turns and `until` - a sequence of "person" / "end" / "phase" / "seat", or the bit set; "seat": some listed
+        seat is a pending target of the record the turn left (its observation's `legal` is not 0).  The turn is step_rooms's: the
+        room's own seat mask decides whom the policy plays, the seat list plays no part in it.  `played` (uint32 or int32, count
+        entries, the kinds of object observe_seats takes) gets the turns each room played, `stopped` (optional, the same) the
+        RUN_SEATS_UNTIL bits that held after its last turn (0: the limit).  The batch's turn advances by max_turns whatever the
+        rooms played.  Launched on `stream`, asynchronous, ordered behind the batch's earlier work as step() is; nothing crosses
+        to the host."""
+        seats = np.ascontiguousarray(seats, dtype=np.uint32)
+        count = self.n_rooms - first if count is None else count
+        bits = _named_bits(until, RUN_SEATS_UNTIL, "until: unknown stop condition")
+        if int(max_turns) < 0 or int(max_turns) > 0xFFFFFFFF:   # no uint32 at all (0 and values above the cap go to the library's checks)
+            raise GeError(GE_ERR_ARG, "run_seats: max_turns")
+        need = 4 * int(count)
+        ptr, nbytes = _device_buffer(played) if played is not None else (None, need)
+        st_ptr, st_bytes = _device_buffer(stopped) if stopped is not None else (None, need)
+        if nbytes < need or st_bytes < need:
+            raise GeError(GE_ERR_ARG, "run_seats: played / stopped hold fewer than count 4-byte entries")
+        _check(self._lib.ge_batch_run_seats(self._h, first, count, len(seats), seats.ctypes.data if len(seats) else None, max_turns, bits,
+                                            ptr, st_ptr, C.c_void_p(stream or None)), "ge_batch_run_seats")
 
     def teach_seats(self, seats, out, n_rollouts: int, max_turns: int = 1024, *, first: int = 0, count: Optional[int] = None, keys=None,
                     key0: int = 0, turn: Optional[int] = None, seed: Optional[int] = None, full_view: bool = False, stream: int = 0):

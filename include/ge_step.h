@@ -54,7 +54,8 @@ extern "C" {
  *      ge_batch_find_rooms + ge_room_hit + GE_FIND_* (a device scan of a range: the rooms that wait for a person, have ended or stand in given phases);
  *      ge_batch_advise_seats + ge_advice + GE_ADVISE_FULL_VIEW (listed seats advised on the device: their legal choices found, played and ranked);
  *      ge_batch_observe_seats + ge_batch_act_seats + ge_seat_obs (a seat of every room observed into, and played from, device memory the caller owns);
- *      ge_batch_teach_seats (ge_batch_advise_seats for a seat list of every room of a range, into device memory the caller owns) */
+ *      ge_batch_teach_seats (ge_batch_advise_seats for a seat list of every room of a range, into device memory the caller owns);
+ *      ge_batch_run_seats + GE_RUN_UNTIL_SEAT (every room of a range played on until a listed seat must act, turn counts and stop bits in device memory) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -806,6 +807,53 @@ int ge_batch_teach_seats(ge_batch *b, uint64_t first, uint64_t count, uint32_t n
                          const uint64_t *keys_dev /* DEVICE: count, or NULL */, uint64_t key0, uint32_t turn,
                          uint32_t n_rollouts, uint32_t max_turns, uint64_t seed, uint32_t flags /* GE_ADVISE_FULL_VIEW */,
                          ge_advice *out_dev /* DEVICE: count * n_seats */, size_t cap_bytes, void *hip_stream);
+
+/* Every room of a range played on until a listed seat must act, in device memory (POLICY.md §3p): the step between
+ * ge_batch_act_seats and ge_batch_observe_seats that loses no game end.  Under GE_FLAG_RESTART a fused ge_batch_step recycles a
+ * finished room on the very next turn, so the observation behind it never shows `done`; here a room stops where the learner has
+ * to look at it.  Result, by composition: with T the batch's turn counter at the call, every room r of first .. first + count - 1
+ * (local indices, as ge_batch_read_rooms counts) takes exactly ge_batch_run_rooms's entry (rooms = r, keys = the global index of r,
+ * turns = T) under max_turns and until & 7, with one more stop test:
+ *   GE_RUN_UNTIL_SEAT    on the record the turn left, some listed seat is a pending target: ge_batch_inject_action(r, seat, c)
+ *                        would be accepted for at least one c - ge_seat_obs.legal != 0 for that seat.  It is GE_RUN_UNTIL_PERSON's
+ *                        test word for word with the listed seats in place of the room's seat mask.
+ * The turn itself is ge_batch_step_rooms's: the room's seat mask (the segment's human_mask, or the seat plane) decides whom the
+ * policy plays, and the seat list plays no part in the turn, as for ge_batch_observe_seats - a caller that plays a seat makes it
+ * host-driven.  The first turn is always played.  played_dev[r - first] = turns played; stopped_dev[r - first] (may be NULL) = the
+ * named bits that held after the last played turn (0: the limit was hit).  The stored record is the one after the last played
+ * turn, without a prepared deal; the Werewolf x 12 side plane is neither read nor written, so ge_batch_step before or after stays
+ * exact.  The turn counter advances by max_turns whatever the rooms played: rooms that stopped early, and rooms outside the
+ * range, simply took no turn at the later indices - the RNG is keyed by (room, turn), so any turn is a valid next turn.  The
+ * GE_FLAG_TRACE buffer and what ge_batch_read_events reports are untouched.  A room that stopped in a terminal phase is recycled by
+ * the first turn of the next call under GE_FLAG_RESTART, as ge_batch_step_rooms does it: every end is there to be observed once.
+ * So max_turns = 1, until = 0 is ge_batch_step_rooms over the range word for word, and until = 0 leaves the records that
+ * ge_batch_step(max_turns) leaves on the same batch with a seat plane.
+ * The stream contract is ge_batch_observe_seats's: the launches go on hip_stream, behind the batch's earlier work; later calls on
+ * the batch are ordered behind them; no byte crosses to the host and the host waits for nothing.  With ge_batch_set_timing on, the
+ * call is one interval of ge_batch_kernel_time.
+ * All checks run before anything is launched, and a failure touches nothing, in this order: GE_ERR_ARG for b NULL; for max_turns
+ * 0 or above 4096; for `until` bits above 15, or GE_RUN_UNTIL_SEAT with n_seats == 0; for played_dev NULL with count > 0; for
+ * seats NULL with n_seats > 0, n_seats > 12 or a repeated seat; GE_ERR_RANGE for a range beyond the batch; GE_ERR_ARG for a seat
+ * of 0 or above the n_players of a segment the range touches; for played_dev / stopped_dev (count x 4 bytes each) that the
+ * batch's device does not reach, vetted as ge_batch_observe_seats vets obs_dev; GE_ERR_RANGE for T + max_turns > 0xFFFFFFFF; then
+ * count == 0: GE_OK, nothing launched, the turn counter unchanged.  ge_batch_run_rooms and its siblings go on refusing bit 8.
+ * On the device: lane = room, one wavefront per block, one launch per segment of the range; ge_batch_step's ranged turn loop under
+ * a seat plane with ge_batch_run_rooms's stop tests, no trace plane and no staging.  The action queue is a wave-wide collective,
+ * so a room that has stopped stores its record, its turn count and its stop bits and its lane stays on as a shadow that never
+ * acts: a wavefront leaves with its last room, which is the call's inherent cost.
+ * Measured on an MI355X (tools/run_seats_probe.py, profiles/run_seats_probe.txt: Werewolf x 8, human_mask = 1, restart on, 40 turns
+ * stepped first, seat 1 played by a uniform legal choice computed in torch on the device, max_turns = 16; medians of 15).  (a) Wall
+ * time per decision point delivered - an observation entry with legal != 0 or done - through act_seats, run_seats, observe_seats
+ * against the one way without the call that loses no game end under restart, act_seats, ge_batch_step(1), observe_seats per turn:
+ * 4.61 ns against 36.0 ns at 65 536 rooms (x 7.8), 0.96 ns against 5.22 ns at 1 048 576 (x 5.5); the baseline timed against itself
+ * in the same run: x 0.99 and x 1.00.  (b) The call alone, launch interval: 30.8 us (+- 11.6) and 269.6 us (+- 11.4) at a mean
+ * `played` of 8.1 turns; 49.4 % of the wavefront-turns are spent by shadow lanes (1 - mean played / mean over wavefronts of the
+ * most any of its rooms played): what compacting live rooms across wavefronts could shed at most.  No other shape has been measured. */
+#define GE_RUN_UNTIL_SEAT 8u   /* accepted by ge_batch_run_seats only: stop after a turn that leaves a listed seat a pending target */
+int ge_batch_run_seats(ge_batch *b, uint64_t first, uint64_t count, uint32_t n_seats,
+                       const uint32_t *seats /* host, 1-based, may be NULL with n_seats == 0 */, uint32_t max_turns, uint32_t until,
+                       uint32_t *played_dev /* DEVICE: count */, uint32_t *stopped_dev /* DEVICE: count, may be NULL */,
+                       void *hip_stream);
 
 /* GE_FLAG_TRACE: events of the most recent ge_batch_step call, dst[(room - first) * *n_turns + t].
  * cap_bytes >= count * n_turns * sizeof(ge_turn_event).  Synchronises. */

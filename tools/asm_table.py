@@ -45,6 +45,9 @@ def describe(mangled: str) -> dict:
     m = re.search(r"ge_seat_step_kernelILi(\d)ELi(\d)E", mangled)
     if m:
         return {"kernel": "ge_seat_step_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": False}
+    m = re.search(r"ge_seat_run_kernelILi(\d)ELi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_seat_run_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True}
     m = re.search(r"ge_rollout_kernelILi(\d)ELi(\d)E(?:Li(\d)E)?", mangled)
     if m:
         return {"kernel": "ge_rollout_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True,
@@ -116,6 +119,8 @@ def label(r):
         return f"{r['kernel']} (ge_batch_find_rooms: {what})"
     if r["kernel"] == "ge_seat_step_kernel":                     # ge_batch_step of a batch with a seat plane: one launch per segment and per max_fuse turns
         return f"{r['layout']}, whole-batch step under per-room seats (ge_batch_step after ge_batch_set_seats)" + (", GENERIC" if r["generic"] else "")
+    if r["kernel"] == "ge_seat_run_kernel":                      # ge_batch_run_seats: one launch per segment of the range
+        return f"{r['layout']}, seat run-on (ge_batch_run_seats)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] in ("ge_seats_fill", "ge_seats_scatter"):     # ge_batch_set_seats
         what = {"ge_seats_fill": "a segment's mask for its rooms", "ge_seats_scatter": "the listed rooms' masks"}[r["kernel"]]
         return f"{r['kernel']} (ge_batch_set_seats: {what})"
