@@ -95,12 +95,13 @@ SEAT_OBS_BYTES = C.sizeof(SeatObs)               # 192
 
 ADVISE_FULL_VIEW = 1                             # GE_ADVISE_FULL_VIEW
 BELIEF_SLOTS = 16                                # GE_BELIEF_SLOTS
+GATHER_WANT = {"seat": 1, "end": 2}              # GE_GATHER_SEAT, GE_GATHER_END
 
 # every symbol include/ge_step.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = ["ge_table_compile_json", "ge_table_dev_row", "ge_batch_create", "ge_batch_step", "ge_batch_reset", "ge_batch_set_turn", "ge_batch_inject_actions", "ge_batch_sync", "ge_batch_turn",
            "ge_batch_n_rooms", "ge_batch_read_rooms", "ge_batch_write_rooms", "ge_batch_read_events", "ge_batch_inject_action", "ge_batch_summary",
            "ge_batch_state", "ge_batch_set_timing", "ge_batch_kernel_time", "ge_batch_destroy", "ge_batch_step_rooms", "ge_batch_read_rooms_at",
-           "ge_batch_write_rooms_at", "ge_batch_rollout_rooms", "ge_batch_rollout_actions", "ge_batch_rollout_seats", "ge_batch_rollout_compare", "ge_batch_rollout_beliefs", "ge_batch_step_rooms_playout", "ge_batch_run_rooms", "ge_batch_run_rooms_playout", "ge_batch_run_rooms_forecast", "ge_batch_find_rooms", "ge_batch_set_seats", "ge_batch_get_seats", "ge_batch_clear_seats", "ge_batch_advise_seats", "ge_batch_observe_seats", "ge_batch_act_seats", "ge_batch_teach_seats", "ge_batch_run_seats", "ge_group_partition", "ge_batch_create_shard", "ge_group_create", "ge_group_size", "ge_group_shard", "ge_group_step", "ge_group_sync", "ge_group_summary", "ge_group_destroy",
+           "ge_batch_write_rooms_at", "ge_batch_rollout_rooms", "ge_batch_rollout_actions", "ge_batch_rollout_seats", "ge_batch_rollout_compare", "ge_batch_rollout_beliefs", "ge_batch_step_rooms_playout", "ge_batch_run_rooms", "ge_batch_run_rooms_playout", "ge_batch_run_rooms_forecast", "ge_batch_find_rooms", "ge_batch_set_seats", "ge_batch_get_seats", "ge_batch_clear_seats", "ge_batch_advise_seats", "ge_batch_observe_seats", "ge_batch_act_seats", "ge_batch_teach_seats", "ge_batch_run_seats", "ge_batch_gather_seats", "ge_batch_act_listed", "ge_group_partition", "ge_batch_create_shard", "ge_group_create", "ge_group_size", "ge_group_shard", "ge_group_step", "ge_group_sync", "ge_group_summary", "ge_group_destroy",
            "ge_strerror", "ge_last_hip_error", "ge_last_rejected_room", "ge_last_comm_error", "ge_abi_version", "ge_device_count"]
 
 _lib = None
@@ -203,6 +204,9 @@ def load() -> C.CDLL:
         lib.ge_batch_teach_seats.argtypes = [vp, u64, u64, u32, vp, vp, u64, u32, u32, u32, u64, u32, vp, C.c_size_t, vp]
     if hasattr(lib, "ge_batch_run_seats") or not any_abi:
         lib.ge_batch_run_seats.argtypes = [vp, u64, u64, u32, vp, u32, u32, vp, vp, vp]
+    if hasattr(lib, "ge_batch_gather_seats") or not any_abi:
+        lib.ge_batch_gather_seats.argtypes = [vp, u64, u64, u32, vp, u32, vp, vp, u64, vp, vp]
+        lib.ge_batch_act_listed.argtypes = [vp, u64, u64, u32, vp, vp, u64, vp, vp, vp, vp]
     if hasattr(lib, "ge_group_create") or not any_abi:
         lib.ge_group_create.argtypes = [C.POINTER(BatchDesc), C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
         lib.ge_group_size.argtypes = [vp]

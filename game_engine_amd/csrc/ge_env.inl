@@ -4,6 +4,8 @@
 // offsets).  Between them ge_batch_step is unchanged.  Both calls keep ge_batch_step's stream contract - launched on the
 // caller's stream behind the batch's earlier work, no host copy, no host wait - so nothing here uses the indexed calls' staging.
 //
+//   ObsRoom            a room as its seats are shown it - the record unpacked, what its seats' records share, and one seat's record
+//                      vector by vector; ge_observe_kernel and ge_gather_emit (ge_decide.inl) both build their records with it.
 //   ge_observe_kernel  lane = room, one wavefront per block, the record loaded as ge_find_kernel loads it; one launch per
 //                      segment of the range, the seat list by value in the arguments (a nibble per seat: no array to index).
 //                      Per listed seat: the knowledge sets of §3c from the statements ge_rollout.inl's re-deal itself runs
@@ -129,36 +131,35 @@ __device__ __forceinline__ void obs_columns(TT<NB> s, uint32_t seat, uint32_t n,
     put(11, dv);
 }
 
-template <int KIND>
-__global__ void __launch_bounds__(64) ge_observe_kernel(const SegDev *__restrict__ segs, const DevTable *__restrict__ tables, const EnvArgs a) {
-    constexpr int NB = KindOf<KIND>::NB;
-    constexpr bool WWP = KindOf<KIND>::WW;
+// a room as its seats are shown it: the record loaded and unpacked, what every seat's record shares, and record(seat, put) - the
+// `legal` loop, the columns and the two header vectors of one seat.  ge_observe_kernel and ge_gather_emit (ge_decide.inl) both
+// build their records here
+template <int NB, bool WWP> struct ObsRoom {
     using G = PlayoutGame<NB, WWP>;
     using L = typename G::L;
-    __shared__ u32x4 stage[64u * OBS_LDS_VEC];
-    const SegDev &sg = segs[a.seg];
-    const uint64_t kb = (uint64_t)blockIdx.x * 64u, k = kb + threadIdx.x;
-    const bool valid = k < a.nr;
-    const uint64_t room = a.r0 + (valid ? k : 0u);            // lanes past the part read its first room and store nothing
-    uint32_t w[L::WORDS];
-    load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
     typename G::S s;
-    L::unpack(w, s);
-    const DevRow &row = tables[sg.table_idx].rows[s.phase];
-    const DevCond &cond = tables[sg.table_idx].conds[s.phase];   // read in place, as inject_group_ww / inject_group_tt
-    const uint32_t n = sg.n_players, act = (row.r0 >> 2) & 7u, C = WWP ? n : 3u;
-    const bool done = ((sg.term_mask >> s.phase) & 1u) != 0u;
+    const DevRow *row;
+    const DevCond *cond;
+    uint32_t n, act, phase_id;
+    bool done;
     u32x4 h1;
-    h1.x = (uint32_t)a.phase_ids[s.prev & (GE_MAX_PHASES - 1u)]; h1.y = s.end_turn == END_NONE ? 0xFFFFFFFFu : s.end_turn; h1.z = s.games; h1.w = 0u;
-    const uint32_t phase_id = (uint32_t)a.phase_ids[s.phase & (GE_MAX_PHASES - 1u)];   // (a row index is below 32: the mask keeps any record inside the table)
-    auto *out = (__attribute__((address_space(1))) u32x4 *)(uintptr_t)a.obs;
-    for (uint32_t j = 0; j < a.n_seats; j++) {
-        const uint32_t seat = (uint32_t)(a.seats >> (4u * j)) & 15u;
-        auto put = [&](int i, u32x4 v) { stage[threadIdx.x * OBS_LDS_VEC + (uint32_t)i] = v; };
+    __device__ __forceinline__ void open(const SegDev &sg, const DevTable *__restrict__ tables, const int32_t *__restrict__ phase_ids, uint64_t room) {
+        uint32_t w[L::WORDS];
+        load_words<L::WORDS>(sg.base, sg.rooms_padded, room, w);
+        L::unpack(w, s);
+        row = &tables[sg.table_idx].rows[s.phase];
+        cond = &tables[sg.table_idx].conds[s.phase];          // read in place, as inject_group_ww / inject_group_tt
+        n = sg.n_players; act = (row->r0 >> 2) & 7u;
+        done = ((sg.term_mask >> s.phase) & 1u) != 0u;
+        h1.x = (uint32_t)phase_ids[s.prev & (GE_MAX_PHASES - 1u)]; h1.y = s.end_turn == END_NONE ? 0xFFFFFFFFu : s.end_turn; h1.z = s.games; h1.w = 0u;
+        phase_id = (uint32_t)phase_ids[s.phase & (GE_MAX_PHASES - 1u)];   // (a row index is below 32: the mask keeps any record inside the table)
+    }
+    template <class PUT> __device__ __forceinline__ void record(uint32_t seat, PUT &&put) const {
+        const uint32_t C = WWP ? n : 3u;
         uint32_t legal = 0;
         for (uint32_t c = 1; c <= C; c++) {                   // ge_advise_plan's loop: legal exactly when the injected action would be accepted
             typename G::S t = s;
-            legal |= (G::inject(t, row, cond, n, seat, c) == GE_OK ? 1u : 0u) << (c - 1u);
+            legal |= (G::inject(t, *row, *cond, n, seat, c) == GE_OK ? 1u : 0u) << (c - 1u);
         }
         uint32_t unknown, won;
         obs_columns(s, seat, n, act, done, unknown, won, put);
@@ -169,6 +170,22 @@ __global__ void __launch_bounds__(64) ge_observe_kernel(const SegDev *__restrict
         h0.w = phase_id;
         put(0, h0);
         put(1, h1);
+    }
+};
+
+template <int KIND>
+__global__ void __launch_bounds__(64) ge_observe_kernel(const SegDev *__restrict__ segs, const DevTable *__restrict__ tables, const EnvArgs a) {
+    __shared__ u32x4 stage[64u * OBS_LDS_VEC];
+    const SegDev &sg = segs[a.seg];
+    const uint64_t kb = (uint64_t)blockIdx.x * 64u, k = kb + threadIdx.x;
+    const bool valid = k < a.nr;
+    const uint64_t room = a.r0 + (valid ? k : 0u);            // lanes past the part read its first room and store nothing
+    ObsRoom<KindOf<KIND>::NB, KindOf<KIND>::WW> o;
+    o.open(sg, tables, a.phase_ids, room);
+    auto *out = (__attribute__((address_space(1))) u32x4 *)(uintptr_t)a.obs;
+    for (uint32_t j = 0; j < a.n_seats; j++) {
+        const uint32_t seat = (uint32_t)(a.seats >> (4u * j)) & 15u;
+        o.record(seat, [&](int i, u32x4 v) { stage[threadIdx.x * OBS_LDS_VEC + (uint32_t)i] = v; });
         __syncthreads();
         const uint64_t left = a.nr - kb;                      // (the block holds a room: kb < nr)
         const uint32_t live = left < 64u ? (uint32_t)left : 64u;
@@ -236,13 +253,9 @@ static_assert(sizeof(ge_seat_obs) == 16 * OBS_VEC, "an observation is 12 16-byte
 static_assert(offsetof(ge_seat_obs, legal) == 8 && offsetof(ge_seat_obs, phase_id) == 12 && offsetof(ge_seat_obs, prev_phase_id) == 16 &&
               offsetof(ge_seat_obs, players) == 32 && offsetof(ge_seat_obs, det) == 176, "header, header, nine vectors of columns, det");
 
-// the checks both calls share, in their order (ABI behaviour); dev / dev2: the call's device pointers (dev2 may be null) and their
-// bytes per entry.  GE_OK with *go = false: nothing to do
-static int env_check(const ge_batch *b, uint64_t first, uint64_t count, uint32_t n_seats, const uint32_t *seats, const void *dev, size_t per_entry,
-                     const void *dev2, size_t per_entry2, size_t cap_bytes, uint64_t *packed, bool *go) {
-    *go = false;
-    const bool some = count > 0u && n_seats > 0u;
-    if (some && (!seats || !dev)) return GE_ERR_ARG;
+// the seat list and the range of a ranged seat call, in their order (ABI behaviour): at most twelve seats, pairwise distinct; the
+// range inside the batch; every seat one of each segment the range touches.  *packed: nibble j = seats[j]
+static int env_check_list(const ge_batch *b, uint64_t first, uint64_t count, uint32_t n_seats, const uint32_t *seats, uint64_t *packed) {
     if (n_seats > GE_MAX_PLAYERS) return GE_ERR_ARG;
     *packed = 0;
     for (uint32_t j = 0; seats && j < n_seats; j++)
@@ -255,6 +268,18 @@ static int env_check(const ge_batch *b, uint64_t first, uint64_t count, uint32_t
             if (std::max(first, s.local_first) < std::min(first + count, s.local_first + s.dev.rooms) && seats[j] > s.dev.n_players) return GE_ERR_ARG;
         if (seats[j] <= GE_MAX_PLAYERS) *packed |= (uint64_t)seats[j] << (4u * j);
     }
+    return GE_OK;
+}
+
+// the checks both calls share, in their order (ABI behaviour); dev / dev2: the call's device pointers (dev2 may be null) and their
+// bytes per entry.  GE_OK with *go = false: nothing to do
+static int env_check(const ge_batch *b, uint64_t first, uint64_t count, uint32_t n_seats, const uint32_t *seats, const void *dev, size_t per_entry,
+                     const void *dev2, size_t per_entry2, size_t cap_bytes, uint64_t *packed, bool *go) {
+    *go = false;
+    const bool some = count > 0u && n_seats > 0u;
+    if (some && (!seats || !dev)) return GE_ERR_ARG;
+    const int rc = env_check_list(b, first, count, n_seats, seats, packed);
+    if (rc != GE_OK) return rc;
     const uint64_t entries = count * (uint64_t)n_seats;       // (count <= n_rooms, n_seats <= 12)
     if (cap_bytes / per_entry < entries) return GE_ERR_ARG;
     if (some && (!env_reachable(b, dev, (size_t)entries * per_entry) || (dev2 && !env_reachable(b, dev2, (size_t)entries * per_entry2)))) return GE_ERR_ARG;

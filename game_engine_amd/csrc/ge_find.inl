@@ -8,7 +8,8 @@
 //                    reads 64 consecutive elements of each plane).  One result word per room - why | pending << 8 | row << 24,
 //                    or 0 - and one match count per wavefront (__ballot + popcount).  One launch per segment of the range: a
 //                    segment's part of the range owns a stretch of result words padded to whole wavefronts.
-//   ge_find_scan     one block: the exclusive scan of the wavefront counts, FIND_SCAN_WAVES of them per pass, and the total.
+//   ge_find_scan     one block: the exclusive scan of the wavefront counts, FIND_SCAN_WAVES of them per pass, and the total
+//                    (find_scan_block: ge_decide.inl's ge_gather_scan is the same block with another way to report the total).
 //   ge_find_emit     re-reads the result words (not the records) and stores each hit at its wavefront's offset + its rank among
 //                    the wavefront's hits (mbcnt), dropping what lies at or beyond cap.  So the order of the output is the order
 //                    of the rooms, whatever the order the blocks ran in.
@@ -76,9 +77,9 @@ __global__ void __launch_bounds__(FIND_BLOCK) ge_find_kernel(const SegDev *__res
     }
 }
 
-// counts[0 .. n_waves) -> offsets[w] = hits in front of wavefront w; *total = all of them.  One block of FIND_SCAN_WAVES threads
-__global__ void __launch_bounds__(FIND_SCAN_WAVES) ge_find_scan(const uint32_t *__restrict__ counts, uint64_t n_waves, uint64_t *__restrict__ offsets,
-                                                                uint64_t *__restrict__ total) {
+// counts[0 .. n_waves) -> offsets[w] = hits in front of wavefront w; returns all of them (in every thread).  One block of
+// FIND_SCAN_WAVES threads: the body of ge_find_scan and of ge_gather_scan (ge_decide.inl)
+__device__ __forceinline__ uint64_t find_scan_block(const uint32_t *__restrict__ counts, uint64_t n_waves, uint64_t *__restrict__ offsets) {
     __shared__ uint32_t wave_sum[FIND_SCAN_WAVES / 64u];
     const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
     uint64_t carry = 0;
@@ -106,7 +107,14 @@ __global__ void __launch_bounds__(FIND_SCAN_WAVES) ge_find_scan(const uint32_t *
         carry += all;
         __syncthreads();
     }
-    if (t == 0u) *total = carry;
+    return carry;
+}
+
+// ... and *total = all of them
+__global__ void __launch_bounds__(FIND_SCAN_WAVES) ge_find_scan(const uint32_t *__restrict__ counts, uint64_t n_waves, uint64_t *__restrict__ offsets,
+                                                                uint64_t *__restrict__ total) {
+    const uint64_t all = find_scan_block(counts, n_waves, offsets);
+    if (threadIdx.x == 0u) *total = all;
 }
 
 // result word j -> hits[offset of its wavefront + rank], if below cap

@@ -970,3 +970,4 @@ void ge_batch_destroy(ge_batch *b) {
 #include "ge_env.inl"           // behind ge_advise.inl: seat observations and actions in device memory (ge_batch_observe_seats, ge_batch_act_seats)
 #include "ge_teach.inl"         // behind ge_env.inl: a seat of every room advised into device memory (ge_batch_teach_seats)
 #include "ge_run_seats.inl"     // behind ge_teach.inl: every room of a range played on until a listed seat must act (ge_batch_run_seats)
+#include "ge_decide.inl"       // behind ge_run_seats.inl: decision lists - the due (room, seat) entries of a range gathered and played (ge_batch_gather_seats, ge_batch_act_listed)

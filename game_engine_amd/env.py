@@ -19,7 +19,16 @@ n > 1 fuses its turns: under restart=True a game that ends inside the call is re
 never observed.  step_until is the call that shows every end (POLICY.md §3p): each room plays on until a listed seat must act, its
 game has ended or the turn limit, so every observation is a decision point, a finished game or the limit -
 
-        obs, done, won = env.step_until(actions)         # env.played: the turns each room took, env.stopped: why it stopped"""
+        obs, done, won = env.step_until(actions)         # env.played: the turns each room took, env.stopped: why it stopped
+
+Where the learner sits in every seat (self-play: all seats listed and host-driven), most entries of the [R, S] grid are no decision
+point.  decisions() / step_decisions() work on a decision list instead (POLICY.md §3q): only the entries that are due, in entry
+order, with their observations -
+
+    dec_obs, dec_entries, dec_n = env.decisions()
+    for _ in range(steps):
+        choices = SeatEnv.random_legal(dec_obs)          # over all cap rows: no mask, the list's length stays on the device
+        dec_obs, dec_entries, dec_n = env.step_decisions(choices)"""
 from typing import Dict, Sequence
 
 from .stepper import RoomBatch, ADVICE_BYTES
@@ -35,7 +44,8 @@ _ADVICE_HEAD = {"status": 0, "legal_bits": 1, "best": 2, "phase_id": 3}
 class SeatEnv:
     """Owns `obs` (uint8 [R, S, 192]: one ge_seat_obs per room and listed seat), `actions` and `status` (int32 [R, S]) on the
     batch's device, and `advice` (uint8 [R, S, 224]: one ge_advice each) from the first teach() on; R = batch.n_rooms,
-    S = len(seats).  The human mask and the seat plane play no part: to keep the policy from playing a listed seat as well, make
+    S = len(seats); from the first decisions() on the decision list as well: `dec_obs` (uint8 [cap, 192]), `dec_entries`,
+    `dec_choices`, `dec_status` (int32 [cap]) and `dec_n` (int32 [2]).  The human mask and the seat plane play no part: to keep the policy from playing a listed seat as well, make
     it host-driven in the batch (human_mask / set_seats)."""
 
     def __init__(self, batch: RoomBatch, seats: Sequence[int]):
@@ -53,7 +63,9 @@ class SeatEnv:
         self.actions = torch.zeros(shape, dtype=torch.int32, device=dev)
         self.status = torch.zeros(shape, dtype=torch.int32, device=dev)
         self.advice = None                                   # uint8 [R, S, 224], made by the first teach()
-        self.played = self.stopped = None                    # int32 [R], made by the first step_until()
+        self.played = self.stopped = None                    # int32 [R], made by the first step_until() / step_decisions()
+        self.dec_obs = self.dec_entries = self.dec_n = None  # the decision list, made by the first decisions()
+        self.dec_choices = self.dec_status = None            # int32 [cap], beside it
 
     def _stream(self) -> int:
         return int(self._torch.cuda.current_stream(self.obs.device).cuda_stream)
@@ -102,6 +114,55 @@ class SeatEnv:
         self.batch.observe_seats(self.seats, self.obs, stream=st)
         f = self.fields(self.obs)
         return self.obs, f["done"], f["won"]
+
+    def decisions(self, cap=None, want=("seat", "end")):
+        """The decision list of the batch as it stands (RoomBatch.gather_seats, POLICY.md §3q), on torch's current stream: of the
+        R * S entries of `obs`, those that are due - a listed seat that must act ("seat": legal != 0) or whose game has ended
+        ("end": done) - in ascending entry order.  Returns (dec_obs, dec_entries, dec_n): dec_obs uint8 [cap, 192], the due
+        records; dec_entries int32 [cap], their entry indices r * S + j; dec_n int32 [2], the number of rows filled and the
+        number of due entries (they differ when cap is too small).  All three are allocated on first use, and again when cap
+        changes; cap defaults to R * S, which always holds the whole list.
+        Rows at and beyond dec_n[0] hold stale bytes - earlier lists' records, or zeros - never anything of this list.  A caller
+        that runs its network over all cap rows need not mask them: step_decisions hands dec_n to act_listed, which reads it on
+        the device and ignores every row behind the list.  fields() and random_legal() work on dec_obs as on obs.  teach() has
+        no list form: index the dense `advice` with dec_entries."""
+        torch = self._torch
+        cap = self.actions.numel() if cap is None else int(cap)
+        if self.dec_obs is None or self.dec_obs.shape[0] != cap:
+            dev = self.obs.device
+            self.dec_obs = torch.zeros((cap, SEAT_OBS_BYTES), dtype=torch.uint8, device=dev)
+            self.dec_entries = torch.zeros(cap, dtype=torch.int32, device=dev)
+            self.dec_choices = torch.zeros(cap, dtype=torch.int32, device=dev)
+            self.dec_status = torch.zeros(cap, dtype=torch.int32, device=dev)
+            self.dec_n = torch.zeros(2, dtype=torch.int32, device=dev)
+        self._dec_want = want
+        self.batch.gather_seats(self.seats, self.dec_obs, self.dec_entries, self.dec_n, want, cap=cap, stream=self._stream())
+        return self.dec_obs, self.dec_entries, self.dec_n
+
+    def step_decisions(self, choices, max_turns: int = 16, until=("seat", "end")):
+        """act_listed(choices) with the list the last decisions() / step_decisions() left, batch.run_seats(max_turns, until),
+        gather_seats - all on torch's current stream (POLICY.md §3q): step_until() for a learner that sits in many seats and
+        looks only at those that are due.  choices: [cap] (any integer dtype or device; an int32 tensor on the batch's device is
+        read where it lies), choices[i] for the entry dec_entries[i], 0 = no action; rows at and beyond dec_n[0] are ignored on
+        the device, whatever they hold.  `dec_status` (int32 [cap]) holds each listed entry's verdict afterwards, `played` and
+        `stopped` what step_until() leaves there.  The new list is gathered under the `want` of the last decisions().  Returns
+        (dec_obs, dec_entries, dec_n) as decisions()."""
+        if self.dec_obs is None:
+            raise RuntimeError("SeatEnv.step_decisions: call decisions() first")
+        torch = self._torch
+        if self.played is None:
+            self.played = torch.zeros(self.batch.n_rooms, dtype=torch.int32, device=self.obs.device)
+            self.stopped = torch.zeros(self.batch.n_rooms, dtype=torch.int32, device=self.obs.device)
+        c = choices
+        if not (c.dtype == torch.int32 and c.device == self.obs.device and c.is_contiguous() and c.shape == self.dec_entries.shape):
+            self.dec_choices.copy_(c.reshape(self.dec_entries.shape))
+            c = self.dec_choices
+        st = self._stream()
+        cap = self.dec_entries.shape[0]
+        self.batch.act_listed(self.seats, self.dec_n, self.dec_entries, c, self.dec_status, cap=cap, stream=st)
+        self.batch.run_seats(self.seats, self.played, self.stopped, max_turns, until, stream=st)
+        self.batch.gather_seats(self.seats, self.dec_obs, self.dec_entries, self.dec_n, self._dec_want, cap=cap, stream=st)
+        return self.dec_obs, self.dec_entries, self.dec_n
 
     def teach(self, n_rollouts: int, max_turns: int = 1024, key0: int = 0, full_view: bool = False):
         """The playout advice of every listed seat for the batch as it stands (RoomBatch.teach_seats, POLICY.md §3o), on torch's

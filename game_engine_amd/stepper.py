@@ -709,6 +709,50 @@ class RoomBatch:
         _check(self._lib.ge_batch_run_seats(self._h, first, count, len(seats), seats.ctypes.data if len(seats) else None, max_turns, bits,
                                             ptr, st_ptr, C.c_void_p(stream or None)), "ge_batch_run_seats")
 
+    def gather_seats(self, seats, out, entries, n, want=("seat", "end"), first: int = 0, count: Optional[int] = None, cap: Optional[int] = None,
+                     stream: int = 0):
+        """The decision list of rooms first .. first + count - 1 into DEVICE memory the caller owns (POLICY.md §3q): of the
+        count * len(seats) records observe_seats would store, those that are due - `want` "seat": legal != 0, "end": done != 0;
+        a sequence of the names, one of them, or the GATHER_WANT bit set - in ascending entry order.  `out` (192 bytes per
+        entry) gets the first min(M, cap) due records byte for byte, `entries` (uint32 or int32) their entry indices
+        (r - first) * len(seats) + j, and `n` (two 4-byte words) min(M, cap) and M, the number of due entries.  Nothing beyond
+        the list is written: rows at and behind n[0] keep what they held.  cap None: what `out` and `entries` both hold; cap = 0
+        counts only (out and entries may then be None).  The kinds of object observe_seats takes.  Launched on `stream`,
+        asynchronous, ordered behind the batch's earlier work as step() is; nothing crosses to the host (a call of a larger
+        shape than any before it grows the batch's scratch, which may wait for the device).  The batch is only read."""
+        seats = np.ascontiguousarray(seats, dtype=np.uint32)
+        count = self.n_rooms - first if count is None else count
+        bits = _named_bits(want, _lib.GATHER_WANT, "want: unknown condition")
+        o_ptr, o_bytes = _device_buffer(out) if out is not None else (None, 0)
+        e_ptr, e_bytes = _device_buffer(entries) if entries is not None else (None, 0)
+        n_ptr, n_bytes = _device_buffer(n) if n is not None else (None, 8)
+        cap = min(o_bytes // _lib.SEAT_OBS_BYTES, e_bytes // 4) if cap is None else int(cap)
+        if cap < 0 or o_bytes < cap * _lib.SEAT_OBS_BYTES or e_bytes < 4 * cap or n_bytes < 8:
+            raise GeError(GE_ERR_ARG, "gather_seats: out / entries hold fewer than cap entries, or n fewer than two words")
+        _check(self._lib.ge_batch_gather_seats(self._h, first, count, len(seats), seats.ctypes.data if len(seats) else None, bits, o_ptr, e_ptr,
+                                               cap, n_ptr, C.c_void_p(stream or None)), "ge_batch_gather_seats")
+
+    def act_listed(self, seats, n, entries, choices, status=None, first: int = 0, count: Optional[int] = None, cap: Optional[int] = None,
+                   stream: int = 0):
+        """act_seats from a list in DEVICE memory (POLICY.md §3q): with D the dense count * len(seats) choices that are 0 except
+        D[entries[i]] = choices[i] for i < min(n[0], cap) - n[0] read on the device -, the call is act_seats(seats, D), and
+        status[i] (int32, optional) that call's verdict at entries[i].  `n`, `entries`, `choices` as gather_seats left them or in
+        any order (choices int32); an entry at or above count * len(seats) gets GE_ERR_ARG and touches nothing; status behind the
+        list is not written; of an entry named twice one choice is applied and every copy reports its verdict.  cap None: what
+        entries, choices and status all hold.  Launched on `stream`, asynchronous, ordered as step() is."""
+        seats = np.ascontiguousarray(seats, dtype=np.uint32)
+        count = self.n_rooms - first if count is None else count
+        n_ptr, n_bytes = _device_buffer(n) if n is not None else (None, 4)
+        e_ptr, e_bytes = _device_buffer(entries) if entries is not None else (None, 0)
+        c_ptr, c_bytes = _device_buffer(choices) if choices is not None else (None, 0)
+        s_ptr, s_bytes = _device_buffer(status) if status is not None else (None, None)
+        holds = min(e_bytes, c_bytes, c_bytes if s_bytes is None else s_bytes) // 4
+        cap = holds if cap is None else int(cap)
+        if cap < 0 or cap > holds or n_bytes < 4:
+            raise GeError(GE_ERR_ARG, "act_listed: entries / choices / status hold fewer than cap 4-byte entries, or n no word")
+        _check(self._lib.ge_batch_act_listed(self._h, first, count, len(seats), seats.ctypes.data if len(seats) else None, n_ptr, cap, e_ptr,
+                                             c_ptr, s_ptr, C.c_void_p(stream or None)), "ge_batch_act_listed")
+
     def teach_seats(self, seats, out, n_rollouts: int, max_turns: int = 1024, *, first: int = 0, count: Optional[int] = None, keys=None,
                     key0: int = 0, turn: Optional[int] = None, seed: Optional[int] = None, full_view: bool = False, stream: int = 0):
         """advise_seats for each listed seat (1-based, pairwise distinct) of rooms first .. first + count - 1, into DEVICE memory the

@@ -55,7 +55,8 @@ extern "C" {
  *      ge_batch_advise_seats + ge_advice + GE_ADVISE_FULL_VIEW (listed seats advised on the device: their legal choices found, played and ranked);
  *      ge_batch_observe_seats + ge_batch_act_seats + ge_seat_obs (a seat of every room observed into, and played from, device memory the caller owns);
  *      ge_batch_teach_seats (ge_batch_advise_seats for a seat list of every room of a range, into device memory the caller owns);
- *      ge_batch_run_seats + GE_RUN_UNTIL_SEAT (every room of a range played on until a listed seat must act, turn counts and stop bits in device memory) */
+ *      ge_batch_run_seats + GE_RUN_UNTIL_SEAT (every room of a range played on until a listed seat must act, turn counts and stop bits in device memory);
+ *      ge_batch_gather_seats + ge_batch_act_listed + GE_GATHER_* (decision lists: the due (room, seat) entries of a range compacted in order with their observations, and played from such a list) */
 #define GE_ABI_VERSION 5
 #define GE_MAX_PHASES 32
 #define GE_MAX_PLAYERS 12
@@ -854,6 +855,87 @@ int ge_batch_run_seats(ge_batch *b, uint64_t first, uint64_t count, uint32_t n_s
                        const uint32_t *seats /* host, 1-based, may be NULL with n_seats == 0 */, uint32_t max_turns, uint32_t until,
                        uint32_t *played_dev /* DEVICE: count */, uint32_t *stopped_dev /* DEVICE: count, may be NULL */,
                        void *hip_stream);
+
+/* Decision lists: observe and play only the seats that must act (POLICY.md §3q).  Where the learner sits in every seat - self-play,
+ * multi-agent training - the dense [rooms, listed seats] grid of the calls above is mostly entries that are no decision point:
+ * at night only a few seats may act, dead seats never act.  These two calls work on a compact list of entries in device memory
+ * instead; an entry index is ge_batch_observe_seats's, e = (r - first) * n_seats + j.  Both are compositions of the calls above.
+ *   ge_batch_gather_seats  Let O be what ge_batch_observe_seats(first, count, seats) would store.  Entry e is due when
+ *                          (want & GE_GATHER_SEAT and O[e].legal != 0) or (want & GE_GATHER_END and O[e].done != 0).  With
+ *                          e_0 < e_1 < ... < e_(M-1) the due entries in ascending order: for i < min(M, cap), obs_dev[i] = O[e_i]
+ *                          byte for byte and entries_dev[i] = e_i; n_dev[0] = min(M, cap), n_dev[1] = M.  Nothing at or beyond
+ *                          index n_dev[0] of obs_dev / entries_dev is written.  cap = 0 counts only (obs_dev and entries_dev may
+ *                          then be NULL).  The batch is only read; neither the human mask nor the seat plane plays a part.  A
+ *                          finished room under GE_GATHER_END emits every listed seat, each with its own `won`.
+ *   ge_batch_act_listed    Let n = min(*n_dev, cap), read on the device, and D the dense array of count * n_seats choices that is 0
+ *                          except D[entries_dev[i]] = choices_dev[i] for i < n with entries_dev[i] < count * n_seats.  The call is
+ *                          ge_batch_act_seats(first, count, seats, D), and status_dev[i] (may be NULL) that call's status at
+ *                          entries_dev[i]; an entry at or above count * n_seats gets GE_ERR_ARG and touches nothing;
+ *                          status_dev[i] for i >= n is not written.  The list may be in any order - a room's actions are applied in
+ *                          ascending seat-list position, as ge_batch_act_seats applies them.  Of an entry named twice one choice
+ *                          is applied, which one is unspecified, and every copy reports the applied one's status.  Whatever the
+ *                          list holds, a record is written by one lane only, and nothing is written but records of the range
+ *                          and status_dev[0 .. n).
+ * ge_batch_teach_seats over a list is not offered: a caller indexes the dense advice with entries_dev.
+ * The stream contract is ge_batch_observe_seats's: every launch and memset goes on hip_stream, behind the batch's earlier work;
+ * later calls on the batch are ordered behind it; no byte crosses to the host and the host waits for nothing - with the exception
+ * of ge_batch_teach_seats: a call of a larger shape than any before grows the batch's scratch, and hipFree / hipMalloc may wait
+ * for the device.  With ge_batch_set_timing on, each call is one interval of ge_batch_kernel_time.
+ * All checks run before anything is launched, and a failure leaves the outputs untouched.  ge_batch_gather_seats, in this order:
+ * GE_ERR_ARG for b NULL; for want 0 or with bits above 3; for n_dev NULL; for obs_dev or entries_dev NULL with cap > 0 and
+ * count * n_seats > 0; then ge_batch_observe_seats's checks in their order - GE_ERR_ARG for seats NULL with count * n_seats > 0,
+ * for n_seats > 12, for a repeated seat; GE_ERR_RANGE for a range beyond the batch; GE_ERR_ARG for a seat of 0 or above the
+ * n_players of a segment the range touches; for obs_dev (cap x 192 bytes) or entries_dev (cap x 4 bytes), with cap > 0 and
+ * count * n_seats > 0, or n_dev (8 bytes) that the batch's device does not reach, vetted as ge_batch_observe_seats vets obs_dev -;
+ * GE_ERR_ARG for count * n_seats >= 2^32.  An empty range or an empty seat list is not an error and is not silent either: GE_OK,
+ * and n_dev = {0, 0} is stored on hip_stream (so n_dev is vetted even then).  ge_batch_act_listed: ge_batch_act_seats's checks in
+ * their order with n_dev beside seats - GE_ERR_ARG for b NULL; for seats or n_dev NULL, or entries_dev or choices_dev NULL with
+ * cap > 0, where count * n_seats > 0; for n_seats > 12; for a repeated seat; GE_ERR_RANGE for a range beyond the batch; GE_ERR_ARG
+ * for a seat of 0 or above the n_players of a segment the range touches; for count * n_seats >= 2^32; then count * n_seats == 0:
+ * GE_OK; GE_ERR_ARG for n_dev (4 bytes), entries_dev, choices_dev or a non-NULL status_dev (cap x 4 bytes each) that the batch's
+ * device does not reach; then cap == 0: GE_OK, nothing launched.
+ * On the device, ge_batch_gather_seats has ge_batch_find_rooms's shape - no block waits for another: no flag to spin on, no
+ * look-back, no cooperative launch.  Test launches (one per segment of the range, lane = room): the due seats of the room as one
+ * word - GE_GATHER_SEAT is GE_RUN_UNTIL_SEAT's test, the pending targets among the listed seats, far cheaper than `legal`'s
+ * n_players injections per seat - and one due-entry count per wavefront.  One scan launch (ge_batch_find_rooms's scan block) turns
+ * the counts into offsets and stores n_dev.  Emit launches (one per segment, lane = room): a wavefront without a due entry or
+ * wholly beyond cap leaves before it loads a record; a listed seat none of the wavefront's rooms has due is skipped; a due entry's
+ * record is built by ge_batch_observe_seats's own code and stored at the wavefront's offset + the due entries of the wavefront's
+ * earlier rooms + the seat's rank among the room's due seats.  So the list's order is entry order whatever order the blocks ran in,
+ * and a record is three whole 64-byte lines at any list position.  ge_batch_act_listed: a zeroed dense choice plane and a dense
+ * status plane in the batch's scratch, a scatter (lane = list position), ge_batch_act_seats's kernel unchanged, a status gather.
+ * Measured on an MI355X (tools/decisions_probe.py, profiles/decisions_probe.txt: Werewolf x 8, all eight seats listed and
+ * host-driven, restart on, 40 turns stepped first, the seats played by a uniform legal choice computed in torch on the device,
+ * max_turns = 16; medians of 15; decision points counted outside the timed windows).  (a) A decision point delivered - a list row,
+ * an entry with legal != 0 or done - through act_listed, run_seats, gather_seats and the choice over all cap rows costs 1.38 ns of
+ * wall time at 65 536 rooms and 0.86 ns at 1 048 576 (0.26 ms and 2.61 ms per call), against 1.28 ns and 0.89 ns through the dense
+ * way on the same build - act_seats, run_seats, observe_seats over eight seats, the choice over [rooms, 8] (0.24 ms and 2.72 ms per
+ * call): at 65 536 rooms the list loop is the slower one, x 0.93, at 1 048 576 the list loop is the faster one, x 1.04; the dense
+ * way timed against itself x 1.03 and x 1.00.  The list does not pay here: of a call, the library's kernels are 91.4 us and 520.5
+ * us in the list loop and 74.7 us and 626.2 us in the dense loop (kernel trace), and the rest is the choice over rooms x 8 rows in
+ * either loop, which the list does not shorten because its length stays on the device.  (b) The call alone, gather_seats against
+ * observe_seats on the same records, launch interval: 59.6 us (+- 9.9) against 54.2 us at 65 536 rooms - the list call is the
+ * slower one there, x 0.91 - and 344.0 us (+- 73.5) against 491.2 us at 1 048 576 (x 1.43); 35.5 % and 35.6 % of the entries were
+ * due; 41 MB against 103 MB and 661 MB against 1644 MB moved; of the call, by kernel trace, the test launch 4.2 and 10.1 us, the
+ * scan 2.2 and 16.6 us, the emit launch 50.3 and 302.2 us: per record the emit costs 1.8 times what the dense kernel does at 1 048
+ * 576 rooms, because a wavefront works through every seat that any of its rooms has due while the lanes of its other rooms idle.
+ * (c) The emit launch with each lane storing its own record 49.1 and 297.3 us, with a wavefront's records staged through LDS 51.6
+ * and 369.9 us (profiles/decisions_probe_stores.txt, measured once on a build that held both) - the opposite of
+ * ge_batch_observe_seats, whose staged records leave as consecutive kilobytes while a list's destinations are scattered; the staged
+ * layout was deleted.  (d) The loop at the one-seat shape of ge_batch_run_seats's measurement (human_mask = 1, seat 1 listed, 85 %
+ * of the entries due): 3.02 ns against 2.59 ns per point at 65 536 rooms - the list loop is the slower one, x 0.86 -, 0.75 ns
+ * against 0.69 ns at 1 048 576 - the list loop is the slower one, x 0.92: where almost every entry is due the list is extra work.
+ * No other shape has been measured. */
+#define GE_GATHER_SEAT 1u   /* the entry's ge_seat_obs.legal != 0 */
+#define GE_GATHER_END  2u   /* the entry's ge_seat_obs.done  != 0 */
+int ge_batch_gather_seats(ge_batch *b, uint64_t first, uint64_t count, uint32_t n_seats,
+                          const uint32_t *seats /* host, 1-based */, uint32_t want,
+                          ge_seat_obs *obs_dev /* DEVICE: cap */, uint32_t *entries_dev /* DEVICE: cap */,
+                          uint64_t cap /* entries */, uint32_t *n_dev /* DEVICE: 2 words */, void *hip_stream);
+int ge_batch_act_listed(ge_batch *b, uint64_t first, uint64_t count, uint32_t n_seats, const uint32_t *seats /* host */,
+                        const uint32_t *n_dev /* DEVICE: 1 word */, uint64_t cap,
+                        const uint32_t *entries_dev /* DEVICE: cap */, const int32_t *choices_dev /* DEVICE: cap */,
+                        int32_t *status_dev /* DEVICE: cap, may be NULL */, void *hip_stream);
 
 /* GE_FLAG_TRACE: events of the most recent ge_batch_step call, dst[(room - first) * *n_turns + t].
  * cap_bytes >= count * n_turns * sizeof(ge_turn_event).  Synchronises. */

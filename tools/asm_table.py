@@ -48,6 +48,12 @@ def describe(mangled: str) -> dict:
     m = re.search(r"ge_seat_run_kernelILi(\d)ELi(\d)E", mangled)
     if m:
         return {"kernel": "ge_seat_run_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True}
+    m = re.search(r"ge_gather_testILi(\d)ELi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_gather_test", "layout": KINDS[int(m.group(1))], "lowocc": False, "generic": int(m.group(2)), "single": True}
+    m = re.search(r"ge_gather_emitILi(\d)E", mangled)
+    if m:
+        return {"kernel": "ge_gather_emit", "layout": KINDS[int(m.group(1))], "lowocc": False, "generic": False, "single": True}
     m = re.search(r"ge_rollout_kernelILi(\d)ELi(\d)E(?:Li(\d)E)?", mangled)
     if m:
         return {"kernel": "ge_rollout_kernel", "layout": KINDS[int(m.group(1))], "lowocc": True, "generic": int(m.group(2)), "single": True,
@@ -121,6 +127,15 @@ def label(r):
         return f"{r['layout']}, whole-batch step under per-room seats (ge_batch_step after ge_batch_set_seats)" + (", GENERIC" if r["generic"] else "")
     if r["kernel"] == "ge_seat_run_kernel":                      # ge_batch_run_seats: one launch per segment of the range
         return f"{r['layout']}, seat run-on (ge_batch_run_seats)" + (", GENERIC" if r["generic"] else "")
+    if r["kernel"] == "ge_gather_test":                          # ge_batch_gather_seats: one launch per segment of the range
+        return f"{r['layout']}, due seats of a range of rooms (ge_batch_gather_seats)" + (", GENERIC" if r["generic"] else "")
+    if r["kernel"] == "ge_gather_emit":                          # ge_batch_gather_seats: one launch per segment of the range, behind the scan
+        return f"{r['layout']}, the ordered store of the due seats' observations (ge_batch_gather_seats)"
+    if r["kernel"] == "ge_gather_scan":                          # ge_batch_gather_seats: between the test and the emit launches
+        return "ge_gather_scan (ge_batch_gather_seats: the scan of the wavefront counts, and the list's two counts)"
+    if r["kernel"] in ("ge_list_scatter", "ge_list_status"):     # ge_batch_act_listed: around ge_act_kernel
+        what = {"ge_list_scatter": "the listed choices into the dense plane", "ge_list_status": "the listed entries' statuses from the dense plane"}[r["kernel"]]
+        return f"{r['kernel']} (ge_batch_act_listed: {what})"
     if r["kernel"] in ("ge_seats_fill", "ge_seats_scatter"):     # ge_batch_set_seats
         what = {"ge_seats_fill": "a segment's mask for its rooms", "ge_seats_scatter": "the listed rooms' masks"}[r["kernel"]]
         return f"{r['kernel']} (ge_batch_set_seats: {what})"
